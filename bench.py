@@ -10,11 +10,17 @@ hot path over the batch:
 followed by the fetch of the per-utterance statistics (a few KB) and, for N > 1, the single all-gather of those
 statistics (RCCL).  `--workload c2` (configs[1]) leaves the Whisper leg out.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 prints ONE JSON line (rank 0).  `value` = audio seconds processed by all ranks / wall time.  With --gpus N > 1 and no
 WORLD_SIZE in the environment this process starts the N ranks itself (it never touches the GPU: the ranks are fresh
 child processes); under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the ranks.
 `--gpus 8 --clips 1250` is configs[3] (C4: 10 000 clips over 8 GPUs).
+
+A plain run sets up, warms up, times the K steps and prints the line (per-kernel figures, stages and the roofline come
+from the event pairs inside those K steps).  `--full` adds the measurements that take runs of their own: the CPU
+baseline, the streamed, transcribe, Whisper-medium and framing_hbm passes (each left `null` in a plain line; an
+explicit --cpu-clips / --streamed-steps / --transcribe-steps / --medium-steps / --framing-clips value wins either way).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64 / float32, at most 64 MB).
 """
 import argparse
 import json
@@ -161,6 +167,51 @@ def cpu_whisper_baseline(clips, rate, model, W_enc, W_dec, dims, tdims, align_to
 
 
 # --------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step handed back, for comparing two builds output for output
+# --------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_PATHS_BYTES = 32 << 20     # DTW paths: every clip up to this size, then a fixed sample of clips
+DUMP_STFT_BYTES = 16 << 20      # STFT-dB matrices (1.3 MB per 10 s clip): a fixed sample of clips
+
+
+def _sample(n, per_item_bytes, budget, seed):
+    """Sorted indices of at most budget // per_item_bytes of n items (all of them if they fit), the same for the same n."""
+    k = max(1, min(n, budget // max(per_item_bytes, 1)))
+    return np.arange(n) if k == n else np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, rec, last, pe):
+    """DIR/<name>.npy of the last timed step: the gathered records, this rank's energy / LUFS / pitch summaries and DTW paths (rows past a
+    clip's path length are -1), and the STFT-dB matrices of a fixed sample of this rank's clips (fetched after the timed region)."""
+    out = {"records": np.asarray(rec, dtype=np.float64)}
+    st = last["stats"]
+    for f in ("n", "sum_sq", "sum_sq_wrap16", "n_loud", "peak_abs"):
+        out[f"energy_{f}"] = st["energy"][f].astype(np.float64)
+    out["lufs"] = st["lufs"][0].astype(np.float64)
+    out["lufs_status"] = st["lufs"][1].astype(np.float64)
+    for f in ("n_frames", "n_voiced", "median_f0", "mean_log_f0", "t1", "status"):
+        out[f"pitch_{f}"] = st["pitch"][f].astype(np.float64)
+    if "paths" in last:
+        pl, ti, tj = last["paths"]
+        rows = _sample(len(pl), 2 * 4 * ti.shape[1], DUMP_PATHS_BYTES, 1)
+        past = np.arange(ti.shape[1])[None, :] >= pl[rows, None]
+        out["align_path_len"] = pl.astype(np.float64)
+        out["align_clips"] = rows.astype(np.float64)
+        out["align_text_idx"] = np.where(past, -1, ti[rows]).astype(np.float32)
+        out["align_time_idx"] = np.where(past, -1, tj[rows]).astype(np.float32)
+    first = pe.stft_db_fetch(0)                                     # (its size sets how many clips the sample holds)
+    clips = _sample(len(out["lufs"]), first.nbytes, DUMP_STFT_BYTES, 2)
+    out["stft_db_clips"] = clips.astype(np.float64)
+    out["stft_db"] = np.stack([first if i == 0 else pe.stft_db_fetch(int(i)) for i in clips]).astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+# --------------------------------------------------------------------------------------------------------------
 # launcher: --gpus N without a rendezvous in the environment
 # --------------------------------------------------------------------------------------------------------------
 def spawn_ranks(n, argv):
@@ -202,23 +253,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=None, help="untimed steps (default 2 for c3, 3 for c2)")
     ap.add_argument("--clips", type=int, default=256, help="clips per GPU")
     ap.add_argument("--seconds", type=float, default=10.0)
-    ap.add_argument("--cpu-clips", type=int, default=256, help="clips timed on the CPU oracle's prosody leg (0 = no cpu_baseline)")
+    ap.add_argument("--full", action="store_true", help="also run the extra measurements below (their defaults without --full: 0 = skip)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step computed to DIR/<name>.npy "
+                    "(float64 / float32, a fixed sample of the larger arrays, at most 64 MB)")
+    ap.add_argument("--cpu-clips", type=int, default=None, help="clips timed on the CPU oracle's prosody leg (default 256 with --full; 0 = no cpu_baseline)")
     ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
     ap.add_argument("--whisper-model", choices=["tiny", "base", "small", "medium"], default="small",
                     help="architecture of the c3 workload (BASELINE.json names small; the reference's config.yaml:15 default is medium)")
     ap.add_argument("--workload", choices=["c2", "c3"], default="c3",
                     help="c3 (default, BASELINE.json configs[2]): prosody + log-mel + Whisper encoder + forced alignment; "
                          "c2 (configs[1]): F0 + energy + LUFS + STFT only")
-    ap.add_argument("--streamed-steps", type=int, default=4, help="extra steps with the batch uploaded from pinned host memory "
-                    "(double buffered) for `streamed_value`; 0 = skip")
-    ap.add_argument("--transcribe-steps", type=int, default=32, help="c3: free-running decoding steps per window of the extra `transcribe` "
-                    "measurement (log-mel + encoder + device-resident decoding loop + forced alignment; never `value`); 0 = skip")
-    ap.add_argument("--medium-steps", type=int, default=2, help="c3 with --whisper-model small on one GPU: extra steps with Whisper-medium dims (the "
-                    "reference's default model) for the `medium` object; 0 = skip")
+    ap.add_argument("--streamed-steps", type=int, default=None, help="extra steps with the batch uploaded from pinned host memory "
+                    "(double buffered) for `streamed_value` (default 4 with --full); 0 = skip")
+    ap.add_argument("--transcribe-steps", type=int, default=None, help="c3: free-running decoding steps per window of the extra `transcribe` "
+                    "measurement (log-mel + encoder + device-resident decoding loop + forced alignment; never `value`; default 32 with --full); 0 = skip")
+    ap.add_argument("--medium-steps", type=int, default=None, help="c3 with --whisper-model small on one GPU: extra steps with Whisper-medium dims (the "
+                    "reference's default model) for the `medium` object (default 2 with --full); 0 = skip")
     ap.add_argument("--prosody-context", type=int, default=0, help="c3: 1 = the prosody leg (energy, LUFS, F0, STFT-dB) runs in a SECOND engine context (its own "
                     "HIP streams) on the same resident PCM, beside the Whisper leg instead of behind it")
-    ap.add_argument("--framing-clips", type=int, default=1250, help="clips of the extra `framing_hbm` measurement (k_energy / k_frame_energy beyond the Infinity "
-                    "Cache: the per-GPU shard of BASELINE config 4); 0 = skip")
+    ap.add_argument("--framing-clips", type=int, default=None, help="clips of the extra `framing_hbm` measurement (k_energy / k_frame_energy beyond the Infinity "
+                    "Cache: the per-GPU shard of BASELINE config 4; default 1250 with --full); 0 = skip")
     ap.add_argument("--dump-records", default=None, help="rank 0 writes the gathered per-utterance records of the last timed step to this .npy file")
     ap.add_argument("--first-clip", type=int, default=0, help="seed offset of the first synthetic clip (rank r owns first + [r*clips, (r+1)*clips))")
     ap.add_argument("--selftest-launcher", action="store_true",
@@ -228,6 +282,11 @@ def main():
         args.steps = 6 if args.workload == "c3" else 20
     if args.warmup is None:
         args.warmup = 2 if args.workload == "c3" else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    for name, full_default in (("cpu_clips", 256), ("streamed_steps", 4), ("transcribe_steps", 32), ("medium_steps", 2), ("framing_clips", 1250)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -346,13 +405,16 @@ def run_rank(args, world, rank, local_rank):
         pe.stats_enqueue(slot)
 
     path_steps = []                                                # DTW path steps that reached the host per step (c3)
+    last = {}                                                      # what the latest finished step handed back (--dump-outputs)
 
     def finish(slot):
         if wdims:
-            pl, _, _ = eng.whisper_align_paths_wait(slot)           # what a pipeline writes TextGrids from: the alignment leaves the device inside the step
+            pl, ti, tj = eng.whisper_align_paths_wait(slot)         # what a pipeline writes TextGrids from: the alignment leaves the device inside the step
             path_steps.append(int(pl.sum()))
+            last["paths"] = (pl, ti, tj)
         r = pe.stats_wait(slot)
         en, lu, pi = r["energy"], r["lufs"][0], r["pitch"]
+        last["stats"] = r
         # per-utterance record: [median F0, LUFS, rms, peak, silence ratio, duration, n_voiced]
         rec = np.stack([pi["median_f0"], lu, np.sqrt(en["sum_sq"] / np.maximum(en["n"], 1)), en["peak_abs"].astype(np.float64),
                         1.0 - en["n_loud"] / np.maximum(en["n"], 1), en["n"] / float(rate), pi["n_voiced"].astype(np.float64)], axis=1)
@@ -413,6 +475,8 @@ def run_rank(args, world, rank, local_rank):
     assert rec.shape == (args.clips * world, 7)
     if args.dump_records and rank == 0:
         np.save(args.dump_records, rec)                              # the gathered per-utterance records of the last timed step (tests compare world 2 with world 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec, last, pe)
 
     # H2D-inclusive rate: the batch arrives from pinned host memory every step, double buffered (the copy of batch i+1
     # runs on a copy stream beside the kernels of batch i; the engine adopts the device buffer without a copy).

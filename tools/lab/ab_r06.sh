@@ -2,7 +2,7 @@
 # Same-box A/B of libpce builds (tools/lab/bin/libpce_<tag>.so; "product" = the tree's own library) over the C3 bench line: step, log-mel, STFT,
 # the free-running decoding step and the alignment.  usage: tools/lab/ab_r06.sh tagA tagB ...   (each twice, interleaved)
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; mkdir -p gpurun_out/ab6
-ARGS=${AB_BENCH_ARGS:---cpu-clips 0 --streamed-steps 0 --medium-steps 0 --framing-clips 0 --steps 4}
+ARGS=${AB_BENCH_ARGS:---full --cpu-clips 0 --streamed-steps 0 --medium-steps 0 --framing-clips 0 --steps 4}
 for round in 1 2; do for tag in "$@"; do
   lib=$PWD/tools/lab/bin/libpce_$tag.so; [ "$tag" = product ] && lib=$PWD/prosody-control-french-tts_amd/libpce.so
   [ -f $lib ] || { echo "no $lib"; exit 1; }

@@ -6,8 +6,8 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/${1:-r05}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $OUT/bench_c3.json 2> $OUT/bench_c3.err
-python3 $R/bench.py --workload c2 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+python3 $R/bench.py --full > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+python3 $R/bench.py --full --workload c2 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
 C3="--steps 3 --warmup 1 --cpu-clips 0 --streamed-steps 0 --transcribe-steps 0 --medium-steps 0 --framing-clips 0"
 C2="--workload c2 --steps 5 --warmup 2 --cpu-clips 0 --streamed-steps 0 --framing-clips 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c3 -- python3 $R/bench.py $C3 > $OUT/stats_c3.log 2>&1
