@@ -1401,14 +1401,19 @@ struct SelfAttn1Args {
     op_t *ck, *cv; int64_t c_clip; int d;     // caches: row t of clip c at + c * c_clip + t * d
     const int *pos, *skip;                    // position of the new token (= cached keys) per clip; skip may be null
     op_t *out; int64_t out_ld;
+    int heads;
 };
+// More than 16 heads (large-v3 / turbo: 20): the heads are cut into groups of at most 16 waves, one workgroup per (clip, group) -- grid (clips, groups),
+// wave w of group y is head y * (waves per group) + w; each wave appends its own head's columns.  Up to 16 heads: one group, the launch of round 5.
 __global__ __launch_bounds__(1024) void k_self_attn1w(SelfAttn1Args A)
 {
-    extern __shared__ float sa_sp[];                              // [heads][512]
+    extern __shared__ float sa_sp[];                              // [waves of the group][512]
     const int clip = blockIdx.x;
     if (A.skip && A.skip[clip]) return;
-    const int lane = threadIdx.x & 63, head = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float *sp = sa_sp + head * 512;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int head = (int)blockIdx.y * (int)(blockDim.x >> 6) + wv;
+    if (head >= A.heads) return;                                  // (a short last group; no barrier in this kernel)
+    float *sp = sa_sp + wv * 512;
     const int Sc = A.pos[clip];                                   // cached keys 0 .. Sc - 1; the new one is key Sc
     const int g = lane >> 3, ch = lane & 7;
     const op_t *nq = A.qkv + (int64_t)clip * A.qkv_ld + head * 64;
@@ -1548,6 +1553,7 @@ struct Attn1Args {
     // k_cross_attn1w only: when app_pos is set, the wave of (clip, head) first writes the new position's key / value slice (app_k / app_v
     // + c * app_ld + head * 64) into K row app_pos[c] and V^T column app_pos[c] (k_append_kv's job, without its launch), then attends
     const op_t *app_k, *app_v; int64_t app_ld; const int *app_pos;
+    int heads;                                // k_cross_attn1w: heads in all (the grid's y counts head groups)
 };
 // 128 threads: 16 workgroups fit a CU, so the 3 072 (clip, head) pairs of 256 clips at Whisper-small size are ONE resident round
 // (with 256 threads 2 048 run at a time and the second round leaves half the chip idle)
@@ -1645,13 +1651,16 @@ __global__ __launch_bounds__(A1_T) void k_cross_attn1(Attn1Args A)
 // 128-byte slices of all heads side by side (1 536 B at Whisper-small size); with a workgroup per (clip, head) the twelve slices of a row
 // are fetched by twelve workgroups on different XCDs at different times -- twelve visits to the same DRAM page; here the waves of a
 // workgroup walk the rows together.  Each wave keeps its scores in its own LDS slice: no workgroup barrier anywhere.
+// More than 16 heads: groups of at most 16 waves, grid (clips, groups), as k_self_attn1w.
 __global__ __launch_bounds__(1024) void k_cross_attn1w(Attn1Args A)
 {
-    extern __shared__ float spw[];                               // [heads][1536 + 64]
+    extern __shared__ float spw[];                               // [waves of the group][1536 + 64]
     const int clip = blockIdx.x;
     if (A.skip && A.skip[clip]) return;
-    const int lane = threadIdx.x & 63, head = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    float *sp = spw + head * 1600;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int head = (int)blockIdx.y * (int)(blockDim.x >> 6) + wv;
+    if (head >= A.heads) return;                                  // (a short last group)
+    float *sp = spw + wv * 1600;
     const int Sk = A.k_len[clip];
     const int g = lane >> 3, ch = lane & 7;
     // Appending (the self-attention of an incremental step): the new position's key and value go to the cache with plain stores that
@@ -2790,7 +2799,7 @@ int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const 
                        int32_t workgroups_per_clip, uint16_t *out)
 {
     if (!c || !resid || !ln_w || !ln_b || !wq || !bq || !wk || !wv || !bv || !E || !k_len || !out || n <= 0 || k_cap <= 0) return PCE_E_INVALID;
-    if (!(d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024) || heads * 64 != d || heads > 16)
+    if (!(d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024 || d == 1280) || heads * 64 != d || heads > 32)
         return pce_fail(c, PCE_E_INVALID, "selftest xattn: d = %d with %d heads is not a width the encoder-output form is built for", d, heads);
     if (!(workgroups_per_clip == 0 || workgroups_per_clip == 1 || workgroups_per_clip == 2 || workgroups_per_clip == 4)) return PCE_E_INVALID;
     for (int i = 0; i < n; i++) if (k_len[i] <= 0 || k_len[i] > k_cap) return pce_fail(c, PCE_E_INVALID, "selftest xattn: clip %d has %d frames of %d", i, k_len[i], k_cap);
@@ -2800,8 +2809,9 @@ int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const 
     PCE_HIP(c, dres.reserve(sizeof(float) * (size_t)n * d)); PCE_HIP(c, dlw.reserve(sizeof(float) * d)); PCE_HIP(c, dlb.reserve(sizeof(float) * d));
     PCE_HIP(c, dwq.reserve(2 * dd)); PCE_HIP(c, dbq.reserve(sizeof(float) * d)); PCE_HIP(c, dwk.reserve(2 * dd)); PCE_HIP(c, dwkT.reserve(2 * dd));
     PCE_HIP(c, dwv.reserve(2 * dd)); PCE_HIP(c, dbv.reserve(sizeof(float) * d)); PCE_HIP(c, dE.reserve(2 * ne + 4096)); PCE_HIP(c, dkl.reserve(sizeof(int) * (size_t)n));
-    PCE_HIP(c, dqp.reserve(2 * 2 * (size_t)n * 16 * d + 256)); PCE_HIP(c, dup.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * 16 * d + 256));
-    PCE_HIP(c, dml.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * 16 * 2 + 256)); PCE_HIP(c, dout.reserve(2 * (size_t)n * d + 64));
+    const size_t R = (size_t)xa_rows(heads);
+    PCE_HIP(c, dqp.reserve(2 * 2 * (size_t)n * R * d + 256)); PCE_HIP(c, dup.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
+    PCE_HIP(c, dml.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * 2 + 256)); PCE_HIP(c, dout.reserve(2 * (size_t)n * d + 64));
     struct Up { void *dst; const void *src; size_t bytes; } ups[] = {
         {dres.p, resid, sizeof(float) * (size_t)n * d}, {dlw.p, ln_w, sizeof(float) * d}, {dlb.p, ln_b, sizeof(float) * d}, {dwq.p, wq, 2 * dd}, {dbq.p, bq, sizeof(float) * d},
         {dwk.p, wk, 2 * dd}, {dwv.p, wv, 2 * dd}, {dbv.p, bv, sizeof(float) * d}, {dE.p, E, 2 * ne}, {dkl.p, k_len, sizeof(int) * (size_t)n}};
@@ -2811,28 +2821,29 @@ int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const 
     int nsplit = workgroups_per_clip ? workgroups_per_clip : n >= 512 ? 1 : n >= 256 ? 2 : 4;
     if (nsplit > XA_LEAVES) nsplit = XA_LEAVES;
     const bool pairs = nsplit <= XA_LEAVES / 2 && d <= 768;
-    op_t *qp_hi = dqp.as<op_t>(), *qp_lo = qp_hi + (size_t)n * 16 * d;
+    op_t *qp_hi = dqp.as<op_t>(), *qp_lo = qp_hi + (size_t)n * R * d;
     XaArgs a{};
     a.E = dE.as<op_t>(); a.e_clip = (int64_t)k_cap * d; a.e_ld = d; a.qp_hi = qp_hi; a.qp_lo = qp_lo; a.k_len = dkl.as<int>(); a.skip = nullptr;
-    a.u_part = dup.as<float>(); a.ml_part = dml.as<float>(); a.heads = heads; a.nsplit = nsplit;
+    a.u_part = dup.as<float>(); a.ml_part = dml.as<float>(); a.heads = heads; a.nsplit = nsplit; a.rows = (int)R;
     auto xq = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((unsigned)heads, (unsigned)div_up(n, 16)), dim3(256), 0, c->stream, dres.as<float>(), dlw.as<float>(), dlb.as<float>(), dwq.as<op_t>(),
-                           dbq.as<float>(), dwkT.as<op_t>(), (int)n, 0.125f * 1.4426950408889634f, (const int *)nullptr, qp_hi, qp_lo);
+                           dbq.as<float>(), dwkT.as<op_t>(), (int)n, 0.125f * 1.4426950408889634f, (const int *)nullptr, qp_hi, qp_lo, (int)R);
     };
     auto go = [&](auto kern, int nslot) {
-        const size_t lds = (size_t)nslot * XA_TF * d * 2 + 4096;
+        const size_t lds = xa_lds(d, nslot);
         (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)(n * nsplit)), dim3(256), lds, c->stream, a);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(n * nsplit)), dim3(64 * (unsigned)xa_waves(d)), lds, c->stream, a);
     };
     auto uv = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3((unsigned)heads, (unsigned)div_up(n, 16)), dim3(256), 0, c->stream, dup.as<float>(), dml.as<float>(), dwv.as<op_t>(), dbv.as<float>(),
-                           (int)n, (const int *)nullptr, dout.as<op_t>(), (int64_t)d);
+                           (int)n, (const int *)nullptr, dout.as<op_t>(), (int64_t)d, (int)R);
     };
 #define PCE_XA_ST(D_, NS_) do { xq(k_xq_fused<D_>); if (pairs) { go(k_xattn_absorbed<D_, NS_, true>, NS_); uv(k_uv_absorb<D_, true>); } \
                                 else { go(k_xattn_absorbed<D_, NS_, false>, NS_); uv(k_uv_absorb<D_, false>); } } while (0)
     if (d == 128) PCE_XA_ST(128, 3); else if (d == 256) PCE_XA_ST(256, 3); else if (d == 384) PCE_XA_ST(384, 3); else if (d == 512) PCE_XA_ST(512, 2);
     else if (d == 768) PCE_XA_ST(768, 2);
-    else { xq(k_xq_fused<1024>); go(k_xattn_absorbed<1024, 2, false>, 2); uv(k_uv_absorb<1024, false>); }
+    else if (d == 1024) { xq(k_xq_fused<1024>); go(k_xattn_absorbed<1024, 2, false>, 2); uv(k_uv_absorb<1024, false>); }
+    else { xq(k_xq_fused<1280>); go(k_xattn_absorbed<1280, 3, false, 8, 2>, 3); uv(k_uv_absorb<1280, false>); }
 #undef PCE_XA_ST
     PCE_HIP(c, hipGetLastError());
     PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)n * d, hipMemcpyDeviceToHost, c->stream));
@@ -3283,8 +3294,10 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
     hipLaunchKernelGGL(k_embed_one, dim3((unsigned)div_up((int64_t)n * d, 256)), dim3(256), 0, c->stream, CT, w->d_tok_emb.as<float>(),
                        w->d_pos_emb.as<float>(), POS, d, n, w->g_c_resid.as<float>());
     // up to 16 heads: one workgroup per clip, one wave per head (115.8 against 119.6 us per launch with a workgroup per clip and head); that
-    // kernel also appends the new position to the self-attention cache
-    bool wave_per_head = H <= 16;
+    // kernel also appends the new position to the self-attention cache.  More heads (20 at large-v3 / turbo): workgroups of at most 16 waves,
+    // grid (clip, head group) -- the attribute below (16 waves' slices) covers the largest group
+    const int hgroups = (H + 15) / 16, hg_waves = (H + hgroups - 1) / hgroups;
+    bool wave_per_head = H <= 32;
     if (wave_per_head && !c->attn1w_attr[PCE_OP_INDEX]) {
         if (hipFuncSetAttribute((const void *)k_cross_attn1w, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1600 * 4) == hipSuccess) c->attn1w_attr[PCE_OP_INDEX] = true;
         else { (void)hipGetLastError(); wave_per_head = false; }
@@ -3298,7 +3311,8 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
         KernelTimer kt(c, PCE_K_CROSS_ATTN1);
         if (wave_per_head) {
             if (app_qkv) { a.app_k = app_qkv + d; a.app_v = app_qkv + 2 * d; a.app_ld = 3 * d; a.app_pos = POS; }
-            hipLaunchKernelGGL(k_cross_attn1w, dim3((unsigned)n), dim3(64 * (unsigned)H), (size_t)H * 1600 * 4, c->stream, a);
+            a.heads = H;
+            hipLaunchKernelGGL(k_cross_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 1600 * 4, c->stream, a);
             return;
         }
         hipLaunchKernelGGL(k_cross_attn1, dim3((unsigned)H, (unsigned)n), dim3(A1_T), 0, c->stream, a);
@@ -3307,8 +3321,11 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
         hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(n, 4)), dim3(256), 0, c->stream, w->g_c_resid.as<float>(), Wf + w_off, Wf + b_off,
                            (int64_t)n, d, w->g_c_ln.as<op_t>());
     };
-    // cross-attention from the encoder output (pce_xattn.inc): E once per layer instead of K and V^T
-    const bool absorb = c->xattn_absorb && H <= 16 && (d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024) && w->g_qp.p && w->g_wkT.p;
+    // cross-attention from the encoder output (pce_xattn.inc): E once per layer instead of K and V^T.  d = 1280 (large-v3 / turbo, 20 heads): two
+    // 16-row tiles of heads, 8 waves per workgroup
+    const bool absorb = c->xattn_absorb && ((H <= 16 && (d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024)) || (d == 1280 && H <= 32 && H * 64 == d))
+                        && w->g_qp.p && w->g_wkT.p;
+    const int xrows = xa_rows(H);                                 // rows of Q' and of the partials per clip: 16, or 32 at 20 heads
     // workgroups per clip (two per CU): ONLY the work distribution follows the batch size -- the frames are always cut into the same XA_LEAVES ranges
     // and merged in the same order (pce_xattn.inc), so a clip's bits do not depend on what it is batched with.  PCE_XATTN_WPC = 1 | 2 | 4 overrides (tests)
     static const int env_wpc = getenv("PCE_XATTN_WPC") ? atoi(getenv("PCE_XATTN_WPC")) : 0;
@@ -3316,46 +3333,48 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
     if (nsplit > XA_LEAVES) nsplit = XA_LEAVES;
     auto xattn = [&](int l) {
         const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-        op_t *qp_hi = w->g_qp.as<op_t>(), *qp_lo = qp_hi + (size_t)n * 16 * d;
+        op_t *qp_hi = w->g_qp.as<op_t>(), *qp_lo = qp_hi + (size_t)n * xrows * d;
         KernelTimer kt(c, PCE_K_CROSS_ATTN1);
         auto xq = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3((unsigned)H, (unsigned)div_up(n, 16)), dim3(256), 0, c->stream, w->g_c_resid.as<float>(), Wf + ly.lnx_w, Wf + ly.lnx_b,
-                               Wb + ly.xq_w, Wf + ly.xq_b, w->g_wkT.as<op_t>() + (size_t)d * d * (size_t)l, n, 0.125f * 1.4426950408889634f, ended, qp_hi, qp_lo);
+                               Wb + ly.xq_w, Wf + ly.xq_b, w->g_wkT.as<op_t>() + (size_t)d * d * (size_t)l, n, 0.125f * 1.4426950408889634f, ended, qp_hi, qp_lo, xrows);
         };
         if (d == 128) xq(k_xq_fused<128>); else if (d == 256) xq(k_xq_fused<256>); else if (d == 384) xq(k_xq_fused<384>); else if (d == 512) xq(k_xq_fused<512>);
-        else if (d == 768) xq(k_xq_fused<768>); else xq(k_xq_fused<1024>);
+        else if (d == 768) xq(k_xq_fused<768>); else if (d == 1024) xq(k_xq_fused<1024>); else xq(k_xq_fused<1280>);
         XaArgs a{};
         a.E = w->d_enc_bf16.as<op_t>(); a.e_clip = (int64_t)W_CTX * d; a.e_ld = d; a.qp_hi = qp_hi; a.qp_lo = qp_lo; a.k_len = XL; a.skip = ended;
-        a.u_part = w->g_upart.as<float>(); a.ml_part = w->g_mlpart.as<float>(); a.heads = H; a.nsplit = nsplit;
+        a.u_part = w->g_upart.as<float>(); a.ml_part = w->g_mlpart.as<float>(); a.heads = H; a.nsplit = nsplit; a.rows = xrows;
         // a workgroup that owns both leaves of a pair (nsplit <= 2) merges them in registers and writes pair nodes; d = 1024 has no registers for the
         // waiting leaf (194 + 64) and always writes leaves
         const bool pairs = nsplit <= XA_LEAVES / 2 && d <= 768;
         const dim3 grid((unsigned)(n * nsplit));
         auto go = [&](auto kern, int nslot) {
-            const size_t lds = (size_t)nslot * XA_TF * d * 2 + 4096;
+            const size_t lds = xa_lds(d, nslot);
             const unsigned bit = 1u << (d / 128 + (pairs ? 16 : 0)); // one instantiation per (d, pair form): each is its own function and needs its own attribute
             if (!(c->xattn_attr[PCE_OP_INDEX] & bit)) {
                 (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 c->xattn_attr[PCE_OP_INDEX] |= bit;
             }
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, c->stream, a);
+            hipLaunchKernelGGL(kern, grid, dim3(64 * (unsigned)xa_waves(d)), lds, c->stream, a);
         };
         if (d == 128) { if (pairs) go(k_xattn_absorbed<128, 3, true>, 3); else go(k_xattn_absorbed<128, 3, false>, 3); }
         else if (d == 256) { if (pairs) go(k_xattn_absorbed<256, 3, true>, 3); else go(k_xattn_absorbed<256, 3, false>, 3); }
         else if (d == 384) { if (pairs) go(k_xattn_absorbed<384, 3, true>, 3); else go(k_xattn_absorbed<384, 3, false>, 3); }
         else if (d == 512) { if (pairs) go(k_xattn_absorbed<512, 2, true>, 2); else go(k_xattn_absorbed<512, 2, false>, 2); }
         else if (d == 768) { if (pairs) go(k_xattn_absorbed<768, 2, true>, 2); else go(k_xattn_absorbed<768, 2, false>, 2); }
-        else go(k_xattn_absorbed<1024, 2, false>, 2);
+        else if (d == 1024) go(k_xattn_absorbed<1024, 2, false>, 2);
+        else go(k_xattn_absorbed<1280, 3, false, 8, 2>, 3);        // (136 KB of LDS: one workgroup of 8 waves per CU)
         auto uv = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3((unsigned)H, (unsigned)div_up(n, 16)), dim3(256), 0, c->stream, w->g_upart.as<float>(), w->g_mlpart.as<float>(),
-                               Wb + ly.xkv_w + (size_t)d * d, Wf + ly.xkv_b + d, n, ended, w->g_c_attn.as<op_t>(), (int64_t)d);
+                               Wb + ly.xkv_w + (size_t)d * d, Wf + ly.xkv_b + d, n, ended, w->g_c_attn.as<op_t>(), (int64_t)d, xrows);
         };
         if (d == 128) { if (pairs) uv(k_uv_absorb<128, true>); else uv(k_uv_absorb<128, false>); }
         else if (d == 256) { if (pairs) uv(k_uv_absorb<256, true>); else uv(k_uv_absorb<256, false>); }
         else if (d == 384) { if (pairs) uv(k_uv_absorb<384, true>); else uv(k_uv_absorb<384, false>); }
         else if (d == 512) { if (pairs) uv(k_uv_absorb<512, true>); else uv(k_uv_absorb<512, false>); }
         else if (d == 768) { if (pairs) uv(k_uv_absorb<768, true>); else uv(k_uv_absorb<768, false>); }
-        else uv(k_uv_absorb<1024, false>);
+        else if (d == 1024) uv(k_uv_absorb<1024, false>);
+        else uv(k_uv_absorb<1280, false>);
     };
     for (int l = 0; l < L; l++) {
         const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
@@ -3371,9 +3390,9 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
             // which rewrite every position they attend to, read it)
             SelfAttn1Args sa{};
             sa.qkv = w->g_c_qkv.as<op_t>(); sa.qkv_ld = 3 * d; sa.ck = w->g_sk.as<op_t>() + sk_l * (size_t)l; sa.cv = w->g_sv.as<op_t>() + sk_l * (size_t)l;
-            sa.c_clip = (int64_t)T_cap * d; sa.d = d; sa.pos = POS; sa.skip = ended; sa.out = w->g_c_attn.as<op_t>(); sa.out_ld = d;
+            sa.c_clip = (int64_t)T_cap * d; sa.d = d; sa.pos = POS; sa.skip = ended; sa.out = w->g_c_attn.as<op_t>(); sa.out_ld = d; sa.heads = H;
             KernelTimer kt(c, PCE_K_CROSS_ATTN1);
-            hipLaunchKernelGGL(k_self_attn1w, dim3((unsigned)n), dim3(64 * (unsigned)H), (size_t)H * 512 * 4, c->stream, sa);
+            hipLaunchKernelGGL(k_self_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 512 * 4, c->stream, sa);
         } else
         cattn(w->g_c_qkv.as<op_t>(), 3 * d, w->g_sk.as<op_t>() + sk_l * (size_t)l, d, w->g_svt.as<op_t>() + svt_l * (size_t)l, (int64_t)d * SPD, SPD, K0, KL,
               w->g_c_qkv.as<op_t>());
@@ -3405,11 +3424,11 @@ static int decode_incremental_reserve(pce_ctx *c, WhisperState *w, int n)
     PCE_HIP(c, w->g_c_q.reserve(sizeof(op_t) * (size_t)(n + 128) * d + 4096));
     PCE_HIP(c, w->g_c_hidden.reserve(sizeof(op_t) * (size_t)(n + 128) * 4 * d + 4096));
     if (c->xattn_absorb) {
-        const size_t before = w->g_qp.cap;
-        PCE_HIP(c, w->g_qp.reserve(sizeof(op_t) * 2 * (size_t)n * 16 * d + 256));
+        const size_t before = w->g_qp.cap, R = (size_t)xa_rows(w->tdims.n_head);   // R rows of heads per clip (pce_xattn.inc)
+        PCE_HIP(c, w->g_qp.reserve(sizeof(op_t) * 2 * (size_t)n * R * d + 256));
         if (w->g_qp.cap != before) PCE_HIP(c, hipMemsetAsync(w->g_qp.p, 0, w->g_qp.cap, c->stream));               // (rows >= heads feed MFMA rows nobody reads: finite all the same)
-        PCE_HIP(c, w->g_upart.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * 16 * d + 256));
-        PCE_HIP(c, w->g_mlpart.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * 16 * 2 + 256));
+        PCE_HIP(c, w->g_upart.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
+        PCE_HIP(c, w->g_mlpart.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * 2 + 256));
     }
     return PCE_OK;
 }

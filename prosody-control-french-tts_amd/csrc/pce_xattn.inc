@@ -46,12 +46,14 @@ __device__ __forceinline__ xa_s16x4 xa_tr_read(unsigned addr) { xa_s16x4 r; asm 
 
 struct XaArgs {
     const op_t *E; int64_t e_clip; int e_ld;        // E + clip * e_clip + t * e_ld (+ column)
-    const op_t *qp_hi, *qp_lo;                      // [clip][16][D]: Q' (scaled by log2 e / sqrt(head size)); rows >= heads are never used
+    const op_t *qp_hi, *qp_lo;                      // [clip][R][D]: Q' (scaled by log2 e / sqrt(head size)); rows >= heads are never used
     const int *k_len, *skip;                        // per clip; skip may be null
-    float *u_part;                                  // [clip][nodes][16][D]: sum_t 2^(s_t - m) E[t] over the frames of one node (nodes = 4 leaves, or 2 pairs: PAIR kernels)
-    float *ml_part;                                 // [clip][nodes][16][2]: the node's reference m and sum l
+    float *u_part;                                  // [clip][nodes][R][D]: sum_t 2^(s_t - m) E[t] over the frames of one node (nodes = 4 leaves, or 2 pairs: PAIR kernels)
+    float *ml_part;                                 // [clip][nodes][R][2]: the node's reference m and sum l
     int heads, nsplit;                              // nsplit: workgroups per clip (1, 2 or 4); each walks XA_LEAVES / nsplit consecutive leaves
+    int rows;                                       // R = 16 ceil(heads / 16): the heads are the rows of R / 16 MFMA row tiles (16 up to 16 heads, 32 at 20)
 };
+constexpr int xa_rows(int heads) { return 16 * ((heads + 15) / 16); }
 
 // The frames of a clip are ALWAYS cut into the same four LEAVES, each with its own online softmax, and the leaves are ALWAYS combined in the same tree
 // (L0 + L1) + (L2 + L3), "+" = xa_merge below -- whatever the batch size.  Round 5 cut the frames into as many ranges as workgroups per clip (8 / 4 / 2 / 1 by
@@ -73,14 +75,18 @@ __device__ __forceinline__ void xa_merge_w(float ma, float mb, float &m, float &
 }
 __device__ __forceinline__ float xa_merge_v(float a, float wa, float b, float wb) { return fmaf(b, wb, a * wa); }
 
-// one workgroup = one (clip, split), 4 waves: wave w owns d / 4 of the reduction axis of S^T (partials summed through LDS, every wave in the same
-// order: the same bits) and d / 4 of the columns of U^T.  E streams through a ring of NSLOT slots by LDS-DMA with the non-temporal policy (it is read
-// once per launch and is larger than every cache: without `nt` the same instruction stream is 14 % slower, tools/lab/xattn_absorb.hip), two or
-// three workgroups per CU.
-template <int D, int NSLOT, bool PAIR>
+// one workgroup = one (clip, split), WV waves: wave w owns d / WV of the reduction axis of S^T (partials summed through LDS, every wave in the same
+// order: the same bits) and d / WV of the columns of U^T.  E streams through a ring of NSLOT slots by LDS-DMA with the non-temporal policy (it is read
+// once per launch and is larger than every cache: without `nt` the same instruction stream is 14 % slower, tools/lab/xattn_absorb.hip).
+// d <= 1024 (at most 16 heads): 4 waves, one row tile of heads, two or three workgroups per CU.  d = 1280 (20 heads: large-v3 / turbo): 8 waves and
+// RT = 2 row tiles (rows 16..31 hold heads 16..19 and unused rows): the 4-wave body would hold 160 Q' and 160 U registers per wave at two row tiles;
+// with 8 waves each wave keeps 5 k-steps x 2 tiles of Q' (hi + lo: 80 VGPRs) and 10 column blocks x 2 tiles of U (80), and E still streams once
+// per layer -- every column block of E^T serves both row tiles.  One workgroup per CU (three 40 KB slots + 16 KB of partials), two waves per SIMD.
+template <int D, int NSLOT, bool PAIR, int WV, int RT>
 __device__ __forceinline__ void xattn_absorbed_body(const XaArgs &A, char *smem)
 {
-    constexpr int TF = XA_TF, KS = D / 128, CB = D / 64, LPW = D / 128, TILE = TF * D * 2;   // k-steps / column blocks / DMA instructions per wave; tile bytes
+    static_assert(D % (32 * WV) == 0 && (RT == 1 || !PAIR), "a wave owns whole k-steps; the in-register pair form holds one row tile");
+    constexpr int TF = XA_TF, KS = D / (32 * WV), CB = D / (16 * WV), LPW = D / (32 * WV), TILE = TF * D * 2;   // k-steps / column blocks / DMA instructions per wave; tile bytes
     const int bid = (int)blockIdx.x;
     const int clip = bid / A.nsplit, split = bid - clip * A.nsplit;
     if (A.skip && A.skip[clip]) return;
@@ -92,29 +98,33 @@ __device__ __forceinline__ void xattn_absorbed_body(const XaArgs &A, char *smem)
     const int t_lo = leaf0 * per, nt = max(min(nt_all, t_lo + lpw * per) - t_lo, 0);
     const op_t *eb = A.E + (int64_t)clip * A.e_clip;
     const __amdgpu_buffer_rsrc_t rsE = __builtin_amdgcn_make_buffer_rsrc(const_cast<op_t *>(eb), 0, ((Sk - 1) * A.e_ld + D) * 2, 0x00020000);
-    // Q' fragments of this wave's slice of the d axis (B operand: lane (n16 = head row, g) holds d = 32 kk + 8 g .. + 7)
-    opx8 qh[KS], ql[KS];
+    // Q' fragments of this wave's slice of the d axis (B operand: lane (n16 = head row of row tile rt, g) holds d = 32 kk + 8 g .. + 7)
+    opx8 qh[RT][KS], ql[RT][KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ks++) {
-        const int64_t o = ((int64_t)clip * 16 + n16) * D + 32 * (wv * KS + ks) + 8 * g;
-        qh[ks] = *reinterpret_cast<const opx8 *>(A.qp_hi + o);
-        ql[ks] = *reinterpret_cast<const opx8 *>(A.qp_lo + o);
-    }
+    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) {
+            const int64_t o = ((int64_t)clip * A.rows + 16 * rt + n16) * D + 32 * (wv * KS + ks) + 8 * g;
+            qh[rt][ks] = *reinterpret_cast<const opx8 *>(A.qp_hi + o);
+            ql[rt][ks] = *reinterpret_cast<const opx8 *>(A.qp_lo + o);
+        }
     // Q' must have ARRIVED before the ring starts: left to itself the compiler waits for these loads at their first use inside the loop with a
     // vmcnt count that also drains the tile prefetched behind them -- every iteration
 #pragma unroll
-    for (int ks = 0; ks < KS; ks++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(qh[ks]), "+v"(ql[ks]));
+    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) asm volatile("s_waitcnt vmcnt(0)" : "+v"(qh[rt][ks]), "+v"(ql[rt][ks]));
     int voff[LPW];
 #pragma unroll
     for (int i = 0; i < LPW; i++) {
-        const int X = 64 * (wv + 4 * i) + lane, row = X / (D / 8), ch = (X % (D / 8)) ^ xa_swz(row);
+        const int X = 64 * (wv + WV * i) + lane, row = X / (D / 8), ch = (X % (D / 8)) ^ xa_swz(row);
         voff[i] = (row * A.e_ld + 8 * ch) * 2;
     }
     auto stage = [&](int t) {
         char *slot = smem + (t % NSLOT) * TILE;
 #pragma unroll
         for (int i = 0; i < LPW; i++)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsE, (__attribute__((address_space(3))) void *)(slot + 1024 * (wv + 4 * i)), 16, voff[i], (t_lo + t) * TF * A.e_ld * 2, 0, 3 /* sc0 | nt: streamed once, see the header */);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsE, (__attribute__((address_space(3))) void *)(slot + 1024 * (wv + WV * i)), 16, voff[i], (t_lo + t) * TF * A.e_ld * 2, 0, 3 /* sc0 | nt: streamed once, see the header */);
     };
     int raddr[KS];                                               // row reads: frame pi(n16), d chunk of k-step wv KS + ks
     // The 16 frames of a tile sit on the MFMA rows in the order pi(m) = 4 sigma(m >> 2) + (m & 3), sigma = (0, 2, 1, 3): lane group g then holds the scores of
@@ -128,45 +138,53 @@ __device__ __forceinline__ void xattn_absorbed_body(const XaArgs &A, char *smem)
     float *xs = reinterpret_cast<float *>(smem + NSLOT * TILE);
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 u[CB];
+    f32x4 u[RT][CB];
 #pragma unroll
-    for (int cb = 0; cb < CB; cb++) u[cb] = z4;
-    float m_run = -1e30f, l_part = 0.f;
+    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+        for (int cb = 0; cb < CB; cb++) u[rt][cb] = z4;
+    float m_run[RT], l_part[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; rt++) { m_run[rt] = -1e30f; l_part[rt] = 0.f; }
     // PAIR (a workgroup that owns both leaves of a pair): the even leaf's node waits here for the odd one
     f32x4 uh[PAIR ? CB : 1];
     float mh = -1e30f, lh = 0.f;
     auto flush = [&](int leaf) {                                 // a finished leaf: its node (U, reference m, sum l) leaves, or waits for / joins its pair
-        float l = l_part;
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-        if (PAIR && !(leaf & 1)) {
 #pragma unroll
-            for (int cb = 0; cb < CB; cb++) uh[PAIR ? cb : 0] = u[cb];
-            mh = m_run; lh = l;
-        } else {
-            int node = leaf;
-            float m_out = m_run;
-            if (PAIR) {                                          // (held even leaf) + (this odd leaf): xa_merge, as k_uv_absorb does it from stored leaves
-                float wa, wb;
-                xa_merge_w(mh, m_run, m_out, wa, wb);
-                l = xa_merge_v(lh, wa, l, wb);
+        for (int rt = 0; rt < RT; rt++) {
+            float l = l_part[rt];
+            l += __shfl_xor(l, 16, 64);
+            l += __shfl_xor(l, 32, 64);
+            if (PAIR && !(leaf & 1)) {
 #pragma unroll
-                for (int cb = 0; cb < CB; cb++)
+                for (int cb = 0; cb < CB; cb++) uh[PAIR ? cb : 0] = u[0][cb];
+                mh = m_run[0]; lh = l;
+            } else {
+                int node = leaf;
+                float m_out = m_run[rt];
+                if (PAIR) {                                      // (held even leaf) + (this odd leaf): xa_merge, as k_uv_absorb does it from stored leaves
+                    float wa, wb;
+                    xa_merge_w(mh, m_run[0], m_out, wa, wb);
+                    l = xa_merge_v(lh, wa, l, wb);
 #pragma unroll
-                    for (int e = 0; e < 4; e++) u[cb][e] = xa_merge_v(uh[PAIR ? cb : 0][e], wa, u[cb][e], wb);
-                node = leaf >> 1;
+                    for (int cb = 0; cb < CB; cb++)
+#pragma unroll
+                        for (int e = 0; e < 4; e++) u[0][cb][e] = xa_merge_v(uh[PAIR ? cb : 0][e], wa, u[0][cb][e], wb);
+                    node = leaf >> 1;
+                }
+                constexpr int NODES = PAIR ? XA_LEAVES / 2 : XA_LEAVES;
+                const int row = 16 * rt + n16;
+                if (row < A.heads) {
+                    float *up = A.u_part + (((int64_t)clip * NODES + node) * A.rows + row) * D;
+#pragma unroll
+                    for (int cb = 0; cb < CB; cb++) *reinterpret_cast<f32x4 *>(up + 16 * (wv * CB + cb) + 4 * g) = u[rt][cb];
+                    if (wv == 0 && g == 0) { float *mp = A.ml_part + (((int64_t)clip * NODES + node) * A.rows + row) * 2; mp[0] = m_out; mp[1] = l; }
+                }
             }
-            constexpr int NODES = PAIR ? XA_LEAVES / 2 : XA_LEAVES;
-            if (n16 < A.heads) {
-                float *up = A.u_part + (((int64_t)clip * NODES + node) * 16 + n16) * D;
 #pragma unroll
-                for (int cb = 0; cb < CB; cb++) *reinterpret_cast<f32x4 *>(up + 16 * (wv * CB + cb) + 4 * g) = u[cb];
-                if (wv == 0 && g == 0) { float *mp = A.ml_part + (((int64_t)clip * NODES + node) * 16 + n16) * 2; mp[0] = m_out; mp[1] = l; }
-            }
+            for (int cb = 0; cb < CB; cb++) u[rt][cb] = z4;
+            m_run[rt] = -1e30f; l_part[rt] = 0.f;
         }
-#pragma unroll
-        for (int cb = 0; cb < CB; cb++) u[cb] = z4;
-        m_run = -1e30f; l_part = 0.f;
     };
     int leaf = leaf0;
     for (int t = 0; t < NSLOT - 1 && t < nt; t++) stage(t);
@@ -179,54 +197,64 @@ __device__ __forceinline__ void xattn_absorbed_body(const XaArgs &A, char *smem)
         if (t > 0 && t - (leaf - leaf0 + 1) * per == 0) flush(leaf++);
         const char *sC = smem + (t % NSLOT) * TILE;
         const unsigned sbase = lds0 + (unsigned)((t % NSLOT) * TILE);
-        {   // ---- partial S^T over this wave's quarter of d
-            f32x4 a = z4;
+        {   // ---- partial S^T over this wave's share of d, every row tile
+            f32x4 a[RT];
+#pragma unroll
+            for (int rt = 0; rt < RT; rt++) a[rt] = z4;
 #pragma unroll
             for (int ks = 0; ks < KS; ks++) {
                 const opx8 ef = *reinterpret_cast<const opx8 *>(sC + raddr[ks]);
-                a = mfma16(ef, qh[ks], a);
-                a = mfma16(ef, ql[ks], a);
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++) {
+                    a[rt] = mfma16(ef, qh[rt][ks], a[rt]);
+                    a[rt] = mfma16(ef, ql[rt][ks], a[rt]);
+                }
             }
-            *reinterpret_cast<f32x4 *>(xs + (wv * 64 + lane) * 4) = a;
+#pragma unroll
+            for (int rt = 0; rt < RT; rt++) *reinterpret_cast<f32x4 *>(xs + ((wv * RT + rt) * 64 + lane) * 4) = a[rt];
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);                      // the partials are in LDS (lgkmcnt 0; the DMA of later tiles stays in flight)
         asm volatile("" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        f32x4 sc = z4;
-#pragma unroll
-        for (int w2 = 0; w2 < 4; w2++) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(xs + (w2 * 64 + lane) * 4);
-            sc[0] += v[0]; sc[1] += v[1]; sc[2] += v[2]; sc[3] += v[3];
-        }
         const int f0 = (t_lo + t) * TF;
-        if (f0 + TF > Sk) {
+        xa_opx4 ph[RT], pl[RT];
 #pragma unroll
-            for (int i = 0; i < 4; i++)
-                if (f0 + 4 * sg + i >= Sk) sc[i] = -1e30f;
-        }
-        float m = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        const float mx = fmaxf(m_run, m);
-        if (__builtin_amdgcn_ballot_w64(mx > m_run) != 0) {
-            const float corr = __builtin_amdgcn_exp2f(m_run - mx);
-            l_part *= corr;
+        for (int rt = 0; rt < RT; rt++) {
+            f32x4 sc = z4;
 #pragma unroll
-            for (int cb = 0; cb < CB; cb++) { u[cb][0] *= corr; u[cb][1] *= corr; u[cb][2] *= corr; u[cb][3] *= corr; }
-            m_run = mx;
-        }
-        xa_opx4 ph, pl;
+            for (int w2 = 0; w2 < WV; w2++) {
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(xs + ((w2 * RT + rt) * 64 + lane) * 4);
+                sc[0] += v[0]; sc[1] += v[1]; sc[2] += v[2]; sc[3] += v[3];
+            }
+            if (f0 + TF > Sk) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const float pv = __builtin_amdgcn_exp2f(sc[i] - m_run);
-            l_part += pv;
-            const op_t h = (op_t)pv;
-            ph[i] = h; pl[i] = (op_t)(pv - (float)h);
+                for (int i = 0; i < 4; i++)
+                    if (f0 + 4 * sg + i >= Sk) sc[i] = -1e30f;
+            }
+            float m = fmaxf(fmaxf(sc[0], sc[1]), fmaxf(sc[2], sc[3]));
+            m = fmaxf(m, __shfl_xor(m, 16, 64));
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+            const float mx = fmaxf(m_run[rt], m);
+            if (__builtin_amdgcn_ballot_w64(mx > m_run[rt]) != 0) {
+                const float corr = __builtin_amdgcn_exp2f(m_run[rt] - mx);
+                l_part[rt] *= corr;
+#pragma unroll
+                for (int cb = 0; cb < CB; cb++) { u[rt][cb][0] *= corr; u[rt][cb][1] *= corr; u[rt][cb][2] *= corr; u[rt][cb][3] *= corr; }
+                m_run[rt] = mx;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const float pv = __builtin_amdgcn_exp2f(sc[i] - m_run[rt]);
+                l_part[rt] += pv;
+                const op_t h = (op_t)pv;
+                ph[rt][i] = h; pl[rt][i] = (op_t)(pv - (float)h);
+            }
         }
-        // ---- U^T += E^T P^T over this wave's quarter of the columns on the 16x16x16 MFMA: A = one transposed 4-frame x 16-column block per column
-        // block (lane (column n16, g): frames 4 sigma(g) .. + 3), B = this lane's four probabilities as they lie in the S^T accumulator.
-        // The reads of a group are waited for by hand, the wait carrying them as operands so that no MFMA moves above it.
+        // ---- U^T += E^T P^T over this wave's share of the columns on the 16x16x16 MFMA: A = one transposed 4-frame x 16-column block per column
+        // block (lane (column n16, g): frames 4 sigma(g) .. + 3), B = this lane's four probabilities as they lie in the S^T accumulator (one
+        // column block of E^T serves every row tile).  The reads of a group are waited for by hand, the wait carrying them as operands so that no
+        // MFMA moves above it.
         constexpr int GR = (CB % 4 == 0) ? 4 : 2;
 #pragma unroll
         for (int cb0 = 0; cb0 < CB; cb0 += GR) {
@@ -239,22 +267,27 @@ __device__ __forceinline__ void xattn_absorbed_body(const XaArgs &A, char *smem)
             if (GR == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]));
             else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r[0]), "+v"(r[1]));
 #pragma unroll
-            for (int j = 0; j < GR; j++) {
-                u[cb0 + j] = XaMfmaK16<op_t>::run(r[j], ph, u[cb0 + j]);
-                u[cb0 + j] = XaMfmaK16<op_t>::run(r[j], pl, u[cb0 + j]);
-            }
+            for (int j = 0; j < GR; j++)
+#pragma unroll
+                for (int rt = 0; rt < RT; rt++) {
+                    u[rt][cb0 + j] = XaMfmaK16<op_t>::run(r[j], ph[rt], u[rt][cb0 + j]);
+                    u[rt][cb0 + j] = XaMfmaK16<op_t>::run(r[j], pl[rt], u[rt][cb0 + j]);
+                }
         }
     }
     // the last leaf that holds frames, then the empty partials (U = 0, l = 0, m = -1e30: weight 0 in the merge) of the leaves a short clip does not reach
     for (; leaf < leaf0 + lpw; ) flush(leaf++);
 }
 
-template <int D, int NSLOT, bool PAIR>
-__global__ __launch_bounds__(256, 2) void k_xattn_absorbed(XaArgs A)
+template <int D, int NSLOT, bool PAIR, int WV = 4, int RT = 1>
+__global__ __launch_bounds__(64 * WV, 8 / WV) void k_xattn_absorbed(XaArgs A)
 {
-    extern __shared__ __attribute__((aligned(16))) char xa_smem[];   // NSLOT tiles | 4 x 1 KB of partial S^T
-    xattn_absorbed_body<D, NSLOT, PAIR>(A, xa_smem);
+    extern __shared__ __attribute__((aligned(16))) char xa_smem[];   // NSLOT tiles | WV x RT x 1 KB of partial S^T
+    xattn_absorbed_body<D, NSLOT, PAIR, WV, RT>(A, xa_smem);
 }
+// dynamic LDS of an instantiation; the waves and row tiles of a width
+constexpr size_t xa_lds(int d, int nslot) { return (size_t)nslot * XA_TF * d * 2 + (d > 1024 ? 8 * 2 : 4) * 1024; }
+constexpr int xa_waves(int d) { return d > 1024 ? 8 : 4; }
 
 // The query projection and Q' in ONE launch: grid (heads, ceil(n / 16)), 4 waves.
 //   step 1  q_h^T[i (64)][clip (16)] = Wq[h 64 + i][:] ln[clip][:] + bq, K = d: wave w takes every fourth k-step for all 64 rows i, the four partial sums
@@ -269,7 +302,7 @@ __global__ __launch_bounds__(256, 2) void k_xattn_absorbed(XaArgs A)
 template <int D>
 __global__ __launch_bounds__(256) PCE_NO_PK_F32 void k_xq_fused(const float *__restrict__ resid, const float *__restrict__ ln_w, const float *__restrict__ ln_b, const op_t *__restrict__ wq,
                                                    const float *__restrict__ bq, const op_t *__restrict__ wkT, int n, float scale, const int *__restrict__ skip,
-                                                   op_t *__restrict__ qp_hi, op_t *__restrict__ qp_lo)
+                                                   op_t *__restrict__ qp_hi, op_t *__restrict__ qp_lo, int rows /* R of XaArgs */)
 {
     constexpr int KW = D / 128, JB = D / 64;                        // step 1: k-steps per wave (every fourth one); step 2: 16-row blocks of j per wave
     __shared__ __attribute__((aligned(16))) op_t qs[16][64 + 8];
@@ -369,7 +402,7 @@ __global__ __launch_bounds__(256) PCE_NO_PK_F32 void k_xq_fused(const float *__r
         xa_opx4 h4, l4;
 #pragma unroll
         for (int e = 0; e < 4; e++) { const float v = r[e] * scale; h4[e] = (op_t)v; l4[e] = (op_t)(v - (float)h4[e]); }
-        const int64_t o = ((int64_t)c * 16 + h) * D + wv * (D / 4) + 16 * jb + 4 * g;
+        const int64_t o = ((int64_t)c * rows + h) * D + wv * (D / 4) + 16 * jb + 4 * g;
         *reinterpret_cast<xa_opx4 *>(qp_hi + o) = h4;
         *reinterpret_cast<xa_opx4 *>(qp_lo + o) = l4;
     }
@@ -381,7 +414,8 @@ __global__ __launch_bounds__(256) PCE_NO_PK_F32 void k_xq_fused(const float *__r
 // and the four partial sums meet in LDS (added in wave order: the same bits every run).
 template <int D, bool PAIRS>                                 // PAIRS: the partials are the two pair nodes (written by the PAIR kernels); else the four leaves
 __global__ __launch_bounds__(256) void k_uv_absorb(const float *__restrict__ u_part, const float *__restrict__ ml_part, const op_t *__restrict__ wv_w,
-                                                    const float *__restrict__ bv, int n, const int *__restrict__ skip, op_t *__restrict__ out, int64_t out_ld)
+                                                    const float *__restrict__ bv, int n, const int *__restrict__ skip, op_t *__restrict__ out, int64_t out_ld,
+                                                    int rows /* R of XaArgs */)
 {
     constexpr int KW = D / 128, NS = PAIRS ? XA_LEAVES / 2 : XA_LEAVES;   // k-steps per wave; nodes per clip in the buffer
     __shared__ float red[4][4][64][4];                            // [wave][i block][lane][4]
@@ -393,7 +427,7 @@ __global__ __launch_bounds__(256) void k_uv_absorb(const float *__restrict__ u_p
     {
         float mv[NS], lv[NS];
 #pragma unroll
-        for (int s = 0; s < NS; s++) { const float *mp = ml_part + (((int64_t)cc * NS + s) * 16 + h) * 2; mv[s] = mp[0]; lv[s] = mp[1]; }
+        for (int s = 0; s < NS; s++) { const float *mp = ml_part + (((int64_t)cc * NS + s) * rows + h) * 2; mv[s] = mp[0]; lv[s] = mp[1]; }
         float pm[2], pl[2];
         if (PAIRS) { pm[0] = mv[0]; pm[1] = mv[NS - 1]; pl[0] = lv[0]; pl[1] = lv[NS - 1]; }
         else {
@@ -407,7 +441,7 @@ __global__ __launch_bounds__(256) void k_uv_absorb(const float *__restrict__ u_p
         xa_merge_w(pm[0], pm[1], mr, wp[0], wp[1]);
         inv = 1.0f / xa_merge_v(pl[0], wp[0], pl[1], wp[1]);
     }
-    const float *up = u_part + ((int64_t)cc * NS * 16 + h) * D + 8 * g;
+    const float *up = u_part + ((int64_t)cc * NS * rows + h) * D + 8 * g;
     const op_t *wr = wv_w + (int64_t)(h * 64 + n16) * D + 8 * g;
     // every load of a wave is issued before the first use (one memory round trip: the partials and the weight fragments are independent of each other)
     f32x4 x[KW][NS][2];
@@ -417,8 +451,8 @@ __global__ __launch_bounds__(256) void k_uv_absorb(const float *__restrict__ u_p
         const int ks = 4 * k + wv;
 #pragma unroll
         for (int s = 0; s < NS; s++) {
-            x[k][s][0] = *reinterpret_cast<const f32x4 *>(up + (int64_t)s * 16 * D + 32 * ks);
-            x[k][s][1] = *reinterpret_cast<const f32x4 *>(up + (int64_t)s * 16 * D + 32 * ks + 4);
+            x[k][s][0] = *reinterpret_cast<const f32x4 *>(up + (int64_t)s * rows * D + 32 * ks);
+            x[k][s][1] = *reinterpret_cast<const f32x4 *>(up + (int64_t)s * rows * D + 32 * ks + 4);
         }
 #pragma unroll
         for (int ib = 0; ib < 4; ib++) wf[k][ib] = *reinterpret_cast<const opx8 *>(wr + (int64_t)16 * ib * D + 32 * ks);

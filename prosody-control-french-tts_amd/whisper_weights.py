@@ -10,7 +10,12 @@ DIMS = {
     "base": dict(n_mels=80, n_ctx=1500, n_state=512, n_head=8, n_layer=6),
     "small": dict(n_mels=80, n_ctx=1500, n_state=768, n_head=12, n_layer=12),
     "medium": dict(n_mels=80, n_ctx=1500, n_state=1024, n_head=16, n_layer=24),
+    # large-v3 and its 4-decoder-layer distillation turbo (large-v3-turbo, the reference aligner's default) share the 32-layer encoder
+    "large-v3": dict(n_mels=128, n_ctx=1500, n_state=1280, n_head=20, n_layer=32),
+    "large-v3-turbo": dict(n_mels=128, n_ctx=1500, n_state=1280, n_head=20, n_layer=32),
 }
+DIMS["large"] = DIMS["large-v3"]                                 # openai-whisper 20240930: "large" -> large-v3, "turbo" -> large-v3-turbo
+DIMS["turbo"] = DIMS["large-v3-turbo"]
 
 
 def tensor_order(dims):
@@ -55,7 +60,11 @@ TEXT_DIMS = {
     "base": dict(n_vocab=51865, n_text_ctx=448, n_state=512, n_head=8, n_layer=6),
     "small": dict(n_vocab=51865, n_text_ctx=448, n_state=768, n_head=12, n_layer=12),
     "medium": dict(n_vocab=51865, n_text_ctx=448, n_state=1024, n_head=16, n_layer=24),
+    "large-v3": dict(n_vocab=51866, n_text_ctx=448, n_state=1280, n_head=20, n_layer=32),       # (one more language token: 100)
+    "large-v3-turbo": dict(n_vocab=51866, n_text_ctx=448, n_state=1280, n_head=20, n_layer=4),
 }
+TEXT_DIMS["large"] = TEXT_DIMS["large-v3"]
+TEXT_DIMS["turbo"] = TEXT_DIMS["large-v3-turbo"]
 
 
 def decoder_tensor_order(dims):
