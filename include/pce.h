@@ -265,7 +265,7 @@ int pce_whisper_encode_run(pce_ctx *ctx);
  * (rows_per_clip rows each, key axis padded to vt_sp): out[(clip N + n) vt_sp + t].  N % 256 == 0, K % 64 == 0. */
 int pce_selftest_gemm(pce_ctx *ctx, const uint16_t *A, const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, int32_t epilogue,
                       int32_t rows_per_clip, int32_t vt_sp, uint16_t *out);
-/* Self-test of the attention kernel (64-wide heads; csrc/pce_whisper.hip k_attention_lean) on host arrays of bf16 bit patterns: clips x
+/* Self-test of the attention kernel (64-wide heads; csrc/pce_whisper_impl.inc k_attention_lean16) on host arrays of bf16 bit patterns: clips x
  * heads independent problems, q [clips][q_len][heads * 64], k and v [clips][k_len][heads * 64], out like q; softmax(q k^T / 8) v with the
  * causal mask when causal != 0.  mode 0: the kernel as the engine runs it (fixed softmax reference, exact fallback), 1: its exact
  * path only.  *fell_back (may be NULL): number of workgroups that had to take the exact path (mode 0). */
@@ -295,7 +295,7 @@ int pce_whisper_encode_fetch(pce_ctx *ctx, int32_t clip, float *out /* [1500][n_
  *              mlp_ln.w,b  mlp.0.w,b  mlp.2.w,b
  *   ln.w,b */
 typedef struct pce_whisper_text_dims {
-    int32_t n_vocab /* <= 52224 */, n_text_ctx /* <= 448 */, n_state, n_head, n_layer;
+    int32_t n_vocab /* <= 52224 */, n_text_ctx /* <= 448 */, n_state, n_head /* <= 32: more is PCE_E_LIMIT */, n_layer;
 } pce_whisper_text_dims;
 int pce_whisper_decoder_load(pce_ctx *ctx, const pce_whisper_text_dims *dims, const float *weights, int64_t n_floats);
 /* tokens: concatenated per clip (token_offsets[n_clips+1]); num_frames: mel frames of real audio per clip;

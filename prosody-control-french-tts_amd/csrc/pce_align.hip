@@ -254,7 +254,6 @@ int pce_dtw(pce_ctx *c, const double *x, int32_t n_rows, int32_t n_cols, int32_t
     PCE_HIP(c, hipMemcpyAsync(path_len, dpl.p, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
-    dx.release(); dtr.release(); dpi.release(); dpj.release(); dpl.release();
     return PCE_OK;
 }
 
@@ -306,7 +305,6 @@ int pce_nw_align(pce_ctx *c, const int32_t *a_ids, const int64_t *a_off, const i
     PCE_HIP(c, hipMemcpyAsync(out_len, dol.p, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
-    for (DevBuf *x : {&da, &db, &dao, &dbo, &dtr, &dtro, &doi, &doj, &doo, &dol, &drw, &drwo}) x->release();
     return PCE_OK;
 }
 
@@ -345,7 +343,6 @@ int pce_levenshtein(pce_ctx *c, const uint32_t *a_chars, const int64_t *a_off, c
     PCE_HIP(c, hipMemcpyAsync(out_dist, dout.p, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
-    for (DevBuf *x : {&da, &db, &dao, &dbo, &dro, &drows, &dout}) x->release();
     return PCE_OK;
 }
 

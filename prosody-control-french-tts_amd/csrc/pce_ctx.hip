@@ -121,10 +121,7 @@ pce_ctx *pce_create(int device, void *stream, char *err, size_t errlen)
     c->gemm_flat = !(getenv("PCE_GEMM_FLAT") && atoi(getenv("PCE_GEMM_FLAT")) == 0);
     c->en_cpb = getenv("PCE_EN_CPB") ? atoi(getenv("PCE_EN_CPB")) : 0;
     c->gemm_skinny = !(getenv("PCE_GEMM_SKINNY") && atoi(getenv("PCE_GEMM_SKINNY")) == 0);
-    // attention on v_mfma_f32_16x16x32 (round 5, default: 30.5 -> 29.6 ms per C3 step on one box, profiles/r05); PCE_ATTN_M16=0: the 32x32x16 kernel
-    c->attn_m16 = !(getenv("PCE_ATTN_M16") && atoi(getenv("PCE_ATTN_M16")) == 0);
     c->self_rows = !(getenv("PCE_SELF_ROWS") && atoi(getenv("PCE_SELF_ROWS")) == 0);
-    c->attn_nt = !(getenv("PCE_ATTN_NT") && atoi(getenv("PCE_ATTN_NT")) == 0);
     c->xattn_absorb = !(getenv("PCE_XATTN_ABSORB") && atoi(getenv("PCE_XATTN_ABSORB")) == 0);
     {
         const char *ops = getenv("PCE_WHISPER_OPERANDS");
@@ -169,15 +166,6 @@ void pce_destroy(pce_ctx *c)
         if (sd.join) (void)hipEventDestroy(sd.join);
         if (sd.s) (void)hipStreamDestroy(sd.s);
     }
-    DevBuf *bufs[] = {&c->pcm_own, &c->d_clip_off, &c->en_work, &c->en_out,
-                      &c->lu_meta, &c->lu_chunks, &c->lu_blocks, &c->lu_pow, &c->lu_state_end, &c->lu_state_init,
-                      &c->lu_energy, &c->lu_zbuf, &c->lu_out, &c->lu_en_work, &c->lu_en_acc,
-                      &c->pi_meta, &c->pi_window, &c->pi_windowR, &c->pi_work, &c->pi_cand, &c->pi_gpeak,
-                      &c->pi_psi, &c->pi_f0, &c->pi_strength, &c->pi_summary, &c->pi_peakwork, &c->pi_acc, &c->pi_rr, &c->pi_items, &c->pi_tw, &c->pi_dl, &c->pi_runs, &c->pi_fslice, &c->pi_blob,
-                      &c->st_out, &c->st_max, &c->st_off, &c->st_window, &c->st_twiddle, &c->st_work, &c->st_stage,
-                      &c->fr_doff, &c->fr_sum, &c->fr_cnt,
-                      &c->py_doff, &c->py_tab, &c->py_hdr, &c->py_bin, &c->py_lp, &c->py_ptr, &c->py_states};
-    for (auto b : bufs) b->release();
     for (auto &st : c->stat) {
         if (st.host) (void)hipHostFree(st.host);
         if (st.ev) (void)hipEventDestroy(st.ev);

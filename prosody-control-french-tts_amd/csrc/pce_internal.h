@@ -18,10 +18,18 @@
 #define PCE_NO_PK_F32                                    /* (the host pass of the same source: an x86 target knows no such feature) */
 #endif
 
-// Growable device buffer owned by the context.
+// Growable device buffer; frees itself.  Never give one static storage duration: its destructor would call hipFree after the runtime has shut down.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf &operator=(DevBuf &&o) noexcept {         // frees what this one held, takes o's allocation
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     hipError_t reserve(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
         if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
@@ -62,13 +70,8 @@ struct pce_ctx {
     bool no_side = false;                // PCE_NO_AUX at pce_create: everything on `stream`
     bool generic_median = false;         // PCE_ALIGN_GENERIC_MEDIAN at pce_create: the insertion-sort median filter for every width
     bool pitch_refine_praat = false;     // PCE_PITCH_REFINE=praat at pce_create: the candidate refinement replays NUMminimize_brent's own iterates (round 1 / 2 behaviour)
-    // dynamic-LDS opt-ins (hipFuncSetAttribute) done on this context's device, per operand-type build: the implementation file is compiled
-    // twice, so every kernel below exists as two distinct functions
-    bool attn1w_attr[2] = {false, false};
-    unsigned xattn_attr[2] = {0u, 0u};    // k_xattn_absorbed<d, slots>: bit per instantiation whose dynamic LDS size has been set (per operand build)
-    bool gemm_flat_attr[2][4] = {{false, false, false, false}, {false, false, false, false}};   // k_gemm_flat<EPI>
     bool gemm_few_rows = false;          // set by the incremental decoding step around its launches: k_gemm_skinny is eligible
-    bool gemm_skinny = true, gemm_skinny_attr[2][4] = {{false, false, false, false}, {false, false, false, false}};   // PCE_GEMM_SKINNY=0 at pce_create: few-row launches stay on the 128 x 128 kernel
+    bool gemm_skinny = true;             // PCE_GEMM_SKINNY=0 at pce_create: few-row launches stay on the 128 x 128 kernel
     bool gemm_flat = true;               // PCE_GEMM_FLAT=0 at pce_create: the encoder's projections stay on the 128 x 128 / 128 x 256 tile kernels
     bool stft_two_fft = false;           // PCE_STFT_TWO_FFT at pce_create: traffic-minimal STFT-dB (the FFT runs twice)
     std::string err;
@@ -106,8 +109,6 @@ struct pce_ctx {
     int pi_np2 = 1;
     bool xattn_absorb = true;       // incremental decoding steps: cross-attention from the encoder output (pce_xattn.inc); PCE_XATTN_ABSORB=0: from the K / V^T cache
     bool self_rows = true;          // incremental steps' self-attention on row-major K / V caches (k_self_attn1w); PCE_SELF_ROWS=0: k_cross_attn1w on K rows + V^T
-    bool attn_nt = true;            // single-query-block attention launches stream K / V^T with the non-temporal policy (PCE_ATTN_NT=0: default policy)
-    bool attn_m16 = false;          // attention on v_mfma_f32_16x16x32 (k_attention_lean16) instead of 32x32x16
     bool pi_long_slices = false;    // some slice has more frames than the in-LDS median sort holds (k_pitch_median_long takes those)
     SliceCache pi_cache;
     pce_pitch_params pi_params;

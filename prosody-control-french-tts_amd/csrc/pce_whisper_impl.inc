@@ -71,22 +71,18 @@ namespace {
 typedef PCE_OP_T op_t;
 typedef __attribute__((ext_vector_type(8))) op_t opx8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-// the two MFMA shapes of this file, on whichever 16-bit type the build computes in (same issue rate: 16 / 32 cycles)
+// the MFMA of this file's attention and GEMM kernels, on whichever 16-bit type the build computes in
 template <class T> struct MfmaOf;
 template <> struct MfmaOf<__bf16> {
     typedef __attribute__((ext_vector_type(8))) __bf16 v8;
     static __device__ __forceinline__ f32x4 m16(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x16 m32(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 };
 template <> struct MfmaOf<_Float16> {
     typedef __attribute__((ext_vector_type(8))) _Float16 v8;
     static __device__ __forceinline__ f32x4 m16(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ f32x16 m32(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 };
 __device__ __forceinline__ f32x4 mfma16(opx8 a, opx8 b, f32x4 c) { return MfmaOf<op_t>::m16(a, b, c); }
-__device__ __forceinline__ f32x16 mfma32(opx8 a, opx8 b, f32x16 c) { return MfmaOf<op_t>::m32(a, b, c); }
 
 constexpr int W_NFFT = 400, W_HOP = 160, W_BINS = 201, W_FRAMES = 3000, W_SAMPLES = 480000;
 constexpr int W_CTX = 1500;
@@ -566,6 +562,7 @@ __global__ __launch_bounds__(G_THREADS, G_STAGES == 2 ? 4 : 2) void k_gemm_bf16(
 // ---------------------------------------------------------------------------
 constexpr int S_BM = 64, S_BN = 32, S_KC = 256, S_THREADS = 256, S_NBUF = 3;
 constexpr int S_BUF = (S_BM + S_BN) * S_KC;                       // elements per buffer (48 KB)
+constexpr int S_LDS = S_NBUF * S_BUF * 2;                          // dynamic LDS of a launch (bytes)
 __device__ __forceinline__ int swz512(int row, int chunk) { return chunk ^ (row & 15); }     // 512-byte rows: 32 chunks, the low four bits swizzled
 template <int EPI>
 __global__ __launch_bounds__(S_THREADS) void k_gemm_skinny(const op_t *__restrict__ A, int64_t lda, const op_t *__restrict__ B, int M, int N, int K,
@@ -879,16 +876,10 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *
 #include "pce_gemm256.inc"
 
 // ---------------------------------------------------------------------------
-// attention forward, transposed formulation on v_mfma_f32_32x32x16_bf16.
+// attention forward, transposed formulation (attn_block16 below).
 //   S^T = K Q^T   (keys on the accumulator rows, queries on its columns = lanes)
-//   O^T = V^T P^T (P^T is consumed straight out of the S^T accumulator registers as the B operand:
-//                  a 32x32 result has its column on the lane and its rows in the 16 registers, which is
-//                  exactly a B fragment summed over the row index; no LDS round trip, no cross-lane
-//                  softmax reductions except one exchange between the two lane halves)
-// The S^T accumulator row rho of lane-half h, register 4g+i is rho = i + 8g + 4h.  The k-step s of the
-// second product reads registers 8s..8s+7, i.e. rows 16s + 8a + 4h + b (j = 4a + b).  Softmax does not
-// care about the order of the keys inside a tile, so lane r loads K row pi(r) (pi swaps bits 2 and 3):
-// then slot (h, j) of k-step s is key 16s + 8h + j and the V^T fragment is one contiguous 16-byte read.
+//   O^T = V^T P^T (P^T is consumed straight out of the S^T accumulator registers as the B operand: no LDS round trip, no
+//                  cross-lane softmax reductions except the exchanges between lane groups)
 // One workgroup = 4 waves x 32 queries of one (clip, head); K [64 keys][64 d] and V^T [64 d][64 keys]
 // tiles stream through LDS by DMA (global_load_lds), double buffered, XOR-swizzled like the GEMM operands.
 // ---------------------------------------------------------------------------
@@ -901,11 +892,11 @@ struct AttnArgs {
     const int *q_row0, *q_len, *k_row0, *k_len;   // per clip
     op_t *out; int64_t out_ld;              // out + (q_row0[c] + i) * out_ld + head * 64
     int causal;                             // key j visible to query i only if j <= i
-    int *fell_back;                         // (self-test only, else null) counts the workgroups of k_attention_lean that re-ran on the exact path
+    int *fell_back;                         // (self-test only, else null) counts the workgroups of k_attention_lean16 that re-ran on the exact path
 };
 
 // ---------------------------------------------------------------------------
-// k_attention_lean: the same product with less than half of k_attention's vector instructions per tile.  Per 64-key tile a wave issues
+// The tile loop (round 4, first on v_mfma_f32_32x32x16 as k_attention_lean): less than half of k_attention's vector instructions per tile.  Per 64-key tile a wave issues
 // 16 MFMAs and, in k_attention, about 200 VALU instructions; MFMAs and VALU instructions of all waves of a SIMD share one issue port
 // (v_fma 4 cycles, v_exp 8, an MFMA 8 of its 32: MI355X_MICROARCH.md "vector-instruction ISSUE cost"), and with three waves per SIMD the
 // PMC counters put k_attention's issue port at 96 % busy (SQ_ACTIVE_INST_ANY / SQ_WAVE_CYCLES = 0.32 per wave): it is instruction-count
@@ -923,178 +914,6 @@ struct AttnArgs {
 // interleaved with this tile's exponentials inside one wave (two score sets in registers, 4 slots, two workgroups per CU): 2.59 ms with or
 // without the instruction diet -- waves then wait on LDS-DMA / barriers (SQ_WAIT_ANY 0.41) with too few partners to cover them; the same
 // with eight waves per workgroup (half the DMA instructions per wave): 3.0 ms.
-// ---------------------------------------------------------------------------
-template <bool EXACT>
-__device__ __forceinline__ bool attn_block(const AttnArgs &A, op_t *smem, int bx, int head, int clip)
-{
-    constexpr int NS = 3, DPW = 4;                               // ring slots; DMA wave-instructions per wave and tile (16 pieces of 1 KB, 4 waves)
-    const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const int Sq = A.q_len[clip], Sk = A.k_len[clip];
-    const int q0 = bx * AT_QB + wv * 32;
-    const op_t *qbase = A.q + (int64_t)A.q_row0[clip] * A.q_ld + head * 64;
-    const op_t *kbase = A.k + (int64_t)A.k_row0[clip] * A.k_ld + head * 64;
-    const op_t *vtbase = A.vt + (int64_t)clip * A.vt_clip + (int64_t)head * 64 * A.vt_sp;
-    const int kld = (int)A.k_ld, vsp = A.vt_sp;
-    const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(const_cast<op_t *>(kbase), 0, ((Sk - 1) * kld + 64) * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(const_cast<op_t *>(vtbase), 0, 64 * vsp * 2, 0x00020000);
-    // a tile = 8 pieces of K (8 keys x 128 B each) + 8 pieces of V^T (8 rows of d); wave w moves pieces w and w + 4 of both
-    int voffK[2], voffV[2];
-#pragma unroll
-    for (int i = 0; i < 2; i++) {
-        const int row = (wv + 4 * i) * 8 + (lane >> 3), c8 = swz_chunk(row, lane & 7) * 8;
-        voffK[i] = (row * kld + c8) * 2; voffV[i] = (row * vsp + c8) * 2;
-    }
-    auto stage = [&](int t) {                                    // tile t -> slot t % NS
-        op_t *sK = smem + (t % NS) * (2 * 64 * 64), *sV = sK + 64 * 64;
-        const int key0 = t * 64;
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, (__attribute__((address_space(3))) void *)(sK + (wv + 4 * i) * 8 * 64), 16, voffK[i], key0 * kld * 2, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (__attribute__((address_space(3))) void *)(sV + (wv + 4 * i) * 8 * 64), 16, voffV[i], key0 * 2, 0, 0);
-        }
-    };
-    opx8 qf[4];
-    {
-        int qr = q0 + r; if (qr >= Sq) qr = Sq - 1;
-        const op_t *qp = qbase + (int64_t)qr * A.q_ld;
-#pragma unroll
-        for (int s4 = 0; s4 < 4; s4++) qf[s4] = *reinterpret_cast<const opx8 *>(qp + 16 * s4 + 8 * h);
-    }
-    auto fzero = [] { f32x16 z;
-#pragma unroll
-        for (int e = 0; e < 16; e++) z[e] = 0.f;
-        return z; };
-    opx8 ones;                                                 // A fragment "row 0 = ones, rows 1..31 = 0" of the row-sum MFMA
-#pragma unroll
-    for (int j = 0; j < 8; j++) ones[j] = (op_t)(r == 0 ? 1.0f : 0.0f);
-    f32x16 o[2], osum = fzero();
-    o[0] = fzero(); o[1] = fzero();
-    float m_run = -1e30f, l_run = 0.f;
-    const float sl2 = 0.125f * 1.4426950408889634f;               // softmax scale * log2(e): exp(x) = exp2(x log2 e)
-    const int pr = (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1);   // pi(r): swap bits 2 and 3 (see k_attention)
-    int k_need = Sk;
-    if (A.causal) k_need = min(Sk, bx * AT_QB + AT_QB);
-    const int nt = (k_need + 63) / 64;
-    const int my_q = q0 + r;
-    int kaddr[2][4], vaddr[2][4];                                // LDS addresses of this lane's fragments inside a slot (elements)
-#pragma unroll
-    for (int u = 0; u < 2; u++)
-#pragma unroll
-        for (int s4 = 0; s4 < 4; s4++) {
-            const int row = u * 32 + pr;
-            kaddr[u][s4] = row * 64 + swz_chunk(row, 2 * s4 + h) * 8;
-        }
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-#pragma unroll
-        for (int c = 0; c < 4; c++) {                             // c = 2 u + s2: keys u*32 + 16 s2 + 8 h .. + 7
-            const int row = t * 32 + r;
-            vaddr[t][c] = 64 * 64 + row * 64 + swz_chunk(row, 2 * c + h) * 8;
-        }
-    stage(0);
-    if (nt > 1) stage(1);
-    for (int kt = 0; kt < nt; kt++) {
-        // tile kt landed (each wave issues DPW instructions per tile, in tile order); everyone is done with tile kt-1, whose slot tile kt+2 takes
-        if (kt + 1 < nt) __builtin_amdgcn_s_waitcnt(0x0F70 | DPW); else __builtin_amdgcn_s_waitcnt(0x0F70 | 0);
-        __builtin_amdgcn_s_barrier();
-        if (kt + 2 < nt) stage(kt + 2);
-        const op_t *sC = smem + (kt % NS) * (2 * 64 * 64);
-        f32x16 sc[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++)
-#pragma unroll
-            for (int s4 = 0; s4 < 4; s4++)
-                sc[u] = mfma32(*reinterpret_cast<const opx8 *>(&sC[kaddr[u][s4]]), qf[s4], s4 == 0 ? fzero() : sc[u]);
-        // edge tiles (last keys of the clip, the causal diagonal): invisible scores become -1e30 (unscaled), and exp2(-1e30 c - m) = 0 for
-        // any finite m; tile 0 always holds a visible key for every query, so m is finite from then on
-        if ((kt * 64 + 63 >= Sk) || (A.causal && kt * 64 + 63 > q0)) {                          // wave-uniform
-#pragma unroll
-            for (int u = 0; u < 2; u++)
-#pragma unroll
-                for (int e = 0; e < 16; e++) {
-                    const int rho = (e & 3) + 8 * (e >> 2) + 4 * h;
-                    const int key = kt * 64 + u * 32 + ((rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1));
-                    const bool vis = key < Sk && (!A.causal || key <= my_q);
-                    sc[u][e] = vis ? sc[u][e] : -1e30f;
-                }
-        }
-        if (EXACT || kt == 0) {
-            float m0 = sc[0][0], m1 = sc[0][1], m2 = sc[1][0], m3 = sc[1][1];
-#pragma unroll
-            for (int e = 2; e < 16; e += 2) { m0 = fmaxf(m0, sc[0][e]); m1 = fmaxf(m1, sc[0][e + 1]); m2 = fmaxf(m2, sc[1][e]); m3 = fmaxf(m3, sc[1][e + 1]); }
-            float mx = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-            mx = mx > -1e29f ? mx * sl2 : -1e30f;
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);
-            if (__builtin_amdgcn_ballot_w64(m_new > m_run) != 0) {
-                const float corr = __builtin_amdgcn_exp2f(m_run - m_new);          // (tile 0: everything it scales is still zero)
-                l_run *= corr;
-#pragma unroll
-                for (int t = 0; t < 2; t++)
-#pragma unroll
-                    for (int e = 0; e < 16; e++) o[t][e] *= corr;
-                m_run = m_new;
-            }
-            // fp16 operands: P = 2^(s c - m) must stay below 65 504 = 2^16 (bf16 has fp32's exponent range).  The fixed reference sits
-            // 4 octaves ABOVE the first tile's maximum: a later score may exceed that maximum by 2^20 (13.9 nats) before the row overflows
-            // (and the workgroup re-runs exactly), at the price of flushing weights below 2^-20 of the reference to zero
-            // (<= 1 500 keys x 1e-6: 0.15 % of a row in the worst case; the exact path, like the reference, cuts at 2^-24).
-            if (!EXACT && std::is_same<op_t, _Float16>::value) m_run += 4.0f;
-        }
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-        for (int u = 0; u < 2; u++)
-#pragma unroll
-            for (int e = 0; e < 16; e += 2) {
-                const float p0 = __builtin_amdgcn_exp2f(fmaf(sc[u][e], sl2, -m_run)), p1 = __builtin_amdgcn_exp2f(fmaf(sc[u][e + 1], sl2, -m_run));
-                sc[u][e] = p0; sc[u][e + 1] = p1;
-                if (EXACT) { if (u == 0) { s0 += p0; s1 += p1; } else { s2 += p0; s3 += p1; } }
-            }
-        if (EXACT) {
-            float sum = (s0 + s1) + (s2 + s3);
-            sum += __shfl_xor(sum, 32, 64);
-            l_run += sum;
-        }
-        // O^T += V^T P^T (and the row sums): k-step c = 2 u + s2 covers keys u*32 + 16 s2 .. +15 (in pi order); B = registers 8 s2 .. 8 s2 + 7
-        opx8 vf[2][4];
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) vf[t][c] = *reinterpret_cast<const opx8 *>(&sC[vaddr[t][c]]);
-#pragma unroll
-        for (int c = 0; c < 4; c++) {
-            opx8 pf;
-#pragma unroll
-            for (int j = 0; j < 8; j++) pf[j] = (op_t)sc[c >> 1][8 * (c & 1) + j];
-#pragma unroll
-            for (int t = 0; t < 2; t++) o[t] = mfma32(vf[t][c], pf, o[t]);
-            if (!EXACT) osum = mfma32(ones, pf, osum);
-        }
-    }
-    if (!EXACT) l_run = __shfl(osum[0], r, 64);                  // row 0 of the row-sum product sits in register 0 of the lower lane half
-    // (the accumulators are sums of p * v, up to l_run * max|v|: a row sum near FLT_MAX can pass a bare finiteness test while O has
-    // already overflowed, so the fast path keeps eight decades of headroom; any finite reference is equally exact, the bound costs nothing)
-    const bool ok = EXACT || (l_run > 0.f && l_run < 1.0e30f) || my_q >= Sq;
-    if (!EXACT && __syncthreads_or(!ok)) return false;           // some row overflowed its fixed reference: the workgroup runs again, exactly
-    // O^T[d][q]: this lane owns query q0 + r; d = 32 t + (e & 3) + 8 (e >> 2) + 4 h -> runs of 4 consecutive d
-    if (my_q < Sq) {
-        const float inv = 1.0f / l_run;
-        op_t *op = A.out + ((int64_t)A.q_row0[clip] + my_q) * A.out_ld + head * 64;
-        typedef __attribute__((ext_vector_type(4))) op_t opx4;
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                opx4 v4;
-#pragma unroll
-                for (int i = 0; i < 4; i++) v4[i] = (op_t)(o[t][4 * g + i] * inv);
-                *reinterpret_cast<opx4 *>(op + 32 * t + 8 * g + 4 * h) = v4;
-            }
-    }
-    return true;
-}
-
 // ---------------------------------------------------------------------------
 // attn_block16 (round 5): the same workgroup (4 waves x 32 queries, 64-key tiles, the same ring, the same staging instructions) on
 // v_mfma_f32_16x16x32.  Why: (a) the row-sum products against the "row 0 = ones" fragment waste 15 of 16 rows instead of 31 of 32 -- 4
@@ -1230,7 +1049,10 @@ __device__ __forceinline__ bool attn_block16(const AttnArgs &A, op_t *smem, int 
                     m_run[qb] = mx[qb];
                 }
             }
-            // fp16 operands: the fixed reference sits 4 octaves above the first tile's maximum (see attn_block)
+            // fp16 operands: P = 2^(s c - m) must stay below 65 504 = 2^16 (bf16 has fp32's exponent range).  The fixed reference sits
+            // 4 octaves ABOVE the first tile's maximum: a later score may exceed that maximum by 2^20 (13.9 nats) before the row overflows
+            // (and the workgroup re-runs exactly), at the price of flushing weights below 2^-20 of the reference to zero
+            // (<= 1 500 keys x 1e-6: 0.15 % of a row in the worst case; the exact path, like the reference, cuts at 2^-24).
             if (!EXACT && std::is_same<op_t, _Float16>::value) { m_run[0] += 4.0f; m_run[1] += 4.0f; }
         }
         float rs[2] = {0.f, 0.f};
@@ -1295,24 +1117,9 @@ __device__ __forceinline__ bool attn_block16(const AttnArgs &A, op_t *smem, int 
     return true;
 }
 
-__global__ __launch_bounds__(256, 3) void k_attention_lean(AttnArgs A, int force_exact /* self-test only */)
-{
-    __shared__ __attribute__((aligned(1024))) op_t smem[3 * 2 * 64 * 64];               // [slot][K | V^T][64][64] = 48 KiB
-    // Workgroups go to the 8 XCDs round robin by linear id, and the query blocks of one (clip, head) share its K / V^T through L2: give every XCD
-    // a CONTIGUOUS range of (clip, head, query block) triples, so that the blocks that share keys meet in one L2 instead of eight
-    const unsigned nx = gridDim.x, ny = gridDim.y, total = nx * ny * gridDim.z;
-    const unsigned lin = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), xcd = lin & 7u, per = total >> 3, rem = total & 7u;
-    const unsigned logical = xcd * per + (xcd < rem ? xcd : rem) + (lin >> 3);
-    const int bx = (int)(logical % nx), head = (int)((logical / nx) % ny), clip = (int)(logical / (nx * ny));
-    if (bx * AT_QB >= A.q_len[clip]) return;
-    if (!force_exact && attn_block<false>(A, smem, bx, head, clip)) return;
-    if (!force_exact && A.fell_back && threadIdx.x == 0) atomicAdd(A.fell_back, 1);
-    __syncthreads();
-    attn_block<true>(A, smem, bx, head, clip);
-}
-
-
-// the same launch on attn_block16 (selected per context: pce_ctx::attn_m16)
+// Workgroups go to the 8 XCDs round robin by linear id, and the query blocks of one (clip, head) share its K / V^T through L2: every XCD gets a
+// CONTIGUOUS range of (clip, head, query block) triples, so that the blocks that share keys meet in one L2 instead of eight.
+// NT: a launch with one query block per (clip, head) (see attn_block16's staging).
 template <bool NT>
 __global__ __launch_bounds__(256, 3) void k_attention_lean16(AttnArgs A, int force_exact /* self-test only */)
 {
@@ -1332,9 +1139,8 @@ static void launch_attention(pce_ctx *c, dim3 grid, const AttnArgs &a, double fl
 {
     // flops > 0: a launch the profiler brackets on its own (the encoder's); the decoder's small launches stay inside their composite entry
     KernelTimer kt(c, PCE_K_ATTENTION_LEAN, nullptr, flops);
-    if (c->attn_m16 && grid.x == 1 && c->attn_nt) hipLaunchKernelGGL(k_attention_lean16<true>, grid, dim3(256), 0, c->stream, a, 0);
-    else if (c->attn_m16) hipLaunchKernelGGL(k_attention_lean16<false>, grid, dim3(256), 0, c->stream, a, 0);
-    else hipLaunchKernelGGL(k_attention_lean, grid, dim3(256), 0, c->stream, a, 0);
+    if (grid.x == 1) hipLaunchKernelGGL(k_attention_lean16<true>, grid, dim3(256), 0, c->stream, a, 0);
+    else hipLaunchKernelGGL(k_attention_lean16<false>, grid, dim3(256), 0, c->stream, a, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -1360,23 +1166,13 @@ __global__ void k_gather_last(const float *__restrict__ resid, const int *__rest
 }
 
 // self-attention cache maintenance.  k_cache_k: K rows of a prefix run, [clip * T_pad + t][2d] (second half) -> cache
-// [clip][T_cap][d]; k_append_kv: the new position of an incremental step, compact [clip][3d] (q | k | v) -> K row and V^T column.
+// [clip][T_cap][d] (an incremental step's attention kernel appends its new position itself).
 __global__ void k_cache_k(const op_t *__restrict__ qk, int T_pad, const int *__restrict__ t_len, int d, int T_cap, int n, op_t *__restrict__ ck)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)n * T_pad * d) return;
     const int col = (int)(i % d); const int64_t r = i / d; const int t = (int)(r % T_pad), clip = (int)(r / T_pad);
     if (t < t_len[clip]) ck[((int64_t)clip * T_cap + t) * d + col] = qk[r * 2 * d + d + col];
-}
-__global__ void k_append_kv(const op_t *__restrict__ qkv, const int *__restrict__ pos_of, int d, int T_cap, int sp, int n, op_t *__restrict__ ck,
-                            op_t *__restrict__ cvt)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)n * d) return;
-    const int clip = (int)(i / d), col = (int)(i - (int64_t)clip * d);
-    const int pos = pos_of[clip];
-    ck[((int64_t)clip * T_cap + pos) * d + col] = qkv[(int64_t)clip * 3 * d + d + col];
-    cvt[((int64_t)clip * d + col) * sp + pos] = qkv[(int64_t)clip * 3 * d + 2 * d + col];
 }
 // V rows of a prefix run for the incremental steps' self-attention: V^T image [clip][d][sp] (written by the QKV epilogue) -> row-major [clip][T_cap][d]
 __global__ void k_cache_v_rows(const op_t *__restrict__ cvt, const int *__restrict__ t_len, int d, int T_cap, int sp, int n, op_t *__restrict__ cv)
@@ -1541,7 +1337,7 @@ __global__ __launch_bounds__(256) void k_step_advance(int n, int T_cap, int eot,
 //   phase 1: scores.  8 lanes per key row (16 B = 8 dims each: a wave-instruction covers eight whole 128-byte lines), eight rows per lane
 //            in flight, 8-lane sums by DPP -> fp32 scores in LDS
 //   phase 2: softmax (fp32, max-subtracted) in LDS
-//   phase 3: O[d] = sum_t p[t] V^T[d][t]: a wave streams one V^T row as 1 KB pieces (lane = 8 consecutive keys, p in registers), 16 rows per wave
+//   phase 3: O[d] = sum_t p[t] V^T[d][t]: the wave streams the V^T rows of its head as 1 KB pieces (lane = 8 consecutive keys, p in registers)
 // `skip[clip]` != 0: the sequence has ended, its output is never used (the filters return end-of-text for it): no bytes are read.
 struct Attn1Args {
     const op_t *q; int64_t q_ld;              // query of clip c: q + c * q_ld + head * 64
@@ -1550,104 +1346,12 @@ struct Attn1Args {
     const int *k_row0, *k_len;                // per clip; k_len <= 1536
     const int *skip;                          // per clip or null
     op_t *out; int64_t out_ld;                // out + c * out_ld + head * 64
-    // k_cross_attn1w only: when app_pos is set, the wave of (clip, head) first writes the new position's key / value slice (app_k / app_v
-    // + c * app_ld + head * 64) into K row app_pos[c] and V^T column app_pos[c] (k_append_kv's job, without its launch), then attends
+    // when app_pos is set, the wave of (clip, head) first writes the new position's key / value slice (app_k / app_v + c * app_ld + head * 64)
+    // into K row app_pos[c] and V^T column app_pos[c], then attends
     const op_t *app_k, *app_v; int64_t app_ld; const int *app_pos;
-    int heads;                                // k_cross_attn1w: heads in all (the grid's y counts head groups)
+    int heads;                                // heads in all (the grid's y counts head groups)
 };
-// 128 threads: 16 workgroups fit a CU, so the 3 072 (clip, head) pairs of 256 clips at Whisper-small size are ONE resident round
-// (with 256 threads 2 048 run at a time and the second round leaves half the chip idle)
-constexpr int A1_T = 128, A1_W = A1_T / 64;
-__global__ __launch_bounds__(A1_T) void k_cross_attn1(Attn1Args A)
-{
-    __shared__ float sp[1536];
-    __shared__ float red[2 * A1_W];
-    __shared__ float so[64];
-    const int head = blockIdx.x, clip = blockIdx.y;
-    if (A.skip && A.skip[clip]) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int Sk = A.k_len[clip];
-    const int g = lane >> 3, ch = lane & 7;
-    float qf[8];
-    {
-        const opx8 qv = *reinterpret_cast<const opx8 *>(A.q + (int64_t)clip * A.q_ld + head * 64 + ch * 8);
-#pragma unroll
-        for (int e = 0; e < 8; e++) qf[e] = (float)qv[e] * 0.125f;
-    }
-    const op_t *kb = A.k + (int64_t)A.k_row0[clip] * A.k_ld + head * 64 + ch * 8;
-    constexpr int U = 8;
-    for (int base = wv * 8; base < Sk; base += 8 * A1_W * U) {
-        opx8 kv[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int r = base + u * 8 * A1_W + g;
-            kv[u] = __builtin_nontemporal_load(reinterpret_cast<const opx8 *>(kb + (int64_t)(r < Sk ? r : Sk - 1) * A.k_ld));      // read once per step: streamed
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            float d = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; e++) d = fmaf((float)kv[u][e], qf[e], d);
-            d += __shfl_xor(d, 1, 64); d += __shfl_xor(d, 2, 64); d += __shfl_xor(d, 4, 64);
-            const int r = base + u * 8 * A1_W + g;
-            if (ch == 0 && r < Sk) sp[r] = d;
-        }
-    }
-    __syncthreads();
-    float m = -3.0e38f;
-    for (int t = tid; t < Sk; t += A1_T) m = fmaxf(m, sp[t]);
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if (lane == 0) red[wv] = m;
-    __syncthreads();
-    m = red[0];
-#pragma unroll
-    for (int u = 1; u < A1_W; u++) m = fmaxf(m, red[u]);
-    float sum = 0.f;
-    const int Sp = (Sk + 511) & ~511;                            // p is read in 512-key pieces: zero beyond the last key
-    for (int t = tid; t < Sp; t += A1_T) {
-        const float pv = t < Sk ? __expf(sp[t] - m) : 0.f;
-        sp[t] = pv; sum += pv;
-    }
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if (lane == 0) red[A1_W + wv] = sum;
-    __syncthreads();
-    float tot = red[A1_W];
-#pragma unroll
-    for (int u = 1; u < A1_W; u++) tot += red[A1_W + u];
-    const float inv = 1.0f / tot;
-    const int np = Sp >> 9;                                      // 1..3 pieces
-    float pr[3][8];
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) pr[j][e] = j < np ? sp[j * 512 + lane * 8 + e] : 0.f;
-    constexpr int RW = 64 / A1_W;                                // V^T rows (output dims) per wave
-    const op_t *vb = A.vt + (int64_t)clip * A.vt_clip + (int64_t)(head * 64 + wv * RW) * A.vt_sp + lane * 8;
-#pragma unroll 2
-    for (int r4 = 0; r4 < RW; r4 += 4) {
-        opx8 vv[4][3];
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int j = 0; j < 3; j++)
-                if (j < np) vv[r][j] = __builtin_nontemporal_load(reinterpret_cast<const opx8 *>(vb + (int64_t)(r4 + r) * A.vt_sp + j * 512));
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            float a = 0.f;
-#pragma unroll
-            for (int j = 0; j < 3; j++)
-                if (j < np)
-#pragma unroll
-                    for (int e = 0; e < 8; e++) a = fmaf(pr[j][e], (float)vv[r][j][e], a);
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-            if (lane == 0) so[wv * RW + r4 + r] = a * inv;
-        }
-    }
-    __syncthreads();
-    if (tid < 64) A.out[(int64_t)clip * A.out_ld + head * 64 + tid] = (op_t)so[tid];
-}
-
-// k_cross_attn1w: the same computation with ONE WAVE per (clip, head) and one workgroup per clip (wave = head).  Why: a key row is the
+// k_cross_attn1w: ONE WAVE per (clip, head) and one workgroup per clip (wave = head).  Why: a key row is the
 // 128-byte slices of all heads side by side (1 536 B at Whisper-small size); with a workgroup per (clip, head) the twelve slices of a row
 // are fetched by twelve workgroups on different XCDs at different times -- twelve visits to the same DRAM page; here the waves of a
 // workgroup walk the rows together.  Each wave keeps its scores in its own LDS slice: no workgroup barrier anywhere.
@@ -1666,7 +1370,7 @@ __global__ __launch_bounds__(1024) void k_cross_attn1w(Attn1Args A)
     // Appending (the self-attention of an incremental step): the new position's key and value go to the cache with plain stores that
     // nothing in this launch reads back -- the wave attends to the new key from registers (its score from the key slice it has just
     // loaded, its value added after the sums over the cached keys), so there is no store -> wait -> load chain (that chain cost as much
-    // as the k_append_kv launch it replaced: 7 us).  The V^T cache only ever holds finite values (zeroed at allocation).
+    // as the separate append launch it replaced: 7 us).  The V^T cache only ever holds finite values (zeroed at allocation).
     const bool app = A.app_pos != nullptr;
     const int pos = app ? A.app_pos[clip] : 0;                    // == Sk - 1 when appending
     const int Sc = app ? Sk - 1 : Sk;                             // keys read from memory
@@ -2218,6 +1922,7 @@ struct WhisperState {
     std::vector<int> al_rows, al_cols;
     // asynchronous fetch of every clip's DTW path (pce_whisper_align_paths_enqueue / _wait): pinned staging, two batches in flight
     struct PathSlot { void *host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool armed = false; int n = 0, stride = 0; } al_slot[2];
+    bool lds_opted_in = false;        // lds_optins has run
     MelTables mt{};
     int mel_nmels = 0;
     int32_t n_clips_mel = -1, n_clips_enc = -1, enc_tab_clips = -1;
@@ -2326,28 +2031,10 @@ bool launch_gemm_flat(pce_ctx *c, const op_t *A, const op_t *B, const float *bia
     // of short K (the attention out-projection) column by column in 8-row supertiles (436 -> 422 us), 6 tiles across (cross K|V) the whole width
     // at once (835 -> 817 us); qkv (9 across), fc1 (12) and fc2 (3 across, K = 3072) stay on the default -- the whole width for fc1 gained 5 us
     // there and cost fc2, which reads what fc1 wrote, 22
-    static const bool shape_walk = !(getenv("PCE_FLAT_SHAPE_WALK") && atoi(getenv("PCE_FLAT_SHAPE_WALK")) == 0);
-    if (shape_walk) {
-        if (tiles_n == 3 && K <= 1024) { P.sn = 1; sm_want = 8; }
-        else if (tiles_n == 6) P.sn = tiles_n;
-    }
-    {   // laboratory knobs of the tile walk (tools/lab/flat_walk.sh): supertile width / height, start stagger
-        static const int env_sn = getenv("PCE_FLAT_SN") ? atoi(getenv("PCE_FLAT_SN")) : 0, env_sm = getenv("PCE_FLAT_SM") ? atoi(getenv("PCE_FLAT_SM")) : 0,
-                         env_st = getenv("PCE_FLAT_STAGGER") ? atoi(getenv("PCE_FLAT_STAGGER")) : -1;
-        if (env_sn == -1) P.sn = tiles_n;                                  // the whole width: plain row-major walk
-        else if (env_sn > 0) { for (int cand = env_sn; cand >= 1; cand--) if (tiles_n % cand == 0) { P.sn = cand; break; } }   // the largest divisor not above it
-        if (env_sm > 0) sm_want = env_sm;
-        if (env_st >= 0) P.stagger = env_st;
-    }
+    if (tiles_n == 3 && K <= 1024) { P.sn = 1; sm_want = 8; }
+    else if (tiles_n == 6) P.sn = tiles_n;
     P.sm = tiles_m < sm_want ? tiles_m : sm_want;                           // (a short batch: no padding row tiles in the walk)
-    const int lds = F_RING_BYTES + N * (int)sizeof(float);
-    if (!c->gemm_flat_attr[PCE_OP_INDEX][EPI]) {                           // once per context (the attribute is per device) and epilogue: the ring + the widest bias vector the shape test admits
-        if (hipFuncSetAttribute((const void *)k_gemm_flat<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, F_RING_BYTES + 6144 * (int)sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        c->gemm_flat_attr[PCE_OP_INDEX][EPI] = true;
-    }
+    const int lds = F_RING_BYTES + N * (int)sizeof(float);              // (N <= 6144: within what lds_optins allows)
     const int grid = ((c->cu_count > 0 ? c->cu_count : 256) / 8) * 8;
     KernelTimer kt(c, prof_id, nullptr, 2.0 * M * (double)N * K);
     hipLaunchKernelGGL((k_gemm_flat<EPI>), dim3((unsigned)grid), dim3(F_THREADS), lds, c->stream, P);
@@ -2366,17 +2053,10 @@ void launch_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, const 
         // accumulate epilogues, tools/lab/skinny_vs_tiled.py) but the compiler schedules the inlined GELU differently in the two, and on fp16
         // operands 6e-5 of the GELU outputs then round to the neighbouring value (tests/test_gpu_whisper.py::test_c3_batch_of_256_is_clip_independent)
         if (c->gemm_skinny && c->gemm_few_rows && batch == 1 && M <= 1024 && N <= 4096 && N % S_BN == 0 && K % S_KC == 0 && lda % 8 == 0) {
-            if (!c->gemm_skinny_attr[PCE_OP_INDEX][EPI]) {
-                if (hipFuncSetAttribute((const void *)k_gemm_skinny<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, S_NBUF * S_BUF * 2) == hipSuccess)
-                    c->gemm_skinny_attr[PCE_OP_INDEX][EPI] = true;
-                else (void)hipGetLastError();
-            }
-            if (c->gemm_skinny_attr[PCE_OP_INDEX][EPI]) {
-                KernelTimer kt(c, PCE_K_GEMM_SKINNY, nullptr, 2.0 * M * (double)N * K);
-                hipLaunchKernelGGL((k_gemm_skinny<EPI>), dim3((unsigned)(N / S_BN), (unsigned)div_up(M, S_BM)), dim3(S_THREADS), S_NBUF * S_BUF * 2, c->stream,
-                                   A, lda, B, M, N, K, bias, C, ldc);
-                return;
-            }
+            KernelTimer kt(c, PCE_K_GEMM_SKINNY, nullptr, 2.0 * M * (double)N * K);
+            hipLaunchKernelGGL((k_gemm_skinny<EPI>), dim3((unsigned)(N / S_BN), (unsigned)div_up(M, S_BM)), dim3(S_THREADS), S_LDS, c->stream,
+                               A, lda, B, M, N, K, bias, C, ldc);
+            return;
         }
     }
     const int tiles_n = N / G_BN;
@@ -2408,21 +2088,101 @@ void launch_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, const 
                            v_col0, vt_sp, sn, sm);
 }
 
+// ---- the encoder-output cross-attention of a decoding step (pce_xattn.inc), as the product and pce_selftest_xattn launch it --------------------
+// The widths it is built for, with 64-wide heads (at most 20: large-v3 / turbo)
+static bool xa_has_form(int d, int heads)
+{
+    return heads * 64 == d && (d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024 || d == 1280);
+}
+// workgroups per clip (two per CU): ONLY the work distribution follows the batch size -- the frames are always cut into the same XA_LEAVES ranges
+// and merged in the same order (pce_xattn.inc), so a clip's bits do not depend on what it is batched with.  wpc = 1 | 2 | 4 overrides (tests)
+static int xa_split(int n, int wpc) { return (wpc == 1 || wpc == 2 || wpc == 4) ? wpc : n >= 512 ? 1 : n >= 256 ? 2 : 4; }
+// The choices of one width: ring slots; the pair form (a workgroup that owns both leaves of a pair, nsplit <= 2, merges them in registers and
+// writes pair nodes) up to d = 768 -- d = 1024 has no registers for the waiting leaf (194 + 64) and always writes leaves; d = 1280 (20 heads): two
+// 16-row tiles of heads, 8 waves per workgroup (136 KB of LDS: one workgroup per CU)
+template <int D> struct XaWidth {
+    static constexpr int NSLOT = (D == 512 || D == 768 || D == 1024) ? 2 : 3, WV = xa_waves(D), RT = D > 1024 ? 2 : 1;
+    static constexpr bool PAIRS = D <= 768;
+    static constexpr size_t LDS = xa_lds(D, NSLOT);
+};
+// One layer's operands besides XaArgs: k_xq_fused's (LayerNorm, query projection, Wk^T; it writes Q' to qp_hi | qp_lo) and k_uv_absorb's (Wv, bv, out)
+struct XaLayer {
+    const float *resid, *ln_w, *ln_b, *bq, *bv;
+    const op_t *wq, *wkT, *wv;
+    op_t *qp_hi, *qp_lo, *out; int64_t out_ld;
+};
+// k_xq_fused -> k_xattn_absorbed -> k_uv_absorb for n clips
+template <int D>
+static void xattn_launch_d(pce_ctx *c, int n, XaArgs a, const XaLayer &y)
+{
+    using W = XaWidth<D>;
+    a.qp_hi = y.qp_hi; a.qp_lo = y.qp_lo;
+    const dim3 hgrid((unsigned)a.heads, (unsigned)div_up(n, 16)), grid((unsigned)(n * a.nsplit)), block(64 * (unsigned)W::WV);
+    hipLaunchKernelGGL(k_xq_fused<D>, hgrid, dim3(256), 0, c->stream, y.resid, y.ln_w, y.ln_b, y.wq, y.bq, y.wkT, n, 0.125f * 1.4426950408889634f, a.skip,
+                       y.qp_hi, y.qp_lo, a.rows);
+    auto uv = [&](auto kern) {
+        hipLaunchKernelGGL(kern, hgrid, dim3(256), 0, c->stream, a.u_part, a.ml_part, y.wv, y.bv, n, a.skip, y.out, y.out_ld, a.rows);
+    };
+    if constexpr (W::PAIRS) {
+        if (a.nsplit <= XA_LEAVES / 2) {
+            hipLaunchKernelGGL((k_xattn_absorbed<D, W::NSLOT, true, W::WV, W::RT>), grid, block, W::LDS, c->stream, a);
+            uv(k_uv_absorb<D, true>);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_xattn_absorbed<D, W::NSLOT, false, W::WV, W::RT>), grid, block, W::LDS, c->stream, a);
+    uv(k_uv_absorb<D, false>);
+}
+static void xattn_launch(pce_ctx *c, int d, int n, const XaArgs &a, const XaLayer &y)       // (xa_has_form(d, a.heads))
+{
+    switch (d) {
+    case 128: xattn_launch_d<128>(c, n, a, y); break;
+    case 256: xattn_launch_d<256>(c, n, a, y); break;
+    case 384: xattn_launch_d<384>(c, n, a, y); break;
+    case 512: xattn_launch_d<512>(c, n, a, y); break;
+    case 768: xattn_launch_d<768>(c, n, a, y); break;
+    case 1024: xattn_launch_d<1024>(c, n, a, y); break;
+    default: xattn_launch_d<1280>(c, n, a, y); break;
+    }
+}
+
+// Dynamic-LDS opt-ins (hipFuncSetAttribute) of every kernel of this operand build that launches with more LDS than the default allows: once per
+// WhisperState (the attribute is per device: the context's), before the first launch that needs one -- from the *_load entry points and the
+// self-tests.  A failure is an error: which kernel computes a product follows from the shapes alone.
+template <int D> static hipError_t xattn_optin()
+{
+    using W = XaWidth<D>;
+    if constexpr (W::PAIRS) {
+        const hipError_t e = hipFuncSetAttribute((const void *)k_xattn_absorbed<D, W::NSLOT, true, W::WV, W::RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W::LDS);
+        if (e != hipSuccess) return e;
+    }
+    return hipFuncSetAttribute((const void *)k_xattn_absorbed<D, W::NSLOT, false, W::WV, W::RT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W::LDS);
+}
+static int lds_optins(pce_ctx *c, WhisperState *w)
+{
+    if (w->lds_opted_in) return PCE_OK;
+    const hipFuncAttribute A = hipFuncAttributeMaxDynamicSharedMemorySize;
+    const int flat = F_RING_BYTES + 6144 * (int)sizeof(float);             // the ring + the widest bias vector launch_gemm_flat admits
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_BF16>, A, flat));
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_GELU>, A, flat));
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_VT>, A, flat));
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_SPLIT>, A, flat));
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_skinny<EPI_BF16>, A, S_LDS));
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_skinny<EPI_GELU_BF16>, A, S_LDS));
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_skinny<EPI_RESID_F32>, A, S_LDS));
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_cross_attn1w, A, 16 * 1600 * 4));   // 16 waves' score slices: the largest head group
+    PCE_HIP(c, xattn_optin<128>()); PCE_HIP(c, xattn_optin<256>()); PCE_HIP(c, xattn_optin<384>()); PCE_HIP(c, xattn_optin<512>());
+    PCE_HIP(c, xattn_optin<768>()); PCE_HIP(c, xattn_optin<1024>()); PCE_HIP(c, xattn_optin<1280>());
+    w->lds_opted_in = true;
+    return PCE_OK;
+}
+
 } // namespace
 
 void pce_whisper_free(pce_ctx *c)
 {
     if (!c->whisper_slot[PCE_OP_INDEX]) return;
     WhisperState *w = static_cast<WhisperState *>(c->whisper_slot[PCE_OP_INDEX]);
-    DevBuf *bufs[] = {&w->tables, &w->logspec, &w->clipmax, &w->mel_tm, &w->mel_start, &w->mel_stage, &w->w_bf16, &w->w_f32, &w->pos, &w->c1_out, &w->resid, &w->resid16,
-                      &w->ln_out, &w->qkv, &w->vt, &w->attn, &w->enc_tab, &w->delta, &w->delta2, &w->dw_bf16, &w->dw_f32, &w->d_tok_emb, &w->d_pos_emb, &w->d_tab,
-                      &w->d_tokens, &w->d_resid, &w->d_ln, &w->d_qk, &w->d_vt, &w->d_attn, &w->d_q, &w->d_hidden, &w->d_enc_bf16, &w->d_aw,
-                      &w->d_cost, &w->d_trace, &w->d_pi, &w->d_pj, &w->d_pl, &w->d_heads, &w->hidden, &w->final_out,
-                      &w->g_sv, &w->g_sk, &w->g_svt, &w->g_c_resid, &w->g_c_ln, &w->g_c_qkv, &w->g_c_attn, &w->g_c_q, &w->g_c_hidden, &w->g_c_tab, &w->g_loop,
-                      &w->g_emb_bf16, &w->g_xk, &w->g_xvt, &w->g_last, &w->g_lastln, &w->g_logits, &w->g_mask, &w->g_next, &w->g_keys, &w->g_wkT, &w->g_qp, &w->g_upart, &w->g_mlpart,
-                      &w->bert.w_bf16, &w->bert.w_f32, &w->bert.word, &w->bert.pos, &w->bert.type0, &w->bert.tab, &w->bert.tokens, &w->bert.resid,
-                      &w->bert.ln, &w->bert.qk, &w->bert.vt, &w->bert.attn, &w->bert.hidden, &w->bert.logits};
-    for (auto b : bufs) b->release();
     for (auto &ps : w->al_slot) {
         if (ps.host) (void)hipHostFree(ps.host);
         if (ps.ev) (void)hipEventDestroy(ps.ev);
@@ -2528,6 +2288,7 @@ int pce_whisper_load(pce_ctx *c, const pce_whisper_dims *dims, const float *weig
     if (n_floats != expect) return pce_fail(c, PCE_E_INVALID, "weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
     PCE_HIP(c, hipSetDevice(c->device));
     WhisperState *w = ws_of(c);
+    { const int rc = lds_optins(c, w); if (rc) return rc; }
     w->dims = *dims; w->loaded = false; w->layers.assign((size_t)L, {});
     // host repack: op_t-bound matrices (as fp32, converted on the device) and fp32 vectors
     std::vector<float> mats, vecs;
@@ -2594,7 +2355,6 @@ int pce_whisper_load(pce_ctx *c, const pce_whisper_dims *dims, const float *weig
     hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(),
                        w->w_bf16.as<op_t>(), (int64_t)mats.size());
     PCE_HIP(c, hipStreamSynchronize(c->stream));
-    tmp.release();
     w->loaded = true;
     return PCE_OK;
 }
@@ -2781,8 +2541,7 @@ int pce_selftest_attention(pce_ctx *c, const uint16_t *q, const uint16_t *k, con
     a.q_row0 = dtab.as<int>(); a.q_len = a.q_row0 + clips; a.k_row0 = a.q_row0 + 2 * clips; a.k_len = a.q_row0 + 3 * clips;
     a.out = dout.as<op_t>(); a.out_ld = hd; a.causal = causal; a.fell_back = dcnt.as<int>();
     const dim3 grid((unsigned)div_up(q_len, AT_QB), (unsigned)heads, (unsigned)clips);
-    if (c->attn_m16) hipLaunchKernelGGL(k_attention_lean16<false>, grid, dim3(256), 0, c->stream, a, mode);
-    else hipLaunchKernelGGL(k_attention_lean, grid, dim3(256), 0, c->stream, a, mode);
+    hipLaunchKernelGGL(k_attention_lean16<false>, grid, dim3(256), 0, c->stream, a, mode);
     PCE_HIP(c, hipGetLastError());
     int cnt = 0;
     PCE_HIP(c, hipMemcpyAsync(out, dout.p, nq * 2, hipMemcpyDeviceToHost, c->stream));
@@ -2799,11 +2558,12 @@ int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const 
                        int32_t workgroups_per_clip, uint16_t *out)
 {
     if (!c || !resid || !ln_w || !ln_b || !wq || !bq || !wk || !wv || !bv || !E || !k_len || !out || n <= 0 || k_cap <= 0) return PCE_E_INVALID;
-    if (!(d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024 || d == 1280) || heads * 64 != d || heads > 32)
+    if (!xa_has_form(d, heads))
         return pce_fail(c, PCE_E_INVALID, "selftest xattn: d = %d with %d heads is not a width the encoder-output form is built for", d, heads);
     if (!(workgroups_per_clip == 0 || workgroups_per_clip == 1 || workgroups_per_clip == 2 || workgroups_per_clip == 4)) return PCE_E_INVALID;
     for (int i = 0; i < n; i++) if (k_len[i] <= 0 || k_len[i] > k_cap) return pce_fail(c, PCE_E_INVALID, "selftest xattn: clip %d has %d frames of %d", i, k_len[i], k_cap);
     PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
     const size_t dd = (size_t)d * d, ne = (size_t)n * k_cap * d;
     DevBuf dres, dlw, dlb, dwq, dbq, dwk, dwkT, dwv, dbv, dE, dkl, dqp, dup, dml, dout;
     PCE_HIP(c, dres.reserve(sizeof(float) * (size_t)n * d)); PCE_HIP(c, dlw.reserve(sizeof(float) * d)); PCE_HIP(c, dlb.reserve(sizeof(float) * d));
@@ -2818,37 +2578,16 @@ int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const 
     for (const Up &u : ups) PCE_HIP(c, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemsetAsync(dqp.p, 0, dqp.cap, c->stream)); PCE_HIP(c, hipMemsetAsync(dout.p, 0, dout.cap, c->stream));
     hipLaunchKernelGGL(k_transpose_sq, dim3((unsigned)(d / 32), (unsigned)(d / 32)), dim3(256), 0, c->stream, dwk.as<op_t>(), dwkT.as<op_t>(), d);
-    int nsplit = workgroups_per_clip ? workgroups_per_clip : n >= 512 ? 1 : n >= 256 ? 2 : 4;
-    if (nsplit > XA_LEAVES) nsplit = XA_LEAVES;
-    const bool pairs = nsplit <= XA_LEAVES / 2 && d <= 768;
-    op_t *qp_hi = dqp.as<op_t>(), *qp_lo = qp_hi + (size_t)n * R * d;
     XaArgs a{};
-    a.E = dE.as<op_t>(); a.e_clip = (int64_t)k_cap * d; a.e_ld = d; a.qp_hi = qp_hi; a.qp_lo = qp_lo; a.k_len = dkl.as<int>(); a.skip = nullptr;
-    a.u_part = dup.as<float>(); a.ml_part = dml.as<float>(); a.heads = heads; a.nsplit = nsplit; a.rows = (int)R;
-    auto xq = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)heads, (unsigned)div_up(n, 16)), dim3(256), 0, c->stream, dres.as<float>(), dlw.as<float>(), dlb.as<float>(), dwq.as<op_t>(),
-                           dbq.as<float>(), dwkT.as<op_t>(), (int)n, 0.125f * 1.4426950408889634f, (const int *)nullptr, qp_hi, qp_lo, (int)R);
-    };
-    auto go = [&](auto kern, int nslot) {
-        const size_t lds = xa_lds(d, nslot);
-        (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3((unsigned)(n * nsplit)), dim3(64 * (unsigned)xa_waves(d)), lds, c->stream, a);
-    };
-    auto uv = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)heads, (unsigned)div_up(n, 16)), dim3(256), 0, c->stream, dup.as<float>(), dml.as<float>(), dwv.as<op_t>(), dbv.as<float>(),
-                           (int)n, (const int *)nullptr, dout.as<op_t>(), (int64_t)d, (int)R);
-    };
-#define PCE_XA_ST(D_, NS_) do { xq(k_xq_fused<D_>); if (pairs) { go(k_xattn_absorbed<D_, NS_, true>, NS_); uv(k_uv_absorb<D_, true>); } \
-                                else { go(k_xattn_absorbed<D_, NS_, false>, NS_); uv(k_uv_absorb<D_, false>); } } while (0)
-    if (d == 128) PCE_XA_ST(128, 3); else if (d == 256) PCE_XA_ST(256, 3); else if (d == 384) PCE_XA_ST(384, 3); else if (d == 512) PCE_XA_ST(512, 2);
-    else if (d == 768) PCE_XA_ST(768, 2);
-    else if (d == 1024) { xq(k_xq_fused<1024>); go(k_xattn_absorbed<1024, 2, false>, 2); uv(k_uv_absorb<1024, false>); }
-    else { xq(k_xq_fused<1280>); go(k_xattn_absorbed<1280, 3, false, 8, 2>, 3); uv(k_uv_absorb<1280, false>); }
-#undef PCE_XA_ST
+    a.E = dE.as<op_t>(); a.e_clip = (int64_t)k_cap * d; a.e_ld = d; a.k_len = dkl.as<int>(); a.skip = nullptr;
+    a.u_part = dup.as<float>(); a.ml_part = dml.as<float>(); a.heads = heads; a.nsplit = xa_split(n, workgroups_per_clip); a.rows = (int)R;
+    XaLayer y{};
+    y.resid = dres.as<float>(); y.ln_w = dlw.as<float>(); y.ln_b = dlb.as<float>(); y.wq = dwq.as<op_t>(); y.bq = dbq.as<float>(); y.wkT = dwkT.as<op_t>();
+    y.wv = dwv.as<op_t>(); y.bv = dbv.as<float>(); y.qp_hi = dqp.as<op_t>(); y.qp_lo = y.qp_hi + (size_t)n * R * d; y.out = dout.as<op_t>(); y.out_ld = d;
+    xattn_launch(c, d, n, a, y);
     PCE_HIP(c, hipGetLastError());
     PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)n * d, hipMemcpyDeviceToHost, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
-    for (DevBuf *b : {&dres, &dlw, &dlb, &dwq, &dbq, &dwk, &dwkT, &dwv, &dbv, &dE, &dkl, &dqp, &dup, &dml, &dout}) b->release();
     return PCE_OK;
 }
 
@@ -2859,6 +2598,7 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
 {
     if (!c || !A || !B || !out || M <= 0 || N <= 0 || K <= 0) return PCE_E_INVALID;
     PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
     if (epilogue >= 16 && epilogue <= 19) {
         // the tiled / few-row kernels behind launch_gemm (which of them runs follows from the shape, PCE_GEMM_SKINNY, PCE_GEMM_WIDE): 16 = bias,
         // 17 = bias + GELU (16-bit outputs), 19 = accumulate into a zeroed fp32 matrix (out receives M * N floats)
@@ -2882,7 +2622,6 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
         PCE_HIP(c, hipGetLastError());
         PCE_HIP(c, hipMemcpyAsync(out, tC.p, (size_t)M * N * (f32 ? 4 : 2), hipMemcpyDeviceToHost, c->stream));
         PCE_HIP(c, hipStreamSynchronize(c->stream));
-        tA.release(); tB.release(); tC.release(); tb.release();
         pce_profile_collect(c);
         return PCE_OK;
     }
@@ -2911,7 +2650,6 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
         if (e != hipSuccess) rc = pce_fail(c, PCE_E_DEVICE, "selftest gemm: %s", hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
-    dA.release(); dB.release(); dC.release(); dbias.release();
     pce_profile_collect(c);
     return rc;
 }
@@ -2942,11 +2680,13 @@ int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, cons
     const int d = dims->n_state, L = dims->n_layer, V = dims->n_vocab, TC = dims->n_text_ctx;
     if (d <= 0 || d % 128 || dims->n_head * 64 != d || L <= 0 || V <= 0 || V > DR_K * DR_T || TC <= 0 || TC > 448)
         return pce_fail(c, PCE_E_LIMIT, "unsupported decoder dims (need n_state %% 128 == 0, head size 64, n_text_ctx <= 448, n_vocab <= 52224)");
+    if (dims->n_head > 32) return pce_fail(c, PCE_E_LIMIT, "decoder with %d heads: the decoding kernels take at most 32", dims->n_head);
     const int64_t per_layer = 2LL * d + (4LL * d * d + 3LL * d) + 2LL * d + (4LL * d * d + 3LL * d) + 2LL * d + 8LL * d * d + 5LL * d;
     const int64_t expect = (int64_t)V * d + (int64_t)TC * d + L * per_layer + 2LL * d;
     if (n_floats != expect) return pce_fail(c, PCE_E_INVALID, "decoder weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
     PCE_HIP(c, hipSetDevice(c->device));
     WhisperState *w = ws_of(c);
+    { const int rc = lds_optins(c, w); if (rc) return rc; }
     w->tdims = *dims; w->dec_loaded = false; w->dlayers.assign((size_t)L, {});
     std::vector<float> mats, vecs;
     auto add_vec = [&](const float *p, size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), p, p + n); return o; };
@@ -3006,7 +2746,6 @@ int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, cons
                                w->g_wkT.as<op_t>() + dd * (size_t)l, d);
     }
     PCE_HIP(c, hipStreamSynchronize(c->stream));
-    tmp.release();
     w->dec_loaded = true; w->g_xkv_clips = -1; w->g_cache_len = -1;
     w->g_cache_n = -1;                  // the self-attention cache is sized by THIS decoder's width and layers: another decoder, another cache
     return PCE_OK;
@@ -3295,86 +3034,37 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
                        w->d_pos_emb.as<float>(), POS, d, n, w->g_c_resid.as<float>());
     // up to 16 heads: one workgroup per clip, one wave per head (115.8 against 119.6 us per launch with a workgroup per clip and head); that
     // kernel also appends the new position to the self-attention cache.  More heads (20 at large-v3 / turbo): workgroups of at most 16 waves,
-    // grid (clip, head group) -- the attribute below (16 waves' slices) covers the largest group
+    // grid (clip, head group) -- lds_optins (16 waves' slices) covers the largest group
     const int hgroups = (H + 15) / 16, hg_waves = (H + hgroups - 1) / hgroups;
-    bool wave_per_head = H <= 32;
-    if (wave_per_head && !c->attn1w_attr[PCE_OP_INDEX]) {
-        if (hipFuncSetAttribute((const void *)k_cross_attn1w, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1600 * 4) == hipSuccess) c->attn1w_attr[PCE_OP_INDEX] = true;
-        else { (void)hipGetLastError(); wave_per_head = false; }
-    }
     auto cattn = [&](const op_t *q, int64_t q_ld, const op_t *k, int64_t k_ld, const op_t *vt, int64_t vt_clip, int vt_sp, const int *k0, const int *kl,
                      const op_t *app_qkv = nullptr) {
         // the streaming single-query kernels (the MFMA attention kernel would spend a 32-query tile on the one live query)
         Attn1Args a{};
         a.q = q; a.q_ld = q_ld; a.k = k; a.k_ld = k_ld; a.vt = vt; a.vt_clip = vt_clip; a.vt_sp = vt_sp; a.k_row0 = k0; a.k_len = kl; a.skip = ended;
         a.out = w->g_c_attn.as<op_t>(); a.out_ld = d;
+        if (app_qkv) { a.app_k = app_qkv + d; a.app_v = app_qkv + 2 * d; a.app_ld = 3 * d; a.app_pos = POS; }
+        a.heads = H;
         KernelTimer kt(c, PCE_K_CROSS_ATTN1);
-        if (wave_per_head) {
-            if (app_qkv) { a.app_k = app_qkv + d; a.app_v = app_qkv + 2 * d; a.app_ld = 3 * d; a.app_pos = POS; }
-            a.heads = H;
-            hipLaunchKernelGGL(k_cross_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 1600 * 4, c->stream, a);
-            return;
-        }
-        hipLaunchKernelGGL(k_cross_attn1, dim3((unsigned)H, (unsigned)n), dim3(A1_T), 0, c->stream, a);
+        hipLaunchKernelGGL(k_cross_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 1600 * 4, c->stream, a);
     };
     auto cln = [&](size_t w_off, size_t b_off) {
         hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(n, 4)), dim3(256), 0, c->stream, w->g_c_resid.as<float>(), Wf + w_off, Wf + b_off,
                            (int64_t)n, d, w->g_c_ln.as<op_t>());
     };
-    // cross-attention from the encoder output (pce_xattn.inc): E once per layer instead of K and V^T.  d = 1280 (large-v3 / turbo, 20 heads): two
-    // 16-row tiles of heads, 8 waves per workgroup
-    const bool absorb = c->xattn_absorb && ((H <= 16 && (d == 128 || d == 256 || d == 384 || d == 512 || d == 768 || d == 1024)) || (d == 1280 && H <= 32 && H * 64 == d))
-                        && w->g_qp.p && w->g_wkT.p;
-    const int xrows = xa_rows(H);                                 // rows of Q' and of the partials per clip: 16, or 32 at 20 heads
-    // workgroups per clip (two per CU): ONLY the work distribution follows the batch size -- the frames are always cut into the same XA_LEAVES ranges
-    // and merged in the same order (pce_xattn.inc), so a clip's bits do not depend on what it is batched with.  PCE_XATTN_WPC = 1 | 2 | 4 overrides (tests)
+    // cross-attention from the encoder output (pce_xattn.inc): E once per layer instead of K and V^T
+    const bool absorb = c->xattn_absorb && xa_has_form(d, H) && w->g_qp.p && w->g_wkT.p;
     static const int env_wpc = getenv("PCE_XATTN_WPC") ? atoi(getenv("PCE_XATTN_WPC")) : 0;
-    int nsplit = (env_wpc == 1 || env_wpc == 2 || env_wpc == 4 || env_wpc == 8) ? env_wpc : n >= 512 ? 1 : n >= 256 ? 2 : n >= 128 ? 4 : 8;
-    if (nsplit > XA_LEAVES) nsplit = XA_LEAVES;
+    XaArgs xa{};
+    xa.E = w->d_enc_bf16.as<op_t>(); xa.e_clip = (int64_t)W_CTX * d; xa.e_ld = d; xa.k_len = XL; xa.skip = ended;
+    xa.u_part = w->g_upart.as<float>(); xa.ml_part = w->g_mlpart.as<float>(); xa.heads = H; xa.nsplit = xa_split(n, env_wpc); xa.rows = xa_rows(H);
     auto xattn = [&](int l) {
         const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-        op_t *qp_hi = w->g_qp.as<op_t>(), *qp_lo = qp_hi + (size_t)n * xrows * d;
+        XaLayer y{};
+        y.resid = w->g_c_resid.as<float>(); y.ln_w = Wf + ly.lnx_w; y.ln_b = Wf + ly.lnx_b; y.wq = Wb + ly.xq_w; y.bq = Wf + ly.xq_b;
+        y.wkT = w->g_wkT.as<op_t>() + (size_t)d * d * (size_t)l; y.wv = Wb + ly.xkv_w + (size_t)d * d; y.bv = Wf + ly.xkv_b + d;
+        y.qp_hi = w->g_qp.as<op_t>(); y.qp_lo = y.qp_hi + (size_t)n * xa.rows * d; y.out = w->g_c_attn.as<op_t>(); y.out_ld = d;
         KernelTimer kt(c, PCE_K_CROSS_ATTN1);
-        auto xq = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)H, (unsigned)div_up(n, 16)), dim3(256), 0, c->stream, w->g_c_resid.as<float>(), Wf + ly.lnx_w, Wf + ly.lnx_b,
-                               Wb + ly.xq_w, Wf + ly.xq_b, w->g_wkT.as<op_t>() + (size_t)d * d * (size_t)l, n, 0.125f * 1.4426950408889634f, ended, qp_hi, qp_lo, xrows);
-        };
-        if (d == 128) xq(k_xq_fused<128>); else if (d == 256) xq(k_xq_fused<256>); else if (d == 384) xq(k_xq_fused<384>); else if (d == 512) xq(k_xq_fused<512>);
-        else if (d == 768) xq(k_xq_fused<768>); else if (d == 1024) xq(k_xq_fused<1024>); else xq(k_xq_fused<1280>);
-        XaArgs a{};
-        a.E = w->d_enc_bf16.as<op_t>(); a.e_clip = (int64_t)W_CTX * d; a.e_ld = d; a.qp_hi = qp_hi; a.qp_lo = qp_lo; a.k_len = XL; a.skip = ended;
-        a.u_part = w->g_upart.as<float>(); a.ml_part = w->g_mlpart.as<float>(); a.heads = H; a.nsplit = nsplit; a.rows = xrows;
-        // a workgroup that owns both leaves of a pair (nsplit <= 2) merges them in registers and writes pair nodes; d = 1024 has no registers for the
-        // waiting leaf (194 + 64) and always writes leaves
-        const bool pairs = nsplit <= XA_LEAVES / 2 && d <= 768;
-        const dim3 grid((unsigned)(n * nsplit));
-        auto go = [&](auto kern, int nslot) {
-            const size_t lds = xa_lds(d, nslot);
-            const unsigned bit = 1u << (d / 128 + (pairs ? 16 : 0)); // one instantiation per (d, pair form): each is its own function and needs its own attribute
-            if (!(c->xattn_attr[PCE_OP_INDEX] & bit)) {
-                (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                c->xattn_attr[PCE_OP_INDEX] |= bit;
-            }
-            hipLaunchKernelGGL(kern, grid, dim3(64 * (unsigned)xa_waves(d)), lds, c->stream, a);
-        };
-        if (d == 128) { if (pairs) go(k_xattn_absorbed<128, 3, true>, 3); else go(k_xattn_absorbed<128, 3, false>, 3); }
-        else if (d == 256) { if (pairs) go(k_xattn_absorbed<256, 3, true>, 3); else go(k_xattn_absorbed<256, 3, false>, 3); }
-        else if (d == 384) { if (pairs) go(k_xattn_absorbed<384, 3, true>, 3); else go(k_xattn_absorbed<384, 3, false>, 3); }
-        else if (d == 512) { if (pairs) go(k_xattn_absorbed<512, 2, true>, 2); else go(k_xattn_absorbed<512, 2, false>, 2); }
-        else if (d == 768) { if (pairs) go(k_xattn_absorbed<768, 2, true>, 2); else go(k_xattn_absorbed<768, 2, false>, 2); }
-        else if (d == 1024) go(k_xattn_absorbed<1024, 2, false>, 2);
-        else go(k_xattn_absorbed<1280, 3, false, 8, 2>, 3);        // (136 KB of LDS: one workgroup of 8 waves per CU)
-        auto uv = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)H, (unsigned)div_up(n, 16)), dim3(256), 0, c->stream, w->g_upart.as<float>(), w->g_mlpart.as<float>(),
-                               Wb + ly.xkv_w + (size_t)d * d, Wf + ly.xkv_b + d, n, ended, w->g_c_attn.as<op_t>(), (int64_t)d, xrows);
-        };
-        if (d == 128) { if (pairs) uv(k_uv_absorb<128, true>); else uv(k_uv_absorb<128, false>); }
-        else if (d == 256) { if (pairs) uv(k_uv_absorb<256, true>); else uv(k_uv_absorb<256, false>); }
-        else if (d == 384) { if (pairs) uv(k_uv_absorb<384, true>); else uv(k_uv_absorb<384, false>); }
-        else if (d == 512) { if (pairs) uv(k_uv_absorb<512, true>); else uv(k_uv_absorb<512, false>); }
-        else if (d == 768) { if (pairs) uv(k_uv_absorb<768, true>); else uv(k_uv_absorb<768, false>); }
-        else if (d == 1024) uv(k_uv_absorb<1024, false>);
-        else uv(k_uv_absorb<1280, false>);
+        xattn_launch(c, d, n, xa, y);
     };
     for (int l = 0; l < L; l++) {
         const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
@@ -3382,10 +3072,7 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
         //  and dropped: four dependent L2 round trips per wave, 17 us per launch against 11.8 + 5.5 for the two launches)
         cln(ly.ln1_w, ly.ln1_b);
         launch_gemm<EPI_BF16>(c, w->g_c_ln.as<op_t>(), d, 0, Wb + ly.qkv_w, n, 3 * d, d, Wf + ly.qkv_b, w->g_c_qkv.as<op_t>(), 3 * d, 0, 1);
-        if (!wave_per_head)
-            hipLaunchKernelGGL(k_append_kv, dim3((unsigned)div_up((int64_t)n * d, 256)), dim3(256), 0, c->stream, w->g_c_qkv.as<op_t>(), POS, d, T_cap, SPD, n,
-                               w->g_sk.as<op_t>() + sk_l * (size_t)l, w->g_svt.as<op_t>() + svt_l * (size_t)l);
-        if (wave_per_head && c->self_rows && w->g_sv.p) {
+        if (c->self_rows && w->g_sv.p) {
             // row-major K / V caches: the append is two coalesced row stores (the V^T image is not touched by incremental steps: only prefix runs,
             // which rewrite every position they attend to, read it)
             SelfAttn1Args sa{};
@@ -3803,7 +3490,6 @@ int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, i
     hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(),
                        b.w_bf16.as<op_t>(), (int64_t)mats.size());
     PCE_HIP(c, hipStreamSynchronize(c->stream));
-    tmp.release();
     b.loaded = true;
     return PCE_OK;
 }

@@ -936,6 +936,31 @@ def test_attention_fixed_reference_overflow_takes_the_exact_path(engine, ops):
         assert np.max(np.abs(exact - want)) <= 2e-2
 
 
+def test_attention_selftest_frees_its_device_buffers(engine):
+    """Every device buffer of a call is freed when it returns: eight calls of about 350 MB each (32 clips x 16 heads, 128 queries over 1 500 keys)
+    leave the device's free memory where it was (keeping them would take 2.8 GB)."""
+    import torch
+    rng = np.random.default_rng(11)
+    q = rng.standard_normal((32, 128, 16 * 64)).astype(np.float32)
+    k = rng.standard_normal((32, 1500, 16 * 64)).astype(np.float32)
+    v = rng.standard_normal((32, 1500, 16 * 64)).astype(np.float32)
+    engine.selftest_attention(q, k, v)
+    free_before = torch.cuda.mem_get_info(0)[0]
+    for _ in range(8):
+        engine.selftest_attention(q, k, v)
+    dropped = free_before - torch.cuda.mem_get_info(0)[0]
+    assert dropped < 1 << 30, f"{dropped / 2**20:.0f} MB"
+
+
+def test_decoder_with_more_than_32_heads_is_refused(engine):
+    """The decoding kernels hold at most 32 heads: pce_whisper_decoder_load refuses 34 with PCE_E_LIMIT (-5), checking the dims before the size of
+    the weight blob and before any allocation."""
+    from prosody_control_french_tts_amd.engine import PceError
+    dims = dict(n_vocab=64, n_text_ctx=16, n_state=34 * 64, n_head=34, n_layer=1)
+    with pytest.raises(PceError, match=r"status -5: .*34 heads"):
+        engine.whisper_decoder_load(dims, np.zeros(16, dtype=np.float32))
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # fp16 operands: the reference's own arithmetic (openai-whisper fp16=True), same kernels, same MFMA rate
 # ---------------------------------------------------------------------------------------------------------------

@@ -72,7 +72,7 @@ We, Wd = WW.synthetic_weights(edims, seed=77), WW.greedy_test_decoder_weights(td
 if os.environ.get("PROBE_STAGES", "").startswith("st:"):
     # a neighbour that launches ONE kind of libpce kernel in a tight loop through the self-test entry points (operands converted once), as long as child 0 runs:
     # st:gemm128 (k_gemm_bf16, 66 KB of LDS-DMA ring), st:gemm128deep (k_gemm_bf16<.,4>: few rows, 128 KB ring), st:wide (k_gemm_wide), st:flat (k_gemm_flat 256 x 256,
-    # 128 KB ring), st:skinny (k_gemm_skinny), st:attn (k_attention_lean16), st:attn32 (PCE_ATTN_M16=0 in the environment: k_attention_lean)
+    # 128 KB ring), st:skinny (k_gemm_skinny), st:attn (k_attention_lean16)
     import ctypes as C, torch
     kind = os.environ["PROBE_STAGES"].split(":")[1]
     eng = pkg.ProsodyEngine(0)
@@ -80,7 +80,7 @@ if os.environ.get("PROBE_STAGES", "").startswith("st:"):
     def t16(*shape):
         return torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(torch.float16).contiguous()
     lib, ctx = eng._lib, eng._ctx
-    if kind == "attn" or kind == "attn32":
+    if kind == "attn":
         q, k, v = t16(3, 1500, 128), t16(3, 1500, 128), t16(3, 1500, 128); o = torch.zeros_like(q); fb = C.c_int32(0)
         call = lambda: lib.pce_selftest_attention(ctx, q.data_ptr(), k.data_ptr(), v.data_ptr(), 3, 2, 1500, 1500, 0, 0, o.data_ptr(), C.addressof(fb))
     else:
