@@ -48,9 +48,10 @@ extern "C" {
  * of other streams / contexts / processes (results no longer depend on what else runs on the device: tools/isa_guard.py); pce_selftest_xattn;
  * 4 = Whisper large-v3 / turbo widths on the decoding kernels: the encoder-output cross-attention of a decoding step (and pce_selftest_xattn) at
  * d = 1280 with 20 heads, and the single-query attention kernels of an incremental step for up to 32 heads (before, more than 16 heads fell back to
- * the K / V form without a word). */
+ * the K / V form without a word);  5 = pce_selftest_gemm_tiled, pce_selftest_layernorm; the LayerNorm kernels hold n_state up to 2048 (before, widths
+ * above 1280 loaded and returned wrong numbers) and every loader refuses a width its run path cannot compute (see the dims structs). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 4
+#define PCE_API_MINOR 5
 
 typedef struct pce_ctx pce_ctx;
 
@@ -248,7 +249,9 @@ int pce_pyin_fetch(pce_ctx *ctx, int32_t clip, int32_t *states, double *voiced_p
 typedef struct pce_whisper_dims {
     int32_t n_mels;    /* 80 (128 for large-v3)          */
     int32_t n_ctx;     /* 1500                            */
-    int32_t n_state;   /* d: 384/512/768/1024/1280        */
+    int32_t n_state;   /* d: 384/512/768/1024/1280; d % 128 == 0, d <= 2048 (the LayerNorm kernels), and where d % 256 == 0 the
+                        * persistent GEMM runs fc1 (N = 4 d <= 6144): d <= 1536, unless the context was created with PCE_GEMM_FLAT=0.
+                        * Other widths are PCE_E_LIMIT at load. */
     int32_t n_head;    /* d / 64                          */
     int32_t n_layer;
 } pce_whisper_dims;
@@ -280,6 +283,29 @@ int pce_selftest_attention(pce_ctx *ctx, const uint16_t *q, const uint16_t *k, c
 int pce_selftest_xattn(pce_ctx *ctx, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,
                        const uint16_t *wv, const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads,
                        int32_t workgroups_per_clip, uint16_t *out);
+/* Self-test of the tiled / few-row GEMM kernels the convolutions, the teacher-forced decoder, the decoding steps, BERT and the vocabulary logits run
+ * on, through the product's own launch code: C = epilogue(A B^T + bias) for `batch` problems, A [batch] rows of K at pitch lda (a_batch apart; rows may
+ * overlap: lda < K), B [N][K] and A as 16-bit patterns of the context's operand type, bias [N] fp32 (may be NULL).  epilogue 0: bias, 16-bit C;
+ * 1: bias + exact GELU, 16-bit C; 2: GELU(bias + .) + pos[row % pos_T][n], fp32 C (pos [pos_T][N]); 3: C += . + bias, fp32 (C is read);
+ * 4: columns [0, v_col0) as epilogue 0, columns [v_col0, N) written transposed to vt[(clip (N - v_col0) + n - v_col0) vt_sp + t], clip = row /
+ * rows_per_clip, t = row % rows_per_clip (batch 1); 5: bias, fp32 C.  C [c_len] (element type of the epilogue) is read and written back, with
+ * vt [vt_len]: what a launch does not write keeps the caller's values.  kernel: 0 = what the product's rule picks outside an incremental
+ * decoding step, 1 = the few-row kernel, 2 = 128 x 256, 3 = 128 x 128 two-stage, 4 = 128 x 128 four-stage; *kernel_used (may be NULL) receives
+ * the kernel that ran.  PCE_E_LIMIT where that kernel does not compute the shape (N % 128, K % 64 for 128 x 128; N % 256, K % 32 for 128 x 256;
+ * batch 1, N % 32, K % 256, M <= 1024, N <= 4096 and epilogues 0 / 1 / 3 for the few-row kernel); PCE_E_INVALID where a launch would address
+ * beyond a_len, c_len or vt_len.  Since minor 5. */
+int pce_selftest_gemm_tiled(pce_ctx *ctx, int32_t kernel, int32_t epilogue, const uint16_t *A, int64_t a_len, int64_t lda, int64_t a_batch, int32_t batch,
+                            const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, void *C, int64_t c_len, int64_t ldc, int64_t c_batch,
+                            const float *pos, int32_t pos_T, int32_t v_col0, int32_t rows_per_clip, int32_t vt_sp, uint16_t *vt, int64_t vt_len,
+                            int32_t *kernel_used);
+/* Self-test of the LayerNorm kernels as the product launches them, rows x d (d % 4 == 0, d <= 2048), w / b [d] fp32.  form 0 / 1: LayerNorm of x
+ * (fp32) to out (fp32 / 16-bit); flags bit 0: x is taken as rounded to 16 bits, bit 1: the fp32 result is also written over x (returned in
+ * resid_out).  form 2 + 3 o + s: x (+ delta) (+ delta2), then LayerNorm -- out fp32 (o = 0) or 16-bit (o = 1); s = 0: x and the stream fp32,
+ * 1: x fp32, the stream 16-bit, 2: x and the stream 16-bit (every sum rounded to 16 bits where the stream is); delta / delta2 [rows][d] 16-bit
+ * (delta2 may be NULL); flags bit 2: the stream is written (resid_out receives the stream buffer, rows x d of its type); out_copy (may be NULL):
+ * a 16-bit copy of the output.  Since minor 5. */
+int pce_selftest_layernorm(pce_ctx *ctx, int32_t form, int32_t rows, int32_t d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w,
+                           const float *b, float eps, int32_t flags, void *out, void *resid_out, uint16_t *out_copy);
 int pce_whisper_encode_fetch(pce_ctx *ctx, int32_t clip, float *out /* [1500][n_state] */);
 
 /* ---- R8: forced alignment of known text tokens (teacher-forced decoder + cross-attention DTW) ----
@@ -295,7 +321,7 @@ int pce_whisper_encode_fetch(pce_ctx *ctx, int32_t clip, float *out /* [1500][n_
  *              mlp_ln.w,b  mlp.0.w,b  mlp.2.w,b
  *   ln.w,b */
 typedef struct pce_whisper_text_dims {
-    int32_t n_vocab /* <= 52224 */, n_text_ctx /* <= 448 */, n_state, n_head /* <= 32: more is PCE_E_LIMIT */, n_layer;
+    int32_t n_vocab /* <= 52224 */, n_text_ctx /* <= 448 */, n_state, n_head /* <= 32 (n_state <= 2048): more is PCE_E_LIMIT */, n_layer;
 } pce_whisper_text_dims;
 int pce_whisper_decoder_load(pce_ctx *ctx, const pce_whisper_text_dims *dims, const float *weights, int64_t n_floats);
 /* tokens: concatenated per clip (token_offsets[n_clips+1]); num_frames: mel frames of real audio per clip;
@@ -426,6 +452,7 @@ int pce_levenshtein(pce_ctx *ctx, const uint32_t *a_chars, const int64_t *a_off,
  * needs the checkpoint's vocabulary); token_type_ids = 0, right padding is implicit in the offsets.  MFMA operands of
  * the context's operand mode (pce_whisper_set_operands: fp16 by default, bf16 on request), fp32 accumulation, LayerNorm /
  * residual stream / logits in fp32. */
+/* n_state % 128 == 0 and <= 2048 (the LayerNorm kernels), n_head = n_state / 64, n_pos <= 512, n_labels <= 128: else PCE_E_LIMIT at load */
 typedef struct pce_bert_dims { int32_t n_vocab, n_pos, n_type, n_state, n_head, n_layer, n_labels; } pce_bert_dims;
 int pce_bert_load(pce_ctx *ctx, const pce_bert_dims *dims, const float *weights, int64_t n_floats);
 int pce_bert_run(pce_ctx *ctx, const int32_t *input_ids, const int32_t *offsets /* [n_seq + 1] */, int32_t n_seq);

@@ -47,6 +47,7 @@
 // younger, whose MFMA groups take twice as long) and 700 cycles per K-step behind the in-order wait for the A half issued at the step's top.
 
 constexpr int F_T = 256, F_K = 64, F_THREADS = 512;
+constexpr int F_N_MAX = 6144;            // widest output launch_gemm_flat takes: the bias row of a tile column lives in LDS (ring + N floats)
 constexpr bool F_PINGPONG = true;                          // K-step form: four phases, wave rows one barrier apart (kstep_pp) / two barriers, rows in step (kstep)
 constexpr int F_HALF = 128 * F_K;                          // elements of a half-tile (16 KB)
 constexpr int F_RING_BYTES = 8 * F_HALF * 2;
@@ -470,7 +471,7 @@ __global__ __launch_bounds__(F_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
 //     (model.py LayerNorm.forward: super().forward(x.float()).type(x.dtype)).  Mirrored rounding for rounding: x1 = r16(x + delta) feeds
 //     ln2 AS ROUNDED, x2 = r16(x1 + delta2) is the stream; both passes derive x1 the same way, so nothing depends on which pass ran;
 //   float / op_t: the first layer of that mode (the convolution stem leaves gelu(conv2) + positional embedding in fp32: rounded on the way in).
-template <class OUT, class RIN, class ROUT>
+template <class OUT, class RIN, class ROUT, int NV = 5>       // (NV: float4 per lane, as k_layernorm)
 __global__ __launch_bounds__(256) void k_add_layernorm(const RIN *resid_in, ROUT *resid_out, const op_t *__restrict__ delta, const op_t *__restrict__ delta2,
                                                       int write_resid, const float *__restrict__ w,
                                                       const float *__restrict__ b, int64_t rows, int d, OUT *__restrict__ out, float eps,
@@ -485,10 +486,10 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const RIN *resid_in, ROUT
     const opx4 *dr2 = reinterpret_cast<const opx4 *>(delta2 ? delta2 + row * d : nullptr);
     auto r16 = [](float x) -> float { return OUT16 ? (float)(op_t)x : x; };
     const int nv = d >> 2;
-    float4 v[5];
+    float4 v[NV];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 5; i++) {
+    for (int i = 0; i < NV; i++) {
         const int idx = lane + 64 * i;
         if (idx < nv) {
             // (read once / written once per pass: non-temporal, so that 3.5 GB of stream do not evict the next GEMM's weights from L2)
@@ -519,7 +520,7 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const RIN *resid_in, ROUT
     const float mean = s / (float)d;
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 5; i++) {
+    for (int i = 0; i < NV; i++) {
         if (lane + 64 * i < nv) {
             const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
             q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
@@ -528,7 +529,7 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const RIN *resid_in, ROUT
     q = wave_allsum_f32(q);
     const float inv = rsqrtf(q / (float)d + eps);
 #pragma unroll
-    for (int i = 0; i < 5; i++) {
+    for (int i = 0; i < NV; i++) {
         const int idx = lane + 64 * i;
         if (idx < nv) {
             const float4 ww = reinterpret_cast<const float4 *>(w)[idx], bb = reinterpret_cast<const float4 *>(b)[idx];

@@ -15,6 +15,10 @@ PCE_BOTH(int, pce_whisper_encode_fetch, (pce_ctx *, int32_t, float *))
 PCE_BOTH(int, pce_selftest_attention, (pce_ctx *, const uint16_t *, const uint16_t *, const uint16_t *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *, int32_t *))
 PCE_BOTH(int, pce_selftest_gemm, (pce_ctx *, const uint16_t *, const uint16_t *, const float *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
 PCE_BOTH(int, pce_selftest_xattn, (pce_ctx *, const float *, const float *, const float *, const uint16_t *, const float *, const uint16_t *, const uint16_t *, const float *, const uint16_t *, const int32_t *, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
+PCE_BOTH(int, pce_selftest_gemm_tiled, (pce_ctx *, int32_t, int32_t, const uint16_t *, int64_t, int64_t, int64_t, int32_t, const uint16_t *, const float *, int32_t, int32_t,
+                                         int32_t, void *, int64_t, int64_t, int64_t, const float *, int32_t, int32_t, int32_t, int32_t, uint16_t *, int64_t, int32_t *))
+PCE_BOTH(int, pce_selftest_layernorm, (pce_ctx *, int32_t, int32_t, int32_t, const void *, const uint16_t *, const uint16_t *, const float *, const float *, float, int32_t,
+                                        void *, void *, uint16_t *))
 PCE_BOTH(int, pce_whisper_decoder_load, (pce_ctx *, const pce_whisper_text_dims *, const float *, int64_t))
 PCE_BOTH(int, pce_whisper_align_run, (pce_ctx *, const int32_t *, const int32_t *, const int32_t *, int32_t, const uint8_t *, int32_t, float))
 PCE_BOTH(int, pce_whisper_align_fetch, (pce_ctx *, int32_t, int32_t *, int32_t *, int32_t *, double *))
@@ -66,6 +70,18 @@ int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const 
                        const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads, int32_t workgroups_per_clip, uint16_t *out)
 {
     return PCE_FWD(pce_selftest_xattn, c, resid, ln_w, ln_b, wq, bq, wk, wv, bv, E, k_len, n, k_cap, d, heads, workgroups_per_clip, out);
+}
+int pce_selftest_gemm_tiled(pce_ctx *c, int32_t kernel, int32_t epilogue, const uint16_t *A, int64_t a_len, int64_t lda, int64_t a_batch, int32_t batch,
+                            const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, void *C, int64_t c_len, int64_t ldc, int64_t c_batch,
+                            const float *pos, int32_t pos_T, int32_t v_col0, int32_t rows_per_clip, int32_t vt_sp, uint16_t *vt, int64_t vt_len, int32_t *kernel_used)
+{
+    return PCE_FWD(pce_selftest_gemm_tiled, c, kernel, epilogue, A, a_len, lda, a_batch, batch, B, bias, M, N, K, C, c_len, ldc, c_batch, pos, pos_T, v_col0,
+                   rows_per_clip, vt_sp, vt, vt_len, kernel_used);
+}
+int pce_selftest_layernorm(pce_ctx *c, int32_t form, int32_t rows, int32_t d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w,
+                           const float *b, float eps, int32_t flags, void *out, void *resid_out, uint16_t *out_copy)
+{
+    return PCE_FWD(pce_selftest_layernorm, c, form, rows, d, x, delta, delta2, w, b, eps, flags, out, resid_out, out_copy);
 }
 int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, const float *weights, int64_t n_floats)
 {

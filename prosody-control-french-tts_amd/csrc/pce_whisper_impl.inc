@@ -60,6 +60,8 @@
 #define pce_bert_run PCE_WFN(pce_bert_run)
 #define pce_bert_fetch PCE_WFN(pce_bert_fetch)
 #define pce_selftest_xattn PCE_WFN(pce_selftest_xattn)
+#define pce_selftest_gemm_tiled PCE_WFN(pce_selftest_gemm_tiled)
+#define pce_selftest_layernorm PCE_WFN(pce_selftest_layernorm)
 #define pce_whisper_free PCE_WFN(pce_whisper_free)
 extern "C" int pce_whisper_decode_step_ex(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
                                           const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, int32_t *next_tokens,
@@ -796,8 +798,9 @@ __global__ __launch_bounds__(G_THREADS, 4) void k_gemm_wide(const op_t *__restri
 // ---------------------------------------------------------------------------
 // LayerNorm over the last dimension (one wavefront per row)
 // ---------------------------------------------------------------------------
-// The row (d <= 1280 floats) is read once with 16-byte loads and kept in registers (<= 5 float4 per lane);
-// statistics in fp32, two-pass (mean, then centred second moment) as torch does.
+// The row is read once with 16-byte loads and kept in registers: NV float4 per lane, so d <= 256 NV.  NV = 5 up to d = 1280 (every width of
+// the Whisper / BERT checkpoints: the code and bits that k_xq_fused restates), NV = 8 up to LN_D_MAX; launch_layernorm and launch_add_layernorm
+// pick it from d.  Statistics in fp32, two-pass (mean, then centred second moment) as torch does.
 template <class OUT> __device__ __forceinline__ void ln_store4(OUT *p, float a, float b, float c, float d);
 template <> __device__ __forceinline__ void ln_store4<float>(float *p, float a, float b, float c, float d)
 {
@@ -828,7 +831,8 @@ __device__ __forceinline__ float wave_allsum_f32(float v)
     return (r0 + r1) + (r2 + r3);
 }
 
-template <class OUT>
+constexpr int LN_D_MAX = 2048;
+template <class OUT, int NV = 5>
 __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *__restrict__ w, const float *__restrict__ b,
                                                   int64_t rows, int d, OUT *__restrict__ out, float eps = 1e-5f, float *out2 = nullptr, int round_in16 = 0)
 {   // out2 (optional, may alias x): the same values in fp32 -- the post-LN residual stream of the BERT layers
@@ -839,10 +843,10 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *
     if (row >= rows) return;
     const float4 *xr = reinterpret_cast<const float4 *>(x + row * d);
     const int nv = d >> 2;                               // float4 per row, d % 4 == 0
-    float4 v[5];
+    float4 v[NV];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 5; i++) {
+    for (int i = 0; i < NV; i++) {
         const int idx = lane + 64 * i;
         v[i] = idx < nv ? xr[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
         if (round_in16) v[i] = make_float4((float)(op_t)v[i].x, (float)(op_t)v[i].y, (float)(op_t)v[i].z, (float)(op_t)v[i].w);
@@ -852,7 +856,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *
     const float mean = s / (float)d;
     float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 5; i++) {
+    for (int i = 0; i < NV; i++) {
         if (lane + 64 * i < nv) {
             const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
             q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
@@ -861,7 +865,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *
     q = wave_allsum_f32(q);
     const float inv = rsqrtf(q / (float)d + eps);
 #pragma unroll
-    for (int i = 0; i < 5; i++) {
+    for (int i = 0; i < NV; i++) {
         const int idx = lane + 64 * i;
         if (idx < nv) {
             const float4 ww = reinterpret_cast<const float4 *>(w)[idx], bb = reinterpret_cast<const float4 *>(b)[idx];
@@ -2015,7 +2019,7 @@ bool launch_gemm_flat(pce_ctx *c, const op_t *A, const op_t *B, const float *bia
     constexpr bool HAS_VT = EPI == FEPI_VT || EPI == FEPI_SPLIT, HAS_RM = EPI != FEPI_VT;
     // (no lower bound on M: which kernel computes a projection must follow from the MODEL's dims alone, never from the batch size -- a clip's
     // results are compared across batch compositions and rank counts, tests/test_gpu_world2.py)
-    if (!c->gemm_flat || N % F_T || K % F_K || M < 1 || N > 6144 || (HAS_VT && (S % 4 || S < F_T))) return false;
+    if (!c->gemm_flat || N % F_T || K % F_K || M < 1 || N > F_N_MAX || (HAS_VT && (S % 4 || S < F_T))) return false;
     if (EPI == FEPI_SPLIT && (!C2 || vt_n0 <= 0 || vt_n0 >= N || vt_n0 % F_T)) return false;
     if (HAS_RM && !gemm_flat_offsets_fit(M, N, K, ldc, 0, 0)) return false;
     if (HAS_VT && !gemm_flat_offsets_fit(M, N - vt_n0, K, 0, S, vt_sp)) return false;
@@ -2034,39 +2038,59 @@ bool launch_gemm_flat(pce_ctx *c, const op_t *A, const op_t *B, const float *bia
     if (tiles_n == 3 && K <= 1024) { P.sn = 1; sm_want = 8; }
     else if (tiles_n == 6) P.sn = tiles_n;
     P.sm = tiles_m < sm_want ? tiles_m : sm_want;                           // (a short batch: no padding row tiles in the walk)
-    const int lds = F_RING_BYTES + N * (int)sizeof(float);              // (N <= 6144: within what lds_optins allows)
+    const int lds = F_RING_BYTES + N * (int)sizeof(float);              // (N <= F_N_MAX: within what lds_optins allows)
     const int grid = ((c->cu_count > 0 ? c->cu_count : 256) / 8) * 8;
     KernelTimer kt(c, prof_id, nullptr, 2.0 * M * (double)N * K);
     hipLaunchKernelGGL((k_gemm_flat<EPI>), dim3((unsigned)grid), dim3(F_THREADS), lds, c->stream, P);
     return true;
 }
 
+// ---- the tiled / few-row GEMM kernels behind launch_gemm: which one runs (gemm_choose), what each can compute (gemm_fits), one launcher each
+enum GemmKernel { GK_AUTO = 0, GK_SKINNY = 1, GK_WIDE = 2, GK_128 = 3, GK_128_DEEP = 4 };      // (pce_selftest_gemm_tiled's selector)
+struct GemmShape { int M, N, K; int64_t lda; int batch; int v_col0; };
+// The shapes a kernel computes exactly.  Every tiled kernel stores whole 128-column tiles (N % 128) and walks K in whole steps: k_gemm_bf16's
+// nk = K / 64 and k_gemm_wide's K / 32 would drop a tail.  The few-row kernel: one batch entry, 256-deep K chunks, 16-byte A rows.
+template <int EPI> static bool gemm_fits(int kind, const GemmShape &s)
+{
+    switch (kind) {
+    case GK_SKINNY:
+        return (EPI == EPI_BF16 || EPI == EPI_GELU_BF16 || EPI == EPI_RESID_F32) && s.batch == 1 && s.M <= 1024 && s.N <= 4096 && s.N % S_BN == 0 &&
+               s.K % S_KC == 0 && s.lda % 8 == 0;
+    case GK_WIDE: return s.N % W_BN == 0 && s.K % W_BK == 0 && (EPI != EPI_QKV || s.v_col0 % W_BN == 0);
+    case GK_128: case GK_128_DEEP: return s.N % G_BN == 0 && s.K % G_BK == 0 && (EPI != EPI_QKV || s.v_col0 % G_BN == 0);
+    default: return false;
+    }
+}
+// The product's rule
+template <int EPI> static int gemm_choose(const pce_ctx *c, const GemmShape &s)
+{
+    // a few rows x a few thousand columns (the projections of an incremental decoding step): the latency-shaped kernel
+    // Only where the caller asks for it (the incremental decoding step): which kernel runs must not follow from the BATCH SIZE of a leg whose
+    // results are compared across batch sizes -- the few-row kernel and the tiled ones sum identically (bit-identical bias and fp32
+    // accumulate epilogues, tests/test_gpu_kernels.py) but the compiler schedules the inlined GELU differently in the two, and on fp16
+    // operands 6e-5 of the GELU outputs then round to the neighbouring value (tests/test_gpu_whisper.py::test_c3_batch_of_256_is_clip_independent)
+    if (c->gemm_skinny && c->gemm_few_rows && gemm_fits<EPI>(GK_SKINNY, s)) return GK_SKINNY;
+    // (chosen by N and K alone: the two tiled kernels round a GELU epilogue differently in a few outputs per 10^5, so the choice must not follow from M)
+    // (the vocabulary logits of a decoding step -- a few hundred rows x 51 968 columns, fp32 out -- take the deep-ring 128 x 128 kernel below: 55 against 68 us;
+    //  plain fp32 sums: the tiled kernels add the same products in the same order)
+    if (gemm_fits<EPI>(GK_WIDE, s) && s.N >= 1536 && !(EPI == EPI_F32 && (int64_t)s.M * s.batch <= 1024))     // wide outputs (QKV, fc1; from N = 1536 so
+        return GK_WIDE;                                                                                          // that the tiny model exercises it in the tests)
+    if ((int64_t)s.M * s.batch <= 1024 && s.K >= 4 * G_BK) return GK_128_DEEP;     // a few rows (incremental decoding step): few workgroups, each alone on its CU
+    return GK_128;
+}
 template <int EPI>
-void launch_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, const op_t *B, int M, int N, int K, const float *bias,
-                 void *C, int64_t ldc, int64_t c_batch, int batch, const float *pos = nullptr, int pos_T = 1, int v_col0 = 0,
-                 int vt_sp = AT_SP)
+static void launch_gemm_kernel(pce_ctx *c, int kind, const op_t *A, int64_t lda, int64_t a_batch, const op_t *B, int M, int N, int K, const float *bias,
+                               void *C, int64_t ldc, int64_t c_batch, int batch, const float *pos, int pos_T, int v_col0, int vt_sp)
 {
     if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU_BF16 || EPI == EPI_RESID_F32) {
-        // a few rows x a few thousand columns (the projections of an incremental decoding step): the latency-shaped kernel
-        // Only where the caller asks for it (the incremental decoding step): which kernel runs must not follow from the BATCH SIZE of a leg whose
-        // results are compared across batch sizes -- the few-row kernel and the tiled ones sum identically (bit-identical bias and fp32
-        // accumulate epilogues, tools/lab/skinny_vs_tiled.py) but the compiler schedules the inlined GELU differently in the two, and on fp16
-        // operands 6e-5 of the GELU outputs then round to the neighbouring value (tests/test_gpu_whisper.py::test_c3_batch_of_256_is_clip_independent)
-        if (c->gemm_skinny && c->gemm_few_rows && batch == 1 && M <= 1024 && N <= 4096 && N % S_BN == 0 && K % S_KC == 0 && lda % 8 == 0) {
+        if (kind == GK_SKINNY) {
             KernelTimer kt(c, PCE_K_GEMM_SKINNY, nullptr, 2.0 * M * (double)N * K);
             hipLaunchKernelGGL((k_gemm_skinny<EPI>), dim3((unsigned)(N / S_BN), (unsigned)div_up(M, S_BM)), dim3(S_THREADS), S_LDS, c->stream,
                                A, lda, B, M, N, K, bias, C, ldc);
             return;
         }
     }
-    const int tiles_n = N / G_BN;
-    int sn = 1;
-    for (int cand : {8, 6, 4, 3, 2}) if (tiles_n % cand == 0) { sn = cand; break; }        // supertile width (divides the N tiles)
-    // (chosen by N and K alone: the two tiled kernels round a GELU epilogue differently in a few outputs per 10^5, so the choice must not follow from M)
-    const bool wide_ok = N % W_BN == 0 && K % W_BK == 0 && (EPI != EPI_QKV || v_col0 % W_BN == 0);
-    // (the vocabulary logits of a decoding step -- a few hundred rows x 51 968 columns, fp32 out -- take the deep-ring 128 x 128 kernel below: 55 against 68 us;
-    //  plain fp32 sums: the tiled kernels add the same products in the same order)
-    if (wide_ok && N >= 1536 && !(EPI == EPI_F32 && (int64_t)M * batch <= 1024)) {      // wide outputs (QKV, fc1; from N = 1536 so that the tiny model exercises it in the tests)
+    if (kind == GK_WIDE) {
         const int wt = N / W_BN;
         int wsn = 1;
         for (int cand : {4, 3, 2}) if (wt % cand == 0) { wsn = cand; break; }
@@ -2077,15 +2101,46 @@ void launch_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, const 
                            v_col0, vt_sp, wsn, wsm);
         return;
     }
+    const int tiles_n = N / G_BN;
+    int sn = 1;
+    for (int cand : {8, 6, 4, 3, 2}) if (tiles_n % cand == 0) { sn = cand; break; }        // supertile width (divides the N tiles)
     const int sm = 16;                                     // 16 x sn measured best by a hair (645-656 TFLOP/s over 4..16 x 2..8)
     dim3 grid((unsigned)tiles_n, (unsigned)(div_up(M, G_BM * sm) * sm), (unsigned)batch);
     KernelTimer kt(c, PCE_K_GEMM128, nullptr, 2.0 * M * (double)N * K * batch);
-    if ((int64_t)M * batch <= 1024 && K >= 4 * G_BK)       // a few rows (incremental decoding step): few workgroups, each alone on its CU
+    if (kind == GK_128_DEEP)
         hipLaunchKernelGGL((k_gemm_bf16<EPI, 4>), grid, dim3(G_THREADS), 0, c->stream, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, pos, pos_T,
                            v_col0, vt_sp, sn, sm);
     else
         hipLaunchKernelGGL((k_gemm_bf16<EPI>), grid, dim3(G_THREADS), 0, c->stream, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, pos, pos_T,
                            v_col0, vt_sp, sn, sm);
+}
+template <int EPI>
+void launch_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, const op_t *B, int M, int N, int K, const float *bias,
+                 void *C, int64_t ldc, int64_t c_batch, int batch, const float *pos = nullptr, int pos_T = 1, int v_col0 = 0,
+                 int vt_sp = AT_SP)
+{
+    const int kind = gemm_choose<EPI>(c, GemmShape{M, N, K, lda, batch, v_col0});
+    launch_gemm_kernel<EPI>(c, kind, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, batch, pos, pos_T, v_col0, vt_sp);
+}
+
+// ---- LayerNorm launches: four rows (waves) per workgroup, the register form by width (k_layernorm); d <= LN_D_MAX, d % 4 == 0 (the loaders)
+template <class OUT>
+static void launch_layernorm(pce_ctx *c, const float *x, const float *w, const float *b, int64_t rows, int d, OUT *out, float eps = 1e-5f,
+                             float *out2 = nullptr, int round_in16 = 0)
+{
+    const dim3 grid((unsigned)div_up(rows, 4)), block(256);
+    if (d <= 1280) hipLaunchKernelGGL((k_layernorm<OUT, 5>), grid, block, 0, c->stream, x, w, b, rows, d, out, eps, out2, round_in16);
+    else hipLaunchKernelGGL((k_layernorm<OUT, 8>), grid, block, 0, c->stream, x, w, b, rows, d, out, eps, out2, round_in16);
+}
+template <class OUT, class RIN, class ROUT>
+static void launch_add_layernorm(pce_ctx *c, const RIN *resid_in, ROUT *resid_out, const op_t *delta, const op_t *delta2, int write_resid, const float *w,
+                                 const float *b, int64_t rows, int d, OUT *out, float eps, op_t *out_bf16)
+{
+    const dim3 grid((unsigned)div_up(rows, 4)), block(256);
+    if (d <= 1280)
+        hipLaunchKernelGGL((k_add_layernorm<OUT, RIN, ROUT, 5>), grid, block, 0, c->stream, resid_in, resid_out, delta, delta2, write_resid, w, b, rows, d, out, eps, out_bf16);
+    else
+        hipLaunchKernelGGL((k_add_layernorm<OUT, RIN, ROUT, 8>), grid, block, 0, c->stream, resid_in, resid_out, delta, delta2, write_resid, w, b, rows, d, out, eps, out_bf16);
 }
 
 // ---- the encoder-output cross-attention of a decoding step (pce_xattn.inc), as the product and pce_selftest_xattn launch it --------------------
@@ -2162,7 +2217,7 @@ static int lds_optins(pce_ctx *c, WhisperState *w)
 {
     if (w->lds_opted_in) return PCE_OK;
     const hipFuncAttribute A = hipFuncAttributeMaxDynamicSharedMemorySize;
-    const int flat = F_RING_BYTES + 6144 * (int)sizeof(float);             // the ring + the widest bias vector launch_gemm_flat admits
+    const int flat = F_RING_BYTES + F_N_MAX * (int)sizeof(float);             // the ring + the widest bias vector launch_gemm_flat admits
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_BF16>, A, flat));
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_GELU>, A, flat));
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_VT>, A, flat));
@@ -2174,6 +2229,46 @@ static int lds_optins(pce_ctx *c, WhisperState *w)
     PCE_HIP(c, xattn_optin<128>()); PCE_HIP(c, xattn_optin<256>()); PCE_HIP(c, xattn_optin<384>()); PCE_HIP(c, xattn_optin<512>());
     PCE_HIP(c, xattn_optin<768>()); PCE_HIP(c, xattn_optin<1024>()); PCE_HIP(c, xattn_optin<1280>());
     w->lds_opted_in = true;
+    return PCE_OK;
+}
+
+// pce_selftest_gemm_tiled: the kernel a selector stands for (GK_AUTO: the product's rule), or -1 where that kernel does not compute the shape
+template <int EPI> static int selftest_gemm_kind(const pce_ctx *c, int kernel, const GemmShape &s)
+{
+    const int kind = kernel == GK_AUTO ? gemm_choose<EPI>(c, s) : kernel;
+    return gemm_fits<EPI>(kind, s) ? kind : -1;
+}
+
+// pce_selftest_layernorm's k_add_layernorm forms: the stream is updated in place when it keeps its type (as the encoder runs it), else written to
+// a second buffer
+template <class OUT, class RIN, class ROUT>
+static int selftest_add_layernorm(pce_ctx *c, int64_t rows, int d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w, const float *b,
+                                  float eps, int write_resid, void *out, void *resid_out, uint16_t *out_copy)
+{
+    constexpr bool IN_PLACE = std::is_same<RIN, ROUT>::value;
+    const size_t n = (size_t)rows * d;
+    DevBuf din, dres, ddl, ddl2, dw, db, dout, dcopy;
+    PCE_HIP(c, din.reserve(sizeof(RIN) * n)); PCE_HIP(c, ddl.reserve(2 * n)); PCE_HIP(c, dw.reserve(sizeof(float) * d)); PCE_HIP(c, db.reserve(sizeof(float) * d));
+    PCE_HIP(c, dout.reserve(sizeof(OUT) * n));
+    if (!IN_PLACE) PCE_HIP(c, dres.reserve(sizeof(ROUT) * n));
+    if (delta2) PCE_HIP(c, ddl2.reserve(2 * n));
+    if (out_copy) PCE_HIP(c, dcopy.reserve(2 * n));
+    PCE_HIP(c, hipMemcpyAsync(din.p, x, sizeof(RIN) * n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(ddl.p, delta, 2 * n, hipMemcpyHostToDevice, c->stream));
+    if (delta2) PCE_HIP(c, hipMemcpyAsync(ddl2.p, delta2, 2 * n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dout.p, 0, sizeof(OUT) * n, c->stream));
+    if (!IN_PLACE) PCE_HIP(c, hipMemsetAsync(dres.p, 0, sizeof(ROUT) * n, c->stream));
+    if (out_copy) PCE_HIP(c, hipMemsetAsync(dcopy.p, 0, 2 * n, c->stream));
+    ROUT *rout = IN_PLACE ? din.as<ROUT>() : dres.as<ROUT>();
+    launch_add_layernorm<OUT, RIN, ROUT>(c, din.as<RIN>(), rout, ddl.as<op_t>(), delta2 ? ddl2.as<op_t>() : nullptr, write_resid, dw.as<float>(), db.as<float>(),
+                                         rows, d, dout.as<OUT>(), eps, out_copy ? dcopy.as<op_t>() : nullptr);
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, sizeof(OUT) * n, hipMemcpyDeviceToHost, c->stream));
+    if (resid_out) PCE_HIP(c, hipMemcpyAsync(resid_out, rout, sizeof(ROUT) * n, hipMemcpyDeviceToHost, c->stream));
+    if (out_copy) PCE_HIP(c, hipMemcpyAsync(out_copy, dcopy.p, 2 * n, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
 
@@ -2283,6 +2378,11 @@ int pce_whisper_load(pce_ctx *c, const pce_whisper_dims *dims, const float *weig
     const int d = dims->n_state, L = dims->n_layer, nm = dims->n_mels;
     if (d <= 0 || d % 128 || dims->n_head * 64 != d || L <= 0 || dims->n_ctx != W_CTX || nm <= 0 || nm > 128 || (nm % 8))
         return pce_fail(c, PCE_E_LIMIT, "unsupported encoder dims (need n_state %% 128 == 0, head size 64, n_ctx 1500, n_mels %% 8 == 0)");
+    if (d > LN_D_MAX) return pce_fail(c, PCE_E_LIMIT, "encoder with n_state %d: the LayerNorm kernels hold at most %d", d, LN_D_MAX);
+    // pce_whisper_encode_run takes the persistent GEMM for every projection when n_state % 256 == 0; its fc1 (N = 4 n_state) must fit it too
+    if (c->gemm_flat && d % F_T == 0 && 4 * d > F_N_MAX)
+        return pce_fail(c, PCE_E_LIMIT, "encoder with n_state %d: the persistent GEMM's fc1 holds 4 n_state <= %d (PCE_GEMM_FLAT=0 at pce_create runs it on the "
+                                        "tiled kernels)", d, F_N_MAX);
     const int64_t per_layer = 2LL * d + 4LL * d * d + 3LL * d + 2LL * d + 8LL * d * d + 5LL * d;
     const int64_t expect = (int64_t)d * nm * 3 + d + 3LL * d * d + d + L * per_layer + 2LL * d;
     if (n_floats != expect) return pce_fail(c, PCE_E_INVALID, "weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
@@ -2429,28 +2529,26 @@ int pce_whisper_encode_run(pce_ctx *c)
     auto add_ln = [&](size_t w_off, size_t b_off, bool mid, bool last, bool first_layer) {
         KernelTimer kt(c, PCE_K_ADD_LAYERNORM);
         const op_t *d2 = mid ? nullptr : w->delta2.as<op_t>();
-        const dim3 grid((unsigned)div_up(M, 4)), block(256);
         float *r32 = w->resid.as<float>(); op_t *r16 = w->resid16.as<op_t>();
         const float *lw = Wf + w_off, *lb = Wf + b_off;
         const int wr = mid ? 0 : 1;
         if (last) {      // ln_post: the fp32 encoder output + the op_t copy the decoder's cross K / V projections read
             float *fo = w->final_out.as<float>(); op_t *eo = w->d_enc_bf16.as<op_t>();
-            if (!resid16) hipLaunchKernelGGL((k_add_layernorm<float, float, float>), grid, block, 0, c->stream, r32, r32, w->delta.as<op_t>(), d2, 1, lw, lb, M, d, fo, 1e-5f, eo);
-            else if (first_layer) hipLaunchKernelGGL((k_add_layernorm<float, float, op_t>), grid, block, 0, c->stream, r32, r16, w->delta.as<op_t>(), d2, 1, lw, lb, M, d, fo, 1e-5f, eo);
-            else hipLaunchKernelGGL((k_add_layernorm<float, op_t, op_t>), grid, block, 0, c->stream, r16, r16, w->delta.as<op_t>(), d2, 1, lw, lb, M, d, fo, 1e-5f, eo);
+            if (!resid16) launch_add_layernorm<float, float, float>(c, r32, r32, w->delta.as<op_t>(), d2, 1, lw, lb, M, d, fo, 1e-5f, eo);
+            else if (first_layer) launch_add_layernorm<float, float, op_t>(c, r32, r16, w->delta.as<op_t>(), d2, 1, lw, lb, M, d, fo, 1e-5f, eo);
+            else launch_add_layernorm<float, op_t, op_t>(c, r16, r16, w->delta.as<op_t>(), d2, 1, lw, lb, M, d, fo, 1e-5f, eo);
         } else {
             op_t *lo = w->ln_out.as<op_t>();
-            if (!resid16) hipLaunchKernelGGL((k_add_layernorm<op_t, float, float>), grid, block, 0, c->stream, r32, r32, w->delta.as<op_t>(), d2, wr, lw, lb, M, d, lo, 1e-5f, static_cast<op_t *>(nullptr));
-            else if (first_layer) hipLaunchKernelGGL((k_add_layernorm<op_t, float, op_t>), grid, block, 0, c->stream, r32, r16, w->delta.as<op_t>(), d2, wr, lw, lb, M, d, lo, 1e-5f, static_cast<op_t *>(nullptr));
-            else hipLaunchKernelGGL((k_add_layernorm<op_t, op_t, op_t>), grid, block, 0, c->stream, r16, r16, w->delta.as<op_t>(), d2, wr, lw, lb, M, d, lo, 1e-5f, static_cast<op_t *>(nullptr));
+            if (!resid16) launch_add_layernorm<op_t, float, float>(c, r32, r32, w->delta.as<op_t>(), d2, wr, lw, lb, M, d, lo, 1e-5f, nullptr);
+            else if (first_layer) launch_add_layernorm<op_t, float, op_t>(c, r32, r16, w->delta.as<op_t>(), d2, wr, lw, lb, M, d, lo, 1e-5f, nullptr);
+            else launch_add_layernorm<op_t, op_t, op_t>(c, r16, r16, w->delta.as<op_t>(), d2, wr, lw, lb, M, d, lo, 1e-5f, nullptr);
         }
     };
     for (int l = 0; l < L; l++) {
         const WhisperState::Layer &ly = w->layers[(size_t)l];
         if (!flat || l == 0) {
             KernelTimer kt(c, PCE_K_LAYERNORM);
-            hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(M, 4)), dim3(256), 0, c->stream, w->resid.as<float>(), Wf + ly.ln1_w,
-                               Wf + ly.ln1_b, M, d, w->ln_out.as<op_t>(), 1e-5f, static_cast<float *>(nullptr), resid16 ? 1 : 0);
+            launch_layernorm<op_t>(c, w->resid.as<float>(), Wf + ly.ln1_w, Wf + ly.ln1_b, M, d, w->ln_out.as<op_t>(), 1e-5f, nullptr, resid16 ? 1 : 0);
         }
         // Q | K go to the row-major [M][2d] buffer, V is written transposed per head: one launch sweeps the LayerNorm output once
         const bool done = flat && launch_gemm_flat<FEPI_SPLIT>(c, w->ln_out.as<op_t>(), Wb + ly.qkv_w, Wf + ly.qkv_b, w->qkv.as<op_t>(), (int)M, 3 * d, d, 2 * d,
@@ -2481,16 +2579,14 @@ int pce_whisper_encode_run(pce_ctx *c)
         launch_gemm<EPI_RESID_F32>(c, w->attn.as<op_t>(), d, 0, Wb + ly.out_w, (int)M, d, d, Wf + ly.out_b, w->resid.as<float>(), d, 0, 1);
         {
             KernelTimer kt(c, PCE_K_LAYERNORM);
-            hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(M, 4)), dim3(256), 0, c->stream, w->resid.as<float>(), Wf + ly.ln2_w,
-                               Wf + ly.ln2_b, M, d, w->ln_out.as<op_t>());
+            launch_layernorm<op_t>(c, w->resid.as<float>(), Wf + ly.ln2_w, Wf + ly.ln2_b, M, d, w->ln_out.as<op_t>());
         }
         launch_gemm<EPI_GELU_BF16>(c, w->ln_out.as<op_t>(), d, 0, Wb + ly.m1_w, (int)M, 4 * d, d, Wf + ly.m1_b, w->hidden.as<op_t>(), 4 * d, 0, 1);
         launch_gemm<EPI_RESID_F32>(c, w->hidden.as<op_t>(), 4 * d, 0, Wb + ly.m2_w, (int)M, d, 4 * d, Wf + ly.m2_b, w->resid.as<float>(), d, 0, 1);
     }
     if (!flat) {
         KernelTimer kt(c, PCE_K_LAYERNORM);
-        hipLaunchKernelGGL((k_layernorm<float>), dim3((unsigned)div_up(M, 4)), dim3(256), 0, c->stream, w->resid.as<float>(), Wf + w->lnp_w,
-                           Wf + w->lnp_b, M, d, w->final_out.as<float>());
+        launch_layernorm<float>(c, w->resid.as<float>(), Wf + w->lnp_w, Wf + w->lnp_b, M, d, w->final_out.as<float>());
     }
     PCE_HIP(c, hipGetLastError());
     w->n_clips_enc = n; w->g_xkv_clips = -1; w->g_cache_len = -1; w->g_keys_n = 0; w->enc_bf16_clips = flat ? n : -1;
@@ -2600,7 +2696,8 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
     PCE_HIP(c, hipSetDevice(c->device));
     { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
     if (epilogue >= 16 && epilogue <= 19) {
-        // the tiled / few-row kernels behind launch_gemm (which of them runs follows from the shape, PCE_GEMM_SKINNY, PCE_GEMM_WIDE): 16 = bias,
+        // the tiled / few-row kernels behind launch_gemm (which of them runs follows from the shape and PCE_GEMM_SKINNY; pce_selftest_gemm_tiled
+        // chooses one and takes every epilogue): 16 = bias,
         // 17 = bias + GELU (16-bit outputs), 19 = accumulate into a zeroed fp32 matrix (out receives M * N floats)
         const bool f32 = epilogue == 19;
         DevBuf tA, tB, tC, tb;
@@ -2654,6 +2751,119 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
     return rc;
 }
 
+// Self-test hook of the tiled / few-row GEMM kernels through the product's own launch code (launch_gemm_kernel; see pce.h).  Every byte a launch
+// can address is checked against the caller's buffer lengths before anything is allocated.
+int pce_selftest_gemm_tiled(pce_ctx *c, int32_t kernel, int32_t epilogue, const uint16_t *A, int64_t a_len, int64_t lda, int64_t a_batch, int32_t batch,
+                            const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, void *C, int64_t c_len, int64_t ldc, int64_t c_batch,
+                            const float *pos, int32_t pos_T, int32_t v_col0, int32_t rows_per_clip, int32_t vt_sp, uint16_t *vt, int64_t vt_len,
+                            int32_t *kernel_used)
+{
+    if (!c || !A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || kernel < GK_AUTO || kernel > GK_128_DEEP || epilogue < EPI_BF16 || epilogue > EPI_F32)
+        return PCE_E_INVALID;
+    const bool f32 = epilogue == EPI_GELU_POS_F32 || epilogue == EPI_RESID_F32 || epilogue == EPI_F32, qkv = epilogue == EPI_QKV;
+    const int64_t nc = qkv ? v_col0 : N;                                 // row-major output columns
+    if (lda < 1 || lda % 8 || a_batch < 0 || a_batch % 8 || ldc < nc || ldc % 8 || c_batch < 0 || c_batch % 8)
+        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): lda, a_batch, ldc, c_batch must be multiples of 8 (16-byte rows), ldc >= the output columns");
+    if ((int64_t)(batch - 1) * a_batch + (int64_t)(M - 1) * lda + K > a_len)
+        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): A holds %lld elements, the shape reads beyond them", (long long)a_len);
+    if (nc > 0 && (int64_t)(batch - 1) * c_batch + (int64_t)(M - 1) * ldc + nc > c_len)
+        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): C holds %lld elements, the shape writes beyond them", (long long)c_len);
+    if (epilogue == EPI_GELU_POS_F32 && (!pos || pos_T < 1)) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): GELU_POS_F32 needs pos [pos_T][N]");
+    int64_t n_vt = 0;
+    if (qkv) {
+        // V columns [v_col0, N) leave as vt[clip][column - v_col0][t] (clip = row / rows_per_clip, t < rows_per_clip <= vt_sp): four rows per store
+        const int S = rows_per_clip;
+        if (!vt || batch != 1 || v_col0 < 0 || v_col0 >= N || (N - v_col0) % 64 || S < 4 || S % 4 || vt_sp < S || vt_sp % 4)
+            return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): QKV needs vt, batch 1, 0 <= v_col0 < N, rows_per_clip %% 4 == 0, rows_per_clip <= vt_sp, vt_sp %% 4 == 0");
+        n_vt = (int64_t)div_up(M, S) * (N - v_col0) * vt_sp;
+        if (n_vt > vt_len) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): vt holds %lld elements, the V image needs %lld", (long long)vt_len, (long long)n_vt);
+    }
+    const GemmShape s{M, N, K, lda, batch, qkv ? v_col0 : 0};
+    // refuse what the chosen kernel cannot compute before any allocation
+    const int kind = epilogue == EPI_BF16 ? selftest_gemm_kind<EPI_BF16>(c, kernel, s) : epilogue == EPI_GELU_BF16 ? selftest_gemm_kind<EPI_GELU_BF16>(c, kernel, s)
+                     : epilogue == EPI_GELU_POS_F32 ? selftest_gemm_kind<EPI_GELU_POS_F32>(c, kernel, s) : epilogue == EPI_RESID_F32 ? selftest_gemm_kind<EPI_RESID_F32>(c, kernel, s)
+                     : epilogue == EPI_QKV ? selftest_gemm_kind<EPI_QKV>(c, kernel, s) : selftest_gemm_kind<EPI_F32>(c, kernel, s);
+    if (kind < 0)
+        return pce_fail(c, PCE_E_LIMIT, "selftest gemm (tiled): kernel %d does not compute epilogue %d at M %d x N %d x K %d (lda %lld, batch %d, v_col0 %d)",
+                        kernel, epilogue, M, N, K, (long long)lda, batch, v_col0);
+    if (kernel_used) *kernel_used = kind;
+    PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    const size_t esz = f32 ? 4 : 2;
+    DevBuf dA, dB, dbias, dC, dpos, dvt;
+    PCE_HIP(c, dA.reserve(2 * (size_t)a_len)); PCE_HIP(c, dB.reserve(2 * (size_t)N * K)); PCE_HIP(c, dC.reserve(esz * (size_t)c_len + 16));
+    PCE_HIP(c, hipMemcpyAsync(dA.p, A, 2 * (size_t)a_len, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dB.p, B, 2 * (size_t)N * K, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dC.p, C, esz * (size_t)c_len, hipMemcpyHostToDevice, c->stream));       // (read by RESID_F32; kept where nothing is written)
+    if (bias) { PCE_HIP(c, dbias.reserve(sizeof(float) * N)); PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, sizeof(float) * N, hipMemcpyHostToDevice, c->stream)); }
+    if (epilogue == EPI_GELU_POS_F32) {
+        PCE_HIP(c, dpos.reserve(sizeof(float) * (size_t)pos_T * N));
+        PCE_HIP(c, hipMemcpyAsync(dpos.p, pos, sizeof(float) * (size_t)pos_T * N, hipMemcpyHostToDevice, c->stream));
+    }
+    if (qkv) { PCE_HIP(c, dvt.reserve(2 * (size_t)vt_len)); PCE_HIP(c, hipMemcpyAsync(dvt.p, vt, 2 * (size_t)vt_len, hipMemcpyHostToDevice, c->stream)); }
+    const op_t *a = dA.as<op_t>(), *b = dB.as<op_t>();
+    const float *bp = bias ? dbias.as<float>() : nullptr;
+    switch (epilogue) {
+    case EPI_BF16: launch_gemm_kernel<EPI_BF16>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
+    case EPI_GELU_BF16: launch_gemm_kernel<EPI_GELU_BF16>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
+    case EPI_GELU_POS_F32: launch_gemm_kernel<EPI_GELU_POS_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, dpos.as<float>(), pos_T, 0, 0); break;
+    case EPI_RESID_F32: launch_gemm_kernel<EPI_RESID_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
+    case EPI_QKV:        // (the V^T image travels in the pos argument, its clip length in pos_T: as the product launches it)
+        launch_gemm_kernel<EPI_QKV>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, reinterpret_cast<const float *>(dvt.as<op_t>()),
+                                    rows_per_clip, v_col0, vt_sp);
+        break;
+    default: launch_gemm_kernel<EPI_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
+    }
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(C, dC.p, esz * (size_t)c_len, hipMemcpyDeviceToHost, c->stream));
+    if (qkv) PCE_HIP(c, hipMemcpyAsync(vt, dvt.p, 2 * (size_t)vt_len, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    pce_profile_collect(c);
+    return PCE_OK;
+}
+
+// Self-test hook of the LayerNorm kernels (k_layernorm, k_add_layernorm) as the product launches them (launch_layernorm / launch_add_layernorm; see pce.h)
+int pce_selftest_layernorm(pce_ctx *c, int32_t form, int32_t rows, int32_t d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w,
+                           const float *b, float eps, int32_t flags, void *out, void *resid_out, uint16_t *out_copy)
+{
+    if (!c || !x || !w || !b || !out || rows <= 0 || form < 0 || form > 7) return PCE_E_INVALID;
+    if (d < 4 || d % 4 || d > LN_D_MAX) return pce_fail(c, PCE_E_LIMIT, "selftest layernorm: d = %d (need d %% 4 == 0, d <= %d)", d, LN_D_MAX);
+    PCE_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)rows * d;
+    if (form <= 1) {
+        // k_layernorm<float | op_t>; flags bit 0: round_in16, bit 1: out2 = x (in place, as the BERT layers write their fp32 stream), returned in resid_out
+        const bool in_place = flags & 2;
+        if (in_place && !resid_out) return PCE_E_INVALID;
+        DevBuf dx, dw, db, dout;
+        PCE_HIP(c, dx.reserve(sizeof(float) * n)); PCE_HIP(c, dw.reserve(sizeof(float) * d)); PCE_HIP(c, db.reserve(sizeof(float) * d));
+        PCE_HIP(c, dout.reserve((form ? 2 : 4) * n));
+        PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemsetAsync(dout.p, 0, (form ? 2 : 4) * n, c->stream));
+        float *o2 = in_place ? dx.as<float>() : nullptr;
+        if (form) launch_layernorm<op_t>(c, dx.as<float>(), dw.as<float>(), db.as<float>(), rows, d, dout.as<op_t>(), eps, o2, flags & 1);
+        else launch_layernorm<float>(c, dx.as<float>(), dw.as<float>(), db.as<float>(), rows, d, dout.as<float>(), eps, o2, flags & 1);
+        PCE_HIP(c, hipGetLastError());
+        PCE_HIP(c, hipMemcpyAsync(out, dout.p, (form ? 2 : 4) * n, hipMemcpyDeviceToHost, c->stream));
+        if (in_place) PCE_HIP(c, hipMemcpyAsync(resid_out, dx.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+        PCE_HIP(c, hipStreamSynchronize(c->stream));
+        return PCE_OK;
+    }
+    // k_add_layernorm<OUT, RIN, ROUT>: form 2 + 3 o + s, o = 0: fp32 output, 1: 16-bit output; s = 0: fp32 stream, 1: fp32 in / 16-bit out, 2: 16-bit stream.
+    // flags bit 2: write_resid
+    if (!delta) return PCE_E_INVALID;
+    const int o = (form - 2) / 3, st = (form - 2) % 3, wr = (flags >> 2) & 1;
+    if (o == 0) {
+        if (st == 0) return selftest_add_layernorm<float, float, float>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+        if (st == 1) return selftest_add_layernorm<float, float, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+        return selftest_add_layernorm<float, op_t, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+    }
+    if (st == 0) return selftest_add_layernorm<op_t, float, float>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+    if (st == 1) return selftest_add_layernorm<op_t, float, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+    return selftest_add_layernorm<op_t, op_t, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+}
+
 int pce_whisper_encode_fetch(pce_ctx *c, int32_t clip, float *out)
 {
     if (!c || !out) return PCE_E_INVALID;
@@ -2681,6 +2891,7 @@ int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, cons
     if (d <= 0 || d % 128 || dims->n_head * 64 != d || L <= 0 || V <= 0 || V > DR_K * DR_T || TC <= 0 || TC > 448)
         return pce_fail(c, PCE_E_LIMIT, "unsupported decoder dims (need n_state %% 128 == 0, head size 64, n_text_ctx <= 448, n_vocab <= 52224)");
     if (dims->n_head > 32) return pce_fail(c, PCE_E_LIMIT, "decoder with %d heads: the decoding kernels take at most 32", dims->n_head);
+    static_assert(32 * 64 <= LN_D_MAX, "the decoder's LayerNorms must hold 32 heads");
     const int64_t per_layer = 2LL * d + (4LL * d * d + 3LL * d) + 2LL * d + (4LL * d * d + 3LL * d) + 2LL * d + 8LL * d * d + 5LL * d;
     const int64_t expect = (int64_t)V * d + (int64_t)TC * d + L * per_layer + 2LL * d;
     if (n_floats != expect) return pce_fail(c, PCE_E_INVALID, "decoder weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
@@ -2861,14 +3072,14 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
     for (int l = 0; l < L; l++) {
         const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
         // masked self attention
-        hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(Mt, 4)), dim3(256), 0, c->stream, w->d_resid.as<float>(), Wf + ly.ln1_w,
+        launch_layernorm<op_t>(c, w->d_resid.as<float>(), Wf + ly.ln1_w,
                            Wf + ly.ln1_b, Mt, d, w->d_ln.as<op_t>());
         launch_gemm<EPI_QKV>(c, w->d_ln.as<op_t>(), d, 0, Wb + ly.qkv_w, (int)Mt, 3 * d, d, Wf + ly.qkv_b, w->d_qk.as<op_t>(), 2 * d, 0, 1,
                              reinterpret_cast<const float *>(w->d_vt.as<op_t>()), T_pad, 2 * d, SPD);
         attn(w->d_qk.as<op_t>(), 2 * d, w->d_qk.as<op_t>() + d, 2 * d, w->d_vt.as<op_t>(), (int64_t)d * SPD, SPD, T0, TL, 1);
         launch_gemm<EPI_RESID_F32>(c, w->d_attn.as<op_t>(), d, 0, Wb + ly.out_w, (int)Mt, d, d, Wf + ly.out_b, w->d_resid.as<float>(), d, 0, 1);
         // cross attention over the audio features
-        hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(Mt, 4)), dim3(256), 0, c->stream, w->d_resid.as<float>(), Wf + ly.lnx_w,
+        launch_layernorm<op_t>(c, w->d_resid.as<float>(), Wf + ly.lnx_w,
                            Wf + ly.lnx_b, Mt, d, w->d_ln.as<op_t>());
         launch_gemm<EPI_BF16>(c, w->d_ln.as<op_t>(), d, 0, Wb + ly.xq_w, (int)Mt, d, d, Wf + ly.xq_b, w->d_q.as<op_t>(), d, 0, 1);
         if (xkv_cached) { xk = w->g_xk.as<op_t>() + xk_cl * (size_t)l; xvt = w->g_xvt.as<op_t>() + xvt_cl * (size_t)l; }
@@ -2891,7 +3102,7 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
         if (!tail) break;
         launch_gemm<EPI_RESID_F32>(c, w->d_attn.as<op_t>(), d, 0, Wb + ly.xout_w, (int)Mt, d, d, Wf + ly.xout_b, w->d_resid.as<float>(), d, 0, 1);
         // MLP
-        hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(Mt, 4)), dim3(256), 0, c->stream, w->d_resid.as<float>(), Wf + ly.ln2_w,
+        launch_layernorm<op_t>(c, w->d_resid.as<float>(), Wf + ly.ln2_w,
                            Wf + ly.ln2_b, Mt, d, w->d_ln.as<op_t>());
         // fc1 on the persistent 256 x 256 kernel when the width allows it (12 column tiles x 36 row tiles at Whisper-small size: 91 -> ~55 us per
         // launch, and fc2 behind it reads a warmer cache; profiles/r05/align_fc1_flat_ab.txt) -- chosen by the model's dims alone, like every kernel
@@ -3048,7 +3259,7 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
         hipLaunchKernelGGL(k_cross_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 1600 * 4, c->stream, a);
     };
     auto cln = [&](size_t w_off, size_t b_off) {
-        hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(n, 4)), dim3(256), 0, c->stream, w->g_c_resid.as<float>(), Wf + w_off, Wf + b_off,
+        launch_layernorm<op_t>(c, w->g_c_resid.as<float>(), Wf + w_off, Wf + b_off,
                            (int64_t)n, d, w->g_c_ln.as<op_t>());
     };
     // cross-attention from the encoder output (pce_xattn.inc): E once per layer instead of K and V^T
@@ -3093,7 +3304,7 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
         launch_gemm<EPI_GELU_BF16>(c, w->g_c_ln.as<op_t>(), d, 0, Wb + ly.m1_w, n, 4 * d, d, Wf + ly.m1_b, w->g_c_hidden.as<op_t>(), 4 * d, 0, 1);
         launch_gemm<EPI_RESID_F32>(c, w->g_c_hidden.as<op_t>(), 4 * d, 0, Wb + ly.m2_w, n, d, 4 * d, Wf + ly.m2_b, w->g_c_resid.as<float>(), d, 0, 1);
     }
-    hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(n, 4)), dim3(256), 0, c->stream, w->g_c_resid.as<float>(), Wf + w->dln_w, Wf + w->dln_b,
+    launch_layernorm<op_t>(c, w->g_c_resid.as<float>(), Wf + w->dln_w, Wf + w->dln_b,
                        (int64_t)n, d, w->g_lastln.as<op_t>());
 }
 static int decode_incremental_reserve(pce_ctx *c, WhisperState *w, int n)
@@ -3283,7 +3494,7 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
         launch_attention(c, dim3((unsigned)div_up(T_pad, AT_QB), (unsigned)H, (unsigned)n), a);
     };
     auto ln = [&](size_t w_off, size_t b_off) {
-        hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(Mt, 4)), dim3(256), 0, c->stream, w->d_resid.as<float>(), Wf + w_off, Wf + b_off,
+        launch_layernorm<op_t>(c, w->d_resid.as<float>(), Wf + w_off, Wf + b_off,
                            Mt, d, w->d_ln.as<op_t>());
     };
     for (int l = 0; l < L; l++) {
@@ -3309,7 +3520,7 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
     // ---- last position -> ln -> logits = hidden . E^T (fp32, zero-initialised accumulator)
     hipLaunchKernelGGL(k_gather_last, dim3((unsigned)div_up((int64_t)n * d, 256)), dim3(256), 0, c->stream, w->d_resid.as<float>(), TL, T_pad, d, n,
                        w->g_last.as<float>());
-    hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(n, 4)), dim3(256), 0, c->stream, w->g_last.as<float>(), Wf + w->dln_w, Wf + w->dln_b,
+    launch_layernorm<op_t>(c, w->g_last.as<float>(), Wf + w->dln_w, Wf + w->dln_b,
                        (int64_t)n, d, w->g_lastln.as<op_t>());
     last_ln = w->g_lastln.as<op_t>();
     }
@@ -3442,6 +3653,7 @@ int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, i
     const int d = dims->n_state, L = dims->n_layer, V = dims->n_vocab, P = dims->n_pos, TY = dims->n_type, NL = dims->n_labels;
     if (d <= 0 || d % 128 || dims->n_head * 64 != d || L <= 0 || V <= 0 || P <= 0 || P > 512 || TY <= 0 || NL <= 0 || NL > 128)
         return pce_fail(c, PCE_E_LIMIT, "unsupported BERT dims (need n_state %% 128 == 0, head size 64, n_pos <= 512, n_labels <= 128)");
+    if (d > LN_D_MAX) return pce_fail(c, PCE_E_LIMIT, "BERT with n_state %d: the LayerNorm kernels hold at most %d", d, LN_D_MAX);
     const int64_t dd = (int64_t)d * d;
     const int64_t per_layer = 4 * (dd + d) + 2LL * d + (4 * dd + 4LL * d) + (4 * dd + d) + 2LL * d;
     const int64_t expect = ((int64_t)V + P + TY) * d + 2LL * d + L * per_layer + (int64_t)NL * (d + 1);
@@ -3545,7 +3757,7 @@ int pce_bert_run(pce_ctx *c, const int32_t *input_ids, const int32_t *offsets, i
     hipLaunchKernelGGL(k_bert_embed, dim3((unsigned)div_up(M * d, 256)), dim3(256), 0, c->stream, b.tokens.as<int>(), b.word.as<float>(),
                        b.pos.as<float>(), b.type0.as<float>(), T_pad, b.dims.n_pos, d, M, b.resid.as<float>());
     auto ln = [&](size_t w_off, size_t b_off) {                  // resid <- LN(resid) (fp32, in place) and its op_t copy
-        hipLaunchKernelGGL((k_layernorm<op_t>), dim3((unsigned)div_up(M, 4)), dim3(256), 0, c->stream, b.resid.as<float>(), Wf + w_off, Wf + b_off,
+        launch_layernorm<op_t>(c, b.resid.as<float>(), Wf + w_off, Wf + b_off,
                            M, d, b.ln.as<op_t>(), eps, b.resid.as<float>());
     };
     ln(b.lne_w, b.lne_b);

@@ -111,7 +111,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_pitch_plan", "pce_pitch_run", "pce_pitch_set_refine", "pce_pitch_fetch",
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
-           "pce_dtw", "pce_nw_align", "pce_levenshtein", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn",
+           "pce_dtw", "pce_nw_align", "pce_levenshtein", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
            "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_attention", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
@@ -183,6 +183,8 @@ def load_library() -> C.CDLL:
     lib.pce_selftest_gemm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.pce_selftest_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     lib.pce_selftest_xattn.argtypes = [vp] * 11 + [i32] * 5 + [vp]
+    lib.pce_selftest_gemm_tiled.argtypes = [vp, i32, i32, vp, i64, i64, i64, i32, vp, vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp]
+    lib.pce_selftest_layernorm.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp]
     lib.pce_whisper_encode_fetch.argtypes = [vp, i32, vp]
     lib.pce_profile_enable.argtypes = [vp, C.c_int]
     lib.pce_profile_reset.argtypes = [vp]
@@ -518,6 +520,53 @@ class ProsodyEngine:
         self._check(self._lib.pce_selftest_xattn(self._ctx, res.ctypes.data, lw.ctypes.data, lb.ctypes.data, ptr(tq), vq.ctypes.data, ptr(tk), ptr(tv), vv.ctypes.data,
                                                  ptr(tE), kl.ctypes.data, int(n), int(k_cap), int(d), int(heads), int(workgroups_per_clip), ptr(out)))
         return out.float().numpy(), tq.float().numpy(), tk.float().numpy(), tv.float().numpy(), tE.float().numpy()
+
+    def selftest_gemm_tiled(self, epilogue: int, A, B, bias, M: int, N: int, K: int, C, lda: int, ldc: int, kernel: int = 0, a_batch: int = 0,
+                            batch: int = 1, c_batch: int = 0, pos=None, v_col0: int = 0, rows_per_clip: int = 0, vt=None, vt_sp: int = 0) -> int:
+        """``pce_selftest_gemm_tiled``: one launch of the tiled / few-row GEMM kernels as the product makes it.  A (flat) and B [N][K] are uint16 bit
+        patterns of the context's operand type, bias [N] / pos [pos_T][N] float32; C (flat: uint16 for epilogues 0, 1, 4, else float32) and vt
+        (flat uint16, epilogue 4) are read and updated in place.  Returns the kernel that ran (1 few-row, 2 128 x 256, 3 / 4 128 x 128)."""
+        def arr(x, dt):
+            assert isinstance(x, np.ndarray) and x.dtype == dt and x.flags["C_CONTIGUOUS"], (None if x is None else x.dtype, dt)
+            return x
+        f32 = epilogue in (2, 3, 5)
+        A, B, C = arr(A, np.uint16), arr(B, np.uint16), arr(C, np.float32 if f32 else np.uint16)
+        assert B.size == N * K
+        bv = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        assert bv is None or bv.size == N
+        pv = None if pos is None else np.ascontiguousarray(pos, dtype=np.float32)
+        assert pv is None or pv.size % N == 0
+        if vt is not None:
+            arr(vt, np.uint16)
+        used = np.zeros(1, dtype=np.int32)
+        self._check(self._lib.pce_selftest_gemm_tiled(self._ctx, int(kernel), int(epilogue), A.ctypes.data, A.size, int(lda), int(a_batch), int(batch),
+                                                      B.ctypes.data, None if bv is None else bv.ctypes.data, int(M), int(N), int(K), C.ctypes.data, C.size,
+                                                      int(ldc), int(c_batch), None if pv is None else pv.ctypes.data, 0 if pv is None else pv.size // N,
+                                                      int(v_col0), int(rows_per_clip), int(vt_sp), None if vt is None else vt.ctypes.data,
+                                                      0 if vt is None else vt.size, used.ctypes.data))
+        return int(used[0])
+
+    def selftest_layernorm(self, form: int, x, w, b, eps: float = 1e-5, flags: int = 0, delta=None, delta2=None, want_copy: bool = False):
+        """``pce_selftest_layernorm``: form 0 / 1 = k_layernorm to fp32 / 16-bit, form 2 + 3 o + s = k_add_layernorm (o: 16-bit output; s = 0 fp32
+        stream, 1 fp32 in / 16-bit stream out, 2 16-bit stream).  x [rows][d]: float32, or uint16 bit patterns where the stream comes in 16-bit
+        (s = 2); delta / delta2 uint16 bit patterns.  Returns (out, stream after the call or None, 16-bit copy or None); 16-bit arrays as uint16."""
+        x = np.ascontiguousarray(x)
+        rows, d = x.shape
+        o, st = (form - 2) // 3, (form - 2) % 3
+        assert x.dtype == (np.uint16 if form >= 2 and st == 2 else np.float32)
+        out = np.zeros((rows, d), dtype=np.uint16 if form == 1 or (form >= 2 and o == 1) else np.float32)
+        if form <= 1:
+            resid = np.zeros((rows, d), dtype=np.float32) if flags & 2 else None
+        else:
+            resid = np.zeros((rows, d), dtype=np.float32 if st == 0 else np.uint16)
+        cp = np.zeros((rows, d), dtype=np.uint16) if want_copy else None
+        f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+        u = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.uint16)
+        w, b, delta, delta2 = f(w), f(b), u(delta), u(delta2)
+        ptr = lambda v: None if v is None else v.ctypes.data
+        self._check(self._lib.pce_selftest_layernorm(self._ctx, int(form), rows, d, x.ctypes.data, ptr(delta), ptr(delta2), w.ctypes.data, b.ctypes.data,
+                                                     float(eps), int(flags), out.ctypes.data, ptr(resid), ptr(cp)))
+        return out, resid, cp
 
     def whisper_encode_fetch(self, clip: int) -> np.ndarray:
         out = np.zeros((1500, self._wdims.n_state), dtype=np.float32)
