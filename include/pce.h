@@ -49,9 +49,10 @@ extern "C" {
  * 4 = Whisper large-v3 / turbo widths on the decoding kernels: the encoder-output cross-attention of a decoding step (and pce_selftest_xattn) at
  * d = 1280 with 20 heads, and the single-query attention kernels of an incremental step for up to 32 heads (before, more than 16 heads fell back to
  * the K / V form without a word);  5 = pce_selftest_gemm_tiled, pce_selftest_layernorm; the LayerNorm kernels hold n_state up to 2048 (before, widths
- * above 1280 loaded and returned wrong numbers) and every loader refuses a width its run path cannot compute (see the dims structs). */
+ * above 1280 loaded and returned wrong numbers) and every loader refuses a width its run path cannot compute (see the dims structs);
+ * 6 = pce_dtw_series (DTW of pairs of fp64 series, tiled over the whole device) and its two kernel ids. */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 5
+#define PCE_API_MINOR 6
 
 typedef struct pce_ctx pce_ctx;
 
@@ -423,6 +424,28 @@ int pce_whisper_decode_loop(pce_ctx *ctx, const int32_t *tokens, const int32_t *
 int pce_dtw(pce_ctx *ctx, const double *x, int32_t n_rows, int32_t n_cols, int32_t batch, int32_t *path_i, int32_t *path_j,
             int32_t *path_len);
 
+/* ---- DTW of pairs of series (scoring a synthesis against the recording) -------
+ * The dynamic programme inside fastdtw(x, y, radius = 25), which Code/Pipeline/evaluate_voice.ipynb (cell 518367fb, compute_f0_rmse) runs on
+ * the voiced log-F0 frames of an episode and of its synthesis: two 1-D series of 10^4 .. 10^5 points.  The fastdtw package is third party
+ * and absent: restated from its published source, parity unpinned.  Pair q aligns a[a_off[q] .. a_off[q+1]) (rows, n of them) with
+ * b[b_off[q] .. b_off[q+1]) (columns, m).  dt = |a[i] - b[j]|;  D[i+1][j+1] = min(D[i][j+1] + dt, D[i+1][j] + dt, D[i][j] + dt), the three
+ * SUMS compared in this order (up, left, diagonal), the first minimum wins;  D[0][0] = 0, the rest of row 0 and column 0 is +inf.
+ * win_lo / win_hi (both NULL: none) give every row of every pair, indexed like a, its columns [win_lo, win_hi), 0 <= lo <= hi <= m; cells
+ * outside are +inf.  fp64 adds and compares only: path and distance are bit-identical to a CPU restatement of these lines (this is NOT
+ * the recurrence of pce_dtw below: diagonal first on a dense matrix, float32 accumulator).
+ * path_i / path_j: the path of pair q from (0, 0) to (n - 1, m - 1) starts at element a_off[q] + b_off[q] (room n + m), path_len[q] entries;
+ * dist[q] = D[n][m].  status[q]: PCE_DTW_OK; PCE_DTW_EMPTY when n or m is 0 (path_len 0, dist NaN); PCE_DTW_NO_PATH when the window
+ * leaves D[n][m] = +inf (path_len 0, dist +inf).  NaN / infinite inputs and malformed windows are PCE_E_INVALID.
+ * No length limit: a pair is swept in tiles of PCE_DTW_SERIES_ROWS x PCE_DTW_SERIES_COLS cells, one launch per anti-diagonal of tiles over
+ * all pairs, and a pair's tiling (hence its result) depends on its own n, m and window only.  The trace takes 2 bits per cell of a swept
+ * tile (x 1.5 for the skewed layout); pairs are processed in groups whose traces fit PCE_DTW_TRACE_MB MiB together (environment, read at
+ * pce_create; default 4096), and a single pair over that budget is PCE_E_LIMIT.  Since minor 6. */
+#define PCE_DTW_SERIES_ROWS 1024
+#define PCE_DTW_SERIES_COLS 2048
+enum pce_dtw_status { PCE_DTW_OK = 0, PCE_DTW_EMPTY = 1, PCE_DTW_NO_PATH = 2 };
+int pce_dtw_series(pce_ctx *ctx, const double *a, const int64_t *a_off, const double *b, const int64_t *b_off, const int32_t *win_lo,
+                   const int32_t *win_hi, int32_t batch, int32_t *path_i, int32_t *path_j, int32_t *path_len, double *dist, int32_t *status);
+
 /* ---- batched Needleman-Wunsch word alignment ------------------------------
  * Replaces needleman_wunsch (Code/Pipeline/NeedlemanWunschAlignement.py:27-81) for a batch of sequence pairs.
  * Pair b aligns a_ids[a_off[b] .. a_off[b+1]) (rows; any number since round 5) with b_ids[b_off[b] .. b_off[b+1]); the ids are
@@ -485,7 +508,9 @@ enum pce_kernel_id {
      * ("k_gemm_flat:<shape>"; PCE_K_GEMM_FLAT keeps the launches no shape is named for) */
     PCE_K_ADD_LAYERNORM, PCE_K_STFT_RAW, PCE_K_LOGMEL_NORM, PCE_K_ATTENTION_LEAN,
     PCE_K_GEMM_FLAT_QKV, PCE_K_GEMM_FLAT_OUT, PCE_K_GEMM_FLAT_FC1, PCE_K_GEMM_FLAT_FC2, PCE_K_GEMM_FLAT_XKV,
-    PCE_K_DECODE_LOOP, PCE_K_CROSS_ATTN1, PCE_K_GEMM_SKINNY, PCE_K_LEVENSHTEIN, PCE_K_COUNT
+    PCE_K_DECODE_LOOP, PCE_K_CROSS_ATTN1, PCE_K_GEMM_SKINNY, PCE_K_LEVENSHTEIN,
+    /* minor 6: the tile sweeps and the walk back of pce_dtw_series; their work count (pce_profile_get_work) is in-window CELLS, not flops */
+    PCE_K_DTW_SERIES, PCE_K_DTW_SERIES_TRACE, PCE_K_COUNT
 };
 int pce_profile_enable(pce_ctx *ctx, int on);
 int pce_profile_reset(pce_ctx *ctx);

@@ -139,6 +139,7 @@ pce_ctx *pce_create(int device, void *stream, char *err, size_t errlen)
         c->resid16 = c->whisper_ops == 2;
     }
     c->pitch_refine_praat = getenv("PCE_PITCH_REFINE") && !strcmp(getenv("PCE_PITCH_REFINE"), "praat");
+    if (getenv("PCE_DTW_TRACE_MB") && atoll(getenv("PCE_DTW_TRACE_MB")) > 0) c->dtw_trace_budget = (size_t)atoll(getenv("PCE_DTW_TRACE_MB")) << 20;
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     for (int si = 0; si < pce_ctx::SIDE_COUNT; si++) {
@@ -351,7 +352,7 @@ const char *pce_kernel_name(int id)
         "k_gemm_bf16", "k_gemm_wide", "k_attention", "k_layernorm", "k_gemm_flat",
         "k_add_layernorm", "k_stft_raw", "k_logmel_norm", "k_attention_lean",
         "k_gemm_flat:qkv", "k_gemm_flat:out", "k_gemm_flat:fc1", "k_gemm_flat:fc2", "k_gemm_flat:xkv",
-        "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein"};
+        "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace"};
     return (id >= 0 && id < PCE_K_COUNT) ? names[id] : "?";
 }
 

@@ -138,6 +138,10 @@ struct pce_ctx {
     std::vector<int64_t> py_off;
     bool py_ran = false;
 
+    // DTW of series pairs (pce_dtw_series.hip): the batch's inputs and results, the tables of the group in flight, its boundary rows / columns and trace
+    struct DtwSeries { DevBuf a, b, lo, hi, pi, pj, dist, len, status, pairs, tab, tiles, rows, cols, trace; } ds;
+    size_t dtw_trace_budget = (size_t)4096 << 20;   // PCE_DTW_TRACE_MB at pce_create: bytes of trace one group of pairs may hold
+
     // whisper / BERT state, opaque (pce_whisper_impl.inc): one slot per operand-type build (0: bf16, 1: fp16); whisper_ops selects the build the
     // entry points of include/pce.h forward to (pce_whisper_set_operands, or PCE_WHISPER_OPERANDS=fp16 at pce_create)
     void *whisper_slot[2] = {nullptr, nullptr};

@@ -95,13 +95,15 @@ assert SLICE_DTYPE.itemsize == C.sizeof(Slice) and ENERGY_DTYPE.itemsize == C.si
 assert SUMMARY_DTYPE.itemsize == C.sizeof(PitchSummary)
 
 SLICE_OK, SLICE_TOO_SHORT, SLICE_EMPTY = 0, 1, 2
+DTW_OK, DTW_EMPTY, DTW_NO_PATH = 0, 1, 2                      # enum pce_dtw_status
+DTW_SERIES_ROWS, DTW_SERIES_COLS = 1024, 2048                 # PCE_DTW_SERIES_ROWS / _COLS of include/pce.h: the tile of k_dtw_series
 
 KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs_gate",
               "k_pitch_refine", "k_pitch_frames", "k_pitch_path", "k_pitch_median", "k_pitch_delta", "k_stft_max", "k_stft_db", "k_logmel_frames", "whisper_encoder", "k_resample", "k_dtw", "whisper_align", "k_nw", "k_stft_norm", "k_frame_energy", "bert_forward", "k_pyin_frames", "k_pyin_viterbi", "whisper_decode_step",
               "k_gemm_bf16", "k_gemm_wide", "k_attention", "k_layernorm", "k_gemm_flat",
               "k_add_layernorm", "k_stft_raw", "k_logmel_norm", "k_attention_lean",
               "k_gemm_flat:qkv", "k_gemm_flat:out", "k_gemm_flat:fc1", "k_gemm_flat:fc2", "k_gemm_flat:xkv",
-              "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
+              "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
 # every symbol include/pce.h declares
 EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_version", "pce_api_minor", "pce_device_info",
@@ -111,7 +113,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_pitch_plan", "pce_pitch_run", "pce_pitch_set_refine", "pce_pitch_fetch",
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
-           "pce_dtw", "pce_nw_align", "pce_levenshtein", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
+           "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
            "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_attention", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
@@ -160,6 +162,7 @@ def load_library() -> C.CDLL:
     lib.pce_resample_run.argtypes = [vp, i32, i32, vp, i32, i64]
     lib.pce_download_pcm_s16.argtypes = [vp, vp, vp, C.POINTER(i32)]
     lib.pce_dtw.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+    lib.pce_dtw_series.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.pce_whisper_decoder_load.argtypes = [vp, C.POINTER(WhisperTextDims), vp, i64]
     lib.pce_whisper_align_run.argtypes = [vp, vp, vp, vp, i32, vp, i32, C.c_float]
     lib.pce_whisper_align_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -634,6 +637,41 @@ class ProsodyEngine:
         self._check(self._lib.pce_dtw(self._ctx, x.ctypes.data, n, m, b, pi.ctypes.data, pj.ctypes.data, pl.ctypes.data))
         return [(pi[k, :pl[k]].copy(), pj[k, :pl[k]].copy()) for k in range(b)]
 
+    def dtw_series(self, pairs, windows=None):
+        """DTW of a batch of pairs of 1-D float64 series with the cost ``|a_i - b_j|`` formed on the device (``pce_dtw_series``: the
+        dynamic programme of ``fastdtw``, candidates up / left / diagonal, first minimum).  ``pairs`` = [(a, b), ...]; ``windows`` = None
+        or one entry per pair, each None or ``(lo, hi)``: int arrays giving every row of ``a`` its columns ``[lo, hi)``.
+        -> [(path int32 [k, 2], dist float, status), ...]; status ``DTW_EMPTY``: a side is empty (no path, dist NaN), ``DTW_NO_PATH``:
+        the window admits no path (dist inf)."""
+        nb = len(pairs)
+        if not nb:
+            return []
+        xs = [np.ascontiguousarray(p[0], dtype=np.float64).reshape(-1) for p in pairs]
+        ys = [np.ascontiguousarray(p[1], dtype=np.float64).reshape(-1) for p in pairs]
+        ao = np.zeros(nb + 1, dtype=np.int64); bo = np.zeros(nb + 1, dtype=np.int64)
+        np.cumsum([len(x) for x in xs], out=ao[1:]); np.cumsum([len(y) for y in ys], out=bo[1:])
+        a = np.concatenate(xs + [np.zeros(1)]); b = np.concatenate(ys + [np.zeros(1)])
+        lo = hi = None
+        if windows is not None and any(w is not None for w in windows):
+            if len(windows) != nb:
+                raise ValueError("windows: one entry (or None) per pair")
+            lo = np.zeros(int(ao[-1]) + 1, dtype=np.int32); hi = np.zeros(int(ao[-1]) + 1, dtype=np.int32)
+            for k, w in enumerate(windows):
+                if w is None:
+                    hi[ao[k]:ao[k + 1]] = len(ys[k])
+                    continue
+                wl = np.asarray(w[0]); wh = np.asarray(w[1])
+                if wl.shape != (len(xs[k]),) or wh.shape != (len(xs[k]),):
+                    raise ValueError(f"windows[{k}]: one [lo, hi) per row of the pair's first series")
+                lo[ao[k]:ao[k + 1]] = wl; hi[ao[k]:ao[k + 1]] = wh
+        oo = ao + bo
+        pi = np.zeros(int(oo[-1]) + 1, dtype=np.int32); pj = np.zeros_like(pi)
+        pl = np.zeros(nb, dtype=np.int32); dist = np.zeros(nb, dtype=np.float64); st = np.zeros(nb, dtype=np.int32)
+        self._check(self._lib.pce_dtw_series(self._ctx, a.ctypes.data, ao.ctypes.data, b.ctypes.data, bo.ctypes.data,
+                                             lo.ctypes.data if lo is not None else None, hi.ctypes.data if hi is not None else None, nb,
+                                             pi.ctypes.data, pj.ctypes.data, pl.ctypes.data, dist.ctypes.data, st.ctypes.data))
+        return [(np.stack([pi[oo[k]:oo[k] + pl[k]], pj[oo[k]:oo[k] + pl[k]]], axis=1), float(dist[k]), int(st[k])) for k in range(nb)]
+
     def frame_energy_run(self, window: int, hop: int = None, requantize: bool = False):
         """Exact integer energy of every analysis window of every clip (k_frame_energy): frame k covers
         [k*hop, min(k*hop + window, n)); hop defaults to window (auditok's blocks)."""
@@ -754,6 +792,22 @@ class ProsodyEngine:
             cps = [np.frombuffer(s.encode("utf-32-le", "surrogatepass"), dtype=np.uint32) for s in strings]
             off = np.zeros(len(cps) + 1, dtype=np.int64); np.cumsum([len(x) for x in cps], out=off[1:])
             return np.ascontiguousarray(np.concatenate(cps + [np.zeros(0, np.uint32)])), off
+        a, ao = pack([p[0] for p in pairs]); b, bo = pack([p[1] for p in pairs])
+        out = np.zeros(len(pairs), dtype=np.int32)
+        self._check(self._lib.pce_levenshtein(self._ctx, a.ctypes.data if a.size else None, ao.ctypes.data, b.ctypes.data if b.size else None,
+                                              bo.ctypes.data, len(pairs), out.ctypes.data))
+        return out
+
+    def levenshtein_ids(self, pairs):
+        """``pce_levenshtein`` on sequences of arbitrary uint32 symbols (word ids: the edit distance behind a word error rate):
+        ``pairs`` = [(ids_a, ids_b), ...] -> int32 array."""
+        if not len(pairs):
+            return np.zeros(0, dtype=np.int32)
+
+        def pack(seqs):
+            seqs = [np.ascontiguousarray(s, dtype=np.uint32).reshape(-1) for s in seqs]
+            off = np.zeros(len(seqs) + 1, dtype=np.int64); np.cumsum([len(x) for x in seqs], out=off[1:])
+            return np.ascontiguousarray(np.concatenate(seqs + [np.zeros(0, np.uint32)])), off
         a, ao = pack([p[0] for p in pairs]); b, bo = pack([p[1] for p in pairs])
         out = np.zeros(len(pairs), dtype=np.int32)
         self._check(self._lib.pce_levenshtein(self._ctx, a.ctypes.data if a.size else None, ao.ctypes.data, b.ctypes.data if b.size else None,
