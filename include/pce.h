@@ -50,9 +50,10 @@ extern "C" {
  * d = 1280 with 20 heads, and the single-query attention kernels of an incremental step for up to 32 heads (before, more than 16 heads fell back to
  * the K / V form without a word);  5 = pce_selftest_gemm_tiled, pce_selftest_layernorm; the LayerNorm kernels hold n_state up to 2048 (before, widths
  * above 1280 loaded and returned wrong numbers) and every loader refuses a width its run path cannot compute (see the dims structs);
- * 6 = pce_dtw_series (DTW of pairs of fp64 series, tiled over the whole device) and its two kernel ids. */
+ * 6 = pce_dtw_series (DTW of pairs of fp64 series, tiled over the whole device) and its two kernel ids;
+ * 7 = pce_intensity_plan / _run / _fetch (Praat's Sound_to_Intensity over slices, with per-slice summaries) and their two kernel ids. */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 6
+#define PCE_API_MINOR 7
 
 typedef struct pce_ctx pce_ctx;
 
@@ -200,6 +201,46 @@ enum { PCE_REFINE_SEEDED = 0, PCE_REFINE_PRAAT = 1 };
 int pce_pitch_set_refine(pce_ctx *ctx, int32_t mode);
 /* f0 / strength: ragged [frame_offsets[n_slices]], either may be NULL. */
 int pce_pitch_fetch(pce_ctx *ctx, double *f0, double *strength, pce_pitch_summary *summary /* n_slices */);
+
+/* ---- Praat intensity ------------------------------------------------------
+ * Replaces parselmouth Sound.to_intensity() as Code/visualisation/Compare_speech_noenhanced.py calls it (extract_mean_volume :19-26, the
+ * 'volume' branch of plot_zscore_feature / plot_raw_feature :166-168, :300-302): Praat's Sound_to_Intensity over slices of the resident
+ * batch, sample values x / 32768, everything in fp64.  parselmouth and the Praat sources are absent: restated from the published
+ * algorithm, parity with Praat unpinned (checked by known answers only).
+ *   window = 6.4 / pitch_floor, half = window / 2, hs = floor(half / dx): 2 hs + 1 taps
+ *   taps[k + hs] = I0f((2 pi^2 + 0.5) sqrt(max(0, 1 - (k dx / half)^2))), I0f = Praat's NUMbessel_i0_f (Abramowitz-Stegun 9.8.1 / 9.8.2);
+ *   the table is host logic (hostrules.intensity_window) and is handed to the run call: n_taps != 2 hs + 1 is PCE_E_INVALID;
+ *   frames by Sampled_shortTermAnalysis (the rule of the pitch plan entry) with this window and dt = time_step: window > n dx is
+ *   PCE_SLICE_TOO_SHORT, no samples PCE_SLICE_EMPTY, n_frames = floor((n dx - window) / dt) + 1;
+ *   frame f: centre = the sample nearest t1 + f dt, span = centre +- hs CLIPPED to the slice (Praat clips here: the weight sum shrinks
+ *   with the clip; samples of the slice that lie outside its clip are zeros as everywhere else); with subtract_mean the unweighted mean of
+ *   the span is removed first (exact integer numerator: a constant signal gives exactly zero);
+ *   I = sum (a - mean)^2 w / sum w / 4e-10;  value = -300 when I < 1e-30, else 10 log10 I.
+ * A frame's bits depend on its own samples and the table only (lane-strided sums, a fixed reduction tree, no atomics), not on the batch.
+ * Limit: at most 6145 taps (pitch_floor >= 50 Hz at 48 kHz, >= 16.7 Hz at 16 kHz); more is PCE_E_LIMIT from the run call. */
+typedef struct pce_intensity_params {
+    double  pitch_floor;      /* 100.0 (Praat: minimum pitch)                 */
+    double  time_step;        /* <= 0: 0.8 / pitch_floor                      */
+    int32_t subtract_mean;    /* 1                                            */
+    int32_t reserved;
+} pce_intensity_params;
+
+typedef struct pce_intensity_summary {
+    int64_t n_frames;         /* 0 when status != PCE_SLICE_OK                             */
+    int64_t n_positive;       /* frames with a value > 0                                   */
+    double  mean_positive;    /* mean of those values (fixed order), NaN when none         */
+    double  t1;               /* centre time of the first frame                            */
+    int32_t status;           /* pce_slice_status                                          */
+    int32_t reserved;
+} pce_intensity_summary;
+
+/* Host-only sizing: frame_offsets[n_slices+1] (prefix sum of frame counts); status may be NULL. */
+int pce_intensity_plan(pce_ctx *ctx, const pce_intensity_params *p, const pce_slice *slices, int32_t n_slices,
+                       int64_t *frame_offsets, int32_t *status);
+int pce_intensity_run(pce_ctx *ctx, const pce_intensity_params *p, const double *taps, int32_t n_taps, const pce_slice *slices,
+                      int32_t n_slices);
+/* values: ragged [frame_offsets[n_slices]] dB, may be NULL (a corpus run downloads 40 bytes per slice); summary [n_slices], may be NULL. */
+int pce_intensity_fetch(pce_ctx *ctx, double *values, pce_intensity_summary *summary);
 
 /* ---- R10: STFT magnitude in dB -----------------------------------------
  * Replaces librosa.amplitude_to_db(np.abs(librosa.stft(y, n_fft, hop_length)),
@@ -510,7 +551,9 @@ enum pce_kernel_id {
     PCE_K_GEMM_FLAT_QKV, PCE_K_GEMM_FLAT_OUT, PCE_K_GEMM_FLAT_FC1, PCE_K_GEMM_FLAT_FC2, PCE_K_GEMM_FLAT_XKV,
     PCE_K_DECODE_LOOP, PCE_K_CROSS_ATTN1, PCE_K_GEMM_SKINNY, PCE_K_LEVENSHTEIN,
     /* minor 6: the tile sweeps and the walk back of pce_dtw_series; their work count (pce_profile_get_work) is in-window CELLS, not flops */
-    PCE_K_DTW_SERIES, PCE_K_DTW_SERIES_TRACE, PCE_K_COUNT
+    PCE_K_DTW_SERIES, PCE_K_DTW_SERIES_TRACE,
+    /* minor 7 */
+    PCE_K_INTENSITY, PCE_K_INTENSITY_SUMMARY, PCE_K_COUNT
 };
 int pce_profile_enable(pce_ctx *ctx, int on);
 int pce_profile_reset(pce_ctx *ctx);

@@ -8,6 +8,6 @@ mirrors of the reference modules (``Pipeline``, ``Aligners``, ``Preprocessing``)
 There is no CPU fallback: constructing :class:`ProsodyEngine` without the built library
 or without a GPU raises.
 """
-from .engine import ProsodyEngine, PceError, build_native, native_library_path, PitchParams  # noqa: F401
+from .engine import ProsodyEngine, PceError, build_native, native_library_path, PitchParams, IntensityParams  # noqa: F401
 
-__all__ = ["ProsodyEngine", "PceError", "build_native", "native_library_path", "PitchParams"]
+__all__ = ["ProsodyEngine", "PceError", "build_native", "native_library_path", "PitchParams", "IntensityParams"]

@@ -138,6 +138,21 @@ struct pce_ctx {
     std::vector<int64_t> py_off;
     bool py_ran = false;
 
+    // Praat intensity (pce_intensity.hip): slice table, runs of frames, the tap table, the ragged contour, per-slice {n_positive, mean_positive}
+    DevBuf in_meta, in_work, in_taps, in_out, in_summary;
+    SliceCache in_cache;
+    pce_intensity_params in_params;
+    bool in_params_valid = false;
+    std::vector<double> in_taps_host;    // the table the plan was made for
+    int in_hs = 0, in_fpb = 0, in_span = 0;
+    double in_dt = 0.0;
+    size_t in_lds = 0;
+    int64_t in_n_work = 0, in_total_frames = 0;
+    int32_t in_n = -1;
+    std::vector<int64_t> in_frame_off;
+    std::vector<int32_t> in_status;
+    std::vector<double> in_t1;
+
     // DTW of series pairs (pce_dtw_series.hip): the batch's inputs and results, the tables of the group in flight, its boundary rows / columns and trace
     struct DtwSeries { DevBuf a, b, lo, hi, pi, pj, dist, len, status, pairs, tab, tiles, rows, cols, trace; } ds;
     size_t dtw_trace_budget = (size_t)4096 << 20;   // PCE_DTW_TRACE_MB at pce_create: bytes of trace one group of pairs may hold

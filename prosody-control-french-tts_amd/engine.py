@@ -64,6 +64,20 @@ class PitchSummary(C.Structure):
                 ("t1", C.c_double), ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class IntensityParams(C.Structure):
+    _fields_ = [("pitch_floor", C.c_double), ("time_step", C.c_double), ("subtract_mean", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def praat(cls, pitch_floor=100.0, time_step=0.0, subtract_mean=True):
+        """parselmouth ``Sound.to_intensity(minimum_pitch, time_step, subtract_mean)`` defaults."""
+        return cls(float(pitch_floor), time_step or 0.0, 1 if subtract_mean else 0, 0)
+
+
+class IntensitySummary(C.Structure):
+    _fields_ = [("n_frames", C.c_int64), ("n_positive", C.c_int64), ("mean_positive", C.c_double), ("t1", C.c_double),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
 class WhisperDims(C.Structure):
     _fields_ = [("n_mels", C.c_int32), ("n_ctx", C.c_int32), ("n_state", C.c_int32), ("n_head", C.c_int32), ("n_layer", C.c_int32)]
 
@@ -93,6 +107,9 @@ SUMMARY_DTYPE = np.dtype([("n_frames", "<i8"), ("n_voiced", "<i8"), ("median_f0"
                           ("t1", "<f8"), ("status", "<i4"), ("reserved", "<i4")])
 assert SLICE_DTYPE.itemsize == C.sizeof(Slice) and ENERGY_DTYPE.itemsize == C.sizeof(Energy)
 assert SUMMARY_DTYPE.itemsize == C.sizeof(PitchSummary)
+INTENSITY_SUMMARY_DTYPE = np.dtype([("n_frames", "<i8"), ("n_positive", "<i8"), ("mean_positive", "<f8"), ("t1", "<f8"),
+                                    ("status", "<i4"), ("reserved", "<i4")])
+assert INTENSITY_SUMMARY_DTYPE.itemsize == C.sizeof(IntensitySummary) == 40 and C.sizeof(IntensityParams) == 24
 
 SLICE_OK, SLICE_TOO_SHORT, SLICE_EMPTY = 0, 1, 2
 DTW_OK, DTW_EMPTY, DTW_NO_PATH = 0, 1, 2                      # enum pce_dtw_status
@@ -103,7 +120,8 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "k_gemm_bf16", "k_gemm_wide", "k_attention", "k_layernorm", "k_gemm_flat",
               "k_add_layernorm", "k_stft_raw", "k_logmel_norm", "k_attention_lean",
               "k_gemm_flat:qkv", "k_gemm_flat:out", "k_gemm_flat:fc1", "k_gemm_flat:fc2", "k_gemm_flat:xkv",
-              "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
+              "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace",
+              "k_intensity", "k_intensity_summary"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
 # every symbol include/pce.h declares
 EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_version", "pce_api_minor", "pce_device_info",
@@ -111,6 +129,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_energy_run", "pce_energy_fetch", "pce_lufs_set_meter_rate", "pce_lufs_run", "pce_lufs_fetch",
            "pce_frame_energy_run", "pce_frame_energy_shape", "pce_frame_energy_fetch", "pce_pyin_run", "pce_pyin_shape", "pce_pyin_fetch",
            "pce_pitch_plan", "pce_pitch_run", "pce_pitch_set_refine", "pce_pitch_fetch",
+           "pce_intensity_plan", "pce_intensity_run", "pce_intensity_fetch",
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
            "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
@@ -151,6 +170,9 @@ def load_library() -> C.CDLL:
     lib.pce_pitch_plan.argtypes = [vp, C.POINTER(PitchParams), vp, i32, vp, vp]
     lib.pce_pitch_run.argtypes = [vp, C.POINTER(PitchParams), vp, i32]
     lib.pce_pitch_fetch.argtypes = [vp, vp, vp, vp]
+    lib.pce_intensity_plan.argtypes = [vp, C.POINTER(IntensityParams), vp, i32, vp, vp]
+    lib.pce_intensity_run.argtypes = [vp, C.POINTER(IntensityParams), vp, i32, vp, i32]
+    lib.pce_intensity_fetch.argtypes = [vp, vp, vp]
     lib.pce_stats_enqueue.argtypes = [vp, i32]
     lib.pce_nw_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.pce_levenshtein.argtypes = [vp, vp, vp, vp, vp, i32, vp]
@@ -349,6 +371,42 @@ class ProsodyEngine:
     def pitch(self, slices, params: PitchParams, want_f0=True, want_strength=False):
         self.pitch_run(slices, params)
         return self.pitch_fetch(want_f0, want_strength)
+
+    def intensity_plan(self, slices, params: IntensityParams):
+        """Host-only sizing of a Praat intensity analysis -> (frame_offsets int64 [n + 1], status int32 [n])."""
+        s = self._slices(slices)
+        off = np.zeros(len(s) + 1, dtype=np.int64); st = np.zeros(len(s), dtype=np.int32)
+        self._check(self._lib.pce_intensity_plan(self._ctx, C.byref(params), s.ctypes.data, len(s), off.ctypes.data, st.ctypes.data))
+        return off, st
+
+    def intensity_run(self, slices, params: IntensityParams):
+        """Enqueue Praat's ``Sound_to_Intensity`` over ``slices`` (``pce_intensity_run``); the window's tap table is built here
+        (``hostrules.intensity_window``, kept per (rate, pitch floor)) and travels with the call.  A repeated call with the same slices,
+        parameters and table skips the host plan."""
+        from .hostrules import intensity_window
+        key = (self.rate, float(params.pitch_floor))
+        cache = self.__dict__.setdefault("_in_windows", {})
+        if key not in cache:
+            cache.clear()
+            cache[key] = np.ascontiguousarray(intensity_window(self.rate, float(params.pitch_floor))[1], dtype=np.float64)
+        taps = cache[key]
+        s = self._slices(slices); self._in_slices = s; self._in_params = params
+        self._check(self._lib.pce_intensity_run(self._ctx, C.byref(params), taps.ctypes.data, len(taps), s.ctypes.data, len(s)))
+
+    def intensity_fetch(self, want_contour=True):
+        """-> {"values": ragged float64 dB contour or None, "frame_offsets", "summary": INTENSITY_SUMMARY_DTYPE [n]}; without the
+        contour a slice costs 40 bytes of download."""
+        s = self._in_slices
+        off, _ = self.intensity_plan(s, self._in_params)
+        vals = np.zeros(int(off[-1]), dtype=np.float64) if want_contour else None
+        summ = np.zeros(len(s), dtype=INTENSITY_SUMMARY_DTYPE)
+        self._check(self._lib.pce_intensity_fetch(self._ctx, vals.ctypes.data if want_contour and vals.size else None, summ.ctypes.data))
+        return {"values": vals, "frame_offsets": off, "summary": summ}
+
+    def intensity(self, slices, params: IntensityParams = None, want_contour=True):
+        """parselmouth ``Sound.to_intensity()`` of every slice: ``values[frame_offsets[i]:frame_offsets[i + 1]]`` is slice i's contour."""
+        self.intensity_run(slices, params if params is not None else IntensityParams.praat())
+        return self.intensity_fetch(want_contour)
 
     def stats_enqueue(self, slot: int = 0):
         """Queue the device-to-host copies of the last energy / LUFS / pitch-summary results behind their

@@ -148,3 +148,47 @@ def resample_filter(rate_in: int, rate_out: int, beta: float = 5.0):
     # scipy adds post padding until the filtered length covers n_out + n_pre_remove; harmless extra zeros here
     taps = np.concatenate([np.zeros(n_pre_pad), h, np.zeros(down)])
     return up, down, taps, int(n_pre_remove)
+
+
+# ---------------------------------------------------------------- Praat intensity window (host-side table)
+def bessel_i0_f(x):
+    """Praat's ``NUMbessel_i0_f``: the Abramowitz-Stegun polynomials 9.8.1 (``|x| < 3.75``, stated accuracy 1.6e-7) and 9.8.2
+    (beyond, 1.9e-7 on the polynomial factor).  Not an exact Bessel function: the window of ``Sound_to_Intensity`` is made of these."""
+    x = np.abs(np.asarray(x, dtype=np.float64))
+    small = x < 3.75
+    t = np.where(small, x / 3.75, 0.0)
+    t = t * t
+    lo = 1.0 + t * (3.5156229 + t * (3.0899424 + t * (1.2067492 + t * (0.2659732 + t * (0.0360768 + t * 0.0045813)))))
+    xs = np.where(small, 3.75, x)                                # (keeps the unused branch finite)
+    t = 3.75 / xs
+    hi = np.exp(xs) / np.sqrt(xs) * (0.39894228 + t * (0.01328592 + t * (0.00225319 + t * (-0.00157565 + t * (0.00916281
+         + t * (-0.02057706 + t * (0.02635537 + t * (-0.01647633 + t * 0.00392377))))))))
+    return np.where(small, lo, hi)
+
+
+def intensity_window(rate: int, pitch_floor: float = 100.0):
+    """Tap table of Praat's ``Sound_to_Intensity`` -> (half_samples, taps float64 [2 * half_samples + 1]): physical window
+    ``6.4 / pitch_floor``, ``taps[k + hs] = I0f((2 pi^2 + 0.5) sqrt(max(0, 1 - (k dx / half)^2)))``.  ``pce_intensity_run`` takes
+    this table, so the kernel and a checker weigh with the same doubles."""
+    dx = 1.0 / rate
+    half = 0.5 * (6.4 / pitch_floor)
+    hs = int(math.floor(half / dx))
+    x = np.arange(-hs, hs + 1, dtype=np.float64) * dx / half
+    root = np.sqrt(np.maximum(0.0, 1.0 - x * x))
+    return hs, bessel_i0_f((2.0 * math.pi * math.pi + 0.5) * root)
+
+
+def intensity_frames(n: int, rate: int, x1: float, pitch_floor: float = 100.0, time_step: float = 0.0):
+    """``Sampled_shortTermAnalysis`` for Praat's intensity (what ``pce_intensity_plan`` computes): -> (n_frames, t1, dt), n_frames 0
+    where Praat refuses the sound (shorter than the window ``6.4 / pitch_floor``)."""
+    dx = 1.0 / rate
+    window = 6.4 / pitch_floor
+    dt = 0.8 / pitch_floor if time_step <= 0.0 else float(time_step)
+    dur = dx * float(n)
+    if n < 1 or window > dur:
+        return 0, 0.0, dt
+    nf = int(math.floor((dur - window) / dt)) + 1
+    if nf < 1:
+        return 0, 0.0, dt
+    t1 = (x1 - 0.5 * dx + 0.5 * dur) - 0.5 * (float(nf) * dt) + 0.5 * dt
+    return nf, t1, dt
