@@ -51,9 +51,11 @@ extern "C" {
  * the K / V form without a word);  5 = pce_selftest_gemm_tiled, pce_selftest_layernorm; the LayerNorm kernels hold n_state up to 2048 (before, widths
  * above 1280 loaded and returned wrong numbers) and every loader refuses a width its run path cannot compute (see the dims structs);
  * 6 = pce_dtw_series (DTW of pairs of fp64 series, tiled over the whole device) and its two kernel ids;
- * 7 = pce_intensity_plan / _run / _fetch (Praat's Sound_to_Intensity over slices, with per-slice summaries) and their two kernel ids. */
+ * 7 = pce_intensity_plan / _run / _fetch (Praat's Sound_to_Intensity over slices, with per-slice summaries) and their two kernel ids;
+ * 8 = pce_selftest_attn1 (the single-query attention kernels of a decoding step) and pce_selftest_attention_ragged; pce_selftest_attention launches
+ * through the product's rule (one query block: the streaming instantiation). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 7
+#define PCE_API_MINOR 8
 
 typedef struct pce_ctx pce_ctx;
 
@@ -316,6 +318,25 @@ int pce_selftest_gemm(pce_ctx *ctx, const uint16_t *A, const uint16_t *B, const 
  * path only.  *fell_back (may be NULL): number of workgroups that had to take the exact path (mode 0). */
 int pce_selftest_attention(pce_ctx *ctx, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, int32_t q_len,
                            int32_t k_len, int32_t causal, int32_t mode, uint16_t *out, int32_t *fell_back);
+/* The same kernel with per-clip lengths, through the launch the teacher-forced decoder makes (grid of the longest clip; one query block takes the
+ * streaming instantiation): the rows of the clips lie back to back, q [sum q_len][heads * 64], k and v [sum k_len][heads * 64], q_len / k_len [clips]
+ * >= 1.  out [out_rows][heads * 64], out_rows >= sum q_len, is read and written back whole: rows no query owns keep the caller's values.
+ * pce_selftest_attention is this call with equal lengths and a zeroed out.  Since minor 8. */
+int pce_selftest_attention_ragged(pce_ctx *ctx, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, const int32_t *q_len,
+                                  const int32_t *k_len, int32_t causal, int32_t mode, uint16_t *out, int64_t out_rows, int32_t *fell_back);
+/* Self-test of the single-query attention kernels of an incremental decoding step (one query per clip and head, 64-wide heads, d = heads * 64) on
+ * host arrays of 16-bit patterns of the context's operand type, through the launches the decoding step makes (head groups of at most 16 waves).
+ *   form 0: k_cross_attn1w over given keys.  q [n][d]; k: key rows [.][d], clip i reads rows k_row0[i] .. + len[i]; v: the V^T image [n][d][span]
+ *           WHOLE, padding columns included (span = its pitch, a multiple of 8; columns >= len[i] must be finite); 1 <= len[i] <= 1536.
+ *   form 1: k_cross_attn1w appending.  q = q | k | v of the new position [n][3 d]; k: K cache [n][span][d]; v: V^T cache [n][d][512]; len[i] = the
+ *           position (row / column the new key / value are written to; keys 0 .. len[i] are attended to); span = T_cap <= 512.  k_row0 unused.
+ *   form 2: k_self_attn1w.  As form 1 with v: the row-major V cache [n][span][d].
+ * skip [n] (may be NULL): a clip with skip != 0 is left alone.  out [n][d] is read and written back whole, and in forms 1 and 2 so are k and v (the
+ * caches after the call): what a launch does not write keeps the caller's values.  PCE_E_INVALID, before anything is launched, for more than 32
+ * heads, len out of range (form 0: < 1, > 1536 or past the image's pitch; forms 1 / 2: < 0 or >= span), span > 512 in forms 1 / 2, and arrays
+ * (q_elems, k_elems, v_elems, out_elems: their lengths in elements) shorter than the shape needs.  Since minor 8. */
+int pce_selftest_attn1(pce_ctx *ctx, int32_t form, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, uint16_t *k, int64_t k_elems, uint16_t *v,
+                       int64_t v_elems, const int32_t *k_row0, const int32_t *len, const int32_t *skip, int32_t span, uint16_t *out, int64_t out_elems);
 /* Self-test of the cross-attention of an incremental decoding step from the ENCODER OUTPUT (csrc/pce_xattn.inc: LayerNorm + query projection + Q' = q Wk,
  * one streaming pass over E with an online softmax per leaf of frames, the merge tree, out = Wv U + bv) for ONE layer on host arrays: resid [n][d] fp32,
  * ln_w / ln_b / bq / bv [d] fp32, wq / wk / wv [d][d] and E [n][k_cap][d] as 16-bit patterns of the context's operand type (rows of the weights = output

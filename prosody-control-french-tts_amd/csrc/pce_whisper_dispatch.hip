@@ -13,6 +13,8 @@ PCE_BOTH(int, pce_whisper_load, (pce_ctx *, const pce_whisper_dims *, const floa
 PCE_BOTH(int, pce_whisper_encode_run, (pce_ctx *))
 PCE_BOTH(int, pce_whisper_encode_fetch, (pce_ctx *, int32_t, float *))
 PCE_BOTH(int, pce_selftest_attention, (pce_ctx *, const uint16_t *, const uint16_t *, const uint16_t *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *, int32_t *))
+PCE_BOTH(int, pce_selftest_attention_ragged, (pce_ctx *, const uint16_t *, const uint16_t *, const uint16_t *, int32_t, int32_t, const int32_t *, const int32_t *, int32_t, int32_t, uint16_t *, int64_t, int32_t *))
+PCE_BOTH(int, pce_selftest_attn1, (pce_ctx *, int32_t, int32_t, int32_t, const uint16_t *, int64_t, uint16_t *, int64_t, uint16_t *, int64_t, const int32_t *, const int32_t *, const int32_t *, int32_t, uint16_t *, int64_t))
 PCE_BOTH(int, pce_selftest_gemm, (pce_ctx *, const uint16_t *, const uint16_t *, const float *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
 PCE_BOTH(int, pce_selftest_xattn, (pce_ctx *, const float *, const float *, const float *, const uint16_t *, const float *, const uint16_t *, const uint16_t *, const float *, const uint16_t *, const int32_t *, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
 PCE_BOTH(int, pce_selftest_gemm_tiled, (pce_ctx *, int32_t, int32_t, const uint16_t *, int64_t, int64_t, int64_t, int32_t, const uint16_t *, const float *, int32_t, int32_t,
@@ -60,6 +62,16 @@ int pce_selftest_attention(pce_ctx *c, const uint16_t *q, const uint16_t *k, con
                            int32_t causal, int32_t mode, uint16_t *out, int32_t *fell_back)
 {
     return PCE_FWD(pce_selftest_attention, c, q, k, v, clips, heads, q_len, k_len, causal, mode, out, fell_back);
+}
+int pce_selftest_attention_ragged(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, const int32_t *q_len,
+                                  const int32_t *k_len, int32_t causal, int32_t mode, uint16_t *out, int64_t out_rows, int32_t *fell_back)
+{
+    return PCE_FWD(pce_selftest_attention_ragged, c, q, k, v, clips, heads, q_len, k_len, causal, mode, out, out_rows, fell_back);
+}
+int pce_selftest_attn1(pce_ctx *c, int32_t form, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, uint16_t *k, int64_t k_elems, uint16_t *v,
+                       int64_t v_elems, const int32_t *k_row0, const int32_t *len, const int32_t *skip, int32_t span, uint16_t *out, int64_t out_elems)
+{
+    return PCE_FWD(pce_selftest_attn1, c, form, n, heads, q, q_elems, k, k_elems, v, v_elems, k_row0, len, skip, span, out, out_elems);
 }
 int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t rows_per_clip,
                       int32_t vt_sp, uint16_t *out)

@@ -28,6 +28,7 @@
 //                    online softmax in registers with DPP row reductions, K / V^T tiles in LDS
 // The residual stream is fp32, every GEMM operand op_t.  Roofline: MFMA (dense op_t).
 #include "pce_internal.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -45,6 +46,8 @@
 #define pce_whisper_encode_run PCE_WFN(pce_whisper_encode_run)
 #define pce_whisper_encode_fetch PCE_WFN(pce_whisper_encode_fetch)
 #define pce_selftest_attention PCE_WFN(pce_selftest_attention)
+#define pce_selftest_attention_ragged PCE_WFN(pce_selftest_attention_ragged)
+#define pce_selftest_attn1 PCE_WFN(pce_selftest_attn1)
 #define pce_selftest_gemm PCE_WFN(pce_selftest_gemm)
 #define pce_whisper_decoder_load PCE_WFN(pce_whisper_decoder_load)
 #define pce_whisper_align_run PCE_WFN(pce_whisper_align_run)
@@ -1139,12 +1142,12 @@ __global__ __launch_bounds__(256, 3) void k_attention_lean16(AttnArgs A, int for
     attn_block16<true, NT>(A, smem, bx, head, clip);
 }
 
-static void launch_attention(pce_ctx *c, dim3 grid, const AttnArgs &a, double flops = 0.0)
+static void launch_attention(pce_ctx *c, dim3 grid, const AttnArgs &a, double flops = 0.0, int force_exact = 0 /* self-test only */)
 {
     // flops > 0: a launch the profiler brackets on its own (the encoder's); the decoder's small launches stay inside their composite entry
     KernelTimer kt(c, PCE_K_ATTENTION_LEAN, nullptr, flops);
-    if (grid.x == 1) hipLaunchKernelGGL(k_attention_lean16<true>, grid, dim3(256), 0, c->stream, a, 0);
-    else hipLaunchKernelGGL(k_attention_lean16<false>, grid, dim3(256), 0, c->stream, a, 0);
+    if (grid.x == 1) hipLaunchKernelGGL(k_attention_lean16<true>, grid, dim3(256), 0, c->stream, a, force_exact);
+    else hipLaunchKernelGGL(k_attention_lean16<false>, grid, dim3(256), 0, c->stream, a, force_exact);
 }
 
 // ---------------------------------------------------------------------------
@@ -1501,6 +1504,26 @@ __global__ __launch_bounds__(1024) void k_cross_attn1w(Attn1Args A)
         }
     }
     A.out[(int64_t)clip * A.out_ld + head * 64 + lane] = (op_t)keep;
+}
+
+// The launches of the two single-query kernels, n clips x H heads (the decoding step and pce_selftest_attn1 make them here).  Up to 16 heads: one
+// workgroup per clip, one wave per head (115.8 against 119.6 us per launch with a workgroup per clip and head).  More heads (20 at large-v3 /
+// turbo): workgroups of at most 16 waves, grid (clip, head group) -- lds_optins (16 waves' slices) covers the largest group.
+static void launch_cross_attn1(pce_ctx *c, int n, int H, const Attn1Args &args)
+{
+    const int hgroups = (H + 15) / 16, hg_waves = (H + hgroups - 1) / hgroups;
+    Attn1Args a = args;
+    a.heads = H;
+    KernelTimer kt(c, PCE_K_CROSS_ATTN1);
+    hipLaunchKernelGGL(k_cross_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 1600 * 4, c->stream, a);
+}
+static void launch_self_attn1(pce_ctx *c, int n, int H, const SelfAttn1Args &args)
+{
+    const int hgroups = (H + 15) / 16, hg_waves = (H + hgroups - 1) / hgroups;
+    SelfAttn1Args a = args;
+    a.heads = H;
+    KernelTimer kt(c, PCE_K_CROSS_ATTN1);
+    hipLaunchKernelGGL(k_self_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 512 * 4, c->stream, a);
 }
 
 #include "pce_xattn.inc"
@@ -2602,48 +2625,132 @@ static void project_cross_kv(pce_ctx *c, const op_t *enc, int Ma, int d, const o
     launch_gemm<EPI_QKV>(c, enc, d, 0, W, Ma, 2 * d, d, bias, xk, d, 0, 1, reinterpret_cast<const float *>(xvt), W_CTX, d, AT_SP);
 }
 
-// V rows [clips][k_len][heads * 64] -> the V^T image the attention kernels read: [clip][head * 64 + d][sp] (key axis padded with zeros)
-static __global__ void k_selftest_vt(const op_t *__restrict__ v, int k_len, int hd, int sp, int64_t n, op_t *__restrict__ vt)
+// V rows of clip c at rows k_row0[c] .. + k_len[c] of [.][heads * 64] -> the V^T image the attention kernels read: [clip][head * 64 + d][sp] (the
+// rest of the key axis keeps its zeros)
+static __global__ void k_selftest_vt(const op_t *__restrict__ v, const int *__restrict__ k_row0, const int *__restrict__ k_len, int hd, int sp,
+                                     op_t *__restrict__ vt)
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int col = (int)(i % hd); const int64_t r = i / hd; const int t = (int)(r % k_len); const int64_t clip = r / k_len;
-    vt[(clip * hd + col) * sp + t] = v[i];
+    const int clip = blockIdx.y;
+    const int64_t n = (int64_t)k_len[clip] * hd;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int col = (int)(i % hd), t = (int)(i / hd);
+        vt[((int64_t)clip * hd + col) * sp + t] = v[(int64_t)k_row0[clip] * hd + i];
+    }
 }
 
-// Self-test hook of the attention kernels (see pce.h)
-int pce_selftest_attention(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, int32_t q_len,
-                           int32_t k_len, int32_t causal, int32_t mode, uint16_t *out, int32_t *fell_back)
+// Self-test hooks of the attention kernel through launch_attention (see pce.h)
+int pce_selftest_attention_ragged(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, const int32_t *q_len,
+                                  const int32_t *k_len, int32_t causal, int32_t mode, uint16_t *out, int64_t out_rows, int32_t *fell_back)
 {
-    if (!c || !q || !k || !v || !out || clips <= 0 || heads <= 0 || q_len <= 0 || k_len <= 0 || mode < 0 || mode > 1) return PCE_E_INVALID;
+    if (!c || !q || !k || !v || !out || !q_len || !k_len || clips <= 0 || clips > 65535 || heads <= 0 || heads > 65535 || mode < 0 || mode > 1)
+        return PCE_E_INVALID;
+    std::vector<int> tab((size_t)4 * clips);
+    int64_t q_rows = 0, k_rows = 0;
+    int q_max = 0, k_max = 0;
+    for (int i = 0; i < clips; i++) {
+        if (q_len[i] < 1 || k_len[i] < 1 || q_len[i] > (1 << 20) || k_len[i] > (1 << 20)) return pce_fail(c, PCE_E_INVALID, "selftest attention: clip %d has %d queries, %d keys", i, q_len[i], k_len[i]);
+        tab[(size_t)i] = (int)q_rows; tab[(size_t)clips + i] = q_len[i]; tab[(size_t)2 * clips + i] = (int)k_rows; tab[(size_t)3 * clips + i] = k_len[i];
+        q_rows += q_len[i]; k_rows += k_len[i];
+        q_max = q_len[i] > q_max ? q_len[i] : q_max; k_max = k_len[i] > k_max ? k_len[i] : k_max;
+    }
+    const int hd = heads * 64, sp = div_up(k_max, 64) * 64;
+    if (out_rows < q_rows || (out_rows + k_rows) * hd >= ((int64_t)1 << 30)) return pce_fail(c, PCE_E_INVALID, "selftest attention: %lld output rows for %lld queries", (long long)out_rows, (long long)q_rows);
     PCE_HIP(c, hipSetDevice(c->device));
-    const int hd = heads * 64, sp = div_up(k_len, 64) * 64;
-    const size_t nq = (size_t)clips * q_len * hd, nk = (size_t)clips * k_len * hd, nvt = (size_t)clips * hd * sp;
+    const size_t nq = (size_t)q_rows * hd, nk = (size_t)k_rows * hd, nvt = (size_t)clips * hd * sp, no = (size_t)out_rows * hd;
     DevBuf dq, dk, dv, dvt, dout, dtab, dcnt;
     PCE_HIP(c, dq.reserve(nq * 2 + 64)); PCE_HIP(c, dk.reserve(nk * 2 + 64)); PCE_HIP(c, dv.reserve(nk * 2 + 64)); PCE_HIP(c, dvt.reserve(nvt * 2 + 128));
-    PCE_HIP(c, dout.reserve(nq * 2 + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * 4 * (size_t)clips)); PCE_HIP(c, dcnt.reserve(sizeof(int)));
-    std::vector<int> tab((size_t)4 * clips);
-    for (int i = 0; i < clips; i++) { tab[(size_t)i] = i * q_len; tab[(size_t)clips + i] = q_len; tab[(size_t)2 * clips + i] = i * k_len; tab[(size_t)3 * clips + i] = k_len; }
+    PCE_HIP(c, dout.reserve(no * 2 + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * 4 * (size_t)clips)); PCE_HIP(c, dcnt.reserve(sizeof(int)));
     PCE_HIP(c, hipMemcpyAsync(dq.p, q, nq * 2, hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(dk.p, k, nk * 2, hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(dv.p, v, nk * 2, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dout.p, out, no * 2, hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemsetAsync(dvt.p, 0, nvt * 2 + 128, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dout.p, 0, nq * 2, c->stream));
     PCE_HIP(c, hipMemsetAsync(dcnt.p, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_selftest_vt, dim3((unsigned)div_up((int64_t)nk, 256)), dim3(256), 0, c->stream, dv.as<op_t>(), k_len, hd, sp, (int64_t)nk, dvt.as<op_t>());
     AttnArgs a{};
     a.q = dq.as<op_t>(); a.q_ld = hd; a.k = dk.as<op_t>(); a.k_ld = hd; a.vt = dvt.as<op_t>(); a.vt_clip = (int64_t)hd * sp; a.vt_sp = sp;
     a.q_row0 = dtab.as<int>(); a.q_len = a.q_row0 + clips; a.k_row0 = a.q_row0 + 2 * clips; a.k_len = a.q_row0 + 3 * clips;
     a.out = dout.as<op_t>(); a.out_ld = hd; a.causal = causal; a.fell_back = dcnt.as<int>();
-    const dim3 grid((unsigned)div_up(q_len, AT_QB), (unsigned)heads, (unsigned)clips);
-    hipLaunchKernelGGL(k_attention_lean16<false>, grid, dim3(256), 0, c->stream, a, mode);
+    hipLaunchKernelGGL(k_selftest_vt, dim3((unsigned)div_up((int64_t)k_max * hd, 256), (unsigned)clips), dim3(256), 0, c->stream, dv.as<op_t>(), a.k_row0,
+                       a.k_len, hd, sp, dvt.as<op_t>());
+    // the grid of the longest clip, as the teacher-forced decoder launches it: one query block takes the NT instantiation
+    launch_attention(c, dim3((unsigned)div_up(q_max, AT_QB), (unsigned)heads, (unsigned)clips), a, 0.0, mode);
     PCE_HIP(c, hipGetLastError());
     int cnt = 0;
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, nq * 2, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, no * 2, hipMemcpyDeviceToHost, c->stream));
     PCE_HIP(c, hipMemcpyAsync(&cnt, dcnt.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     if (fell_back) *fell_back = cnt;
+    return PCE_OK;
+}
+int pce_selftest_attention(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, int32_t q_len,
+                           int32_t k_len, int32_t causal, int32_t mode, uint16_t *out, int32_t *fell_back)
+{
+    if (!c || !out || clips <= 0 || heads <= 0 || q_len <= 0 || k_len <= 0) return PCE_E_INVALID;
+    const std::vector<int32_t> ql((size_t)clips, q_len), kl((size_t)clips, k_len);
+    std::fill(out, out + (size_t)clips * q_len * heads * 64, (uint16_t)0);
+    return pce_selftest_attention_ragged(c, q, k, v, clips, heads, ql.data(), kl.data(), causal, mode, out, (int64_t)clips * q_len, fell_back);
+}
+
+// Self-test hook of the single-query attention kernels of an incremental decoding step, through the launches the step makes (see pce.h)
+int pce_selftest_attn1(pce_ctx *c, int32_t form, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, uint16_t *k, int64_t k_elems, uint16_t *v,
+                       int64_t v_elems, const int32_t *k_row0, const int32_t *len, const int32_t *skip, int32_t span, uint16_t *out, int64_t out_elems)
+{
+    if (!c || form < 0 || form > 2 || !q || !k || !v || !len || !out || n < 1 || n > 65535 || heads < 1 || span < 1) return PCE_E_INVALID;
+    if (heads > 32) return pce_fail(c, PCE_E_INVALID, "selftest attn1: %d heads (the kernels hold 32)", heads);
+    const int64_t d = (int64_t)heads * 64;
+    const int T_cap = span, vt_sp = form == 0 ? span : 512;
+    if (form == 0 && (!k_row0 || vt_sp % 8 != 0)) return pce_fail(c, PCE_E_INVALID, "selftest attn1: form 0 needs k_row0 and vt_sp %% 8 == 0 (%d)", vt_sp);
+    if (form != 0 && T_cap > 512) return pce_fail(c, PCE_E_INVALID, "selftest attn1: T_cap %d > 512", T_cap);
+    const int64_t q_need = (int64_t)n * d * (form == 0 ? 1 : 3), v_need = (int64_t)n * d * (form == 2 ? T_cap : vt_sp), o_need = (int64_t)n * d;
+    int64_t k_need = form == 0 ? 0 : (int64_t)n * T_cap * d;
+    std::vector<int> tab((size_t)4 * n, 0);                        // k_row0 | k_len | pos | skip
+    for (int i = 0; i < n; i++) {
+        if (form == 0) {
+            if (len[i] < 1 || len[i] > 1536 || k_row0[i] < 0 || (len[i] + 7) / 8 * 8 > vt_sp)
+                return pce_fail(c, PCE_E_INVALID, "selftest attn1: clip %d has %d keys from row %d (V^T pitch %d)", i, len[i], k_row0[i], vt_sp);
+            const int64_t end = ((int64_t)k_row0[i] + len[i]) * d;
+            k_need = end > k_need ? end : k_need;
+            tab[(size_t)i] = k_row0[i]; tab[(size_t)n + i] = len[i];
+        } else {
+            if (len[i] < 0 || len[i] >= T_cap) return pce_fail(c, PCE_E_INVALID, "selftest attn1: clip %d at position %d of %d", i, len[i], T_cap);
+            tab[(size_t)i] = i * T_cap; tab[(size_t)n + i] = len[i] + 1; tab[(size_t)2 * n + i] = len[i];
+        }
+        tab[(size_t)3 * n + i] = skip ? skip[i] : 0;
+    }
+    if (q_elems < q_need || k_elems < k_need || v_elems < v_need || out_elems < o_need || k_elems >= ((int64_t)1 << 31) || v_elems >= ((int64_t)1 << 31))
+        return pce_fail(c, PCE_E_INVALID, "selftest attn1: form %d needs q %lld, k %lld, v %lld, out %lld elements", form, (long long)q_need, (long long)k_need,
+                        (long long)v_need, (long long)o_need);
+    PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    DevBuf dq, dk, dv, dout, dtab;
+    PCE_HIP(c, dq.reserve(2 * (size_t)q_elems + 64)); PCE_HIP(c, dk.reserve(2 * (size_t)k_elems + 64)); PCE_HIP(c, dv.reserve(2 * (size_t)v_elems + 64));
+    PCE_HIP(c, dout.reserve(2 * (size_t)out_elems + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * tab.size()));
+    PCE_HIP(c, hipMemcpyAsync(dq.p, q, 2 * (size_t)q_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dk.p, k, 2 * (size_t)k_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dv.p, v, 2 * (size_t)v_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dout.p, out, 2 * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    const int *T = dtab.as<int>(), *SKIP = skip ? T + 3 * n : nullptr;
+    if (form == 2) {
+        SelfAttn1Args sa{};
+        sa.qkv = dq.as<op_t>(); sa.qkv_ld = 3 * d; sa.ck = dk.as<op_t>(); sa.cv = dv.as<op_t>(); sa.c_clip = (int64_t)T_cap * d; sa.d = (int)d;
+        sa.pos = T + 2 * n; sa.skip = SKIP; sa.out = dout.as<op_t>(); sa.out_ld = d;
+        launch_self_attn1(c, n, heads, sa);
+    } else {
+        Attn1Args a{};
+        a.q = dq.as<op_t>(); a.q_ld = form == 0 ? d : 3 * d; a.k = dk.as<op_t>(); a.k_ld = d; a.vt = dv.as<op_t>(); a.vt_clip = d * vt_sp; a.vt_sp = vt_sp;
+        a.k_row0 = T; a.k_len = T + n; a.skip = SKIP; a.out = dout.as<op_t>(); a.out_ld = d;
+        if (form == 1) { a.app_k = dq.as<op_t>() + d; a.app_v = dq.as<op_t>() + 2 * d; a.app_ld = 3 * d; a.app_pos = T + 2 * n; }
+        launch_cross_attn1(c, n, heads, a);
+    }
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
+    if (form != 0) {
+        PCE_HIP(c, hipMemcpyAsync(k, dk.p, 2 * (size_t)k_elems, hipMemcpyDeviceToHost, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(v, dv.p, 2 * (size_t)v_elems, hipMemcpyDeviceToHost, c->stream));
+    }
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
 
@@ -3243,10 +3350,7 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
     struct FewRows { pce_ctx *c; explicit FewRows(pce_ctx *cc) : c(cc) { c->gemm_few_rows = true; } ~FewRows() { c->gemm_few_rows = false; } } few_rows(c);
     hipLaunchKernelGGL(k_embed_one, dim3((unsigned)div_up((int64_t)n * d, 256)), dim3(256), 0, c->stream, CT, w->d_tok_emb.as<float>(),
                        w->d_pos_emb.as<float>(), POS, d, n, w->g_c_resid.as<float>());
-    // up to 16 heads: one workgroup per clip, one wave per head (115.8 against 119.6 us per launch with a workgroup per clip and head); that
-    // kernel also appends the new position to the self-attention cache.  More heads (20 at large-v3 / turbo): workgroups of at most 16 waves,
-    // grid (clip, head group) -- lds_optins (16 waves' slices) covers the largest group
-    const int hgroups = (H + 15) / 16, hg_waves = (H + hgroups - 1) / hgroups;
+    // the self-attention kernel also appends the new position to its cache
     auto cattn = [&](const op_t *q, int64_t q_ld, const op_t *k, int64_t k_ld, const op_t *vt, int64_t vt_clip, int vt_sp, const int *k0, const int *kl,
                      const op_t *app_qkv = nullptr) {
         // the streaming single-query kernels (the MFMA attention kernel would spend a 32-query tile on the one live query)
@@ -3254,9 +3358,7 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
         a.q = q; a.q_ld = q_ld; a.k = k; a.k_ld = k_ld; a.vt = vt; a.vt_clip = vt_clip; a.vt_sp = vt_sp; a.k_row0 = k0; a.k_len = kl; a.skip = ended;
         a.out = w->g_c_attn.as<op_t>(); a.out_ld = d;
         if (app_qkv) { a.app_k = app_qkv + d; a.app_v = app_qkv + 2 * d; a.app_ld = 3 * d; a.app_pos = POS; }
-        a.heads = H;
-        KernelTimer kt(c, PCE_K_CROSS_ATTN1);
-        hipLaunchKernelGGL(k_cross_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 1600 * 4, c->stream, a);
+        launch_cross_attn1(c, n, H, a);
     };
     auto cln = [&](size_t w_off, size_t b_off) {
         launch_layernorm<op_t>(c, w->g_c_resid.as<float>(), Wf + w_off, Wf + b_off,
@@ -3288,9 +3390,8 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
             // which rewrite every position they attend to, read it)
             SelfAttn1Args sa{};
             sa.qkv = w->g_c_qkv.as<op_t>(); sa.qkv_ld = 3 * d; sa.ck = w->g_sk.as<op_t>() + sk_l * (size_t)l; sa.cv = w->g_sv.as<op_t>() + sk_l * (size_t)l;
-            sa.c_clip = (int64_t)T_cap * d; sa.d = d; sa.pos = POS; sa.skip = ended; sa.out = w->g_c_attn.as<op_t>(); sa.out_ld = d; sa.heads = H;
-            KernelTimer kt(c, PCE_K_CROSS_ATTN1);
-            hipLaunchKernelGGL(k_self_attn1w, dim3((unsigned)n, (unsigned)hgroups), dim3(64 * (unsigned)hg_waves), (size_t)hg_waves * 512 * 4, c->stream, sa);
+            sa.c_clip = (int64_t)T_cap * d; sa.d = d; sa.pos = POS; sa.skip = ended; sa.out = w->g_c_attn.as<op_t>(); sa.out_ld = d;
+            launch_self_attn1(c, n, H, sa);
         } else
         cattn(w->g_c_qkv.as<op_t>(), 3 * d, w->g_sk.as<op_t>() + sk_l * (size_t)l, d, w->g_svt.as<op_t>() + svt_l * (size_t)l, (int64_t)d * SPD, SPD, K0, KL,
               w->g_c_qkv.as<op_t>());

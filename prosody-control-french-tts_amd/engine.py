@@ -133,7 +133,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
            "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
-           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_attention", "pce_whisper_encode_fetch",
+           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
 
@@ -207,6 +207,8 @@ def load_library() -> C.CDLL:
     lib.pce_whisper_encode_run.argtypes = [vp]
     lib.pce_selftest_gemm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.pce_selftest_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    lib.pce_selftest_attention_ragged.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i64, vp]
+    lib.pce_selftest_attn1.argtypes = [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i64]
     lib.pce_selftest_xattn.argtypes = [vp] * 11 + [i32] * 5 + [vp]
     lib.pce_selftest_gemm_tiled.argtypes = [vp, i32, i32, vp, i64, i64, i64, i32, vp, vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp]
     lib.pce_selftest_layernorm.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp]
@@ -563,6 +565,40 @@ class ProsodyEngine:
                                                      tv.view(torch.int16).numpy().ctypes.data, clips, hd // 64, q_len, k_len, int(bool(causal)), int(mode),
                                                      out.view(torch.int16).numpy().ctypes.data, C.addressof(fb)))
         return out.float().numpy(), int(fb.value)
+
+    def selftest_attention_ragged(self, q, k, v, q_len, k_len, out, causal: bool = False, mode: int = 0) -> int:
+        """``pce_selftest_attention_ragged``: the attention kernel through the product's launch with per-clip lengths.  q [sum q_len][heads * 64],
+        k / v [sum k_len][heads * 64] and out [rows >= sum q_len][heads * 64] are uint16 bit patterns of the context's operand type; out is read and
+        updated in place.  Returns the number of workgroups that fell back to the exact path."""
+        u = lambda x: self._u16(x)
+        q, k, v, out = u(q), u(k), u(v), u(out)
+        ql, kl = np.ascontiguousarray(q_len, dtype=np.int32), np.ascontiguousarray(k_len, dtype=np.int32)
+        hd = q.shape[1]
+        assert hd % 64 == 0 and k.shape == v.shape == (int(kl.sum()), hd) and q.shape[0] == int(ql.sum()) and out.shape[1] == hd and ql.size == kl.size
+        fb = C.c_int32(0)
+        self._check(self._lib.pce_selftest_attention_ragged(self._ctx, q.ctypes.data, k.ctypes.data, v.ctypes.data, int(ql.size), hd // 64, ql.ctypes.data,
+                                                            kl.ctypes.data, int(bool(causal)), int(mode), out.ctypes.data, int(out.shape[0]), C.addressof(fb)))
+        return int(fb.value)
+
+    @staticmethod
+    def _u16(x):
+        assert isinstance(x, np.ndarray) and x.dtype == np.uint16 and x.flags["C_CONTIGUOUS"], getattr(x, "dtype", None)
+        return x
+
+    def selftest_attn1(self, form: int, heads: int, q, k, v, length, out, k_row0=None, skip=None, span: int = 0):
+        """``pce_selftest_attn1``: one launch of the single-query attention kernels as a decoding step makes it.  form 0: k_cross_attn1w over given
+        keys (q [n][d], k key rows, v the whole V^T image [n][d][span], length = keys per clip, k_row0 = first key row per clip); form 1: the same
+        kernel appending (q = q | k | v [n][3 d], k cache [n][span][d], v = V^T cache [n][d][512], length = position); form 2: k_self_attn1w (as
+        form 1, v = row-major cache [n][span][d]).  All arrays are uint16 bit patterns of the context's operand type; out [n][d], and in forms 1 / 2
+        k and v, are read and updated in place."""
+        q, k, v, out = self._u16(q), self._u16(k), self._u16(v), self._u16(out)
+        i32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+        ln, r0, sk = i32(length), i32(k_row0), i32(skip)
+        n = ln.size
+        assert (r0 is None or r0.size == n) and (sk is None or sk.size == n)
+        ptr = lambda x: None if x is None else x.ctypes.data
+        self._check(self._lib.pce_selftest_attn1(self._ctx, int(form), int(n), int(heads), q.ctypes.data, q.size, k.ctypes.data, k.size, v.ctypes.data,
+                                                 v.size, ptr(r0), ln.ctypes.data, ptr(sk), int(span), out.ctypes.data, out.size))
 
     def selftest_xattn(self, resid, ln_w, ln_b, wq, bq, wk, wv, bv, E, k_len, heads: int, workgroups_per_clip: int = 0):
         """One layer of the encoder-output cross-attention of a decoding step (``pce_selftest_xattn``): resid [n][d], E [n][k_cap][d], weights [d][d]
