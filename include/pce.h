@@ -53,9 +53,10 @@ extern "C" {
  * 6 = pce_dtw_series (DTW of pairs of fp64 series, tiled over the whole device) and its two kernel ids;
  * 7 = pce_intensity_plan / _run / _fetch (Praat's Sound_to_Intensity over slices, with per-slice summaries) and their two kernel ids;
  * 8 = pce_selftest_attn1 (the single-query attention kernels of a decoding step) and pce_selftest_attention_ragged; pce_selftest_attention launches
- * through the product's rule (one query block: the streaming instantiation). */
+ * through the product's rule (one query block: the streaming instantiation);
+ * 9 = pce_silence_run / _shape / _fetch (pydub's detect_silence over slices, exact integers) and their three kernel ids. */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 8
+#define PCE_API_MINOR 9
 
 typedef struct pce_ctx pce_ctx;
 
@@ -243,6 +244,29 @@ int pce_intensity_run(pce_ctx *ctx, const pce_intensity_params *p, const double 
                       int32_t n_slices);
 /* values: ragged [frame_offsets[n_slices]] dB, may be NULL (a corpus run downloads 40 bytes per slice); summary [n_slices], may be NULL. */
 int pce_intensity_fetch(pce_ctx *ctx, double *values, pce_intensity_summary *summary);
+
+/* ---- silence detection (pydub.silence) --------------------------------------
+ * Replaces pydub.silence.detect_silence, the loop under split_on_silence(audio, min_silence_len=1000, silence_thresh=-50, keep_silence=300)
+ * of Code/Preprocessing/preprocess_audio.py:41-46 and under detect_nonsilent (Code/audioPipeline.py:720, :786-797).  pydub 0.25.1 is third party
+ * and absent: the range bookkeeping is restated from its published source, parity unpinned; the window test is the arithmetic of stdlib
+ * audioop.rms, the function pydub calls.  For a slice of n frames (channels interleaved samples each) at the batch's frame rate:
+ *   len_ms = round-half-even(1000 * (n / rate));  b(m) = (int64)((double)m * (rate / 1000.0)) frames, the fp64 product of pydub's slicing;
+ *   windows start at i = 0, seek_step, 2 seek_step, ... <= last = len_ms - min_silence_len, and at `last` itself where seek_step does not
+ *   divide it; none when len_ms < min_silence_len.  Window i covers frames [b(i), b(i + min_silence_len)); frames at or beyond n are zeros that
+ *   count (pydub's silence padding) and samples of the slice outside its clip are zeros as everywhere else;
+ *   window i is silent iff  sum x^2 < (rms_max + 1)^2 * samples in the window  (<=> audioop.rms(window) <= threshold for rms_max =
+ *   floor(threshold): no square root, no floating point in the decision; the dB -> rms_max rule is host logic, hostrules.silence_rms_max);
+ *   a silent start s opens a new range iff there is no silent start p before it or (s != p + seek_step and s > p + min_silence_len); a range is
+ *   [its first start, its last start + min_silence_len] in milliseconds.
+ * Slice bounds are in interleaved samples and must be multiples of `channels`.  status[i]: PCE_SLICE_EMPTY for a slice without samples.
+ * PCE_E_INVALID: min_silence_len < 1, seek_step < 1, channels < 1, an rms_max < 0, misaligned slice bounds; PCE_E_LIMIT: a slice longer than
+ * 2^31 - 1 ms; PCE_E_STATE: _shape / _fetch before _run.  A slice has at most len_ms / (min_silence_len + 1) + 1 ranges.  All integer: a slice's
+ * ranges depend on its own samples only, not on the batch.  Since minor 9. */
+typedef struct pce_silence_params { int32_t min_silence_len, seek_step, channels, reserved; } pce_silence_params;
+int pce_silence_run(pce_ctx *ctx, const pce_silence_params *p, const pce_slice *slices, const int32_t *rms_max /* [n_slices] */, int32_t n_slices);
+int pce_silence_shape(pce_ctx *ctx, int64_t *range_offsets /* [n_slices + 1] */, int32_t *len_ms /* [n_slices] or NULL */, int32_t *status /* [n_slices] or NULL */);
+/* ranges: (start_ms, end_ms) pairs, slice after slice: [2 * range_offsets[n_slices]] */
+int pce_silence_fetch(pce_ctx *ctx, int32_t *ranges);
 
 /* ---- R10: STFT magnitude in dB -----------------------------------------
  * Replaces librosa.amplitude_to_db(np.abs(librosa.stft(y, n_fft, hop_length)),
@@ -574,7 +598,9 @@ enum pce_kernel_id {
     /* minor 6: the tile sweeps and the walk back of pce_dtw_series; their work count (pce_profile_get_work) is in-window CELLS, not flops */
     PCE_K_DTW_SERIES, PCE_K_DTW_SERIES_TRACE,
     /* minor 7 */
-    PCE_K_INTENSITY, PCE_K_INTENSITY_SUMMARY, PCE_K_COUNT
+    PCE_K_INTENSITY, PCE_K_INTENSITY_SUMMARY,
+    /* minor 9: PCE_K_SILENCE_RANGES brackets three launches (tiles, carry, tiles with the carry) */
+    PCE_K_MS_ENERGY, PCE_K_SILENCE_SCAN, PCE_K_SILENCE_RANGES, PCE_K_COUNT
 };
 int pce_profile_enable(pce_ctx *ctx, int on);
 int pce_profile_reset(pce_ctx *ctx);

@@ -153,6 +153,14 @@ struct pce_ctx {
     std::vector<int32_t> in_status;
     std::vector<double> in_t1;
 
+    // silence detection (pce_silence.hip): slice table, in-chunk prefix sums of the millisecond bins, chunk totals and offsets, tile summaries and
+    // carries of the range pass, the ranges at their per-slice bound, the per-slice range counts
+    DevBuf si_meta, si_pl, si_csum, si_coff, si_tsum, si_tin, si_out, si_count;
+    std::vector<int32_t> si_len_ms, si_status, si_counts;
+    std::vector<int64_t> si_cap_off;     // ranges the slices before slice i may have (n + 1)
+    bool si_counts_valid = false;
+    int32_t si_n = -1;
+
     // DTW of series pairs (pce_dtw_series.hip): the batch's inputs and results, the tables of the group in flight, its boundary rows / columns and trace
     struct DtwSeries { DevBuf a, b, lo, hi, pi, pj, dist, len, status, pairs, tab, tiles, rows, cols, trace; } ds;
     size_t dtw_trace_budget = (size_t)4096 << 20;   // PCE_DTW_TRACE_MB at pce_create: bytes of trace one group of pairs may hold

@@ -78,6 +78,10 @@ class IntensitySummary(C.Structure):
                 ("status", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SilenceParams(C.Structure):
+    _fields_ = [("min_silence_len", C.c_int32), ("seek_step", C.c_int32), ("channels", C.c_int32), ("reserved", C.c_int32)]
+
+
 class WhisperDims(C.Structure):
     _fields_ = [("n_mels", C.c_int32), ("n_ctx", C.c_int32), ("n_state", C.c_int32), ("n_head", C.c_int32), ("n_layer", C.c_int32)]
 
@@ -121,7 +125,7 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "k_add_layernorm", "k_stft_raw", "k_logmel_norm", "k_attention_lean",
               "k_gemm_flat:qkv", "k_gemm_flat:out", "k_gemm_flat:fc1", "k_gemm_flat:fc2", "k_gemm_flat:xkv",
               "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace",
-              "k_intensity", "k_intensity_summary"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
+              "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
 # every symbol include/pce.h declares
 EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_version", "pce_api_minor", "pce_device_info",
@@ -130,6 +134,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_frame_energy_run", "pce_frame_energy_shape", "pce_frame_energy_fetch", "pce_pyin_run", "pce_pyin_shape", "pce_pyin_fetch",
            "pce_pitch_plan", "pce_pitch_run", "pce_pitch_set_refine", "pce_pitch_fetch",
            "pce_intensity_plan", "pce_intensity_run", "pce_intensity_fetch",
+           "pce_silence_run", "pce_silence_shape", "pce_silence_fetch",
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
            "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
@@ -173,6 +178,9 @@ def load_library() -> C.CDLL:
     lib.pce_intensity_plan.argtypes = [vp, C.POINTER(IntensityParams), vp, i32, vp, vp]
     lib.pce_intensity_run.argtypes = [vp, C.POINTER(IntensityParams), vp, i32, vp, i32]
     lib.pce_intensity_fetch.argtypes = [vp, vp, vp]
+    lib.pce_silence_run.argtypes = [vp, C.POINTER(SilenceParams), vp, vp, i32]
+    lib.pce_silence_shape.argtypes = [vp, vp, vp, vp]
+    lib.pce_silence_fetch.argtypes = [vp, vp]
     lib.pce_stats_enqueue.argtypes = [vp, i32]
     lib.pce_nw_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.pce_levenshtein.argtypes = [vp, vp, vp, vp, vp, i32, vp]
@@ -409,6 +417,60 @@ class ProsodyEngine:
         """parselmouth ``Sound.to_intensity()`` of every slice: ``values[frame_offsets[i]:frame_offsets[i + 1]]`` is slice i's contour."""
         self.intensity_run(slices, params if params is not None else IntensityParams.praat())
         return self.intensity_fetch(want_contour)
+
+    # ---------------------------------------------------------------- pydub.silence
+    def silence_run(self, slices, rms_max, min_silence_len: int = 1000, seek_step: int = 1, channels: int = 1):
+        """Enqueue pydub's ``detect_silence`` over ``slices`` (``pce_silence_run``).  ``rms_max``: the integer threshold ``T`` of every slice
+        (``hostrules.silence_rms_max``), a scalar or one value per slice.  With ``channels`` > 1 the uploaded clips are interleaved streams,
+        the upload's rate is the frame rate and slice bounds are in interleaved samples."""
+        s = self._slices(slices)
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(rms_max, dtype=np.int32), (len(s),)))
+        self._si_n = len(s)
+        params = SilenceParams(int(min_silence_len), int(seek_step), int(channels), 0)
+        self._check(self._lib.pce_silence_run(self._ctx, C.byref(params), s.ctypes.data, t.ctypes.data, len(s)))
+
+    def silence_fetch(self):
+        """-> {"range_offsets": int64 [n + 1], "ranges": int32 [total, 2] (start_ms, end_ms), "len_ms": int32 [n], "status": int32 [n]}."""
+        n = self._si_n
+        off = np.zeros(n + 1, dtype=np.int64); len_ms = np.zeros(n, dtype=np.int32); st = np.zeros(n, dtype=np.int32)
+        self._check(self._lib.pce_silence_shape(self._ctx, off.ctypes.data, len_ms.ctypes.data, st.ctypes.data))
+        ranges = np.zeros((int(off[-1]), 2), dtype=np.int32)
+        self._check(self._lib.pce_silence_fetch(self._ctx, ranges.ctypes.data if ranges.size else None))
+        return {"range_offsets": off, "ranges": ranges, "len_ms": len_ms, "status": st}
+
+    def _silence(self, slices, min_silence_len, silence_thresh, seek_step, channels):
+        from .hostrules import silence_rms_max
+        thr = np.broadcast_to(np.asarray(silence_thresh, dtype=np.float64), (len(slices),))
+        self.silence_run(slices, [silence_rms_max(t) for t in thr], min_silence_len, seek_step, channels)
+        res = self.silence_fetch()
+        off = res["range_offsets"]
+        return [res["ranges"][off[i]:off[i + 1]].tolist() for i in range(len(slices))], res["len_ms"].tolist()
+
+    def detect_silence(self, slices, min_silence_len=1000, silence_thresh=-16, seek_step=1, channels=1):
+        """``pydub.silence.detect_silence`` of every slice -> per slice, the list of ``[start_ms, end_ms]`` silent ranges.
+        ``silence_thresh`` (dBFS): a scalar or one value per slice."""
+        return self._silence(slices, min_silence_len, silence_thresh, seek_step, channels)[0]
+
+    def detect_nonsilent(self, slices, min_silence_len=1000, silence_thresh=-16, seek_step=1, channels=1):
+        """``pydub.silence.detect_nonsilent`` of every slice -> per slice, the list of ``[start_ms, end_ms]`` nonsilent ranges."""
+        from .hostrules import nonsilent_from_silent
+        silent, len_ms = self._silence(slices, min_silence_len, silence_thresh, seek_step, channels)
+        return [nonsilent_from_silent(r, n) for r, n in zip(silent, len_ms)]
+
+    def split_on_silence(self, slices, min_silence_len=1000, silence_thresh=-16, seek_step=1, keep_silence=100, channels=1):
+        """``pydub.silence.split_on_silence`` of every slice -> (per slice, the ``[start_ms, end_ms]`` of its chunks; per slice, their
+        ``(begin, end)`` frame ranges relative to the slice, ``hostrules.pydub_slice_frames``: frames at or beyond the slice's length are
+        pydub's silence padding)."""
+        from .hostrules import nonsilent_from_silent, pydub_slice_frames, split_ranges
+        s = self._slices(slices)
+        silent, lens = self._silence(s, min_silence_len, silence_thresh, seek_step, channels)
+        ms, frames = [], []
+        for i, len_ms in enumerate(lens):
+            n_frames = int(s["end"][i] - s["begin"][i]) // int(channels)
+            cut = split_ranges(nonsilent_from_silent(silent[i], len_ms), keep_silence, len_ms)
+            ms.append(cut)
+            frames.append([pydub_slice_frames(n_frames, self.rate, a, b) for a, b in cut])
+        return ms, frames
 
     def stats_enqueue(self, slot: int = 0):
         """Queue the device-to-host copies of the last energy / LUFS / pitch-summary results behind their

@@ -22,6 +22,21 @@ class PraatError(RuntimeError):
     """Mirror of ``parselmouth.PraatError``: raised where Praat refuses the analysis."""
 
 
+def decode_wav_channels(path):
+    """Decode a 16-bit PCM RIFF/WAVE file with every channel kept -> (frame_rate, channels, interleaved int16 samples): what
+    ``AudioSegment.from_file`` holds (Code/Preprocessing/preprocess_audio.py:39; Demucs output is stereo).  Anything else raises
+    :class:`CouldntDecodeError`."""
+    try:
+        with wave.open(os.fspath(path), "rb") as w:
+            if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+                raise CouldntDecodeError(f"{path}: only 16-bit PCM WAV is supported")
+            rate, ch = w.getframerate(), w.getnchannels()
+            data = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2")
+    except (wave.Error, EOFError, OSError) as e:
+        raise CouldntDecodeError(f"{path}: {e}") from e
+    return rate, ch, np.ascontiguousarray(data[:len(data) - len(data) % ch], dtype=np.int16)
+
+
 def decode_wav(path):
     """Decode a 16-bit PCM RIFF/WAVE file -> (frame_rate, int16 mono samples).
 
@@ -83,6 +98,51 @@ def seconds_slice_frames(n_frames: int, rate: int, t0: float, t1):
     if t1 is None:
         return 0, n_frames
     return pydub_slice_frames(n_frames, rate, int(t0 * 1000), int(t1 * 1000))
+
+
+# ---------------------------------------------------------------- pydub.silence 0.25.1 (range bookkeeping; the windows are the engine's)
+def silence_rms_max(silence_thresh_db) -> int:
+    """The integer ``T`` of ``pce_silence_run`` for pydub's ``silence_thresh``: pydub calls a window silent when
+    ``audioop.rms(window) <= db_to_float(silence_thresh) * 32768``; the rms is an integer, so that is ``rms <= T`` with
+    ``T = floor(10 ** (dB / 20) * 32768)``, capped at 32768 (no 16-bit window is louder)."""
+    thr = 10 ** (float(silence_thresh_db) / 20) * 32768.0
+    return int(min(math.floor(thr), 32768))
+
+
+def pydub_dbfs(sum_sq: int, n: int) -> float:
+    """``AudioSegment.dBFS`` from the exact sum of squares of ``n`` samples: ``20 log10(audioop.rms / 32768)``, the rms truncated to an
+    integer as audioop does; ``-inf`` for digital silence (and for no samples)."""
+    rms = math.isqrt(int(sum_sq) // int(n)) if n else 0
+    return 20 * math.log10(rms / 32768.0) if rms else -float("inf")
+
+
+def nonsilent_from_silent(ranges, len_ms: int):
+    """``detect_nonsilent`` from ``detect_silence``'s ranges: the gaps between the silent ranges of a sound of ``len_ms``."""
+    ranges = [list(map(int, r)) for r in ranges]
+    if not ranges:
+        return [[0, len_ms]]
+    if ranges[0][0] == 0 and ranges[0][1] == len_ms:
+        return []
+    out, prev_end = [], 0
+    for start, end in ranges:
+        out.append([prev_end, start])
+        prev_end = end
+    if prev_end != len_ms:
+        out.append([prev_end, len_ms])
+    if out[0] == [0, 0]:
+        out.pop(0)
+    return out
+
+
+def split_ranges(nonsilent, keep_silence, len_ms: int):
+    """The ms ranges ``split_on_silence`` cuts: every nonsilent range widened by ``keep_silence`` (``True``: the whole length, ``False``: 0),
+    neighbours that now overlap meeting at the midpoint, all clipped to ``[0, len_ms]``."""
+    keep = (len_ms if keep_silence else 0) if isinstance(keep_silence, bool) else keep_silence
+    out = [[start - keep, end + keep] for start, end in nonsilent]
+    for cur, nxt in zip(out, out[1:]):
+        if nxt[0] < cur[1]:
+            cur[1] = nxt[0] = (cur[1] + nxt[0]) // 2
+    return [[max(start, 0), min(end, len_ms)] for start, end in out]
 
 
 # ---------------------------------------------------------------- Praat extract_part
