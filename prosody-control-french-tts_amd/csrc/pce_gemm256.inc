@@ -1,4 +1,4 @@
-// pce_gemm256.inc -- persistent 256 x 256 tile GEMM for the big encoder projections (included by pce_whisper.hip).
+// pce_gemm256.inc -- persistent 256 x 256 tile GEMM for the big encoder projections (included by pce_whisper_impl.inc).
 //
 //   C[M][N] (op_t) = epilogue(A[M][K] * B[N][K]^T + bias),  A dense row-major (pitch K), N % 256 == 0, K % 64 == 0.
 //

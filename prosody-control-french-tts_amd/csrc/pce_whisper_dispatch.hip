@@ -1,4 +1,4 @@
-// pce_whisper_dispatch.hip -- the Whisper / BERT entry points of include/pce.h: each forwards to the build of pce_whisper_impl.inc
+// pce_whisper_dispatch.hip -- the Whisper / BERT entry points of include/pce.h: each forwards to the build of pce_whisper_impl.inc (and the .inc files it includes)
 // (bf16 or fp16 operands) the context has selected.  The two builds keep separate state (weights, buffers): switching the operand
 // type means loading the weights again.
 #include "pce_internal.h"

@@ -1,6 +1,8 @@
-// pce_whisper.hip -- the transformer work of the alignment step (R8) on gfx950: log-mel spectrogram, Whisper audio encoder,
+// pce_whisper_impl.inc -- the transformer work of the alignment step (R8) on gfx950: log-mel spectrogram, Whisper audio encoder,
 // text decoder (teacher-forced forced alignment with cross-attention DTW; free-running greedy decoding with a K / V
 // cache and openai-whisper's logit filters), and the break-prediction BERT forward, which shares the same kernels.
+// This file: the kernels (with pce_gemm256.inc, pce_xattn.inc), WhisperState, the launchers, the log-mel and encoder entry points; it ends by
+// including the other entry points: pce_whisper_selftest.inc, pce_whisper_decoder.inc, pce_bert.inc (one translation unit per operand type).
 //
 // Replaces the device work of whisper_timestamped.transcribe
 // (Code/Aligners/use_whisper_timestamped.py:139,150-163), as openai-whisper==20240930 defines it (third-party,
@@ -1149,6 +1151,15 @@ static void launch_attention(pce_ctx *c, dim3 grid, const AttnArgs &a, double fl
     if (grid.x == 1) hipLaunchKernelGGL(k_attention_lean16<true>, grid, dim3(256), 0, c->stream, a, force_exact);
     else hipLaunchKernelGGL(k_attention_lean16<false>, grid, dim3(256), 0, c->stream, a, force_exact);
 }
+// The product's attention launch (the one place it fills an AttnArgs): H heads of n clips, up to q_rows queries each, out rows of H * 64
+static void launch_attention_rows(pce_ctx *c, int n, int H, int q_rows, const op_t *q, int64_t q_ld, const op_t *k, int64_t k_ld, const op_t *vt, int vt_sp,
+                                  const int *q_row0, const int *q_len, const int *k_row0, const int *k_len, op_t *out, int causal, double flops = 0.0)
+{
+    AttnArgs a{};
+    a.q = q; a.q_ld = q_ld; a.k = k; a.k_ld = k_ld; a.vt = vt; a.vt_clip = (int64_t)H * 64 * vt_sp; a.vt_sp = vt_sp;
+    a.q_row0 = q_row0; a.q_len = q_len; a.k_row0 = k_row0; a.k_len = k_len; a.out = out; a.out_ld = H * 64; a.causal = causal;
+    launch_attention(c, dim3((unsigned)div_up(q_rows, AT_QB), (unsigned)H, (unsigned)n), a, flops);
+}
 
 // ---------------------------------------------------------------------------
 // Text decoder (teacher forced) and cross-attention alignment  -- openai-whisper timing.py find_alignment
@@ -1703,17 +1714,6 @@ __global__ __launch_bounds__(DR_T) void k_decode_rules(const float *__restrict__
     }
 }
 
-// BERT embeddings: word[id] + token_type[0] + position[t] (the LayerNorm follows as its own launch)
-__global__ void k_bert_embed(const int *__restrict__ tokens /* [seqs][T_pad] */, const float *__restrict__ word, const float *__restrict__ pos,
-                             const float *__restrict__ type0, int T_pad, int n_pos, int d, int64_t rows, float *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * d) return;
-    const int64_t m = i / d; const int col = (int)(i - m * d);
-    int t = (int)(m % T_pad); if (t >= n_pos) t = n_pos - 1;        // pad rows: any finite value
-    out[i] = (word[(int64_t)tokens[m] * d + col] + type0[col]) + pos[(int64_t)t * d + col];
-}
-
 // softmax over the audio frames of the (scaled) cross-attention logits of one alignment head:
 // w[clip][sel][t][s] = softmax_s(q_t . k_s * 0.125 * qk_scale), s < F_c.  16 tokens per workgroup, 4 waves x 16
 // keys per 64-key tile on v_mfma_f32_16x16x32_bf16, two passes (row max / sum, then normalised write).
@@ -2255,46 +2255,6 @@ static int lds_optins(pce_ctx *c, WhisperState *w)
     return PCE_OK;
 }
 
-// pce_selftest_gemm_tiled: the kernel a selector stands for (GK_AUTO: the product's rule), or -1 where that kernel does not compute the shape
-template <int EPI> static int selftest_gemm_kind(const pce_ctx *c, int kernel, const GemmShape &s)
-{
-    const int kind = kernel == GK_AUTO ? gemm_choose<EPI>(c, s) : kernel;
-    return gemm_fits<EPI>(kind, s) ? kind : -1;
-}
-
-// pce_selftest_layernorm's k_add_layernorm forms: the stream is updated in place when it keeps its type (as the encoder runs it), else written to
-// a second buffer
-template <class OUT, class RIN, class ROUT>
-static int selftest_add_layernorm(pce_ctx *c, int64_t rows, int d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w, const float *b,
-                                  float eps, int write_resid, void *out, void *resid_out, uint16_t *out_copy)
-{
-    constexpr bool IN_PLACE = std::is_same<RIN, ROUT>::value;
-    const size_t n = (size_t)rows * d;
-    DevBuf din, dres, ddl, ddl2, dw, db, dout, dcopy;
-    PCE_HIP(c, din.reserve(sizeof(RIN) * n)); PCE_HIP(c, ddl.reserve(2 * n)); PCE_HIP(c, dw.reserve(sizeof(float) * d)); PCE_HIP(c, db.reserve(sizeof(float) * d));
-    PCE_HIP(c, dout.reserve(sizeof(OUT) * n));
-    if (!IN_PLACE) PCE_HIP(c, dres.reserve(sizeof(ROUT) * n));
-    if (delta2) PCE_HIP(c, ddl2.reserve(2 * n));
-    if (out_copy) PCE_HIP(c, dcopy.reserve(2 * n));
-    PCE_HIP(c, hipMemcpyAsync(din.p, x, sizeof(RIN) * n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(ddl.p, delta, 2 * n, hipMemcpyHostToDevice, c->stream));
-    if (delta2) PCE_HIP(c, hipMemcpyAsync(ddl2.p, delta2, 2 * n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dout.p, 0, sizeof(OUT) * n, c->stream));
-    if (!IN_PLACE) PCE_HIP(c, hipMemsetAsync(dres.p, 0, sizeof(ROUT) * n, c->stream));
-    if (out_copy) PCE_HIP(c, hipMemsetAsync(dcopy.p, 0, 2 * n, c->stream));
-    ROUT *rout = IN_PLACE ? din.as<ROUT>() : dres.as<ROUT>();
-    launch_add_layernorm<OUT, RIN, ROUT>(c, din.as<RIN>(), rout, ddl.as<op_t>(), delta2 ? ddl2.as<op_t>() : nullptr, write_resid, dw.as<float>(), db.as<float>(),
-                                         rows, d, dout.as<OUT>(), eps, out_copy ? dcopy.as<op_t>() : nullptr);
-    PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, sizeof(OUT) * n, hipMemcpyDeviceToHost, c->stream));
-    if (resid_out) PCE_HIP(c, hipMemcpyAsync(resid_out, rout, sizeof(ROUT) * n, hipMemcpyDeviceToHost, c->stream));
-    if (out_copy) PCE_HIP(c, hipMemcpyAsync(out_copy, dcopy.p, 2 * n, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    return PCE_OK;
-}
-
 } // namespace
 
 void pce_whisper_free(pce_ctx *c)
@@ -2580,14 +2540,9 @@ int pce_whisper_encode_run(pce_ctx *c)
         if (!done)
             launch_gemm<EPI_QKV>(c, w->ln_out.as<op_t>(), d, 0, Wb + ly.qkv_w, (int)M, 3 * d, d, Wf + ly.qkv_b, w->qkv.as<op_t>(), 2 * d, 0, 1,
                                  reinterpret_cast<const float *>(w->vt.as<op_t>()), W_CTX, 2 * d, AT_SP);
-        {
-            AttnArgs a{};
-            a.q = w->qkv.as<op_t>(); a.q_ld = 2 * d; a.k = w->qkv.as<op_t>() + d; a.k_ld = 2 * d;
-            a.vt = w->vt.as<op_t>(); a.vt_clip = (int64_t)d * AT_SP; a.vt_sp = AT_SP;
-            a.q_row0 = a.k_row0 = w->enc_tab.as<int>(); a.q_len = a.k_len = w->enc_tab.as<int>() + n;
-            a.out = w->attn.as<op_t>(); a.out_ld = d; a.causal = 0;
-            launch_attention(c, dim3((unsigned)div_up(W_CTX, AT_QB), (unsigned)H, (unsigned)n), a, 4.0 * W_CTX * (double)W_CTX * d * n);
-        }
+        const int *row0 = w->enc_tab.as<int>(), *len = row0 + n;
+        launch_attention_rows(c, n, H, W_CTX, w->qkv.as<op_t>(), 2 * d, w->qkv.as<op_t>() + d, 2 * d, w->vt.as<op_t>(), AT_SP, row0, len, row0, len,
+                              w->attn.as<op_t>(), 0, 4.0 * W_CTX * (double)W_CTX * d * n);
         if (flat) {
             if (!launch_gemm_flat<FEPI_BF16>(c, w->attn.as<op_t>(), Wb + ly.out_w, Wf + ly.out_b, w->delta.as<op_t>(), (int)M, d, d, d, 1, 0, PCE_K_GEMM_FLAT_OUT))
                 return pce_fail(c, PCE_E_LIMIT, "attention projection does not fit the 256 x 256 kernel");
@@ -2616,361 +2571,6 @@ int pce_whisper_encode_run(pce_ctx *c)
     return PCE_OK;
 }
 
-// Cross-attention keys (rows, [Ma][d]) and values (transposed per clip, key axis padded to AT_SP) of one decoder layer from the
-// encoded audio: W = [K weights | V weights] (2d rows of d).  On the persistent 256 x 256 kernel when the shape fits.
-static void project_cross_kv(pce_ctx *c, const op_t *enc, int Ma, int d, const op_t *W, const float *bias, op_t *xk, op_t *xvt)
-{
-    // one launch: K columns leave row-major, V columns as the transposed image (the 590 MB of encoded audio are swept once)
-    if (launch_gemm_flat<FEPI_SPLIT>(c, enc, W, bias, xk, Ma, 2 * d, d, d, W_CTX, AT_SP, PCE_K_GEMM_FLAT_XKV, xvt, d)) return;
-    launch_gemm<EPI_QKV>(c, enc, d, 0, W, Ma, 2 * d, d, bias, xk, d, 0, 1, reinterpret_cast<const float *>(xvt), W_CTX, d, AT_SP);
-}
-
-// V rows of clip c at rows k_row0[c] .. + k_len[c] of [.][heads * 64] -> the V^T image the attention kernels read: [clip][head * 64 + d][sp] (the
-// rest of the key axis keeps its zeros)
-static __global__ void k_selftest_vt(const op_t *__restrict__ v, const int *__restrict__ k_row0, const int *__restrict__ k_len, int hd, int sp,
-                                     op_t *__restrict__ vt)
-{
-    const int clip = blockIdx.y;
-    const int64_t n = (int64_t)k_len[clip] * hd;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int col = (int)(i % hd), t = (int)(i / hd);
-        vt[((int64_t)clip * hd + col) * sp + t] = v[(int64_t)k_row0[clip] * hd + i];
-    }
-}
-
-// Self-test hooks of the attention kernel through launch_attention (see pce.h)
-int pce_selftest_attention_ragged(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, const int32_t *q_len,
-                                  const int32_t *k_len, int32_t causal, int32_t mode, uint16_t *out, int64_t out_rows, int32_t *fell_back)
-{
-    if (!c || !q || !k || !v || !out || !q_len || !k_len || clips <= 0 || clips > 65535 || heads <= 0 || heads > 65535 || mode < 0 || mode > 1)
-        return PCE_E_INVALID;
-    std::vector<int> tab((size_t)4 * clips);
-    int64_t q_rows = 0, k_rows = 0;
-    int q_max = 0, k_max = 0;
-    for (int i = 0; i < clips; i++) {
-        if (q_len[i] < 1 || k_len[i] < 1 || q_len[i] > (1 << 20) || k_len[i] > (1 << 20)) return pce_fail(c, PCE_E_INVALID, "selftest attention: clip %d has %d queries, %d keys", i, q_len[i], k_len[i]);
-        tab[(size_t)i] = (int)q_rows; tab[(size_t)clips + i] = q_len[i]; tab[(size_t)2 * clips + i] = (int)k_rows; tab[(size_t)3 * clips + i] = k_len[i];
-        q_rows += q_len[i]; k_rows += k_len[i];
-        q_max = q_len[i] > q_max ? q_len[i] : q_max; k_max = k_len[i] > k_max ? k_len[i] : k_max;
-    }
-    const int hd = heads * 64, sp = div_up(k_max, 64) * 64;
-    if (out_rows < q_rows || (out_rows + k_rows) * hd >= ((int64_t)1 << 30)) return pce_fail(c, PCE_E_INVALID, "selftest attention: %lld output rows for %lld queries", (long long)out_rows, (long long)q_rows);
-    PCE_HIP(c, hipSetDevice(c->device));
-    const size_t nq = (size_t)q_rows * hd, nk = (size_t)k_rows * hd, nvt = (size_t)clips * hd * sp, no = (size_t)out_rows * hd;
-    DevBuf dq, dk, dv, dvt, dout, dtab, dcnt;
-    PCE_HIP(c, dq.reserve(nq * 2 + 64)); PCE_HIP(c, dk.reserve(nk * 2 + 64)); PCE_HIP(c, dv.reserve(nk * 2 + 64)); PCE_HIP(c, dvt.reserve(nvt * 2 + 128));
-    PCE_HIP(c, dout.reserve(no * 2 + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * 4 * (size_t)clips)); PCE_HIP(c, dcnt.reserve(sizeof(int)));
-    PCE_HIP(c, hipMemcpyAsync(dq.p, q, nq * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dk.p, k, nk * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dv.p, v, nk * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dout.p, out, no * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dvt.p, 0, nvt * 2 + 128, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dcnt.p, 0, sizeof(int), c->stream));
-    AttnArgs a{};
-    a.q = dq.as<op_t>(); a.q_ld = hd; a.k = dk.as<op_t>(); a.k_ld = hd; a.vt = dvt.as<op_t>(); a.vt_clip = (int64_t)hd * sp; a.vt_sp = sp;
-    a.q_row0 = dtab.as<int>(); a.q_len = a.q_row0 + clips; a.k_row0 = a.q_row0 + 2 * clips; a.k_len = a.q_row0 + 3 * clips;
-    a.out = dout.as<op_t>(); a.out_ld = hd; a.causal = causal; a.fell_back = dcnt.as<int>();
-    hipLaunchKernelGGL(k_selftest_vt, dim3((unsigned)div_up((int64_t)k_max * hd, 256), (unsigned)clips), dim3(256), 0, c->stream, dv.as<op_t>(), a.k_row0,
-                       a.k_len, hd, sp, dvt.as<op_t>());
-    // the grid of the longest clip, as the teacher-forced decoder launches it: one query block takes the NT instantiation
-    launch_attention(c, dim3((unsigned)div_up(q_max, AT_QB), (unsigned)heads, (unsigned)clips), a, 0.0, mode);
-    PCE_HIP(c, hipGetLastError());
-    int cnt = 0;
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, no * 2, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(&cnt, dcnt.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    if (fell_back) *fell_back = cnt;
-    return PCE_OK;
-}
-int pce_selftest_attention(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, int32_t q_len,
-                           int32_t k_len, int32_t causal, int32_t mode, uint16_t *out, int32_t *fell_back)
-{
-    if (!c || !out || clips <= 0 || heads <= 0 || q_len <= 0 || k_len <= 0) return PCE_E_INVALID;
-    const std::vector<int32_t> ql((size_t)clips, q_len), kl((size_t)clips, k_len);
-    std::fill(out, out + (size_t)clips * q_len * heads * 64, (uint16_t)0);
-    return pce_selftest_attention_ragged(c, q, k, v, clips, heads, ql.data(), kl.data(), causal, mode, out, (int64_t)clips * q_len, fell_back);
-}
-
-// Self-test hook of the single-query attention kernels of an incremental decoding step, through the launches the step makes (see pce.h)
-int pce_selftest_attn1(pce_ctx *c, int32_t form, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, uint16_t *k, int64_t k_elems, uint16_t *v,
-                       int64_t v_elems, const int32_t *k_row0, const int32_t *len, const int32_t *skip, int32_t span, uint16_t *out, int64_t out_elems)
-{
-    if (!c || form < 0 || form > 2 || !q || !k || !v || !len || !out || n < 1 || n > 65535 || heads < 1 || span < 1) return PCE_E_INVALID;
-    if (heads > 32) return pce_fail(c, PCE_E_INVALID, "selftest attn1: %d heads (the kernels hold 32)", heads);
-    const int64_t d = (int64_t)heads * 64;
-    const int T_cap = span, vt_sp = form == 0 ? span : 512;
-    if (form == 0 && (!k_row0 || vt_sp % 8 != 0)) return pce_fail(c, PCE_E_INVALID, "selftest attn1: form 0 needs k_row0 and vt_sp %% 8 == 0 (%d)", vt_sp);
-    if (form != 0 && T_cap > 512) return pce_fail(c, PCE_E_INVALID, "selftest attn1: T_cap %d > 512", T_cap);
-    const int64_t q_need = (int64_t)n * d * (form == 0 ? 1 : 3), v_need = (int64_t)n * d * (form == 2 ? T_cap : vt_sp), o_need = (int64_t)n * d;
-    int64_t k_need = form == 0 ? 0 : (int64_t)n * T_cap * d;
-    std::vector<int> tab((size_t)4 * n, 0);                        // k_row0 | k_len | pos | skip
-    for (int i = 0; i < n; i++) {
-        if (form == 0) {
-            if (len[i] < 1 || len[i] > 1536 || k_row0[i] < 0 || (len[i] + 7) / 8 * 8 > vt_sp)
-                return pce_fail(c, PCE_E_INVALID, "selftest attn1: clip %d has %d keys from row %d (V^T pitch %d)", i, len[i], k_row0[i], vt_sp);
-            const int64_t end = ((int64_t)k_row0[i] + len[i]) * d;
-            k_need = end > k_need ? end : k_need;
-            tab[(size_t)i] = k_row0[i]; tab[(size_t)n + i] = len[i];
-        } else {
-            if (len[i] < 0 || len[i] >= T_cap) return pce_fail(c, PCE_E_INVALID, "selftest attn1: clip %d at position %d of %d", i, len[i], T_cap);
-            tab[(size_t)i] = i * T_cap; tab[(size_t)n + i] = len[i] + 1; tab[(size_t)2 * n + i] = len[i];
-        }
-        tab[(size_t)3 * n + i] = skip ? skip[i] : 0;
-    }
-    if (q_elems < q_need || k_elems < k_need || v_elems < v_need || out_elems < o_need || k_elems >= ((int64_t)1 << 31) || v_elems >= ((int64_t)1 << 31))
-        return pce_fail(c, PCE_E_INVALID, "selftest attn1: form %d needs q %lld, k %lld, v %lld, out %lld elements", form, (long long)q_need, (long long)k_need,
-                        (long long)v_need, (long long)o_need);
-    PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
-    DevBuf dq, dk, dv, dout, dtab;
-    PCE_HIP(c, dq.reserve(2 * (size_t)q_elems + 64)); PCE_HIP(c, dk.reserve(2 * (size_t)k_elems + 64)); PCE_HIP(c, dv.reserve(2 * (size_t)v_elems + 64));
-    PCE_HIP(c, dout.reserve(2 * (size_t)out_elems + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * tab.size()));
-    PCE_HIP(c, hipMemcpyAsync(dq.p, q, 2 * (size_t)q_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dk.p, k, 2 * (size_t)k_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dv.p, v, 2 * (size_t)v_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dout.p, out, 2 * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    const int *T = dtab.as<int>(), *SKIP = skip ? T + 3 * n : nullptr;
-    if (form == 2) {
-        SelfAttn1Args sa{};
-        sa.qkv = dq.as<op_t>(); sa.qkv_ld = 3 * d; sa.ck = dk.as<op_t>(); sa.cv = dv.as<op_t>(); sa.c_clip = (int64_t)T_cap * d; sa.d = (int)d;
-        sa.pos = T + 2 * n; sa.skip = SKIP; sa.out = dout.as<op_t>(); sa.out_ld = d;
-        launch_self_attn1(c, n, heads, sa);
-    } else {
-        Attn1Args a{};
-        a.q = dq.as<op_t>(); a.q_ld = form == 0 ? d : 3 * d; a.k = dk.as<op_t>(); a.k_ld = d; a.vt = dv.as<op_t>(); a.vt_clip = d * vt_sp; a.vt_sp = vt_sp;
-        a.k_row0 = T; a.k_len = T + n; a.skip = SKIP; a.out = dout.as<op_t>(); a.out_ld = d;
-        if (form == 1) { a.app_k = dq.as<op_t>() + d; a.app_v = dq.as<op_t>() + 2 * d; a.app_ld = 3 * d; a.app_pos = T + 2 * n; }
-        launch_cross_attn1(c, n, heads, a);
-    }
-    PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
-    if (form != 0) {
-        PCE_HIP(c, hipMemcpyAsync(k, dk.p, 2 * (size_t)k_elems, hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(v, dv.p, 2 * (size_t)v_elems, hipMemcpyDeviceToHost, c->stream));
-    }
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    return PCE_OK;
-}
-
-// Self-test hook of the encoder-output cross-attention of an incremental decoding step (pce_xattn.inc): k_xq_fused -> k_xattn_absorbed -> k_uv_absorb of ONE
-// layer on host arrays, with the number of workgroups per clip forced (0: what the batch size selects).  See include/pce.h.
-int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,
-                       const uint16_t *wv, const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads,
-                       int32_t workgroups_per_clip, uint16_t *out)
-{
-    if (!c || !resid || !ln_w || !ln_b || !wq || !bq || !wk || !wv || !bv || !E || !k_len || !out || n <= 0 || k_cap <= 0) return PCE_E_INVALID;
-    if (!xa_has_form(d, heads))
-        return pce_fail(c, PCE_E_INVALID, "selftest xattn: d = %d with %d heads is not a width the encoder-output form is built for", d, heads);
-    if (!(workgroups_per_clip == 0 || workgroups_per_clip == 1 || workgroups_per_clip == 2 || workgroups_per_clip == 4)) return PCE_E_INVALID;
-    for (int i = 0; i < n; i++) if (k_len[i] <= 0 || k_len[i] > k_cap) return pce_fail(c, PCE_E_INVALID, "selftest xattn: clip %d has %d frames of %d", i, k_len[i], k_cap);
-    PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
-    const size_t dd = (size_t)d * d, ne = (size_t)n * k_cap * d;
-    DevBuf dres, dlw, dlb, dwq, dbq, dwk, dwkT, dwv, dbv, dE, dkl, dqp, dup, dml, dout;
-    PCE_HIP(c, dres.reserve(sizeof(float) * (size_t)n * d)); PCE_HIP(c, dlw.reserve(sizeof(float) * d)); PCE_HIP(c, dlb.reserve(sizeof(float) * d));
-    PCE_HIP(c, dwq.reserve(2 * dd)); PCE_HIP(c, dbq.reserve(sizeof(float) * d)); PCE_HIP(c, dwk.reserve(2 * dd)); PCE_HIP(c, dwkT.reserve(2 * dd));
-    PCE_HIP(c, dwv.reserve(2 * dd)); PCE_HIP(c, dbv.reserve(sizeof(float) * d)); PCE_HIP(c, dE.reserve(2 * ne + 4096)); PCE_HIP(c, dkl.reserve(sizeof(int) * (size_t)n));
-    const size_t R = (size_t)xa_rows(heads);
-    PCE_HIP(c, dqp.reserve(2 * 2 * (size_t)n * R * d + 256)); PCE_HIP(c, dup.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
-    PCE_HIP(c, dml.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * 2 + 256)); PCE_HIP(c, dout.reserve(2 * (size_t)n * d + 64));
-    struct Up { void *dst; const void *src; size_t bytes; } ups[] = {
-        {dres.p, resid, sizeof(float) * (size_t)n * d}, {dlw.p, ln_w, sizeof(float) * d}, {dlb.p, ln_b, sizeof(float) * d}, {dwq.p, wq, 2 * dd}, {dbq.p, bq, sizeof(float) * d},
-        {dwk.p, wk, 2 * dd}, {dwv.p, wv, 2 * dd}, {dbv.p, bv, sizeof(float) * d}, {dE.p, E, 2 * ne}, {dkl.p, k_len, sizeof(int) * (size_t)n}};
-    for (const Up &u : ups) PCE_HIP(c, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dqp.p, 0, dqp.cap, c->stream)); PCE_HIP(c, hipMemsetAsync(dout.p, 0, dout.cap, c->stream));
-    hipLaunchKernelGGL(k_transpose_sq, dim3((unsigned)(d / 32), (unsigned)(d / 32)), dim3(256), 0, c->stream, dwk.as<op_t>(), dwkT.as<op_t>(), d);
-    XaArgs a{};
-    a.E = dE.as<op_t>(); a.e_clip = (int64_t)k_cap * d; a.e_ld = d; a.k_len = dkl.as<int>(); a.skip = nullptr;
-    a.u_part = dup.as<float>(); a.ml_part = dml.as<float>(); a.heads = heads; a.nsplit = xa_split(n, workgroups_per_clip); a.rows = (int)R;
-    XaLayer y{};
-    y.resid = dres.as<float>(); y.ln_w = dlw.as<float>(); y.ln_b = dlb.as<float>(); y.wq = dwq.as<op_t>(); y.bq = dbq.as<float>(); y.wkT = dwkT.as<op_t>();
-    y.wv = dwv.as<op_t>(); y.bv = dbv.as<float>(); y.qp_hi = dqp.as<op_t>(); y.qp_lo = y.qp_hi + (size_t)n * R * d; y.out = dout.as<op_t>(); y.out_ld = d;
-    xattn_launch(c, d, n, a, y);
-    PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)n * d, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    return PCE_OK;
-}
-
-// Self-test hook of the persistent 256 x 256 GEMM: C = epilogue(A B^T + bias) on host arrays (op_t bit patterns in, op_t bit patterns out).
-// epilogue 0: bias, 1: bias + GELU, 2: bias, written transposed per clip (rows_per_clip rows, key axis padded to vt_sp): out[(clip N + n) vt_sp + t]
-int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, int32_t epilogue,
-                      int32_t rows_per_clip, int32_t vt_sp, uint16_t *out)
-{
-    if (!c || !A || !B || !out || M <= 0 || N <= 0 || K <= 0) return PCE_E_INVALID;
-    PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
-    if (epilogue >= 16 && epilogue <= 19) {
-        // the tiled / few-row kernels behind launch_gemm (which of them runs follows from the shape and PCE_GEMM_SKINNY; pce_selftest_gemm_tiled
-        // chooses one and takes every epilogue): 16 = bias,
-        // 17 = bias + GELU (16-bit outputs), 19 = accumulate into a zeroed fp32 matrix (out receives M * N floats)
-        const bool f32 = epilogue == 19;
-        DevBuf tA, tB, tC, tb;
-        PCE_HIP(c, tA.reserve((size_t)M * K * 2 + 4096)); PCE_HIP(c, tB.reserve((size_t)(N + 128) * K * 2 + 4096)); PCE_HIP(c, tC.reserve((size_t)M * N * 4 + 4096));
-        PCE_HIP(c, tb.reserve((size_t)(N + 128) * 4));
-        PCE_HIP(c, hipMemsetAsync(tB.p, 0, (size_t)(N + 128) * K * 2, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(tA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(tB.p, B, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemsetAsync(tb.p, 0, (size_t)(N + 128) * 4, c->stream));
-        if (bias) PCE_HIP(c, hipMemcpyAsync(tb.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemsetAsync(tC.p, 0, (size_t)M * N * 4, c->stream));
-        if (N % 128) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): N must be a multiple of 128");
-        c->gemm_few_rows = true;                                   // (the few-row kernel is eligible here, as in an incremental decoding step)
-        struct Off { pce_ctx *c; ~Off() { c->gemm_few_rows = false; } } off{c};
-        if (epilogue == 16) launch_gemm<EPI_BF16>(c, tA.as<op_t>(), K, 0, tB.as<op_t>(), M, N, K, tb.as<float>(), tC.p, N, 0, 1);
-        else if (epilogue == 17) launch_gemm<EPI_GELU_BF16>(c, tA.as<op_t>(), K, 0, tB.as<op_t>(), M, N, K, tb.as<float>(), tC.p, N, 0, 1);
-        else if (epilogue == 19) launch_gemm<EPI_RESID_F32>(c, tA.as<op_t>(), K, 0, tB.as<op_t>(), M, N, K, tb.as<float>(), tC.p, N, 0, 1);
-        else return pce_fail(c, PCE_E_INVALID, "selftest gemm: epilogue 18 does not exist");
-        PCE_HIP(c, hipGetLastError());
-        PCE_HIP(c, hipMemcpyAsync(out, tC.p, (size_t)M * N * (f32 ? 4 : 2), hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipStreamSynchronize(c->stream));
-        pce_profile_collect(c);
-        return PCE_OK;
-    }
-    const size_t n_out = epilogue == 2 ? (size_t)(M / rows_per_clip) * N * vt_sp
-                         : epilogue >= 256 ? (size_t)M * epilogue + (size_t)(M / rows_per_clip) * (N - epilogue) * vt_sp : (size_t)M * N;
-    DevBuf dA, dB, dC, dbias;
-    PCE_HIP(c, dA.reserve((size_t)M * K * 2)); PCE_HIP(c, dB.reserve((size_t)N * K * 2)); PCE_HIP(c, dC.reserve(n_out * 2)); PCE_HIP(c, dbias.reserve((size_t)N * 4));
-    PCE_HIP(c, hipMemcpyAsync(dA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dB.p, B, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
-    if (bias) PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dC.p, 0, n_out * 2, c->stream));
-    bool ok = false;
-    const float *bp = bias ? dbias.as<float>() : nullptr;
-    if (epilogue == 0) ok = launch_gemm_flat<FEPI_BF16>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, N);
-    else if (epilogue == 1) ok = launch_gemm_flat<FEPI_GELU>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, N);
-    else if (epilogue == 2) ok = launch_gemm_flat<FEPI_VT>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, 0, rows_per_clip, vt_sp);
-    else if (epilogue >= 256 && epilogue % 256 == 0 && epilogue < N)      // split launch: columns [0, epilogue) row-major [M][epilogue], then the V^T image of the rest
-        ok = launch_gemm_flat<FEPI_SPLIT>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, epilogue, rows_per_clip, vt_sp, PCE_K_GEMM_FLAT,
-                                          dC.as<op_t>() + (size_t)M * epilogue, epilogue);
-    int rc = PCE_OK;
-    if (!ok) rc = pce_fail(c, PCE_E_LIMIT, "shape not handled by the 256 x 256 kernel (N %% 256, K %% 64)");
-    else {
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dC.p, n_out * 2, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = pce_fail(c, PCE_E_DEVICE, "selftest gemm: %s", hipGetErrorString(e));
-    }
-    (void)hipStreamSynchronize(c->stream);
-    pce_profile_collect(c);
-    return rc;
-}
-
-// Self-test hook of the tiled / few-row GEMM kernels through the product's own launch code (launch_gemm_kernel; see pce.h).  Every byte a launch
-// can address is checked against the caller's buffer lengths before anything is allocated.
-int pce_selftest_gemm_tiled(pce_ctx *c, int32_t kernel, int32_t epilogue, const uint16_t *A, int64_t a_len, int64_t lda, int64_t a_batch, int32_t batch,
-                            const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, void *C, int64_t c_len, int64_t ldc, int64_t c_batch,
-                            const float *pos, int32_t pos_T, int32_t v_col0, int32_t rows_per_clip, int32_t vt_sp, uint16_t *vt, int64_t vt_len,
-                            int32_t *kernel_used)
-{
-    if (!c || !A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || kernel < GK_AUTO || kernel > GK_128_DEEP || epilogue < EPI_BF16 || epilogue > EPI_F32)
-        return PCE_E_INVALID;
-    const bool f32 = epilogue == EPI_GELU_POS_F32 || epilogue == EPI_RESID_F32 || epilogue == EPI_F32, qkv = epilogue == EPI_QKV;
-    const int64_t nc = qkv ? v_col0 : N;                                 // row-major output columns
-    if (lda < 1 || lda % 8 || a_batch < 0 || a_batch % 8 || ldc < nc || ldc % 8 || c_batch < 0 || c_batch % 8)
-        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): lda, a_batch, ldc, c_batch must be multiples of 8 (16-byte rows), ldc >= the output columns");
-    if ((int64_t)(batch - 1) * a_batch + (int64_t)(M - 1) * lda + K > a_len)
-        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): A holds %lld elements, the shape reads beyond them", (long long)a_len);
-    if (nc > 0 && (int64_t)(batch - 1) * c_batch + (int64_t)(M - 1) * ldc + nc > c_len)
-        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): C holds %lld elements, the shape writes beyond them", (long long)c_len);
-    if (epilogue == EPI_GELU_POS_F32 && (!pos || pos_T < 1)) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): GELU_POS_F32 needs pos [pos_T][N]");
-    int64_t n_vt = 0;
-    if (qkv) {
-        // V columns [v_col0, N) leave as vt[clip][column - v_col0][t] (clip = row / rows_per_clip, t < rows_per_clip <= vt_sp): four rows per store
-        const int S = rows_per_clip;
-        if (!vt || batch != 1 || v_col0 < 0 || v_col0 >= N || (N - v_col0) % 64 || S < 4 || S % 4 || vt_sp < S || vt_sp % 4)
-            return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): QKV needs vt, batch 1, 0 <= v_col0 < N, rows_per_clip %% 4 == 0, rows_per_clip <= vt_sp, vt_sp %% 4 == 0");
-        n_vt = (int64_t)div_up(M, S) * (N - v_col0) * vt_sp;
-        if (n_vt > vt_len) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): vt holds %lld elements, the V image needs %lld", (long long)vt_len, (long long)n_vt);
-    }
-    const GemmShape s{M, N, K, lda, batch, qkv ? v_col0 : 0};
-    // refuse what the chosen kernel cannot compute before any allocation
-    const int kind = epilogue == EPI_BF16 ? selftest_gemm_kind<EPI_BF16>(c, kernel, s) : epilogue == EPI_GELU_BF16 ? selftest_gemm_kind<EPI_GELU_BF16>(c, kernel, s)
-                     : epilogue == EPI_GELU_POS_F32 ? selftest_gemm_kind<EPI_GELU_POS_F32>(c, kernel, s) : epilogue == EPI_RESID_F32 ? selftest_gemm_kind<EPI_RESID_F32>(c, kernel, s)
-                     : epilogue == EPI_QKV ? selftest_gemm_kind<EPI_QKV>(c, kernel, s) : selftest_gemm_kind<EPI_F32>(c, kernel, s);
-    if (kind < 0)
-        return pce_fail(c, PCE_E_LIMIT, "selftest gemm (tiled): kernel %d does not compute epilogue %d at M %d x N %d x K %d (lda %lld, batch %d, v_col0 %d)",
-                        kernel, epilogue, M, N, K, (long long)lda, batch, v_col0);
-    if (kernel_used) *kernel_used = kind;
-    PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
-    const size_t esz = f32 ? 4 : 2;
-    DevBuf dA, dB, dbias, dC, dpos, dvt;
-    PCE_HIP(c, dA.reserve(2 * (size_t)a_len)); PCE_HIP(c, dB.reserve(2 * (size_t)N * K)); PCE_HIP(c, dC.reserve(esz * (size_t)c_len + 16));
-    PCE_HIP(c, hipMemcpyAsync(dA.p, A, 2 * (size_t)a_len, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dB.p, B, 2 * (size_t)N * K, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dC.p, C, esz * (size_t)c_len, hipMemcpyHostToDevice, c->stream));       // (read by RESID_F32; kept where nothing is written)
-    if (bias) { PCE_HIP(c, dbias.reserve(sizeof(float) * N)); PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, sizeof(float) * N, hipMemcpyHostToDevice, c->stream)); }
-    if (epilogue == EPI_GELU_POS_F32) {
-        PCE_HIP(c, dpos.reserve(sizeof(float) * (size_t)pos_T * N));
-        PCE_HIP(c, hipMemcpyAsync(dpos.p, pos, sizeof(float) * (size_t)pos_T * N, hipMemcpyHostToDevice, c->stream));
-    }
-    if (qkv) { PCE_HIP(c, dvt.reserve(2 * (size_t)vt_len)); PCE_HIP(c, hipMemcpyAsync(dvt.p, vt, 2 * (size_t)vt_len, hipMemcpyHostToDevice, c->stream)); }
-    const op_t *a = dA.as<op_t>(), *b = dB.as<op_t>();
-    const float *bp = bias ? dbias.as<float>() : nullptr;
-    switch (epilogue) {
-    case EPI_BF16: launch_gemm_kernel<EPI_BF16>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
-    case EPI_GELU_BF16: launch_gemm_kernel<EPI_GELU_BF16>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
-    case EPI_GELU_POS_F32: launch_gemm_kernel<EPI_GELU_POS_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, dpos.as<float>(), pos_T, 0, 0); break;
-    case EPI_RESID_F32: launch_gemm_kernel<EPI_RESID_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
-    case EPI_QKV:        // (the V^T image travels in the pos argument, its clip length in pos_T: as the product launches it)
-        launch_gemm_kernel<EPI_QKV>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, reinterpret_cast<const float *>(dvt.as<op_t>()),
-                                    rows_per_clip, v_col0, vt_sp);
-        break;
-    default: launch_gemm_kernel<EPI_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
-    }
-    PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(C, dC.p, esz * (size_t)c_len, hipMemcpyDeviceToHost, c->stream));
-    if (qkv) PCE_HIP(c, hipMemcpyAsync(vt, dvt.p, 2 * (size_t)vt_len, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    pce_profile_collect(c);
-    return PCE_OK;
-}
-
-// Self-test hook of the LayerNorm kernels (k_layernorm, k_add_layernorm) as the product launches them (launch_layernorm / launch_add_layernorm; see pce.h)
-int pce_selftest_layernorm(pce_ctx *c, int32_t form, int32_t rows, int32_t d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w,
-                           const float *b, float eps, int32_t flags, void *out, void *resid_out, uint16_t *out_copy)
-{
-    if (!c || !x || !w || !b || !out || rows <= 0 || form < 0 || form > 7) return PCE_E_INVALID;
-    if (d < 4 || d % 4 || d > LN_D_MAX) return pce_fail(c, PCE_E_LIMIT, "selftest layernorm: d = %d (need d %% 4 == 0, d <= %d)", d, LN_D_MAX);
-    PCE_HIP(c, hipSetDevice(c->device));
-    const size_t n = (size_t)rows * d;
-    if (form <= 1) {
-        // k_layernorm<float | op_t>; flags bit 0: round_in16, bit 1: out2 = x (in place, as the BERT layers write their fp32 stream), returned in resid_out
-        const bool in_place = flags & 2;
-        if (in_place && !resid_out) return PCE_E_INVALID;
-        DevBuf dx, dw, db, dout;
-        PCE_HIP(c, dx.reserve(sizeof(float) * n)); PCE_HIP(c, dw.reserve(sizeof(float) * d)); PCE_HIP(c, db.reserve(sizeof(float) * d));
-        PCE_HIP(c, dout.reserve((form ? 2 : 4) * n));
-        PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemsetAsync(dout.p, 0, (form ? 2 : 4) * n, c->stream));
-        float *o2 = in_place ? dx.as<float>() : nullptr;
-        if (form) launch_layernorm<op_t>(c, dx.as<float>(), dw.as<float>(), db.as<float>(), rows, d, dout.as<op_t>(), eps, o2, flags & 1);
-        else launch_layernorm<float>(c, dx.as<float>(), dw.as<float>(), db.as<float>(), rows, d, dout.as<float>(), eps, o2, flags & 1);
-        PCE_HIP(c, hipGetLastError());
-        PCE_HIP(c, hipMemcpyAsync(out, dout.p, (form ? 2 : 4) * n, hipMemcpyDeviceToHost, c->stream));
-        if (in_place) PCE_HIP(c, hipMemcpyAsync(resid_out, dx.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipStreamSynchronize(c->stream));
-        return PCE_OK;
-    }
-    // k_add_layernorm<OUT, RIN, ROUT>: form 2 + 3 o + s, o = 0: fp32 output, 1: 16-bit output; s = 0: fp32 stream, 1: fp32 in / 16-bit out, 2: 16-bit stream.
-    // flags bit 2: write_resid
-    if (!delta) return PCE_E_INVALID;
-    const int o = (form - 2) / 3, st = (form - 2) % 3, wr = (flags >> 2) & 1;
-    if (o == 0) {
-        if (st == 0) return selftest_add_layernorm<float, float, float>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
-        if (st == 1) return selftest_add_layernorm<float, float, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
-        return selftest_add_layernorm<float, op_t, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
-    }
-    if (st == 0) return selftest_add_layernorm<op_t, float, float>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
-    if (st == 1) return selftest_add_layernorm<op_t, float, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
-    return selftest_add_layernorm<op_t, op_t, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
-}
-
 int pce_whisper_encode_fetch(pce_ctx *c, int32_t clip, float *out)
 {
     if (!c || !out) return PCE_E_INVALID;
@@ -2986,930 +2586,6 @@ int pce_whisper_encode_fetch(pce_ctx *c, int32_t clip, float *out)
 
 } // extern "C"
 
-int pce_dtw_launch(pce_ctx *c, const double *d_x, int64_t x_stride, int ld, const int *d_rows, const int *d_cols, int N_max, int M_max,
-                   int batch, unsigned char *d_trace, int *d_pi, int *d_pj, int *d_pl);
-
-extern "C" {
-
-int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, const float *weights, int64_t n_floats)
-{
-    if (!c || !dims || !weights) return PCE_E_INVALID;
-    const int d = dims->n_state, L = dims->n_layer, V = dims->n_vocab, TC = dims->n_text_ctx;
-    if (d <= 0 || d % 128 || dims->n_head * 64 != d || L <= 0 || V <= 0 || V > DR_K * DR_T || TC <= 0 || TC > 448)
-        return pce_fail(c, PCE_E_LIMIT, "unsupported decoder dims (need n_state %% 128 == 0, head size 64, n_text_ctx <= 448, n_vocab <= 52224)");
-    if (dims->n_head > 32) return pce_fail(c, PCE_E_LIMIT, "decoder with %d heads: the decoding kernels take at most 32", dims->n_head);
-    static_assert(32 * 64 <= LN_D_MAX, "the decoder's LayerNorms must hold 32 heads");
-    const int64_t per_layer = 2LL * d + (4LL * d * d + 3LL * d) + 2LL * d + (4LL * d * d + 3LL * d) + 2LL * d + 8LL * d * d + 5LL * d;
-    const int64_t expect = (int64_t)V * d + (int64_t)TC * d + L * per_layer + 2LL * d;
-    if (n_floats != expect) return pce_fail(c, PCE_E_INVALID, "decoder weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
-    PCE_HIP(c, hipSetDevice(c->device));
-    WhisperState *w = ws_of(c);
-    { const int rc = lds_optins(c, w); if (rc) return rc; }
-    w->tdims = *dims; w->dec_loaded = false; w->dlayers.assign((size_t)L, {});
-    std::vector<float> mats, vecs;
-    auto add_vec = [&](const float *p, size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), p, p + n); return o; };
-    auto add_zero = [&](size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), n, 0.f); return o; };
-    auto add_mat = [&](const float *p, size_t n) { size_t o = mats.size(); mats.insert(mats.end(), p, p + n); return o; };
-    const float *p = weights;
-    const float *tok = p; p += (size_t)V * d;
-    const float *pos = p; p += (size_t)TC * d;
-    const size_t dd = (size_t)d * d;
-    for (int l = 0; l < L; l++) {
-        WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-        ly.ln1_w = add_vec(p, (size_t)d); p += d; ly.ln1_b = add_vec(p, (size_t)d); p += d;
-        {   // self attention: q.w q.b k.w v.w v.b out.w out.b -> fused [3d][d]
-            const float *qw = p, *qb = qw + dd, *kw = qb + d, *vw = kw + dd, *vb = vw + dd;
-            ly.qkv_w = add_mat(qw, dd); add_mat(kw, dd); add_mat(vw, dd);
-            ly.qkv_b = add_vec(qb, (size_t)d); add_zero((size_t)d); add_vec(vb, (size_t)d);
-            p = vb + d;
-            ly.out_w = add_mat(p, dd); p += dd; ly.out_b = add_vec(p, (size_t)d); p += d;
-        }
-        ly.lnx_w = add_vec(p, (size_t)d); p += d; ly.lnx_b = add_vec(p, (size_t)d); p += d;
-        {   // cross attention: q from text, k | v from audio -> [d][d] and fused [2d][d]
-            const float *qw = p, *qb = qw + dd, *kw = qb + d, *vw = kw + dd, *vb = vw + dd;
-            ly.xq_w = add_mat(qw, dd); ly.xq_b = add_vec(qb, (size_t)d);
-            ly.xkv_w = add_mat(kw, dd); add_mat(vw, dd);
-            ly.xkv_b = add_zero((size_t)d); add_vec(vb, (size_t)d);
-            p = vb + d;
-            ly.xout_w = add_mat(p, dd); p += dd; ly.xout_b = add_vec(p, (size_t)d); p += d;
-        }
-        ly.ln2_w = add_vec(p, (size_t)d); p += d; ly.ln2_b = add_vec(p, (size_t)d); p += d;
-        ly.m1_w = add_mat(p, 4 * dd); p += 4 * dd; ly.m1_b = add_vec(p, (size_t)4 * d); p += 4 * d;
-        ly.m2_w = add_mat(p, 4 * dd); p += 4 * dd; ly.m2_b = add_vec(p, (size_t)d); p += d;
-    }
-    w->dln_w = add_vec(p, (size_t)d); p += d; w->dln_b = add_vec(p, (size_t)d); p += d;
-    DevBuf tmp;
-    PCE_HIP(c, tmp.reserve(sizeof(float) * mats.size()));
-    PCE_HIP(c, w->dw_bf16.reserve(sizeof(op_t) * mats.size() + 256));
-    PCE_HIP(c, w->dw_f32.reserve(sizeof(float) * vecs.size()));
-    PCE_HIP(c, w->d_tok_emb.reserve(sizeof(float) * (size_t)V * d));
-    PCE_HIP(c, w->d_pos_emb.reserve(sizeof(float) * (size_t)TC * d));
-    PCE_HIP(c, hipMemcpyAsync(tmp.p, mats.data(), sizeof(float) * mats.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->dw_f32.p, vecs.data(), sizeof(float) * vecs.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->d_tok_emb.p, tok, sizeof(float) * (size_t)V * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->d_pos_emb.p, pos, sizeof(float) * (size_t)TC * d, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(),
-                       w->dw_bf16.as<op_t>(), (int64_t)mats.size());
-    {   // tied output projection for free-running decoding: the token embedding in op_t, rows padded to the 128-column GEMM tile
-        const size_t Vp = (size_t)div_up(V, 128) * 128;
-        PCE_HIP(c, w->g_emb_bf16.reserve(sizeof(op_t) * Vp * (size_t)d + 256));
-        PCE_HIP(c, hipMemsetAsync(w->g_emb_bf16.p, 0, sizeof(op_t) * Vp * (size_t)d, c->stream));
-        hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)V * d, 256)), dim3(256), 0, c->stream, w->d_tok_emb.as<float>(),
-                           w->g_emb_bf16.as<op_t>(), (int64_t)V * d);
-    }
-    {   // Wk^T of every layer's cross-attention: the second operand of k_xq_fused (pce_xattn.inc)
-        PCE_HIP(c, w->g_wkT.reserve(sizeof(op_t) * dd * (size_t)L + 256));
-        for (int l = 0; l < L; l++)
-            hipLaunchKernelGGL(k_transpose_sq, dim3((unsigned)(d / 32), (unsigned)(d / 32)), dim3(256), 0, c->stream, w->dw_bf16.as<op_t>() + w->dlayers[(size_t)l].xkv_w,
-                               w->g_wkT.as<op_t>() + dd * (size_t)l, d);
-    }
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    w->dec_loaded = true; w->g_xkv_clips = -1; w->g_cache_len = -1;
-    w->g_cache_n = -1;                  // the self-attention cache is sized by THIS decoder's width and layers: another decoder, another cache
-    return PCE_OK;
-}
-
-int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const int32_t *num_frames, int32_t sot_len,
-                          const uint8_t *head_mask, int32_t medfilt_width, float qk_scale)
-{
-    if (!c || !tokens || !token_offsets || !num_frames) return PCE_E_INVALID;
-    WhisperState *w = ws_of(c);
-    if (!w->dec_loaded) return pce_fail(c, PCE_E_STATE, "pce_whisper_align_run before pce_whisper_decoder_load");
-    if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "run pce_whisper_encode_run first");
-    if (w->tdims.n_state != w->dims.n_state) return pce_fail(c, PCE_E_INVALID, "decoder and encoder widths differ");
-    if (medfilt_width < 1 || medfilt_width > 15 || !(medfilt_width & 1)) return pce_fail(c, PCE_E_INVALID, "median filter width must be odd, <= 15");
-    PCE_HIP(c, hipSetDevice(c->device));
-    const int n = w->n_clips_enc, d = w->tdims.n_state, H = w->tdims.n_head, L = w->tdims.n_layer, V = w->tdims.n_vocab;
-    // ---- shapes
-    int T_max = 0, F_max = 0, N_max = 0;
-    std::vector<int> t_len((size_t)n), f_len((size_t)n);
-    for (int i = 0; i < n; i++) {
-        const int T = token_offsets[i + 1] - token_offsets[i];
-        if (T < sot_len + 2 || T > w->tdims.n_text_ctx) return pce_fail(c, PCE_E_INVALID, "clip %d: %d tokens (need %d..%d)", i, T, sot_len + 2, w->tdims.n_text_ctx);
-        int F = num_frames[i] / 2; if (F > W_CTX) F = W_CTX; if (F < 1) return pce_fail(c, PCE_E_INVALID, "clip %d: no audio frames", i);
-        t_len[(size_t)i] = T; f_len[(size_t)i] = F;
-        T_max = std::max(T_max, T); F_max = std::max(F_max, F); N_max = std::max(N_max, T - sot_len - 1);
-    }
-    const int T_pad = (int)div_up(T_max, 16) * 16, F_pad = (int)div_up(F_max, 64) * 64, SPD = 512;   // (token rows: 16-row granularity, see the prefix run)
-    const int64_t Mt = (int64_t)n * T_pad, Ma = (int64_t)n * W_CTX;
-    // selected heads (default: every head of the last half of the layers, as whisper's Whisper.__init__ sets alignment_heads)
-    std::vector<int> heads; std::vector<int> layer_first((size_t)L + 1, 0);
-    for (int l = 0; l < L; l++) {
-        layer_first[(size_t)l] = (int)heads.size();
-        for (int hh = 0; hh < H; hh++)
-            if (head_mask ? head_mask[l * H + hh] != 0 : l >= L / 2) heads.push_back(hh);
-    }
-    layer_first[(size_t)L] = (int)heads.size();
-    const int n_sel = (int)heads.size();
-    if (n_sel == 0) return pce_fail(c, PCE_E_INVALID, "no alignment head selected");
-    // ---- tables: [q_row0 | q_len | a_row0 | a_len | f_len | n_rows(dtw)] and padded tokens
-    std::vector<int> tab((size_t)6 * n), tok((size_t)Mt, 0);
-    for (int i = 0; i < n; i++) {
-        tab[(size_t)i] = i * T_pad; tab[(size_t)n + i] = t_len[(size_t)i]; tab[(size_t)2 * n + i] = i * W_CTX; tab[(size_t)3 * n + i] = W_CTX;
-        tab[(size_t)4 * n + i] = f_len[(size_t)i]; tab[(size_t)5 * n + i] = t_len[(size_t)i] - sot_len - 1;
-        for (int t = 0; t < t_len[(size_t)i]; t++) {
-            const int v = tokens[token_offsets[i] + t];
-            if (v < 0 || v >= V) return pce_fail(c, PCE_E_INVALID, "token %d out of the vocabulary", v);
-            tok[(size_t)i * T_pad + t] = v;
-        }
-    }
-    w->al_rows.assign(tab.begin() + 5 * n, tab.begin() + 6 * n); w->al_cols = f_len;
-    {
-        const size_t c0 = w->d_tab.cap, c1 = w->d_tokens.cap, c2 = w->d_heads.cap;
-        PCE_HIP(c, w->d_tab.reserve(sizeof(int) * tab.size()));
-        PCE_HIP(c, w->d_tokens.reserve(sizeof(int) * tok.size()));
-        PCE_HIP(c, w->d_heads.reserve(sizeof(int) * heads.size()));
-        if (c0 != w->d_tab.cap || c1 != w->d_tokens.cap || c2 != w->d_heads.cap) w->al_tab_host.clear();     // reallocated: nothing is held
-    }
-    // the tables go up (and the host waits for the copy out of these pageable vectors: a drain of everything queued before, the encoder
-    // included) only when they differ from what the device already holds: a caller that aligns the same token lists again -- the
-    // bench's step, a retried batch -- keeps enqueuing
-    if (w->al_tab_host.empty() || tab != w->al_tab_host || tok != w->al_tok_host || heads != w->al_heads_host) {
-        PCE_HIP(c, hipMemcpyAsync(w->d_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(w->d_tokens.p, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(w->d_heads.p, heads.data(), sizeof(int) * heads.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipStreamSynchronize(c->stream));
-        w->al_tab_host = tab; w->al_tok_host = tok; w->al_heads_host = heads;
-    }
-    const int *T0 = w->d_tab.as<int>(), *TL = T0 + n, *A0 = T0 + 2 * n, *AL = T0 + 3 * n, *FL = T0 + 4 * n, *NR = T0 + 5 * n;
-    // ---- buffers
-    PCE_HIP(c, w->d_resid.reserve(sizeof(float) * (size_t)Mt * d));
-    PCE_HIP(c, w->d_ln.reserve(sizeof(op_t) * (size_t)Mt * d + 4096));
-    PCE_HIP(c, w->d_qk.reserve(sizeof(op_t) * (size_t)Mt * 2 * d + 4096));
-    PCE_HIP(c, w->d_attn.reserve(sizeof(op_t) * (size_t)Mt * d + 4096));
-    // k_attention writes the rows of real tokens only: the pad rows (T..T_pad of every clip) must not hold stale bits, a NaN
-    // there would reach the next layer's V^T and poison valid queries through 0 * NaN (seen as an intermittent NaN cost matrix)
-    PCE_HIP(c, hipMemsetAsync(w->d_attn.p, 0, sizeof(op_t) * (size_t)Mt * d + 4096, c->stream));
-    PCE_HIP(c, w->d_q.reserve(sizeof(op_t) * (size_t)Mt * d + 4096));
-    PCE_HIP(c, w->d_hidden.reserve(sizeof(op_t) * (size_t)Mt * 4 * d + 4096));
-    PCE_HIP(c, w->d_enc_bf16.reserve(sizeof(op_t) * (size_t)Ma * d + 4096));
-    const size_t dvt_elems = (size_t)n * (size_t)d * SPD + 64;
-    PCE_HIP(c, w->d_vt.reserve(sizeof(op_t) * dvt_elems));
-    if (w->d_vt.cap != w->dvt_zero_cap) {                     // (only ever holds finite values afterwards: columns past a sequence's tokens are masked, never NaN)
-        PCE_HIP(c, hipMemsetAsync(w->d_vt.p, 0, w->d_vt.cap, c->stream));
-        w->dvt_zero_cap = w->d_vt.cap;
-    }
-    PCE_HIP(c, w->d_aw.reserve(sizeof(float) * (size_t)n * n_sel * T_pad * (size_t)F_pad));
-    PCE_HIP(c, w->d_cost.reserve(sizeof(double) * (size_t)n * N_max * (size_t)F_pad));
-    PCE_HIP(c, w->d_trace.reserve((size_t)n * (size_t)(N_max + 1) * (size_t)(F_max + 1)));
-    PCE_HIP(c, w->d_pi.reserve(sizeof(int) * (size_t)n * (size_t)(N_max + F_max)));
-    PCE_HIP(c, w->d_pj.reserve(sizeof(int) * (size_t)n * (size_t)(N_max + F_max)));
-    PCE_HIP(c, w->d_pl.reserve(sizeof(int) * (size_t)n));
-    // the audio keys/values reuse the encoder's q|k and V^T buffers (the encoder is finished)
-    op_t *xk = w->qkv.as<op_t>(), *xvt = w->vt.as<op_t>();
-    // when a decoding step has already projected this encoded batch (pce_whisper_decode_step keeps the cross K / V of all
-    // layers), the 12 projections (15 of this call's 27 ms at 256 clips) are read from there
-    const bool xkv_cached = w->g_xkv_clips == n;
-    const size_t xk_cl = (size_t)Ma * d, xvt_cl = (size_t)n * (size_t)d * AT_SP;
-    const op_t *Wb = w->dw_bf16.as<op_t>();
-    const float *Wf = w->dw_f32.as<float>();
-    KernelTimer timer(c, PCE_K_WHISPER_ALIGN);
-    if (w->enc_bf16_clips != n)                                   // (the persistent-GEMM encoder path has already written it)
-        hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up(Ma * d, 256)), dim3(256), 0, c->stream, w->final_out.as<float>(),
-                               w->d_enc_bf16.as<op_t>(), Ma * d);
-    hipLaunchKernelGGL(k_embed_tokens, dim3((unsigned)div_up(Mt * d, 256)), dim3(256), 0, c->stream, w->d_tokens.as<int>(),
-                       w->d_tok_emb.as<float>(), w->d_pos_emb.as<float>(), T_pad, w->tdims.n_text_ctx, d, Mt, w->d_resid.as<float>());
-    auto attn = [&](const op_t *q, int64_t q_ld, const op_t *k, int64_t k_ld, const op_t *vt, int64_t vt_clip, int vt_sp,
-                    const int *k0, const int *kl, int causal) {
-        AttnArgs a{};
-        a.q = q; a.q_ld = q_ld; a.k = k; a.k_ld = k_ld; a.vt = vt; a.vt_clip = vt_clip; a.vt_sp = vt_sp;
-        a.q_row0 = T0; a.q_len = TL; a.k_row0 = k0; a.k_len = kl; a.out = w->d_attn.as<op_t>(); a.out_ld = d; a.causal = causal;
-        launch_attention(c, dim3((unsigned)div_up(T_pad, AT_QB), (unsigned)H, (unsigned)n), a);
-    };
-    for (int l = 0; l < L; l++) {
-        const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-        // masked self attention
-        launch_layernorm<op_t>(c, w->d_resid.as<float>(), Wf + ly.ln1_w,
-                           Wf + ly.ln1_b, Mt, d, w->d_ln.as<op_t>());
-        launch_gemm<EPI_QKV>(c, w->d_ln.as<op_t>(), d, 0, Wb + ly.qkv_w, (int)Mt, 3 * d, d, Wf + ly.qkv_b, w->d_qk.as<op_t>(), 2 * d, 0, 1,
-                             reinterpret_cast<const float *>(w->d_vt.as<op_t>()), T_pad, 2 * d, SPD);
-        attn(w->d_qk.as<op_t>(), 2 * d, w->d_qk.as<op_t>() + d, 2 * d, w->d_vt.as<op_t>(), (int64_t)d * SPD, SPD, T0, TL, 1);
-        launch_gemm<EPI_RESID_F32>(c, w->d_attn.as<op_t>(), d, 0, Wb + ly.out_w, (int)Mt, d, d, Wf + ly.out_b, w->d_resid.as<float>(), d, 0, 1);
-        // cross attention over the audio features
-        launch_layernorm<op_t>(c, w->d_resid.as<float>(), Wf + ly.lnx_w,
-                           Wf + ly.lnx_b, Mt, d, w->d_ln.as<op_t>());
-        launch_gemm<EPI_BF16>(c, w->d_ln.as<op_t>(), d, 0, Wb + ly.xq_w, (int)Mt, d, d, Wf + ly.xq_b, w->d_q.as<op_t>(), d, 0, 1);
-        if (xkv_cached) { xk = w->g_xk.as<op_t>() + xk_cl * (size_t)l; xvt = w->g_xvt.as<op_t>() + xvt_cl * (size_t)l; }
-        else if (l + 1 < L || !launch_gemm_flat<FEPI_BF16>(c, w->d_enc_bf16.as<op_t>(), Wb + ly.xkv_w, Wf + ly.xkv_b, xk, (int)Ma, d, d, d, 1, 0, PCE_K_GEMM_FLAT_XKV))
-            project_cross_kv(c, w->d_enc_bf16.as<op_t>(), (int)Ma, d, Wb + ly.xkv_w, Wf + ly.xkv_b, xk, xvt);      // (the last layer: keys only when the 256 x 256 kernel takes the shape -- its values are never read, see below)
-        // Nothing downstream reads the decoder's output here (find_alignment's token probabilities are not produced by this entry point: the
-        // alignment matrix is all that leaves), so the last layer ends at its alignment scores: its cross-attention product, output projection
-        // and MLP are not run (round 5)
-        const bool tail = l + 1 < L;
-        if (tail) attn(w->d_q.as<op_t>(), d, xk, d, xvt, (int64_t)d * AT_SP, AT_SP, A0, AL, 0);
-        const int ns_l = layer_first[(size_t)l + 1] - layer_first[(size_t)l];
-        if (ns_l > 0) {
-            AlignArgs g{};
-            g.q = w->d_q.as<op_t>(); g.q_ld = d; g.k = xk; g.k_ld = d; g.t_len = TL; g.f_len = FL;
-            g.heads = w->d_heads.as<int>() + layer_first[(size_t)l];
-            g.w = w->d_aw.as<float>(); g.sel0 = layer_first[(size_t)l]; g.n_sel_total = n_sel; g.T_pad = T_pad; g.F_pad = F_pad;
-            g.scale = 0.125f * qk_scale;
-            hipLaunchKernelGGL(k_align_scores, dim3((unsigned)div_up(T_pad, 16), (unsigned)ns_l, (unsigned)n), dim3(256), 0, c->stream, g);
-        }
-        if (!tail) break;
-        launch_gemm<EPI_RESID_F32>(c, w->d_attn.as<op_t>(), d, 0, Wb + ly.xout_w, (int)Mt, d, d, Wf + ly.xout_b, w->d_resid.as<float>(), d, 0, 1);
-        // MLP
-        launch_layernorm<op_t>(c, w->d_resid.as<float>(), Wf + ly.ln2_w,
-                           Wf + ly.ln2_b, Mt, d, w->d_ln.as<op_t>());
-        // fc1 on the persistent 256 x 256 kernel when the width allows it (12 column tiles x 36 row tiles at Whisper-small size: 91 -> ~55 us per
-        // launch, and fc2 behind it reads a warmer cache; profiles/r05/align_fc1_flat_ab.txt) -- chosen by the model's dims alone, like every kernel
-        if (!launch_gemm_flat<FEPI_GELU>(c, w->d_ln.as<op_t>(), Wb + ly.m1_w, Wf + ly.m1_b, w->d_hidden.as<op_t>(), (int)Mt, 4 * d, d, 4 * d, 1, 0, PCE_K_GEMM_FLAT_FC1))
-            launch_gemm<EPI_GELU_BF16>(c, w->d_ln.as<op_t>(), d, 0, Wb + ly.m1_w, (int)Mt, 4 * d, d, Wf + ly.m1_b, w->d_hidden.as<op_t>(), 4 * d, 0, 1);
-        launch_gemm<EPI_RESID_F32>(c, w->d_hidden.as<op_t>(), 4 * d, 0, Wb + ly.m2_w, (int)Mt, d, 4 * d, Wf + ly.m2_b, w->d_resid.as<float>(), d, 0, 1);
-    }
-    // alignment matrix: normalise over tokens, median filter over time, mean over heads, DTW
-    hipLaunchKernelGGL(k_align_colnorm, dim3((unsigned)div_up(F_pad, 256), (unsigned)n_sel, (unsigned)n), dim3(256), 0, c->stream,
-                       w->d_aw.as<float>(), TL, FL, n_sel, T_pad, F_pad);
-    if (medfilt_width == 7 && !c->generic_median)
-        hipLaunchKernelGGL((k_align_cost<7>), dim3((unsigned)div_up(F_pad, 256), (unsigned)N_max, (unsigned)n), dim3(256), 0, c->stream,
-                           w->d_aw.as<float>(), TL, FL, n_sel, T_pad, F_pad, (int)sot_len, (int)medfilt_width, N_max, w->d_cost.as<double>());
-    else
-        hipLaunchKernelGGL((k_align_cost<0>), dim3((unsigned)div_up(F_pad, 256), (unsigned)N_max, (unsigned)n), dim3(256), 0, c->stream,
-                           w->d_aw.as<float>(), TL, FL, n_sel, T_pad, F_pad, (int)sot_len, (int)medfilt_width, N_max, w->d_cost.as<double>());
-    int rc = pce_dtw_launch(c, w->d_cost.as<double>(), (int64_t)N_max * F_pad, F_pad, NR, FL, N_max, F_max, n, w->d_trace.as<unsigned char>(),
-                            w->d_pi.as<int>(), w->d_pj.as<int>(), w->d_pl.as<int>());
-    if (rc) return rc;
-    PCE_HIP(c, hipGetLastError());
-    w->al_n = n; w->al_Nmax = N_max; w->al_Fpad = F_pad; w->al_Mmax = F_max;
-    return PCE_OK;
-}
-
-int pce_whisper_align_fetch(pce_ctx *c, int32_t clip, int32_t *text_idx, int32_t *time_idx, int32_t *path_len, double *cost)
-{
-    if (!c || !path_len) return PCE_E_INVALID;
-    WhisperState *w = ws_of(c);
-    if (w->al_n < 0) return pce_fail(c, PCE_E_STATE, "pce_whisper_align_fetch before pce_whisper_align_run");
-    if (clip < 0 || clip >= w->al_n) return pce_fail(c, PCE_E_INVALID, "clip out of range");
-    PCE_HIP(c, hipSetDevice(c->device));
-    const size_t stride = (size_t)(w->al_Nmax + w->al_Mmax);
-    int n = 0;
-    PCE_HIP(c, hipMemcpyAsync(&n, w->d_pl.as<int>() + clip, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    *path_len = n;
-    if (text_idx) PCE_HIP(c, hipMemcpyAsync(text_idx, w->d_pi.as<int>() + stride * (size_t)clip, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (time_idx) PCE_HIP(c, hipMemcpyAsync(time_idx, w->d_pj.as<int>() + stride * (size_t)clip, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (cost) {
-        const int N = w->al_rows[(size_t)clip], F = w->al_cols[(size_t)clip];
-        PCE_HIP(c, hipMemcpy2DAsync(cost, sizeof(double) * (size_t)F, w->d_cost.as<double>() + (size_t)clip * w->al_Nmax * (size_t)w->al_Fpad,
-                                    sizeof(double) * (size_t)w->al_Fpad, sizeof(double) * (size_t)F, (size_t)N, hipMemcpyDeviceToHost, c->stream));
-    }
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    pce_profile_collect(c);
-    return PCE_OK;
-}
-
-int pce_whisper_align_paths_enqueue(pce_ctx *c, int32_t slot, int32_t *n_clips, int32_t *path_stride)
-{
-    if (!c || slot < 0 || slot > 1) return PCE_E_INVALID;
-    WhisperState *w = ws_of(c);
-    if (w->al_n < 0) return pce_fail(c, PCE_E_STATE, "pce_whisper_align_paths_enqueue before pce_whisper_align_run");
-    PCE_HIP(c, hipSetDevice(c->device));
-    WhisperState::PathSlot &ps = w->al_slot[slot];
-    // a slot whose previous fetch nobody has waited for: its copies may still be in flight into the pinned buffer this call would overwrite (or free and
-    // reallocate, if the new batch is larger) -- the caller's protocol error (ADVICE r05), reported instead of raced
-    if (ps.armed) return pce_fail(c, PCE_E_STATE, "pce_whisper_align_paths_enqueue: slot %d still holds an enqueued fetch (pce_whisper_align_paths_wait first)", slot);
-    const size_t n = (size_t)w->al_n, stride = (size_t)(w->al_Nmax + w->al_Mmax), ints = n * (2 * stride + 1);
-    if (sizeof(int) * ints > ps.cap) {
-        if (ps.host) { PCE_HIP(c, hipHostFree(ps.host)); ps.host = nullptr; ps.cap = 0; }
-        PCE_HIP(c, hipHostMalloc(&ps.host, sizeof(int) * ints + (sizeof(int) * ints >> 2), hipHostMallocDefault));
-        ps.cap = sizeof(int) * ints + (sizeof(int) * ints >> 2);
-    }
-    if (!ps.ev) PCE_HIP(c, hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
-    int *h = static_cast<int *>(ps.host);
-    // behind the DTW on the context's stream: lengths, then the two index arrays as they lie ([clip][stride], a few MB at most)
-    PCE_HIP(c, hipMemcpyAsync(h, w->d_pl.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(h + n, w->d_pi.p, sizeof(int) * n * stride, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(h + n + n * stride, w->d_pj.p, sizeof(int) * n * stride, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipEventRecord(ps.ev, c->stream));
-    ps.armed = true; ps.n = (int)n; ps.stride = (int)stride;
-    if (n_clips) *n_clips = (int32_t)n;
-    if (path_stride) *path_stride = (int32_t)stride;
-    return PCE_OK;
-}
-
-int pce_whisper_align_paths_wait(pce_ctx *c, int32_t slot, int32_t *path_len, int32_t *text_idx, int32_t *time_idx)
-{
-    if (!c || slot < 0 || slot > 1 || !path_len) return PCE_E_INVALID;
-    WhisperState *w = ws_of(c);
-    WhisperState::PathSlot &ps = w->al_slot[slot];
-    if (!ps.armed) return pce_fail(c, PCE_E_STATE, "pce_whisper_align_paths_wait: slot %d has no enqueued fetch", slot);
-    PCE_HIP(c, hipSetDevice(c->device));
-    PCE_HIP(c, hipEventSynchronize(ps.ev));
-    ps.armed = false;
-    const int *h = static_cast<const int *>(ps.host);
-    const size_t n = (size_t)ps.n, stride = (size_t)ps.stride;
-    memcpy(path_len, h, sizeof(int) * n);
-    for (size_t i = 0; i < n; i++) {
-        const size_t len = (size_t)(h[i] < 0 ? 0 : h[i]);
-        if (len > stride) return pce_fail(c, PCE_E_STATE, "clip %zu: a DTW path of %zu steps in a buffer of %zu", i, len, stride);
-        if (text_idx) memcpy(text_idx + i * stride, h + n + i * stride, sizeof(int) * len);
-        if (time_idx) memcpy(time_idx + i * stride, h + n + n * stride + i * stride, sizeof(int) * len);
-    }
-    return PCE_OK;
-}
-
-int pce_whisper_align_shape(pce_ctx *c, int32_t clip, int32_t *n_rows, int32_t *n_cols)
-{
-    if (!c) return PCE_E_INVALID;
-    WhisperState *w = ws_of(c);
-    if (w->al_n < 0) return pce_fail(c, PCE_E_STATE, "pce_whisper_align_shape before pce_whisper_align_run");
-    if (clip < 0 || clip >= w->al_n) return pce_fail(c, PCE_E_INVALID, "clip out of range");
-    if (n_rows) *n_rows = w->al_rows[(size_t)clip];
-    if (n_cols) *n_cols = w->al_cols[(size_t)clip];
-    return PCE_OK;
-}
-
-} // extern "C"
-
-// ---------------------------------------------------------------------------
-// Free-running decoding, one step: the text decoder over the sequences so far (cross K / V of every layer computed once
-// per encoded batch and kept), logits of the last position through the tied output projection, openai-whisper's logit
-// filters and greedy choice.  The loop over steps, the prompt and the stopping rule are host logic
-// (Aligners/decoding.py); every step re-runs the decoder over the whole prefix (a per-step K / V cache for the
-// self-attention is the next refinement, DESIGN.md section 8).
-// ---------------------------------------------------------------------------
-extern "C" int pce_whisper_decode_step(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, int32_t sample_begin,
-                                       const pce_whisper_decode_rules *rules, const uint8_t *vocab_mask, int32_t *next_tokens,
-                                       float *next_logprobs)
-{
-    pce_whisper_decode_opts o{};
-    o.sample_begin = nullptr; o.sample_begin_all = sample_begin; o.temperature = 0.f; o.probe_token = -1;
-    return pce_whisper_decode_step_ex(c, tokens, token_offsets, rules, vocab_mask, &o, next_tokens, next_logprobs, nullptr);
-}
-
-// launches of ONE incremental step (one new position per sequence) from the tables ct[8 n] (see k_step_advance) -- host-uploaded by
-// pce_whisper_decode_step_ex, device-maintained inside pce_whisper_decode_loop -- down to the final LayerNorm of the new position
-static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, const int *CT, const int *ended)
-{
-    const int d = w->tdims.n_state, H = w->tdims.n_head, L = w->tdims.n_layer, SPD = 512, T_cap = w->tdims.n_text_ctx;
-    const int64_t Ma = (int64_t)n * W_CTX;
-    const size_t xk_l = (size_t)Ma * d, xvt_l = (size_t)n * (size_t)d * AT_SP, sk_l = (size_t)n * T_cap * d, svt_l = (size_t)n * (size_t)d * SPD;
-    const op_t *Wb = w->dw_bf16.as<op_t>();
-    const float *Wf = w->dw_f32.as<float>();
-    const int *K0 = CT + 3 * n, *KL = CT + 4 * n, *X0 = CT + 5 * n, *XL = CT + 6 * n, *POS = CT + 7 * n;
-    struct FewRows { pce_ctx *c; explicit FewRows(pce_ctx *cc) : c(cc) { c->gemm_few_rows = true; } ~FewRows() { c->gemm_few_rows = false; } } few_rows(c);
-    hipLaunchKernelGGL(k_embed_one, dim3((unsigned)div_up((int64_t)n * d, 256)), dim3(256), 0, c->stream, CT, w->d_tok_emb.as<float>(),
-                       w->d_pos_emb.as<float>(), POS, d, n, w->g_c_resid.as<float>());
-    // the self-attention kernel also appends the new position to its cache
-    auto cattn = [&](const op_t *q, int64_t q_ld, const op_t *k, int64_t k_ld, const op_t *vt, int64_t vt_clip, int vt_sp, const int *k0, const int *kl,
-                     const op_t *app_qkv = nullptr) {
-        // the streaming single-query kernels (the MFMA attention kernel would spend a 32-query tile on the one live query)
-        Attn1Args a{};
-        a.q = q; a.q_ld = q_ld; a.k = k; a.k_ld = k_ld; a.vt = vt; a.vt_clip = vt_clip; a.vt_sp = vt_sp; a.k_row0 = k0; a.k_len = kl; a.skip = ended;
-        a.out = w->g_c_attn.as<op_t>(); a.out_ld = d;
-        if (app_qkv) { a.app_k = app_qkv + d; a.app_v = app_qkv + 2 * d; a.app_ld = 3 * d; a.app_pos = POS; }
-        launch_cross_attn1(c, n, H, a);
-    };
-    auto cln = [&](size_t w_off, size_t b_off) {
-        launch_layernorm<op_t>(c, w->g_c_resid.as<float>(), Wf + w_off, Wf + b_off,
-                           (int64_t)n, d, w->g_c_ln.as<op_t>());
-    };
-    // cross-attention from the encoder output (pce_xattn.inc): E once per layer instead of K and V^T
-    const bool absorb = c->xattn_absorb && xa_has_form(d, H) && w->g_qp.p && w->g_wkT.p;
-    static const int env_wpc = getenv("PCE_XATTN_WPC") ? atoi(getenv("PCE_XATTN_WPC")) : 0;
-    XaArgs xa{};
-    xa.E = w->d_enc_bf16.as<op_t>(); xa.e_clip = (int64_t)W_CTX * d; xa.e_ld = d; xa.k_len = XL; xa.skip = ended;
-    xa.u_part = w->g_upart.as<float>(); xa.ml_part = w->g_mlpart.as<float>(); xa.heads = H; xa.nsplit = xa_split(n, env_wpc); xa.rows = xa_rows(H);
-    auto xattn = [&](int l) {
-        const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-        XaLayer y{};
-        y.resid = w->g_c_resid.as<float>(); y.ln_w = Wf + ly.lnx_w; y.ln_b = Wf + ly.lnx_b; y.wq = Wb + ly.xq_w; y.bq = Wf + ly.xq_b;
-        y.wkT = w->g_wkT.as<op_t>() + (size_t)d * d * (size_t)l; y.wv = Wb + ly.xkv_w + (size_t)d * d; y.bv = Wf + ly.xkv_b + d;
-        y.qp_hi = w->g_qp.as<op_t>(); y.qp_lo = y.qp_hi + (size_t)n * xa.rows * d; y.out = w->g_c_attn.as<op_t>(); y.out_ld = d;
-        KernelTimer kt(c, PCE_K_CROSS_ATTN1);
-        xattn_launch(c, d, n, xa, y);
-    };
-    for (int l = 0; l < L; l++) {
-        const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-        // (the LayerNorm as a prologue of the projection that consumes it -- every workgroup normalising its own 64 rows -- was measured
-        //  and dropped: four dependent L2 round trips per wave, 17 us per launch against 11.8 + 5.5 for the two launches)
-        cln(ly.ln1_w, ly.ln1_b);
-        launch_gemm<EPI_BF16>(c, w->g_c_ln.as<op_t>(), d, 0, Wb + ly.qkv_w, n, 3 * d, d, Wf + ly.qkv_b, w->g_c_qkv.as<op_t>(), 3 * d, 0, 1);
-        if (c->self_rows && w->g_sv.p) {
-            // row-major K / V caches: the append is two coalesced row stores (the V^T image is not touched by incremental steps: only prefix runs,
-            // which rewrite every position they attend to, read it)
-            SelfAttn1Args sa{};
-            sa.qkv = w->g_c_qkv.as<op_t>(); sa.qkv_ld = 3 * d; sa.ck = w->g_sk.as<op_t>() + sk_l * (size_t)l; sa.cv = w->g_sv.as<op_t>() + sk_l * (size_t)l;
-            sa.c_clip = (int64_t)T_cap * d; sa.d = d; sa.pos = POS; sa.skip = ended; sa.out = w->g_c_attn.as<op_t>(); sa.out_ld = d;
-            launch_self_attn1(c, n, H, sa);
-        } else
-        cattn(w->g_c_qkv.as<op_t>(), 3 * d, w->g_sk.as<op_t>() + sk_l * (size_t)l, d, w->g_svt.as<op_t>() + svt_l * (size_t)l, (int64_t)d * SPD, SPD, K0, KL,
-              w->g_c_qkv.as<op_t>());
-        launch_gemm<EPI_RESID_F32>(c, w->g_c_attn.as<op_t>(), d, 0, Wb + ly.out_w, n, d, d, Wf + ly.out_b, w->g_c_resid.as<float>(), d, 0, 1);
-        if (!absorb) cln(ly.lnx_w, ly.lnx_b);                       // (the encoder-output form normalises inside its first launch)
-        if (!absorb) launch_gemm<EPI_BF16>(c, w->g_c_ln.as<op_t>(), d, 0, Wb + ly.xq_w, n, d, d, Wf + ly.xq_b, w->g_c_q.as<op_t>(), d, 0, 1);
-        if (absorb) xattn(l);          // (its first launch is the query projection itself)
-        else cattn(w->g_c_q.as<op_t>(), d, w->g_xk.as<op_t>() + xk_l * (size_t)l, d, w->g_xvt.as<op_t>() + xvt_l * (size_t)l, (int64_t)d * AT_SP, AT_SP, X0, XL);
-        launch_gemm<EPI_RESID_F32>(c, w->g_c_attn.as<op_t>(), d, 0, Wb + ly.xout_w, n, d, d, Wf + ly.xout_b, w->g_c_resid.as<float>(), d, 0, 1);
-        cln(ly.ln2_w, ly.ln2_b);
-        launch_gemm<EPI_GELU_BF16>(c, w->g_c_ln.as<op_t>(), d, 0, Wb + ly.m1_w, n, 4 * d, d, Wf + ly.m1_b, w->g_c_hidden.as<op_t>(), 4 * d, 0, 1);
-        launch_gemm<EPI_RESID_F32>(c, w->g_c_hidden.as<op_t>(), 4 * d, 0, Wb + ly.m2_w, n, d, 4 * d, Wf + ly.m2_b, w->g_c_resid.as<float>(), d, 0, 1);
-    }
-    launch_layernorm<op_t>(c, w->g_c_resid.as<float>(), Wf + w->dln_w, Wf + w->dln_b,
-                       (int64_t)n, d, w->g_lastln.as<op_t>());
-}
-static int decode_incremental_reserve(pce_ctx *c, WhisperState *w, int n)
-{
-    const int d = w->tdims.n_state;
-    PCE_HIP(c, w->g_c_tab.reserve(sizeof(int) * 8 * (size_t)n));
-    PCE_HIP(c, w->g_c_resid.reserve(sizeof(float) * (size_t)n * d));
-    PCE_HIP(c, w->g_c_ln.reserve(sizeof(op_t) * (size_t)(n + 128) * d + 4096));
-    PCE_HIP(c, w->g_c_qkv.reserve(sizeof(op_t) * (size_t)(n + 128) * 3 * d + 4096));
-    {
-        const size_t before = w->g_c_attn.cap;
-        PCE_HIP(c, w->g_c_attn.reserve(sizeof(op_t) * (size_t)(n + 128) * d + 4096));
-        if (w->g_c_attn.cap != before) PCE_HIP(c, hipMemsetAsync(w->g_c_attn.p, 0, w->g_c_attn.cap, c->stream));   // rows of ended sequences are skipped: never uninitialised bits
-    }
-    PCE_HIP(c, w->g_c_q.reserve(sizeof(op_t) * (size_t)(n + 128) * d + 4096));
-    PCE_HIP(c, w->g_c_hidden.reserve(sizeof(op_t) * (size_t)(n + 128) * 4 * d + 4096));
-    if (c->xattn_absorb) {
-        const size_t before = w->g_qp.cap, R = (size_t)xa_rows(w->tdims.n_head);   // R rows of heads per clip (pce_xattn.inc)
-        PCE_HIP(c, w->g_qp.reserve(sizeof(op_t) * 2 * (size_t)n * R * d + 256));
-        if (w->g_qp.cap != before) PCE_HIP(c, hipMemsetAsync(w->g_qp.p, 0, w->g_qp.cap, c->stream));               // (rows >= heads feed MFMA rows nobody reads: finite all the same)
-        PCE_HIP(c, w->g_upart.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
-        PCE_HIP(c, w->g_mlpart.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * 2 + 256));
-    }
-    return PCE_OK;
-}
-
-// one decoding step; results stay on the device in g_next (next token | log-probability | probe probability, n each).  `resident`: the
-// caller (pce_whisper_decode_loop) keeps the tables of an incremental step on the device: `tokens` is then only consulted for step 0.
-static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
-                              const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, bool want_probe);
-
-// the ids temperature sampling keys its noise by, one per clip of the encoded batch; they last until the next pce_whisper_encode_run
-extern "C" int pce_whisper_sample_keys(pce_ctx *c, const int32_t *keys, int32_t n)
-{
-    if (!c || n < 0 || (n > 0 && !keys)) return PCE_E_INVALID;
-    WhisperState *w = ws_of(c);
-    if (n == 0) { w->g_keys_n = 0; return PCE_OK; }
-    if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "pce_whisper_sample_keys before pce_whisper_encode_run");
-    if (n != w->n_clips_enc) return pce_fail(c, PCE_E_INVALID, "pce_whisper_sample_keys: %d keys for %d encoded clips", n, w->n_clips_enc);
-    PCE_HIP(c, hipSetDevice(c->device));
-    PCE_HIP(c, w->g_keys.reserve(sizeof(int) * (size_t)n));
-    // (pageable source: the copy has left `keys` when the call returns; it is ordered before the next decode on the same stream)
-    PCE_HIP(c, hipMemcpyAsync(w->g_keys.p, keys, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    w->g_keys_n = n;
-    return PCE_OK;
-}
-
-extern "C" int pce_whisper_decode_step_ex(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
-                                          const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, int32_t *next_tokens,
-                                          float *next_logprobs, float *probe_prob)
-{
-    if (!c || !tokens || !token_offsets || !rules || !vocab_mask || !next_tokens || !opts) return PCE_E_INVALID;
-    const int rc = decode_step_device(c, tokens, token_offsets, rules, vocab_mask, opts, probe_prob != nullptr);
-    if (rc) return rc;
-    WhisperState *w = ws_of(c);
-    const int n = w->n_clips_enc;
-    if (n == 0) return PCE_OK;
-    PCE_HIP(c, hipMemcpyAsync(next_tokens, w->g_next.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (next_logprobs) PCE_HIP(c, hipMemcpyAsync(next_logprobs, w->g_next.as<int>() + n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (probe_prob && opts->probe_token >= 0)
-        PCE_HIP(c, hipMemcpyAsync(probe_prob, w->g_next.as<int>() + 2 * n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    return PCE_OK;
-}
-
-static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
-                              const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, bool want_probe)
-{
-    float probe_dummy = 0.f;
-    float *probe_prob = want_probe ? &probe_dummy : nullptr;      // (only its non-nullness is consulted below)
-    const int32_t sample_begin = opts->sample_begin_all;
-    WhisperState *w = ws_of(c);
-    if (!w->dec_loaded) return pce_fail(c, PCE_E_STATE, "pce_whisper_decode_step before pce_whisper_decoder_load");
-    if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "run pce_whisper_encode_run first");
-    if (w->tdims.n_state != w->dims.n_state) return pce_fail(c, PCE_E_INVALID, "decoder and encoder widths differ");
-    PCE_HIP(c, hipSetDevice(c->device));
-    const int n = w->n_clips_enc, d = w->tdims.n_state, H = w->tdims.n_head, L = w->tdims.n_layer, V = w->tdims.n_vocab, SPD = 512;
-    if (rules->eot < 0 || rules->eot >= V || rules->timestamp_begin <= rules->eot || rules->timestamp_begin > V || (!opts->sample_begin && sample_begin < 1))
-        return pce_fail(c, PCE_E_INVALID, "decoding rules: need 0 <= eot < timestamp_begin <= n_vocab, sample_begin >= 1");
-    if (!(opts->temperature >= 0.f) || opts->probe_token >= V) return pce_fail(c, PCE_E_INVALID, "decoding options: temperature >= 0, probe_token < n_vocab");
-    if (n == 0) return PCE_OK;
-    int T_max = 0;
-    std::vector<int> t_len((size_t)n);
-    for (int i = 0; i < n; i++) {
-        const int T = token_offsets[i + 1] - token_offsets[i];
-        const int sb = opts->sample_begin ? opts->sample_begin[i] : sample_begin;
-        if (sb < 1 || T < sb || T > w->tdims.n_text_ctx) return pce_fail(c, PCE_E_INVALID, "clip %d: %d tokens (need %d..%d)", i, T, sb, w->tdims.n_text_ctx);
-        t_len[(size_t)i] = T; T_max = std::max(T_max, T);
-    }
-    // rows per sequence: the longest prefix rounded up to 16 (a V^T store writes 4 positions, an MFMA row block is 16 rows): a step over
-    // the 3-token start sequence used to run 64 rows per clip, 21 times the live ones (10.8 ms per 256 clips against 3.4 for an
-    // incremental step)
-    const int T_pad = (int)div_up(T_max, 16) * 16;
-    const int64_t Mt = (int64_t)n * T_pad, Ma = (int64_t)n * W_CTX;
-    const int64_t Vp = div_up(V, 128) * 128;
-    std::vector<int> tab((size_t)5 * n), tok((size_t)Mt, 0);
-    for (int i = 0; i < n; i++) {
-        tab[(size_t)i] = i * T_pad; tab[(size_t)n + i] = t_len[(size_t)i]; tab[(size_t)2 * n + i] = i * W_CTX; tab[(size_t)3 * n + i] = W_CTX;
-        tab[(size_t)4 * n + i] = opts->sample_begin ? opts->sample_begin[i] : sample_begin;
-        for (int t = 0; t < t_len[(size_t)i]; t++) {
-            const int v = tokens[token_offsets[i] + t];
-            if (v < 0 || v >= V) return pce_fail(c, PCE_E_INVALID, "token %d out of the vocabulary", v);
-            tok[(size_t)i * T_pad + t] = v;
-        }
-    }
-    PCE_HIP(c, w->d_tab.reserve(sizeof(int) * tab.size()));
-    PCE_HIP(c, w->d_tokens.reserve(sizeof(int) * tok.size()));
-    PCE_HIP(c, w->d_resid.reserve(sizeof(float) * (size_t)Mt * d));
-    PCE_HIP(c, w->d_ln.reserve(sizeof(op_t) * (size_t)Mt * d + 4096));
-    PCE_HIP(c, w->d_qk.reserve(sizeof(op_t) * (size_t)Mt * 2 * d + 4096));
-    PCE_HIP(c, w->d_attn.reserve(sizeof(op_t) * (size_t)Mt * d + 4096));
-    PCE_HIP(c, w->d_q.reserve(sizeof(op_t) * (size_t)Mt * d + 4096));
-    PCE_HIP(c, w->d_hidden.reserve(sizeof(op_t) * (size_t)Mt * 4 * d + 4096));
-    PCE_HIP(c, w->g_last.reserve(sizeof(float) * (size_t)n * d));
-    PCE_HIP(c, w->g_lastln.reserve(sizeof(op_t) * (size_t)(n + 128) * d + 4096));
-    PCE_HIP(c, w->g_logits.reserve(sizeof(float) * (size_t)n * (size_t)Vp));
-    PCE_HIP(c, w->g_mask.reserve((size_t)V + 64));
-    PCE_HIP(c, w->g_next.reserve((sizeof(int) + 2 * sizeof(float)) * (size_t)n));
-    w->al_tab_host.clear();                                     // (d_tab / d_tokens are shared with pce_whisper_align_run: it uploads again)
-    PCE_HIP(c, hipMemcpyAsync(w->d_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->d_tokens.p, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->g_mask.p, vocab_mask, (size_t)V, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    const int *T0 = w->d_tab.as<int>(), *TL = T0 + n, *A0 = T0 + 2 * n, *AL = T0 + 3 * n;
-    const op_t *Wb = w->dw_bf16.as<op_t>();
-    const float *Wf = w->dw_f32.as<float>();
-    KernelTimer timer(c, PCE_K_WHISPER_DECODE);
-    // ---- cross K / V of every layer, once per encoded batch
-    const size_t xk_l = (size_t)Ma * d, xvt_l = (size_t)n * (size_t)d * AT_SP;
-    if (w->g_xkv_clips != n) {
-        PCE_HIP(c, w->g_xk.reserve(sizeof(op_t) * xk_l * (size_t)L + 4096));
-        PCE_HIP(c, w->g_xvt.reserve(sizeof(op_t) * xvt_l * (size_t)L + 4096));
-        PCE_HIP(c, w->d_enc_bf16.reserve(sizeof(op_t) * (size_t)Ma * d + 4096));
-        PCE_HIP(c, hipMemsetAsync(w->g_xvt.p, 0, sizeof(op_t) * xvt_l * (size_t)L, c->stream));      // V^T columns 1500..AT_SP are read as zeros
-        if (w->enc_bf16_clips != n)
-            hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up(Ma * d, 256)), dim3(256), 0, c->stream, w->final_out.as<float>(),
-                               w->d_enc_bf16.as<op_t>(), Ma * d);
-        for (int l = 0; l < L; l++) {
-            const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-            project_cross_kv(c, w->d_enc_bf16.as<op_t>(), (int)Ma, d, Wb + ly.xkv_w, Wf + ly.xkv_b, w->g_xk.as<op_t>() + xk_l * (size_t)l,
-                             w->g_xvt.as<op_t>() + xvt_l * (size_t)l);
-        }
-        w->g_xkv_clips = n;
-    }
-    // ---- self-attention K / V cache [layer][clip][T_cap] (rows) / [layer][clip][d][512] (transposed)
-    const int T_cap = w->tdims.n_text_ctx;
-    const size_t sk_l = (size_t)n * T_cap * d, svt_l = (size_t)n * (size_t)d * SPD;
-    if (w->g_cache_n != n || !w->g_sk.p) {
-        PCE_HIP(c, w->g_sk.reserve(sizeof(op_t) * sk_l * (size_t)L + 4096));
-        PCE_HIP(c, w->g_svt.reserve(sizeof(op_t) * svt_l * (size_t)L + 4096));
-        PCE_HIP(c, w->g_sv.reserve(sizeof(op_t) * sk_l * (size_t)L + 4096));
-        PCE_HIP(c, hipMemsetAsync(w->g_sv.p, 0, sizeof(op_t) * sk_l * (size_t)L, c->stream));
-        PCE_HIP(c, hipMemsetAsync(w->g_sk.p, 0, sizeof(op_t) * sk_l * (size_t)L, c->stream));
-        PCE_HIP(c, hipMemsetAsync(w->g_svt.p, 0, sizeof(op_t) * svt_l * (size_t)L, c->stream));
-        w->g_cache_n = n; w->g_cache_len = -1; w->g_cache_tok.assign((size_t)n * T_cap, 0); w->g_cache_lens.assign((size_t)n, -1);
-    }
-    // incremental: every sequence extends what the cache holds for it by exactly one token (lengths may differ between sequences)
-    bool incremental = w->g_cache_len >= 0 && !(opts->flags & 1);
-    for (int i = 0; incremental && i < n; i++) {
-        const int Li = t_len[(size_t)i];
-        incremental = Li >= 2 && w->g_cache_lens[(size_t)i] == Li - 1 &&
-                      memcmp(&w->g_cache_tok[(size_t)i * T_cap], &tokens[token_offsets[i]], sizeof(int) * (size_t)(Li - 1)) == 0;
-    }
-    const op_t *last_ln = nullptr;                                // [n][d] op_t: the final LayerNorm of the last position
-    if (incremental) {
-        // ---- one new position per sequence: every GEMM has M = clips rows, the attention one query per (clip, head)
-        std::vector<int> ct((size_t)8 * n);                     // new token | q_row0 | q_len | k_row0 | k_len | a_row0 | a_len | position
-        for (int i = 0; i < n; i++) {
-            const int pos_i = t_len[(size_t)i] - 1;
-            ct[(size_t)i] = tokens[token_offsets[i] + pos_i]; ct[(size_t)n + i] = i; ct[(size_t)2 * n + i] = 1; ct[(size_t)3 * n + i] = i * T_cap;
-            ct[(size_t)4 * n + i] = pos_i + 1; ct[(size_t)5 * n + i] = i * W_CTX; ct[(size_t)6 * n + i] = W_CTX; ct[(size_t)7 * n + i] = pos_i;
-        }
-        { const int rc = decode_incremental_reserve(c, w, n); if (rc) return rc; }
-        PCE_HIP(c, hipMemcpyAsync(w->g_c_tab.p, ct.data(), sizeof(int) * ct.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipStreamSynchronize(c->stream));
-        decode_incremental_launches(c, w, n, w->g_c_tab.as<int>(), nullptr);
-        last_ln = w->g_lastln.as<op_t>();
-    } else {
-    PCE_HIP(c, hipMemsetAsync(w->d_attn.p, 0, sizeof(op_t) * (size_t)Mt * d + 4096, c->stream));      // pad rows: no stale bits (see pce_whisper_align_run)
-    hipLaunchKernelGGL(k_embed_tokens, dim3((unsigned)div_up(Mt * d, 256)), dim3(256), 0, c->stream, w->d_tokens.as<int>(),
-                       w->d_tok_emb.as<float>(), w->d_pos_emb.as<float>(), T_pad, w->tdims.n_text_ctx, d, Mt, w->d_resid.as<float>());
-    auto attn = [&](const op_t *q, int64_t q_ld, const op_t *k, int64_t k_ld, const op_t *vt, int64_t vt_clip, int vt_sp,
-                    const int *k0, const int *kl, int causal) {
-        AttnArgs a{};
-        a.q = q; a.q_ld = q_ld; a.k = k; a.k_ld = k_ld; a.vt = vt; a.vt_clip = vt_clip; a.vt_sp = vt_sp;
-        a.q_row0 = T0; a.q_len = TL; a.k_row0 = k0; a.k_len = kl; a.out = w->d_attn.as<op_t>(); a.out_ld = d; a.causal = causal;
-        launch_attention(c, dim3((unsigned)div_up(T_pad, AT_QB), (unsigned)H, (unsigned)n), a);
-    };
-    auto ln = [&](size_t w_off, size_t b_off) {
-        launch_layernorm<op_t>(c, w->d_resid.as<float>(), Wf + w_off, Wf + b_off,
-                           Mt, d, w->d_ln.as<op_t>());
-    };
-    for (int l = 0; l < L; l++) {
-        const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-        ln(ly.ln1_w, ly.ln1_b);
-        op_t *svt = w->g_svt.as<op_t>() + svt_l * (size_t)l;       // the prefix run fills the cache: V^T straight from the epilogue, K rows copied
-        launch_gemm<EPI_QKV>(c, w->d_ln.as<op_t>(), d, 0, Wb + ly.qkv_w, (int)Mt, 3 * d, d, Wf + ly.qkv_b, w->d_qk.as<op_t>(), 2 * d, 0, 1,
-                             reinterpret_cast<const float *>(svt), T_pad, 2 * d, SPD);
-        hipLaunchKernelGGL(k_cache_k, dim3((unsigned)div_up(Mt * d, 256)), dim3(256), 0, c->stream, w->d_qk.as<op_t>(), T_pad, TL, d, T_cap, n,
-                           w->g_sk.as<op_t>() + sk_l * (size_t)l);
-        hipLaunchKernelGGL(k_cache_v_rows, dim3((unsigned)(d / 32), (unsigned)div_up(T_pad, 32), (unsigned)n), dim3(256), 0, c->stream, svt, TL, d, T_cap, SPD, n,
-                           w->g_sv.as<op_t>() + sk_l * (size_t)l);
-        attn(w->d_qk.as<op_t>(), 2 * d, w->d_qk.as<op_t>() + d, 2 * d, svt, (int64_t)d * SPD, SPD, T0, TL, 1);
-        launch_gemm<EPI_RESID_F32>(c, w->d_attn.as<op_t>(), d, 0, Wb + ly.out_w, (int)Mt, d, d, Wf + ly.out_b, w->d_resid.as<float>(), d, 0, 1);
-        ln(ly.lnx_w, ly.lnx_b);
-        launch_gemm<EPI_BF16>(c, w->d_ln.as<op_t>(), d, 0, Wb + ly.xq_w, (int)Mt, d, d, Wf + ly.xq_b, w->d_q.as<op_t>(), d, 0, 1);
-        attn(w->d_q.as<op_t>(), d, w->g_xk.as<op_t>() + xk_l * (size_t)l, d, w->g_xvt.as<op_t>() + xvt_l * (size_t)l, (int64_t)d * AT_SP, AT_SP, A0, AL, 0);
-        launch_gemm<EPI_RESID_F32>(c, w->d_attn.as<op_t>(), d, 0, Wb + ly.xout_w, (int)Mt, d, d, Wf + ly.xout_b, w->d_resid.as<float>(), d, 0, 1);
-        ln(ly.ln2_w, ly.ln2_b);
-        launch_gemm<EPI_GELU_BF16>(c, w->d_ln.as<op_t>(), d, 0, Wb + ly.m1_w, (int)Mt, 4 * d, d, Wf + ly.m1_b, w->d_hidden.as<op_t>(), 4 * d, 0, 1);
-        launch_gemm<EPI_RESID_F32>(c, w->d_hidden.as<op_t>(), 4 * d, 0, Wb + ly.m2_w, (int)Mt, d, 4 * d, Wf + ly.m2_b, w->d_resid.as<float>(), d, 0, 1);
-    }
-    // ---- last position -> ln -> logits = hidden . E^T (fp32, zero-initialised accumulator)
-    hipLaunchKernelGGL(k_gather_last, dim3((unsigned)div_up((int64_t)n * d, 256)), dim3(256), 0, c->stream, w->d_resid.as<float>(), TL, T_pad, d, n,
-                       w->g_last.as<float>());
-    launch_layernorm<op_t>(c, w->g_last.as<float>(), Wf + w->dln_w, Wf + w->dln_b,
-                       (int64_t)n, d, w->g_lastln.as<op_t>());
-    last_ln = w->g_lastln.as<op_t>();
-    }
-    // the cache now holds every position of these prefixes
-    for (int i = 0; i < n; i++) {
-        memcpy(&w->g_cache_tok[(size_t)i * T_cap], &tokens[token_offsets[i]], sizeof(int) * (size_t)t_len[(size_t)i]);
-        w->g_cache_lens[(size_t)i] = t_len[(size_t)i];
-    }
-    w->g_cache_len = 0;
-    launch_gemm<EPI_F32>(c, last_ln, d, 0, w->g_emb_bf16.as<op_t>(), n, (int)Vp, d, nullptr, w->g_logits.as<float>(), Vp, 0, 1);
-    DecRules R{rules->eot, rules->timestamp_begin, V, (int)Vp, sample_begin, rules->max_initial_timestamp_index, opts->temperature, opts->seed_lo,
-               opts->seed_hi, probe_prob ? opts->probe_token : -1};
-    hipLaunchKernelGGL(k_decode_rules, dim3((unsigned)n), dim3(DR_T), 0, c->stream, w->g_logits.as<float>(), w->d_tokens.as<int>(), TL, T_pad,
-                       w->g_mask.as<unsigned char>(), R, T0 + 4 * n, w->g_next.as<int>(), reinterpret_cast<float *>(w->g_next.as<int>() + n),
-                       reinterpret_cast<float *>(w->g_next.as<int>() + 2 * n), w->g_keys_n == n ? w->g_keys.as<int>() : nullptr);
-    PCE_HIP(c, hipGetLastError());
-    return PCE_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Free-running decoding with the loop on the device (round 3).  pce_whisper_decode_step_ex round-trips every step through the
-// host (tokens up, next token down, a synchronisation each way); here the prompts go up once, every later step reads what it
-// needs -- the token it embeds, its position, the self-attention key count, which sequences have ended -- from tables the previous
-// step's k_step_advance left on the device, and the host only looks at an "ended" counter every `check_every` steps.
-// Same kernels, same filters, same counter-based sampling keys (seed, clip, position): token for token what the host-driven loop
-// of Aligners/decoding.py produces (tests/test_gpu_aligner.py).
-// ---------------------------------------------------------------------------
-extern "C" int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
-                                       const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, int32_t max_new, int32_t check_every,
-                                       int32_t *out_tokens, float *out_logprobs, int32_t *out_steps, float *probe_prob)
-{
-    if (!c || !tokens || !token_offsets || !rules || !vocab_mask || !opts || !out_tokens || !out_steps) return PCE_E_INVALID;
-    if (max_new < 1) return pce_fail(c, PCE_E_INVALID, "decode loop: max_new must be >= 1");
-    if (check_every < 1) check_every = 4;
-    WhisperState *w = ws_of(c);
-    if (!w->dec_loaded) return pce_fail(c, PCE_E_STATE, "pce_whisper_decode_loop before pce_whisper_decoder_load");
-    if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "run pce_whisper_encode_run first");
-    const int n = w->n_clips_enc, d = w->tdims.n_state, V = w->tdims.n_vocab, T_cap = w->tdims.n_text_ctx;
-    *out_steps = 0;
-    if (n == 0) return PCE_OK;
-    // (a sequence that fills the text context stops there -- k_step_advance -- as openai-whisper's loop breaks when tokens.shape[-1] > n_ctx
-    // (decoding.py, DecodingTask._main_loop); the others go on: nothing is refused for what max_new MIGHT reach)
-    PCE_HIP(c, hipSetDevice(c->device));
-    KernelTimer loop_timer(c, PCE_K_DECODE_LOOP);
-    // ---- step 0: the prompts (prefix run, or one more position when the cache already holds them); next token stays in g_next
-    {
-        const int rc = decode_step_device(c, tokens, token_offsets, rules, vocab_mask, opts, probe_prob != nullptr && opts->probe_token >= 0);
-        if (rc) return rc;
-    }
-    { const int rc = decode_incremental_reserve(c, w, n); if (rc) return rc; }
-    const int64_t Vp = div_up(V, 128) * 128;
-    // ---- device-resident loop state
-    const size_t n_state_ints = (size_t)n * T_cap + 3 * (size_t)n + (size_t)n * max_new + 8 + (size_t)max_new;
-    PCE_HIP(c, w->g_loop.reserve(sizeof(int) * n_state_ints + sizeof(float) * (size_t)n * max_new + 256));
-    int *tok_table = w->g_loop.as<int>(), *len = tok_table + (size_t)n * T_cap, *ended = len + n, *sb = ended + n, *out_tok = sb + n,
-        *ctr = out_tok + (size_t)n * max_new, *n_ended = ctr + 8;
-    float *out_lp = reinterpret_cast<float *>(n_ended + max_new);
-    std::vector<int> h_tab((size_t)n * T_cap, 0), h_len((size_t)n), h_sb((size_t)n), ct((size_t)8 * n, 0);
-    for (int i = 0; i < n; i++) {
-        const int T = token_offsets[i + 1] - token_offsets[i];
-        memcpy(&h_tab[(size_t)i * T_cap], &tokens[token_offsets[i]], sizeof(int) * (size_t)T);
-        h_len[(size_t)i] = T; h_sb[(size_t)i] = opts->sample_begin ? opts->sample_begin[i] : opts->sample_begin_all;
-        ct[(size_t)n + i] = i; ct[(size_t)2 * n + i] = 1; ct[(size_t)3 * n + i] = i * T_cap; ct[(size_t)5 * n + i] = i * W_CTX; ct[(size_t)6 * n + i] = W_CTX;
-    }
-    PCE_HIP(c, hipMemsetAsync(ended, 0, sizeof(int) * (n_state_ints - (size_t)n * T_cap - (size_t)n) + sizeof(float) * (size_t)n * max_new, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(tok_table, h_tab.data(), sizeof(int) * h_tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(len, h_len.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(sb, h_sb.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->g_c_tab.p, ct.data(), sizeof(int) * ct.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));                 // (the host vectors are done with; the ONE upload of the window)
-    int *CT = w->g_c_tab.as<int>();
-    const int *next = w->g_next.as<int>();
-    const float *next_lp = reinterpret_cast<const float *>(w->g_next.as<int>() + n);
-    auto advance = [&]() {
-        hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(256), 0, c->stream, n, T_cap, (int)rules->eot, (int)max_new, tok_table, len, next, next_lp, CT, ended,
-                           out_tok, out_lp, ctr, n_ended);
-    };
-    auto all_ended = [&](int step, bool *yes) -> int {
-        int cnt = 0;
-        PCE_HIP(c, hipMemcpyAsync(&cnt, n_ended + step, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipStreamSynchronize(c->stream));
-        *yes = cnt >= n;
-        return PCE_OK;
-    };
-    advance();
-    int steps = 1;
-    bool stop = false;
-    DecRules R{rules->eot, rules->timestamp_begin, V, (int)Vp, opts->sample_begin_all, rules->max_initial_timestamp_index, opts->temperature, opts->seed_lo,
-               opts->seed_hi, -1};
-    if (max_new > 1) { const int rc = all_ended(0, &stop); if (rc) return rc; }
-    while (!stop && steps < max_new) {
-        decode_incremental_launches(c, w, n, CT, ended);
-        launch_gemm<EPI_F32>(c, w->g_lastln.as<op_t>(), d, 0, w->g_emb_bf16.as<op_t>(), n, (int)Vp, d, nullptr, w->g_logits.as<float>(), Vp, 0, 1);
-        hipLaunchKernelGGL(k_decode_rules, dim3((unsigned)n), dim3(DR_T), 0, c->stream, w->g_logits.as<float>(), tok_table, len, T_cap,
-                           w->g_mask.as<unsigned char>(), R, sb, w->g_next.as<int>(), reinterpret_cast<float *>(w->g_next.as<int>() + n),
-                           static_cast<float *>(nullptr), w->g_keys_n == n ? w->g_keys.as<int>() : nullptr);
-        advance();
-        steps++;
-        if (steps % check_every == 0 && steps < max_new) { const int rc = all_ended(steps - 1, &stop); if (rc) return rc; }
-    }
-    PCE_HIP(c, hipGetLastError());
-    // ---- the ONE download of the window
-    std::vector<int> h_out((size_t)n * max_new);
-    std::vector<float> h_lp((size_t)n * max_new);
-    PCE_HIP(c, hipMemcpyAsync(h_out.data(), out_tok, sizeof(int) * h_out.size(), hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(h_lp.data(), out_lp, sizeof(float) * h_lp.size(), hipMemcpyDeviceToHost, c->stream));
-    if (probe_prob && opts->probe_token >= 0)
-        PCE_HIP(c, hipMemcpyAsync(probe_prob, w->g_next.as<int>() + 2 * n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    for (int i = 0; i < n; i++)
-        for (int sidx = 0; sidx < max_new; sidx++) {
-            // steps that never ran read as "already ended": end-of-text with a zero log-probability, what further steps would have produced
-            out_tokens[(size_t)i * max_new + sidx] = sidx < steps ? h_out[(size_t)i * max_new + sidx] : rules->eot;
-            if (out_logprobs) out_logprobs[(size_t)i * max_new + sidx] = sidx < steps ? h_lp[(size_t)i * max_new + sidx] : 0.f;
-        }
-    *out_steps = steps;
-    w->g_cache_len = -1;                                         // the host's copy of the cached prefixes is stale: the next host-driven step re-runs its prefixes
-    return PCE_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Break-prediction token classifier: BertForTokenClassification forward (post-LN encoder layers on the same GEMM /
-// attention / LayerNorm kernels as the Whisper encoder; Code/baseline_models/pause_bert.py:127-132).
-// ---------------------------------------------------------------------------
-extern "C" {
-
-int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, int64_t n_floats)
-{
-    if (!c || !dims || !weights) return PCE_E_INVALID;
-    const int d = dims->n_state, L = dims->n_layer, V = dims->n_vocab, P = dims->n_pos, TY = dims->n_type, NL = dims->n_labels;
-    if (d <= 0 || d % 128 || dims->n_head * 64 != d || L <= 0 || V <= 0 || P <= 0 || P > 512 || TY <= 0 || NL <= 0 || NL > 128)
-        return pce_fail(c, PCE_E_LIMIT, "unsupported BERT dims (need n_state %% 128 == 0, head size 64, n_pos <= 512, n_labels <= 128)");
-    if (d > LN_D_MAX) return pce_fail(c, PCE_E_LIMIT, "BERT with n_state %d: the LayerNorm kernels hold at most %d", d, LN_D_MAX);
-    const int64_t dd = (int64_t)d * d;
-    const int64_t per_layer = 4 * (dd + d) + 2LL * d + (4 * dd + 4LL * d) + (4 * dd + d) + 2LL * d;
-    const int64_t expect = ((int64_t)V + P + TY) * d + 2LL * d + L * per_layer + (int64_t)NL * (d + 1);
-    if (n_floats != expect) return pce_fail(c, PCE_E_INVALID, "BERT weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
-    PCE_HIP(c, hipSetDevice(c->device));
-    WhisperState::Bert &b = ws_of(c)->bert;
-    b.dims = *dims; b.loaded = false; b.n_seq = -1; b.layers.assign((size_t)L, {});
-    std::vector<float> mats, vecs;
-    auto add_vec = [&](const float *p, size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), p, p + n); return o; };
-    auto add_mat = [&](const float *p, size_t n) { size_t o = mats.size(); mats.insert(mats.end(), p, p + n); return o; };
-    const float *p = weights;
-    const float *word = p; p += (size_t)V * d;
-    const float *pos = p; p += (size_t)P * d;
-    const float *type = p; p += (size_t)TY * d;
-    b.lne_w = add_vec(p, (size_t)d); p += d; b.lne_b = add_vec(p, (size_t)d); p += d;
-    for (int l = 0; l < L; l++) {
-        WhisperState::Bert::Layer &ly = b.layers[(size_t)l];
-        const float *qw = p, *qb = qw + dd, *kw = qb + d, *kb = kw + dd, *vw = kb + d, *vb = vw + dd;
-        ly.qkv_w = add_mat(qw, (size_t)dd); add_mat(kw, (size_t)dd); add_mat(vw, (size_t)dd);          // fused [3d][d]
-        ly.qkv_b = add_vec(qb, (size_t)d); add_vec(kb, (size_t)d); add_vec(vb, (size_t)d);
-        p = vb + d;
-        ly.out_w = add_mat(p, (size_t)dd); p += dd; ly.out_b = add_vec(p, (size_t)d); p += d;
-        ly.ln1_w = add_vec(p, (size_t)d); p += d; ly.ln1_b = add_vec(p, (size_t)d); p += d;
-        ly.m1_w = add_mat(p, (size_t)(4 * dd)); p += 4 * dd; ly.m1_b = add_vec(p, (size_t)4 * d); p += 4 * d;
-        ly.m2_w = add_mat(p, (size_t)(4 * dd)); p += 4 * dd; ly.m2_b = add_vec(p, (size_t)d); p += d;
-        ly.ln2_w = add_vec(p, (size_t)d); p += d; ly.ln2_b = add_vec(p, (size_t)d); p += d;
-    }
-    {   // classifier [n_labels][d] padded with zero rows to one 128-column GEMM tile
-        std::vector<float> cw((size_t)128 * d, 0.f), cb(128, 0.f);
-        memcpy(cw.data(), p, sizeof(float) * (size_t)NL * d); p += (size_t)NL * d;
-        memcpy(cb.data(), p, sizeof(float) * (size_t)NL); p += NL;
-        b.cls_w = add_mat(cw.data(), cw.size()); b.cls_b = add_vec(cb.data(), cb.size());
-    }
-    DevBuf tmp;
-    PCE_HIP(c, tmp.reserve(sizeof(float) * mats.size()));
-    PCE_HIP(c, b.w_bf16.reserve(sizeof(op_t) * mats.size() + 256));
-    PCE_HIP(c, b.w_f32.reserve(sizeof(float) * vecs.size()));
-    PCE_HIP(c, b.word.reserve(sizeof(float) * (size_t)V * d));
-    PCE_HIP(c, b.pos.reserve(sizeof(float) * (size_t)P * d));
-    PCE_HIP(c, b.type0.reserve(sizeof(float) * (size_t)d));
-    PCE_HIP(c, hipMemcpyAsync(tmp.p, mats.data(), sizeof(float) * mats.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.w_f32.p, vecs.data(), sizeof(float) * vecs.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.word.p, word, sizeof(float) * (size_t)V * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.pos.p, pos, sizeof(float) * (size_t)P * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.type0.p, type, sizeof(float) * (size_t)d, hipMemcpyHostToDevice, c->stream));      // token_type_ids = 0
-    hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(),
-                       b.w_bf16.as<op_t>(), (int64_t)mats.size());
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    b.loaded = true;
-    return PCE_OK;
-}
-
-int pce_bert_run(pce_ctx *c, const int32_t *input_ids, const int32_t *offsets, int32_t n_seq)
-{
-    if (!c || !input_ids || !offsets || n_seq < 0) return PCE_E_INVALID;
-    WhisperState::Bert &b = ws_of(c)->bert;
-    if (!b.loaded) return pce_fail(c, PCE_E_STATE, "pce_bert_run before pce_bert_load");
-    PCE_HIP(c, hipSetDevice(c->device));
-    const int d = b.dims.n_state, H = b.dims.n_head, L = b.dims.n_layer, V = b.dims.n_vocab, n = n_seq, SPD = 512;
-    b.n_seq = -1;
-    b.lens.assign((size_t)n, 0);
-    int T_max = 0;
-    for (int i = 0; i < n; i++) {
-        const int T = offsets[i + 1] - offsets[i];
-        if (T < 1 || T > b.dims.n_pos) return pce_fail(c, PCE_E_INVALID, "sequence %d: %d tokens (need 1..%d)", i, T, b.dims.n_pos);
-        b.lens[(size_t)i] = T; T_max = std::max(T_max, T);
-    }
-    if (n == 0) { b.n_seq = 0; return PCE_OK; }
-    const int T_pad = (int)div_up(T_max, 16) * 16;
-    const int64_t M = (int64_t)n * T_pad;
-    std::vector<int> tab((size_t)2 * n), tok((size_t)M, 0);
-    for (int i = 0; i < n; i++) {
-        tab[(size_t)i] = i * T_pad; tab[(size_t)n + i] = b.lens[(size_t)i];
-        for (int t = 0; t < b.lens[(size_t)i]; t++) {
-            const int v = input_ids[offsets[i] + t];
-            if (v < 0 || v >= V) return pce_fail(c, PCE_E_INVALID, "token id %d out of the vocabulary", v);
-            tok[(size_t)i * T_pad + t] = v;
-        }
-    }
-    PCE_HIP(c, b.tab.reserve(sizeof(int) * tab.size()));
-    PCE_HIP(c, b.tokens.reserve(sizeof(int) * tok.size()));
-    PCE_HIP(c, b.resid.reserve(sizeof(float) * (size_t)M * d));
-    PCE_HIP(c, b.ln.reserve(sizeof(op_t) * (size_t)M * d + 4096));
-    PCE_HIP(c, b.qk.reserve(sizeof(op_t) * (size_t)M * 2 * d + 4096));
-    PCE_HIP(c, b.attn.reserve(sizeof(op_t) * (size_t)M * d + 4096));
-    PCE_HIP(c, b.hidden.reserve(sizeof(op_t) * (size_t)M * 4 * d + 4096));
-    PCE_HIP(c, b.logits.reserve(sizeof(float) * (size_t)M * 128));
-    const size_t vt_elems = (size_t)n * (size_t)d * SPD + 64;
-    PCE_HIP(c, b.vt.reserve(sizeof(op_t) * vt_elems));
-    PCE_HIP(c, hipMemcpyAsync(b.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.tokens.p, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    // the attention kernel writes the rows of real tokens only and V^T columns beyond T_pad are never written: no stale bits
-    PCE_HIP(c, hipMemsetAsync(b.attn.p, 0, sizeof(op_t) * (size_t)M * d + 4096, c->stream));
-    PCE_HIP(c, hipMemsetAsync(b.vt.p, 0, sizeof(op_t) * vt_elems, c->stream));
-    const int *T0 = b.tab.as<int>(), *TL = T0 + n;
-    const op_t *Wb = b.w_bf16.as<op_t>();
-    const float *Wf = b.w_f32.as<float>();
-    const float eps = 1e-12f;                                    // BertConfig.layer_norm_eps
-    KernelTimer timer(c, PCE_K_BERT);
-    hipLaunchKernelGGL(k_bert_embed, dim3((unsigned)div_up(M * d, 256)), dim3(256), 0, c->stream, b.tokens.as<int>(), b.word.as<float>(),
-                       b.pos.as<float>(), b.type0.as<float>(), T_pad, b.dims.n_pos, d, M, b.resid.as<float>());
-    auto ln = [&](size_t w_off, size_t b_off) {                  // resid <- LN(resid) (fp32, in place) and its op_t copy
-        launch_layernorm<op_t>(c, b.resid.as<float>(), Wf + w_off, Wf + b_off,
-                           M, d, b.ln.as<op_t>(), eps, b.resid.as<float>());
-    };
-    ln(b.lne_w, b.lne_b);
-    for (int l = 0; l < L; l++) {
-        const WhisperState::Bert::Layer &ly = b.layers[(size_t)l];
-        launch_gemm<EPI_QKV>(c, b.ln.as<op_t>(), d, 0, Wb + ly.qkv_w, (int)M, 3 * d, d, Wf + ly.qkv_b, b.qk.as<op_t>(), 2 * d, 0, 1,
-                             reinterpret_cast<const float *>(b.vt.as<op_t>()), T_pad, 2 * d, SPD);
-        {
-            AttnArgs a{};
-            a.q = b.qk.as<op_t>(); a.q_ld = 2 * d; a.k = b.qk.as<op_t>() + d; a.k_ld = 2 * d;
-            a.vt = b.vt.as<op_t>(); a.vt_clip = (int64_t)d * SPD; a.vt_sp = SPD;
-            a.q_row0 = a.k_row0 = T0; a.q_len = a.k_len = TL;    // keys beyond the sequence length are masked (right padding)
-            a.out = b.attn.as<op_t>(); a.out_ld = d; a.causal = 0;
-            launch_attention(c, dim3((unsigned)div_up(T_pad, AT_QB), (unsigned)H, (unsigned)n), a);
-        }
-        launch_gemm<EPI_RESID_F32>(c, b.attn.as<op_t>(), d, 0, Wb + ly.out_w, (int)M, d, d, Wf + ly.out_b, b.resid.as<float>(), d, 0, 1);
-        ln(ly.ln1_w, ly.ln1_b);
-        launch_gemm<EPI_GELU_BF16>(c, b.ln.as<op_t>(), d, 0, Wb + ly.m1_w, (int)M, 4 * d, d, Wf + ly.m1_b, b.hidden.as<op_t>(), 4 * d, 0, 1);
-        launch_gemm<EPI_RESID_F32>(c, b.hidden.as<op_t>(), 4 * d, 0, Wb + ly.m2_w, (int)M, d, 4 * d, Wf + ly.m2_b, b.resid.as<float>(), d, 0, 1);
-        ln(ly.ln2_w, ly.ln2_b);
-    }
-    // classifier: logits[M][128] = 0 + hidden . W^T + b (the first n_labels columns are real)
-    launch_gemm<EPI_F32>(c, b.ln.as<op_t>(), d, 0, Wb + b.cls_w, (int)M, 128, d, Wf + b.cls_b, b.logits.as<float>(), 128, 0, 1);
-    PCE_HIP(c, hipGetLastError());
-    b.n_seq = n; b.T_pad = T_pad;
-    return PCE_OK;
-}
-
-int pce_bert_fetch(pce_ctx *c, int32_t seq, float *logits, int32_t *labels)
-{
-    if (!c) return PCE_E_INVALID;
-    WhisperState::Bert &b = ws_of(c)->bert;
-    if (b.n_seq < 0) return pce_fail(c, PCE_E_STATE, "pce_bert_fetch before pce_bert_run");
-    if (seq < 0 || seq >= b.n_seq) return pce_fail(c, PCE_E_INVALID, "sequence out of range");
-    PCE_HIP(c, hipSetDevice(c->device));
-    const int T = b.lens[(size_t)seq], NL = b.dims.n_labels;
-    std::vector<float> rows((size_t)T * 128);
-    PCE_HIP(c, hipMemcpyAsync(rows.data(), b.logits.as<float>() + (size_t)seq * b.T_pad * 128, sizeof(float) * rows.size(), hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    pce_profile_collect(c);
-    for (int t = 0; t < T; t++) {
-        int best = 0;
-        for (int k = 0; k < NL; k++) {
-            const float v = rows[(size_t)t * 128 + k];
-            if (logits) logits[(size_t)t * NL + k] = v;
-            if (v > rows[(size_t)t * 128 + best]) best = k;          // first maximum, as argmax
-        }
-        if (labels) labels[t] = best;
-    }
-    return PCE_OK;
-}
-
-} // extern "C"
-
+#include "pce_whisper_selftest.inc"
+#include "pce_whisper_decoder.inc"
+#include "pce_bert.inc"

@@ -1,0 +1,392 @@
+// pce_whisper_selftest.inc -- the pce_selftest_* entry points (include/pce.h) and their helpers, included by pce_whisper_impl.inc: its kernels on host arrays.
+namespace {
+// pce_selftest_gemm_tiled: the kernel a selector stands for (GK_AUTO: the product's rule), or -1 where that kernel does not compute the shape
+template <int EPI> static int selftest_gemm_kind(const pce_ctx *c, int kernel, const GemmShape &s)
+{
+    const int kind = kernel == GK_AUTO ? gemm_choose<EPI>(c, s) : kernel;
+    return gemm_fits<EPI>(kind, s) ? kind : -1;
+}
+
+// pce_selftest_layernorm's k_add_layernorm forms: the stream is updated in place when it keeps its type (as the encoder runs it), else written to
+// a second buffer
+template <class OUT, class RIN, class ROUT>
+static int selftest_add_layernorm(pce_ctx *c, int64_t rows, int d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w, const float *b,
+                                  float eps, int write_resid, void *out, void *resid_out, uint16_t *out_copy)
+{
+    constexpr bool IN_PLACE = std::is_same<RIN, ROUT>::value;
+    const size_t n = (size_t)rows * d;
+    DevBuf din, dres, ddl, ddl2, dw, db, dout, dcopy;
+    PCE_HIP(c, din.reserve(sizeof(RIN) * n)); PCE_HIP(c, ddl.reserve(2 * n)); PCE_HIP(c, dw.reserve(sizeof(float) * d)); PCE_HIP(c, db.reserve(sizeof(float) * d));
+    PCE_HIP(c, dout.reserve(sizeof(OUT) * n));
+    if (!IN_PLACE) PCE_HIP(c, dres.reserve(sizeof(ROUT) * n));
+    if (delta2) PCE_HIP(c, ddl2.reserve(2 * n));
+    if (out_copy) PCE_HIP(c, dcopy.reserve(2 * n));
+    PCE_HIP(c, hipMemcpyAsync(din.p, x, sizeof(RIN) * n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(ddl.p, delta, 2 * n, hipMemcpyHostToDevice, c->stream));
+    if (delta2) PCE_HIP(c, hipMemcpyAsync(ddl2.p, delta2, 2 * n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dout.p, 0, sizeof(OUT) * n, c->stream));
+    if (!IN_PLACE) PCE_HIP(c, hipMemsetAsync(dres.p, 0, sizeof(ROUT) * n, c->stream));
+    if (out_copy) PCE_HIP(c, hipMemsetAsync(dcopy.p, 0, 2 * n, c->stream));
+    ROUT *rout = IN_PLACE ? din.as<ROUT>() : dres.as<ROUT>();
+    launch_add_layernorm<OUT, RIN, ROUT>(c, din.as<RIN>(), rout, ddl.as<op_t>(), delta2 ? ddl2.as<op_t>() : nullptr, write_resid, dw.as<float>(), db.as<float>(),
+                                         rows, d, dout.as<OUT>(), eps, out_copy ? dcopy.as<op_t>() : nullptr);
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, sizeof(OUT) * n, hipMemcpyDeviceToHost, c->stream));
+    if (resid_out) PCE_HIP(c, hipMemcpyAsync(resid_out, rout, sizeof(ROUT) * n, hipMemcpyDeviceToHost, c->stream));
+    if (out_copy) PCE_HIP(c, hipMemcpyAsync(out_copy, dcopy.p, 2 * n, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+} // namespace
+
+extern "C" {
+
+// V rows of clip c at rows k_row0[c] .. + k_len[c] of [.][heads * 64] -> the V^T image the attention kernels read: [clip][head * 64 + d][sp] (the
+// rest of the key axis keeps its zeros)
+static __global__ void k_selftest_vt(const op_t *__restrict__ v, const int *__restrict__ k_row0, const int *__restrict__ k_len, int hd, int sp,
+                                     op_t *__restrict__ vt)
+{
+    const int clip = blockIdx.y;
+    const int64_t n = (int64_t)k_len[clip] * hd;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int col = (int)(i % hd), t = (int)(i / hd);
+        vt[((int64_t)clip * hd + col) * sp + t] = v[(int64_t)k_row0[clip] * hd + i];
+    }
+}
+
+// Self-test hooks of the attention kernel through launch_attention (see pce.h)
+int pce_selftest_attention_ragged(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, const int32_t *q_len,
+                                  const int32_t *k_len, int32_t causal, int32_t mode, uint16_t *out, int64_t out_rows, int32_t *fell_back)
+{
+    if (!c || !q || !k || !v || !out || !q_len || !k_len || clips <= 0 || clips > 65535 || heads <= 0 || heads > 65535 || mode < 0 || mode > 1)
+        return PCE_E_INVALID;
+    std::vector<int> tab((size_t)4 * clips);
+    int64_t q_rows = 0, k_rows = 0;
+    int q_max = 0, k_max = 0;
+    for (int i = 0; i < clips; i++) {
+        if (q_len[i] < 1 || k_len[i] < 1 || q_len[i] > (1 << 20) || k_len[i] > (1 << 20)) return pce_fail(c, PCE_E_INVALID, "selftest attention: clip %d has %d queries, %d keys", i, q_len[i], k_len[i]);
+        tab[(size_t)i] = (int)q_rows; tab[(size_t)clips + i] = q_len[i]; tab[(size_t)2 * clips + i] = (int)k_rows; tab[(size_t)3 * clips + i] = k_len[i];
+        q_rows += q_len[i]; k_rows += k_len[i];
+        q_max = q_len[i] > q_max ? q_len[i] : q_max; k_max = k_len[i] > k_max ? k_len[i] : k_max;
+    }
+    const int hd = heads * 64, sp = div_up(k_max, 64) * 64;
+    if (out_rows < q_rows || (out_rows + k_rows) * hd >= ((int64_t)1 << 30)) return pce_fail(c, PCE_E_INVALID, "selftest attention: %lld output rows for %lld queries", (long long)out_rows, (long long)q_rows);
+    PCE_HIP(c, hipSetDevice(c->device));
+    const size_t nq = (size_t)q_rows * hd, nk = (size_t)k_rows * hd, nvt = (size_t)clips * hd * sp, no = (size_t)out_rows * hd;
+    DevBuf dq, dk, dv, dvt, dout, dtab, dcnt;
+    PCE_HIP(c, dq.reserve(nq * 2 + 64)); PCE_HIP(c, dk.reserve(nk * 2 + 64)); PCE_HIP(c, dv.reserve(nk * 2 + 64)); PCE_HIP(c, dvt.reserve(nvt * 2 + 128));
+    PCE_HIP(c, dout.reserve(no * 2 + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * 4 * (size_t)clips)); PCE_HIP(c, dcnt.reserve(sizeof(int)));
+    PCE_HIP(c, hipMemcpyAsync(dq.p, q, nq * 2, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dk.p, k, nk * 2, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dv.p, v, nk * 2, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dout.p, out, no * 2, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dvt.p, 0, nvt * 2 + 128, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dcnt.p, 0, sizeof(int), c->stream));
+    AttnArgs a{};
+    a.q = dq.as<op_t>(); a.q_ld = hd; a.k = dk.as<op_t>(); a.k_ld = hd; a.vt = dvt.as<op_t>(); a.vt_clip = (int64_t)hd * sp; a.vt_sp = sp;
+    a.q_row0 = dtab.as<int>(); a.q_len = a.q_row0 + clips; a.k_row0 = a.q_row0 + 2 * clips; a.k_len = a.q_row0 + 3 * clips;
+    a.out = dout.as<op_t>(); a.out_ld = hd; a.causal = causal; a.fell_back = dcnt.as<int>();
+    hipLaunchKernelGGL(k_selftest_vt, dim3((unsigned)div_up((int64_t)k_max * hd, 256), (unsigned)clips), dim3(256), 0, c->stream, dv.as<op_t>(), a.k_row0,
+                       a.k_len, hd, sp, dvt.as<op_t>());
+    // the grid of the longest clip, as the teacher-forced decoder launches it: one query block takes the NT instantiation
+    launch_attention(c, dim3((unsigned)div_up(q_max, AT_QB), (unsigned)heads, (unsigned)clips), a, 0.0, mode);
+    PCE_HIP(c, hipGetLastError());
+    int cnt = 0;
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, no * 2, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(&cnt, dcnt.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    if (fell_back) *fell_back = cnt;
+    return PCE_OK;
+}
+int pce_selftest_attention(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, int32_t q_len,
+                           int32_t k_len, int32_t causal, int32_t mode, uint16_t *out, int32_t *fell_back)
+{
+    if (!c || !out || clips <= 0 || heads <= 0 || q_len <= 0 || k_len <= 0) return PCE_E_INVALID;
+    const std::vector<int32_t> ql((size_t)clips, q_len), kl((size_t)clips, k_len);
+    std::fill(out, out + (size_t)clips * q_len * heads * 64, (uint16_t)0);
+    return pce_selftest_attention_ragged(c, q, k, v, clips, heads, ql.data(), kl.data(), causal, mode, out, (int64_t)clips * q_len, fell_back);
+}
+
+// Self-test hook of the single-query attention kernels of an incremental decoding step, through the launches the step makes (see pce.h)
+int pce_selftest_attn1(pce_ctx *c, int32_t form, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, uint16_t *k, int64_t k_elems, uint16_t *v,
+                       int64_t v_elems, const int32_t *k_row0, const int32_t *len, const int32_t *skip, int32_t span, uint16_t *out, int64_t out_elems)
+{
+    if (!c || form < 0 || form > 2 || !q || !k || !v || !len || !out || n < 1 || n > 65535 || heads < 1 || span < 1) return PCE_E_INVALID;
+    if (heads > 32) return pce_fail(c, PCE_E_INVALID, "selftest attn1: %d heads (the kernels hold 32)", heads);
+    const int64_t d = (int64_t)heads * 64;
+    const int T_cap = span, vt_sp = form == 0 ? span : 512;
+    if (form == 0 && (!k_row0 || vt_sp % 8 != 0)) return pce_fail(c, PCE_E_INVALID, "selftest attn1: form 0 needs k_row0 and vt_sp %% 8 == 0 (%d)", vt_sp);
+    if (form != 0 && T_cap > 512) return pce_fail(c, PCE_E_INVALID, "selftest attn1: T_cap %d > 512", T_cap);
+    const int64_t q_need = (int64_t)n * d * (form == 0 ? 1 : 3), v_need = (int64_t)n * d * (form == 2 ? T_cap : vt_sp), o_need = (int64_t)n * d;
+    int64_t k_need = form == 0 ? 0 : (int64_t)n * T_cap * d;
+    std::vector<int> tab((size_t)4 * n, 0);                        // k_row0 | k_len | pos | skip
+    for (int i = 0; i < n; i++) {
+        if (form == 0) {
+            if (len[i] < 1 || len[i] > 1536 || k_row0[i] < 0 || (len[i] + 7) / 8 * 8 > vt_sp)
+                return pce_fail(c, PCE_E_INVALID, "selftest attn1: clip %d has %d keys from row %d (V^T pitch %d)", i, len[i], k_row0[i], vt_sp);
+            const int64_t end = ((int64_t)k_row0[i] + len[i]) * d;
+            k_need = end > k_need ? end : k_need;
+            tab[(size_t)i] = k_row0[i]; tab[(size_t)n + i] = len[i];
+        } else {
+            if (len[i] < 0 || len[i] >= T_cap) return pce_fail(c, PCE_E_INVALID, "selftest attn1: clip %d at position %d of %d", i, len[i], T_cap);
+            tab[(size_t)i] = i * T_cap; tab[(size_t)n + i] = len[i] + 1; tab[(size_t)2 * n + i] = len[i];
+        }
+        tab[(size_t)3 * n + i] = skip ? skip[i] : 0;
+    }
+    if (q_elems < q_need || k_elems < k_need || v_elems < v_need || out_elems < o_need || k_elems >= ((int64_t)1 << 31) || v_elems >= ((int64_t)1 << 31))
+        return pce_fail(c, PCE_E_INVALID, "selftest attn1: form %d needs q %lld, k %lld, v %lld, out %lld elements", form, (long long)q_need, (long long)k_need,
+                        (long long)v_need, (long long)o_need);
+    PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    DevBuf dq, dk, dv, dout, dtab;
+    PCE_HIP(c, dq.reserve(2 * (size_t)q_elems + 64)); PCE_HIP(c, dk.reserve(2 * (size_t)k_elems + 64)); PCE_HIP(c, dv.reserve(2 * (size_t)v_elems + 64));
+    PCE_HIP(c, dout.reserve(2 * (size_t)out_elems + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * tab.size()));
+    PCE_HIP(c, hipMemcpyAsync(dq.p, q, 2 * (size_t)q_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dk.p, k, 2 * (size_t)k_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dv.p, v, 2 * (size_t)v_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dout.p, out, 2 * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    const int *T = dtab.as<int>(), *SKIP = skip ? T + 3 * n : nullptr;
+    if (form == 2) {
+        SelfAttn1Args sa{};
+        sa.qkv = dq.as<op_t>(); sa.qkv_ld = 3 * d; sa.ck = dk.as<op_t>(); sa.cv = dv.as<op_t>(); sa.c_clip = (int64_t)T_cap * d; sa.d = (int)d;
+        sa.pos = T + 2 * n; sa.skip = SKIP; sa.out = dout.as<op_t>(); sa.out_ld = d;
+        launch_self_attn1(c, n, heads, sa);
+    } else {
+        Attn1Args a{};
+        a.q = dq.as<op_t>(); a.q_ld = form == 0 ? d : 3 * d; a.k = dk.as<op_t>(); a.k_ld = d; a.vt = dv.as<op_t>(); a.vt_clip = d * vt_sp; a.vt_sp = vt_sp;
+        a.k_row0 = T; a.k_len = T + n; a.skip = SKIP; a.out = dout.as<op_t>(); a.out_ld = d;
+        if (form == 1) { a.app_k = dq.as<op_t>() + d; a.app_v = dq.as<op_t>() + 2 * d; a.app_ld = 3 * d; a.app_pos = T + 2 * n; }
+        launch_cross_attn1(c, n, heads, a);
+    }
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
+    if (form != 0) {
+        PCE_HIP(c, hipMemcpyAsync(k, dk.p, 2 * (size_t)k_elems, hipMemcpyDeviceToHost, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(v, dv.p, 2 * (size_t)v_elems, hipMemcpyDeviceToHost, c->stream));
+    }
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+
+// Self-test hook of the encoder-output cross-attention of an incremental decoding step (pce_xattn.inc): k_xq_fused -> k_xattn_absorbed -> k_uv_absorb of ONE
+// layer on host arrays, with the number of workgroups per clip forced (0: what the batch size selects).  See include/pce.h.
+int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,
+                       const uint16_t *wv, const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads,
+                       int32_t workgroups_per_clip, uint16_t *out)
+{
+    if (!c || !resid || !ln_w || !ln_b || !wq || !bq || !wk || !wv || !bv || !E || !k_len || !out || n <= 0 || k_cap <= 0) return PCE_E_INVALID;
+    if (!xa_has_form(d, heads))
+        return pce_fail(c, PCE_E_INVALID, "selftest xattn: d = %d with %d heads is not a width the encoder-output form is built for", d, heads);
+    if (!(workgroups_per_clip == 0 || workgroups_per_clip == 1 || workgroups_per_clip == 2 || workgroups_per_clip == 4)) return PCE_E_INVALID;
+    for (int i = 0; i < n; i++) if (k_len[i] <= 0 || k_len[i] > k_cap) return pce_fail(c, PCE_E_INVALID, "selftest xattn: clip %d has %d frames of %d", i, k_len[i], k_cap);
+    PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    const size_t dd = (size_t)d * d, ne = (size_t)n * k_cap * d;
+    DevBuf dres, dlw, dlb, dwq, dbq, dwk, dwkT, dwv, dbv, dE, dkl, dqp, dup, dml, dout;
+    PCE_HIP(c, dres.reserve(sizeof(float) * (size_t)n * d)); PCE_HIP(c, dlw.reserve(sizeof(float) * d)); PCE_HIP(c, dlb.reserve(sizeof(float) * d));
+    PCE_HIP(c, dwq.reserve(2 * dd)); PCE_HIP(c, dbq.reserve(sizeof(float) * d)); PCE_HIP(c, dwk.reserve(2 * dd)); PCE_HIP(c, dwkT.reserve(2 * dd));
+    PCE_HIP(c, dwv.reserve(2 * dd)); PCE_HIP(c, dbv.reserve(sizeof(float) * d)); PCE_HIP(c, dE.reserve(2 * ne + 4096)); PCE_HIP(c, dkl.reserve(sizeof(int) * (size_t)n));
+    const size_t R = (size_t)xa_rows(heads);
+    PCE_HIP(c, dqp.reserve(2 * 2 * (size_t)n * R * d + 256)); PCE_HIP(c, dup.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
+    PCE_HIP(c, dml.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * 2 + 256)); PCE_HIP(c, dout.reserve(2 * (size_t)n * d + 64));
+    struct Up { void *dst; const void *src; size_t bytes; } ups[] = {
+        {dres.p, resid, sizeof(float) * (size_t)n * d}, {dlw.p, ln_w, sizeof(float) * d}, {dlb.p, ln_b, sizeof(float) * d}, {dwq.p, wq, 2 * dd}, {dbq.p, bq, sizeof(float) * d},
+        {dwk.p, wk, 2 * dd}, {dwv.p, wv, 2 * dd}, {dbv.p, bv, sizeof(float) * d}, {dE.p, E, 2 * ne}, {dkl.p, k_len, sizeof(int) * (size_t)n}};
+    for (const Up &u : ups) PCE_HIP(c, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dqp.p, 0, dqp.cap, c->stream)); PCE_HIP(c, hipMemsetAsync(dout.p, 0, dout.cap, c->stream));
+    hipLaunchKernelGGL(k_transpose_sq, dim3((unsigned)(d / 32), (unsigned)(d / 32)), dim3(256), 0, c->stream, dwk.as<op_t>(), dwkT.as<op_t>(), d);
+    XaArgs a{};
+    a.E = dE.as<op_t>(); a.e_clip = (int64_t)k_cap * d; a.e_ld = d; a.k_len = dkl.as<int>(); a.skip = nullptr;
+    a.u_part = dup.as<float>(); a.ml_part = dml.as<float>(); a.heads = heads; a.nsplit = xa_split(n, workgroups_per_clip); a.rows = (int)R;
+    XaLayer y{};
+    y.resid = dres.as<float>(); y.ln_w = dlw.as<float>(); y.ln_b = dlb.as<float>(); y.wq = dwq.as<op_t>(); y.bq = dbq.as<float>(); y.wkT = dwkT.as<op_t>();
+    y.wv = dwv.as<op_t>(); y.bv = dbv.as<float>(); y.qp_hi = dqp.as<op_t>(); y.qp_lo = y.qp_hi + (size_t)n * R * d; y.out = dout.as<op_t>(); y.out_ld = d;
+    xattn_launch(c, d, n, a, y);
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)n * d, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+
+// Self-test hook of the persistent 256 x 256 GEMM: C = epilogue(A B^T + bias) on host arrays (op_t bit patterns in, op_t bit patterns out).
+// epilogue 0: bias, 1: bias + GELU, 2: bias, written transposed per clip (rows_per_clip rows, key axis padded to vt_sp): out[(clip N + n) vt_sp + t]
+int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, int32_t epilogue,
+                      int32_t rows_per_clip, int32_t vt_sp, uint16_t *out)
+{
+    if (!c || !A || !B || !out || M <= 0 || N <= 0 || K <= 0) return PCE_E_INVALID;
+    PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    if (epilogue >= 16 && epilogue <= 19) {
+        // the tiled / few-row kernels behind launch_gemm (which of them runs follows from the shape and PCE_GEMM_SKINNY; pce_selftest_gemm_tiled
+        // chooses one and takes every epilogue): 16 = bias,
+        // 17 = bias + GELU (16-bit outputs), 19 = accumulate into a zeroed fp32 matrix (out receives M * N floats)
+        const bool f32 = epilogue == 19;
+        DevBuf tA, tB, tC, tb;
+        PCE_HIP(c, tA.reserve((size_t)M * K * 2 + 4096)); PCE_HIP(c, tB.reserve((size_t)(N + 128) * K * 2 + 4096)); PCE_HIP(c, tC.reserve((size_t)M * N * 4 + 4096));
+        PCE_HIP(c, tb.reserve((size_t)(N + 128) * 4));
+        PCE_HIP(c, hipMemsetAsync(tB.p, 0, (size_t)(N + 128) * K * 2, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(tA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(tB.p, B, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemsetAsync(tb.p, 0, (size_t)(N + 128) * 4, c->stream));
+        if (bias) PCE_HIP(c, hipMemcpyAsync(tb.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemsetAsync(tC.p, 0, (size_t)M * N * 4, c->stream));
+        if (N % 128) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): N must be a multiple of 128");
+        c->gemm_few_rows = true;                                   // (the few-row kernel is eligible here, as in an incremental decoding step)
+        struct Off { pce_ctx *c; ~Off() { c->gemm_few_rows = false; } } off{c};
+        if (epilogue == 16) launch_gemm<EPI_BF16>(c, tA.as<op_t>(), K, 0, tB.as<op_t>(), M, N, K, tb.as<float>(), tC.p, N, 0, 1);
+        else if (epilogue == 17) launch_gemm<EPI_GELU_BF16>(c, tA.as<op_t>(), K, 0, tB.as<op_t>(), M, N, K, tb.as<float>(), tC.p, N, 0, 1);
+        else if (epilogue == 19) launch_gemm<EPI_RESID_F32>(c, tA.as<op_t>(), K, 0, tB.as<op_t>(), M, N, K, tb.as<float>(), tC.p, N, 0, 1);
+        else return pce_fail(c, PCE_E_INVALID, "selftest gemm: epilogue 18 does not exist");
+        PCE_HIP(c, hipGetLastError());
+        PCE_HIP(c, hipMemcpyAsync(out, tC.p, (size_t)M * N * (f32 ? 4 : 2), hipMemcpyDeviceToHost, c->stream));
+        PCE_HIP(c, hipStreamSynchronize(c->stream));
+        pce_profile_collect(c);
+        return PCE_OK;
+    }
+    const size_t n_out = epilogue == 2 ? (size_t)(M / rows_per_clip) * N * vt_sp
+                         : epilogue >= 256 ? (size_t)M * epilogue + (size_t)(M / rows_per_clip) * (N - epilogue) * vt_sp : (size_t)M * N;
+    DevBuf dA, dB, dC, dbias;
+    PCE_HIP(c, dA.reserve((size_t)M * K * 2)); PCE_HIP(c, dB.reserve((size_t)N * K * 2)); PCE_HIP(c, dC.reserve(n_out * 2)); PCE_HIP(c, dbias.reserve((size_t)N * 4));
+    PCE_HIP(c, hipMemcpyAsync(dA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dB.p, B, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+    if (bias) PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dC.p, 0, n_out * 2, c->stream));
+    bool ok = false;
+    const float *bp = bias ? dbias.as<float>() : nullptr;
+    if (epilogue == 0) ok = launch_gemm_flat<FEPI_BF16>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, N);
+    else if (epilogue == 1) ok = launch_gemm_flat<FEPI_GELU>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, N);
+    else if (epilogue == 2) ok = launch_gemm_flat<FEPI_VT>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, 0, rows_per_clip, vt_sp);
+    else if (epilogue >= 256 && epilogue % 256 == 0 && epilogue < N)      // split launch: columns [0, epilogue) row-major [M][epilogue], then the V^T image of the rest
+        ok = launch_gemm_flat<FEPI_SPLIT>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, epilogue, rows_per_clip, vt_sp, PCE_K_GEMM_FLAT,
+                                          dC.as<op_t>() + (size_t)M * epilogue, epilogue);
+    int rc = PCE_OK;
+    if (!ok) rc = pce_fail(c, PCE_E_LIMIT, "shape not handled by the 256 x 256 kernel (N %% 256, K %% 64)");
+    else {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out, dC.p, n_out * 2, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = pce_fail(c, PCE_E_DEVICE, "selftest gemm: %s", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    pce_profile_collect(c);
+    return rc;
+}
+
+// Self-test hook of the tiled / few-row GEMM kernels through the product's own launch code (launch_gemm_kernel; see pce.h).  Every byte a launch
+// can address is checked against the caller's buffer lengths before anything is allocated.
+int pce_selftest_gemm_tiled(pce_ctx *c, int32_t kernel, int32_t epilogue, const uint16_t *A, int64_t a_len, int64_t lda, int64_t a_batch, int32_t batch,
+                            const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, void *C, int64_t c_len, int64_t ldc, int64_t c_batch,
+                            const float *pos, int32_t pos_T, int32_t v_col0, int32_t rows_per_clip, int32_t vt_sp, uint16_t *vt, int64_t vt_len,
+                            int32_t *kernel_used)
+{
+    if (!c || !A || !B || !C || M <= 0 || N <= 0 || K <= 0 || batch <= 0 || kernel < GK_AUTO || kernel > GK_128_DEEP || epilogue < EPI_BF16 || epilogue > EPI_F32)
+        return PCE_E_INVALID;
+    const bool f32 = epilogue == EPI_GELU_POS_F32 || epilogue == EPI_RESID_F32 || epilogue == EPI_F32, qkv = epilogue == EPI_QKV;
+    const int64_t nc = qkv ? v_col0 : N;                                 // row-major output columns
+    if (lda < 1 || lda % 8 || a_batch < 0 || a_batch % 8 || ldc < nc || ldc % 8 || c_batch < 0 || c_batch % 8)
+        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): lda, a_batch, ldc, c_batch must be multiples of 8 (16-byte rows), ldc >= the output columns");
+    if ((int64_t)(batch - 1) * a_batch + (int64_t)(M - 1) * lda + K > a_len)
+        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): A holds %lld elements, the shape reads beyond them", (long long)a_len);
+    if (nc > 0 && (int64_t)(batch - 1) * c_batch + (int64_t)(M - 1) * ldc + nc > c_len)
+        return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): C holds %lld elements, the shape writes beyond them", (long long)c_len);
+    if (epilogue == EPI_GELU_POS_F32 && (!pos || pos_T < 1)) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): GELU_POS_F32 needs pos [pos_T][N]");
+    int64_t n_vt = 0;
+    if (qkv) {
+        // V columns [v_col0, N) leave as vt[clip][column - v_col0][t] (clip = row / rows_per_clip, t < rows_per_clip <= vt_sp): four rows per store
+        const int S = rows_per_clip;
+        if (!vt || batch != 1 || v_col0 < 0 || v_col0 >= N || (N - v_col0) % 64 || S < 4 || S % 4 || vt_sp < S || vt_sp % 4)
+            return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): QKV needs vt, batch 1, 0 <= v_col0 < N, rows_per_clip %% 4 == 0, rows_per_clip <= vt_sp, vt_sp %% 4 == 0");
+        n_vt = (int64_t)div_up(M, S) * (N - v_col0) * vt_sp;
+        if (n_vt > vt_len) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): vt holds %lld elements, the V image needs %lld", (long long)vt_len, (long long)n_vt);
+    }
+    const GemmShape s{M, N, K, lda, batch, qkv ? v_col0 : 0};
+    // refuse what the chosen kernel cannot compute before any allocation
+    const int kind = epilogue == EPI_BF16 ? selftest_gemm_kind<EPI_BF16>(c, kernel, s) : epilogue == EPI_GELU_BF16 ? selftest_gemm_kind<EPI_GELU_BF16>(c, kernel, s)
+                     : epilogue == EPI_GELU_POS_F32 ? selftest_gemm_kind<EPI_GELU_POS_F32>(c, kernel, s) : epilogue == EPI_RESID_F32 ? selftest_gemm_kind<EPI_RESID_F32>(c, kernel, s)
+                     : epilogue == EPI_QKV ? selftest_gemm_kind<EPI_QKV>(c, kernel, s) : selftest_gemm_kind<EPI_F32>(c, kernel, s);
+    if (kind < 0)
+        return pce_fail(c, PCE_E_LIMIT, "selftest gemm (tiled): kernel %d does not compute epilogue %d at M %d x N %d x K %d (lda %lld, batch %d, v_col0 %d)",
+                        kernel, epilogue, M, N, K, (long long)lda, batch, v_col0);
+    if (kernel_used) *kernel_used = kind;
+    PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    const size_t esz = f32 ? 4 : 2;
+    DevBuf dA, dB, dbias, dC, dpos, dvt;
+    PCE_HIP(c, dA.reserve(2 * (size_t)a_len)); PCE_HIP(c, dB.reserve(2 * (size_t)N * K)); PCE_HIP(c, dC.reserve(esz * (size_t)c_len + 16));
+    PCE_HIP(c, hipMemcpyAsync(dA.p, A, 2 * (size_t)a_len, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dB.p, B, 2 * (size_t)N * K, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dC.p, C, esz * (size_t)c_len, hipMemcpyHostToDevice, c->stream));       // (read by RESID_F32; kept where nothing is written)
+    if (bias) { PCE_HIP(c, dbias.reserve(sizeof(float) * N)); PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, sizeof(float) * N, hipMemcpyHostToDevice, c->stream)); }
+    if (epilogue == EPI_GELU_POS_F32) {
+        PCE_HIP(c, dpos.reserve(sizeof(float) * (size_t)pos_T * N));
+        PCE_HIP(c, hipMemcpyAsync(dpos.p, pos, sizeof(float) * (size_t)pos_T * N, hipMemcpyHostToDevice, c->stream));
+    }
+    if (qkv) { PCE_HIP(c, dvt.reserve(2 * (size_t)vt_len)); PCE_HIP(c, hipMemcpyAsync(dvt.p, vt, 2 * (size_t)vt_len, hipMemcpyHostToDevice, c->stream)); }
+    const op_t *a = dA.as<op_t>(), *b = dB.as<op_t>();
+    const float *bp = bias ? dbias.as<float>() : nullptr;
+    switch (epilogue) {
+    case EPI_BF16: launch_gemm_kernel<EPI_BF16>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
+    case EPI_GELU_BF16: launch_gemm_kernel<EPI_GELU_BF16>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
+    case EPI_GELU_POS_F32: launch_gemm_kernel<EPI_GELU_POS_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, dpos.as<float>(), pos_T, 0, 0); break;
+    case EPI_RESID_F32: launch_gemm_kernel<EPI_RESID_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
+    case EPI_QKV:        // (the V^T image travels in the pos argument, its clip length in pos_T: as the product launches it)
+        launch_gemm_kernel<EPI_QKV>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, reinterpret_cast<const float *>(dvt.as<op_t>()),
+                                    rows_per_clip, v_col0, vt_sp);
+        break;
+    default: launch_gemm_kernel<EPI_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
+    }
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(C, dC.p, esz * (size_t)c_len, hipMemcpyDeviceToHost, c->stream));
+    if (qkv) PCE_HIP(c, hipMemcpyAsync(vt, dvt.p, 2 * (size_t)vt_len, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    pce_profile_collect(c);
+    return PCE_OK;
+}
+
+// Self-test hook of the LayerNorm kernels (k_layernorm, k_add_layernorm) as the product launches them (launch_layernorm / launch_add_layernorm; see pce.h)
+int pce_selftest_layernorm(pce_ctx *c, int32_t form, int32_t rows, int32_t d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w,
+                           const float *b, float eps, int32_t flags, void *out, void *resid_out, uint16_t *out_copy)
+{
+    if (!c || !x || !w || !b || !out || rows <= 0 || form < 0 || form > 7) return PCE_E_INVALID;
+    if (d < 4 || d % 4 || d > LN_D_MAX) return pce_fail(c, PCE_E_LIMIT, "selftest layernorm: d = %d (need d %% 4 == 0, d <= %d)", d, LN_D_MAX);
+    PCE_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)rows * d;
+    if (form <= 1) {
+        // k_layernorm<float | op_t>; flags bit 0: round_in16, bit 1: out2 = x (in place, as the BERT layers write their fp32 stream), returned in resid_out
+        const bool in_place = flags & 2;
+        if (in_place && !resid_out) return PCE_E_INVALID;
+        DevBuf dx, dw, db, dout;
+        PCE_HIP(c, dx.reserve(sizeof(float) * n)); PCE_HIP(c, dw.reserve(sizeof(float) * d)); PCE_HIP(c, db.reserve(sizeof(float) * d));
+        PCE_HIP(c, dout.reserve((form ? 2 : 4) * n));
+        PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemsetAsync(dout.p, 0, (form ? 2 : 4) * n, c->stream));
+        float *o2 = in_place ? dx.as<float>() : nullptr;
+        if (form) launch_layernorm<op_t>(c, dx.as<float>(), dw.as<float>(), db.as<float>(), rows, d, dout.as<op_t>(), eps, o2, flags & 1);
+        else launch_layernorm<float>(c, dx.as<float>(), dw.as<float>(), db.as<float>(), rows, d, dout.as<float>(), eps, o2, flags & 1);
+        PCE_HIP(c, hipGetLastError());
+        PCE_HIP(c, hipMemcpyAsync(out, dout.p, (form ? 2 : 4) * n, hipMemcpyDeviceToHost, c->stream));
+        if (in_place) PCE_HIP(c, hipMemcpyAsync(resid_out, dx.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+        PCE_HIP(c, hipStreamSynchronize(c->stream));
+        return PCE_OK;
+    }
+    // k_add_layernorm<OUT, RIN, ROUT>: form 2 + 3 o + s, o = 0: fp32 output, 1: 16-bit output; s = 0: fp32 stream, 1: fp32 in / 16-bit out, 2: 16-bit stream.
+    // flags bit 2: write_resid
+    if (!delta) return PCE_E_INVALID;
+    const int o = (form - 2) / 3, st = (form - 2) % 3, wr = (flags >> 2) & 1;
+    if (o == 0) {
+        if (st == 0) return selftest_add_layernorm<float, float, float>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+        if (st == 1) return selftest_add_layernorm<float, float, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+        return selftest_add_layernorm<float, op_t, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+    }
+    if (st == 0) return selftest_add_layernorm<op_t, float, float>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+    if (st == 1) return selftest_add_layernorm<op_t, float, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+    return selftest_add_layernorm<op_t, op_t, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+}
+
+} // extern "C"

@@ -121,11 +121,14 @@ def test_encoder_with_the_fp16_residual_stream(engine, clips, dims):
         assert np.linalg.norm(a - b) / np.linalg.norm(a) <= 1.5e-3
 
 
-@pytest.mark.parametrize("width,heads", [(128, 2), (768, 12)])
-def test_forced_alignment_matches_torch(engine, clips, width, heads):
+@pytest.mark.parametrize("width,heads,mask_layers", [(128, 2, None), (768, 12, None), (128, 2, (0, 2))],
+                         ids=["128-2", "768-12", "128-2-no_head_in_the_last_layer"])
+def test_forced_alignment_matches_torch(engine, clips, width, heads, mask_layers):
     """Teacher-forced decoder + cross-attention alignment (openai-whisper find_alignment up to the DTW path).
     The cost matrix agrees with the torch fp32 restatement within bf16 tolerance; the GPU DTW path is EXACTLY the
-    CPU recurrence's path on the GPU's own cost matrix (alignment indices bit-exact given identical costs)."""
+    CPU recurrence's path on the GPU's own cost matrix (alignment indices bit-exact given identical costs).
+    mask_layers: a head mask of every head of these layers instead of the default (the upper half): with (0, 2) the last
+    layer, which ends at its alignment scores, and a middle one launch none (as many heads as the default averages)."""
     edims = dict(n_mels=80, n_ctx=1500, n_state=width, n_head=heads, n_layer=2)
     tdims = dict(n_vocab=300, n_text_ctx=96, n_state=width, n_head=heads, n_layer=4)     # 768: the width of "small" (wide cross K/V GEMM)
     We, Wd = WW.synthetic_weights(edims), WW.synthetic_decoder_weights(tdims)
@@ -139,10 +142,13 @@ def test_forced_alignment_matches_torch(engine, clips, width, heads):
     sot_len = 3
     toks = [rng.integers(0, 300, size=n).tolist() for n in (37, 70)]
     num_frames = [len(c) // 160 for c in use]                      # mel frames of the real audio
-    res = engine.whisper_align(toks, num_frames, sot_len, want_cost=True)
+    hm = None
+    if mask_layers is not None:
+        hm = np.zeros((tdims["n_layer"], heads), dtype=bool); hm[list(mask_layers)] = True
+    res = engine.whisper_align(toks, num_frames, sot_len, head_mask=hm, want_cost=True)
     for i in range(2):
         enc = engine.whisper_encode_fetch(i)                       # same audio features for both sides
-        cost, ti, tj = WO.find_alignment(toks[i], enc, Wd, tdims, num_frames[i], sot_len)
+        cost, ti, tj = WO.find_alignment(toks[i], enc, Wd, tdims, num_frames[i], sot_len, head_mask=hm)
         got = res[i]
         assert got["cost"].shape == cost.shape == (len(toks[i]) - sot_len - 1, num_frames[i] // 2)
         assert np.max(np.abs(got["cost"] - cost)) <= 0.08                                    # observed 0.035 at std 0.4
@@ -156,7 +162,7 @@ def test_forced_alignment_matches_torch(engine, clips, width, heads):
         assert len(jumps_g) == len(jumps_w) and np.mean(np.abs(jumps_g - jumps_w) <= 1) >= 0.95          # observed: identical
     # the batched asynchronous fetch (pce_whisper_align_paths_enqueue / _wait: what a batch pipeline and bench.py's timed step use) hands over
     # the same indices as the clip-by-clip fetch; two slots in flight; a wait without an enqueue is an error
-    engine.whisper_align_run(toks, num_frames, sot_len)
+    engine.whisper_align_run(toks, num_frames, sot_len, head_mask=hm)
     engine.whisper_align_paths_enqueue(0); engine.whisper_align_paths_enqueue(1)
     for slot in (1, 0):
         pl, pi, pj = engine.whisper_align_paths_wait(slot)
