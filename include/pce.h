@@ -54,9 +54,11 @@ extern "C" {
  * 7 = pce_intensity_plan / _run / _fetch (Praat's Sound_to_Intensity over slices, with per-slice summaries) and their two kernel ids;
  * 8 = pce_selftest_attn1 (the single-query attention kernels of a decoding step) and pce_selftest_attention_ragged; pce_selftest_attention launches
  * through the product's rule (one query block: the streaming instantiation);
- * 9 = pce_silence_run / _shape / _fetch (pydub's detect_silence over slices, exact integers) and their three kernel ids. */
+ * 9 = pce_silence_run / _shape / _fetch (pydub's detect_silence over slices, exact integers) and their three kernel ids;
+ * 10 = pce_seqmatch / pce_seqmatch_align (difflib.SequenceMatcher's matched totals for batches of string pairs, and the fuzzy alignment of
+ * "Compare Breaks" on them) and their two kernel ids. */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 9
+#define PCE_API_MINOR 10
 
 typedef struct pce_ctx pce_ctx;
 
@@ -553,6 +555,48 @@ int pce_nw_align(pce_ctx *ctx, const int32_t *a_ids, const int64_t *a_off, const
 int pce_levenshtein(pce_ctx *ctx, const uint32_t *a_chars, const int64_t *a_off, const uint32_t *b_chars, const int64_t *b_off,
                     int32_t batch, int32_t *out_dist);
 
+/* ---- batched difflib.SequenceMatcher and the fuzzy alignment of "Compare Breaks" -------------
+ * sim() of Code/audioPipeline.py:970-971 is difflib.SequenceMatcher(None, a, b).ratio() = 2.0 * matches / (len(a) + len(b)) (1.0 for two
+ * empty strings); pce_seqmatch returns `matches`, the summed sizes of get_matching_blocks, for pairs of strings of Unicode code points (any
+ * uint32 values; equal values = equal elements).  The rules, with isjunk = None:
+ *   popular    with autojunk != 0 and len(b) >= 200, an element that occurs more than len(b) / 100 + 1 times in b is popular: it never
+ *              starts or continues a run of find_longest_match, but it is not junk: the extension runs over it;
+ *   longest    find_longest_match(alo, ahi, blo, bhi): over i in [alo, ahi) ascending and the non-popular j in [blo, bhi) with
+ *              b[j] == a[i] ascending, k = len[i-1][j-1] + 1, a run never continuing across blo; the best run is replaced on k > best
+ *              only, so the winner has the largest k, then the smallest start in a, then the smallest start in b (k = 0: (alo, blo));
+ *   extension  left while i > alo, j > blo and a[i-1] == b[j-1], then right in the same way within ahi / bhi (moves only where popular
+ *              elements exist);
+ *   blocks     a LIFO stack that starts with (0, la, 0, lb): pop a range, find its longest match; k > 0 adds k to `matches` and pushes
+ *              (alo, i, blo, j) when alo < i and blo < j, then (i + k, ahi, j + k, bhi) when i + k < ahi and j + k < bhi.
+ * Integer arithmetic: `matches` is exactly difflib's.  String s of a table is chars[off[s] .. off[s+1]), off[0] = 0.  Pair p compares string
+ * pair_a[p] of the a table with string pair_b[p] of the b table; pair_a == pair_b == NULL: all n_a * n_b pairs, row-major (pair i * n_b + j =
+ * a string i with b string j; n_pairs must equal n_a * n_b).  The result is not symmetric in a and b (difflib's is not).
+ * Limits (PCE_E_LIMIT): a string has fewer than 2^30 elements, a call at most PCE_SEQMATCH_MAX_PAIRS pairs, and the scratch of one
+ * workgroup of 4 waves -- per wave 4 bytes per element of the longest b string when that is longer than PCE_SEQMATCH_ROW_LDS, and 16 bytes
+ * per stack entry, min(longest a, longest b) + 1 of them -- at most PCE_SEQMATCH_SCRATCH_MAX bytes, which strings of up to 2^23 elements
+ * always meet.  PCE_E_INVALID: NULL or decreasing offsets, a pair index outside its table.  A range of b of up to PCE_SEQMATCH_ROW_LDS columns is swept with its row of run
+ * lengths in LDS, a wider one through a global row; the stack holds PCE_SEQMATCH_STACK_LDS ranges in LDS and spills the rest: neither is a
+ * limit, and a pair's result depends on its two strings only.
+ *
+ * pce_seqmatch_align: all pairs, then the alignment of Code/audioPipeline.py:973-998 on the device: sim[i][j] = 2.0 * matches / (la_i + lb_j)
+ * in fp64 (1.0 for two empty strings); dp[0][.] = dp[.][0] = 0; match = dp[i-1][j-1] + sim[i-1][j-1]; dp[i][j] = dp[i-1][j] (up) if
+ * dp[i-1][j] >= dp[i][j-1] and dp[i-1][j] >= match, else dp[i][j-1] (left) if dp[i][j-1] >= match, else match (diagonal).  The walk back from
+ * (n_a, n_b) ends when i == 0 or j == 0; its diagonal steps (i-1, j-1), ascending, are match_a / match_b (room min(n_a, n_b)), *n_matches
+ * their count.  sim: [n_a * n_b] row-major or NULL.  fp64 multiply, divide, add and compare only: bit-identical to the Python lines.
+ * n_a == 0 or n_b == 0: PCE_OK with *n_matches = 0.  n_a * n_b > PCE_SEQMATCH_MAX_PAIRS: PCE_E_LIMIT.  Any number of rows.  Since minor 10. */
+#define PCE_SEQMATCH_MAX_PAIRS ((int64_t)1 << 26)
+#define PCE_SEQMATCH_ROW_LDS 2048
+#define PCE_SEQMATCH_SCRATCH_MAX ((int64_t)1 << 30)
+#define PCE_SEQMATCH_STACK_LDS 8
+/* pairs (pair_a[p], pair_b[p]) of the two string tables; pair_a == pair_b == NULL: all n_a * n_b pairs, row-major (n_pairs must equal n_a * n_b) */
+int pce_seqmatch(pce_ctx *ctx, const uint32_t *a_chars, const int64_t *a_off, int32_t n_a,
+                 const uint32_t *b_chars, const int64_t *b_off, int32_t n_b,
+                 const int32_t *pair_a, const int32_t *pair_b, int64_t n_pairs, int32_t autojunk, int32_t *out_matches);
+/* all pairs + the DP of Code/audioPipeline.py:973-998; sim: [n_a * n_b] or NULL; match_a / match_b: [min(n_a, n_b)] */
+int pce_seqmatch_align(pce_ctx *ctx, const uint32_t *a_chars, const int64_t *a_off, int32_t n_a,
+                       const uint32_t *b_chars, const int64_t *b_off, int32_t n_b, int32_t autojunk,
+                       double *sim, int32_t *match_a, int32_t *match_b, int32_t *n_matches);
+
 /* ---- break-prediction token classifier --------------------
  * Forward pass of transformers.BertForTokenClassification, the model Code/baseline_models/pause_bert.py:127-132 trains
  * (bert-base-multilingual-uncased, num_labels = 2, MAX_LENGTH = 128; the reference has training code only: this is the
@@ -600,7 +644,9 @@ enum pce_kernel_id {
     /* minor 7 */
     PCE_K_INTENSITY, PCE_K_INTENSITY_SUMMARY,
     /* minor 9: PCE_K_SILENCE_RANGES brackets three launches (tiles, carry, tiles with the carry) */
-    PCE_K_MS_ENERGY, PCE_K_SILENCE_SCAN, PCE_K_SILENCE_RANGES, PCE_K_COUNT
+    PCE_K_MS_ENERGY, PCE_K_SILENCE_SCAN, PCE_K_SILENCE_RANGES,
+    /* minor 10: their work count is swept CELLS (k_seqmatch: every range of every pair, recursion included; k_seqmatch_align: n_a * n_b) */
+    PCE_K_SEQMATCH, PCE_K_SEQMATCH_ALIGN, PCE_K_COUNT
 };
 int pce_profile_enable(pce_ctx *ctx, int on);
 int pce_profile_reset(pce_ctx *ctx);

@@ -12,7 +12,9 @@ The two Whisper steps (``"Align+Transcribe"``, ``"Final Transcribe"``, :179-241 
 aligner of :mod:`.Aligners.use_whisper_timestamped` and leave the reference's folders.  Steps that are not on the hot
 path (demucs, Azure synthesis, JSON export, break comparison: SURVEY.md section 8 marks them out of scope) are not
 reimplemented: ``run()`` skips them with a warning unless ``strict_steps: true`` is set (additive config key), in
-which case selecting one fails at construction.
+which case selecting one fails at construction.  ``"Compare Breaks"`` (:895-1074) is the exception: it needs neither Azure nor
+Demucs, :mod:`.break_check` runs it with its alignment on the device, and ``run()`` dispatches it when the additive key
+``compare_breaks_on_device: true`` is set (without the key it is skipped as before).
 """
 from __future__ import annotations
 
@@ -33,6 +35,7 @@ from .textgrid_io import read_textgrid
 STEP_NAMES = ["Preprocess", "Align+Transcribe", "Raw Synthesis", "Measure & Build SSML", "Synthesize+Merge",
               "Export JSON", "Final Transcribe", "Compare Breaks"]                    # Code/audioPipeline.py:1077-1086
 ACCELERATED_STEPS = ("Align+Transcribe", "Measure & Build SSML", "Final Transcribe")
+OPT_IN_STEPS = {"Compare Breaks": "compare_breaks_on_device"}                         # step -> the additive config key that makes run() dispatch it
 
 
 class BatchedMeasurements:
@@ -319,7 +322,7 @@ class AudioPipeline:
         unknown = [n for n in wanted if n not in STEP_NAMES]
         if unknown:
             raise ValueError(f"steps_to_run names unknown steps {unknown}; known: {STEP_NAMES}")
-        outside = [n for n in wanted if n not in ACCELERATED_STEPS]
+        outside = [n for n in wanted if n not in ACCELERATED_STEPS and not cfg.get(OPT_IN_STEPS.get(n, ""))]
         if outside and cfg.get("strict_steps"):
             raise NotImplementedError(f"steps {outside} are outside the accelerated hot path (SURVEY.md section 8): run them with the "
                                       "reference implementation, or drop strict_steps to skip them")
@@ -459,6 +462,20 @@ class AudioPipeline:
                     txt.rename(self.results_dir / txt.name)
         logging.info(f"Final transcription files saved in {self.results_dir}")
 
+    # ------------------------------------------------------------------ the pipeline's own check of the synthesised pauses
+    def compare_breaks(self, tol_ms: int = 5):
+        """Code/audioPipeline.py:895-1074: ``OUT.TextGrid`` against ``BDD_syntagme_for_synth.csv`` -> ``pause_comparison_full.csv`` in the
+        results folder, the n x m fuzzy ratios and the alignment DP in one device call (:mod:`.break_check`).  One voice is one small
+        problem: rank 0 runs it and returns the table, the other ranks wait and return None."""
+        logging.info(">>> Compare Breaks")
+        from . import break_check, shard
+        res = None
+        with shard.agreed(only_rank=0) as sec:
+            if sec.mine:
+                res = break_check.compare_breaks(self.results_dir / "OUT.TextGrid", self.bdd_syntagme_synth_csv,
+                                                 self.results_dir / "pause_comparison_full.csv", tol_ms=tol_ms, engine=self._get_engine())
+        return res
+
     # ------------------------------------------------------------------ break prediction (BASELINE.json configs[4]: additive, not a reference step)
     def predict_breaks(self, word_piecer=None, weights=None, dims=None, cls_id: int = 101, sep_id: int = 102):
         """Break prediction for every segment of the voice with the token classifier the reference trains
@@ -535,6 +552,8 @@ class AudioPipeline:
         ``used_config.yaml`` in the results folder.  Steps outside the hot path are skipped with a warning."""
         steps = {"Align+Transcribe": self.align_and_transcribe, "Measure & Build SSML": self.measure_prosody_and_build_ssml,
                  "Final Transcribe": self.final_transcribe}
+        if self.cfg.get(OPT_IN_STEPS["Compare Breaks"]):
+            steps["Compare Breaks"] = self.compare_breaks
         wanted = self.cfg.get("steps_to_run") or STEP_NAMES
         for n in [n for n in STEP_NAMES if n in wanted]:
             if n not in steps:

@@ -353,7 +353,7 @@ const char *pce_kernel_name(int id)
         "k_add_layernorm", "k_stft_raw", "k_logmel_norm", "k_attention_lean",
         "k_gemm_flat:qkv", "k_gemm_flat:out", "k_gemm_flat:fc1", "k_gemm_flat:fc2", "k_gemm_flat:xkv",
         "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace", "k_intensity", "k_intensity_summary",
-        "k_ms_energy", "k_silence_scan", "k_silence_ranges"};
+        "k_ms_energy", "k_silence_scan", "k_silence_ranges", "k_seqmatch", "k_seqmatch_align"};
     return (id >= 0 && id < PCE_K_COUNT) ? names[id] : "?";
 }
 

@@ -125,7 +125,7 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "k_add_layernorm", "k_stft_raw", "k_logmel_norm", "k_attention_lean",
               "k_gemm_flat:qkv", "k_gemm_flat:out", "k_gemm_flat:fc1", "k_gemm_flat:fc2", "k_gemm_flat:xkv",
               "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace",
-              "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
+              "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges", "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
 # every symbol include/pce.h declares
 EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_version", "pce_api_minor", "pce_device_info",
@@ -137,7 +137,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_silence_run", "pce_silence_shape", "pce_silence_fetch",
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
-           "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
+           "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
            "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
@@ -184,6 +184,8 @@ def load_library() -> C.CDLL:
     lib.pce_stats_enqueue.argtypes = [vp, i32]
     lib.pce_nw_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.pce_levenshtein.argtypes = [vp, vp, vp, vp, vp, i32, vp]
+    lib.pce_seqmatch.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i64, i32, vp]
+    lib.pce_seqmatch_align.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, C.POINTER(i32)]
     lib.pce_stats_wait.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.pce_stft_db_run.argtypes = [vp, i32, i32]
     lib.pce_stft_db_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -969,6 +971,59 @@ class ProsodyEngine:
         self._check(self._lib.pce_levenshtein(self._ctx, a.ctypes.data if a.size else None, ao.ctypes.data, b.ctypes.data if b.size else None,
                                               bo.ctypes.data, len(pairs), out.ctypes.data))
         return out
+
+    @staticmethod
+    def _pack_strings(strings):
+        """``str`` list -> (code points uint32, offsets int64 [n + 1]), as ``levenshtein`` packs its strings."""
+        cps = [np.frombuffer(s.encode("utf-32-le", "surrogatepass"), dtype=np.uint32) for s in strings]
+        off = np.zeros(len(cps) + 1, dtype=np.int64); np.cumsum([len(x) for x in cps], out=off[1:])
+        return np.ascontiguousarray(np.concatenate(cps + [np.zeros(0, np.uint32)])), off
+
+    def _seqmatch(self, a, b, pairs, autojunk):
+        ac, ao = self._pack_strings(a); bc, bo = self._pack_strings(b)
+        if pairs is None:
+            pa = pb = None; n = len(a) * len(b)
+        else:
+            pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            if pr.size and (pr.min() < -2 ** 31 or pr.max() >= 2 ** 31):
+                raise ValueError("pair indices do not fit int32")
+            pa = np.ascontiguousarray(pr[:, 0], dtype=np.int32); pb = np.ascontiguousarray(pr[:, 1], dtype=np.int32); n = len(pr)
+        out = np.zeros(n, dtype=np.int32)
+        self._check(self._lib.pce_seqmatch(self._ctx, ac.ctypes.data if ac.size else None, ao.ctypes.data, len(a), bc.ctypes.data if bc.size else None,
+                                           bo.ctypes.data, len(b), pa.ctypes.data if pa is not None else None, pb.ctypes.data if pb is not None else None,
+                                           n, 1 if autojunk else 0, out.ctypes.data))
+        la, lb = np.diff(ao), np.diff(bo)
+        total = (la[:, None] + lb[None, :]).reshape(-1) if pairs is None else la[pa] + lb[pb]
+        return out, total
+
+    def seqmatch_matches(self, a, b, pairs=None, autojunk=True):
+        """``sum(block.size for block in difflib.SequenceMatcher(None, a[i], b[j], autojunk).get_matching_blocks())`` in one launch
+        (``pce_seqmatch``): ``a`` / ``b`` lists of ``str``; ``pairs`` = [(i, j), ...] or None for all ``len(a) * len(b)`` pairs, row-major
+        -> int32 array.  Elements are code points."""
+        return self._seqmatch(a, b, pairs, autojunk)[0]
+
+    def seqmatch_ratio(self, a, b, pairs=None, autojunk=True):
+        """``SequenceMatcher(None, a[i], b[j], autojunk).ratio()`` per pair -> float64 array, bit-identical: ``2.0 * matches / length``
+        (difflib's ``_calculate_ratio``), 1.0 where both strings are empty."""
+        m, total = self._seqmatch(a, b, pairs, autojunk)
+        out = np.ones(len(m), dtype=np.float64)
+        nz = total > 0
+        out[nz] = 2.0 * m[nz].astype(np.float64) / total[nz].astype(np.float64)
+        return out
+
+    def seqmatch_align(self, a, b, autojunk=True):
+        """The fuzzy alignment of "Compare Breaks" (Code/audioPipeline.py:970-998) in one call (``pce_seqmatch_align``): all
+        ``len(a) x len(b)`` ratios and the DP over them on the device -> (matches int32 [k, 2] of (index in a, index in b), ascending;
+        sim float64 [len(a), len(b)])."""
+        n, m = len(a), len(b)
+        ac, ao = self._pack_strings(a); bc, bo = self._pack_strings(b)
+        sim = np.zeros((n, m), dtype=np.float64)
+        k_max = max(min(n, m), 1)
+        ma = np.zeros(k_max, dtype=np.int32); mb = np.zeros(k_max, dtype=np.int32); k = C.c_int32()
+        self._check(self._lib.pce_seqmatch_align(self._ctx, ac.ctypes.data if ac.size else None, ao.ctypes.data, n, bc.ctypes.data if bc.size else None,
+                                                 bo.ctypes.data, m, 1 if autojunk else 0, sim.ctypes.data if sim.size else None, ma.ctypes.data,
+                                                 mb.ctypes.data, C.byref(k)))
+        return np.stack([ma[:k.value], mb[:k.value]], axis=1), sim
 
     def nw_align(self, pairs, match=1, mismatch=-1, gap=-1):
         """Batched Needleman-Wunsch over integer token ids: ``pairs`` = [(ids_a, ids_b), ...] ->
