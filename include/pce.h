@@ -56,9 +56,10 @@ extern "C" {
  * through the product's rule (one query block: the streaming instantiation);
  * 9 = pce_silence_run / _shape / _fetch (pydub's detect_silence over slices, exact integers) and their three kernel ids;
  * 10 = pce_seqmatch / pce_seqmatch_align (difflib.SequenceMatcher's matched totals for batches of string pairs, and the fuzzy alignment of
- * "Compare Breaks" on them) and their two kernel ids. */
+ * "Compare Breaks" on them) and their two kernel ids;
+ * 11 = pce_whisper_detect_language (openai-whisper's detect_language for the encoded batch: the language rows of the output projection only). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 10
+#define PCE_API_MINOR 11
 
 typedef struct pce_ctx pce_ctx;
 
@@ -502,6 +503,23 @@ int pce_whisper_decode_loop(pce_ctx *ctx, const int32_t *tokens, const int32_t *
                             const pce_whisper_decode_rules *rules, const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts,
                             int32_t max_new, int32_t check_every, int32_t *out_tokens, float *out_logprobs /* or NULL */,
                             int32_t *out_steps, float *probe_prob /* [clips] or NULL */);
+
+/* openai-whisper decoding.py detect_language for every clip of the encoded batch (what whisper.transcribe runs on the first 30 s window when no
+ * language is given): the text decoder over the single token `sot` (<|startoftranscript|>), the logits of that position on the language tokens
+ * alone -- every other token counts as -inf -- their softmax and the arg-max (first maximum).  Language tokens are the contiguous ids
+ * lang_begin .. lang_begin + n_lang - 1 (lang_begin = sot + 1; n_lang = 99 for n_vocab 51 865, 100 for 51 866; 1..128 here).
+ * ids[clips]: the winning token ids; probs[clips][n_lang]: the probabilities in id order (either may be NULL).  A clip's results do not depend on
+ * what it is batched with.
+ * Cost: one prefix pass of the decoder over one position per clip (and, at the first decoding call after pce_whisper_encode_run, the cross-attention
+ * K / V of all layers, which are kept for the calls that follow), then n_lang rows of the tied output projection instead of n_vocab: no logits over
+ * the vocabulary are formed.
+ * Cache: the pass leaves position 0 of every clip's self-attention K / V cache filled for `sot`, and the record of what the cache holds is dropped:
+ * the next pce_whisper_decode_step* / pce_whisper_decode_loop runs its prompts through the prefix pass, exactly as after a fresh
+ * pce_whisper_encode_run, and returns the same bits as if this call had not been made.
+ * PCE_E_STATE before pce_whisper_decoder_load or pce_whisper_encode_run; PCE_E_INVALID for n_lang < 1, n_lang > 128, or a token range that leaves
+ * [0, n_vocab) (a vocabulary without language tokens has nothing to pass here: that is the caller's error to raise). */
+int pce_whisper_detect_language(pce_ctx *ctx, int32_t sot, int32_t lang_begin, int32_t n_lang, int32_t *ids /* [clips] or NULL */,
+                                float *probs /* [clips][n_lang] or NULL */);
 
 /* ---- R8: dynamic time warping (alignment indices) ------------------------
  * The DTW of openai-whisper's timing.py (dtw_cpu) that whisper_timestamped's word alignment rests on

@@ -192,7 +192,7 @@ def load_model(model_size: str, model_dir: Optional[str] = None) -> WhisperModel
     return WhisperModel(enc, dec, heads, name=model_size)
 
 
-def load_tokenizer(model_dir: Optional[str] = None, language: str = "fr", n_vocab: Optional[int] = None):
+def load_tokenizer(model_dir: Optional[str] = None, language: Optional[str] = "fr", n_vocab: Optional[int] = None):
     from .tokenizer import WhisperTokenizer
     model_dir = model_dir or os.environ.get("PCE_WHISPER_DIR")
     path = os.path.join(model_dir or "", "multilingual.tiktoken")

@@ -105,6 +105,21 @@ def no_speech_probs(engine, n_vocab: int, prompts, sot_index, rules: dict, no_sp
     return np.asarray(probe, dtype=np.float64)
 
 
+def detect_language(engine, tokenizer):
+    """decoding.py ``detect_language`` for every clip the engine has encoded (``whisper_encode_run``): the decoder over
+    <|startoftranscript|> alone, every token that is no language token masked, arg-max and softmax
+    (``ProsodyEngine.whisper_detect_language``: the language rows of the output projection only).
+    -> (language code per clip, {code: probability} per clip).  The next decoding call is not affected."""
+    if tokenizer.num_languages == 0 or not tokenizer.all_language_tokens:
+        raise ValueError("This model doesn't have language tokens so it can't perform lang id")
+    lang_tokens, codes = tokenizer.all_language_tokens, tokenizer.all_language_codes
+    if list(lang_tokens) != list(range(tokenizer.sot + 1, tokenizer.sot + 1 + len(lang_tokens))):
+        raise ValueError("language tokens must be the contiguous ids after <|startoftranscript|>")
+    ids, probs = engine.whisper_detect_language(tokenizer.sot, lang_tokens[0], len(lang_tokens))
+    detected = [codes[int(t) - lang_tokens[0]] for t in ids]
+    return detected, [{c: float(p) for c, p in zip(codes, row)} for row in np.asarray(probs)]
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # Windows of a long recording: the seek logic of whisper.transcribe (openai-whisper transcribe.py, restated; the
 # package is absent: parity unpinned, hand-made cases in tests/test_decoding_host.py)

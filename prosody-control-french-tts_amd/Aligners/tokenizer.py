@@ -82,6 +82,16 @@ class WhisperTokenizer:
         """<|startoftranscript|><|lang|><|task|> (tokenizer.py ``sot_sequence`` for a multilingual model)."""
         return (self.sot, self.language_token(language), self.transcribe if (task or self.task) == "transcribe" else self.translate)
 
+    @property
+    def all_language_tokens(self) -> Tuple[int, ...]:
+        """tokenizer.py ``all_language_tokens``: the contiguous ids ``sot + 1 .. sot + num_languages``, in ``LANGUAGES`` order."""
+        return tuple(self.special[f"<|{lang}|>"] for lang in LANGUAGES[:self.num_languages])
+
+    @property
+    def all_language_codes(self) -> Tuple[str, ...]:
+        """tokenizer.py ``all_language_codes``: the code of every entry of ``all_language_tokens``."""
+        return tuple(LANGUAGES[:self.num_languages])
+
     # ------------------------------------------------------------------ ids -> text
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
         return b"".join(self.id_to_bytes[t] for t in tokens if t < len(self.id_to_bytes))
@@ -185,7 +195,8 @@ class WhisperTokenizer:
                 word_tokens[-1].extend(st)
         return words, word_tokens
 
-    def split_to_word_tokens(self, tokens: Sequence[int]):
-        if self.language in {"zh", "ja", "th", "lo", "my", "yue"}:
+    def split_to_word_tokens(self, tokens: Sequence[int], language: str = None):
+        """``language``: the language of THESE tokens when it is not the tokenizer's own (a detected one, per clip)."""
+        if (language or self.language) in {"zh", "ja", "th", "lo", "my", "yue"}:
             return self.split_tokens_on_unicode(tokens)
         return self.split_tokens_on_spaces(tokens)

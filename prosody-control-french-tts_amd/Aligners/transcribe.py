@@ -45,7 +45,7 @@ APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
 
 @dataclass
 class TranscribeOptions:
-    language: str = "fr"
+    language: Optional[str] = "fr"         # None: detected per clip on its first window (decoding.py detect_language), as whisper.transcribe does
     vad: Optional[str] = "auditok"
     compute_word_confidence: bool = True
     detect_disfluencies: bool = True
@@ -177,10 +177,10 @@ def merge_punctuations(words: List[dict], prepended: str = PREPEND_PUNCTUATIONS,
         j += 1
 
 
-def words_from_path(tokenizer, text_tokens: List[int], token_logprobs: List[float], text_indices, time_indices) -> List[dict]:
+def words_from_path(tokenizer, text_tokens: List[int], token_logprobs: List[float], text_indices, time_indices, language: Optional[str] = None) -> List[dict]:
     """The tail of timing.py ``find_alignment``: DTW path over (text tokens + end-of-text) x frames -> words with
-    start / end on the window's own timeline."""
-    words, word_tokens = tokenizer.split_to_word_tokens(list(text_tokens) + [tokenizer.eot])
+    start / end on the window's own timeline.  ``language``: the clip's own when it is not the tokenizer's (a detected one)."""
+    words, word_tokens = tokenizer.split_to_word_tokens(list(text_tokens) + [tokenizer.eot], language)
     if len(word_tokens) <= 1:
         return []
     text_indices, time_indices = np.asarray(text_indices), np.asarray(time_indices)
@@ -206,7 +206,11 @@ def transcribe_batch(engine, model, tokenizer, clips: Sequence[np.ndarray], opti
     """Transcribe every clip (int16, 16 kHz mono) -> one ``whisper_timestamped`` result dict per clip:
     ``{"text", "segments": [{"id", "seek", "start", "end", "text", "tokens", "temperature", "avg_logprob",
     "compression_ratio", "no_speech_prob", "confidence", "words": [{"text", "start", "end", "confidence"}]}], "language"}``.
-    ``model``: ``checkpoint.WhisperModel`` already loaded into ``engine``."""
+    ``model``: ``checkpoint.WhisperModel`` already loaded into ``engine``.
+    ``options.language`` None: every clip's language is detected once, on its first window and before the first decoding call
+    (``decoding.detect_language`` on the batch that window's encoder run has left: no further encoder run); the clip's prompts, its word
+    splitting and its ``result["language"]`` follow its own code, and clips of different languages share the batch.  (A batch in which no clip
+    has any audio never reaches the encoder: its results keep ``"language": None``.)"""
     opt = options or TranscribeOptions()
     log = logger or logging.getLogger(__name__)
     n = len(clips)
@@ -232,7 +236,9 @@ def transcribe_batch(engine, model, tokenizer, clips: Sequence[np.ndarray], opti
     n_text_ctx = model.text_dims["n_text_ctx"]
     sample_len = opt.sample_len or n_text_ctx // 2
     rules = tokenizer.decoding_rules()
-    sot_seq = list(tokenizer.sot_sequence(opt.language))
+    # one start sequence per clip (all of one length: <|startoftranscript|><|lang|><|task|>); with a language to detect they are filled in at the first window
+    langs: Optional[List[str]] = [opt.language] * n if opt.language is not None else None
+    sot_seqs = [list(tokenizer.sot_sequence(opt.language))] * n if langs is not None else None
     content = [len(a) // HOP for a in audio]                                # mel frames of content per clip
     seeks = [0] * n
     clip_ids = [zlib.crc32(np.ascontiguousarray(a, dtype=np.int16).tobytes()) for a in audio]      # (what names a recording: its samples)
@@ -245,15 +251,20 @@ def transcribe_batch(engine, model, tokenizer, clips: Sequence[np.ndarray], opti
             break
         engine.logmel_run_at(n_mels, [min(seeks[i], content[i]) for i in range(n)])
         engine.whisper_encode_run()
+        if langs is None:
+            langs, _ = DEC.detect_language(engine, tokenizer)
+            sot_seqs = [list(tokenizer.sot_sequence(code)) for code in langs]
+            for i in range(n):
+                results[i]["language"] = langs[i]
         # prompts: <|startofprev|> + the tail of the previous text + the sot sequence (DecodingTask._get_initial_tokens)
         prompts, sot_index = [], []
         for i in range(n):
             prev = all_tokens[i][prompt_reset[i]:] if (opt.condition_on_previous_text and active[i]) else []
             if prev:
                 prev = prev[-(n_text_ctx // 2 - 1):]
-                prompts.append([tokenizer.sot_prev] + prev + sot_seq); sot_index.append(1 + len(prev))
+                prompts.append([tokenizer.sot_prev] + prev + sot_seqs[i]); sot_index.append(1 + len(prev))
             else:
-                prompts.append(list(sot_seq)); sot_index.append(0)
+                prompts.append(list(sot_seqs[i])); sot_index.append(0)
         begins = [len(p) for p in prompts]
         nsp = (DEC.no_speech_probs(engine, n_vocab, prompts, sot_index, rules, tokenizer.no_speech)
                if opt.no_speech_threshold is not None else np.zeros(n))
@@ -290,7 +301,7 @@ def transcribe_batch(engine, model, tokenizer, clips: Sequence[np.ndarray], opti
         align_frames: List[int] = []
         for i in range(n):
             seg_size = min(N_FRAMES, max(content[i] - seeks[i], 0))
-            minimal = sot_seq + [tokenizer.no_timestamps, tokenizer.eot]
+            minimal = sot_seqs[i] + [tokenizer.no_timestamps, tokenizer.eot]
             if not active[i]:
                 align_tokens.append(minimal); align_frames.append(64); continue
             r = final[i]
@@ -317,7 +328,7 @@ def transcribe_batch(engine, model, tokenizer, clips: Sequence[np.ndarray], opti
             for sg in segs:
                 sg["_window"] = (seeks[i], seg_size)
             if text_tokens:
-                align_tokens.append(sot_seq + [tokenizer.no_timestamps] + text_tokens + [tokenizer.eot]); align_frames.append(max(seg_size, 2))
+                align_tokens.append(sot_seqs[i] + [tokenizer.no_timestamps] + text_tokens + [tokenizer.eot]); align_frames.append(max(seg_size, 2))
                 win_segments[i][0]["_align"] = (text_tokens, text_lps)
             else:
                 align_tokens.append(minimal); align_frames.append(64)
@@ -327,13 +338,14 @@ def transcribe_batch(engine, model, tokenizer, clips: Sequence[np.ndarray], opti
             seeks[i] = new_seek
         # ---- 3. forced alignment of every clip's window text in one pass
         if any("_align" in s[0] for s in win_segments if s):
-            paths = engine.whisper_align(align_tokens, align_frames, len(sot_seq), head_mask=model.alignment_heads)
+            paths = engine.whisper_align(align_tokens, align_frames, len(sot_seqs[0]), head_mask=model.alignment_heads)
             for i in range(n):
                 segs = win_segments[i]
                 if not segs or "_align" not in segs[0]:
                     continue
                 text_tokens, text_lps = segs[0].pop("_align")
-                words = words_from_path(tokenizer, text_tokens, text_lps, paths[i]["text_indices"], paths[i]["time_indices"])
+                words = words_from_path(tokenizer, text_tokens, text_lps, paths[i]["text_indices"], paths[i]["time_indices"],
+                                        None if opt.language is not None else langs[i])
                 merge_punctuations(words)
                 offset = segs[0]["_window"][0] * HOP / SAMPLE_RATE
                 wi = 0

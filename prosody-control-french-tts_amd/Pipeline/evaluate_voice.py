@@ -15,7 +15,9 @@ restatements are checked against independent Python restatements in tests/test_e
 * F0: the notebook's TEXT names ``librosa.pyin`` (hop 512), its CODE calls torchcrepe (``model="full"``, periodicity threshold 0.1), a neural
   pitch tracker whose weights are not available.  This module builds the first, on the engine's probabilistic YIN (``pce_pyin_*``), so
   **the RMSE values printed in the notebook are not expected to be reproduced**; F1 and WER depend on the Whisper checkpoint only.
-* Language detection is not built: ``model.transcribe(path)`` detects the language, here it is an argument (default ``"fr"``).
+* Language: the notebook's ``model.transcribe(path)`` detects it; here it is an argument whose default stays ``"fr"``, and ``language=None``
+  detects it per recording as openai-whisper's ``detect_language`` does on the first 30 s window (``Aligners.decoding.detect_language`` ->
+  ``pce_whisper_detect_language``; pinned to the ``transformers`` forward by tests/golden/whisper_langid_tiny.npz in tests/test_gpu_langid.py).
 * No plotting and no ``compare_episode`` HTML diff.
 """
 from __future__ import annotations
@@ -244,7 +246,9 @@ class WhisperHandle:
         self.model, self.tokenizer = model, tokenizer
 
     @classmethod
-    def load(cls, engine, model_size: str = "large-v3", model_dir: Optional[str] = None, language: str = "fr"):
+    def load(cls, engine, model_size: str = "large-v3", model_dir: Optional[str] = None, language: Optional[str] = "fr"):
+        """``language``: the tokenizer's own language (prompts and word splitting when a call names none); None for a handle that is only ever
+        used with ``language=None`` (detection per recording)."""
         from ..Aligners import checkpoint as CK
         model = CK.load_model(model_size, model_dir).load_into(engine)
         return cls(model, CK.load_tokenizer(model_dir, language, model.text_dims["n_vocab"]))
@@ -274,9 +278,10 @@ def _load(audio):
     return to_pcm16(pcm), int(rate)
 
 
-def extract_transcripts_and_breaks(engine, model: WhisperHandle, audios, language: str = "fr"):
+def extract_transcripts_and_breaks(engine, model: WhisperHandle, audios, language: Optional[str] = "fr"):
     """Batched ``extract_transcript_and_breaks``: ``audios`` = paths of 16-bit WAV files or ``(samples, rate)`` -> one
-    ``(text, breaks, segments)`` per recording, all recordings one transcription batch."""
+    ``(text, breaks, segments)`` per recording, all recordings one transcription batch.  ``language=None``: detected per recording
+    (recordings of different languages share the batch)."""
     from ..Aligners import transcribe as TR
     engine = _engine(engine)
     loaded = [_load(a) for a in audios]
@@ -292,9 +297,9 @@ def extract_transcripts_and_breaks(engine, model: WhisperHandle, audios, languag
     return out
 
 
-def extract_transcript_and_breaks(engine, model: WhisperHandle, audio, language: str = "fr"):
+def extract_transcript_and_breaks(engine, model: WhisperHandle, audio, language: Optional[str] = "fr"):
     """Transcript, phrase-break times (the end of every segment but the last) and segments of one recording, through
-    ``Aligners/transcribe.py`` with ``vad=None``.  The language is an argument: language detection is not built."""
+    ``Aligners/transcribe.py`` with ``vad=None``.  The language is an argument; None detects it, as the notebook's ``model.transcribe(path)`` does."""
     return extract_transcripts_and_breaks(engine, model, [audio], language)[0]
 
 
@@ -315,7 +320,7 @@ def _write_side(save_path: Path, prefix: str, txt: str, breaks, segments):
         json.dump(segments, f)
 
 
-def process_episodes(ep_ids: Sequence[str], voice_base, results_base, save_dir, engine=None, model: WhisperHandle = None, language: str = "fr",
+def process_episodes(ep_ids: Sequence[str], voice_base, results_base, save_dir, engine=None, model: WhisperHandle = None, language: Optional[str] = "fr",
                      method: str = "fastdtw", radius: int = 25):
     """``process_episode`` for a list of episodes, stage by stage over all of them -> [(ep_id, rmse_f0, f1_break, wer, error | None)].
     Folder contract of the notebook: ``{voice_base}/{ep}/brute/segment_demucs.wav`` is the reference, ``{results_base}/{ep}/OUT.wav`` the
@@ -380,7 +385,7 @@ def process_episode(ep_id: str, voice_base, results_base, save_dir, engine=None,
     return process_episodes([ep_id], voice_base, results_base, save_dir, engine, model, **kw)[0]
 
 
-def evaluate_all(voice_base, results_base, save_dir, engine=None, model: WhisperHandle = None, language: str = "fr", method: str = "fastdtw",
+def evaluate_all(voice_base, results_base, save_dir, engine=None, model: WhisperHandle = None, language: Optional[str] = "fr", method: str = "fastdtw",
                  radius: int = 25):
     """Every episode folder of ``results_base`` -> ``pandas.DataFrame`` indexed by ``episode`` with ``rmse_f0``, ``f1_break``, ``wer``
     (episodes that failed -- a missing ``OUT.wav`` among them -- are reported and left out, as in the notebook).  All episodes form one

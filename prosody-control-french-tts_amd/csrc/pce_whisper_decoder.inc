@@ -1,5 +1,6 @@
 // pce_whisper_decoder.inc -- the Whisper text decoder's entry points (included by pce_whisper_impl.inc, whose kernels and launchers they use):
-// weights, the prefix pass over padded token rows (forced alignment and the prefill of a decoding step share it), incremental steps, the device-resident loop.
+// weights, the prefix pass over padded token rows (forced alignment and the prefill of a decoding step share it), incremental steps, the device-resident loop,
+// language detection (a decoding call's first half -- prompts to the last position's LayerNorm -- then the language rows of the output projection).
 int pce_dtw_launch(pce_ctx *c, const double *d_x, int64_t x_stride, int ld, const int *d_rows, const int *d_cols, int N_max, int M_max,
                    int batch, unsigned char *d_trace, int *d_pi, int *d_pj, int *d_pl);
 
@@ -528,48 +529,45 @@ extern "C" int pce_whisper_decode_step_ex(pce_ctx *c, const int32_t *tokens, con
     return PCE_OK;
 }
 
-static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
-                              const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, bool want_probe)
+// ---- A decoding call up to the final LayerNorm of every sequence's last position, in two parts (pce_whisper_decode_step_ex / pce_whisper_decode_loop go on to the
+// output projection and the logit filters, pce_whisper_detect_language to the language rows of the embedding alone).
+// Part 1, before the first launch: lengths checked against the text context, the prompts as padded token rows and the tables
+// [q_row0 | q_len | a_row0 | a_len | sample_begin] on the device (with the vocabulary mask, when the caller has one), one synchronisation.
+static int decode_stage_prompts(pce_ctx *c, WhisperState *w, const int32_t *tokens, const int32_t *token_offsets, const int32_t *sample_begin_of,
+                                int32_t sample_begin_all, const uint8_t *vocab_mask, TokenRows &rows)
 {
-    float probe_dummy = 0.f;
-    float *probe_prob = want_probe ? &probe_dummy : nullptr;      // (only its non-nullness is consulted below)
-    const int32_t sample_begin = opts->sample_begin_all;
-    WhisperState *w = ws_of(c);
-    if (!w->dec_loaded) return pce_fail(c, PCE_E_STATE, "pce_whisper_decode_step before pce_whisper_decoder_load");
-    if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "run pce_whisper_encode_run first");
-    if (w->tdims.n_state != w->dims.n_state) return pce_fail(c, PCE_E_INVALID, "decoder and encoder widths differ");
-    PCE_HIP(c, hipSetDevice(c->device));
-    const int n = w->n_clips_enc, d = w->tdims.n_state, L = w->tdims.n_layer, V = w->tdims.n_vocab, SPD = PREFIX_SP;
-    if (rules->eot < 0 || rules->eot >= V || rules->timestamp_begin <= rules->eot || rules->timestamp_begin > V || (!opts->sample_begin && sample_begin < 1))
-        return pce_fail(c, PCE_E_INVALID, "decoding rules: need 0 <= eot < timestamp_begin <= n_vocab, sample_begin >= 1");
-    if (!(opts->temperature >= 0.f) || opts->probe_token >= V) return pce_fail(c, PCE_E_INVALID, "decoding options: temperature >= 0, probe_token < n_vocab");
-    if (n == 0) return PCE_OK;
+    const int n = w->n_clips_enc, d = w->tdims.n_state, V = w->tdims.n_vocab;
     for (int i = 0; i < n; i++) {
         const int T = token_offsets[i + 1] - token_offsets[i];
-        const int sb = opts->sample_begin ? opts->sample_begin[i] : sample_begin;
+        const int sb = sample_begin_of ? sample_begin_of[i] : sample_begin_all;
         if (sb < 1 || T < sb || T > w->tdims.n_text_ctx) return pce_fail(c, PCE_E_INVALID, "clip %d: %d tokens (need %d..%d)", i, T, sb, w->tdims.n_text_ctx);
     }
-    TokenRows rows;                                             // tables: [q_row0 | q_len | a_row0 | a_len | sample_begin]
     { const int rc = pad_token_rows(c, tokens, token_offsets, n, V, "token", 5, rows); if (rc) return rc; }
-    const int T_pad = rows.T_pad;
-    std::vector<int> &t_len = rows.t_len, &tok = rows.tok, &tab = rows.tab;
-    const int64_t Ma = (int64_t)n * W_CTX, Vp = div_up(V, 128) * 128;
-    for (int i = 0; i < n; i++) tab[(size_t)4 * n + i] = opts->sample_begin ? opts->sample_begin[i] : sample_begin;
+    std::vector<int> &tok = rows.tok, &tab = rows.tab;
+    for (int i = 0; i < n; i++) tab[(size_t)4 * n + i] = sample_begin_of ? sample_begin_of[i] : sample_begin_all;
     PCE_HIP(c, w->d_tab.reserve(sizeof(int) * tab.size()));
     PCE_HIP(c, w->d_tokens.reserve(sizeof(int) * tok.size()));
     PCE_HIP(c, w->g_last.reserve(sizeof(float) * (size_t)n * d));
     PCE_HIP(c, w->g_lastln.reserve(sizeof(op_t) * (size_t)(n + 128) * d + 4096));
-    PCE_HIP(c, w->g_logits.reserve(sizeof(float) * (size_t)n * (size_t)Vp));
-    PCE_HIP(c, w->g_mask.reserve((size_t)V + 64));
-    PCE_HIP(c, w->g_next.reserve((sizeof(int) + 2 * sizeof(float)) * (size_t)n));
+    if (vocab_mask) PCE_HIP(c, w->g_mask.reserve((size_t)V + 64));
     w->al_tab_host.clear();                                     // (d_tab / d_tokens are shared with pce_whisper_align_run: it uploads again)
     PCE_HIP(c, hipMemcpyAsync(w->d_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(w->d_tokens.p, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->g_mask.p, vocab_mask, (size_t)V, hipMemcpyHostToDevice, c->stream));
+    if (vocab_mask) PCE_HIP(c, hipMemcpyAsync(w->g_mask.p, vocab_mask, (size_t)V, hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+// Part 2, the launches: cross K / V of every layer (once per encoded batch), then one new position per sequence when the self-attention cache holds
+// all but the last token of every prompt (`use_cache`), else the prefix pass, which fills that cache -> g_lastln [n][d] op_t.  The host's record
+// of what the cache holds is brought up to date.
+static int decode_prompts_to_lastln(pce_ctx *c, WhisperState *w, const int32_t *tokens, const int32_t *token_offsets, const TokenRows &rows, bool use_cache)
+{
+    const int n = w->n_clips_enc, d = w->tdims.n_state, L = w->tdims.n_layer, SPD = PREFIX_SP;
+    const int T_pad = rows.T_pad;
+    const std::vector<int> &t_len = rows.t_len;
+    const int64_t Ma = (int64_t)n * W_CTX;
     const PrefixRun run = prefix_run(w, n, T_pad);
-    const int *T0 = run.T0, *TL = run.TL;
-    KernelTimer timer(c, PCE_K_WHISPER_DECODE);
+    const int *TL = run.TL;
     // ---- cross K / V of every layer, once per encoded batch
     const size_t xk_l = (size_t)Ma * d, xvt_l = (size_t)n * (size_t)d * AT_SP;
     if (w->g_xkv_clips != n) {
@@ -600,13 +598,12 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
         w->g_cache_n = n; w->g_cache_len = -1; w->g_cache_tok.assign((size_t)n * T_cap, 0); w->g_cache_lens.assign((size_t)n, -1);
     }
     // incremental: every sequence extends what the cache holds for it by exactly one token (lengths may differ between sequences)
-    bool incremental = w->g_cache_len >= 0 && !(opts->flags & 1);
+    bool incremental = w->g_cache_len >= 0 && use_cache;
     for (int i = 0; incremental && i < n; i++) {
         const int Li = t_len[(size_t)i];
         incremental = Li >= 2 && w->g_cache_lens[(size_t)i] == Li - 1 &&
                       memcmp(&w->g_cache_tok[(size_t)i * T_cap], &tokens[token_offsets[i]], sizeof(int) * (size_t)(Li - 1)) == 0;
     }
-    const op_t *last_ln = nullptr;                                // [n][d] op_t: the final LayerNorm of the last position
     if (incremental) {
         // ---- one new position per sequence: every GEMM has M = clips rows, the attention one query per (clip, head)
         std::vector<int> ct((size_t)8 * n);                     // new token | q_row0 | q_len | k_row0 | k_len | a_row0 | a_len | position
@@ -619,7 +616,6 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
         PCE_HIP(c, hipMemcpyAsync(w->g_c_tab.p, ct.data(), sizeof(int) * ct.size(), hipMemcpyHostToDevice, c->stream));
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         decode_incremental_launches(c, w, n, w->g_c_tab.as<int>(), nullptr);
-        last_ln = w->g_lastln.as<op_t>();
     } else {
     { const int rc = prefix_reserve_and_embed(c, w, run); if (rc) return rc; }
     for (int l = 0; l < L; l++) {
@@ -634,11 +630,10 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
         prefix_cross_attention(c, w, run, w->g_xk.as<op_t>() + xk_l * (size_t)l, w->g_xvt.as<op_t>() + xvt_l * (size_t)l);
         prefix_cross_out_mlp(c, w, run, ly, false);               // (tiled fc1: the prefill has never been measured on the persistent kernel)
     }
-    // ---- last position -> ln -> logits = hidden . E^T (fp32, zero-initialised accumulator)
+    // ---- last position -> ln
     hipLaunchKernelGGL(k_gather_last, dim3((unsigned)div_up((int64_t)n * d, 256)), dim3(256), 0, c->stream, w->d_resid.as<float>(), TL, T_pad, d, n,
                        w->g_last.as<float>());
     launch_layernorm<op_t>(c, w->g_last.as<float>(), run.Wf + w->dln_w, run.Wf + w->dln_b, (int64_t)n, d, w->g_lastln.as<op_t>());
-    last_ln = w->g_lastln.as<op_t>();
     }
     // the cache now holds every position of these prefixes
     for (int i = 0; i < n; i++) {
@@ -646,13 +641,83 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
         w->g_cache_lens[(size_t)i] = t_len[(size_t)i];
     }
     w->g_cache_len = 0;
-    launch_gemm<EPI_F32>(c, last_ln, d, 0, w->g_emb_bf16.as<op_t>(), n, (int)Vp, d, nullptr, w->g_logits.as<float>(), Vp, 0, 1);
+    return PCE_OK;
+}
+
+static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
+                              const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, bool want_probe)
+{
+    float probe_dummy = 0.f;
+    float *probe_prob = want_probe ? &probe_dummy : nullptr;      // (only its non-nullness is consulted below)
+    const int32_t sample_begin = opts->sample_begin_all;
+    WhisperState *w = ws_of(c);
+    if (!w->dec_loaded) return pce_fail(c, PCE_E_STATE, "pce_whisper_decode_step before pce_whisper_decoder_load");
+    if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "run pce_whisper_encode_run first");
+    if (w->tdims.n_state != w->dims.n_state) return pce_fail(c, PCE_E_INVALID, "decoder and encoder widths differ");
+    PCE_HIP(c, hipSetDevice(c->device));
+    const int n = w->n_clips_enc, d = w->tdims.n_state, V = w->tdims.n_vocab;
+    if (rules->eot < 0 || rules->eot >= V || rules->timestamp_begin <= rules->eot || rules->timestamp_begin > V || (!opts->sample_begin && sample_begin < 1))
+        return pce_fail(c, PCE_E_INVALID, "decoding rules: need 0 <= eot < timestamp_begin <= n_vocab, sample_begin >= 1");
+    if (!(opts->temperature >= 0.f) || opts->probe_token >= V) return pce_fail(c, PCE_E_INVALID, "decoding options: temperature >= 0, probe_token < n_vocab");
+    if (n == 0) return PCE_OK;
+    const int64_t Vp = div_up(V, 128) * 128;
+    PCE_HIP(c, w->g_logits.reserve(sizeof(float) * (size_t)n * (size_t)Vp));
+    PCE_HIP(c, w->g_next.reserve((sizeof(int) + 2 * sizeof(float)) * (size_t)n));
+    TokenRows rows;
+    { const int rc = decode_stage_prompts(c, w, tokens, token_offsets, opts->sample_begin, sample_begin, vocab_mask, rows); if (rc) return rc; }
+    KernelTimer timer(c, PCE_K_WHISPER_DECODE);
+    { const int rc = decode_prompts_to_lastln(c, w, tokens, token_offsets, rows, !(opts->flags & 1)); if (rc) return rc; }
+    // ---- logits = hidden . E^T (fp32, zero-initialised accumulator), the filters and the choice
+    const int *T0 = w->d_tab.as<int>(), *TL = T0 + n;
+    launch_gemm<EPI_F32>(c, w->g_lastln.as<op_t>(), d, 0, w->g_emb_bf16.as<op_t>(), n, (int)Vp, d, nullptr, w->g_logits.as<float>(), Vp, 0, 1);
     DecRules R{rules->eot, rules->timestamp_begin, V, (int)Vp, sample_begin, rules->max_initial_timestamp_index, opts->temperature, opts->seed_lo,
                opts->seed_hi, probe_prob ? opts->probe_token : -1};
-    hipLaunchKernelGGL(k_decode_rules, dim3((unsigned)n), dim3(DR_T), 0, c->stream, w->g_logits.as<float>(), w->d_tokens.as<int>(), TL, T_pad,
+    hipLaunchKernelGGL(k_decode_rules, dim3((unsigned)n), dim3(DR_T), 0, c->stream, w->g_logits.as<float>(), w->d_tokens.as<int>(), TL, rows.T_pad,
                        w->g_mask.as<unsigned char>(), R, T0 + 4 * n, w->g_next.as<int>(), reinterpret_cast<float *>(w->g_next.as<int>() + n),
                        reinterpret_cast<float *>(w->g_next.as<int>() + 2 * n), w->g_keys_n == n ? w->g_keys.as<int>() : nullptr);
     PCE_HIP(c, hipGetLastError());
+    return PCE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Language detection (openai-whisper decoding.py detect_language): the decoder over the one token <|startoftranscript|> per clip, then k_lang_probs
+// (pce_whisper_impl.inc) on the n_lang language rows of the tied embedding -- no output projection over the vocabulary, no k_decode_rules.
+// ---------------------------------------------------------------------------
+extern "C" int pce_whisper_detect_language(pce_ctx *c, int32_t sot, int32_t lang_begin, int32_t n_lang, int32_t *ids, float *probs)
+{
+    if (!c) return PCE_E_INVALID;
+    WhisperState *w = ws_of(c);
+    if (!w->dec_loaded) return pce_fail(c, PCE_E_STATE, "pce_whisper_detect_language before pce_whisper_decoder_load");
+    if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "run pce_whisper_encode_run first");
+    if (w->tdims.n_state != w->dims.n_state) return pce_fail(c, PCE_E_INVALID, "decoder and encoder widths differ");
+    const int n = w->n_clips_enc, d = w->tdims.n_state, V = w->tdims.n_vocab;
+    if (n_lang < 1 || n_lang > LANG_MAX) return pce_fail(c, PCE_E_INVALID, "language detection over %d tokens (1..%d)", n_lang, LANG_MAX);
+    if (lang_begin < 0 || lang_begin > V - n_lang) return pce_fail(c, PCE_E_INVALID, "language tokens %d..%d leave the vocabulary of %d", lang_begin, lang_begin + n_lang - 1, V);
+    if (sot < 0 || sot >= V) return pce_fail(c, PCE_E_INVALID, "token %d out of the vocabulary", sot);
+    PCE_HIP(c, hipSetDevice(c->device));
+    if (n == 0) return PCE_OK;
+    std::vector<int32_t> tokens((size_t)n, sot), offsets((size_t)n + 1);
+    for (int i = 0; i <= n; i++) offsets[(size_t)i] = i;
+    PCE_HIP(c, w->g_lang.reserve((sizeof(float) * (size_t)n_lang + sizeof(int)) * (size_t)n));
+    TokenRows rows;
+    { const int rc = decode_stage_prompts(c, w, tokens.data(), offsets.data(), nullptr, 1, nullptr, rows); if (rc) return rc; }
+    float *d_probs = w->g_lang.as<float>();
+    int *d_ids = reinterpret_cast<int *>(d_probs + (size_t)n * n_lang);
+    {
+        KernelTimer timer(c, PCE_K_WHISPER_DECODE);
+        // (never the incremental form: a one-token prompt extends nothing)
+        { const int rc = decode_prompts_to_lastln(c, w, tokens.data(), offsets.data(), rows, false); if (rc) return rc; }
+        hipLaunchKernelGGL(k_lang_probs, dim3((unsigned)n), dim3(LANG_T), 0, c->stream, w->g_lastln.as<op_t>(), w->g_emb_bf16.as<op_t>(), d, (int)lang_begin,
+                           (int)n_lang, d_probs, d_ids);
+        PCE_HIP(c, hipGetLastError());
+    }
+    // The cache now holds position 0 of every clip for the token `sot`, which is what any later prompt starts with; all the same the host's record of it is
+    // dropped, so that the next decoding call runs its prompts through the prefix pass exactly as it does after a fresh pce_whisper_encode_run
+    // (the cross K / V of the batch stay: they are what that call would compute first)
+    w->g_cache_len = -1;
+    if (ids) PCE_HIP(c, hipMemcpyAsync(ids, d_ids, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (probs) PCE_HIP(c, hipMemcpyAsync(probs, d_probs, sizeof(float) * (size_t)n * n_lang, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
 

@@ -31,6 +31,7 @@ PCE_BOTH(int, pce_whisper_sample_keys, (pce_ctx *, const int32_t *, int32_t))
 PCE_BOTH(int, pce_whisper_decode_step, (pce_ctx *, const int32_t *, const int32_t *, int32_t, const pce_whisper_decode_rules *, const uint8_t *, int32_t *, float *))
 PCE_BOTH(int, pce_whisper_decode_step_ex, (pce_ctx *, const int32_t *, const int32_t *, const pce_whisper_decode_rules *, const uint8_t *, const pce_whisper_decode_opts *, int32_t *, float *, float *))
 PCE_BOTH(int, pce_whisper_decode_loop, (pce_ctx *, const int32_t *, const int32_t *, const pce_whisper_decode_rules *, const uint8_t *, const pce_whisper_decode_opts *, int32_t, int32_t, int32_t *, float *, int32_t *, float *))
+PCE_BOTH(int, pce_whisper_detect_language, (pce_ctx *, int32_t, int32_t, int32_t, int32_t *, float *))
 PCE_BOTH(int, pce_bert_load, (pce_ctx *, const pce_bert_dims *, const float *, int64_t))
 PCE_BOTH(int, pce_bert_run, (pce_ctx *, const int32_t *, const int32_t *, int32_t))
 PCE_BOTH(int, pce_bert_fetch, (pce_ctx *, int32_t, float *, int32_t *))
@@ -130,6 +131,10 @@ int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *to
                             float *probe_prob)
 {
     return PCE_FWD(pce_whisper_decode_loop, c, tokens, token_offsets, rules, vocab_mask, opts, max_new, check_every, out_tokens, out_logprobs, out_steps, probe_prob);
+}
+int pce_whisper_detect_language(pce_ctx *c, int32_t sot, int32_t lang_begin, int32_t n_lang, int32_t *ids, float *probs)
+{
+    return PCE_FWD(pce_whisper_detect_language, c, sot, lang_begin, n_lang, ids, probs);
 }
 int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, int64_t n_floats) { return PCE_FWD(pce_bert_load, c, dims, weights, n_floats); }
 int pce_bert_run(pce_ctx *c, const int32_t *input_ids, const int32_t *offsets, int32_t n_seq) { return PCE_FWD(pce_bert_run, c, input_ids, offsets, n_seq); }

@@ -61,6 +61,7 @@
 #define pce_whisper_decode_step PCE_WFN(pce_whisper_decode_step)
 #define pce_whisper_decode_step_ex PCE_WFN(pce_whisper_decode_step_ex)
 #define pce_whisper_decode_loop PCE_WFN(pce_whisper_decode_loop)
+#define pce_whisper_detect_language PCE_WFN(pce_whisper_detect_language)
 #define pce_bert_load PCE_WFN(pce_bert_load)
 #define pce_bert_run PCE_WFN(pce_bert_run)
 #define pce_bert_fetch PCE_WFN(pce_bert_fetch)
@@ -1714,6 +1715,53 @@ __global__ __launch_bounds__(DR_T) void k_decode_rules(const float *__restrict__
     }
 }
 
+// openai-whisper decoding.py detect_language on the hidden state of the <|startoftranscript|> position, one workgroup per clip: the logits of the
+// n_lang language tokens alone (rows lang_begin .. lang_begin + n_lang - 1 of the tied embedding: 99 or 100 rows of the 51 865 the output projection
+// multiplies), their softmax -- every other token is masked to -inf there, so it is the softmax over the vocabulary -- and the arg-max, first maximum.
+// Waves take rows (w, w + LANG_W, ...), the lanes of a wave split the width in runs of 8 operands (16-byte loads; column = 8 lane + 512 j), fp32
+// accumulation in ascending column order per lane, the 64 partial sums added by xor shuffles 32 .. 1; wave 0 then holds logits i and i + 64 in lane i.
+// The order of every addition follows from (d, n_lang) alone: a clip's results do not depend on what it is batched with, and two identical embedding
+// rows give identical bits.  d: a multiple of 8, at most LN_D_MAX (pce_whisper_decoder_load: a multiple of 128).
+constexpr int LANG_MAX = 128, LANG_T = 512, LANG_W = LANG_T / 64;
+__global__ __launch_bounds__(LANG_T) void k_lang_probs(const op_t *__restrict__ hidden, const op_t *__restrict__ emb, int d, int lang_begin, int n_lang,
+                                                       float *__restrict__ probs, int *__restrict__ ids)
+{
+    __shared__ float s_x[LN_D_MAX];
+    __shared__ float s_logit[LANG_MAX];
+    const int clip = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const op_t *x = hidden + (int64_t)clip * d;
+    for (int col = tid; col < d; col += LANG_T) s_x[col] = (float)x[col];
+    __syncthreads();
+    for (int r = wv; r < n_lang; r += LANG_W) {                    // (n_lang is no multiple of the wave count: the last round is short)
+        const op_t *row = emb + (int64_t)(lang_begin + r) * d;
+        float acc = 0.f;
+        for (int col = lane * 8; col < d; col += 512) {            // (d is no multiple of 512 either: the high lanes sit out the last round, or every round)
+            const opx8 e = *reinterpret_cast<const opx8 *>(row + col);
+#pragma unroll
+            for (int u = 0; u < 8; u++) acc = fmaf((float)e[u], s_x[col + u], acc);
+        }
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (lane == 0) s_logit[r] = acc;
+    }
+    __syncthreads();
+    if (wv != 0) return;
+    const float NEG = -__builtin_huge_valf();
+    const float a0 = lane < n_lang ? s_logit[lane] : NEG, a1 = lane + 64 < n_lang ? s_logit[lane + 64] : NEG;
+    float best = a0; int bi = lane;                                // (lane 0 always holds a real logit: n_lang >= 1)
+    if (a1 > best) { best = a1; bi = lane + 64; }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    const float e0 = lane < n_lang ? expf(a0 - best) : 0.f, e1 = lane + 64 < n_lang ? expf(a1 - best) : 0.f;
+    float sum = e0 + e1;
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    float *p = probs + (int64_t)clip * n_lang;
+    if (lane < n_lang) p[lane] = e0 / sum;
+    if (lane + 64 < n_lang) p[lane + 64] = e1 / sum;
+    if (lane == 0) ids[clip] = lang_begin + bi;
+}
+
 // softmax over the audio frames of the (scaled) cross-attention logits of one alignment head:
 // w[clip][sel][t][s] = softmax_s(q_t . k_s * 0.125 * qk_scale), s < F_c.  16 tokens per workgroup, 4 waves x 16
 // keys per 64-key tile on v_mfma_f32_16x16x32_bf16, two passes (row max / sum, then normalised write).
@@ -1932,6 +1980,7 @@ struct WhisperState {
     int enc_bf16_clips = -1;             // d_enc_bf16 holds the op_t copy of final_out for this many clips (written by the encoder's last LayerNorm)
     // free-running decoding: tied output projection in op_t (rows padded to 128), cross K / V of every layer, last-position buffers
     DevBuf g_emb_bf16, g_xk, g_xvt, g_last, g_lastln, g_logits, g_mask, g_next, g_keys;
+    DevBuf g_lang;                   // pce_whisper_detect_language: probabilities [clips][n_lang] fp32 | token ids [clips]
     DevBuf g_wkT, g_qp, g_upart, g_mlpart;   // cross-attention from the encoder output (pce_xattn.inc): Wk^T of every layer, Q' hi | lo, the splits' partial U and (m, l)
     int g_keys_n = 0;                // sampling keys of the encoded batch (pce_whisper_sample_keys); 0: the batch position is the key
     int g_xkv_clips = -1;            // clips the cross K / V cache was computed for (-1: stale)

@@ -137,7 +137,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_silence_run", "pce_silence_shape", "pce_silence_fetch",
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
-           "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
+           "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
            "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
@@ -207,6 +207,7 @@ def load_library() -> C.CDLL:
     lib.pce_whisper_align_paths_enqueue.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.pce_whisper_align_paths_wait.argtypes = [vp, i32, vp, vp, vp]
     lib.pce_whisper_sample_keys.argtypes = [vp, vp, i32]
+    lib.pce_whisper_detect_language.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.pce_bert_load.argtypes = [vp, C.POINTER(BertDims), vp, i64]
     lib.pce_bert_run.argtypes = [vp, vp, vp, i32]
     lib.pce_bert_fetch.argtypes = [vp, i32, vp, vp]
@@ -901,6 +902,16 @@ class ProsodyEngine:
                                                       int(max_new), int(check_every), out.ctypes.data, lp.ctypes.data, C.byref(steps),
                                                       pr.ctypes.data if pr is not None else None))
         return out[:, :steps.value], lp[:, :steps.value], pr
+
+    def whisper_detect_language(self, sot: int, lang_begin: int, n_lang: int):
+        """``pce_whisper_detect_language``: openai-whisper's ``detect_language`` for every encoded clip -- the decoder over
+        <|startoftranscript|> alone, softmax over the ``n_lang`` language tokens ``lang_begin ..`` (every other token masked) and the
+        arg-max.  -> (token ids int32 [clips], probabilities float32 [clips, n_lang]).  The next decoding call behaves as if this one
+        had not been made."""
+        n = self.whisper_num_encoded()
+        ids = np.zeros(max(n, 0), dtype=np.int32); probs = np.zeros((max(n, 0), max(int(n_lang), 0)), dtype=np.float32)
+        self._check(self._lib.pce_whisper_detect_language(self._ctx, int(sot), int(lang_begin), int(n_lang), ids.ctypes.data, probs.ctypes.data))
+        return ids, probs
 
     # ---------------------------------------------------------------- probabilistic YIN (viewers)
     def pyin_run(self, plan, tables):
