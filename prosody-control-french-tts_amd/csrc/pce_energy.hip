@@ -11,6 +11,7 @@
 // group), reduces in registers -> wave shuffles -> LDS -> one set of integer atomics per
 // block.  Integer accumulation makes the result independent of the reduction order.
 #include "pce_internal.h"
+#include "pce_wave.h"
 
 namespace {
 
@@ -24,43 +25,9 @@ struct EnWork { int64_t g0, g1; int32_t slice; int32_t pad; };
 // zero-initialisable encodings of the slice maximum and minimum, used by the pitch path.
 struct EnAcc { unsigned long long sum_sq; long long sum_wrap; unsigned long long n_loud; long long sum; int peak; int m_hi; int m_lo; int pad; };
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ long long wave_sum_i64(long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_max_i32(int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_down(v, off, 64));
-    return v;
-}
-
-// wave-wide integer reductions without LDS round trips: four DPP steps leave every lane of a 16-lane row with the row's total, four
-// v_readlane combine the rows on the scalar unit (the result is wave-uniform).  The shuffle form (ds_bpermute, six dependent steps per
-// value, seven values, two of them 64-bit) plus the LDS hand-off between waves was the larger part of a workgroup's life after its loads.
-template <int CTRL> __device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ int wave_sum_dpp(int v)
-{
-    v += dpp_i32<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_i32<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += dpp_i32<0x141>(v);     // row_half_mirror
-    v += dpp_i32<0x140>(v);     // row_mirror
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
-__device__ __forceinline__ int wave_max_dpp(int v)
-{
-    v = max(v, dpp_i32<0xB1>(v));
-    v = max(v, dpp_i32<0x4E>(v));
-    v = max(v, dpp_i32<0x141>(v));
-    v = max(v, dpp_i32<0x140>(v));
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-
+// The wave totals are taken by DPP rows and v_readlane (wave_dpp_sum_i32 / wave_dpp_max_i32, pce_wave.h), without LDS round trips: the shuffle form
+// (ds_bpermute, six dependent steps per value, seven values, two of them 64-bit) plus the LDS hand-off between waves was the larger part of a
+// workgroup's life after its loads.
 // A workgroup streams `cpb` CONSECUTIVE chunks (mostly of one slice), one after the other, with its accumulators in registers, and
 // adds its share to a slice's accumulators ONCE per (workgroup, slice): wave totals by DPP, one LDS hand-off, seven atomics from one
 // lane.  What the measurements of round 3 said about the one-chunk form (400 MB, 93 us): without its atomics 79 us, without the
@@ -142,9 +109,9 @@ __global__ __launch_bounds__(EN_THREADS) void k_energy(const int16_t *__restrict
         // cpb * EN_ITERS * 8 <= 2^10 samples; sum and wrapped-square sum: 2^10 x 2^15 per lane, x 64 lanes <= 2^31 in magnitude (only
         // -2^31 is reached); the 64-bit sum of squares (< 2^40 per lane) travels as its low 20 bits and the rest: 64 x 2^20 each.
         // The four waves are then added as 64-bit values.
-        const int r_sq_lo = wave_sum_dpp((int)(s_sq & 0xFFFFFull)), r_sq_hi = wave_sum_dpp((int)(s_sq >> 20));
-        const int r_wrap = wave_sum_dpp(s_wrap), r_loud = wave_sum_dpp(n_loud), r_sum = wave_sum_dpp(s_sum);
-        const int r_peak = wave_max_dpp(peak), r_hi = wave_max_dpp(m_hi), r_lo = wave_max_dpp(m_lo);
+        const int r_sq_lo = wave_dpp_sum_i32((int)(s_sq & 0xFFFFFull)), r_sq_hi = wave_dpp_sum_i32((int)(s_sq >> 20));
+        const int r_wrap = wave_dpp_sum_i32(s_wrap), r_loud = wave_dpp_sum_i32(n_loud), r_sum = wave_dpp_sum_i32(s_sum);
+        const int r_peak = wave_dpp_max_i32(peak), r_hi = wave_dpp_max_i32(m_hi), r_lo = wave_dpp_max_i32(m_lo);
         if (lane == 0) {
             l_part[wv][0] = r_sq_lo; l_part[wv][1] = r_sq_hi; l_part[wv][2] = r_wrap; l_part[wv][3] = r_loud;
             l_part[wv][4] = r_sum; l_part[wv][5] = r_peak; l_part[wv][6] = r_hi; l_part[wv][7] = r_lo;

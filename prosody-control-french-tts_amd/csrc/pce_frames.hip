@@ -14,19 +14,12 @@
 // Roofline: HBM-bound, 2 bytes per sample read once when hop == window, 12 bytes written per frame.
 // One wavefront per frame: 16-byte loads (8 samples per lane and load), register sums, wave shuffle reduction.
 #include "pce_internal.h"
+#include "pce_wave.h"
 
 namespace {
 
 constexpr int FR_THREADS = 256;
 constexpr int FR_FPW = 8;                 // frames per wavefront and trip on the common path (windows of at most 1 024 samples)
-
-// wave-wide integer sum without LDS round trips (see pce_energy.hip): DPP inside the 16-lane rows, v_readlane across them
-template <int CTRL> __device__ __forceinline__ int fr_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-__device__ __forceinline__ int fr_wave_sum(int v)
-{
-    v += fr_dpp<0xB1>(v); v += fr_dpp<0x4E>(v); v += fr_dpp<0x141>(v); v += fr_dpp<0x140>(v);
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48);
-}
 
 // FR_FPW frames per wavefront on the common path (a window of at most 1 024 samples = two 16-byte loads per lane): the 2 FR_FPW loads of a
 // lane are all requested before the first is used and a wavefront lives FPW times longer; one frame per wavefront (rounds 1-3a) left
@@ -64,7 +57,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_frame_energy(const int16_t *__re
     };
     // a lane's share of a frame is below 2^40 whenever the frame has at most 2^16 samples: low 20 bits and the rest both sum to < 2^31 over the wave
     auto wave_total = [&](unsigned long long s) -> unsigned long long {
-        const int lo = fr_wave_sum((int)(s & 0xFFFFFull)), hi = fr_wave_sum((int)(s >> 20));
+        const int lo = wave_dpp_sum_i32((int)(s & 0xFFFFFull)), hi = wave_dpp_sum_i32((int)(s >> 20));
         return ((unsigned long long)(unsigned int)hi << 20) + (unsigned long long)(unsigned int)lo;
     };
     for (int clip = blockIdx.y; clip < n_clips; clip += gridDim.y) {
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_frame_energy(const int16_t *__re
                 consume(v0, r, nfr, s);
                 consume(v1, r1, nfr, s);
             }
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+            s = wave_down_sum(s);
             if (lane == 0) { sum_sq[f0 + k] = (long long)s; count[f0 + k] = (int)(e - b); }
         }
     }

@@ -516,7 +516,7 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const RIN *resid_in, ROUT
         } else v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    s = wave_allsum_f32(s);
+    s = wave_dpp_sum_f32(s);
     const float mean = s / (float)d;
     float q = 0.f;
 #pragma unroll
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const RIN *resid_in, ROUT
             q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
         }
     }
-    q = wave_allsum_f32(q);
+    q = wave_dpp_sum_f32(q);
     const float inv = rsqrtf(q / (float)d + eps);
 #pragma unroll
     for (int i = 0; i < NV; i++) {

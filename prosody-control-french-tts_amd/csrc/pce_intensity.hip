@@ -17,6 +17,7 @@
 // l, l + 64, ... in order, the 64 partial sums meet in a fixed xor butterfly.  No atomics: a frame's bits depend on its own samples only.
 // Bound: LDS reads (10 bytes per tap and frame) and the dependent fp64 adds, not HBM.
 #include "pce_internal.h"
+#include "pce_wave.h"
 #include <cmath>
 
 namespace {
@@ -30,17 +31,6 @@ struct InSlice { int64_t begin, clip_len, clip_off, nx, frame_off; double x1, t1
 struct InWork { int32_t slice, frame0; };
 struct InParams { double dx, dt; int hs, fpb, span, subtract_mean; };
 struct InSummaryDev { long long n_positive; double mean_positive; };
-
-__device__ __forceinline__ double in_wave_sum_f64(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ int in_wave_sum_i32(int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // Sampled_indexToX of the Intensity, then Sampled_xToNearestIndex of the Sound (Melder_iround = floor(x + 0.5)), 0-based
 __device__ __forceinline__ int64_t in_centre(const InSlice &s, const InParams &P, int frame)
@@ -110,7 +100,7 @@ __global__ __launch_bounds__(IN_THREADS) void k_intensity(const int16_t *__restr
             if (P.subtract_mean) {
                 int isum = 0;                                  // |sum| <= 6145 x 32768 < 2^31
                 for (int k = lane; k < n; k += 64) isum += (int)x[k];
-                isum = in_wave_sum_i32(isum);
+                isum = wave_xor_sum(isum);
                 mean = ((double)isum / 32768.0) / (double)n;
             }
             double num = 0.0, den = 0.0;
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(IN_THREADS) void k_intensity(const int16_t *__restr
                 num += (d * d) * wk_;
                 den += wk_;
             }
-            num = in_wave_sum_f64(num); den = in_wave_sum_f64(den);
+            num = wave_xor_sum(num); den = wave_xor_sum(den);
             const double I = num / den / 4.0e-10;
             value = I < 1.0e-30 ? -300.0 : 10.0 * log10(I);
         }
@@ -140,7 +130,7 @@ __global__ __launch_bounds__(64) void k_intensity_summary(const InSlice *__restr
         const double v = values[s.frame_off + f];
         if (v > 0.0) { np++; sum += v; }
     }
-    np = in_wave_sum_i32(np); sum = in_wave_sum_f64(sum);
+    np = wave_xor_sum(np); sum = wave_xor_sum(sum);
     if (lane == 0) {
         out[blockIdx.x].n_positive = np;
         out[blockIdx.x].mean_positive = np > 0 ? sum / (double)np : __builtin_nan("");

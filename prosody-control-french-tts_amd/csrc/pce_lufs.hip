@@ -19,6 +19,7 @@
 // flops per sample); algorithmic HBM traffic is 2 B/sample read twice (L2-resident
 // the second time).
 #include "pce_internal.h"
+#include "pce_wave.h"
 #include <algorithm>
 #include <cmath>
 
@@ -92,13 +93,6 @@ __global__ void k_lufs_pass1(const int16_t *__restrict__ pcm, const LuSlice *__r
     o[0] = st[0]; o[1] = st[1]; o[2] = st[2]; o[3] = st[3];
 }
 
-__device__ __forceinline__ double lu_readlane_f64(double v, int src)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-    return __hiloint2double(hi, lo);
-}
-
 // One wavefront per slice, three levels (the plain chain over a 10 s slice is 625 dependent 4x4
 // matrix-vector steps; this is 16 + n_groups + 16):
 //   1. lane g folds its group of LU_GROUP consecutive chunks from a zero state: z_g, and the
@@ -156,8 +150,8 @@ __global__ __launch_bounds__(64) void k_lufs_scan(const LuSlice *__restrict__ sl
             if (lane == q) { b0 = c0; b1 = c1; b2 = c2; b3 = c3; }
             double Mq[16];
 #pragma unroll
-            for (int t = 0; t < 16; t++) Mq[t] = lu_readlane_f64(M[t], q);
-            lu_matvec(Mq, c0, c1, c2, c3, lu_readlane_f64(z0, q), lu_readlane_f64(z1, q), lu_readlane_f64(z2, q), lu_readlane_f64(z3, q));
+            for (int t = 0; t < 16; t++) Mq[t] = readlane_f64(M[t], q);
+            lu_matvec(Mq, c0, c1, c2, c3, readlane_f64(z0, q), readlane_f64(z1, q), readlane_f64(z2, q), readlane_f64(z3, q));
         }
         // level 3: replay the group from its true begin state
         for (int c = cb; c < ce; c++) {
@@ -187,12 +181,6 @@ __global__ void k_lufs_pass2(const int16_t *__restrict__ pcm, const LuSlice *__r
     energy[i] = lu_run<true>(pcm, s, ch, k, lu_peak(peaks, pstride, ch.slice), st, pcm_total);
 }
 
-__device__ __forceinline__ double lu_wave_sum(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // One wavefront per slice: lanes own gating blocks (block energies = sums of whole chunks,
 // in chunk order), the two gated means are butterfly reductions.
 __global__ __launch_bounds__(64) void k_lufs_gate(const LuSlice *__restrict__ slices, const LuBlock *__restrict__ blocks, int n_slices, LuCoef k,
@@ -216,7 +204,7 @@ __global__ __launch_bounds__(64) void k_lufs_gate(const LuSlice *__restrict__ sl
         const double lj = -0.691 + 10.0 * log10(zj);
         if (lj >= gamma_a) { sum += zj; cnt += 1.0; }
     }
-    sum = lu_wave_sum(sum); cnt = lu_wave_sum(cnt);
+    sum = wave_xor_sum(sum); cnt = wave_xor_sum(cnt);
     const double zavg1 = cnt > 0.0 ? sum / cnt : nan("");
     const double gamma_r = -0.691 + 10.0 * log10(zavg1) - 10.0;
     sum = 0.0; cnt = 0.0;
@@ -225,7 +213,7 @@ __global__ __launch_bounds__(64) void k_lufs_gate(const LuSlice *__restrict__ sl
         const double lj = -0.691 + 10.0 * log10(zj);
         if (lj > gamma_r && lj > gamma_a) { sum += zj; cnt += 1.0; }
     }
-    sum = lu_wave_sum(sum); cnt = lu_wave_sum(cnt);
+    sum = wave_xor_sum(sum); cnt = wave_xor_sum(cnt);
     const double zavg2 = cnt > 0.0 ? sum / cnt : 0.0;
     if (lane == 0) lufs[i] = -0.691 + 10.0 * log10(zavg2);
 }

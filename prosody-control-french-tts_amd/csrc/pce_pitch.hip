@@ -26,6 +26,7 @@
 // byte), not HBM bound: algorithmic traffic is 2 B of PCM per
 // sample plus 8 B of F0 per frame.
 #include "pce_internal.h"
+#include "pce_wave.h"
 #include <cmath>
 #include <cstdlib>
 
@@ -95,22 +96,6 @@ struct PiSlice {
 struct PiWork { int32_t slice, frame0; };
 struct RefineItem { long long frame; int slot; int imax; };
 
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v)
-{
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // Praat NUM_interpolate_sinc with its terms spread over the wave.  y is the LDS image of
 // r[-bix..bix] (0-based storage of Praat's 1-based y[1..nx]); every lane passes the same x
 // and receives the same result.
@@ -149,7 +134,7 @@ __device__ double sinc_wave(const double *y, int nx, double x, int maxDepth, int
         const double d = hs / a * (1.0 + cos(aa));
         acc += y[ix - 1] * d;
     }
-    return wave_sum_f64(acc);
+    return wave_xor_sum(acc);
 }
 
 // ---------------------------------------------------------------------------
@@ -392,17 +377,6 @@ __device__ __forceinline__ void fft256_half(double2 (&z)[8], double2 *ex, const 
     }
 }
 
-template <int W> __device__ __forceinline__ int group_sum_i32(int v)
-{
-    for (int off = W / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-template <int W> __device__ __forceinline__ double group_max_f64(double v)
-{
-    for (int off = W / 2; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 // MODE 0: any N, one frame per wavefront, Stockham passes between two LDS buffers.
 // MODE 1: N = 1024, one frame per wavefront, register-resident transform.
 // MODE 2: N = 512 (16 kHz at the reference's 150 Hz floor, Code/audioPipeline.py:329), TWO frames per
@@ -522,7 +496,7 @@ __global__ __launch_bounds__(64 * WPB) void k_pitch_frames(
                 v[2 * r + h] = x;
             }
         }
-        isum = group_sum_i32<LW>(isum);
+        isum = wave_xor_sum<LW>(isum);
         const double localMean = ((double)isum / 32768.0) / (double)(2 * P.nsp);
 #pragma unroll
         for (int r = 0; r < R; r++) {
@@ -550,7 +524,7 @@ __global__ __launch_bounds__(64 * WPB) void k_pitch_frames(
         }
         xr[2 * ZP(j >> 1) + (j & 1)] = (double)v / 32768.0;
     }
-    isum = wave_sum_i32(isum);
+    isum = wave_xor_sum(isum);
     const double localMean = ((double)isum / 32768.0) / (double)(2 * P.nsp);
     for (int j = lane; j < P.nw; j += 64) {
         const int a = 2 * ZP(j >> 1) + (j & 1);
@@ -559,7 +533,7 @@ __global__ __launch_bounds__(64 * WPB) void k_pitch_frames(
         if (j + 1 >= pk0 && j + 1 <= pk1) lpk = fmax(lpk, fabs(f));
     }
     }
-    const double localPeak = group_max_f64<LW>(lpk);
+    const double localPeak = wave_xor_max<LW>(lpk);
     const double inten = localPeak > globalPeak ? 1.0 : localPeak / globalPeak;
     const bool active = live && localPeak != 0.0;
 
@@ -745,30 +719,6 @@ __global__ __launch_bounds__(64 * WPB) void k_pitch_frames(
 // arguments form an arithmetic progression, so only the two rows nearest x on each side take
 // the polynomial and the rest follow by the three-term cosine recurrence.
 // ---------------------------------------------------------------------------
-template <int CTRL> __device__ __forceinline__ double dpp_f64(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-// sum over the 16 lanes of a DPP row; every lane of the row receives the same bits
-__device__ __forceinline__ double row_sum16(double v)
-{
-    v += dpp_f64<0xB1>(v);     // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);     // quad_perm [2,3,0,1]
-    v += dpp_f64<0x141>(v);    // row_half_mirror
-    v += dpp_f64<0x140>(v);    // row_mirror
-    return v;
-}
-// sum over the 8 lanes of half a DPP row
-__device__ __forceinline__ double row_sum8(double v)
-{
-    v += dpp_f64<0xB1>(v);
-    v += dpp_f64<0x4E>(v);
-    v += dpp_f64<0x141>(v);
-    return v;
-}
 // cos(h) and sin(h) for h in [0, pi/2] (Taylor about 0; truncation < 1e-19), evaluated by Estrin's
 // scheme: a dependent fp64 FMA costs ~30 cycles on this part (measured), so the 13-deep Horner chain
 // was the critical path of every evaluation; this form is 5 deep for two more multiplies.
@@ -816,13 +766,6 @@ __device__ __forceinline__ double sinc_w(double kd, double a0, double yu /* y (1
 {
     return yu * rcp_f64(fma(kd, PI_D, a0));         // the side's +-0.5 sin factor is applied once per side
 }
-template <int G> __device__ __forceinline__ double group_sum(double v)
-{
-    v += dpp_f64<0xB1>(v);                              // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);                              // quad_perm [2,3,0,1]
-    if (G == 8) v += dpp_f64<0x141>(v);                 // row_half_mirror
-    return v;
-}
 // G lanes per candidate, NR = 144 / G rows per lane; row RS straddles x, rows < RS lie left, rows > RS right.
 template <int G>
 __device__ __forceinline__ double sinc_group_reg(const double (&yv)[144 / G], int wbase, int ynx, double x, int maxDepth, int lg)
@@ -833,7 +776,7 @@ __device__ __forceinline__ double sinc_group_reg(const double (&yv)[144 / G], in
         double pick = 0.0;
 #pragma unroll
         for (int m = 0; m < NR; m++) if (wbase + lg + G * m == midleft) pick = yv[m];
-        return group_sum<G>(pick);
+        return dpp_row_sum<G>(pick);
     }
     int D = maxDepth;
     if (D > midright - 1) D = midright - 1;
@@ -909,7 +852,7 @@ __device__ __forceinline__ double sinc_group_reg(const double (&yv)[144 / G], in
         if (NRt & 1) side += tv[NRt - 1] * rcp_f64(av[NRt - 1]);
         acc = fma(hs_r, side, acc);
     }
-    return group_sum<G>(acc);
+    return dpp_row_sum<G>(acc);
 }
 
 // generic NUM_interpolate_sinc with y in global memory (depth 700, or windows near the array ends)
@@ -949,7 +892,7 @@ template <int G> __device__ double sinc_group_mem(const double *__restrict__ yh 
         const int ix = is_left ? midleft - k : midright + k;
         acc += Y(ix) * (hs * rcp_f64(a) * one_plus_cos_0pi(aa));
     }
-    return group_sum<G>(acc);
+    return dpp_row_sum<G>(acc);
 }
 
 template <int G>
@@ -1115,13 +1058,6 @@ constexpr int RUN_LISTS = 64;             // independent run lists (see RF_LISTS
 constexpr double PATH_VOICELESS = 1e300;
 
 struct PathRun { long long frame; long long gend; int has_prev; int pad; };   // run start, slice end (global frame indices), a cut frame precedes
-
-__device__ __forceinline__ double readlane_f64(double v, int src)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-    return __hiloint2double(hi, lo);
-}
 
 // Elementwise pre-pass of Pitch_pathFinder over every (frame, candidate):
 //   dl = {local delta (the finder's first loop), log2 f or PATH_VOICELESS}
@@ -1359,7 +1295,7 @@ __global__ __launch_bounds__(256) void k_pitch_median(const PiSlice *__restrict_
             }
             __syncthreads();
         }
-    for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
+    lsum = wave_xor_sum(lsum);
     if ((tid & 63) == 0) s_red[tid >> 6] = lsum;
     __syncthreads();
     if (tid == 0) {
@@ -1399,7 +1335,7 @@ __global__ __launch_bounds__(256) void k_pitch_median_long(const PiSlice *__rest
         if (v > 0.0) { mine++; lsum += log(v); }
     }
     atomicAdd(&s_cnt, mine);
-    for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off, 64);
+    lsum = wave_xor_sum(lsum);
     if ((tid & 63) == 0) s_red[tid >> 6] = lsum;
     __syncthreads();
     const int nv = s_cnt;

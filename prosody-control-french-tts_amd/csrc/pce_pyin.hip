@@ -18,6 +18,7 @@
 // Host-computed tables (numpy, so that every constant has the bits the restatement uses): thresholds, beta
 // probabilities and their prefix sums, Boltzmann factors, log transition rows.
 #include "pce_internal.h"
+#include "pce_wave.h"
 
 namespace {
 
@@ -33,19 +34,6 @@ struct PyPlan {
 };
 struct PyObs { int n; int status; double voiced_prob; double log_unvoiced; };   // per frame header
 // per frame: header + PY_MAXTR (bin, log-prob) pairs
-
-__device__ __forceinline__ double shfl_up_f64(double v, int d)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_up(lo, d, 64); hi = __shfl_up(hi, d, 64);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double shfl_f64(double v, int src)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl(lo, src, 64); hi = __shfl(hi, src, 64);
-    return __hiloint2double(hi, lo);
-}
 
 template <int NG>   // lag groups per lane (5 at 16 kHz, 12 at 44.1 kHz); 0: taken from the plan at run time
 __global__ __launch_bounds__(64 * PY_WPB) void k_pyin_frames(const int16_t *__restrict__ pcm, const int64_t *__restrict__ clip_off,
@@ -169,6 +157,7 @@ __global__ __launch_bounds__(64 * PY_WPB) void k_pyin_frames(const int16_t *__re
             }
             int nb = 0;                                             // thresholds NOT above the minimum: !(h < thr[k])
             for (int k = lane; k < P.n_thr; k += 64) nb += !(best < thr[k]);
+            // (written out, not wave_xor_sum: this butterfly shares its partner indices lane ^ o with the arg-min above; __shfl_xor forms six of its own, 6 VGPRs)
             for (int o = 32; o > 0; o >>= 1) nb += __shfl(nb, lane ^ o, 64);
             const double extra = P.no_trough_prob * tab[P.o_bprefix + nb];
 #pragma unroll

@@ -24,6 +24,7 @@
 //
 // Roofline: k_stft_db is HBM-write bound: 513*4 B written per frame, 512 B of PCM read.
 #include "pce_internal.h"
+#include "pce_wave.h"
 #include <cmath>
 
 namespace {
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_stft_max(const int16_t *__restri
             stft_frame<true>(pcm, cl, frame, hop, C, zbuf[wv], lane, [&](int, float mag2) { m = fmaxf(m, mag2); });
         }
     }
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    m = wave_xor_max(m);
     if (lane == 0) red[wv] = m;
     __syncthreads();
     if (tid == 0 && bid < n_tiles) {
@@ -293,7 +294,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_stft_raw(const int16_t *__restri
             tile[k][fr] = 10.0f * __log10f(fmaxf(amin2, pw));
         });
     }
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    m = wave_xor_max(m);
     if (lane == 0) red[wv] = m;
     __syncthreads();
     if (tid == 0) {

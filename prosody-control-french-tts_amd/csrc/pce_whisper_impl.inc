@@ -30,6 +30,7 @@
 //                    online softmax in registers with DPP row reductions, K / V^T tiles in LDS
 // The residual stream is fp32, every GEMM operand op_t.  Roofline: MFMA (dense op_t).
 #include "pce_internal.h"
+#include "pce_wave.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256) PCE_NO_PK_F32 void k_logmel_frames(const int16
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
     }
-    for (int off = 32; off > 0; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off, 64));
+    vmax = wave_xor_max(vmax);
     if (lane == 0) atomicMax(clip_max + clip, f32_order_key(vmax));
 }
 
@@ -819,24 +820,6 @@ template <> __device__ __forceinline__ void ln_store4<op_t>(op_t *p, float a, fl
     *reinterpret_cast<opx4 *>(p) = v;
 }
 
-// The sum of a value over the wave, the same bits in every lane, without LDS round trips: DPP inside the 16-lane rows (lane pairs, quads,
-// half rows, rows: a balanced tree), v_readlane across the four rows.
-template <int CTRL> __device__ __forceinline__ float dpp_f32(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float wave_allsum_f32(float v)
-{
-    v += dpp_f32<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_f32<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += dpp_f32<0x141>(v);     // row_half_mirror
-    v += dpp_f32<0x140>(v);     // row_mirror
-    const int b = __builtin_bit_cast(int, v);
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-    return (r0 + r1) + (r2 + r3);
-}
-
 constexpr int LN_D_MAX = 2048;
 template <class OUT, int NV = 5>
 __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *__restrict__ w, const float *__restrict__ b,
@@ -858,7 +841,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *
         if (round_in16) v[i] = make_float4((float)(op_t)v[i].x, (float)(op_t)v[i].y, (float)(op_t)v[i].z, (float)(op_t)v[i].w);
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    s = wave_allsum_f32(s);
+    s = wave_dpp_sum_f32(s);
     const float mean = s / (float)d;
     float q = 0.f;
 #pragma unroll
@@ -868,7 +851,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *
             q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
         }
     }
-    q = wave_allsum_f32(q);
+    q = wave_dpp_sum_f32(q);
     const float inv = rsqrtf(q / (float)d + eps);
 #pragma unroll
     for (int i = 0; i < NV; i++) {
@@ -1268,14 +1251,14 @@ __global__ __launch_bounds__(1024) void k_self_attn1w(SelfAttn1Args A)
         dd += __shfl_xor(dd, 1, 64); dd += __shfl_xor(dd, 2, 64); dd += __shfl_xor(dd, 4, 64);
         s_new = dd; m = fmaxf(m, dd);
     }
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_xor_max(m);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
     float sum = 0.f;
     for (int t = lane; t < Sc; t += 64) {
         const float pv = __expf(sp[t] - m);
         sp[t] = pv; sum += pv;
     }
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = wave_xor_sum(sum);
     const float p_new = __expf(s_new - m);                       // (the same value in every lane)
     sum += p_new;
     const float inv = 1.0f / sum;
@@ -1438,7 +1421,7 @@ __global__ __launch_bounds__(1024) void k_cross_attn1w(Attn1Args A)
         m = fmaxf(m, d);
         if (lane == 0) sp[pos] = d;
     }
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_xor_max(m);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
     float sum = 0.f;
     const int Sp = (Sk + 511) & ~511;
@@ -1446,7 +1429,7 @@ __global__ __launch_bounds__(1024) void k_cross_attn1w(Attn1Args A)
         const float pv = t < Sk ? __expf(sp[t] - m) : 0.f;
         sp[t] = pv; sum += pv;
     }
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = wave_xor_sum(sum);
     const float inv = 1.0f / sum;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
     const int np = Sp >> 9;
@@ -1510,7 +1493,7 @@ __global__ __launch_bounds__(1024) void k_cross_attn1w(Attn1Args A)
                 if (j < np)
 #pragma unroll
                     for (int e = 0; e < 8; e++) a = fmaf(pr[j][e], (float)vv[r][j][e], a);
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+            a = wave_xor_sum(a);
             if (app) a = fmaf(p_new, __builtin_bit_cast(float, __builtin_amdgcn_readlane(v_new_bits, r4 + r)), a);
             if (lane == r4 + r) keep = a * inv;
         }
@@ -1587,14 +1570,14 @@ __global__ __launch_bounds__(DR_T) void k_decode_rules(const float *__restrict__
         float m = -__builtin_huge_valf();
 #pragma unroll
         for (int k = 0; k < DR_K; k++) if (tid + k * DR_T < R.n_vocab) m = fmaxf(m, xr[k]);
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        m = wave_xor_max(m);
         if (lane == 0) r_f[0][wv] = m;
         __syncthreads();
         m = dr_max(r_f[0]);
         float se = 0.f;
 #pragma unroll
         for (int k = 0; k < DR_K; k++) if (tid + k * DR_T < R.n_vocab) se += __expf(xr[k] - m);
-        for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+        se = wave_xor_sum(se);
         if (lane == 0) r_f[1][wv] = se;
         __syncthreads();
         if (tid == 0) probe_prob[clip] = __expf(x[R.probe] - m) / dr_sum(r_f[1]);
@@ -1633,7 +1616,7 @@ __global__ __launch_bounds__(DR_T) void k_decode_rules(const float *__restrict__
         xr[k] = a;
         if (v < R.ts_begin) m_text = fmaxf(m_text, a); else m_ts = fmaxf(m_ts, a);
     }
-    for (int o = 32; o > 0; o >>= 1) { m_text = fmaxf(m_text, __shfl_xor(m_text, o, 64)); m_ts = fmaxf(m_ts, __shfl_xor(m_ts, o, 64)); }
+    m_text = wave_xor_max(m_text); m_ts = wave_xor_max(m_ts);
     if (lane == 0) { r_f[0][wv] = m_text; r_f[1][wv] = m_ts; }
     __syncthreads();
     m_text = dr_max(r_f[0]);
@@ -1647,7 +1630,7 @@ __global__ __launch_bounds__(DR_T) void k_decode_rules(const float *__restrict__
 #pragma unroll
         for (int k = 0; k < DR_K; k++) { const int v = tid + k * DR_T; if (v >= R.ts_begin && v < R.n_vocab) se += __expf(xr[k] - m_ts); }
     }
-    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o, 64);
+    se = wave_xor_sum(se);
     if (lane == 0) r_f[0][wv] = se;
     __syncthreads();
     if (tid == 0) {
@@ -1704,7 +1687,7 @@ __global__ __launch_bounds__(DR_T) void k_decode_rules(const float *__restrict__
 #pragma unroll
             for (int k = 0; k < DR_K; k++) { const int v = tid + k * DR_T; if (v >= v_lo && v < R.n_vocab) se2 += __expf(xr[k] - top); }
         }
-        for (int o = 32; o > 0; o >>= 1) se2 += __shfl_xor(se2, o, 64);
+        se2 = wave_xor_sum(se2);
         __syncthreads();
         if (lane == 0) r_f[1][wv] = se2;
         __syncthreads();
@@ -1740,7 +1723,7 @@ __global__ __launch_bounds__(LANG_T) void k_lang_probs(const op_t *__restrict__ 
 #pragma unroll
             for (int u = 0; u < 8; u++) acc = fmaf((float)e[u], s_x[col + u], acc);
         }
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        acc = wave_xor_sum(acc);
         if (lane == 0) s_logit[r] = acc;
     }
     __syncthreads();
@@ -1755,7 +1738,7 @@ __global__ __launch_bounds__(LANG_T) void k_lang_probs(const op_t *__restrict__ 
     }
     const float e0 = lane < n_lang ? expf(a0 - best) : 0.f, e1 = lane + 64 < n_lang ? expf(a1 - best) : 0.f;
     float sum = e0 + e1;
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    sum = wave_xor_sum(sum);
     float *p = probs + (int64_t)clip * n_lang;
     if (lane < n_lang) p[lane] = e0 / sum;
     if (lane + 64 < n_lang) p[lane + 64] = e1 / sum;
@@ -1765,16 +1748,6 @@ __global__ __launch_bounds__(LANG_T) void k_lang_probs(const op_t *__restrict__ 
 // softmax over the audio frames of the (scaled) cross-attention logits of one alignment head:
 // w[clip][sel][t][s] = softmax_s(q_t . k_s * 0.125 * qk_scale), s < F_c.  16 tokens per workgroup, 4 waves x 16
 // keys per 64-key tile on v_mfma_f32_16x16x32_bf16, two passes (row max / sum, then normalised write).
-__device__ __forceinline__ float row_max16(float v)      // over the 16 lanes of a DPP row, result in every lane
-{
-    v = fmaxf(v, dpp_f32<0xB1>(v)); v = fmaxf(v, dpp_f32<0x4E>(v)); v = fmaxf(v, dpp_f32<0x141>(v)); v = fmaxf(v, dpp_f32<0x140>(v));
-    return v;
-}
-__device__ __forceinline__ float row_sum16f(float v)
-{
-    v += dpp_f32<0xB1>(v); v += dpp_f32<0x4E>(v); v += dpp_f32<0x141>(v); v += dpp_f32<0x140>(v);
-    return v;
-}
 struct AlignArgs {
     const op_t *q; int64_t q_ld;             // decoder cross-attention queries [clips * T_pad][d]
     const op_t *k; int64_t k_ld;             // audio keys of this layer      [clips * 1500][d]
@@ -1818,10 +1791,10 @@ __global__ __launch_bounds__(256) void k_align_scores(AlignArgs A)
             for (int r4 = 0; r4 < 4; r4++) {
                 const float v = valid ? acc[r4] * A.scale : -1e30f;
                 if (pass == 0) {
-                    const float mx = row_max16(v);
+                    const float mx = dpp_row_max<16>(v);
                     const float m_new = fmaxf(m_run[r4], mx);
                     const float e = valid ? __expf(v - m_new) : 0.f;
-                    l_run[r4] = l_run[r4] * __expf(m_run[r4] - m_new) + row_sum16f(e);
+                    l_run[r4] = l_run[r4] * __expf(m_run[r4] - m_new) + dpp_row_sum<16>(e);
                     m_run[r4] = m_new;
                 } else if (valid && t0 + fq * 4 + r4 < T) {
                     wb[(int64_t)(t0 + fq * 4 + r4) * A.F_pad + s0 + fr] = __expf(v - m_run[r4]) / l_run[r4];

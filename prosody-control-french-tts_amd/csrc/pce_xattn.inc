@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) PCE_NO_PK_F32 void k_xq_fused(const float *__r
                 float sm = 0.f;
 #pragma unroll
                 for (int i = 0; i < NI; i++) sm += (v[r][i].x + v[r][i].y) + (v[r][i].z + v[r][i].w);
-                sm = wave_allsum_f32(sm);
+                sm = wave_dpp_sum_f32(sm);
                 const float mean = sm / (float)D;
                 float q = 0.f;
 #pragma unroll
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256) PCE_NO_PK_F32 void k_xq_fused(const float *__r
                         const float a0 = v[r][i].x - mean, a1 = v[r][i].y - mean, a2 = v[r][i].z - mean, a3 = v[r][i].w - mean;
                         q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
                     }
-                q = wave_allsum_f32(q);
+                q = wave_dpp_sum_f32(q);
                 const float inv = rsqrtf(q / (float)D + 1e-5f);
 #pragma unroll
                 for (int i = 0; i < NI; i++) {
