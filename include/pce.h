@@ -57,9 +57,11 @@ extern "C" {
  * 9 = pce_silence_run / _shape / _fetch (pydub's detect_silence over slices, exact integers) and their three kernel ids;
  * 10 = pce_seqmatch / pce_seqmatch_align (difflib.SequenceMatcher's matched totals for batches of string pairs, and the fuzzy alignment of
  * "Compare Breaks" on them) and their two kernel ids;
- * 11 = pce_whisper_detect_language (openai-whisper's detect_language for the encoded batch: the language rows of the output projection only). */
+ * 11 = pce_whisper_detect_language (openai-whisper's detect_language for the encoded batch: the language rows of the output projection only);
+ * 12 = pce_selftest_gemm_resid; the 16-bit-stream encoder adds its residuals in the attention-projection / fc2 GEMM epilogues (same bits; a context
+ * created with PCE_RESID_EPILOGUE=0 keeps the stored branch outputs and the adds in the LayerNorm passes; =2 fuses fc2 only, for A/B runs). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 11
+#define PCE_API_MINOR 12
 
 typedef struct pce_ctx pce_ctx;
 
@@ -339,6 +341,9 @@ int pce_whisper_encode_run(pce_ctx *ctx);
  * (rows_per_clip rows each, key axis padded to vt_sp): out[(clip N + n) vt_sp + t].  N % 256 == 0, K % 64 == 0. */
 int pce_selftest_gemm(pce_ctx *ctx, const uint16_t *A, const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, int32_t epilogue,
                       int32_t rows_per_clip, int32_t vt_sp, uint16_t *out);
+/* The same kernel with its residual epilogue, in place as the encoder's attention projection and fc2 run it on the 16-bit residual stream:
+ * resid_inout[M][N] = r16(resid_inout + r16(A B^T + bias)) (r16: rounding to the context's 16-bit operand type; bit patterns in and out). */
+int pce_selftest_gemm_resid(pce_ctx *ctx, const uint16_t *A, const uint16_t *B, const float *bias, uint16_t *resid_inout, int32_t M, int32_t N, int32_t K);
 /* Self-test of the attention kernel (64-wide heads; csrc/pce_whisper_impl.inc k_attention_lean16) on host arrays of bf16 bit patterns: clips x
  * heads independent problems, q [clips][q_len][heads * 64], k and v [clips][k_len][heads * 64], out like q; softmax(q k^T / 8) v with the
  * causal mask when causal != 0.  mode 0: the kernel as the engine runs it (fixed softmax reference, exact fallback), 1: its exact

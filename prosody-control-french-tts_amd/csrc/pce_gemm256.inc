@@ -25,6 +25,9 @@
 //     lane ends up with 8 CONSECUTIVE COLUMNS of one row: rows leave as 16-byte buffer stores straight from the
 //     accumulators.  The transposed-V variant does the mirror image (A rows permuted, operands in natural order): a
 //     lane holds 8 consecutive ROWS (key positions) of one column;
+//   * FEPI_RESID: the row-major epilogue also ADDS the tile to a 16-bit residual matrix, in place (C = R): the encoder's attention projection and fc2
+//     update the fp16 residual stream themselves, x = r16(x + r16(acc + bias)), so no branch output is stored and the LayerNorm passes read the
+//     stream once (k_add_layernorm without deltas); the tile's 16 residual pieces are loaded into the fragment registers, dead between two tiles;
 //   * the bias vector lives in LDS behind the ring; the accumulators are cleared after the epilogue (starting a tile from the zero
 //     constant is NOT safe: see the note in the K loop); workgroups start staggered over a tile time so that their store bursts do not coincide.
 //
@@ -51,7 +54,7 @@ constexpr int F_N_MAX = 6144;            // widest output launch_gemm_flat takes
 constexpr bool F_PINGPONG = true;                          // K-step form: four phases, wave rows one barrier apart (kstep_pp) / two barriers, rows in step (kstep)
 constexpr int F_HALF = 128 * F_K;                          // elements of a half-tile (16 KB)
 constexpr int F_RING_BYTES = 8 * F_HALF * 2;
-enum { FEPI_BF16 = 0, FEPI_GELU = 1, FEPI_VT = 2, FEPI_SPLIT = 3 };
+enum { FEPI_BF16 = 0, FEPI_GELU = 1, FEPI_VT = 2, FEPI_SPLIT = 3, FEPI_RESID = 4 };
 // FEPI_SPLIT (round 3): ONE launch for a projection whose leading columns leave row-major and whose trailing columns leave as the
 // transposed-V image (encoder Q | K | V: N = 3 d, cross-attention K | V: N = 2 d).  The A panel is swept once instead of twice and the
 // tile list of the two products is one stream (no second launch tail).  A tile of the transposed part is computed as the TRANSPOSED
@@ -92,6 +95,7 @@ struct FArgs {
     int S, vt_sp;                         // FEPI_VT: rows per clip, padded key axis of the V^T image: C[(clip * N + n) * vt_sp + t]
     int sm, sn, stagger;
     op_t *C2; int vt_n0;                  // FEPI_SPLIT: columns >= vt_n0 (a multiple of 256) go to the V^T image C2[(clip * (N - vt_n0) + n - vt_n0) * vt_sp + t]
+    const op_t *R;                        // FEPI_RESID: the residual rows, pitch ldc like C; may BE C (the encoder's stream, updated in place)
 };
 
 template <int N> __device__ __forceinline__ void f_wait_vm() { __builtin_amdgcn_s_waitcnt(((N >> 4) << 14) | 0x0F70 | (N & 15)); }
@@ -211,9 +215,40 @@ __global__ __launch_bounds__(F_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
     op_t *const vt_ptr = SPLIT ? P.C2 : P.C;
     const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(P.C, 0, HAS_RM ? (int)((unsigned)M * (unsigned)P.ldc * 2u) : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(vt_ptr, 0, HAS_VT ? (int)((unsigned)(M / P.S) * (unsigned)Nv * (unsigned)P.vt_sp * 2u) : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(const_cast<op_t *>(EPI == FEPI_RESID ? P.R : P.C), 0,
+                                                                         EPI == FEPI_RESID ? (int)((unsigned)M * (unsigned)P.ldc * 2u) : 0, 0x00020000);
     const int voffC = (fr * P.ldc + fq * 8) * 2, voffV = (fr * P.vt_sp + fq * 8) * 2;
     // row-major tile.  lane: row fr of the row block, 8 consecutive columns fq * 8 .. + 7 of the wave's 32-column group
+    // FEPI_RESID: C[m][n] = (op_t)((float)R[m][n] + (float)(op_t)(acc + bias)): the rounded branch output added to the residual row and rounded
+    // again, which is what k_add_layernorm computes from a stored branch output (x1 = r16(x + delta)), bit for bit.  The tile's 16 residual
+    // pieces are loaded first, every lane the 16 bytes it will store (same resource size, same offsets: rows past M read zeros and their
+    // stores are dropped), non-temporal: the stream is read once.  They take 64 VGPRs, and 64 are free here: in the ping-pong K-step every
+    // fragment is re-read from LDS in phases 1-3, so FFrags is dead between a tile's last K-step and the next tile's first.
+    // R may be C: a 16-byte piece is read and written by the same lane, the store takes its data from the load, and no other workgroup
+    // touches the tile.
+    // The counted waits that follow an epilogue (after_stores 1 and 2, and the plain count of a one-step K loop) stay as they are.  They
+    // rely on ONE property of the in-order vmcnt queue: behind the last LDS-DMA instruction issued before the epilogue sit AT LEAST EPI_OPS
+    // operations of the epilogue.  Loads only add to that number, so no wait can return early.  And no wait returns later either: piece i is
+    // consumed by store i, so hipcc retires load i (and with it, in order, everything older: the other row's half-tiles of K-steps s + 1
+    // and s + 2, issued up to four phases ago) before store i; when the epilogue ends, the queue holds its stores and nothing older, the
+    // parent's state exactly.  after_stores == 1 then leaves this K-step's 8 DMA instructions + 16 stores in flight, after_stores == 2 waits
+    // for A-bottom(s + 1) and so for every store; with nk == 1 the plain vmcnt(6) of the next tile's only K-step retires the stores.
+    // (Issuing the first four loads a phase earlier, in phase 4 of the tile's last K-step where the B-right fragments are dead, with that step's
+    // wait raised to vmcnt(10), measured 0.3 ms of GEMM per step less in the kernel statistics and nothing in the step time: profiles/r15.)
     auto store_rm = [&](int m0, int n0) {
+        u32x4 rv[2][2][4];
+        if constexpr (EPI == FEPI_RESID) {
+#pragma unroll
+            for (int hB = 0; hB < 2; hB++)
+#pragma unroll
+                for (int hA = 0; hA < 2; hA++)
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        const unsigned soff = ((unsigned)(m0 + hA * 128 + wr * 64 + i * 16) * (unsigned)P.ldc + (unsigned)(n0 + hB * 128 + wc * 32)) * 2u;
+                        rv[hB][hA][i] = __builtin_amdgcn_raw_buffer_load_b128(rsR, voffC, (int)soff, 2 /* nt */);
+                    }
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
         for (int hB = 0; hB < 2; hB++) {
             const float *bp = sbias + n0 + hB * 128 + wc * 32 + fq * 8;
@@ -230,6 +265,11 @@ __global__ __launch_bounds__(F_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
                     if (EPI == FEPI_GELU) gelu_exact8(t);
 #pragma unroll
                     for (int e = 0; e < 8; e++) o[e] = (op_t)t[e];
+                    if constexpr (EPI == FEPI_RESID) {
+                        const opx8 r = __builtin_bit_cast(opx8, rv[hB][hA][i]);
+#pragma unroll
+                        for (int e = 0; e < 8; e++) o[e] = (op_t)((float)r[e] + (float)o[e]);
+                    }
                     const unsigned soff = ((unsigned)(m0 + hA * 128 + wr * 64 + i * 16) * (unsigned)P.ldc + (unsigned)(n0 + hB * 128 + wc * 32)) * 2u;
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsC, voffC, (int)soff, F_STORE_AUX);
                     __builtin_amdgcn_sched_barrier(0);
@@ -537,6 +577,73 @@ __global__ __launch_bounds__(256) void k_add_layernorm(const RIN *resid_in, ROUT
                         y2 = (v[i].z - mean) * inv * ww.z + bb.z, y3 = (v[i].w - mean) * inv * ww.w + bb.w;
             ln_store4<OUT>(out + row * d + 4 * idx, y0, y1, y2, y3);
             if (out_bf16) ln_store4<op_t>(out_bf16 + row * d + 4 * idx, y0, y1, y2, y3);
+        }
+    }
+}
+
+// k_add_layernorm with nothing to add: LayerNorm of the 16-bit stream as the FEPI_RESID epilogues left it (the two passes of a layer on the fused
+// encoder path; no stream write).  The statistics are k_add_layernorm's, sum for sum.  One load of 8 bytes per lane in flight per wave left this
+// pass latency-bound, so a wave takes LN0_ROWS consecutive rows and issues every load of them before the first use.
+constexpr int LN0_ROWS = 2;
+template <class OUT, int NV = 5>
+__global__ __launch_bounds__(256) void k_add_layernorm0(const op_t *__restrict__ x, const float *__restrict__ w, const float *__restrict__ b, int64_t rows, int d,
+                                                       OUT *__restrict__ out, float eps, op_t *__restrict__ out_bf16 = nullptr)
+{
+    const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * LN0_ROWS;
+    const int lane = threadIdx.x & 63;
+    if (row0 >= rows) return;
+    typedef __attribute__((ext_vector_type(4))) op_t opx4;
+    const int nv = d >> 2;
+    opx4 raw[LN0_ROWS][NV];
+    float4 ww[NV], bb[NV];                                                  // (read before the statistics too: a load between two rows' stores waits for the stores)
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+        const int idx = lane + 64 * i;
+        ww[i] = bb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (idx < nv) { ww[i] = reinterpret_cast<const float4 *>(w)[idx]; bb[i] = reinterpret_cast<const float4 *>(b)[idx]; }
+    }
+#pragma unroll
+    for (int r = 0; r < LN0_ROWS; r++) {
+        const int64_t row = row0 + r < rows ? row0 + r : rows - 1;         // (a last odd row is read twice and written once)
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            const int idx = lane + 64 * i;
+            raw[r][i] = opx4{(op_t)0.f, (op_t)0.f, (op_t)0.f, (op_t)0.f};
+            if (idx < nv) raw[r][i] = __builtin_nontemporal_load(reinterpret_cast<const opx4 *>(x + row * d) + idx);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < LN0_ROWS; r++) {
+        const int64_t row = row0 + r;
+        if (row >= rows) break;
+        float4 v[NV];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            v[i] = make_float4((float)raw[r][i][0], (float)raw[r][i][1], (float)raw[r][i][2], (float)raw[r][i][3]);
+            s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+        }
+        s = wave_dpp_sum_f32(s);
+        const float mean = s / (float)d;
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            if (lane + 64 * i < nv) {
+                const float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
+                q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+            }
+        }
+        q = wave_dpp_sum_f32(q);
+        const float inv = rsqrtf(q / (float)d + eps);
+#pragma unroll
+        for (int i = 0; i < NV; i++) {
+            const int idx = lane + 64 * i;
+            if (idx < nv) {
+                const float y0 = (v[i].x - mean) * inv * ww[i].x + bb[i].x, y1 = (v[i].y - mean) * inv * ww[i].y + bb[i].y,
+                            y2 = (v[i].z - mean) * inv * ww[i].z + bb[i].z, y3 = (v[i].w - mean) * inv * ww[i].w + bb[i].w;
+                ln_store4<OUT>(out + row * d + 4 * idx, y0, y1, y2, y3);
+                if (out_bf16) ln_store4<op_t>(out_bf16 + row * d + 4 * idx, y0, y1, y2, y3);
+            }
         }
     }
 }

@@ -16,6 +16,7 @@ PCE_BOTH(int, pce_selftest_attention, (pce_ctx *, const uint16_t *, const uint16
 PCE_BOTH(int, pce_selftest_attention_ragged, (pce_ctx *, const uint16_t *, const uint16_t *, const uint16_t *, int32_t, int32_t, const int32_t *, const int32_t *, int32_t, int32_t, uint16_t *, int64_t, int32_t *))
 PCE_BOTH(int, pce_selftest_attn1, (pce_ctx *, int32_t, int32_t, int32_t, const uint16_t *, int64_t, uint16_t *, int64_t, uint16_t *, int64_t, const int32_t *, const int32_t *, const int32_t *, int32_t, uint16_t *, int64_t))
 PCE_BOTH(int, pce_selftest_gemm, (pce_ctx *, const uint16_t *, const uint16_t *, const float *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
+PCE_BOTH(int, pce_selftest_gemm_resid, (pce_ctx *, const uint16_t *, const uint16_t *, const float *, uint16_t *, int32_t, int32_t, int32_t))
 PCE_BOTH(int, pce_selftest_xattn, (pce_ctx *, const float *, const float *, const float *, const uint16_t *, const float *, const uint16_t *, const uint16_t *, const float *, const uint16_t *, const int32_t *, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
 PCE_BOTH(int, pce_selftest_gemm_tiled, (pce_ctx *, int32_t, int32_t, const uint16_t *, int64_t, int64_t, int64_t, int32_t, const uint16_t *, const float *, int32_t, int32_t,
                                          int32_t, void *, int64_t, int64_t, int64_t, const float *, int32_t, int32_t, int32_t, int32_t, uint16_t *, int64_t, int32_t *))
@@ -78,6 +79,10 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
                       int32_t vt_sp, uint16_t *out)
 {
     return PCE_FWD(pce_selftest_gemm, c, A, B, bias, M, N, K, epilogue, rows_per_clip, vt_sp, out);
+}
+int pce_selftest_gemm_resid(pce_ctx *c, const uint16_t *A, const uint16_t *B, const float *bias, uint16_t *resid_inout, int32_t M, int32_t N, int32_t K)
+{
+    return PCE_FWD(pce_selftest_gemm_resid, c, A, B, bias, resid_inout, M, N, K);
 }
 int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk, const uint16_t *wv,
                        const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads, int32_t workgroups_per_clip, uint16_t *out)

@@ -52,6 +52,7 @@
 #define pce_selftest_attention_ragged PCE_WFN(pce_selftest_attention_ragged)
 #define pce_selftest_attn1 PCE_WFN(pce_selftest_attn1)
 #define pce_selftest_gemm PCE_WFN(pce_selftest_gemm)
+#define pce_selftest_gemm_resid PCE_WFN(pce_selftest_gemm_resid)
 #define pce_whisper_decoder_load PCE_WFN(pce_whisper_decoder_load)
 #define pce_whisper_align_run PCE_WFN(pce_whisper_align_run)
 #define pce_whisper_align_fetch PCE_WFN(pce_whisper_align_fetch)
@@ -823,10 +824,12 @@ template <> __device__ __forceinline__ void ln_store4<op_t>(op_t *p, float a, fl
 constexpr int LN_D_MAX = 2048;
 template <class OUT, int NV = 5>
 __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *__restrict__ w, const float *__restrict__ b,
-                                                  int64_t rows, int d, OUT *__restrict__ out, float eps = 1e-5f, float *out2 = nullptr, int round_in16 = 0)
+                                                  int64_t rows, int d, OUT *__restrict__ out, float eps = 1e-5f, float *out2 = nullptr, int round_in16 = 0,
+                                                  op_t *__restrict__ in16_out = nullptr)
 {   // out2 (optional, may alias x): the same values in fp32 -- the post-LN residual stream of the BERT layers
     // round_in16: the input is taken as rounded to op_t (the first LayerNorm of the encoder in the 16-bit-stream mode: the reference's stem output
     // IS fp16 -- gelu(conv2) + positional embedding in half precision -- and k_add_layernorm's first-layer form rounds the same values the same way)
+    // in16_out (with round_in16): the rounded input itself, as op_t rows -- the 16-bit residual stream the GEMM epilogues of layer 0 add to
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= rows) return;
@@ -839,6 +842,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const float *x, const float *
         const int idx = lane + 64 * i;
         v[i] = idx < nv ? xr[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
         if (round_in16) v[i] = make_float4((float)(op_t)v[i].x, (float)(op_t)v[i].y, (float)(op_t)v[i].z, (float)(op_t)v[i].w);
+        if (in16_out && idx < nv) ln_store4<op_t>(in16_out + row * d + 4 * idx, v[i].x, v[i].y, v[i].z, v[i].w);
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
     s = wave_dpp_sum_f32(s);
@@ -2057,7 +2061,7 @@ static bool gemm_flat_offsets_fit(int64_t M, int64_t N, int64_t K, int64_t ldc, 
 // (the caller then takes the tiled kernels).
 template <int EPI>
 bool launch_gemm_flat(pce_ctx *c, const op_t *A, const op_t *B, const float *bias, op_t *C, int M, int N, int K, int ldc, int S = 1, int vt_sp = 0,
-                      int prof_id = PCE_K_GEMM_FLAT, op_t *C2 = nullptr, int vt_n0 = 0)
+                      int prof_id = PCE_K_GEMM_FLAT, op_t *C2 = nullptr, int vt_n0 = 0, const op_t *R = nullptr)
 {
     // 32-bit byte offsets: the kernel addresses the row tiles up to the PADDED tile count (16 row tiles per supertile); rows past M must
     // fall outside the buffer resources (loads read zeros, stores are dropped), which only holds while their offsets do not wrap
@@ -2066,10 +2070,11 @@ bool launch_gemm_flat(pce_ctx *c, const op_t *A, const op_t *B, const float *bia
     // results are compared across batch compositions and rank counts, tests/test_gpu_world2.py)
     if (!c->gemm_flat || N % F_T || K % F_K || M < 1 || N > F_N_MAX || (HAS_VT && (S % 4 || S < F_T))) return false;
     if (EPI == FEPI_SPLIT && (!C2 || vt_n0 <= 0 || vt_n0 >= N || vt_n0 % F_T)) return false;
+    if (EPI == FEPI_RESID && !R) return false;
     if (HAS_RM && !gemm_flat_offsets_fit(M, N, K, ldc, 0, 0)) return false;
     if (HAS_VT && !gemm_flat_offsets_fit(M, N - vt_n0, K, 0, S, vt_sp)) return false;
     FArgs P{};
-    P.A = A; P.B = B; P.bias = bias; P.C = C; P.M = M; P.N = N; P.K = K; P.ldc = ldc; P.S = S; P.vt_sp = vt_sp; P.C2 = C2; P.vt_n0 = vt_n0;
+    P.A = A; P.B = B; P.bias = bias; P.C = C; P.M = M; P.N = N; P.K = K; P.ldc = ldc; P.S = S; P.vt_sp = vt_sp; P.C2 = C2; P.vt_n0 = vt_n0; P.R = R;
     const int tiles_n = N / F_T;
     P.sn = 1;
     for (int cand : {4, 3, 2}) if (tiles_n % cand == 0) { P.sn = cand; break; }
@@ -2171,11 +2176,11 @@ void launch_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, const 
 // ---- LayerNorm launches: four rows (waves) per workgroup, the register form by width (k_layernorm); d <= LN_D_MAX, d % 4 == 0 (the loaders)
 template <class OUT>
 static void launch_layernorm(pce_ctx *c, const float *x, const float *w, const float *b, int64_t rows, int d, OUT *out, float eps = 1e-5f,
-                             float *out2 = nullptr, int round_in16 = 0)
+                             float *out2 = nullptr, int round_in16 = 0, op_t *in16_out = nullptr)
 {
     const dim3 grid((unsigned)div_up(rows, 4)), block(256);
-    if (d <= 1280) hipLaunchKernelGGL((k_layernorm<OUT, 5>), grid, block, 0, c->stream, x, w, b, rows, d, out, eps, out2, round_in16);
-    else hipLaunchKernelGGL((k_layernorm<OUT, 8>), grid, block, 0, c->stream, x, w, b, rows, d, out, eps, out2, round_in16);
+    if (d <= 1280) hipLaunchKernelGGL((k_layernorm<OUT, 5>), grid, block, 0, c->stream, x, w, b, rows, d, out, eps, out2, round_in16, in16_out);
+    else hipLaunchKernelGGL((k_layernorm<OUT, 8>), grid, block, 0, c->stream, x, w, b, rows, d, out, eps, out2, round_in16, in16_out);
 }
 template <class OUT, class RIN, class ROUT>
 static void launch_add_layernorm(pce_ctx *c, const RIN *resid_in, ROUT *resid_out, const op_t *delta, const op_t *delta2, int write_resid, const float *w,
@@ -2186,6 +2191,14 @@ static void launch_add_layernorm(pce_ctx *c, const RIN *resid_in, ROUT *resid_ou
         hipLaunchKernelGGL((k_add_layernorm<OUT, RIN, ROUT, 5>), grid, block, 0, c->stream, resid_in, resid_out, delta, delta2, write_resid, w, b, rows, d, out, eps, out_bf16);
     else
         hipLaunchKernelGGL((k_add_layernorm<OUT, RIN, ROUT, 8>), grid, block, 0, c->stream, resid_in, resid_out, delta, delta2, write_resid, w, b, rows, d, out, eps, out_bf16);
+}
+
+template <class OUT>
+static void launch_add_layernorm0(pce_ctx *c, const op_t *x, const float *w, const float *b, int64_t rows, int d, OUT *out, float eps, op_t *out_bf16)
+{
+    const dim3 grid((unsigned)div_up(rows, 4 * LN0_ROWS)), block(256);
+    if (d <= 1280) hipLaunchKernelGGL((k_add_layernorm0<OUT, 5>), grid, block, 0, c->stream, x, w, b, rows, d, out, eps, out_bf16);
+    else hipLaunchKernelGGL((k_add_layernorm0<OUT, 8>), grid, block, 0, c->stream, x, w, b, rows, d, out, eps, out_bf16);
 }
 
 // ---- the encoder-output cross-attention of a decoding step (pce_xattn.inc), as the product and pce_selftest_xattn launch it --------------------
@@ -2267,6 +2280,7 @@ static int lds_optins(pce_ctx *c, WhisperState *w)
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_GELU>, A, flat));
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_VT>, A, flat));
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_SPLIT>, A, flat));
+    PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_flat<FEPI_RESID>, A, flat));
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_skinny<EPI_BF16>, A, S_LDS));
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_skinny<EPI_GELU_BF16>, A, S_LDS));
     PCE_HIP(c, hipFuncSetAttribute((const void *)k_gemm_skinny<EPI_RESID_F32>, A, S_LDS));
@@ -2521,22 +2535,37 @@ int pce_whisper_encode_run(pce_ctx *c)
     // plus the LayerNorm's read.
     const bool flat = c->gemm_flat && d % F_T == 0 && gemm_flat_offsets_fit(M, 4 * d, 4 * d, 4 * d, 0, 0) &&
                       gemm_flat_offsets_fit(M, d, d, 0, W_CTX, AT_SP);
-    if (flat) {
-        PCE_HIP(c, w->delta.reserve(sizeof(op_t) * (size_t)M * d)); PCE_HIP(c, w->delta2.reserve(sizeof(op_t) * (size_t)M * d));
-        PCE_HIP(c, w->d_enc_bf16.reserve(sizeof(op_t) * (size_t)M * d + 4096));
-    }
+    if (flat) PCE_HIP(c, w->d_enc_bf16.reserve(sizeof(op_t) * (size_t)M * d + 4096));
     // mid = the pass after the attention projection (x = resid + delta feeds ln2, the stream is not written), else the pass at the end of
     // the layer (x = (resid + delta) + delta2 is written back and feeds the next layer's ln1, or ln_post -> the fp32 encoder output)
     // resid16: the 16-bit residual stream of the flat path (fp16 operands only; pce_whisper_set_operands(PCE_OPERANDS_F16_RESID16)): layer 0 reads
     // the fp32 stem output and leaves the stream in w->resid16, the later layers read and write that
     const bool resid16 = flat && c->resid16 && PCE_OP_INDEX == 1;
     if (resid16) PCE_HIP(c, w->resid16.reserve(sizeof(op_t) * (size_t)M * d));
+    // fused (resid16 unless PCE_RESID_EPILOGUE=0 at pce_create): the attention projection and fc2 add their rounded output to the 16-bit stream in
+    // their epilogue (FEPI_RESID, in place in w->resid16: x1 = r16(x + r16(acc + bias)), x2 likewise -- the roundings k_add_layernorm makes), the
+    // two passes of a layer are LayerNorm only (one read of the stream, one write of ln_out) and no branch output is stored; layer 0's
+    // k_layernorm, which reads the fp32 stem output and rounds it on the way in, leaves that rounded copy in w->resid16
+    // (PCE_RESID_EPILOGUE=2, the per-shape A/B: only fc2 is fused; the attention projection stores its output and the pass after it adds it and writes
+    //  x1 back into the stream, which fc2's epilogue then reads)
+    const bool fused = resid16 && c->resid_epilogue != 0, fused_out = fused && c->resid_epilogue == 1;
+    if (flat && !fused_out) PCE_HIP(c, w->delta.reserve(sizeof(op_t) * (size_t)M * d));
+    if (flat && !fused) PCE_HIP(c, w->delta2.reserve(sizeof(op_t) * (size_t)M * d));
     auto add_ln = [&](size_t w_off, size_t b_off, bool mid, bool last, bool first_layer) {
         KernelTimer kt(c, PCE_K_ADD_LAYERNORM);
         const op_t *d2 = mid ? nullptr : w->delta2.as<op_t>();
         float *r32 = w->resid.as<float>(); op_t *r16 = w->resid16.as<op_t>();
         const float *lw = Wf + w_off, *lb = Wf + b_off;
         const int wr = mid ? 0 : 1;
+        if (fused && mid && !fused_out) {
+            launch_add_layernorm<op_t, op_t, op_t>(c, r16, r16, w->delta.as<op_t>(), nullptr, 1, lw, lb, M, d, w->ln_out.as<op_t>(), 1e-5f, nullptr);
+            return;
+        }
+        if (fused) {     // LayerNorm of the stream as the epilogues left it
+            if (last) launch_add_layernorm0<float>(c, r16, lw, lb, M, d, w->final_out.as<float>(), 1e-5f, w->d_enc_bf16.as<op_t>());
+            else launch_add_layernorm0<op_t>(c, r16, lw, lb, M, d, w->ln_out.as<op_t>(), 1e-5f, nullptr);
+            return;
+        }
         if (last) {      // ln_post: the fp32 encoder output + the op_t copy the decoder's cross K / V projections read
             float *fo = w->final_out.as<float>(); op_t *eo = w->d_enc_bf16.as<op_t>();
             if (!resid16) launch_add_layernorm<float, float, float>(c, r32, r32, w->delta.as<op_t>(), d2, 1, lw, lb, M, d, fo, 1e-5f, eo);
@@ -2553,7 +2582,8 @@ int pce_whisper_encode_run(pce_ctx *c)
         const WhisperState::Layer &ly = w->layers[(size_t)l];
         if (!flat || l == 0) {
             KernelTimer kt(c, PCE_K_LAYERNORM);
-            launch_layernorm<op_t>(c, w->resid.as<float>(), Wf + ly.ln1_w, Wf + ly.ln1_b, M, d, w->ln_out.as<op_t>(), 1e-5f, nullptr, resid16 ? 1 : 0);
+            launch_layernorm<op_t>(c, w->resid.as<float>(), Wf + ly.ln1_w, Wf + ly.ln1_b, M, d, w->ln_out.as<op_t>(), 1e-5f, nullptr, resid16 ? 1 : 0,
+                                   fused ? w->resid16.as<op_t>() : nullptr);
         }
         // Q | K go to the row-major [M][2d] buffer, V is written transposed per head: one launch sweeps the LayerNorm output once
         const bool done = flat && launch_gemm_flat<FEPI_SPLIT>(c, w->ln_out.as<op_t>(), Wb + ly.qkv_w, Wf + ly.qkv_b, w->qkv.as<op_t>(), (int)M, 3 * d, d, 2 * d,
@@ -2566,11 +2596,14 @@ int pce_whisper_encode_run(pce_ctx *c)
         launch_attention_rows(c, n, H, W_CTX, w->qkv.as<op_t>(), 2 * d, w->qkv.as<op_t>() + d, 2 * d, w->vt.as<op_t>(), AT_SP, row0, len, row0, len,
                               w->attn.as<op_t>(), 0, 4.0 * W_CTX * (double)W_CTX * d * n);
         if (flat) {
-            if (!launch_gemm_flat<FEPI_BF16>(c, w->attn.as<op_t>(), Wb + ly.out_w, Wf + ly.out_b, w->delta.as<op_t>(), (int)M, d, d, d, 1, 0, PCE_K_GEMM_FLAT_OUT))
+            op_t *const r16 = w->resid16.as<op_t>();
+            if (!(fused_out ? launch_gemm_flat<FEPI_RESID>(c, w->attn.as<op_t>(), Wb + ly.out_w, Wf + ly.out_b, r16, (int)M, d, d, d, 1, 0, PCE_K_GEMM_FLAT_OUT, nullptr, 0, r16)
+                        : launch_gemm_flat<FEPI_BF16>(c, w->attn.as<op_t>(), Wb + ly.out_w, Wf + ly.out_b, w->delta.as<op_t>(), (int)M, d, d, d, 1, 0, PCE_K_GEMM_FLAT_OUT)))
                 return pce_fail(c, PCE_E_LIMIT, "attention projection does not fit the 256 x 256 kernel");
             add_ln(ly.ln2_w, ly.ln2_b, true, false, l == 0);
             if (!launch_gemm_flat<FEPI_GELU>(c, w->ln_out.as<op_t>(), Wb + ly.m1_w, Wf + ly.m1_b, w->hidden.as<op_t>(), (int)M, 4 * d, d, 4 * d, 1, 0, PCE_K_GEMM_FLAT_FC1) ||
-                !launch_gemm_flat<FEPI_BF16>(c, w->hidden.as<op_t>(), Wb + ly.m2_w, Wf + ly.m2_b, w->delta2.as<op_t>(), (int)M, d, 4 * d, d, 1, 0, PCE_K_GEMM_FLAT_FC2))
+                !(fused ? launch_gemm_flat<FEPI_RESID>(c, w->hidden.as<op_t>(), Wb + ly.m2_w, Wf + ly.m2_b, r16, (int)M, d, 4 * d, d, 1, 0, PCE_K_GEMM_FLAT_FC2, nullptr, 0, r16)
+                        : launch_gemm_flat<FEPI_BF16>(c, w->hidden.as<op_t>(), Wb + ly.m2_w, Wf + ly.m2_b, w->delta2.as<op_t>(), (int)M, d, 4 * d, d, 1, 0, PCE_K_GEMM_FLAT_FC2)))
                 return pce_fail(c, PCE_E_LIMIT, "MLP does not fit the 256 x 256 kernel");
             if (l + 1 < L) add_ln(w->layers[(size_t)l + 1].ln1_w, w->layers[(size_t)l + 1].ln1_b, false, false, l == 0);
             else add_ln(w->lnp_w, w->lnp_b, false, true, l == 0);

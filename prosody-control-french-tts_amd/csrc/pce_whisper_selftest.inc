@@ -276,6 +276,34 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
     return rc;
 }
 
+// Self-test hook of the persistent 256 x 256 GEMM's residual epilogue (FEPI_RESID), in place as the encoder runs it:
+// resid_inout[M][N] = r16(resid_inout + r16(A B^T + bias)), 16-bit bit patterns of the context's operand type.
+int pce_selftest_gemm_resid(pce_ctx *c, const uint16_t *A, const uint16_t *B, const float *bias, uint16_t *resid_inout, int32_t M, int32_t N, int32_t K)
+{
+    if (!c || !A || !B || !resid_inout || M <= 0 || N <= 0 || K <= 0) return PCE_E_INVALID;
+    PCE_HIP(c, hipSetDevice(c->device));
+    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    DevBuf dA, dB, dC, dbias;
+    PCE_HIP(c, dA.reserve((size_t)M * K * 2)); PCE_HIP(c, dB.reserve((size_t)N * K * 2)); PCE_HIP(c, dC.reserve((size_t)M * N * 2)); PCE_HIP(c, dbias.reserve((size_t)N * 4));
+    PCE_HIP(c, hipMemcpyAsync(dA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dB.p, B, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
+    if (bias) PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dC.p, resid_inout, (size_t)M * N * 2, hipMemcpyHostToDevice, c->stream));
+    int rc = PCE_OK;
+    if (!launch_gemm_flat<FEPI_RESID>(c, dA.as<op_t>(), dB.as<op_t>(), bias ? dbias.as<float>() : nullptr, dC.as<op_t>(), M, N, K, N, 1, 0, PCE_K_GEMM_FLAT, nullptr, 0,
+                                      dC.as<op_t>()))
+        rc = pce_fail(c, PCE_E_LIMIT, "shape not handled by the 256 x 256 kernel (N %% 256, K %% 64)");
+    else {
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(resid_inout, dC.p, (size_t)M * N * 2, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = pce_fail(c, PCE_E_DEVICE, "selftest gemm (residual epilogue): %s", hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    pce_profile_collect(c);
+    return rc;
+}
+
 // Self-test hook of the tiled / few-row GEMM kernels through the product's own launch code (launch_gemm_kernel; see pce.h).  Every byte a launch
 // can address is checked against the caller's buffer lengths before anything is allocated.
 int pce_selftest_gemm_tiled(pce_ctx *c, int32_t kernel, int32_t epilogue, const uint16_t *A, int64_t a_len, int64_t lda, int64_t a_batch, int32_t batch,

@@ -138,7 +138,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
            "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
-           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_whisper_encode_fetch",
+           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
 
@@ -217,6 +217,7 @@ def load_library() -> C.CDLL:
     lib.pce_whisper_load.argtypes = [vp, C.POINTER(WhisperDims), vp, i64]
     lib.pce_whisper_encode_run.argtypes = [vp]
     lib.pce_selftest_gemm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.pce_selftest_gemm_resid.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32]
     lib.pce_selftest_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     lib.pce_selftest_attention_ragged.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i64, vp]
     lib.pce_selftest_attn1.argtypes = [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i64]
@@ -614,6 +615,22 @@ class ProsodyEngine:
         if split:
             return res[:M * split].reshape(M, split), res[M * split:].reshape(M // rows_per_clip, N - split, vt_sp)
         return res.reshape(M // rows_per_clip, N, vt_sp) if epilogue == 2 else res.reshape(M, N)
+
+    def selftest_gemm_resid(self, A, B, bias, resid):
+        """``pce_selftest_gemm_resid``: the persistent 256 x 256 GEMM with its residual epilogue, in place as the encoder runs it.  A [M][K], B [N][K]
+        float arrays (rounded to the operand type here), resid [M][N] uint16 bit patterns of the operand type -> uint16 bit patterns of
+        r16(resid + r16(A B^T + bias))."""
+        import torch
+        a = torch.from_numpy(np.ascontiguousarray(A, dtype=np.float32)).to(self._op_dtype()).contiguous()
+        b = torch.from_numpy(np.ascontiguousarray(B, dtype=np.float32)).to(self._op_dtype()).contiguous()
+        M, K = a.shape; N = b.shape[0]
+        out = np.array(resid, dtype=np.uint16, order="C", copy=True)
+        if out.shape != (M, N):
+            raise ValueError("resid must be [M][N]")
+        bv = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        self._check(self._lib.pce_selftest_gemm_resid(self._ctx, a.view(torch.int16).numpy().ctypes.data, b.view(torch.int16).numpy().ctypes.data,
+                                                      bv.ctypes.data if bv is not None else None, out.ctypes.data, M, N, K))
+        return out
 
     def selftest_attention(self, q, k, v, causal: bool = False, mode: int = 0):
         """softmax(q k^T / 8) v per (clip, head) on the attention kernel; q [clips][q_len][heads*64], k / v [clips][k_len][heads*64] float
