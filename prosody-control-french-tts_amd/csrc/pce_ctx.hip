@@ -120,6 +120,7 @@ pce_ctx *pce_create(int device, void *stream, char *err, size_t errlen)
     c->generic_median = getenv("PCE_ALIGN_GENERIC_MEDIAN") != nullptr;
     c->gemm_flat = !(getenv("PCE_GEMM_FLAT") && atoi(getenv("PCE_GEMM_FLAT")) == 0);
     if (const char *re = getenv("PCE_RESID_EPILOGUE")) c->resid_epilogue = atoi(re) == 0 ? 0 : atoi(re) == 2 ? 2 : 1;
+    c->stem_skip = !(getenv("PCE_STEM_SKIP") && atoi(getenv("PCE_STEM_SKIP")) == 0);
     c->en_cpb = getenv("PCE_EN_CPB") ? atoi(getenv("PCE_EN_CPB")) : 0;
     c->gemm_skinny = !(getenv("PCE_GEMM_SKINNY") && atoi(getenv("PCE_GEMM_SKINNY")) == 0);
     c->self_rows = !(getenv("PCE_SELF_ROWS") && atoi(getenv("PCE_SELF_ROWS")) == 0);

@@ -75,6 +75,7 @@ struct pce_ctx {
     bool gemm_flat = true;               // PCE_GEMM_FLAT=0 at pce_create: the encoder's projections stay on the 128 x 128 / 128 x 256 tile kernels
     int resid_epilogue = 1;              // PCE_RESID_EPILOGUE at pce_create: 0 = the 16-bit-stream encoder stores its branch outputs and adds them in k_add_layernorm (A/B, bit-identity
                                          // test), 2 = only fc2 adds in its epilogue (the per-shape A/B of DESIGN.md section 4); default 1: the attention projection and fc2 do
+    bool stem_skip = true;               // PCE_STEM_SKIP=0 at pce_create: the conv stem multiplies every row of the 30 s window, the zero padding's included (A/B, bit-identity test)
     bool stft_two_fft = false;           // PCE_STFT_TWO_FFT at pce_create: traffic-minimal STFT-dB (the FFT runs twice)
     std::string err;
     int cu_count = 0;

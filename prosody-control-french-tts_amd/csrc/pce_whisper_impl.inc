@@ -96,6 +96,31 @@ __device__ __forceinline__ f32x4 mfma16(opx8 a, opx8 b, f32x4 c) { return MfmaOf
 
 constexpr int W_NFFT = 400, W_HOP = 160, W_BINS = 201, W_FRAMES = 3000, W_SAMPLES = 480000;
 constexpr int W_CTX = 1500;
+// The conv stem does not multiply the rows of the zero padding behind a clip's audio (DESIGN.md section 5).  With P = the first padded frame of a
+// clip's window (k_logmel_frames' predicate), frames P .. 2999 of the log-mel image are one constant row, so conv1 rows P+1 .. 2998 are one row
+// and conv2 rows ceil((P+2)/2) .. 1498 have one accumulator row (row 1499 sees the zero row behind the window; the outputs differ by the
+// positional row alone).  Conv2 runs its row tiles [0, s) and its last one, conv1 the tiles those read; k_stem_fill writes conv2 rows
+// [ST_TILE s, ST_TILE ST_C2_LAST) from the accumulators of row ST_TILE ST_C2_LAST, which the last tile leaves behind.  s = ST_C2_LAST: nothing skipped.
+constexpr int ST_TILE = 128;                                        // rows of a k_gemm_bf16 tile (G_BM)
+constexpr int ST_C2_LAST = (W_CTX - 1) / ST_TILE;                   // conv2's last row tile (11): rows 1408 .. 1499, always computed
+constexpr int ST_C1_KEEP = (2 * ST_TILE * ST_C2_LAST - 1) / ST_TILE; // first conv1 tile the last conv2 tile reads (21: frame 2815)
+static_assert(ST_TILE * ST_C2_LAST < W_CTX - 1, "the last conv2 tile must hold a repeated row in front of row 1499");
+struct GemmSkip {                   // k_gemm_bf16: row tiles tiles[z].x .. tiles[z].y of batch entry z return at once (tiles == nullptr: none);
+    const int2 *tiles;              // rep != nullptr (EPI_GELU_POS_F32): the raw fp32 accumulators of row rep_row of every batch entry go to rep[z][N]
+    float *rep; int rep_row;        // (rep_row % 128 == 0, in a tile no entry skips)
+    int64_t skipped_rows;           // host side: the rows of all skipped tiles together, taken off the work count of the launch's timer
+};
+// The first conv2 row tile a clip leaves out (ST_C2_LAST: none), for a window that starts f_begin frames into len samples: P = the smallest f in
+// [0, 3000] with (f_begin + f) * 160 - 200 >= len, the `padded` predicate of k_logmel_norm.  The device derives the ranges from it (k_logmel_norm), the
+// host the batch's totals (logmel_run_impl): one expression for both.
+__host__ __device__ inline int stem_first_skipped_tile(int64_t len, int64_t f_begin)
+{
+    const int64_t p64 = (len + W_NFFT / 2 + W_HOP - 1) / W_HOP - f_begin;
+    const int P = (int)(p64 < 0 ? 0 : p64 > W_FRAMES ? W_FRAMES : p64);
+    const int r2 = (P + 3) / 2;                                             // first conv2 row of the repeated accumulators, ceil((P + 2) / 2)
+    const int s = (r2 + ST_TILE - 1) / ST_TILE;                             // conv2 tiles [s, ST_C2_LAST) hold nothing else
+    return s < ST_C2_LAST ? s : ST_C2_LAST;
+}
 constexpr double W_PI = 3.14159265358979323846;
 
 // ---------------------------------------------------------------------------
@@ -263,13 +288,20 @@ __global__ __launch_bounds__(256) PCE_NO_PK_F32 void k_logmel_frames(const int16
 // device reads it.
 __global__ __launch_bounds__(256) void k_logmel_norm(const float *__restrict__ logspec, const unsigned int *__restrict__ clip_max, int n_mels,
                                                     const int64_t *__restrict__ clip_off, const int64_t *__restrict__ frame0, int clip0,
-                                                    op_t *__restrict__ out_tm, float *__restrict__ out_f32)
+                                                    op_t *__restrict__ out_tm, float *__restrict__ out_f32,
+                                                    int2 *__restrict__ skip_c1, int2 *__restrict__ skip_c2)
 {
     __shared__ float tile[64][65];
     const int clip = clip0 + blockIdx.z, f0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
     const float floor_v = f32_from_key(clip_max[clip]) - 8.0f;
     const int64_t full = clip_off[clip + 1] - clip_off[clip];
     const int64_t len = frame0 ? full : min<int64_t>(full, (int64_t)W_SAMPLES), f_begin = frame0 ? frame0[clip] : 0;
+    if (skip_c1 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        // the row tiles the conv stem leaves out for this clip (ST_TILE above), from the image this launch writes
+        const int s = stem_first_skipped_tile(len, f_begin);
+        skip_c2[clip] = make_int2(s, ST_C2_LAST - 1);
+        skip_c1[clip] = s < ST_C2_LAST ? make_int2(2 * s, ST_C1_KEEP - 1) : make_int2(1, 0);      // conv2 tiles [0, s) read conv1 rows < 2 ST_TILE s
+    }
     const float pad_v = (fmaxf(log10f(fmaxf(0.f, 1e-10f)), floor_v) + 4.0f) / 4.0f;           // a frame of the zero padding (k_logmel_frames' own expression)
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const bool padded = (f_begin + f0 + tx) * W_HOP - W_NFFT / 2 >= len;
@@ -295,6 +327,7 @@ __global__ __launch_bounds__(256) void k_logmel_norm(const float *__restrict__ l
 enum { EPI_BF16 = 0, EPI_GELU_BF16 = 1, EPI_GELU_POS_F32 = 2, EPI_RESID_F32 = 3, EPI_QKV = 4, EPI_F32 = 5 };    // EPI_F32: C = A B^T + bias in fp32, C not read (the vocabulary logits)
 constexpr int AT_SP = 1536;               // padded key axis of the transposed V image (multiple of the 64-key tile)
 constexpr int G_BM = 128, G_BN = 128, G_BK = 64;
+static_assert(G_BM == ST_TILE, "the stem's skip ranges count k_gemm_bf16 row tiles");
 
 // GELU(x) = x/2 (1 + erf(x/sqrt 2)) = x/2 + |x|/2 erf(|x|/sqrt 2) (erf is odd: no sign select); erf by Abramowitz-Stegun 7.1.26,
 // erf(z) = 1 - t P(t) exp(-z^2), t = 1/(1 + p z), |error| < 1.5e-7 -- far below the op_t step of the outputs (libm's erff costs more than
@@ -382,7 +415,7 @@ __device__ __forceinline__ void gemm_fetch_bias(const float *__restrict__ bias, 
 template <int EPI>
 __device__ __forceinline__ void gemm_store_tile(const float *tile, int tid, int m0, int n0, int M, int N, const float (&bv)[8], float bv_col,
                                                 void *__restrict__ Cv, int64_t ldc, int64_t cbase, const float *__restrict__ pos, int pos_T,
-                                                int v_col0, int vt_sp)
+                                                int v_col0, int vt_sp, float *__restrict__ rep = nullptr, int rep_row = 0)
 {
     if (EPI == EPI_QKV && n0 >= v_col0) {
         // V columns: written transposed, vt[clip][head][d][key], so the attention kernel can stage V^T tiles
@@ -446,6 +479,8 @@ __device__ __forceinline__ void gemm_store_tile(const float *tile, int tid, int 
             float4 *dst = reinterpret_cast<float4 *>(reinterpret_cast<float *>(Cv) + cbase + (int64_t)(m0 + row) * ldc + n0 + cx);
             float4 o;
             if (EPI == EPI_GELU_POS_F32) {
+                // (conv2 of the stem) the accumulators of the row whose output the skipped rows repeat: k_stem_fill finishes them with the expression below
+                if (rep && m0 + row == rep_row) *reinterpret_cast<float4 *>(rep + n0 + cx) = v;
                 const float4 pe = *reinterpret_cast<const float4 *>(pos + (int64_t)((m0 + row) % pos_T) * N + n0 + cx);
                 o = make_float4(gelu_exact(v.x + bv[0]) + pe.x, gelu_exact(v.y + bv[1]) + pe.y, gelu_exact(v.z + bv[2]) + pe.z,
                                 gelu_exact(v.w + bv[3]) + pe.w);
@@ -470,7 +505,8 @@ template <int EPI, int G_STAGES = 2>
 __global__ __launch_bounds__(G_THREADS, G_STAGES == 2 ? 4 : 2) void k_gemm_bf16(const op_t *__restrict__ A, int64_t lda, int64_t a_batch,
                                                         const op_t *__restrict__ B, int M, int N, int K,
                                                         const float *__restrict__ bias, void *__restrict__ Cv, int64_t ldc, int64_t c_batch,
-                                                        const float *__restrict__ pos, int pos_T, int v_col0, int vt_sp, int sn_tiles, int sm_tiles)
+                                                        const float *__restrict__ pos, int pos_T, int v_col0, int vt_sp, int sn_tiles, int sm_tiles,
+                                                        GemmSkip skip)
 {
     // operand ring [stage][A|B][128][64] op_t, re-used as the fp32 epilogue tile [128][G_TLD]
     constexpr int SMEM_ELEMS = (G_STAGES * 2 * G_BM * G_BK * 2 > G_BM * G_TLD * 4 ? G_STAGES * 2 * G_BM * G_BK : G_BM * G_TLD * 2);
@@ -485,7 +521,10 @@ __global__ __launch_bounds__(G_THREADS, G_STAGES == 2 ? 4 : 2) void k_gemm_bf16(
     const int tiles_n = (int)gridDim.x, tiles_m_pad = (int)gridDim.y;          // gridDim.y is padded to a multiple of 8
     int lin = (int)blockIdx.y * tiles_n + (int)blockIdx.x;
     const int total = tiles_n * tiles_m_pad;
-    if ((total & 7) == 0) lin = (lin & 7) * (total >> 3) + (lin >> 3);
+    // With a skip description the XCD's range rotates with the batch entry: every entry skips the SAME stretch of the sequence (a 10 s clip: conv2's row
+    // tiles 4-10 beside the grid's padding tiles 12-15), and un-rotated the XCDs that own that stretch idle through the whole launch while two of them carry
+    // all the work (measured: 58 % of the tiles skipped, 6 % of the time).  Which workgroup computes a tile does not change the tile.
+    if ((total & 7) == 0) lin = (((lin & 7) + (skip.tiles ? (int)blockIdx.z : 0)) & 7) * (total >> 3) + (lin >> 3);
     int m0, n0;
     {
         const int per = sm_tiles * sn_tiles, sup = lin / per, r = lin - sup * per;
@@ -493,6 +532,10 @@ __global__ __launch_bounds__(G_THREADS, G_STAGES == 2 ? 4 : 2) void k_gemm_bf16(
         const int tm = (sup / n_sn) * sm_tiles + r / sn_tiles, tn = (sup % n_sn) * sn_tiles + r % sn_tiles;
         m0 = tm * G_BM; n0 = tn * G_BN;
         if (m0 >= M) return;                                                     // padding tile
+        if (skip.tiles) {                                                        // a tile this batch entry does not need (the conv stem: rows of the zero padding)
+            const int2 sk = skip.tiles[blockIdx.z];
+            if (tm >= sk.x && tm <= sk.y) return;
+        }
     }
     // the epilogue's bias values are fetched now: after the K loop their load latency (1-2 us) was fully exposed
     float bv[8]; float bv_col;
@@ -558,7 +601,30 @@ __global__ __launch_bounds__(G_THREADS, G_STAGES == 2 ? 4 : 2) void k_gemm_bf16(
             for (int r = 0; r < 4; r++)
                 tile[(wr * 64 + i * 16 + fq * 4 + r) * G_TLD + wc * 32 + j * 16 + fr] = acc[i][j][r];
     __syncthreads();
-    gemm_store_tile<EPI>(tile, tid, m0, n0, M, N, bv, bv_col, Cv, ldc, (int64_t)blockIdx.z * c_batch, pos, pos_T, v_col0, vt_sp);
+    gemm_store_tile<EPI>(tile, tid, m0, n0, M, N, bv, bv_col, Cv, ldc, (int64_t)blockIdx.z * c_batch, pos, pos_T, v_col0, vt_sp,
+                         skip.rep ? skip.rep + (int64_t)blockIdx.z * N : nullptr, skip.rep_row);
+}
+
+// k_stem_fill: the conv2 rows k_gemm_bf16 skipped (GemmSkip).  Rows [ST_TILE s, ST_TILE ST_C2_LAST) of clip blockIdx.y, s = tiles[clip].x, have the
+// accumulators of the row the last tile left in rep[clip][d]; what differs is the positional row.  The expression is EPI_GELU_POS_F32's, so the bits are.
+constexpr int SF_ROWS = 16;                                   // rows per workgroup (divides ST_TILE: a workgroup is skipped rows only, or none)
+static_assert(ST_TILE % SF_ROWS == 0, "a fill workgroup must not straddle a tile boundary");
+__global__ __launch_bounds__(256) void k_stem_fill(const int2 *__restrict__ tiles, const float *__restrict__ rep, const float *__restrict__ bias,
+                                                   const float *__restrict__ pos /* [W_CTX][d] */, int d /* % 4 == 0 */, float *__restrict__ out /* [clip][W_CTX][d] */)
+{
+    const int clip = blockIdx.y, t0 = blockIdx.x * SF_ROWS;
+    if (t0 < tiles[clip].x * ST_TILE || t0 >= ST_C2_LAST * ST_TILE) return;
+    const int d4 = d >> 2;
+    const float *acc = rep + (int64_t)clip * d;
+    float *dst = out + ((int64_t)clip * W_CTX + t0) * d;
+    const float *pe0 = pos + (int64_t)t0 * d;
+    for (int i = threadIdx.x; i < SF_ROWS * d4; i += 256) {
+        const int cx = (i % d4) * 4;
+        const float4 v = *reinterpret_cast<const float4 *>(acc + cx), b = *reinterpret_cast<const float4 *>(bias + cx);
+        const float4 pe = *reinterpret_cast<const float4 *>(pe0 + (int64_t)i * 4);
+        const float4 o = make_float4(gelu_exact(v.x + b.x) + pe.x, gelu_exact(v.y + b.y) + pe.y, gelu_exact(v.z + b.z) + pe.z, gelu_exact(v.w + b.w) + pe.w);
+        *reinterpret_cast<float4 *>(dst + (int64_t)i * 4) = o;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1943,6 +2009,10 @@ struct WhisperState {
     bool loaded = false;
     DevBuf tables, logspec, clipmax, mel_tm, mel_start, mel_stage, w_bf16, w_f32, pos;
     bool mel_windowed = false;             // the last pce_logmel_run_at: windows start at mel_start[clip]
+    int64_t stem_tiles_c1 = 0, stem_tiles_c2 = 0;     // row tiles the batch of the last log-mel run leaves out in conv1 / conv2, all clips together (0: the stem
+                                                      // runs its two full launches, with no description and no fill)
+    DevBuf stem_skip, stem_rep;            // int2 [2][n_clips_mel]: the row tiles conv1 | conv2 leave out per clip (k_logmel_norm writes them with the image);
+                                           // float [clips][d]: conv2's accumulators of the repeated row (GemmSkip, k_stem_fill)
     DevBuf c1_out, resid, resid16, ln_out, qkv, vt, attn, hidden, final_out, enc_tab, delta, delta2;
     size_t vt_elems_zeroed = 0;
     std::vector<int> al_tab_host, al_tok_host, al_heads_host;     // what d_tab / d_tokens / d_heads hold (pce_whisper_align_run)
@@ -2130,7 +2200,8 @@ template <int EPI> static int gemm_choose(const pce_ctx *c, const GemmShape &s)
 }
 template <int EPI>
 static void launch_gemm_kernel(pce_ctx *c, int kind, const op_t *A, int64_t lda, int64_t a_batch, const op_t *B, int M, int N, int K, const float *bias,
-                               void *C, int64_t ldc, int64_t c_batch, int batch, const float *pos, int pos_T, int v_col0, int vt_sp)
+                               void *C, int64_t ldc, int64_t c_batch, int batch, const float *pos, int pos_T, int v_col0, int vt_sp,
+                               const GemmSkip &skip = GemmSkip{nullptr, nullptr, 0, 0})       // only the GK_128 kernel takes one (pce_whisper_encode_run asks first)
 {
     if constexpr (EPI == EPI_BF16 || EPI == EPI_GELU_BF16 || EPI == EPI_RESID_F32) {
         if (kind == GK_SKINNY) {
@@ -2156,21 +2227,22 @@ static void launch_gemm_kernel(pce_ctx *c, int kind, const op_t *A, int64_t lda,
     for (int cand : {8, 6, 4, 3, 2}) if (tiles_n % cand == 0) { sn = cand; break; }        // supertile width (divides the N tiles)
     const int sm = 16;                                     // 16 x sn measured best by a hair (645-656 TFLOP/s over 4..16 x 2..8)
     dim3 grid((unsigned)tiles_n, (unsigned)(div_up(M, G_BM * sm) * sm), (unsigned)batch);
-    KernelTimer kt(c, PCE_K_GEMM128, nullptr, 2.0 * M * (double)N * K * batch);
+    KernelTimer kt(c, PCE_K_GEMM128, nullptr, 2.0 * ((double)M * batch - (double)skip.skipped_rows) * N * K);      // the rows that are multiplied
     if (kind == GK_128_DEEP)
         hipLaunchKernelGGL((k_gemm_bf16<EPI, 4>), grid, dim3(G_THREADS), 0, c->stream, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, pos, pos_T,
-                           v_col0, vt_sp, sn, sm);
+                           v_col0, vt_sp, sn, sm, GemmSkip{nullptr, nullptr, 0, 0});
     else
         hipLaunchKernelGGL((k_gemm_bf16<EPI>), grid, dim3(G_THREADS), 0, c->stream, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, pos, pos_T,
-                           v_col0, vt_sp, sn, sm);
+                           v_col0, vt_sp, sn, sm, skip);
 }
 template <int EPI>
 void launch_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, const op_t *B, int M, int N, int K, const float *bias,
                  void *C, int64_t ldc, int64_t c_batch, int batch, const float *pos = nullptr, int pos_T = 1, int v_col0 = 0,
-                 int vt_sp = AT_SP)
+                 int vt_sp = AT_SP, const GemmSkip *skip = nullptr)
 {
     const int kind = gemm_choose<EPI>(c, GemmShape{M, N, K, lda, batch, v_col0});
-    launch_gemm_kernel<EPI>(c, kind, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, batch, pos, pos_T, v_col0, vt_sp);
+    if (skip && kind == GK_128) launch_gemm_kernel<EPI>(c, kind, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, batch, pos, pos_T, v_col0, vt_sp, *skip);
+    else launch_gemm_kernel<EPI>(c, kind, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, batch, pos, pos_T, v_col0, vt_sp);
 }
 
 // ---- LayerNorm launches: four rows (waves) per workgroup, the register form by width (k_layernorm); d <= LN_D_MAX, d % 4 == 0 (the loaders)
@@ -2329,6 +2401,13 @@ static int logmel_run_impl(pce_ctx *c, int32_t n_mels, const int64_t *start_fram
     PCE_HIP(c, w->logspec.reserve(sizeof(float) * (size_t)n * (size_t)n_mels * W_FRAMES));
     PCE_HIP(c, w->clipmax.reserve(sizeof(unsigned int) * (size_t)n));
     PCE_HIP(c, w->mel_tm.reserve(sizeof(op_t) * tm_elems));
+    PCE_HIP(c, w->stem_skip.reserve(sizeof(int2) * 2 * (size_t)(n > 0 ? n : 1)));
+    w->stem_tiles_c1 = w->stem_tiles_c2 = 0;
+    for (int32_t i = 0; i < n; i++) {      // what k_logmel_norm will write per clip, summed from the host's copy of the same lengths and starts
+        const int64_t full = c->clip_off[(size_t)i + 1] - c->clip_off[(size_t)i];
+        const int s = stem_first_skipped_tile(start_frames ? full : std::min<int64_t>(full, W_SAMPLES), start_frames ? start_frames[i] : 0);
+        if (s < ST_C2_LAST) { w->stem_tiles_c2 += ST_C2_LAST - s; w->stem_tiles_c1 += ST_C1_KEEP - 2 * s; }
+    }
     PCE_HIP(c, hipMemsetAsync(w->clipmax.p, 0, sizeof(unsigned int) * (size_t)n, c->stream));
     if (w->mel_tm.cap != w->mel_tm_zero_cap || w->mel_tm_zero_nm != n_mels) {
         PCE_HIP(c, hipMemsetAsync(w->mel_tm.p, 0, w->mel_tm.cap, c->stream));
@@ -2363,7 +2442,8 @@ static int logmel_run_impl(pce_ctx *c, int32_t n_mels, const int64_t *start_fram
     {
         KernelTimer t(c, PCE_K_LOGMEL_NORM);
         hipLaunchKernelGGL(k_logmel_norm, dim3(div_up(W_FRAMES, 64), div_up(n_mels, 64), (unsigned)n), dim3(256), 0, c->stream,
-                           w->logspec.as<float>(), w->clipmax.as<unsigned int>(), (int)n_mels, c->d_clip_off.as<int64_t>(), d_start, 0, w->mel_tm.as<op_t>(), (float *)nullptr);
+                           w->logspec.as<float>(), w->clipmax.as<unsigned int>(), (int)n_mels, c->d_clip_off.as<int64_t>(), d_start, 0, w->mel_tm.as<op_t>(), (float *)nullptr,
+                           w->stem_skip.as<int2>(), w->stem_skip.as<int2>() + n);
     }
     PCE_HIP(c, hipGetLastError());
     w->n_clips_mel = n;
@@ -2383,7 +2463,7 @@ int pce_logmel_fetch(pce_ctx *c, int32_t clip, float *out)
     PCE_HIP(c, w->mel_stage.reserve(sizeof(float) * per + 64));
     hipLaunchKernelGGL(k_logmel_norm, dim3(div_up(W_FRAMES, 64), div_up(w->mel_nmels, 64), 1), dim3(256), 0, c->stream, w->logspec.as<float>(),
                        w->clipmax.as<unsigned int>(), (int)w->mel_nmels, c->d_clip_off.as<int64_t>(), w->mel_windowed ? w->mel_start.as<int64_t>() : (const int64_t *)nullptr,
-                       (int)clip, (op_t *)nullptr, w->mel_stage.as<float>());
+                       (int)clip, (op_t *)nullptr, w->mel_stage.as<float>(), (int2 *)nullptr, (int2 *)nullptr);
     PCE_HIP(c, hipGetLastError());
     PCE_HIP(c, hipMemcpyAsync(out, w->mel_stage.p, sizeof(float) * per, hipMemcpyDeviceToHost, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
@@ -2523,12 +2603,29 @@ int pce_whisper_encode_run(pce_ctx *c)
         PCE_HIP(c, hipMemsetAsync(w->c1_out.p, 0, w->c1_out.cap, c->stream));
         w->c1_zero_cap = w->c1_out.cap; w->c1_zero_d = d;
     }
+    // The stem leaves out the row tiles of the zero padding behind each clip's audio (ST_TILE; PCE_STEM_SKIP=0 at pce_create: two full launches), when both
+    // convolutions run on the 128 x 128 kernel, whose tiles the ranges count.  INVARIANT: a c1_out row conv1 skipped is never read -- conv2 computes its tiles
+    // [0, s) and its last one, which read conv1 tiles [0, 2 s) and [ST_C1_KEEP, 24), exactly what conv1 computed.  c1_out is reused across calls, so such a
+    // row holds whatever an older batch left there.
+    const bool stem_skip = c->stem_skip && w->stem_tiles_c2 > 0 && gemm_choose<EPI_GELU_BF16>(c, GemmShape{W_FRAMES, d, K1p, nm, n, 0}) == GK_128 &&
+                           gemm_choose<EPI_GELU_POS_F32>(c, GemmShape{W_CTX, d, 3 * d, 2 * (int64_t)d, n, 0}) == GK_128;
+    GemmSkip skip1{nullptr, nullptr, 0, 0}, skip2 = skip1;       // a batch in which no clip leaves a tile out (full 30 s windows) runs the two full launches
+    if (stem_skip) {
+        PCE_HIP(c, w->stem_rep.reserve(sizeof(float) * (size_t)n * d));
+        const int2 *sk = w->stem_skip.as<int2>();
+        skip1 = GemmSkip{sk, nullptr, 0, w->stem_tiles_c1 * ST_TILE};
+        skip2 = GemmSkip{sk + n, w->stem_rep.as<float>(), ST_TILE * ST_C2_LAST, w->stem_tiles_c2 * ST_TILE};
+    }
     // conv1: per clip, A row t starts at padded row t (= t-1 unpadded), K = 3 n_mels (padded to K1p with zero weights)
     launch_gemm<EPI_GELU_BF16>(c, w->mel_tm.as<op_t>(), nm, (int64_t)(W_FRAMES + 2) * nm, Wb + w->c1_w, W_FRAMES, d, K1p, Wf + w->c1_b,
-                               w->c1_out.as<op_t>() + d, d, (int64_t)(W_FRAMES + 2) * d, n);
+                               w->c1_out.as<op_t>() + d, d, (int64_t)(W_FRAMES + 2) * d, n, nullptr, 1, 0, AT_SP, stem_skip ? &skip1 : nullptr);
     // conv2 (stride 2): A row t' starts at padded row 2 t', K = 3 d, lda = 2 d; epilogue adds the positional embedding
     launch_gemm<EPI_GELU_POS_F32>(c, w->c1_out.as<op_t>(), 2 * (int64_t)d, (int64_t)(W_FRAMES + 2) * d, Wb + w->c2_w, W_CTX, d, 3 * d,
-                                  Wf + w->c2_b, w->resid.as<float>(), d, (int64_t)W_CTX * d, n, w->pos.as<float>(), W_CTX);
+                                  Wf + w->c2_b, w->resid.as<float>(), d, (int64_t)W_CTX * d, n, w->pos.as<float>(), W_CTX, 0, AT_SP, stem_skip ? &skip2 : nullptr);
+    if (stem_skip)         // the skipped conv2 rows: the repeated row's accumulators through conv2's own epilogue expression, plus each row's positions
+                           // (no timer id of its own: it runs inside the whisper_encoder bracket; d % 128 == 0 by pce_whisper_load, pos is [W_CTX][d])
+        hipLaunchKernelGGL(k_stem_fill, dim3((unsigned)(ST_TILE * ST_C2_LAST / SF_ROWS), (unsigned)n), dim3(256), 0, c->stream, skip2.tiles, w->stem_rep.as<float>(),
+                           Wf + w->c2_b, w->pos.as<float>(), d, w->resid.as<float>());
     // The big projections run on the persistent 256 x 256 kernel when the MODEL's shape allows it (n_state % 256 == 0; any batch size,
     // one clip included: the arithmetic of a clip does not depend on what it is batched with).  On that path a branch (attention projection, MLP) leaves its output as a op_t row block and the residual add is fused
     // into the LayerNorm that follows (k_add_layernorm): one pass over the residual stream instead of the GEMM's read-modify-write

@@ -1,0 +1,121 @@
+"""The conv stem leaves out the row tiles of the 30 s window's zero padding (csrc/pce_whisper_impl.inc: GemmSkip, k_stem_fill).
+
+Everything here is bit for bit: a surviving row keeps its own K loop, a skipped conv2 row is the repeated row's accumulators through conv2's own
+epilogue expression, so the encoder output of a default context must be the bytes of a context created with PCE_STEM_SKIP=0 (two full launches).
+
+P = the first padded frame of a clip's window = ceil((len + 200) / 160) - first frame; the first conv2 row with the repeated accumulators is
+ceil((P + 2) / 2), conv2 skips the whole 128-row tiles from there up to tile 10 (tile 11 holds row 1499 and is always computed)."""
+import os
+
+import numpy as np
+import pytest
+
+from prosody_control_french_tts_amd import synth, whisper_weights as WW
+
+pytestmark = pytest.mark.gpu
+
+RATE = 16000
+TINY = WW.DIMS["tiny"]
+# 0.5 s | 10 s (the bench's clip) | 27.5 s | P = 2558 and 2559: the last length at which conv2's tile 10 still drops out and the first at which nothing does |
+# exactly 30 s | 31 s (trimmed) | P = 1021, 1022, 1023: the first repeated conv2 row at 512, 512, 513, on either side of a tile boundary
+LENGTHS = [8000, 160000, 440000, 409080, 409240, 480000, 496000, 163160, 163320, 163480]
+TEN_S = LENGTHS.index(160000)
+
+_state = {}
+
+
+def _long_clip():
+    if "clip" not in _state:
+        _state["clip"] = synth.synth_clip(90, seconds=31.0)
+    return _state["clip"]
+
+
+def _short_batch():
+    return [_long_clip()[:n] for n in LENGTHS]
+
+
+def _fresh_engine(**env):
+    """A context created with the given switches in the environment (the library reads them when a context is created)."""
+    import prosody_control_french_tts_amd as P
+    old = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return P.ProsodyEngine(0)
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+@pytest.fixture(scope="module", params=["fp16-resid16", "fp16", "bf16"])
+def pair(request):
+    """(default context, PCE_STEM_SKIP=0 context) on one operand type, Whisper-tiny with synthetic weights loaded"""
+    made = [_fresh_engine(PCE_WHISPER_OPERANDS=request.param), _fresh_engine(PCE_WHISPER_OPERANDS=request.param, PCE_STEM_SKIP="0")]
+    blob = WW.pack(WW.synthetic_weights(TINY, seed=11), TINY)
+    for e in made:
+        assert e.whisper_operands == request.param
+        e.whisper_load(TINY, blob)
+    yield made
+    for e in made:
+        e.close()
+
+
+def _encode(eng, clips, starts=None, dims=TINY):
+    eng.upload(clips, RATE)
+    if starts is None:
+        eng.logmel_run(dims["n_mels"])
+    else:
+        eng.logmel_run_at(dims["n_mels"], starts)
+    eng.whisper_encode_run()
+    return [eng.whisper_encode_fetch(i) for i in range(len(clips))]
+
+
+def _same(got, want, what):
+    assert len(got) == len(want)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert np.isfinite(a).all() and float(np.std(a)) > 0.05, (what, i)
+        assert a.tobytes() == b.tobytes(), (what, i, int(np.count_nonzero(a != b)), np.flatnonzero((a != b).any(axis=1))[:8].tolist())
+
+
+def test_skipped_stem_returns_the_bytes_of_the_full_stem(pair):
+    skip, full = pair
+    clips = _short_batch()
+    want = _encode(full, clips)
+    _same(_encode(skip, clips), want, "batch")
+    # the 10 s clip alone: no clip's rows depend on what it is batched with
+    alone = _encode(skip, [clips[TEN_S]])
+    assert alone[0].tobytes() == want[TEN_S].tobytes()
+    # stale rows must not leak: c1_out and the residual stream of the same context hold a batch of full windows when the short batch runs
+    base = _long_clip()
+    _encode(skip, [base[k * 1600:k * 1600 + 480000] for k in range(len(clips))])
+    _same(_encode(skip, clips), want, "after a batch of 30 s clips")
+
+
+def test_skipped_stem_on_windows_that_start_inside_the_clip(pair):
+    """logmel_run_at: the padding begins inside the window (20 s from frame 700, 10 s from frame 400), only padding is left (10 s from frame 1000,
+    its last allowed start), a window from frame 0, and one the audio fills (31 s from frame 100)"""
+    skip, full = pair
+    base = _long_clip()
+    clips = [base[:320000], base[:160000], base[:160000], base[:8000], base]
+    starts = [700, 400, 1000, 0, 100]
+    _same(_encode(skip, clips, starts), _encode(full, clips, starts), "windows")
+
+
+def test_skipped_stem_at_the_bench_width():
+    """Whisper-small's width (the persistent 256 x 256 kernels and the 16-bit stream behind the stem), one layer, clips of 10 s and 3 s"""
+    dims = dict(WW.DIMS["small"], n_layer=1)
+    made = [_fresh_engine(), _fresh_engine(PCE_STEM_SKIP="0")]
+    try:
+        blob = WW.pack(WW.synthetic_weights(dims, seed=12), dims)
+        base = _long_clip()
+        clips = [base[:160000], base[:48000]]
+        out = []
+        for e in made:
+            e.whisper_load(dims, blob)
+            out.append(_encode(e, clips, dims=dims))
+        _same(out[0], out[1], "small")
+    finally:
+        for e in made:
+            e.close()
