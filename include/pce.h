@@ -59,9 +59,11 @@ extern "C" {
  * "Compare Breaks" on them) and their two kernel ids;
  * 11 = pce_whisper_detect_language (openai-whisper's detect_language for the encoded batch: the language rows of the output projection only);
  * 12 = pce_selftest_gemm_resid; the 16-bit-stream encoder adds its residuals in the attention-projection / fc2 GEMM epilogues (same bits; a context
- * created with PCE_RESID_EPILOGUE=0 keeps the stored branch outputs and the adds in the LayerNorm passes; =2 fuses fc2 only, for A/B runs). */
+ * created with PCE_RESID_EPILOGUE=0 keeps the stored branch outputs and the adds in the LayerNorm passes; =2 fuses fc2 only, for A/B runs);
+ * 13 = pce_crepe_load / _run / _shape / _fetch, pce_selftest_crepe_layer and pce_selftest_crepe_decode (CREPE pitch tracking of the resident batch) and their seven kernel
+ * ids, which sit in front of PCE_K_SEQMATCH: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by seven (pce_kernel_name follows). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 12
+#define PCE_API_MINOR 13
 
 typedef struct pce_ctx pce_ctx;
 
@@ -301,6 +303,47 @@ int pce_pyin_run(pce_ctx *ctx, const pce_pyin_plan *plan, const double *tables, 
 int pce_pyin_shape(pce_ctx *ctx, int32_t clip, int64_t *n_frames);
 /* states [n_frames] / voiced_prob [n_frames] / status (bit 0: a frame had more troughs than the engine keeps) may be NULL */
 int pce_pyin_fetch(pce_ctx *ctx, int32_t clip, int32_t *states, double *voiced_prob, int32_t *status);
+
+/* ---- CREPE pitch tracking ----------------------------------------------------
+ * Replaces torchcrepe.predict(audio, sr, hop, fmin, fmax, model, batch_size=..., return_periodicity=True) of Code/Pipeline/evaluate_voice.ipynb
+ * (extract_f0_torchcrepe).  torchcrepe is third party and absent: restated from its published implementation, parity unpinned; no trained
+ * weights are on hand either (the loader takes a user's own full.pth / tiny.pth through crepe_weights.py).  Per frame of 1024 samples at 16 kHz
+ * (the batch padded by 512 zeros on both sides, frame t = samples [t hop, t hop + 1024), 1 + n / hop frames; mean removed, divided by
+ * max(1e-10, unbiased std)): six blocks of zero padding (block 1: 254 + 254, others 31 + 32), convolution with bias (block 1: 512 taps, stride 4;
+ * others 64 taps), ReLU, BatchNorm in inference form as (scale, shift), max-pool 2; the last activation flattened time-major then channel; Linear to
+ * 360 bins, sigmoid = the salience.  Convolutions are GEMMs on MFMA with fp16 operands and fp32 accumulation over padded time-major images; every
+ * stored activation is fp16, the classifier's weights and the salience fp32.
+ *
+ * Weight blob (float32), per block i = 1..6: conv weight [c_out][taps][c_in] (PyTorch's [c_out][c_in][taps][1] transposed), bias [c_out],
+ * scale [c_out], shift [c_out]; then classifier weight [360][4 c_out[5]], classifier bias [360] (crepe_weights.py:tensor_order / fold).
+ * Limits (else PCE_E_LIMIT at load): c_out[0] % 64 == 0, every c_out % 16 == 0, 4 c_out[5] % 256 == 0 and <= 4096.  The kernel of a block is
+ * chosen by its N = c_out alone (N % 128 == 0: 128-column tiles, else 16-column tiles), never by the number of frames: a frame's results do not
+ * depend on the chunk size or on what its clip is batched with, bit for bit.
+ *
+ * pce_crepe_run: the resident batch must be at 16 kHz (PCE_E_INVALID otherwise; PCE_E_STATE before pce_crepe_load).  Frames run in chunks of
+ * frames_per_chunk (chunks span clip boundaries), clamped so that a chunk's activation images stay within PCE_CREPE_IMAGE_BUDGET bytes.
+ * Decoding (torchcrepe.postprocess without its dither): salience bins outside [lo, hi) are masked; decoder 0 = Viterbi of
+ * librosa.sequence.viterbi on the softmax of the masked salience, transition max(12 - |i - j|, 0) row-normalised, uniform initial state,
+ * log(p + tiny), fp64, first maximum; decoder 1 = per-frame arg-max (first maximum).  f0 = 10 * 2^((20 bin + 1997.3794084376191) / 1200),
+ * periodicity = salience[t][bin]. */
+#define PCE_CREPE_BINS 360
+#define PCE_CREPE_IMAGE_BUDGET ((int64_t)3 << 30)
+typedef struct pce_crepe_dims { int32_t c_out[6]; int32_t reserved[2]; } pce_crepe_dims;
+typedef struct pce_crepe_plan { int32_t hop, lo, hi, decoder, frames_per_chunk, reserved; } pce_crepe_plan;
+int pce_crepe_load(pce_ctx *ctx, const pce_crepe_dims *dims, const float *weights, int64_t n_floats);
+int pce_crepe_run(pce_ctx *ctx, const pce_crepe_plan *plan);
+int pce_crepe_shape(pce_ctx *ctx, int32_t clip, int64_t *n_frames);
+/* bins [n_frames] / f0 [n_frames] / periodicity [n_frames] / salience [n_frames][360]: any may be NULL */
+int pce_crepe_fetch(pce_ctx *ctx, int32_t clip, int32_t *bins, double *f0, float *periodicity, float *salience);
+/* One block (1..6) as pce_crepe_run launches it, on host arrays of fp16 bit patterns: x [n_frames][t_in][c_in] (block 1: t_in = 1024, c_in = 1;
+ * block b >= 2: t_in = 128 >> (b - 2)), w [c_out][taps][c_in]; out [n_frames][t_in / 2 (block 1: 128)][c_out] =
+ * fp16(max over row pairs of relu(acc + bias) * scale + shift). */
+int pce_selftest_crepe_layer(pce_ctx *ctx, int32_t block, int32_t c_in, int32_t c_out, int32_t n_frames, const uint16_t *x, const uint16_t *w,
+                             const float *bias, const float *scale, const float *shift, uint16_t *out);
+/* The decoding of pce_crepe_run on a host salience [n_frames][360] taken as ONE clip (any float values: the decoder takes the softmax of what it
+ * is given); bins / f0 / periodicity [n_frames], any may be NULL.  Overwrites the results of the last pce_crepe_run. */
+int pce_selftest_crepe_decode(pce_ctx *ctx, const float *salience, int32_t n_frames, int32_t lo, int32_t hi, int32_t decoder, int32_t *bins, double *f0,
+                              float *periodicity);
 
 /* ---- R8: log-mel spectrogram + Whisper audio encoder --------------------
  * Replaces the device work of whisper_timestamped.transcribe before decoding
@@ -668,6 +711,9 @@ enum pce_kernel_id {
     PCE_K_INTENSITY, PCE_K_INTENSITY_SUMMARY,
     /* minor 9: PCE_K_SILENCE_RANGES brackets three launches (tiles, carry, tiles with the carry) */
     PCE_K_MS_ENERGY, PCE_K_SILENCE_SCAN, PCE_K_SILENCE_RANGES,
+    /* minor 13: CREPE (PCE_K_CREPE_CONV2: block 2 alone, the launch that carries most of the work; PCE_K_CREPE_CONV: blocks 3-6; PCE_K_CREPE_DECODE:
+     * the log-softmax / arg-max pass and the gather) */
+    PCE_K_CREPE_FRAMES, PCE_K_CREPE_CONV1, PCE_K_CREPE_CONV2, PCE_K_CREPE_CONV, PCE_K_CREPE_CLASSIFIER, PCE_K_CREPE_DECODE, PCE_K_CREPE_VITERBI,
     /* minor 10: their work count is swept CELLS (k_seqmatch: every range of every pair, recursion included; k_seqmatch_align: n_a * n_b) */
     PCE_K_SEQMATCH, PCE_K_SEQMATCH_ALIGN, PCE_K_COUNT
 };

@@ -12,9 +12,15 @@ restatements are checked against independent Python restatements in tests/test_e
   (``pce_dtw_series``: candidates up, left, diagonal compared as sums, the first minimum wins).
 * ``jiwer.wer`` with its default transforms (``RemoveMultipleSpaces``, ``Strip``, split on ``" "``): words become integer ids on the host,
   the edit distance is ``pce_levenshtein`` on the id sequences.
-* F0: the notebook's TEXT names ``librosa.pyin`` (hop 512), its CODE calls torchcrepe (``model="full"``, periodicity threshold 0.1), a neural
-  pitch tracker whose weights are not available.  This module builds the first, on the engine's probabilistic YIN (``pce_pyin_*``), so
-  **the RMSE values printed in the notebook are not expected to be reproduced**; F1 and WER depend on the Whisper checkpoint only.
+* F0: the notebook's TEXT names ``librosa.pyin`` (hop 512), its CODE calls torchcrepe (``extract_f0_torchcrepe``: ``model="full"``, Viterbi
+  decoding, periodicity threshold 0.1).  Both are here.  ``f0="pyin"`` (every default) is the engine's probabilistic YIN (``pce_pyin_*``).
+  ``f0="crepe"`` is the notebook's code path on the engine (``pce_crepe_*``): torchcrepe restated from its published implementation and checked
+  against a float64 restatement ON RANDOM WEIGHTS (tests/test_gpu_crepe.py) -- no trained checkpoint ships with this project, so the caller
+  passes their own ``full.pth`` / ``tiny.pth`` as ``crepe_weights=``; without one ``f0="crepe"`` raises.  Deviations from torchcrepe: audio at
+  another rate goes through the engine's ``resample`` (``scipy.signal.resample_poly``'s design; torchcrepe calls resampy), and the random
+  one-bin dither of its decoders is not applied.  The RMSE values printed in the notebook are expected only with ``f0="crepe"`` and the
+  checkpoint the notebook used, and then only as closely as those two deviations and fp16 operands allow: that has not been measured.
+  F1 and WER depend on the Whisper checkpoint only.
 * Language: the notebook's ``model.transcribe(path)`` detects it; here it is an argument whose default stays ``"fr"``, and ``language=None``
   detects it per recording as openai-whisper's ``detect_language`` does on the first 30 s window (``Aligners.decoding.detect_language`` ->
   ``pce_whisper_detect_language``; pinned to the ``transformers`` forward by tests/golden/whisper_langid_tiny.npz in tests/test_gpu_langid.py).
@@ -160,9 +166,67 @@ def to_pcm16(y) -> np.ndarray:
     return np.ascontiguousarray(y, dtype=np.int16)
 
 
-def extract_f0_batch(engine, clips, sr: int, hop_length: int = 512, fmin: float = None, fmax: float = None) -> List[np.ndarray]:
-    """F0 contours (Hz, NaN where unvoiced) of ``clips`` -- ONE upload, one probabilistic-YIN run (``librosa.pyin`` with its default
-    frame length 2048, the notebook's stated F0 step; NOT torchcrepe, see the module text)."""
+def _check_f0(f0: str, crepe_weights):
+    if f0 not in ("pyin", "crepe"):
+        raise ValueError('f0: "pyin" or "crepe"')
+    if f0 == "crepe" and crepe_weights is None:
+        raise ValueError('f0="crepe" needs crepe_weights=: the path of a torchcrepe checkpoint (full.pth / tiny.pth), its state_dict, or '
+                         '(c_out, flat vector) from crepe_weights.fold -- no trained CREPE weights ship with this project')
+
+
+def _crepe_ensure(engine, model, weights):
+    """Load ``weights`` (a checkpoint path, a ``state_dict``, or ``(c_out, flat)``) into ``engine`` unless the same object already is."""
+    from .. import crepe_weights as CW
+    _check_f0("crepe", weights)
+    key = (weights if isinstance(weights, (str, Path)) else id(weights), model)
+    if getattr(engine, "_crepe_key", None) == key:
+        return
+    if isinstance(weights, (str, Path)):
+        c_out, flat = CW.load(weights)
+    elif isinstance(weights, dict):
+        c_out, flat = CW.fold(weights)
+    else:
+        c_out, flat = weights
+    if model is not None and tuple(CW.dims(model)) != tuple(c_out):
+        raise ValueError(f"model={model!r} has widths {CW.dims(model)}, the weights have {tuple(c_out)}")
+    engine.crepe_load(c_out, flat)
+    engine._crepe_key = key
+    engine._crepe_keep = weights                                    # (keeps id(weights) from being reused while it is the key)
+
+
+def extract_f0_torchcrepe_batch(engine, clips, sr: int, hop_length: int = 512, fmin: float = None, fmax: float = None, model: str = "full",
+                                threshold: float = 0.1, batch_size: int = 4096, weights=None, decoder: str = "viterbi",
+                                return_periodicity: bool = False):
+    """Batched ``extract_f0_torchcrepe``: ``torchcrepe.predict(audio, sr, hop_length, fmin, fmax, model, batch_size=batch_size,
+    return_periodicity=True)`` of every clip (all at rate ``sr``), then ``f0[periodicity < threshold] = NaN`` -> F0 contours in Hz.  Clips at
+    another rate than 16 kHz go through ``_resample_batch`` and the hop becomes ``int(hop_length * 16000 / sr)``, as in torchcrepe."""
+    from .. import crepe_weights as CW
+    engine = _engine(engine)
+    _crepe_ensure(engine, model, weights)
+    fmin = C2_HZ if fmin is None else fmin
+    fmax = C6_HZ if fmax is None else fmax
+    pcm = _resample_batch(engine, clips, [int(sr)] * len(clips), CW.SAMPLE_RATE)
+    engine.upload(pcm, CW.SAMPLE_RATE)
+    _, f0s, pers = engine.crepe(CW.hop_at_16k(hop_length, sr), fmin, fmax, decoder, batch_size)
+    out = [np.where(p < threshold, np.nan, f) for f, p in zip(f0s, pers)]
+    return (out, pers) if return_periodicity else out
+
+
+def extract_f0_torchcrepe(y, sr: int, hop_length: int = 512, fmin: float = None, fmax: float = None, model: str = "full", threshold: float = 0.1,
+                          batch_size: int = 4096, engine=None, weights=None) -> np.ndarray:
+    """The notebook's ``extract_f0_torchcrepe(y, sr, ...)`` (its ``device`` argument is the engine's): F0 in Hz, NaN where the periodicity is
+    below ``threshold``.  ``weights``: see ``_crepe_ensure``."""
+    return extract_f0_torchcrepe_batch(engine, [y], sr, hop_length, fmin, fmax, model, threshold, batch_size, weights)[0]
+
+
+def extract_f0_batch(engine, clips, sr: int, hop_length: int = 512, fmin: float = None, fmax: float = None, f0: str = "pyin",
+                     crepe_weights=None, crepe_model: str = None, crepe_threshold: float = 0.1) -> List[np.ndarray]:
+    """F0 contours (Hz, NaN where unvoiced) of ``clips`` -- ``f0="pyin"``: ONE upload, one probabilistic-YIN run (``librosa.pyin`` with its
+    default frame length 2048, the notebook's stated F0 step); ``f0="crepe"``: ``extract_f0_torchcrepe_batch`` (the notebook's code; see the
+    module text)."""
+    _check_f0(f0, crepe_weights)
+    if f0 == "crepe":
+        return extract_f0_torchcrepe_batch(engine, clips, sr, hop_length, fmin, fmax, crepe_model, crepe_threshold, weights=crepe_weights)
     from ..visualisation.acoustic_analysis import pyin_batch
     fmin = C2_HZ if fmin is None else fmin
     fmax = C6_HZ if fmax is None else fmax
@@ -171,23 +235,27 @@ def extract_f0_batch(engine, clips, sr: int, hop_length: int = 512, fmin: float 
 
 
 def compute_f0_rmse_batch(engine, episodes, sr: int, hop_length: int = 512, fmin: float = None, fmax: float = None, method: str = "fastdtw",
-                          radius: int = 25) -> List[float]:
+                          radius: int = 25, f0: str = "pyin", crepe_weights=None, crepe_threshold: float = 0.1) -> List[float]:
     """``compute_f0_rmse`` of every ``(y_ref, y_sys)`` of ``episodes`` (all at rate ``sr``): all recordings are clips of one upload, all
-    DTWs one batch."""
+    DTWs one batch.  ``f0``: ``"pyin"`` or ``"crepe"`` (with ``crepe_weights``; frames whose periodicity is below
+    ``crepe_threshold`` are unvoiced), see ``extract_f0_batch``."""
+    _check_f0(f0, crepe_weights)
     engine = _engine(engine)
     if not len(episodes):
         return []
-    f0 = extract_f0_batch(engine, [y for ep in episodes for y in ep], sr, hop_length, fmin, fmax)
+    f0 = extract_f0_batch(engine, [y for ep in episodes for y in ep], sr, hop_length, fmin, fmax, f0, crepe_weights,
+                          crepe_threshold=crepe_threshold)
     return f0_contour_rmse_batch([(f0[2 * k], f0[2 * k + 1]) for k in range(len(episodes))], method, radius, engine)
 
 
 def compute_f0_rmse(engine, y_ref, y_sys, sr: int, hop_length: int = 512, fmin: float = None, fmax: float = None, method: str = "fastdtw",
-                    radius: int = 25) -> float:
-    """RMSE of log-F0 between a recording and a synthesis at the same rate ``sr``: F0 of both by the engine's pYIN (two clips of one
-    upload; ``fmin`` / ``fmax`` default to C2 / C6 as the notebook sets them), voiced frames only, natural log, DTW (``method="fastdtw"``
+                    radius: int = 25, f0: str = "pyin", crepe_weights=None, crepe_threshold: float = 0.1) -> float:
+    """RMSE of log-F0 between a recording and a synthesis at the same rate ``sr``: F0 of both by the engine's pYIN (``f0="pyin"``, the
+    default) or its CREPE (``f0="crepe"`` with ``crepe_weights``: the notebook's code path, module text) -- two clips of one upload;
+    ``fmin`` / ``fmax`` default to C2 / C6 as the notebook sets them --, voiced frames only, natural log, DTW (``method="fastdtw"``
     with ``radius``, or ``"exact"``), then ``sqrt(mean((log_r[wp[:, 0]] - log_s[wp[:, 1]]) ** 2))`` on the fetched path.  NaN when
-    either side has no voiced frame.  The notebook's code takes its F0 from torchcrepe; its printed values are not reproduced (module text)."""
-    return compute_f0_rmse_batch(engine, [(y_ref, y_sys)], sr, hop_length, fmin, fmax, method, radius)[0]
+    either side has no voiced frame."""
+    return compute_f0_rmse_batch(engine, [(y_ref, y_sys)], sr, hop_length, fmin, fmax, method, radius, f0, crepe_weights, crepe_threshold)[0]
 
 
 # --------------------------------------------------------------------------------------------------------- WER
@@ -321,10 +389,11 @@ def _write_side(save_path: Path, prefix: str, txt: str, breaks, segments):
 
 
 def process_episodes(ep_ids: Sequence[str], voice_base, results_base, save_dir, engine=None, model: WhisperHandle = None, language: Optional[str] = "fr",
-                     method: str = "fastdtw", radius: int = 25):
+                     method: str = "fastdtw", radius: int = 25, f0: str = "pyin", crepe_weights=None):
     """``process_episode`` for a list of episodes, stage by stage over all of them -> [(ep_id, rmse_f0, f1_break, wer, error | None)].
     Folder contract of the notebook: ``{voice_base}/{ep}/brute/segment_demucs.wav`` is the reference, ``{results_base}/{ep}/OUT.wav`` the
     synthesis (resampled to the reference's rate by the engine's resampler), the side files go to ``{save_dir}/{ep}/``."""
+    _check_f0(f0, crepe_weights)
     engine = _engine(engine)
     if model is None:
         raise ValueError("model: a WhisperHandle (WhisperHandle.load(engine, 'large-v3', model_dir))")
@@ -367,7 +436,8 @@ def process_episodes(ep_ids: Sequence[str], voice_base, results_base, save_dir, 
     rmse = {}
     for sr_ref in sorted({ref[ep][1] for ep in both}):
         eps = [ep for ep in both if ref[ep][1] == sr_ref]
-        rmse.update(zip(eps, compute_f0_rmse_batch(engine, [(ref[ep][0], syn[ep][0]) for ep in eps], sr_ref, method=method, radius=radius)))
+        rmse.update(zip(eps, compute_f0_rmse_batch(engine, [(ref[ep][0], syn[ep][0]) for ep in eps], sr_ref, method=method, radius=radius, f0=f0,
+                                                    crepe_weights=crepe_weights)))
     wers = {}
     for ep in both:                                                          # an empty reference transcript fails that episode alone
         try:
@@ -386,11 +456,12 @@ def process_episode(ep_id: str, voice_base, results_base, save_dir, engine=None,
 
 
 def evaluate_all(voice_base, results_base, save_dir, engine=None, model: WhisperHandle = None, language: Optional[str] = "fr", method: str = "fastdtw",
-                 radius: int = 25):
+                 radius: int = 25, f0: str = "pyin", crepe_weights=None):
     """Every episode folder of ``results_base`` -> ``pandas.DataFrame`` indexed by ``episode`` with ``rmse_f0``, ``f1_break``, ``wer``
     (episodes that failed -- a missing ``OUT.wav`` among them -- are reported and left out, as in the notebook).  All episodes form one
     batch per stage.  Under an initialised ``torch.distributed`` group every rank takes a contiguous block of the episodes
     (``shard.shard_range``) and the rows are exchanged with ``shard.allgather_records``: every rank returns the whole table."""
+    _check_f0(f0, crepe_weights)
     import pandas as pd
     from .. import shard
     ep_ids = sorted(p.name for p in Path(results_base).iterdir() if p.is_dir())
@@ -399,7 +470,7 @@ def evaluate_all(voice_base, results_base, save_dir, engine=None, model: Whisper
     rows, failed = [], False
     try:
         for k, (ep, rmse, f1_b, wer_score, err) in zip(range(lo, hi), process_episodes(ep_ids[lo:hi], voice_base, results_base, save_dir, engine, model,
-                                                                                      language, method, radius)):
+                                                                                      language, method, radius, f0, crepe_weights)):
             if err:
                 print(f"❌ {ep}: {err}")
             else:

@@ -286,7 +286,7 @@ static int set_offsets(pce_ctx *c, const int64_t *offsets, int32_t n_clips, int3
     PCE_HIP(c, c->d_clip_off.reserve(sizeof(int64_t) * (size_t)(n_clips + 1)));
     PCE_HIP(c, hipMemcpyAsync(c->d_clip_off.p, offsets, sizeof(int64_t) * (size_t)(n_clips + 1), hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
-    c->en_n = c->lu_n = c->pi_n = c->in_n = c->si_n = -1; c->st_nfft = 0; c->st_ran = false; c->fr_ran = false; c->py_ran = false;
+    c->en_n = c->lu_n = c->pi_n = c->in_n = c->si_n = -1; c->st_nfft = 0; c->st_ran = false; c->fr_ran = false; c->py_ran = false; c->cr.ran = false;
     c->en_cache.drop(); c->lu_cache.drop(); c->pi_cache.drop(); c->in_cache.drop();
     return PCE_OK;
 }
@@ -355,7 +355,9 @@ const char *pce_kernel_name(int id)
         "k_add_layernorm", "k_stft_raw", "k_logmel_norm", "k_attention_lean",
         "k_gemm_flat:qkv", "k_gemm_flat:out", "k_gemm_flat:fc1", "k_gemm_flat:fc2", "k_gemm_flat:xkv",
         "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace", "k_intensity", "k_intensity_summary",
-        "k_ms_energy", "k_silence_scan", "k_silence_ranges", "k_seqmatch", "k_seqmatch_align"};
+        "k_ms_energy", "k_silence_scan", "k_silence_ranges",
+        "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
+        "k_seqmatch", "k_seqmatch_align"};
     return (id >= 0 && id < PCE_K_COUNT) ? names[id] : "?";
 }
 

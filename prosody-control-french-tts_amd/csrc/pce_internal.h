@@ -141,6 +141,17 @@ struct pce_ctx {
     std::vector<int64_t> py_off;
     bool py_ran = false;
 
+    // CREPE pitch tracking (pce_crepe.hip): folded weights, the padded time-major operand images of one chunk of frames, salience and decoding of the whole batch
+    struct Crepe {
+        bool loaded = false, ran = false;
+        int c_out[6] = {0}, c_in[6] = {0}, n_emb = 0;
+        int decoder = 0;
+        DevBuf w16[6], bss[6], cls_w, cls_b;            // conv weights [out][taps][in] fp16; bias | scale | shift fp32 [3][out]; classifier fp32
+        DevBuf img[7];                                  // img[0]: block 1's frames; img[i]: block i + 1's padded input; img[6]: the embedding
+        DevBuf doff, P, logp, ptr, amax, bins, f0, per, tab;
+        std::vector<int64_t> off;                       // frames before clip i (n_clips + 1)
+    } cr;
+
     // Praat intensity (pce_intensity.hip): slice table, runs of frames, the tap table, the ragged contour, per-slice {n_positive, mean_positive}
     DevBuf in_meta, in_work, in_taps, in_out, in_summary;
     SliceCache in_cache;

@@ -104,6 +104,15 @@ class BertDims(C.Structure):
                 ("n_layer", C.c_int32), ("n_labels", C.c_int32)]
 
 
+class CrepeDims(C.Structure):
+    _fields_ = [("c_out", C.c_int32 * 6), ("reserved", C.c_int32 * 2)]
+
+
+class CrepePlan(C.Structure):
+    _fields_ = [("hop", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32), ("decoder", C.c_int32), ("frames_per_chunk", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 SLICE_DTYPE = np.dtype([("clip", "<i4"), ("flags", "<i4"), ("begin", "<i8"), ("end", "<i8"), ("x1", "<f8")])
 ENERGY_DTYPE = np.dtype([("n", "<i8"), ("sum_sq", "<i8"), ("sum_sq_wrap16", "<i8"), ("n_loud", "<i8"),
                          ("peak_abs", "<i4"), ("reserved", "<i4")])
@@ -125,13 +134,16 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "k_add_layernorm", "k_stft_raw", "k_logmel_norm", "k_attention_lean",
               "k_gemm_flat:qkv", "k_gemm_flat:out", "k_gemm_flat:fc1", "k_gemm_flat:fc2", "k_gemm_flat:xkv",
               "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace",
-              "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges", "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
+              "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges",
+              "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
+              "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
 # every symbol include/pce.h declares
 EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_version", "pce_api_minor", "pce_device_info",
            "pce_upload_pcm_s16", "pce_bind_pcm_s16_device", "pce_num_clips",
            "pce_energy_run", "pce_energy_fetch", "pce_lufs_set_meter_rate", "pce_lufs_run", "pce_lufs_fetch",
            "pce_frame_energy_run", "pce_frame_energy_shape", "pce_frame_energy_fetch", "pce_pyin_run", "pce_pyin_shape", "pce_pyin_fetch",
+           "pce_crepe_load", "pce_crepe_run", "pce_crepe_shape", "pce_crepe_fetch", "pce_selftest_crepe_layer", "pce_selftest_crepe_decode",
            "pce_pitch_plan", "pce_pitch_run", "pce_pitch_set_refine", "pce_pitch_fetch",
            "pce_intensity_plan", "pce_intensity_run", "pce_intensity_fetch",
            "pce_silence_run", "pce_silence_shape", "pce_silence_fetch",
@@ -169,6 +181,12 @@ def load_library() -> C.CDLL:
     lib.pce_pyin_run.argtypes = [vp, vp, vp, i64]
     lib.pce_pyin_shape.argtypes = [vp, i32, C.POINTER(i64)]
     lib.pce_pyin_fetch.argtypes = [vp, i32, vp, vp, C.POINTER(i32)]
+    lib.pce_crepe_load.argtypes = [vp, C.POINTER(CrepeDims), vp, i64]
+    lib.pce_crepe_run.argtypes = [vp, C.POINTER(CrepePlan)]
+    lib.pce_crepe_shape.argtypes = [vp, i32, C.POINTER(i64)]
+    lib.pce_crepe_fetch.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.pce_selftest_crepe_layer.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.pce_selftest_crepe_decode.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.pce_frame_energy_shape.argtypes = [vp, i32, C.POINTER(i64)]
     lib.pce_frame_energy_fetch.argtypes = [vp, i32, vp, vp]
     lib.pce_lufs_fetch.argtypes = [vp, vp, vp]
@@ -943,6 +961,64 @@ class ProsodyEngine:
         st = np.zeros(nf.value, dtype=np.int32); vp = np.zeros(nf.value, dtype=np.float64); status = C.c_int32()
         self._check(self._lib.pce_pyin_fetch(self._ctx, int(clip), st.ctypes.data, vp.ctypes.data, C.byref(status)))
         return st, vp, status.value
+
+    # ---------------------------------------------------------------- CREPE pitch tracking (evaluate_voice's F0 RMSE)
+    def crepe_load(self, capacity_or_dims, weights):
+        """``capacity_or_dims``: ``"full"``, ``"tiny"`` or six output widths; ``weights``: the flat float32 vector of
+        ``crepe_weights.tensor_order`` (``crepe_weights.fold(state_dict)[1]`` / ``crepe_weights.load(path)[1]``) or a ``state_dict``."""
+        from . import crepe_weights as CW
+        c_out = CW.dims(capacity_or_dims)
+        if isinstance(weights, dict):
+            got, weights = CW.fold(weights)
+            if tuple(got) != tuple(c_out):
+                raise ValueError(f"CREPE state dict has widths {got}, {c_out} were asked for")
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        d = CrepeDims((C.c_int32 * 6)(*c_out), (C.c_int32 * 2)(0, 0))
+        self._check(self._lib.pce_crepe_load(self._ctx, C.byref(d), w.ctypes.data, w.size))
+        self.crepe_dims = tuple(c_out)
+
+    def crepe(self, hop_length: int, fmin: float, fmax: float, decoder: str = "viterbi", frames_per_chunk: int = 4096,
+              return_salience: bool = False):
+        """``torchcrepe.predict(..., return_periodicity=True)`` without its dither, of every clip of the resident batch (which must be at
+        16 kHz; ``hop_length`` in samples at that rate) -> per-clip lists ``(bins int32, f0 float64 Hz, periodicity float32[, salience
+        float32 [n_frames, 360]])``.  ``decoder``: ``"viterbi"`` (torchcrepe's default) or ``"argmax"``.  Frames run ``frames_per_chunk`` at a
+        time (torchcrepe's ``batch_size``); no result depends on it.  The caller masks ``f0[periodicity < threshold] = NaN``."""
+        from . import crepe_weights as CW
+        if decoder not in ("viterbi", "argmax"):
+            raise ValueError('decoder: "viterbi" or "argmax" (the dithered decoders of torchcrepe are not offered)')
+        lo, hi = CW.mask_range(fmin, fmax)
+        plan = CrepePlan(int(hop_length), lo, hi, 0 if decoder == "viterbi" else 1, int(frames_per_chunk), 0)
+        self._check(self._lib.pce_crepe_run(self._ctx, C.byref(plan)))
+        bins, f0s, pers, sals = [], [], [], []
+        for clip in range(len(self.clip_lengths)):
+            nf = C.c_int64()
+            self._check(self._lib.pce_crepe_shape(self._ctx, clip, C.byref(nf)))
+            b = np.zeros(nf.value, dtype=np.int32); f = np.zeros(nf.value, dtype=np.float64); p = np.zeros(nf.value, dtype=np.float32)
+            sal = np.zeros((nf.value, CW.PITCH_BINS), dtype=np.float32) if return_salience else None
+            self._check(self._lib.pce_crepe_fetch(self._ctx, clip, b.ctypes.data, f.ctypes.data, p.ctypes.data,
+                                                  sal.ctypes.data if return_salience else None))
+            bins.append(b); f0s.append(f); pers.append(p); sals.append(sal)
+        return (bins, f0s, pers, sals) if return_salience else (bins, f0s, pers)
+
+    def selftest_crepe_layer(self, block: int, x16, w16, bias, scale, shift):
+        """One CREPE block as the product launches it, on fp16 arrays: ``x16`` [n_frames, t_in, c_in], ``w16`` [c_out, taps, c_in] ->
+        fp16 [n_frames, t_in / 2 (block 1: 128), c_out]."""
+        x = np.ascontiguousarray(x16, dtype=np.float16); w = np.ascontiguousarray(w16, dtype=np.float16)
+        n, t_in, c_in = x.shape; c_out = w.shape[0]
+        b, sc, sh = (np.ascontiguousarray(a, dtype=np.float32) for a in (bias, scale, shift))
+        out = np.zeros((n, 128 if block == 1 else t_in // 2, c_out), dtype=np.float16)
+        self._check(self._lib.pce_selftest_crepe_layer(self._ctx, int(block), c_in, c_out, n, x.ctypes.data, w.ctypes.data, b.ctypes.data,
+                                                       sc.ctypes.data, sh.ctypes.data, out.ctypes.data))
+        return out
+
+    def selftest_crepe_decode(self, salience, lo: int, hi: int, decoder: str = "viterbi"):
+        """The device's decoding of a host salience [n_frames, 360] (one clip) -> (bins, f0, periodicity)."""
+        s = np.ascontiguousarray(salience, dtype=np.float32)
+        n = s.shape[0]
+        b = np.zeros(n, dtype=np.int32); f = np.zeros(n, dtype=np.float64); p = np.zeros(n, dtype=np.float32)
+        self._check(self._lib.pce_selftest_crepe_decode(self._ctx, s.ctypes.data, n, int(lo), int(hi), 0 if decoder == "viterbi" else 1,
+                                                        b.ctypes.data, f.ctypes.data, p.ctypes.data))
+        return b, f, p
 
     # ---------------------------------------------------------------- break-prediction token classifier
     def bert_load(self, dims: dict, weights: np.ndarray):
