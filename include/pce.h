@@ -61,9 +61,10 @@ extern "C" {
  * 12 = pce_selftest_gemm_resid; the 16-bit-stream encoder adds its residuals in the attention-projection / fc2 GEMM epilogues (same bits; a context
  * created with PCE_RESID_EPILOGUE=0 keeps the stored branch outputs and the adds in the LayerNorm passes; =2 fuses fc2 only, for A/B runs);
  * 13 = pce_crepe_load / _run / _shape / _fetch, pce_selftest_crepe_layer and pce_selftest_crepe_decode (CREPE pitch tracking of the resident batch) and their seven kernel
- * ids, which sit in front of PCE_K_SEQMATCH: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by seven (pce_kernel_name follows). */
+ * ids, which sit in front of PCE_K_SEQMATCH: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by seven (pce_kernel_name follows);
+ * 14 = pce_selftest_align_matrix (the three kernels between the forced alignment's queries and its DTW, stage by stage through the run's own launches). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 13
+#define PCE_API_MINOR 14
 
 typedef struct pce_ctx pce_ctx;
 
@@ -412,6 +413,25 @@ int pce_selftest_attention_ragged(pce_ctx *ctx, const uint16_t *q, const uint16_
  * (q_elems, k_elems, v_elems, out_elems: their lengths in elements) shorter than the shape needs.  Since minor 8. */
 int pce_selftest_attn1(pce_ctx *ctx, int32_t form, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, uint16_t *k, int64_t k_elems, uint16_t *v,
                        int64_t v_elems, const int32_t *k_row0, const int32_t *len, const int32_t *skip, int32_t span, uint16_t *out, int64_t out_elems);
+/* Self-test of the forced alignment's matrix kernels (k_align_scores, k_align_colnorm, k_align_cost) on host arrays, through the launches and the
+ * padding code of pce_whisper_align_run: n clips, 64-wide heads, d = heads * 64.  q [n][T_pad][d] (the decoder's cross-attention queries) and
+ * k [n][k_rows][d] (audio keys; placed at the 1500-row pitch per clip the kernel assumes, k_rows >= every f_len) as 16-bit patterns of the context's
+ * operand type; t_len / f_len [n]: tokens and frames per clip; heads_sel [n_sel]: the selected heads in the order of their slices (any order, repeats
+ * allowed); T_pad = max t_len rounded up to 16, F_pad = max f_len rounded up to 64, N_max = max t_len - sot_len - 1.  The scores are launched once
+ * for all selected heads (split == 0 or == n_sel) or twice as two layers would be: heads_sel[0 .. split) with sel0 = 0, then the rest with
+ * sel0 = split.  The kernel's score scale is 0.125f * qk_scale (fp32 product), as in pce_whisper_align_run.
+ *   w_soft [n][n_sel][T_pad][F_pad] fp32: softmax over s < f_len of q_t . k_s, after the score launches;
+ *   w_norm, same shape: the same buffer after the in-place normalisation over t < t_len;
+ *   cost [n][N_max][F_pad] fp64: -mean over heads of the median filter over time, rows t = sot_len .. t_len - 2.
+ * w_soft and cost are read and written back whole: what no launch writes keeps the caller's values (in w_norm: the values w_soft came in with).
+ * PCE_E_INVALID, before anything is launched, for what pce_whisper_align_run refuses (t_len < sot_len + 2 or > 448, f_len < 1, an even
+ * medfilt_width or one above 15), f_len > 1500 or > k_rows, a selected head outside 0 .. heads - 1, more than 32 heads, split outside 0 .. n_sel and
+ * arrays (q_elems, k_elems, w_soft_elems, w_norm_elems, cost_elems: their lengths in elements) shorter than the shape needs.  A context created
+ * with PCE_ALIGN_GENERIC_MEDIAN set takes the insertion-sort filter at width 7 here as in the run.  Since minor 14. */
+int pce_selftest_align_matrix(pce_ctx *ctx, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, const uint16_t *k, int64_t k_elems, int32_t k_rows,
+                              const int32_t *t_len, const int32_t *f_len, const int32_t *heads_sel, int32_t n_sel, int32_t split, int32_t sot_len,
+                              int32_t medfilt_width, float qk_scale, float *w_soft, int64_t w_soft_elems, float *w_norm, int64_t w_norm_elems, double *cost,
+                              int64_t cost_elems);
 /* Self-test of the cross-attention of an incremental decoding step from the ENCODER OUTPUT (csrc/pce_xattn.inc: LayerNorm + query projection + Q' = q Wk,
  * one streaming pass over E with an online softmax per leaf of frames, the merge tree, out = Wv U + bv) for ONE layer on host arrays: resid [n][d] fp32,
  * ln_w / ln_b / bq / bv [d] fp32, wq / wk / wv [d][d] and E [n][k_cap][d] as 16-bit patterns of the context's operand type (rows of the weights = output

@@ -25,7 +25,7 @@ static int pad_token_rows(pce_ctx *c, const int32_t *tokens, const int32_t *toke
 {
     int T_max = 0; r.t_len.resize((size_t)n);
     for (int i = 0; i < n; i++) { r.t_len[(size_t)i] = token_offsets[i + 1] - token_offsets[i]; T_max = std::max(T_max, r.t_len[(size_t)i]); }
-    r.T_pad = (int)div_up(T_max, 16) * 16;
+    r.T_pad = token_rows_pad(T_max);
     r.tok.assign((size_t)n * r.T_pad, 0); r.tab.assign((size_t)columns * n, 0);
     for (int i = 0; i < n; i++) {
         r.tab[(size_t)i] = i * r.T_pad; r.tab[(size_t)n + i] = r.t_len[(size_t)i];
@@ -179,20 +179,18 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
     if (!w->dec_loaded) return pce_fail(c, PCE_E_STATE, "pce_whisper_align_run before pce_whisper_decoder_load");
     if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "run pce_whisper_encode_run first");
     if (w->tdims.n_state != w->dims.n_state) return pce_fail(c, PCE_E_INVALID, "decoder and encoder widths differ");
-    if (medfilt_width < 1 || medfilt_width > 15 || !(medfilt_width & 1)) return pce_fail(c, PCE_E_INVALID, "median filter width must be odd, <= 15");
+    if (!align_width_ok(medfilt_width)) return pce_fail(c, PCE_E_INVALID, "median filter width must be odd, <= 15");
     PCE_HIP(c, hipSetDevice(c->device));
     const int n = w->n_clips_enc, d = w->tdims.n_state, H = w->tdims.n_head, L = w->tdims.n_layer, V = w->tdims.n_vocab;
     // ---- shapes
-    int F_max = 0, N_max = 0;
+    AlignDims dims;
     std::vector<int> f_len((size_t)n);
     for (int i = 0; i < n; i++) {
-        const int T = token_offsets[i + 1] - token_offsets[i];
-        if (T < sot_len + 2 || T > w->tdims.n_text_ctx) return pce_fail(c, PCE_E_INVALID, "clip %d: %d tokens (need %d..%d)", i, T, sot_len + 2, w->tdims.n_text_ctx);
-        int F = num_frames[i] / 2; if (F > W_CTX) F = W_CTX; if (F < 1) return pce_fail(c, PCE_E_INVALID, "clip %d: no audio frames", i);
+        const int F = std::min(num_frames[i] / 2, W_CTX);
+        const int rc = align_clip_dims(c, i, token_offsets[i + 1] - token_offsets[i], F, sot_len, w->tdims.n_text_ctx, dims); if (rc) return rc;
         f_len[(size_t)i] = F;
-        F_max = std::max(F_max, F); N_max = std::max(N_max, T - sot_len - 1);
     }
-    const int F_pad = (int)div_up(F_max, 64) * 64;
+    const int F_max = dims.F_max, N_max = dims.N_max, F_pad = dims.F_pad();
     const int64_t Ma = (int64_t)n * W_CTX;
     // selected heads (default: every head of the last half of the layers, as whisper's Whisper.__init__ sets alignment_heads)
     std::vector<int> heads; std::vector<int> layer_first((size_t)L + 1, 0);
@@ -249,6 +247,7 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
     // layers), the 12 projections (15 of this call's 27 ms at 256 clips) are read from there
     const bool xkv_cached = w->g_xkv_clips == n;
     const size_t xk_cl = (size_t)Ma * d, xvt_cl = (size_t)n * (size_t)d * AT_SP;
+    const AlignMatrix am{w->d_aw.as<float>(), TL, FL, n, n_sel, T_pad, F_pad};
     KernelTimer timer(c, PCE_K_WHISPER_ALIGN);
     if (w->enc_bf16_clips != n)                                   // (the persistent-GEMM encoder path has already written it)
         hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up(Ma * d, 256)), dim3(256), 0, c->stream, w->final_out.as<float>(),
@@ -267,26 +266,12 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
         const bool tail = l + 1 < L;
         if (tail) prefix_cross_attention(c, w, run, xk, xvt);
         const int ns_l = layer_first[(size_t)l + 1] - layer_first[(size_t)l];
-        if (ns_l > 0) {
-            AlignArgs g{};
-            g.q = w->d_q.as<op_t>(); g.q_ld = d; g.k = xk; g.k_ld = d; g.t_len = TL; g.f_len = FL;
-            g.heads = w->d_heads.as<int>() + layer_first[(size_t)l];
-            g.w = w->d_aw.as<float>(); g.sel0 = layer_first[(size_t)l]; g.n_sel_total = n_sel; g.T_pad = T_pad; g.F_pad = F_pad;
-            g.scale = 0.125f * qk_scale;
-            hipLaunchKernelGGL(k_align_scores, dim3((unsigned)div_up(T_pad, 16), (unsigned)ns_l, (unsigned)n), dim3(256), 0, c->stream, g);
-        }
+        if (ns_l > 0) launch_align_scores(c, am, w->d_q.as<op_t>(), xk, d, w->d_heads.as<int>(), layer_first[(size_t)l], ns_l, qk_scale);
         if (!tail) break;
         prefix_cross_out_mlp(c, w, run, ly, true);
     }
     // alignment matrix: normalise over tokens, median filter over time, mean over heads, DTW
-    hipLaunchKernelGGL(k_align_colnorm, dim3((unsigned)div_up(F_pad, 256), (unsigned)n_sel, (unsigned)n), dim3(256), 0, c->stream,
-                       w->d_aw.as<float>(), TL, FL, n_sel, T_pad, F_pad);
-    if (medfilt_width == 7 && !c->generic_median)
-        hipLaunchKernelGGL((k_align_cost<7>), dim3((unsigned)div_up(F_pad, 256), (unsigned)N_max, (unsigned)n), dim3(256), 0, c->stream,
-                           w->d_aw.as<float>(), TL, FL, n_sel, T_pad, F_pad, (int)sot_len, (int)medfilt_width, N_max, w->d_cost.as<double>());
-    else
-        hipLaunchKernelGGL((k_align_cost<0>), dim3((unsigned)div_up(F_pad, 256), (unsigned)N_max, (unsigned)n), dim3(256), 0, c->stream,
-                           w->d_aw.as<float>(), TL, FL, n_sel, T_pad, F_pad, (int)sot_len, (int)medfilt_width, N_max, w->d_cost.as<double>());
+    launch_align_cost(c, am, (int)sot_len, (int)medfilt_width, N_max, w->d_cost.as<double>());
     int rc = pce_dtw_launch(c, w->d_cost.as<double>(), (int64_t)N_max * F_pad, F_pad, NR, FL, N_max, F_max, n, w->d_trace.as<unsigned char>(),
                             w->d_pi.as<int>(), w->d_pj.as<int>(), w->d_pl.as<int>());
     if (rc) return rc;

@@ -15,6 +15,8 @@ PCE_BOTH(int, pce_whisper_encode_fetch, (pce_ctx *, int32_t, float *))
 PCE_BOTH(int, pce_selftest_attention, (pce_ctx *, const uint16_t *, const uint16_t *, const uint16_t *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *, int32_t *))
 PCE_BOTH(int, pce_selftest_attention_ragged, (pce_ctx *, const uint16_t *, const uint16_t *, const uint16_t *, int32_t, int32_t, const int32_t *, const int32_t *, int32_t, int32_t, uint16_t *, int64_t, int32_t *))
 PCE_BOTH(int, pce_selftest_attn1, (pce_ctx *, int32_t, int32_t, int32_t, const uint16_t *, int64_t, uint16_t *, int64_t, uint16_t *, int64_t, const int32_t *, const int32_t *, const int32_t *, int32_t, uint16_t *, int64_t))
+PCE_BOTH(int, pce_selftest_align_matrix, (pce_ctx *, int32_t, int32_t, const uint16_t *, int64_t, const uint16_t *, int64_t, int32_t, const int32_t *, const int32_t *,
+                                           const int32_t *, int32_t, int32_t, int32_t, int32_t, float, float *, int64_t, float *, int64_t, double *, int64_t))
 PCE_BOTH(int, pce_selftest_gemm, (pce_ctx *, const uint16_t *, const uint16_t *, const float *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
 PCE_BOTH(int, pce_selftest_gemm_resid, (pce_ctx *, const uint16_t *, const uint16_t *, const float *, uint16_t *, int32_t, int32_t, int32_t))
 PCE_BOTH(int, pce_selftest_xattn, (pce_ctx *, const float *, const float *, const float *, const uint16_t *, const float *, const uint16_t *, const uint16_t *, const float *, const uint16_t *, const int32_t *, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
@@ -74,6 +76,14 @@ int pce_selftest_attn1(pce_ctx *c, int32_t form, int32_t n, int32_t heads, const
                        int64_t v_elems, const int32_t *k_row0, const int32_t *len, const int32_t *skip, int32_t span, uint16_t *out, int64_t out_elems)
 {
     return PCE_FWD(pce_selftest_attn1, c, form, n, heads, q, q_elems, k, k_elems, v, v_elems, k_row0, len, skip, span, out, out_elems);
+}
+int pce_selftest_align_matrix(pce_ctx *c, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, const uint16_t *k, int64_t k_elems, int32_t k_rows,
+                              const int32_t *t_len, const int32_t *f_len, const int32_t *heads_sel, int32_t n_sel, int32_t split, int32_t sot_len,
+                              int32_t medfilt_width, float qk_scale, float *w_soft, int64_t w_soft_elems, float *w_norm, int64_t w_norm_elems, double *cost,
+                              int64_t cost_elems)
+{
+    return PCE_FWD(pce_selftest_align_matrix, c, n, heads, q, q_elems, k, k_elems, k_rows, t_len, f_len, heads_sel, n_sel, split, sot_len, medfilt_width, qk_scale,
+                   w_soft, w_soft_elems, w_norm, w_norm_elems, cost, cost_elems);
 }
 int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t rows_per_clip,
                       int32_t vt_sp, uint16_t *out)

@@ -51,6 +51,7 @@
 #define pce_selftest_attention PCE_WFN(pce_selftest_attention)
 #define pce_selftest_attention_ragged PCE_WFN(pce_selftest_attention_ragged)
 #define pce_selftest_attn1 PCE_WFN(pce_selftest_attn1)
+#define pce_selftest_align_matrix PCE_WFN(pce_selftest_align_matrix)
 #define pce_selftest_gemm PCE_WFN(pce_selftest_gemm)
 #define pce_selftest_gemm_resid PCE_WFN(pce_selftest_gemm_resid)
 #define pce_whisper_decoder_load PCE_WFN(pce_whisper_decoder_load)
@@ -1974,6 +1975,43 @@ __global__ __launch_bounds__(256) void k_align_cost(const float *__restrict__ w,
         }
     }
     cost[((int64_t)clip * N_max + row) * F_pad + s] = -(double)(acc / (float)n_sel);
+}
+
+// ---- The forced alignment's matrix, as pce_whisper_align_run and pce_selftest_align_matrix (its test hook) build it: shapes, then the three launches.
+// Per clip: T tokens (sot_len + 2 .. T_cap), F frames (1 .. 1500); `dims` keeps the running maxima (F_max, N_max = the DTW's rows of the longest clip).
+static int token_rows_pad(int T_max) { return (int)div_up(T_max, 16) * 16; }            // an MFMA row block is 16 rows
+struct AlignDims { int F_max = 0, N_max = 0; int F_pad() const { return (int)div_up(F_max, 64) * 64; } };
+static bool align_width_ok(int width) { return width >= 1 && width <= 15 && (width & 1); }
+static int align_clip_dims(pce_ctx *c, int clip, int T, int F, int sot_len, int T_cap, AlignDims &dims)
+{
+    if (T < sot_len + 2 || T > T_cap) return pce_fail(c, PCE_E_INVALID, "clip %d: %d tokens (need %d..%d)", clip, T, sot_len + 2, T_cap);
+    if (F < 1) return pce_fail(c, PCE_E_INVALID, "clip %d: no audio frames", clip);
+    dims.F_max = std::max(dims.F_max, F); dims.N_max = std::max(dims.N_max, T - sot_len - 1);
+    return PCE_OK;
+}
+// the weights w [n][n_sel][T_pad][F_pad] with the per-clip lengths on the device
+struct AlignMatrix { float *w; const int *t_len, *f_len; int n, n_sel, T_pad, F_pad; };
+// one layer's scores: its ns selected heads heads[sel0 .. sel0 + ns) fill slices sel0 .. of w; q [n * T_pad][d], k [n * 1500][d]
+static void launch_align_scores(pce_ctx *c, const AlignMatrix &m, const op_t *q, const op_t *k, int d, const int *heads, int sel0, int ns, float qk_scale)
+{
+    AlignArgs g{};
+    g.q = q; g.q_ld = d; g.k = k; g.k_ld = d; g.t_len = m.t_len; g.f_len = m.f_len;
+    g.heads = heads + sel0;
+    g.w = m.w; g.sel0 = sel0; g.n_sel_total = m.n_sel; g.T_pad = m.T_pad; g.F_pad = m.F_pad;
+    g.scale = 0.125f * qk_scale;
+    hipLaunchKernelGGL(k_align_scores, dim3((unsigned)div_up(m.T_pad, 16), (unsigned)ns, (unsigned)m.n), dim3(256), 0, c->stream, g);
+}
+// normalise over tokens (in place), then median filter over time, mean over heads -> cost [n][N_max][F_pad]
+static void launch_align_cost(pce_ctx *c, const AlignMatrix &m, int sot_len, int medfilt_width, int N_max, double *cost)
+{
+    hipLaunchKernelGGL(k_align_colnorm, dim3((unsigned)div_up(m.F_pad, 256), (unsigned)m.n_sel, (unsigned)m.n), dim3(256), 0, c->stream,
+                       m.w, m.t_len, m.f_len, m.n_sel, m.T_pad, m.F_pad);
+    if (medfilt_width == 7 && !c->generic_median)
+        hipLaunchKernelGGL((k_align_cost<7>), dim3((unsigned)div_up(m.F_pad, 256), (unsigned)N_max, (unsigned)m.n), dim3(256), 0, c->stream,
+                           m.w, m.t_len, m.f_len, m.n_sel, m.T_pad, m.F_pad, sot_len, medfilt_width, N_max, cost);
+    else
+        hipLaunchKernelGGL((k_align_cost<0>), dim3((unsigned)div_up(m.F_pad, 256), (unsigned)N_max, (unsigned)m.n), dim3(256), 0, c->stream,
+                           m.w, m.t_len, m.f_len, m.n_sel, m.T_pad, m.F_pad, sot_len, medfilt_width, N_max, cost);
 }
 
 __global__ void k_f32_to_bf16(const float *__restrict__ in, op_t *__restrict__ out, int64_t n)

@@ -172,6 +172,63 @@ int pce_selftest_attn1(pce_ctx *c, int32_t form, int32_t n, int32_t heads, const
     return PCE_OK;
 }
 
+// Self-test hook of the forced alignment's matrix kernels (k_align_scores, k_align_colnorm, k_align_cost<7> / <0>) through the launches
+// pce_whisper_align_run makes (launch_align_scores once or twice, as one or two layers would, then launch_align_cost), with the shapes padded by the
+// run's own code.  See include/pce.h.
+int pce_selftest_align_matrix(pce_ctx *c, int32_t n, int32_t heads, const uint16_t *q, int64_t q_elems, const uint16_t *k, int64_t k_elems, int32_t k_rows,
+                              const int32_t *t_len, const int32_t *f_len, const int32_t *heads_sel, int32_t n_sel, int32_t split, int32_t sot_len,
+                              int32_t medfilt_width, float qk_scale, float *w_soft, int64_t w_soft_elems, float *w_norm, int64_t w_norm_elems, double *cost,
+                              int64_t cost_elems)
+{
+    if (!c || !q || !k || !t_len || !f_len || !heads_sel || !w_soft || !w_norm || !cost || n < 1 || n > 65535 || heads < 1 || n_sel < 1 || n_sel > 65535 || sot_len < 0)
+        return PCE_E_INVALID;
+    if (heads > 32) return pce_fail(c, PCE_E_INVALID, "selftest align: %d heads (a decoder holds 32)", heads);
+    if (!align_width_ok(medfilt_width)) return pce_fail(c, PCE_E_INVALID, "median filter width must be odd, <= 15");
+    if (split < 0 || split > n_sel) return pce_fail(c, PCE_E_INVALID, "selftest align: split %d of %d selected heads", split, n_sel);
+    if (k_rows < 1 || k_rows > W_CTX) return pce_fail(c, PCE_E_INVALID, "selftest align: %d key rows per clip (1..%d)", k_rows, W_CTX);
+    for (int s = 0; s < n_sel; s++)
+        if (heads_sel[s] < 0 || heads_sel[s] >= heads) return pce_fail(c, PCE_E_INVALID, "selftest align: selected head %d of %d", heads_sel[s], heads);
+    AlignDims dims;
+    int T_max = 0;
+    for (int i = 0; i < n; i++) {
+        if (f_len[i] > k_rows) return pce_fail(c, PCE_E_INVALID, "selftest align: clip %d has %d frames, %d key rows", i, f_len[i], k_rows);
+        const int rc = align_clip_dims(c, i, t_len[i], f_len[i], sot_len, 448, dims); if (rc) return rc;      // (448: the longest n_text_ctx a decoder loads with)
+        T_max = std::max(T_max, t_len[i]);
+    }
+    const int d = heads * 64, T_pad = token_rows_pad(T_max), F_pad = dims.F_pad(), N_max = dims.N_max;
+    const int64_t q_need = (int64_t)n * T_pad * d, k_need = (int64_t)n * k_rows * d, w_need = (int64_t)n * n_sel * T_pad * F_pad, c_need = (int64_t)n * N_max * F_pad;
+    if (q_elems < q_need || k_elems < k_need || w_soft_elems < w_need || w_norm_elems < w_need || cost_elems < c_need || w_need >= ((int64_t)1 << 28))
+        return pce_fail(c, PCE_E_INVALID, "selftest align: needs q %lld, k %lld, w_soft / w_norm %lld, cost %lld elements", (long long)q_need, (long long)k_need,
+                        (long long)w_need, (long long)c_need);
+    PCE_HIP(c, hipSetDevice(c->device));
+    std::vector<int> tab((size_t)2 * n + n_sel);                  // t_len | f_len | heads
+    for (int i = 0; i < n; i++) { tab[(size_t)i] = t_len[i]; tab[(size_t)n + i] = f_len[i]; }
+    for (int s = 0; s < n_sel; s++) tab[(size_t)2 * n + s] = heads_sel[s];
+    DevBuf dq, dk, dw, dc, dtab;
+    const size_t k_clip = (size_t)W_CTX * d;                      // the key pitch k_align_scores assumes: 1500 rows per clip
+    PCE_HIP(c, dq.reserve(2 * (size_t)q_need + 64)); PCE_HIP(c, dk.reserve(2 * k_clip * (size_t)n + 64)); PCE_HIP(c, dw.reserve(sizeof(float) * (size_t)w_need));
+    PCE_HIP(c, dc.reserve(sizeof(double) * (size_t)c_need)); PCE_HIP(c, dtab.reserve(sizeof(int) * tab.size()));
+    PCE_HIP(c, hipMemcpyAsync(dq.p, q, 2 * (size_t)q_need, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dk.p, 0, 2 * k_clip * (size_t)n, c->stream));
+    PCE_HIP(c, hipMemcpy2DAsync(dk.p, 2 * k_clip, k, 2 * (size_t)k_rows * d, 2 * (size_t)k_rows * d, (size_t)n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dw.p, w_soft, sizeof(float) * (size_t)w_need, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dc.p, cost, sizeof(double) * (size_t)c_need, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    const int *TL = dtab.as<int>(), *FL = TL + n, *HS = TL + 2 * n;
+    const AlignMatrix am{dw.as<float>(), TL, FL, n, n_sel, T_pad, F_pad};
+    const int first = split == 0 ? n_sel : split;                // heads of the first launch (the rest: a second layer's)
+    launch_align_scores(c, am, dq.as<op_t>(), dk.as<op_t>(), d, HS, 0, first, qk_scale);
+    if (first < n_sel) launch_align_scores(c, am, dq.as<op_t>(), dk.as<op_t>(), d, HS, first, n_sel - first, qk_scale);
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(w_soft, dw.p, sizeof(float) * (size_t)w_need, hipMemcpyDeviceToHost, c->stream));
+    launch_align_cost(c, am, sot_len, medfilt_width, N_max, dc.as<double>());
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(w_norm, dw.p, sizeof(float) * (size_t)w_need, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(cost, dc.p, sizeof(double) * (size_t)c_need, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+
 // Self-test hook of the encoder-output cross-attention of an incremental decoding step (pce_xattn.inc): k_xq_fused -> k_xattn_absorbed -> k_uv_absorb of ONE
 // layer on host arrays, with the number of workgroups per clip forced (0: what the batch size selects).  See include/pce.h.
 int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,

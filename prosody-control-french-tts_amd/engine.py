@@ -150,7 +150,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
            "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
-           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_whisper_encode_fetch",
+           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_selftest_align_matrix", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
 
@@ -239,6 +239,7 @@ def load_library() -> C.CDLL:
     lib.pce_selftest_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     lib.pce_selftest_attention_ragged.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i64, vp]
     lib.pce_selftest_attn1.argtypes = [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i64]
+    lib.pce_selftest_align_matrix.argtypes = [vp, i32, i32, vp, i64, vp, i64, i32, vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, i64, vp, i64, vp, i64]
     lib.pce_selftest_xattn.argtypes = [vp] * 11 + [i32] * 5 + [vp]
     lib.pce_selftest_gemm_tiled.argtypes = [vp, i32, i32, vp, i64, i64, i64, i32, vp, vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp]
     lib.pce_selftest_layernorm.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp]
@@ -699,6 +700,28 @@ class ProsodyEngine:
         ptr = lambda x: None if x is None else x.ctypes.data
         self._check(self._lib.pce_selftest_attn1(self._ctx, int(form), int(n), int(heads), q.ctypes.data, q.size, k.ctypes.data, k.size, v.ctypes.data,
                                                  v.size, ptr(r0), ln.ctypes.data, ptr(sk), int(span), out.ctypes.data, out.size))
+
+    def selftest_align_matrix(self, heads: int, q, k, t_len, f_len, heads_sel, w_soft, w_norm, cost, split: int = 0, sot_len: int = 3,
+                              medfilt_width: int = 7, qk_scale: float = 1.0, k_rows=None):
+        """``pce_selftest_align_matrix``: the forced alignment's k_align_scores -> k_align_colnorm -> k_align_cost through the launches
+        ``pce_whisper_align_run`` makes.  q [n][T_pad][heads * 64] and k [n][k_rows][heads * 64] are uint16 bit patterns of the context's operand type
+        (T_pad: the longest t_len rounded up to 16); heads_sel lists the selected heads, launched in one go (split 0 or len(heads_sel)) or as two
+        layers (the first ``split``, then the rest).  w_soft / w_norm (float32, [n][n_sel][T_pad][F_pad], F_pad: the longest f_len rounded up to 64)
+        and cost (float64, [n][max t_len - sot_len - 1][F_pad]) are read and updated in place.  The kernel scales its scores by
+        float32(0.125) * float32(qk_scale).  k_rows: the key rows per clip where k is not given as [n][k_rows][.]."""
+        q, k = self._u16(q), self._u16(k)
+        for x, dt in ((w_soft, np.float32), (w_norm, np.float32), (cost, np.float64)):
+            assert isinstance(x, np.ndarray) and x.dtype == dt and x.flags["C_CONTIGUOUS"], getattr(x, "dtype", None)
+        tl, fl, hs = (np.ascontiguousarray(x, dtype=np.int32) for x in (t_len, f_len, heads_sel))
+        n = tl.size
+        if k_rows is None:
+            assert k.ndim == 3 and k.shape[0] == n
+            k_rows = k.shape[1]
+        assert fl.size == n
+        self._check(self._lib.pce_selftest_align_matrix(self._ctx, int(n), int(heads), q.ctypes.data, q.size, k.ctypes.data, k.size, int(k_rows),
+                                                        tl.ctypes.data, fl.ctypes.data, hs.ctypes.data, int(hs.size), int(split), int(sot_len),
+                                                        int(medfilt_width), float(qk_scale), w_soft.ctypes.data, w_soft.size, w_norm.ctypes.data,
+                                                        w_norm.size, cost.ctypes.data, cost.size))
 
     def selftest_xattn(self, resid, ln_w, ln_b, wq, bq, wk, wv, bv, E, k_len, heads: int, workgroups_per_clip: int = 0):
         """One layer of the encoder-output cross-attention of a decoding step (``pce_selftest_xattn``): resid [n][d], E [n][k_cap][d], weights [d][d]

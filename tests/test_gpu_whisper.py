@@ -128,7 +128,9 @@ def test_forced_alignment_matches_torch(engine, clips, width, heads, mask_layers
     The cost matrix agrees with the torch fp32 restatement within bf16 tolerance; the GPU DTW path is EXACTLY the
     CPU recurrence's path on the GPU's own cost matrix (alignment indices bit-exact given identical costs).
     mask_layers: a head mask of every head of these layers instead of the default (the upper half): with (0, 2) the last
-    layer, which ends at its alignment scores, and a middle one launch none (as many heads as the default averages)."""
+    layer, which ends at its alignment scores, and a middle one launch none (as many heads as the default averages).
+    The kernels between the queries and the DTW (k_align_scores / colnorm / cost) are checked one by one against float64, at their edges, in
+    tests/test_gpu_align_matrix.py; this test sees them through the whole model."""
     edims = dict(n_mels=80, n_ctx=1500, n_state=width, n_head=heads, n_layer=2)
     tdims = dict(n_vocab=300, n_text_ctx=96, n_state=width, n_head=heads, n_layer=4)     # 768: the width of "small" (wide cross K/V GEMM)
     We, Wd = WW.synthetic_weights(edims), WW.synthetic_decoder_weights(tdims)
@@ -184,7 +186,9 @@ def test_forced_alignment_matches_transformers_token_timestamps(engine, ops):
     transformers model's own cross-attentions (tests/golden/whisper_hf_align.npz, see its generating script): the cost matrix the DTW
     runs on is the golden's normalised / median-filtered / head-averaged matrix (rows ``[sot_len:-1]``, negated) within the operand
     type's rounding, and the alignment indices -- the DTW path and the token jump times -- are the golden's: identical with fp16
-    operands (the reference's arithmetic), at least 95 % within one frame (20 ms) with bf16.  Both head selections, both clips."""
+    operands (the reference's arithmetic), at least 95 % within one frame (20 ms) with bf16.  Both head selections, both clips.
+    The kernels between the queries and the DTW (k_align_scores / colnorm / cost) are checked one by one against float64, at their edges, in
+    tests/test_gpu_align_matrix.py; this test sees them through the whole model."""
     import os
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "whisper_hf_align.npz"))
     edims = dict(n_mels=80, n_ctx=1500, n_state=128, n_head=2, n_layer=2)
@@ -223,7 +227,9 @@ def test_forced_alignment_matches_transformers_token_timestamps(engine, ops):
 def test_median_filter_network_equals_generic_sort(engine, clips, monkeypatch):
     """Width 7 (the default) selects its median with a 13-exchange network in registers; a context created with
     PCE_ALIGN_GENERIC_MEDIAN=1 runs the insertion sort used for every other width.  A median is a selection: the
-    cost matrices must be bit-identical.  Width 5 goes through the generic path and is checked against torch."""
+    cost matrices must be bit-identical.  Width 5 goes through the generic path and is checked against torch.
+    The kernels between the queries and the DTW (k_align_scores / colnorm / cost) are checked one by one against float64, at their edges, in
+    tests/test_gpu_align_matrix.py; this test sees them through the whole model."""
     from prosody_control_french_tts_amd import ProsodyEngine
     edims = dict(n_mels=80, n_ctx=1500, n_state=128, n_head=2, n_layer=2)
     tdims = dict(n_vocab=300, n_text_ctx=96, n_state=128, n_head=2, n_layer=4)
