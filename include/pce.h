@@ -62,9 +62,11 @@ extern "C" {
  * created with PCE_RESID_EPILOGUE=0 keeps the stored branch outputs and the adds in the LayerNorm passes; =2 fuses fc2 only, for A/B runs);
  * 13 = pce_crepe_load / _run / _shape / _fetch, pce_selftest_crepe_layer and pce_selftest_crepe_decode (CREPE pitch tracking of the resident batch) and their seven kernel
  * ids, which sit in front of PCE_K_SEQMATCH: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by seven (pce_kernel_name follows);
- * 14 = pce_selftest_align_matrix (the three kernels between the forced alignment's queries and its DTW, stage by stage through the run's own launches). */
+ * 14 = pce_selftest_align_matrix (the three kernels between the forced alignment's queries and its DTW, stage by stage through the run's own launches);
+ * 15 = pce_ctc_align (CTC forced alignment of a batch of clips: trellis, path and token frames) and its three kernel ids, which sit in
+ * front of PCE_K_SEQMATCH as minor 13's do: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by three (pce_kernel_name follows). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 14
+#define PCE_API_MINOR 15
 
 typedef struct pce_ctx pce_ctx;
 
@@ -620,6 +622,39 @@ enum pce_dtw_status { PCE_DTW_OK = 0, PCE_DTW_EMPTY = 1, PCE_DTW_NO_PATH = 2 };
 int pce_dtw_series(pce_ctx *ctx, const double *a, const int64_t *a_off, const double *b, const int64_t *b_off, const int32_t *win_lo,
                    const int32_t *win_hi, int32_t batch, int32_t *path_i, int32_t *path_j, int32_t *path_len, double *dist, int32_t *status);
 
+/* ---- CTC forced alignment (the numeric core of Code/Aligners/CTCFA.py and of whisperX.py's wav2vec2 pass) ----
+ * A CTC acoustic model gives frame-wise log-probabilities; the Viterbi pass over the 2 L + 1 blank-interleaved states of the transcript gives
+ * the frame-to-label path.  The recurrence is the CPU implementation of torchaudio.functional.forced_align (third party and absent: restated
+ * from its published source, parity unpinned).  State i carries `blank` (i even) or targets[i / 2] (i odd);  t = 0: alpha[0] = lp[0][blank],
+ * alpha[1] = lp[0][targets[0]], the rest -inf;  t >= 1: x0 = alpha[i], x1 = alpha[i - 1] (-inf for i = 0), x2 = alpha[i - 2] where i is odd,
+ * i != 1 and targets[i / 2] != targets[i / 2 - 1] (-inf otherwise);  x2 if x2 > x1 && x2 > x0 (back-pointer 2), else x1 if x1 > x0 && x1 > x2
+ * (back-pointer 1), else x0 (so x1 == x2 > x0 takes x0);  alpha'[i] = fp32(chosen + lp[t][label(i)]).  The final state is 2 L if
+ * alpha[2 L] > alpha[2 L - 1], else 2 L - 1; the trace walks the back-pointers to t = 0.  fp32 adds and compares only: every output is
+ * bit-identical to a CPU restatement of these lines.
+ * emissions: fp32 rows of n_vocab log-probabilities; clip q owns rows row_start[q] .. row_start[q] + n_frames[q] (ragged, or a padded
+ * [B][T_max][V] tensor); emissions_on_device != 0: device memory of this context's device, read in place, never copied through the host.
+ * Every other pointer is host memory.  targets[target_off[q] .. target_off[q + 1]) are clip q's vocabulary indices, 0 <= id < n_vocab and
+ * id != blank (else PCE_E_INVALID, before anything is launched).
+ * path / frame_score (either may be NULL): clip q's frames start at element sum of n_frames[0 .. q); path[t] = the label of frame t's state,
+ * frame_score[t] = lp[t][path[t]] (a copy).  tok_first / tok_last, indexed like targets: first and last frame, inclusive, in the target's own
+ * state.  score[q] = the final alpha.  status[q]: PCE_CTC_EMPTY (L = 0 or T = 0), PCE_CTC_TOO_SHORT (T < L + R, R = adjacent equal targets),
+ * PCE_CTC_NO_PATH (the final alpha is -inf or NaN); such a clip has no path: path -1, frame_score NaN, token frames -1, score NaN (NO_PATH:
+ * the final alpha).
+ * form 0: a clip of up to PCE_CTC_REG_STATES states (2 L + 1) is swept with its states in registers (one wave for up to 256 states, several
+ * such clips per workgroup; else one workgroup, the waves meeting at one barrier per frame), a longer one by the general form (alpha rows in
+ * device memory, any L);  form 1: the register form, a clip over its limit is PCE_E_LIMIT;  form 2: the general form for every clip.  A clip's
+ * outputs depend on its own emissions and targets only: not on the form, the batch, or its place in it.
+ * The trace takes T x (2 L + 1) / 4 bytes (the states rounded up to the sweeping threads); clips are processed in groups whose traces fit
+ * PCE_CTC_TRACE_MB MiB together (environment, read at pce_create; default 4096), and a single clip over that budget is PCE_E_LIMIT.  Since minor 15. */
+#define PCE_CTC_REG_STATES 4096
+typedef struct { int32_t blank; int32_t form; int32_t reserved[2]; } pce_ctc_params;   /* form: 0 auto, 1 register form, 2 general form */
+enum pce_ctc_status { PCE_CTC_OK = 0, PCE_CTC_EMPTY = 1, PCE_CTC_TOO_SHORT = 2, PCE_CTC_NO_PATH = 3 };
+int pce_ctc_align(pce_ctx *ctx, const float *emissions, int32_t emissions_on_device, const int64_t *row_start /* [n] */,
+                  const int32_t *n_frames /* [n] */, int32_t n_vocab, const int32_t *targets, const int64_t *target_off /* [n+1] */,
+                  int32_t n_clips, const pce_ctc_params *p,
+                  int32_t *path /* [sum n_frames] or NULL */, float *frame_score /* [sum n_frames] or NULL */,
+                  int32_t *tok_first, int32_t *tok_last /* [target_off[n]] */, float *score /* [n] */, int32_t *status /* [n] */);
+
 /* ---- batched Needleman-Wunsch word alignment ------------------------------
  * Replaces needleman_wunsch (Code/Pipeline/NeedlemanWunschAlignement.py:27-81) for a batch of sequence pairs.
  * Pair b aligns a_ids[a_off[b] .. a_off[b+1]) (rows; any number since round 5) with b_ids[b_off[b] .. b_off[b+1]); the ids are
@@ -734,6 +769,8 @@ enum pce_kernel_id {
     /* minor 13: CREPE (PCE_K_CREPE_CONV2: block 2 alone, the launch that carries most of the work; PCE_K_CREPE_CONV: blocks 3-6; PCE_K_CREPE_DECODE:
      * the log-softmax / arg-max pass and the gather) */
     PCE_K_CREPE_FRAMES, PCE_K_CREPE_CONV1, PCE_K_CREPE_CONV2, PCE_K_CREPE_CONV, PCE_K_CREPE_CLASSIFIER, PCE_K_CREPE_DECODE, PCE_K_CREPE_VITERBI,
+    /* minor 15: the register form (both launch shapes), the general form and the walk back of pce_ctc_align; work count = trellis CELLS (frames for the walk) */
+    PCE_K_CTC, PCE_K_CTC_GENERAL, PCE_K_CTC_TRACE,
     /* minor 10: their work count is swept CELLS (k_seqmatch: every range of every pair, recursion included; k_seqmatch_align: n_a * n_b) */
     PCE_K_SEQMATCH, PCE_K_SEQMATCH_ALIGN, PCE_K_COUNT
 };

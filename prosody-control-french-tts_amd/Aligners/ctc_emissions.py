@@ -1,0 +1,70 @@
+"""Frame-wise log-probabilities of a ``transformers`` ``...ForCTC`` model for 16 kHz clips (torch plumbing, no kernel of this project:
+the model's forward pass on hand-written kernels is the stated next step).
+
+The windowing is that of ``ctc-forced-aligner``'s ``generate_emissions`` (third party and absent: restated from the published source,
+parity unpinned): a clip is padded to a whole number of windows of ``window_s`` seconds, every window is run with ``context_s`` seconds
+of audio on both sides, the context's frames (50 per second) are cut away, the windows are joined and the frames of the padding dropped.
+Log-softmax in float32; one column of zeros, the ``<star>`` token, is appended after the model's vocabulary."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+SAMPLE_RATE = 16000
+FRAMES_PER_SECOND = 50          # the 20 ms stride of wav2vec2's feature encoder
+
+
+def time_to_frame(seconds: float) -> int:
+    return int(seconds * FRAMES_PER_SECOND)
+
+
+def window_plan(n_samples: int, window_s: float = 30, context_s: float = 2):
+    """-> (windows, padding samples behind the clip, frames kept) of one clip."""
+    window = int(window_s * SAMPLE_RATE)
+    n_win = max(1, math.ceil(n_samples / window))
+    extension = n_win * window - n_samples
+    return n_win, extension, n_win * time_to_frame(window_s) - (time_to_frame(extension / SAMPLE_RATE) if extension > 0 else 0)
+
+
+def hf_emissions(model, pcm_list, device, window_s=30, context_s=2, batch_size=4):
+    """``pcm_list``: int16 (scaled by 1 / 32768) or float 1-D arrays at 16 kHz.  -> (float32 tensor ``[B, T_max, V + 1]`` on ``device``, rows
+    past a clip's frames zero; ``n_frames`` int32 numpy [B]): what ``ProsodyEngine.ctc_align`` takes by pointer."""
+    import torch
+    import torch.nn.functional as F
+
+    dev = torch.device(device)
+    model = model.to(dev).eval()
+    dtype = next(model.parameters()).dtype
+    window, context = int(window_s * SAMPLE_RATE), int(context_s * SAMPLE_RATE)
+    cut = time_to_frame(context_s)
+    chunks, owner = [], []
+    plans = []
+    for ci, pcm in enumerate(pcm_list):
+        x = np.asarray(pcm).reshape(-1)
+        x = x.astype(np.float32) / 32768.0 if x.dtype.kind in "iu" else x.astype(np.float32)
+        n_win, extension, keep = window_plan(len(x), window_s, context_s)
+        plans.append((n_win, keep))
+        padded = F.pad(torch.from_numpy(x), (context, context + extension))
+        chunks.append(padded.unfold(0, window + 2 * context, window))
+        owner += [ci] * n_win
+    per_clip = [[] for _ in pcm_list]
+    if chunks:
+        stack = torch.cat(chunks, dim=0)
+        with torch.inference_mode():
+            for i in range(0, stack.shape[0], batch_size):
+                logits = model(stack[i:i + batch_size].to(dev, dtype)).logits.float()
+                logits = logits[:, cut:logits.shape[1] - cut + 1]                    # the context's frames leave
+                if logits.shape[1] != time_to_frame(window_s):
+                    raise ValueError(f"the model gives {logits.shape[1]} frames per {window_s} s window, {time_to_frame(window_s)} expected (20 ms stride)")
+                for k in range(logits.shape[0]):
+                    per_clip[owner[i + k]].append(logits[k])
+    n_frames = np.array([keep for _, keep in plans], dtype=np.int32)
+    if not len(plans):
+        return torch.zeros((0, 0, 0), dtype=torch.float32, device=dev), n_frames
+    V = per_clip[0][0].shape[-1]
+    out = torch.zeros((len(plans), int(n_frames.max()), V + 1), dtype=torch.float32, device=dev)
+    for ci, parts in enumerate(per_clip):
+        em = torch.log_softmax(torch.cat(parts, dim=0)[:n_frames[ci]], dim=-1)
+        out[ci, :n_frames[ci], :V] = em                                              # (the star column stays zero)
+    return out.contiguous(), n_frames

@@ -142,6 +142,7 @@ pce_ctx *pce_create(int device, void *stream, char *err, size_t errlen)
     }
     c->pitch_refine_praat = getenv("PCE_PITCH_REFINE") && !strcmp(getenv("PCE_PITCH_REFINE"), "praat");
     if (getenv("PCE_DTW_TRACE_MB") && atoll(getenv("PCE_DTW_TRACE_MB")) > 0) c->dtw_trace_budget = (size_t)atoll(getenv("PCE_DTW_TRACE_MB")) << 20;
+    if (getenv("PCE_CTC_TRACE_MB") && atoll(getenv("PCE_CTC_TRACE_MB")) > 0) c->ctc_trace_budget = (size_t)atoll(getenv("PCE_CTC_TRACE_MB")) << 20;
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     for (int si = 0; si < pce_ctx::SIDE_COUNT; si++) {
@@ -357,7 +358,7 @@ const char *pce_kernel_name(int id)
         "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace", "k_intensity", "k_intensity_summary",
         "k_ms_energy", "k_silence_scan", "k_silence_ranges",
         "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
-        "k_seqmatch", "k_seqmatch_align"};
+        "k_ctc", "k_ctc_general", "k_ctc_trace", "k_seqmatch", "k_seqmatch_align"};
     return (id >= 0 && id < PCE_K_COUNT) ? names[id] : "?";
 }
 

@@ -179,6 +179,11 @@ struct pce_ctx {
     struct DtwSeries { DevBuf a, b, lo, hi, pi, pj, dist, len, status, pairs, tab, tiles, rows, cols, trace; } ds;
     size_t dtw_trace_budget = (size_t)4096 << 20;   // PCE_DTW_TRACE_MB at pce_create: bytes of trace one group of pairs may hold
 
+    // CTC forced alignment (pce_ctc.hip): uploaded emissions, clip table, clip-id lists, targets, final alphas, the trace of the group in flight, the general
+    // form's alpha rows, the batch's results
+    struct Ctc { DevBuf lp, tab, ids, tgt, fin, trace, scratch, path, fscore, first, last, score, status; } ctc;
+    size_t ctc_trace_budget = (size_t)4096 << 20;   // PCE_CTC_TRACE_MB at pce_create: bytes of trace one group of clips may hold
+
     // whisper / BERT state, opaque (pce_whisper_impl.inc): one slot per operand-type build (0: bf16, 1: fp16); whisper_ops selects the build the
     // entry points of include/pce.h forward to (pce_whisper_set_operands, or PCE_WHISPER_OPERANDS=fp16 at pce_create)
     void *whisper_slot[2] = {nullptr, nullptr};

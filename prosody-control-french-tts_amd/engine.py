@@ -104,6 +104,10 @@ class BertDims(C.Structure):
                 ("n_layer", C.c_int32), ("n_labels", C.c_int32)]
 
 
+class CtcParams(C.Structure):
+    _fields_ = [("blank", C.c_int32), ("form", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class CrepeDims(C.Structure):
     _fields_ = [("c_out", C.c_int32 * 6), ("reserved", C.c_int32 * 2)]
 
@@ -126,6 +130,9 @@ assert INTENSITY_SUMMARY_DTYPE.itemsize == C.sizeof(IntensitySummary) == 40 and 
 
 SLICE_OK, SLICE_TOO_SHORT, SLICE_EMPTY = 0, 1, 2
 DTW_OK, DTW_EMPTY, DTW_NO_PATH = 0, 1, 2                      # enum pce_dtw_status
+CTC_OK, CTC_EMPTY, CTC_TOO_SHORT, CTC_NO_PATH = 0, 1, 2, 3     # enum pce_ctc_status
+CTC_REG_STATES = 4096                                         # PCE_CTC_REG_STATES of include/pce.h: the states (2 L + 1) the register form of k_ctc holds
+CTC_FORMS = {"auto": 0, "register": 1, "general": 2}
 DTW_SERIES_ROWS, DTW_SERIES_COLS = 1024, 2048                 # PCE_DTW_SERIES_ROWS / _COLS of include/pce.h: the tile of k_dtw_series
 
 KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs_gate",
@@ -136,7 +143,7 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace",
               "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges",
               "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
-              "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
+              "k_ctc", "k_ctc_general", "k_ctc_trace", "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
 # every symbol include/pce.h declares
 EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_version", "pce_api_minor", "pce_device_info",
@@ -149,7 +156,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_silence_run", "pce_silence_shape", "pce_silence_fetch",
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
-           "pce_dtw", "pce_dtw_series", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
+           "pce_dtw", "pce_dtw_series", "pce_ctc_align", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
            "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_selftest_align_matrix", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
@@ -213,6 +220,7 @@ def load_library() -> C.CDLL:
     lib.pce_download_pcm_s16.argtypes = [vp, vp, vp, C.POINTER(i32)]
     lib.pce_dtw.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.pce_dtw_series.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.pce_ctc_align.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     lib.pce_whisper_decoder_load.argtypes = [vp, C.POINTER(WhisperTextDims), vp, i64]
     lib.pce_whisper_align_run.argtypes = [vp, vp, vp, vp, i32, vp, i32, C.c_float]
     lib.pce_whisper_align_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
@@ -888,6 +896,80 @@ class ProsodyEngine:
                                              lo.ctypes.data if lo is not None else None, hi.ctypes.data if hi is not None else None, nb,
                                              pi.ctypes.data, pj.ctypes.data, pl.ctypes.data, dist.ctypes.data, st.ctypes.data))
         return [(np.stack([pi[oo[k]:oo[k] + pl[k]], pj[oo[k]:oo[k] + pl[k]]], axis=1), float(dist[k]), int(st[k])) for k in range(nb)]
+
+    def ctc_align(self, emissions, targets, blank=0, n_frames=None, form="auto", return_path=True):
+        """CTC forced alignment of a batch of clips (``pce_ctc_align``: the Viterbi pass of ``torchaudio.functional.forced_align`` over the
+        ``2 L + 1`` blank-interleaved states of each transcript, bit-identical to its CPU restatement).  ``emissions``: a list of
+        ``[T_c, V]`` float32 arrays of log-probabilities (packed and uploaded by the call), or ONE float32 contiguous torch tensor
+        ``[B, T_max, V]`` with ``n_frames`` (valid frames per clip; default ``T_max`` for all): a ROCm tensor is read in place through its
+        pointer, a CPU tensor is handed over as host memory (a process that uses ROCm tensors imports torch BEFORE it creates its first engine:
+        torch ships its own copy of the HIP runtime, and the copy loaded first serves both).  ``targets``: one sequence of vocabulary indices per clip (none may be ``blank``).
+        ``form``: ``"auto"`` | ``"register"`` | ``"general"`` (the register form holds ``CTC_REG_STATES`` states; asking it for more raises).
+        -> one dict per clip: ``path`` int32 [T] (the label of every frame) and ``frame_score`` float32 [T] (``emissions[t, path[t]]``) unless
+        ``return_path`` is false, ``tok_first`` / ``tok_last`` int32 [L] (first and last frame, inclusive, of every target), ``score``
+        (numpy float32: the final alpha) and ``status`` (``CTC_OK``; ``CTC_EMPTY``: no targets or no frames; ``CTC_TOO_SHORT``: fewer frames
+        than targets + adjacent repeats; ``CTC_NO_PATH``: the best score is -inf or NaN).  A clip without a path has ``path`` -1,
+        ``frame_score`` NaN and token frames -1."""
+        if form not in CTC_FORMS:
+            raise ValueError(f"form: one of {sorted(CTC_FORMS)}")
+        tg = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in targets]
+        keep = None
+        if isinstance(emissions, (list, tuple)):
+            if n_frames is not None:
+                raise ValueError("n_frames goes with a tensor of emissions; a list carries its own lengths")
+            rows = [np.ascontiguousarray(e, dtype=np.float32) for e in emissions]
+            n = len(rows)
+            if n and any(r.ndim != 2 or r.shape[1] != rows[0].shape[1] for r in rows):
+                raise ValueError("emissions: [T, V] arrays with one vocabulary size")
+            V = rows[0].shape[1] if n else 0
+            nfr = np.array([r.shape[0] for r in rows], dtype=np.int32)
+            row_start = np.zeros(n, dtype=np.int64)
+            if n:
+                row_start[1:] = np.cumsum(nfr[:-1], dtype=np.int64)
+            keep = np.concatenate(rows + [np.zeros((1, V), dtype=np.float32)]) if n else None
+            ptr, on_device = (keep.ctypes.data if n else None), 0
+        else:
+            e = emissions
+            if not hasattr(e, "data_ptr") or e.dim() != 3 or str(e.dtype) != "torch.float32" or not e.is_contiguous():
+                raise ValueError("emissions: a list of [T, V] float32 arrays or one contiguous float32 torch tensor [B, T_max, V]")
+            n, t_max, V = (int(x) for x in e.shape)
+            nfr = np.full(n, t_max, dtype=np.int32) if n_frames is None else np.ascontiguousarray(
+                n_frames.cpu().numpy() if hasattr(n_frames, "cpu") else n_frames, dtype=np.int32).reshape(-1)
+            if nfr.shape != (n,) or (n and (nfr.min() < 0 or nfr.max() > t_max)):
+                raise ValueError("n_frames: one count in [0, T_max] per clip")
+            if e.is_cuda and e.device.index not in (None, self.device):
+                raise ValueError(f"emissions live on {e.device}, this engine on device {self.device}")
+            row_start = np.arange(n, dtype=np.int64) * t_max
+            keep = e
+            ptr, on_device = e.data_ptr(), 1 if e.is_cuda else 0
+            if on_device:
+                import torch
+                torch.cuda.current_stream(e.device).synchronize()      # the tensor's producer has finished before this engine's stream reads it
+        if len(tg) != n:
+            raise ValueError("targets: one sequence per clip")
+        if not n:
+            return []
+        toff = np.zeros(n + 1, dtype=np.int64); np.cumsum([len(t) for t in tg], out=toff[1:])
+        tgt = np.concatenate(tg + [np.zeros(1, dtype=np.int32)])
+        foff = np.zeros(n + 1, dtype=np.int64); np.cumsum(nfr, out=foff[1:])
+        path = np.zeros(int(foff[-1]) + 1, dtype=np.int32) if return_path else None
+        fsc = np.zeros(int(foff[-1]) + 1, dtype=np.float32) if return_path else None
+        first = np.zeros(int(toff[-1]) + 1, dtype=np.int32); last = np.zeros_like(first)
+        score = np.zeros(n, dtype=np.float32); status = np.zeros(n, dtype=np.int32)
+        prm = CtcParams(int(blank), CTC_FORMS[form])
+        self._check(self._lib.pce_ctc_align(self._ctx, C.c_void_p(ptr), on_device, row_start.ctypes.data, nfr.ctypes.data, V, tgt.ctypes.data,
+                                            toff.ctypes.data, n, C.byref(prm), path.ctypes.data if return_path else None,
+                                            fsc.ctypes.data if return_path else None, first.ctypes.data, last.ctypes.data,
+                                            score.ctypes.data, status.ctypes.data))
+        del keep
+        out = []
+        for k in range(n):
+            d = {"tok_first": first[toff[k]:toff[k + 1]].copy(), "tok_last": last[toff[k]:toff[k + 1]].copy(),
+                 "score": score[k], "status": int(status[k])}
+            if return_path:
+                d["path"] = path[foff[k]:foff[k + 1]].copy(); d["frame_score"] = fsc[foff[k]:foff[k + 1]].copy()
+            out.append(d)
+        return out
 
     def frame_energy_run(self, window: int, hop: int = None, requantize: bool = False):
         """Exact integer energy of every analysis window of every clip (k_frame_energy): frame k covers
