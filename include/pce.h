@@ -64,9 +64,12 @@ extern "C" {
  * ids, which sit in front of PCE_K_SEQMATCH: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by seven (pce_kernel_name follows);
  * 14 = pce_selftest_align_matrix (the three kernels between the forced alignment's queries and its DTW, stage by stage through the run's own launches);
  * 15 = pce_ctc_align (CTC forced alignment of a batch of clips: trellis, path and token frames) and its three kernel ids, which sit in
- * front of PCE_K_SEQMATCH as minor 13's do: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by three (pce_kernel_name follows). */
+ * front of PCE_K_SEQMATCH as minor 13's do: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by three (pce_kernel_name follows);
+ * 16 = pce_w2v_check / _load / _run / _shape / _fetch / _device, pce_w2v_window_plan and pce_selftest_w2v_wave / _lngelu / _posconv (the wav2vec2 / MMS CTC
+ * forward pass of the resident batch: the emissions pce_ctc_align reads in place) and their four kernel ids, which sit behind minor 13's and in
+ * front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by four (pce_kernel_name follows). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 15
+#define PCE_API_MINOR 16
 
 typedef struct pce_ctx pce_ctx;
 
@@ -733,6 +736,62 @@ int pce_bert_run(pce_ctx *ctx, const int32_t *input_ids, const int32_t *offsets 
 /* logits: [len][n_labels] or NULL; labels: [len] argmax (first maximum) or NULL */
 int pce_bert_fetch(pce_ctx *ctx, int32_t seq, float *logits, int32_t *labels);
 
+/* ---- wav2vec2 / MMS CTC acoustic model: the emissions of the forced alignment (the front half of Code/Aligners/CTCFA.py) ----
+ * Forward pass of transformers.Wav2Vec2ForCTC in eval mode (no dropout, layerdrop or SpecAugment, no attention mask: all windows have one
+ * length) over the resident batch, which must be at 16 kHz.  Both published forms: feat_norm 0 ("group": GroupNorm(C, C) behind the first
+ * convolution, no other normalisation in the feature encoder) with post-LN encoder layers (stable_ln 0: encoder.layer_norm in front of them),
+ * and feat_norm 1 ("layer": bias, LayerNorm and GELU behind every convolution) with pre-LN layers (stable_ln 1: encoder.layer_norm behind them).
+ * weights: the float32 state_dict flattened in the order of prosody-control-french-tts_amd/w2v_weights.py:tensor_order (convolution weights
+ * as [out][tap][in], the positional convolution's weight norm folded, its weights as [out][tap][in / groups]).
+ * Windowing is that of ctc-forced-aligner's generate_emissions (Aligners/ctc_emissions.hf_emissions): samples are int16 / 32768; a clip gets
+ * context_samples zeros in front and zeros behind to a whole number of windows, plus the context; windows of window_samples + 2 context_samples
+ * sit at stride window_samples; the model runs per window; frames [cut, T - cut + 1) of a window are kept, cut = int(context seconds * 50) --
+ * PCE_E_INVALID unless that is int(window seconds * 50) frames; the windows are joined and the first n_frames (pce_w2v_window_plan) kept;
+ * log-softmax in fp32 over the n_vocab columns; with `star` one column of zeros follows (n_cols = n_vocab + 1).  The windows are never
+ * materialised: the waveform layer reads the resident PCM and supplies the zeros itself.
+ * Arithmetic: the waveform convolution, its normalisation (group statistics in fp64 over a fixed partition of the time axis, added in a fixed
+ * order: no atomics) and every LayerNorm / softmax in fp32; every other product on MFMA operands of the context's operand mode
+ * (pce_whisper_set_operands) with fp32 accumulation; the residual stream of the encoder in fp32.  Windows run in chunks of windows_per_chunk
+ * (0: as many as keep one chunk's activation images within PCE_W2V_IMAGE_BUDGET bytes); every kernel is chosen by the model's widths alone and
+ * none reduces across windows: a window's emissions are bit-identical whatever the chunk size and whatever it is batched with.
+ * Limits (PCE_E_LIMIT at load): n_conv == 7; 10 taps at stride <= 8 on the waveform; conv_dim % 64 == 0 and <= 1024, % 128 == 0 behind the
+ * waveform layer, conv_kernel[i] * conv_dim[i - 1] % 64 == 0; n_state % 128 == 0 and <= 2048, n_head * 64 == n_state, n_inter % 128 == 0;
+ * pos_taps == 128 and n_state / pos_groups one of 16, 32, 48, 64.  PCE_E_STATE: run before load, shape / fetch / device before run.
+ * PCE_E_INVALID: a batch that is not at 16 kHz, a blob of the wrong size.  Since minor 16. */
+#define PCE_W2V_IMAGE_BUDGET ((int64_t)3 << 30)
+typedef struct pce_w2v_dims {
+    int32_t n_conv;                                        /* 7 */
+    int32_t conv_dim[8], conv_kernel[8], conv_stride[8];
+    int32_t feat_norm;                                     /* 0 "group", 1 "layer" */
+    int32_t conv_bias, n_state, n_head, n_inter, n_layer, stable_ln, pos_taps, pos_groups, n_vocab;
+    float ln_eps;
+} pce_w2v_dims;
+typedef struct pce_w2v_plan { int32_t window_samples, context_samples, windows_per_chunk /* 0 = by budget */, star /* append the zero column */; } pce_w2v_plan;
+int pce_w2v_load(pce_ctx *ctx, const pce_w2v_dims *dims, const float *weights, int64_t n_floats);
+/* the loader's conditions without a context (host arithmetic only): the status pce_w2v_load would return for these dims and this blob size, its
+ * message in msg (cap bytes; may be NULL) */
+int pce_w2v_check(const pce_w2v_dims *dims, int64_t n_floats, char *msg, size_t cap);
+int pce_w2v_run(pce_ctx *ctx, const pce_w2v_plan *plan);
+int pce_w2v_shape(pce_ctx *ctx, int32_t clip, int64_t *n_frames, int32_t *n_cols);
+/* log_probs: [n_frames][n_cols] */
+int pce_w2v_fetch(pce_ctx *ctx, int32_t clip, float *log_probs);
+/* the packed emissions of the last run, device memory [sum n_frames][n_cols], and the host tables pce_ctc_align takes with it (row_start[q]: the
+ * first row of clip q); all owned by the context and valid until its next pce_w2v_run / pce_w2v_load */
+int pce_w2v_device(pce_ctx *ctx, const float **d_emissions, const int64_t **h_row_start, const int32_t **h_n_frames, int32_t *n_cols);
+/* host arithmetic only (ctx-free): windows and kept frames of a clip of n_samples, as ctc_emissions.window_plan counts them */
+int pce_w2v_window_plan(int64_t n_samples, int32_t window_samples, int32_t context_samples, int64_t *n_windows, int64_t *n_frames);
+/* Stage self-tests: the three new stages through the run's own launches, 16-bit values as raw bits of the context's operand type.
+ * _wave: the waveform layer over the windows of ONE clip: w [C][10], bias [C] or NULL, gamma / beta [C]; out [n_windows][T0][C],
+ * T0 = (window + 2 context - 10) / stride + 1 (nothing is written when the window is shorter than the 10 taps).
+ * _lngelu: LayerNorm over the C columns of 16-bit rows, then GELU where gelu != 0 (in place on the device, as the run launches it).
+ * _posconv: out = x + GELU(conv(x) + bias) for n_win windows of T frames, x / out fp32 [n_win][T][d] (x is rounded to the operand type as it
+ * is staged), w [d][128][d / groups] 16-bit. */
+int pce_selftest_w2v_wave(pce_ctx *ctx, const int16_t *pcm, int64_t n_samples, int32_t window_samples, int32_t context_samples, int32_t feat_norm,
+                          int32_t C, int32_t stride, const float *w, const float *bias, const float *gamma, const float *beta, uint16_t *out);
+int pce_selftest_w2v_lngelu(pce_ctx *ctx, const uint16_t *x, int32_t rows, int32_t C, const float *w, const float *b, float eps, int32_t gelu, uint16_t *out);
+int pce_selftest_w2v_posconv(pce_ctx *ctx, const float *x, int32_t n_win, int32_t T, int32_t d, int32_t groups, const uint16_t *w, const float *bias,
+                             float *out);
+
 /* ---- asynchronous statistics fetch ---------------------------------------
  * The per-slice numbers of the last pce_energy_run / pce_lufs_run / pce_pitch_run are what the reference's
  * driver consumes per utterance (Code/audioPipeline.py:380-400) and what the sharded driver all-gathers
@@ -769,6 +828,8 @@ enum pce_kernel_id {
     /* minor 13: CREPE (PCE_K_CREPE_CONV2: block 2 alone, the launch that carries most of the work; PCE_K_CREPE_CONV: blocks 3-6; PCE_K_CREPE_DECODE:
      * the log-softmax / arg-max pass and the gather) */
     PCE_K_CREPE_FRAMES, PCE_K_CREPE_CONV1, PCE_K_CREPE_CONV2, PCE_K_CREPE_CONV, PCE_K_CREPE_CLASSIFIER, PCE_K_CREPE_DECODE, PCE_K_CREPE_VITERBI,
+    /* minor 16: pce_w2v_run as a whole; the waveform layer (statistics, finish and recompute passes together), the positional convolution, the log-softmax tail */
+    PCE_K_W2V, PCE_K_W2V_WAVE, PCE_K_W2V_POSCONV, PCE_K_W2V_TAIL,
     /* minor 15: the register form (both launch shapes), the general form and the walk back of pce_ctc_align; work count = trellis CELLS (frames for the walk) */
     PCE_K_CTC, PCE_K_CTC_GENERAL, PCE_K_CTC_TRACE,
     /* minor 10: their work count is swept CELLS (k_seqmatch: every range of every pair, recursion included; k_seqmatch_align: n_a * n_b) */

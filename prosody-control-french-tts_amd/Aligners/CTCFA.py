@@ -12,6 +12,7 @@ import os
 import numpy as np
 
 from .. import hostrules
+from ..engine import DeviceEmissions
 from ..textgrid_io import IntervalTier, TextGrid, write_textgrid
 from . import ctc_segments
 from .ctc_segments import preprocess_text  # noqa: F401  (the reference module's own function)
@@ -51,17 +52,21 @@ def write_word_file(rows, path):
 
 
 def process_files(audio_dir, transcription_dir, output_dir, language, star_frequency, romanize, *, engine, model=None, vocab=None,
-                  emissions=None, blank=0, batch_files=64):
+                  emissions=None, blank=0, batch_files=64, acoustic="torch"):
     """Code/Aligners/CTCFA.py:74-112 for a whole directory at once.  ``engine``: a ``ProsodyEngine``; ``model``: a ``transformers``
     ``...ForCTC`` model, run on the engine's device (``language`` only named the command's default checkpoint: the caller brings the
     model); ``vocab``: character -> index of the model's vocabulary (the star is the emissions' last column); ``emissions``:
     precomputed ``(tensor [B, T_max, V + 1], n_frames)`` in place of ``model``, one row per transcribed ``.wav`` of ``sorted(os.listdir)``.
+    ``acoustic``: ``"torch"`` (the default: ``model`` runs under torch, ``ctc_emissions.hf_emissions``) | ``"engine"`` (``model``'s forward pass on
+    the engine's own kernels, ``ctc_emissions.engine_emissions``: the emissions stay in device memory and the alignment reads them in place).
     ``star_frequency``: ``"segment"`` | ``"edges"``.  A clip the alignment gives no path (``status`` not 0: no frames, no characters left, fewer
     frames than characters, or a -inf score) gets an empty word file and a TextGrid whose ``Mots`` tier is empty.  -> {file name: word rows}."""
     if romanize:
         raise NotImplementedError("romanize=True needs uroman, which is absent")
     if vocab is None or (model is None and emissions is None):
         raise ValueError("process_files: vocab and one of model / emissions are required")
+    if acoustic not in ("torch", "engine"):
+        raise ValueError("acoustic: 'torch' or 'engine'")
     os.makedirs(output_dir, exist_ok=True)
     jobs = []
     for file_name in sorted(os.listdir(audio_dir)):
@@ -84,16 +89,20 @@ def process_files(audio_dir, transcription_dir, output_dir, language, star_frequ
             pcm.append(x)
         if emissions is not None:
             em, n_frames = emissions[0][b0:b0 + len(batch)], np.asarray(emissions[1])[b0:b0 + len(batch)]
+        elif acoustic == "engine":
+            from .ctc_emissions import engine_emissions
+            em, n_frames = engine_emissions(engine, model, pcm), None
         else:
             from .ctc_emissions import hf_emissions
             import torch
             em, n_frames = hf_emissions(model, pcm, torch.device("cuda", engine.device))
-        star_index = int(em.shape[2]) - 1                    # the column appended after the model's vocabulary
+        on_engine = isinstance(em, DeviceEmissions)         # (it carries its own lengths)
+        star_index = (em.n_cols if on_engine else int(em.shape[2])) - 1      # the column appended after the model's vocabulary
         if star_index <= max(vocab.values()):
             raise ValueError(f"vocab names index {max(vocab.values())}, the emissions hold {star_index} columns before the star")
         texts = [ctc_segments.tokenize(text, vocab, star_frequency, star_index) for _, text in batch]
         targets = [np.array([lab for word in tokens for lab in word], dtype=np.int32) for _, tokens in texts]
-        aligned = engine.ctc_align(em.contiguous(), targets, blank=blank, n_frames=n_frames)
+        aligned = engine.ctc_align(em, targets, blank=blank) if on_engine else engine.ctc_align(em.contiguous(), targets, blank=blank, n_frames=n_frames)
         for (file_name, _), (text_starred, tokens), res, x in zip(batch, texts, aligned, pcm):
             audio_path = os.path.join(audio_dir, file_name)
             rows = []

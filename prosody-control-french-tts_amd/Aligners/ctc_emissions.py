@@ -1,5 +1,6 @@
-"""Frame-wise log-probabilities of a ``transformers`` ``...ForCTC`` model for 16 kHz clips (torch plumbing, no kernel of this project:
-the model's forward pass on hand-written kernels is the stated next step).
+"""Frame-wise log-probabilities of a ``transformers`` ``...ForCTC`` model for 16 kHz clips: ``hf_emissions`` runs the caller's model under torch
+(plumbing, no kernel of this project; the default), ``engine_emissions`` runs a ``Wav2Vec2ForCTC``'s forward pass on the engine's own kernels
+(``pce_w2v_run``) with the same windowing and leaves the emissions in device memory.
 
 The windowing is that of ``ctc-forced-aligner``'s ``generate_emissions`` (third party and absent: restated from the published source,
 parity unpinned): a clip is padded to a whole number of windows of ``window_s`` seconds, every window is run with ``context_s`` seconds
@@ -68,3 +69,19 @@ def hf_emissions(model, pcm_list, device, window_s=30, context_s=2, batch_size=4
         em = torch.log_softmax(torch.cat(parts, dim=0)[:n_frames[ci]], dim=-1)
         out[ci, :n_frames[ci], :V] = em                                              # (the star column stays zero)
     return out.contiguous(), n_frames
+
+
+def engine_emissions(engine, model, pcm_list, window_s=30, context_s=2):
+    """``hf_emissions``' windows and numbers on the engine's kernels: uploads ``pcm_list`` (int16 arrays at 16 kHz) as the resident batch, loads
+    ``model`` (a ``transformers`` ``Wav2Vec2ForCTC``) once per model and engine, and returns the ``DeviceEmissions`` of
+    ``ProsodyEngine.w2v_emissions`` (star column appended), which ``ProsodyEngine.ctc_align`` reads in place."""
+    clips = []
+    for pcm in pcm_list:
+        x = np.asarray(pcm).reshape(-1)
+        if x.dtype.kind not in "iu":
+            raise ValueError("engine_emissions: int16 samples (the resident batch is PCM)")
+        clips.append(x.astype(np.int16))
+    if not engine.w2v_holds(model):
+        engine.w2v_load(model)
+    engine.upload(clips, SAMPLE_RATE)
+    return engine.w2v_emissions(window_s, context_s, star=True)

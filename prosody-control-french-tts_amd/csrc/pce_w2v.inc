@@ -1,0 +1,730 @@
+// pce_w2v.inc -- the wav2vec2 / MMS CTC acoustic model (transformers' Wav2Vec2ForCTC in eval mode) on the resident 16 kHz batch: the emissions
+// pce_ctc_align reads in place.  Included by pce_whisper_impl.inc after pce_bert.inc: the transformer body and six of the seven feature-encoder
+// convolutions run on that file's GEMM / attention / LayerNorm launchers.  New here: the waveform layer with its normalisation (k_w2v_wave_*), the
+// LayerNorm (+ GELU) over 16-bit rows (k_w2v_ln16), the grouped 128-tap positional convolution on MFMA (k_w2v_posconv) and the log-softmax /
+// context-cut / star-column tail (k_w2v_tail).
+//
+// A window is window + 2 context samples at stride window over the clip, `context` zeros in front and zeros behind to a whole number of windows
+// (ctc-forced-aligner's generate_emissions, as Aligners/ctc_emissions.hf_emissions restates it).  The windows are never materialised: the
+// waveform layer reads the resident PCM through a per-window table {first sample of the clip, the window's first sample relative to it, the
+// clip's length} and supplies the zeros itself.  Every image is time-major, [window][frame][channel]; from the last convolution on a window's
+// frames are padded to T_pad = 16 ceil(T / 16) rows (the transposed-V epilogue writes four frames at a time).  Pad rows hold finite values that
+// no real row ever reads: GEMM rows are independent, the attention masks keys >= T, the positional convolution takes frames >= T as zeros.
+// Which kernel computes a product follows from N and K alone (w2v_gemm), and no kernel reduces across windows: a window's emissions do not
+// depend on the chunk size or on what the window is batched with.
+#include <cstdarg>
+
+namespace {
+
+constexpr int WV_K0 = 10;              // taps of the waveform layer (every published wav2vec2 / MMS checkpoint)
+constexpr int WV_STRIDE_MAX = 8;       // its stride, at most
+constexpr int WV_PART = 1024;          // frames of one partial of the group-norm statistics (the fixed partition of the time axis)
+constexpr int WV_TILE = 256;           // frames per workgroup of the group form's second pass
+constexpr int WV_LN_F = 8;             // frames per workgroup of the layer form
+constexpr int WV_C_MAX = 1024;         // channels of the waveform layer, at most (the layer form's LDS tile)
+constexpr int PC_MT = 256, PC_TAPS = 128, PC_ROWS = PC_MT + PC_TAPS;      // positional convolution: frames per workgroup, taps, staged rows
+
+typedef __attribute__((ext_vector_type(2))) op_t opx2;
+typedef __attribute__((ext_vector_type(4))) op_t opx4_w;
+
+__device__ __forceinline__ float w2v_sample(const int16_t *__restrict__ pcm, int64_t base, int64_t s0, int64_t n, int64_t i)
+{
+    const int64_t p = s0 + i;
+    return (p >= 0 && p < n) ? (float)pcm[base + p] * (1.0f / 32768.0f) : 0.f;      // the zeros of the context and of the padding
+}
+// one output of the waveform convolution: the same operation sequence in the statistics pass and in the pass that recomputes it
+__device__ __forceinline__ float w2v_conv10(const float *x, const float (&wk)[WV_K0], float b)
+{
+    float y = 0.f;
+#pragma unroll
+    for (int k = 0; k < WV_K0; k++) y = fmaf(x[k], wk[k], y);
+    return y + b;
+}
+
+// Group form, pass 1: sum and sum of squares of every channel over the frames [WV_PART p, WV_PART (p + 1)) of window blockIdx.y, in fp64.
+__global__ __launch_bounds__(256) void k_w2v_wave_stats(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win /* [W][3] */,
+                                                        const float *__restrict__ w /* [C][10] */, const float *__restrict__ bias /* or null */, int C,
+                                                        int stride, int T0, int n_part, double *__restrict__ part /* [W][n_part][2][C] */)
+{
+    __shared__ float xs[(WV_PART - 1) * WV_STRIDE_MAX + 16];
+    const int wdx = (int)blockIdx.y, p = (int)blockIdx.x;
+    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];
+    const int f0 = p * WV_PART, nf = min(WV_PART, T0 - f0), ns = (nf - 1) * stride + WV_K0;
+    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i);
+    __syncthreads();
+    for (int ch = (int)threadIdx.x; ch < C; ch += 256) {
+        float wk[WV_K0];
+#pragma unroll
+        for (int k = 0; k < WV_K0; k++) wk[k] = w[ch * WV_K0 + k];
+        const float b = bias ? bias[ch] : 0.f;
+        double s = 0.0, q = 0.0;
+        for (int f = 0; f < nf; f++) {
+            const double y = (double)w2v_conv10(xs + f * stride, wk, b);
+            s += y; q += y * y;
+        }
+        double *o = part + (((int64_t)wdx * n_part + p) * 2) * C;
+        o[ch] = s; o[C + ch] = q;
+    }
+}
+// ... the partials of a (window, channel) added in the order of the partition: scale = gamma rstd, shift = beta - mean scale (biased variance)
+__global__ void k_w2v_wave_finish(const double *__restrict__ part, int n_part, int C, int T0, int W, const float *__restrict__ gamma,
+                                  const float *__restrict__ beta, float eps, float2 *__restrict__ ss /* [W][C] */)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= W * C) return;
+    const int wdx = i / C, ch = i - wdx * C;
+    double s = 0.0, q = 0.0;
+    for (int p = 0; p < n_part; p++) {
+        const double *o = part + (((int64_t)wdx * n_part + p) * 2) * C;
+        s += o[ch]; q += o[C + ch];
+    }
+    const double mean = s / (double)T0;
+    double var = q / (double)T0 - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const double scale = (double)gamma[ch] / sqrt(var + (double)eps);
+    ss[i] = make_float2((float)scale, (float)((double)beta[ch] - mean * scale));
+}
+// Group form, pass 2: the convolution again (its pre-norm image is never stored), normalised, GELU, op_t rows [window][T0][C]
+__global__ __launch_bounds__(256) void k_w2v_wave_group(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win, const float *__restrict__ w,
+                                                        const float *__restrict__ bias, const float2 *__restrict__ ss, int C /* % 2 == 0 */, int stride,
+                                                        int T0, op_t *__restrict__ out)
+{
+    __shared__ float xs[(WV_TILE - 1) * WV_STRIDE_MAX + 16];
+    const int wdx = (int)blockIdx.y;
+    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];
+    const int f0 = (int)blockIdx.x * WV_TILE, nf = min(WV_TILE, T0 - f0), ns = (nf - 1) * stride + WV_K0;
+    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i);
+    __syncthreads();
+    for (int ch = 2 * (int)threadIdx.x; ch < C; ch += 512) {
+        float wa[WV_K0], wb[WV_K0];
+#pragma unroll
+        for (int k = 0; k < WV_K0; k++) { wa[k] = w[ch * WV_K0 + k]; wb[k] = w[(ch + 1) * WV_K0 + k]; }
+        const float ba = bias ? bias[ch] : 0.f, bb = bias ? bias[ch + 1] : 0.f;
+        const float2 sa = ss[(int64_t)wdx * C + ch], sb = ss[(int64_t)wdx * C + ch + 1];
+        op_t *o = out + ((int64_t)wdx * T0 + f0) * C + ch;
+        for (int f = 0; f < nf; f++) {
+            const float ya = w2v_conv10(xs + f * stride, wa, ba), yb = w2v_conv10(xs + f * stride, wb, bb);
+            opx2 v;
+            v[0] = (op_t)gelu_exact(fmaf(ya, sa.x, sa.y)); v[1] = (op_t)gelu_exact(fmaf(yb, sb.x, sb.y));
+            *reinterpret_cast<opx2 *>(o + (int64_t)f * C) = v;
+        }
+    }
+}
+// Layer form: convolution + bias into an LDS tile [frame][channel], then one wave per frame: LayerNorm over the channels (fp32, two-pass), GELU
+__global__ __launch_bounds__(256) void k_w2v_wave_layer(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win, const float *__restrict__ w,
+                                                        const float *__restrict__ bias, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                        int C /* <= WV_C_MAX */, int stride, int T0, float eps, op_t *__restrict__ out)
+{
+    __shared__ float xs[(WV_LN_F - 1) * WV_STRIDE_MAX + 16];
+    __shared__ float tile[WV_LN_F * WV_C_MAX];
+    const int wdx = (int)blockIdx.y, lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
+    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];
+    const int f0 = (int)blockIdx.x * WV_LN_F, nf = min(WV_LN_F, T0 - f0), ns = (nf - 1) * stride + WV_K0;
+    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i);
+    __syncthreads();
+    for (int ch = (int)threadIdx.x; ch < C; ch += 256) {
+        float wk[WV_K0];
+#pragma unroll
+        for (int k = 0; k < WV_K0; k++) wk[k] = w[ch * WV_K0 + k];
+        const float b = bias ? bias[ch] : 0.f;
+        for (int f = 0; f < nf; f++) tile[f * C + ch] = w2v_conv10(xs + f * stride, wk, b);
+    }
+    __syncthreads();
+    for (int f = wv; f < nf; f += 4) {                              // (wave-uniform: the DPP reductions see whole waves)
+        const float *row = tile + f * C;
+        float s = 0.f;
+        for (int ch = lane; ch < C; ch += 64) s += row[ch];
+        const float mean = wave_dpp_sum_f32(s) / (float)C;
+        float q = 0.f;
+        for (int ch = lane; ch < C; ch += 64) { const float a = row[ch] - mean; q += a * a; }
+        const float inv = rsqrtf(wave_dpp_sum_f32(q) / (float)C + eps);
+        op_t *o = out + ((int64_t)wdx * T0 + f0 + f) * C;
+        for (int ch = lane; ch < C; ch += 64) o[ch] = (op_t)gelu_exact((row[ch] - mean) * inv * gamma[ch] + beta[ch]);
+    }
+}
+
+// LayerNorm over the channels of 16-bit rows (one wave per row, the row in registers: C % 8 == 0, C <= LN_D_MAX), then GELU where asked: the
+// layer form's convolutions 1-6 (in place: a wave reads its whole row before it writes) and the feature projection's LayerNorm.
+template <bool GELU>
+__global__ __launch_bounds__(256) void k_w2v_ln16(const op_t *x, const float *__restrict__ w, const float *__restrict__ b, int64_t rows, int C, float eps,
+                                                  op_t *out)
+{
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = (int)threadIdx.x & 63;
+    if (row >= rows) return;
+    const int nc = C >> 3;
+    float v[4][8];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int idx = lane + 64 * i;
+        opx8 t = {};
+        if (idx < nc) t = *reinterpret_cast<const opx8 *>(x + row * C + 8 * idx);
+#pragma unroll
+        for (int e = 0; e < 8; e++) v[i][e] = idx < nc ? (float)t[e] : 0.f;
+        s += ((v[i][0] + v[i][1]) + (v[i][2] + v[i][3])) + ((v[i][4] + v[i][5]) + (v[i][6] + v[i][7]));
+    }
+    const float mean = wave_dpp_sum_f32(s) / (float)C;
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (lane + 64 * i < nc) {
+#pragma unroll
+            for (int e = 0; e < 8; e++) { const float a = v[i][e] - mean; q += a * a; }
+        }
+    const float inv = rsqrtf(wave_dpp_sum_f32(q) / (float)C + eps);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int idx = lane + 64 * i;
+        if (idx < nc) {
+            opx8 o;
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                const float y = (v[i][e] - mean) * inv * w[8 * idx + e] + b[8 * idx + e];
+                o[e] = (op_t)(GELU ? gelu_exact(y) : y);
+            }
+            *reinterpret_cast<opx8 *>(out + row * C + 8 * idx) = o;
+        }
+    }
+}
+
+// Positional convolution: out = x + GELU(Conv1d(d, d, 128, padding 64, groups G)(x) + bias), the last output frame of the convolution dropped, so
+// frame t reads frames t - 64 .. t + 63 of its own window (zeros outside [0, T)).  One workgroup = one group's CG = d / G output columns x
+// PC_MT frames of one window.  Rows t0 - 64 .. t0 + PC_MT + 63 of the group's CG input channels are rounded to op_t into LDS once; the product
+// is a GEMM over K = (tap, channel) whose A fragment of tap k is the same image read k rows further down, so the staged rows serve all 128 taps.
+// The weights [column][tap][channel] stream from L2 straight into the B fragments (16 bytes per lane: 8 channels of one tap, CG % 8 == 0).
+// Four waves x 64 frames; v_mfma_f32_16x16x32: lane (m = lane & 15, g = lane >> 4) gives A[m][8 g ..], B[8 g ..][m] and holds D[4 g + i][m].
+// LDS rows are CG + 8 elements apart: the 16 rows of a fragment read start 16 bytes x an odd multiple apart and meet no bank twice.
+template <int CG>
+__global__ __launch_bounds__(256) void k_w2v_posconv(const float *__restrict__ x /* [window][rows_per_win][d] */, const op_t *__restrict__ w,
+                                                     const float *__restrict__ bias, int T, int rows_per_win, int d, float *__restrict__ out)
+{
+    constexpr int LD = CG + 8, NB = CG / 16, TPR = CG / 4, KT = PC_TAPS * CG / 32;
+    __shared__ __attribute__((aligned(16))) op_t xs[PC_ROWS * LD];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, m = lane & 15, g4 = lane >> 4;
+    const int t0 = (int)blockIdx.x * PC_MT, grp = (int)blockIdx.y;
+    const int64_t row0 = (int64_t)blockIdx.z * rows_per_win;
+    for (int i = tid; i < PC_ROWS * TPR; i += 256) {
+        const int r = i / TPR, c4 = (i - r * TPR) * 4, t = t0 - PC_TAPS / 2 + r;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t >= 0 && t < T) v = *reinterpret_cast<const float4 *>(x + (row0 + t) * d + grp * CG + c4);
+        opx4_w o; o[0] = (op_t)v.x; o[1] = (op_t)v.y; o[2] = (op_t)v.z; o[3] = (op_t)v.w;
+        *reinterpret_cast<opx4_w *>(xs + r * LD + c4) = o;
+    }
+    __syncthreads();
+    f32x4 acc[4][NB];
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++) acc[a][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (t0 + wv * 64 < T) {                                       // (wave-uniform) a wave whose 64 frames lie behind the window's last has no product
+        const op_t *wb = w + (int64_t)(grp * CG + m) * (PC_TAPS * CG) + 8 * g4;
+        const op_t *xa = xs + (wv * 64 + m) * LD;
+#pragma unroll 4
+        for (int s = 0; s < KT; s++) {
+            const int kk = s * 32 + 8 * g4, k = kk / CG, ci = kk - k * CG;
+            opx8 a[4], b[NB];
+#pragma unroll
+            for (int nb = 0; nb < NB; nb++) b[nb] = *reinterpret_cast<const opx8 *>(wb + (int64_t)nb * 16 * (PC_TAPS * CG) + s * 32);
+#pragma unroll
+            for (int mb = 0; mb < 4; mb++) a[mb] = *reinterpret_cast<const opx8 *>(xa + (mb * 16 + k) * LD + ci);
+#pragma unroll
+            for (int mb = 0; mb < 4; mb++)
+#pragma unroll
+                for (int nb = 0; nb < NB; nb++) acc[mb][nb] = mfma16(a[mb], b[nb], acc[mb][nb]);
+        }
+    }
+#pragma unroll
+    for (int mb = 0; mb < 4; mb++)
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int t = t0 + wv * 64 + mb * 16 + 4 * g4 + i, col = grp * CG + nb * 16 + m;
+                if (t >= rows_per_win) continue;
+                const int64_t idx = (row0 + t) * d + col;
+                const float h = x[idx];
+                out[idx] = t < T ? h + gelu_exact(acc[mb][nb][i] + bias[col]) : h;       // (a pad row: any finite value)
+            }
+}
+
+// The tail: frames [cut, cut + n_keep) of every window, log-softmax in fp32 over the V real columns of the padded logits, a zero <star> column
+// behind them where asked, packed at the window's place among its clip's kept frames.  One wave per frame.
+__global__ __launch_bounds__(256) void k_w2v_tail(const float *__restrict__ logits /* [window][rows_per_win][Vp] */, int Vp, int V, int star,
+                                                  const int64_t *__restrict__ tab /* [W][2]: first output row, frames kept */, int rows_per_win, int cut,
+                                                  float *__restrict__ out, int n_cols)
+{
+    const int wdx = (int)blockIdx.y, lane = (int)threadIdx.x & 63;
+    const int64_t f = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (f >= tab[2 * wdx + 1]) return;
+    const float *src = logits + ((int64_t)wdx * rows_per_win + cut + f) * Vp;
+    float *dst = out + (tab[2 * wdx] + f) * n_cols;
+    float mx = -INFINITY;
+    for (int j = lane; j < V; j += 64) mx = fmaxf(mx, src[j]);
+    mx = wave_xor_max(mx);
+    float s = 0.f;
+    for (int j = lane; j < V; j += 64) s += expf(src[j] - mx);
+    const float ls = logf(wave_dpp_sum_f32(s));
+    for (int j = lane; j < V; j += 64) dst[j] = (src[j] - mx) - ls;
+    if (star && lane == 0) dst[V] = 0.f;
+}
+
+static int64_t w2v_frames_of(int64_t samples) { return (int64_t)((double)samples / 16000.0 * 50.0); }      // int(seconds * 50), as the host restatement rounds
+static int w2v_rows_pad(int T) { return (int)div_up(T, 16) * 16; }
+
+// Which tiled kernel computes a product: by N and K alone (launch_gemm's rule also looks at the row count, and the rows here follow the chunk).
+// false, and nothing launched, for a shape the chosen kernel does not compute exactly (w2v_check's limits keep that from happening: N % 128,
+// K % 64, the V columns from a multiple of 128 on)
+template <int EPI>
+static bool w2v_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, const op_t *B, int M, int N, int K, const float *bias, void *C, int64_t ldc,
+                     int64_t c_batch, int batch, const float *pos = nullptr, int pos_T = 1, int v_col0 = 0, int vt_sp = AT_SP)
+{
+    const GemmShape s{M, N, K, lda, batch, v_col0};
+    const int kind = (gemm_fits<EPI>(GK_WIDE, s) && N >= 1536) ? GK_WIDE : GK_128;
+    if (!gemm_fits<EPI>(kind, s)) return false;
+    launch_gemm_kernel<EPI>(c, kind, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, batch, pos, pos_T, v_col0, vt_sp);
+    return true;
+}
+
+static void w2v_launch_posconv(pce_ctx *c, const float *x, const op_t *w, const float *bias, int T, int rows_per_win, int d, int groups, int n_win, float *out)
+{
+    const int cg = d / groups;
+    const dim3 grid((unsigned)div_up(rows_per_win, PC_MT), (unsigned)groups, (unsigned)n_win), block(256);
+    KernelTimer kt(c, PCE_K_W2V_POSCONV, nullptr, 2.0 * n_win * (double)T * d * PC_TAPS * cg);
+    switch (cg) {
+    case 16: hipLaunchKernelGGL(k_w2v_posconv<16>, grid, block, 0, c->stream, x, w, bias, T, rows_per_win, d, out); break;
+    case 32: hipLaunchKernelGGL(k_w2v_posconv<32>, grid, block, 0, c->stream, x, w, bias, T, rows_per_win, d, out); break;
+    case 48: hipLaunchKernelGGL(k_w2v_posconv<48>, grid, block, 0, c->stream, x, w, bias, T, rows_per_win, d, out); break;
+    default: hipLaunchKernelGGL(k_w2v_posconv<64>, grid, block, 0, c->stream, x, w, bias, T, rows_per_win, d, out); break;
+    }
+}
+static bool w2v_posconv_fits(int d, int groups)
+{
+    if (groups <= 0 || d <= 0 || d % groups) return false;
+    const int cg = d / groups;
+    return cg == 16 || cg == 32 || cg == 48 || cg == 64;
+}
+
+// the waveform layer of n_win windows: group form (feat_norm 0: statistics, finish, recompute) or layer form (1)
+static int w2v_launch_wave(pce_ctx *c, int feat_norm, const int64_t *d_win, int n_win, const float *w, const float *bias, const float *gamma,
+                           const float *beta, int C, int stride, int T0, DevBuf &part, DevBuf &ss, op_t *out)
+{
+    KernelTimer kt(c, PCE_K_W2V_WAVE, nullptr, 2.0 * n_win * (double)T0 * C * WV_K0 * (feat_norm == 0 ? 2 : 1));
+    if (feat_norm == 0) {
+        const int n_part = (int)div_up(T0, WV_PART);
+        PCE_HIP(c, part.reserve(sizeof(double) * (size_t)n_win * n_part * 2 * C));
+        PCE_HIP(c, ss.reserve(sizeof(float2) * (size_t)n_win * C));
+        hipLaunchKernelGGL(k_w2v_wave_stats, dim3((unsigned)n_part, (unsigned)n_win), dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias, C, stride, T0, n_part,
+                           part.as<double>());
+        hipLaunchKernelGGL(k_w2v_wave_finish, dim3((unsigned)div_up((int64_t)n_win * C, 256)), dim3(256), 0, c->stream, part.as<double>(), n_part, C, T0, n_win,
+                           gamma, beta, 1e-5f, ss.as<float2>());
+        hipLaunchKernelGGL(k_w2v_wave_group, dim3((unsigned)div_up(T0, WV_TILE), (unsigned)n_win), dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias,
+                           ss.as<float2>(), C, stride, T0, out);
+    } else {
+        hipLaunchKernelGGL(k_w2v_wave_layer, dim3((unsigned)div_up(T0, WV_LN_F), (unsigned)n_win), dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias, gamma,
+                           beta, C, stride, T0, 1e-5f, out);
+    }
+    return PCE_OK;
+}
+static void w2v_launch_ln16(pce_ctx *c, bool gelu, const op_t *x, const float *w, const float *b, int64_t rows, int C, float eps, op_t *out)
+{
+    const dim3 grid((unsigned)div_up(rows, 4)), block(256);
+    if (gelu) hipLaunchKernelGGL(k_w2v_ln16<true>, grid, block, 0, c->stream, x, w, b, rows, C, eps, out);
+    else hipLaunchKernelGGL(k_w2v_ln16<false>, grid, block, 0, c->stream, x, w, b, rows, C, eps, out);
+}
+
+// floats of the weight blob (w2v_weights.tensor_order)
+static int64_t w2v_blob_floats(const pce_w2v_dims &m)
+{
+    const bool layer = m.feat_norm == 1;
+    int64_t n = 0;
+    for (int i = 0; i < m.n_conv; i++) {
+        const int64_t cin = i ? m.conv_dim[i - 1] : 1, co = m.conv_dim[i];
+        n += co * cin * m.conv_kernel[i] + (m.conv_bias ? co : 0) + ((layer || i == 0) ? 2 * co : 0);
+    }
+    const int64_t d = m.n_state, c6 = m.conv_dim[m.n_conv - 1], I = m.n_inter;
+    n += 2 * c6 + d * c6 + d;                                             // feature projection: LayerNorm, projection
+    n += d * (d / m.pos_groups) * m.pos_taps + d + 2 * d;                 // positional convolution (folded), encoder LayerNorm
+    n += (int64_t)m.n_layer * (4 * (d * d + d) + 2 * d + (I * d + I) + (d * I + d) + 2 * d);
+    return n + (int64_t)m.n_vocab * d + m.n_vocab;
+}
+
+// The loader's conditions, host arithmetic only (pce_w2v_check hands them out without a context): status and its message
+static int w2v_refuse(char *msg, size_t cap, int code, const char *fmt, ...) __attribute__((format(printf, 4, 5)));
+static int w2v_refuse(char *msg, size_t cap, int code, const char *fmt, ...)
+{
+    if (msg && cap) { va_list ap; va_start(ap, fmt); vsnprintf(msg, cap, fmt, ap); va_end(ap); }
+    return code;
+}
+static int w2v_check(const pce_w2v_dims &m, int64_t n_floats, char *msg, size_t cap)
+{
+    const int d = m.n_state, I = m.n_inter, L = m.n_layer, V = m.n_vocab;
+    if (m.n_conv != 7) return w2v_refuse(msg, cap, PCE_E_LIMIT, "wav2vec2 with %d feature-encoder layers (the run path holds 7)", m.n_conv);
+    if (m.feat_norm != 0 && m.feat_norm != 1) return w2v_refuse(msg, cap, PCE_E_INVALID, "feat_norm %d (0 = group, 1 = layer)", m.feat_norm);
+    if (m.conv_kernel[0] != WV_K0 || m.conv_stride[0] < 1 || m.conv_stride[0] > WV_STRIDE_MAX)
+        return w2v_refuse(msg, cap, PCE_E_LIMIT, "waveform layer with %d taps at stride %d (the kernel holds %d taps, stride <= %d)", m.conv_kernel[0], m.conv_stride[0], WV_K0,
+                        WV_STRIDE_MAX);
+    for (int i = 0; i < 7; i++) {
+        const int co = m.conv_dim[i];
+        if (co <= 0 || co % 64 || co > WV_C_MAX || (i && co % 128) || m.conv_kernel[i] < 1 || m.conv_stride[i] < 1)
+            return w2v_refuse(msg, cap, PCE_E_LIMIT, "conv layer %d: %d channels, %d taps, stride %d (channels %% 64 == 0 and <= %d, %% 128 == 0 behind the waveform layer)", i,
+                            co, m.conv_kernel[i], m.conv_stride[i], WV_C_MAX);
+        if (i && ((int64_t)m.conv_kernel[i] * m.conv_dim[i - 1]) % 64)
+            return w2v_refuse(msg, cap, PCE_E_LIMIT, "conv layer %d: K = %d taps x %d channels is no multiple of 64 (the GEMM's K step)", i, m.conv_kernel[i], m.conv_dim[i - 1]);
+    }
+    if (d <= 0 || d % 128 || m.n_head * 64 != d || L <= 0 || V <= 0)
+        return w2v_refuse(msg, cap, PCE_E_LIMIT, "unsupported wav2vec2 dims (need n_state %% 128 == 0, head size 64, n_layer >= 1, n_vocab >= 1)");
+    if (d > LN_D_MAX) return w2v_refuse(msg, cap, PCE_E_LIMIT, "wav2vec2 with n_state %d: the LayerNorm kernels hold at most %d", d, LN_D_MAX);
+    if (I <= 0 || I % 128) return w2v_refuse(msg, cap, PCE_E_LIMIT, "n_inter %d is no multiple of 128 (the GEMM's column tile)", I);
+    if (m.pos_taps != PC_TAPS) return w2v_refuse(msg, cap, PCE_E_LIMIT, "positional convolution with %d taps (the kernel holds %d)", m.pos_taps, PC_TAPS);
+    if (!w2v_posconv_fits(d, m.pos_groups))
+        return w2v_refuse(msg, cap, PCE_E_LIMIT, "positional convolution: n_state %d in %d groups (need 16, 32, 48 or 64 columns per group)", d, m.pos_groups);
+    if (!(m.ln_eps > 0.f)) return w2v_refuse(msg, cap, PCE_E_INVALID, "ln_eps must be positive");
+    const int64_t expect = w2v_blob_floats(m);
+    if (n_floats != expect) return w2v_refuse(msg, cap, PCE_E_INVALID, "wav2vec2 weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
+    return PCE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pce_w2v_check(const pce_w2v_dims *dims, int64_t n_floats, char *msg, size_t cap)
+{
+    if (msg && cap) msg[0] = 0;
+    return dims ? w2v_check(*dims, n_floats, msg, cap) : PCE_E_INVALID;
+}
+
+int pce_w2v_load(pce_ctx *c, const pce_w2v_dims *dims, const float *weights, int64_t n_floats)
+{
+    if (!c || !dims || !weights) return PCE_E_INVALID;
+    const pce_w2v_dims &m = *dims;
+    const int d = m.n_state, I = m.n_inter, L = m.n_layer, V = m.n_vocab;
+    {
+        char msg[320];
+        const int rc = w2v_check(m, n_floats, msg, sizeof msg);
+        if (rc) return pce_fail(c, rc, "%s", msg);
+    }
+    PCE_HIP(c, hipSetDevice(c->device));
+    WhisperState::W2v &b = ws_of(c)->w2v;
+    b.dims = m; b.loaded = false; b.n_clips = -1; b.layers.assign((size_t)L, {});
+    std::vector<float> mats, vecs;
+    auto add_vec = [&](const float *p, size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), p, p + n); vecs.resize((vecs.size() + 3) & ~(size_t)3); return o; };
+    auto add_mat = [&](const float *p, size_t n) { size_t o = mats.size(); mats.insert(mats.end(), p, p + n); return o; };
+    const bool layer = m.feat_norm == 1;
+    const float *p = weights;
+    for (int i = 0; i < 7; i++) {
+        const size_t cin = i ? (size_t)m.conv_dim[i - 1] : 1, co = (size_t)m.conv_dim[i], nw = co * cin * (size_t)m.conv_kernel[i];
+        WhisperState::W2v::Conv &cv = b.conv[i];
+        cv.w = i ? add_mat(p, nw) : add_vec(p, nw); p += nw;                       // the waveform layer's taps stay fp32
+        cv.has_b = m.conv_bias != 0; cv.has_ln = layer || i == 0;
+        if (cv.has_b) { cv.b = add_vec(p, co); p += co; }
+        if (cv.has_ln) { cv.g = add_vec(p, co); p += co; cv.beta = add_vec(p, co); p += co; }
+    }
+    const size_t c6 = (size_t)m.conv_dim[6], dd = (size_t)d * d, cg = (size_t)(d / m.pos_groups);
+    b.fp_ln_w = add_vec(p, c6); p += c6; b.fp_ln_b = add_vec(p, c6); p += c6;
+    b.proj_w = add_mat(p, (size_t)d * c6); p += (size_t)d * c6; b.proj_b = add_vec(p, (size_t)d); p += d;
+    b.pos_w = add_mat(p, (size_t)d * cg * PC_TAPS); p += (size_t)d * cg * PC_TAPS; b.pos_b = add_vec(p, (size_t)d); p += d;
+    b.enc_ln_w = add_vec(p, (size_t)d); p += d; b.enc_ln_b = add_vec(p, (size_t)d); p += d;
+    for (int l = 0; l < L; l++) {
+        WhisperState::W2v::Layer &ly = b.layers[(size_t)l];
+        const float *qw = p, *qb = qw + dd, *kw = qb + d, *kb = kw + dd, *vw = kb + d, *vb = vw + dd;
+        ly.qkv_w = add_mat(qw, dd); add_mat(kw, dd); add_mat(vw, dd);                                   // fused [3d][d]
+        {   // (one vector: the three biases contiguous)
+            std::vector<float> qkv_b(3 * (size_t)d);
+            memcpy(qkv_b.data(), qb, sizeof(float) * d); memcpy(qkv_b.data() + d, kb, sizeof(float) * d); memcpy(qkv_b.data() + 2 * d, vb, sizeof(float) * d);
+            ly.qkv_b = add_vec(qkv_b.data(), qkv_b.size());
+        }
+        p = vb + d;
+        ly.out_w = add_mat(p, dd); p += dd; ly.out_b = add_vec(p, (size_t)d); p += d;
+        ly.ln1_w = add_vec(p, (size_t)d); p += d; ly.ln1_b = add_vec(p, (size_t)d); p += d;
+        ly.m1_w = add_mat(p, (size_t)I * d); p += (size_t)I * d; ly.m1_b = add_vec(p, (size_t)I); p += I;
+        ly.m2_w = add_mat(p, (size_t)d * I); p += (size_t)d * I; ly.m2_b = add_vec(p, (size_t)d); p += d;
+        ly.ln2_w = add_vec(p, (size_t)d); p += d; ly.ln2_b = add_vec(p, (size_t)d); p += d;
+    }
+    {   // lm_head [n_vocab][d] padded with zero rows to whole 128-column GEMM tiles
+        b.Vp = (int)div_up(V, 128) * 128;
+        std::vector<float> lw((size_t)b.Vp * d, 0.f), lb((size_t)b.Vp, 0.f);
+        memcpy(lw.data(), p, sizeof(float) * (size_t)V * d); p += (size_t)V * d;
+        memcpy(lb.data(), p, sizeof(float) * (size_t)V); p += V;
+        b.lm_w = add_mat(lw.data(), lw.size()); b.lm_b = add_vec(lb.data(), lb.size());
+    }
+    DevBuf tmp;
+    PCE_HIP(c, tmp.reserve(sizeof(float) * mats.size()));
+    PCE_HIP(c, b.w16.reserve(sizeof(op_t) * mats.size() + 256));
+    PCE_HIP(c, b.w32.reserve(sizeof(float) * vecs.size()));
+    PCE_HIP(c, hipMemcpyAsync(tmp.p, mats.data(), sizeof(float) * mats.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(b.w32.p, vecs.data(), sizeof(float) * vecs.size(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(), b.w16.as<op_t>(),
+                       (int64_t)mats.size());
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    b.loaded = true;
+    return PCE_OK;
+}
+
+int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan)
+{
+    if (!c || !plan) return PCE_E_INVALID;
+    WhisperState::W2v &b = ws_of(c)->w2v;
+    if (!b.loaded) return pce_fail(c, PCE_E_STATE, "pce_w2v_run before pce_w2v_load");
+    if (!c->d_pcm) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
+    if (c->rate != 16000) return pce_fail(c, PCE_E_INVALID, "wav2vec2 runs at 16000 Hz: the resident batch is at %d Hz (resample it first)", c->rate);
+    const pce_w2v_dims &m = b.dims;
+    const int64_t window = plan->window_samples, context = plan->context_samples;
+    if (window < 1 || context < 0 || plan->windows_per_chunk < 0 || window + 2 * context > ((int64_t)1 << 26))
+        return pce_fail(c, PCE_E_INVALID, "bad wav2vec2 plan (window_samples >= 1, context_samples >= 0, window + 2 context <= 2^26, windows_per_chunk >= 0)");
+    int Tl[7];
+    {
+        int64_t t = window + 2 * context;
+        for (int i = 0; i < 7; i++) { t = t >= m.conv_kernel[i] ? (t - m.conv_kernel[i]) / m.conv_stride[i] + 1 : 0; Tl[i] = (int)t; }
+    }
+    const int T = Tl[6], wf = (int)w2v_frames_of(window), cut = (int)w2v_frames_of(context);
+    // frames [cut, T - cut + 1) of a window's T are kept (the slice ends at T at the latest)
+    if (T < 1 || wf < 1 || std::min(T - cut + 1, T) - cut != wf)
+        return pce_fail(c, PCE_E_INVALID, "the model gives %d frames per window of %lld + 2 x %lld samples, %d of them kept behind a cut of %d: %d expected (20 ms stride)", T,
+                        (long long)window, (long long)context, std::min(T - cut + 1, T) - cut, cut, wf);
+    PCE_HIP(c, hipSetDevice(c->device));
+    b.n_clips = -1;
+    const int n = c->n_clips, d = m.n_state, H = m.n_head, I = m.n_inter, L = m.n_layer, V = m.n_vocab, Vp = b.Vp, C6 = m.conv_dim[6];
+    const int T_pad = w2v_rows_pad(T), vt_sp = (int)div_up(T, 64) * 64, n_cols = V + (plan->star ? 1 : 0);
+    // the attention's buffer resources and the transposed-V epilogue form 32-bit byte offsets inside one window
+    if (((int64_t)T * 2 * d + 64) * 2 >= ((int64_t)1 << 31) || (int64_t)64 * vt_sp * 2 >= ((int64_t)1 << 31))
+        return pce_fail(c, PCE_E_LIMIT, "%d frames per window: the attention kernel's 32-bit offsets do not reach that far", T);
+    // the plan: every clip's windows, the rows its kept frames take
+    std::vector<int64_t> win_tab, tail_tab;
+    b.row_start.assign((size_t)n, 0); b.n_frames.assign((size_t)n, 0);
+    int64_t rows_total = 0;
+    for (int q = 0; q < n; q++) {
+        const int64_t len = c->clip_off[(size_t)q + 1] - c->clip_off[(size_t)q];
+        int64_t n_win, keep;
+        pce_w2v_window_plan(len, (int32_t)window, (int32_t)context, &n_win, &keep);
+        b.row_start[(size_t)q] = rows_total; b.n_frames[(size_t)q] = (int32_t)keep;
+        for (int64_t j = 0; j < n_win; j++) {
+            win_tab.push_back(c->clip_off[(size_t)q]); win_tab.push_back(j * window - context); win_tab.push_back(len);
+            tail_tab.push_back(rows_total + j * wf); tail_tab.push_back(std::min<int64_t>(wf, keep - j * wf));
+        }
+        rows_total += keep;
+        if (rows_total > INT32_MAX) return pce_fail(c, PCE_E_LIMIT, "more than 2^31 emission frames in one batch");
+    }
+    const int64_t W = (int64_t)(win_tab.size() / 3);
+    b.n_cols = n_cols;
+    if (W == 0) { b.n_clips = 0; return PCE_OK; }
+    // chunk size: the images of one window (the two ping-pong convolution images, the encoder's buffers)
+    int64_t img_e[2] = {0, 0};
+    for (int i = 0; i < 7; i++) img_e[i & 1] = std::max<int64_t>(img_e[i & 1], (int64_t)(i == 6 ? T_pad : Tl[i]) * m.conv_dim[i]);
+    const int64_t per_window = 2 * (img_e[0] + img_e[1]) + (int64_t)T_pad * (2LL * C6 + 8LL * d + 2LL * d + 4LL * d + 2LL * d + 2LL * I + 4LL * Vp) +
+                               2LL * d * vt_sp + (m.feat_norm == 0 ? 16LL * div_up(Tl[0], WV_PART) * m.conv_dim[0] : 0);
+    int64_t wpc = plan->windows_per_chunk > 0 ? plan->windows_per_chunk : std::max<int64_t>(1, PCE_W2V_IMAGE_BUDGET / per_window);
+    wpc = std::min<int64_t>(std::min<int64_t>(wpc, W), 4096);
+    while (wpc > 1 && wpc * T_pad * (int64_t)std::max(std::max(3 * d, I), Vp) >= ((int64_t)1 << 31)) wpc--;      // (the launchers count rows in int)
+    const int64_t M_max = wpc * T_pad;
+    PCE_HIP(c, b.wintab.reserve(sizeof(int64_t) * win_tab.size()));
+    PCE_HIP(c, b.tailtab.reserve(sizeof(int64_t) * tail_tab.size()));
+    PCE_HIP(c, b.atab.reserve(sizeof(int) * 2 * (size_t)wpc));
+    PCE_HIP(c, b.img[0].reserve(sizeof(op_t) * (size_t)(wpc * img_e[0]) + 4096));
+    PCE_HIP(c, b.img[1].reserve(sizeof(op_t) * (size_t)(wpc * img_e[1]) + 4096));
+    PCE_HIP(c, b.fpln.reserve(sizeof(op_t) * (size_t)M_max * C6 + 4096));
+    PCE_HIP(c, b.h0.reserve(sizeof(float) * (size_t)M_max * d));
+    PCE_HIP(c, b.h.reserve(sizeof(float) * (size_t)M_max * d));
+    PCE_HIP(c, b.ln.reserve(sizeof(op_t) * (size_t)M_max * d + 4096));
+    PCE_HIP(c, b.qk.reserve(sizeof(op_t) * (size_t)M_max * 2 * d + 4096));
+    PCE_HIP(c, b.attn.reserve(sizeof(op_t) * (size_t)M_max * d + 4096));
+    PCE_HIP(c, b.hidden.reserve(sizeof(op_t) * (size_t)M_max * I + 4096));
+    PCE_HIP(c, b.logits.reserve(sizeof(float) * (size_t)M_max * Vp));
+    const size_t vt_elems = (size_t)wpc * (size_t)d * vt_sp + 64;
+    PCE_HIP(c, b.vt.reserve(sizeof(op_t) * vt_elems));
+    PCE_HIP(c, b.em.reserve(sizeof(float) * (size_t)rows_total * n_cols + 256));
+    {
+        std::vector<int> at(2 * (size_t)wpc);
+        for (int64_t i = 0; i < wpc; i++) { at[(size_t)i] = (int)(i * T_pad); at[(size_t)(wpc + i)] = T; }
+        PCE_HIP(c, hipMemcpyAsync(b.wintab.p, win_tab.data(), sizeof(int64_t) * win_tab.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(b.tailtab.p, tail_tab.data(), sizeof(int64_t) * tail_tab.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(b.atab.p, at.data(), sizeof(int) * at.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    // pad rows and the key columns no launch writes: cleared, so that no stale bits (a NaN) meet a zero probability
+    PCE_HIP(c, hipMemsetAsync(b.img[0].p, 0, sizeof(op_t) * (size_t)(wpc * img_e[0]) + 4096, c->stream));
+    PCE_HIP(c, hipMemsetAsync(b.attn.p, 0, sizeof(op_t) * (size_t)M_max * d + 4096, c->stream));
+    PCE_HIP(c, hipMemsetAsync(b.vt.p, 0, sizeof(op_t) * vt_elems, c->stream));
+    const int *R0 = b.atab.as<int>(), *RL = R0 + wpc;
+    const op_t *Wb = b.w16.as<op_t>();
+    const float *Wf = b.w32.as<float>();
+    const float eps = m.ln_eps;
+    KernelTimer timer(c, PCE_K_W2V);
+    bool fit = true;                                             // every product's shape fits its kernel (w2v_gemm)
+    for (int64_t w0 = 0; w0 < W; w0 += wpc) {
+        const int Wc = (int)std::min<int64_t>(wpc, W - w0);
+        const int M = Wc * T_pad;
+        {   // the feature encoder
+            const WhisperState::W2v::Conv &c0 = b.conv[0];
+            const int rc = w2v_launch_wave(c, m.feat_norm, b.wintab.as<int64_t>() + 3 * w0, Wc, Wf + c0.w, c0.has_b ? Wf + c0.b : nullptr, Wf + c0.g, Wf + c0.beta,
+                                           m.conv_dim[0], m.conv_stride[0], Tl[0], b.part, b.ss, b.img[0].as<op_t>());
+            if (rc) return rc;
+            for (int i = 1; i < 7; i++) {
+                const WhisperState::W2v::Conv &cv = b.conv[i];
+                const int ci = m.conv_dim[i - 1], co = m.conv_dim[i];
+                const op_t *src = b.img[(i - 1) & 1].as<op_t>();
+                op_t *dst = b.img[i & 1].as<op_t>();
+                const int64_t rows_out = i == 6 ? T_pad : Tl[i];
+                const float *bias = cv.has_b ? Wf + cv.b : nullptr;
+                if (cv.has_ln) {
+                    fit &= w2v_gemm<EPI_BF16>(c, src, (int64_t)m.conv_stride[i] * ci, (int64_t)Tl[i - 1] * ci, Wb + cv.w, Tl[i], co, m.conv_kernel[i] * ci, bias, dst, co,
+                                       rows_out * co, Wc);
+                    w2v_launch_ln16(c, true, dst, Wf + cv.g, Wf + cv.beta, (int64_t)Wc * rows_out, co, 1e-5f, dst);
+                } else {
+                    fit &= w2v_gemm<EPI_GELU_BF16>(c, src, (int64_t)m.conv_stride[i] * ci, (int64_t)Tl[i - 1] * ci, Wb + cv.w, Tl[i], co, m.conv_kernel[i] * ci, bias, dst,
+                                            co, rows_out * co, Wc);
+                }
+            }
+        }
+        // feature projection, positional convolution
+        w2v_launch_ln16(c, false, b.img[0].as<op_t>(), Wf + b.fp_ln_w, Wf + b.fp_ln_b, M, C6, eps, b.fpln.as<op_t>());
+        fit &= w2v_gemm<EPI_F32>(c, b.fpln.as<op_t>(), C6, 0, Wb + b.proj_w, M, d, C6, Wf + b.proj_b, b.h0.as<float>(), d, 0, 1);
+        w2v_launch_posconv(c, b.h0.as<float>(), Wb + b.pos_w, Wf + b.pos_b, T, T_pad, d, m.pos_groups, Wc, b.h.as<float>());
+        float *resid = b.h.as<float>();
+        auto ln = [&](size_t w_off, size_t b_off, bool in_place) {          // ln <- LN(resid) as op_t; the post-LN stream also keeps it in fp32, in place
+            launch_layernorm<op_t>(c, resid, Wf + w_off, Wf + b_off, M, d, b.ln.as<op_t>(), eps, in_place ? resid : nullptr);
+        };
+        const bool pre = m.stable_ln != 0;
+        if (!pre) ln(b.enc_ln_w, b.enc_ln_b, true);
+        for (int l = 0; l < L; l++) {
+            const WhisperState::W2v::Layer &ly = b.layers[(size_t)l];
+            if (pre) ln(ly.ln1_w, ly.ln1_b, false);
+            fit &= w2v_gemm<EPI_QKV>(c, b.ln.as<op_t>(), d, 0, Wb + ly.qkv_w, M, 3 * d, d, Wf + ly.qkv_b, b.qk.as<op_t>(), 2 * d, 0, 1,
+                              reinterpret_cast<const float *>(b.vt.as<op_t>()), T_pad, 2 * d, vt_sp);
+            launch_attention_rows(c, Wc, H, T_pad, b.qk.as<op_t>(), 2 * d, b.qk.as<op_t>() + d, 2 * d, b.vt.as<op_t>(), vt_sp, R0, RL, R0, RL, b.attn.as<op_t>(), 0,
+                                  4.0 * Wc * (double)T * T * d);
+            fit &= w2v_gemm<EPI_RESID_F32>(c, b.attn.as<op_t>(), d, 0, Wb + ly.out_w, M, d, d, Wf + ly.out_b, resid, d, 0, 1);
+            if (pre) ln(ly.ln2_w, ly.ln2_b, false); else ln(ly.ln1_w, ly.ln1_b, true);
+            fit &= w2v_gemm<EPI_GELU_BF16>(c, b.ln.as<op_t>(), d, 0, Wb + ly.m1_w, M, I, d, Wf + ly.m1_b, b.hidden.as<op_t>(), I, 0, 1);
+            fit &= w2v_gemm<EPI_RESID_F32>(c, b.hidden.as<op_t>(), I, 0, Wb + ly.m2_w, M, d, I, Wf + ly.m2_b, resid, d, 0, 1);
+            if (!pre) ln(ly.ln2_w, ly.ln2_b, true);
+        }
+        if (pre) ln(b.enc_ln_w, b.enc_ln_b, false);
+        fit &= w2v_gemm<EPI_F32>(c, b.ln.as<op_t>(), d, 0, Wb + b.lm_w, M, Vp, d, Wf + b.lm_b, b.logits.as<float>(), Vp, 0, 1);
+        {
+            KernelTimer kt(c, PCE_K_W2V_TAIL);
+            hipLaunchKernelGGL(k_w2v_tail, dim3((unsigned)div_up(wf, 4), (unsigned)Wc), dim3(256), 0, c->stream, b.logits.as<float>(), Vp, V, plan->star ? 1 : 0,
+                               b.tailtab.as<int64_t>() + 2 * w0, T_pad, cut, b.em.as<float>(), n_cols);
+        }
+        PCE_HIP(c, hipGetLastError());
+        if (!fit) return pce_fail(c, PCE_E_LIMIT, "a product of this model has a shape the tiled GEMM kernels do not compute (N %% 128, K %% 64)");
+    }
+    b.n_clips = n;
+    return PCE_OK;
+}
+
+int pce_w2v_shape(pce_ctx *c, int32_t clip, int64_t *n_frames, int32_t *n_cols)
+{
+    if (!c || !n_frames || !n_cols) return PCE_E_INVALID;
+    WhisperState::W2v &b = ws_of(c)->w2v;
+    if (b.n_clips < 0) return pce_fail(c, PCE_E_STATE, "pce_w2v_shape before pce_w2v_run");
+    if (clip < 0 || clip >= b.n_clips) return pce_fail(c, PCE_E_INVALID, "clip out of range");
+    *n_frames = b.n_frames[(size_t)clip]; *n_cols = b.n_cols;
+    return PCE_OK;
+}
+
+int pce_w2v_fetch(pce_ctx *c, int32_t clip, float *log_probs)
+{
+    if (!c || !log_probs) return PCE_E_INVALID;
+    WhisperState::W2v &b = ws_of(c)->w2v;
+    if (b.n_clips < 0) return pce_fail(c, PCE_E_STATE, "pce_w2v_fetch before pce_w2v_run");
+    if (clip < 0 || clip >= b.n_clips) return pce_fail(c, PCE_E_INVALID, "clip out of range");
+    PCE_HIP(c, hipSetDevice(c->device));
+    PCE_HIP(c, hipMemcpyAsync(log_probs, b.em.as<float>() + b.row_start[(size_t)clip] * b.n_cols, sizeof(float) * (size_t)b.n_frames[(size_t)clip] * b.n_cols,
+                              hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    pce_profile_collect(c);
+    return PCE_OK;
+}
+
+int pce_w2v_device(pce_ctx *c, const float **d_emissions, const int64_t **h_row_start, const int32_t **h_n_frames, int32_t *n_cols)
+{
+    if (!c || !d_emissions || !h_row_start || !h_n_frames || !n_cols) return PCE_E_INVALID;
+    WhisperState::W2v &b = ws_of(c)->w2v;
+    if (b.n_clips < 0) return pce_fail(c, PCE_E_STATE, "pce_w2v_device before pce_w2v_run");
+    PCE_HIP(c, hipSetDevice(c->device));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));                  // the emissions are complete when the pointer is handed out
+    *d_emissions = b.em.as<float>(); *h_row_start = b.row_start.data(); *h_n_frames = b.n_frames.data(); *n_cols = b.n_cols;
+    return PCE_OK;
+}
+
+// ---- stage self-tests: the three new stages through the run's own launches -----------------------------------------------------------------
+int pce_selftest_w2v_wave(pce_ctx *c, const int16_t *pcm, int64_t n_samples, int32_t window_samples, int32_t context_samples, int32_t feat_norm, int32_t C,
+                          int32_t stride, const float *w, const float *bias, const float *gamma, const float *beta, uint16_t *out)
+{
+    if (!c || !pcm || !w || !gamma || !beta || !out || n_samples < 1 || window_samples < 1 || context_samples < 0 || (feat_norm != 0 && feat_norm != 1))
+        return PCE_E_INVALID;
+    if (C <= 0 || C % 64 || C > WV_C_MAX || stride < 1 || stride > WV_STRIDE_MAX)
+        return pce_fail(c, PCE_E_LIMIT, "selftest waveform layer: %d channels at stride %d (channels %% 64 == 0 and <= %d, stride <= %d)", C, stride, WV_C_MAX, WV_STRIDE_MAX);
+    PCE_HIP(c, hipSetDevice(c->device));
+    const int64_t L = (int64_t)window_samples + 2 * (int64_t)context_samples, T0 = L >= WV_K0 ? (L - WV_K0) / stride + 1 : 0;
+    int64_t n_win, keep;
+    pce_w2v_window_plan(n_samples, window_samples, context_samples, &n_win, &keep);
+    if (T0 == 0) return PCE_OK;                                                 // shorter than one tap window: no frames
+    if (T0 > INT32_MAX / 2 || n_win > 65535) return pce_fail(c, PCE_E_LIMIT, "selftest waveform layer: too many frames or windows");
+    std::vector<int64_t> tab;
+    for (int64_t j = 0; j < n_win; j++) { tab.push_back(0); tab.push_back(j * window_samples - context_samples); tab.push_back(n_samples); }
+    DevBuf dp, dt, dw, db, dg, dbe, part, ss, dout;
+    const size_t n_out = (size_t)n_win * (size_t)T0 * C;
+    PCE_HIP(c, dp.reserve(sizeof(int16_t) * (size_t)n_samples)); PCE_HIP(c, dt.reserve(sizeof(int64_t) * tab.size()));
+    PCE_HIP(c, dw.reserve(sizeof(float) * (size_t)C * WV_K0)); PCE_HIP(c, db.reserve(sizeof(float) * C)); PCE_HIP(c, dg.reserve(sizeof(float) * C));
+    PCE_HIP(c, dbe.reserve(sizeof(float) * C)); PCE_HIP(c, dout.reserve(sizeof(op_t) * n_out));
+    PCE_HIP(c, hipMemcpyAsync(dp.p, pcm, sizeof(int16_t) * (size_t)n_samples, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dt.p, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * (size_t)C * WV_K0, hipMemcpyHostToDevice, c->stream));
+    if (bias) PCE_HIP(c, hipMemcpyAsync(db.p, bias, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dg.p, gamma, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dbe.p, beta, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dout.p, 0, sizeof(op_t) * n_out, c->stream));
+    const int16_t *keep_pcm = c->d_pcm;                                          // (w2v_launch_wave reads the context's resident batch)
+    c->d_pcm = dp.as<int16_t>();
+    const int rc = w2v_launch_wave(c, feat_norm, dt.as<int64_t>(), (int)n_win, dw.as<float>(), bias ? db.as<float>() : nullptr, dg.as<float>(), dbe.as<float>(), C,
+                                   stride, (int)T0, part, ss, dout.as<op_t>());
+    c->d_pcm = keep_pcm;
+    if (rc) return rc;
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, sizeof(op_t) * n_out, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+
+int pce_selftest_w2v_lngelu(pce_ctx *c, const uint16_t *x, int32_t rows, int32_t C, const float *w, const float *b, float eps, int32_t gelu, uint16_t *out)
+{
+    if (!c || !x || !w || !b || !out || rows < 1) return PCE_E_INVALID;
+    if (C < 8 || C % 8 || C > LN_D_MAX) return pce_fail(c, PCE_E_LIMIT, "selftest LayerNorm + GELU: C = %d (need C %% 8 == 0, C <= %d)", C, LN_D_MAX);
+    PCE_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)rows * C;
+    DevBuf dx, dw, db;
+    PCE_HIP(c, dx.reserve(sizeof(op_t) * n)); PCE_HIP(c, dw.reserve(sizeof(float) * C)); PCE_HIP(c, db.reserve(sizeof(float) * C));
+    PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(op_t) * n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
+    w2v_launch_ln16(c, gelu != 0, dx.as<op_t>(), dw.as<float>(), db.as<float>(), rows, C, eps, dx.as<op_t>());      // in place, as the run launches it
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(out, dx.p, sizeof(op_t) * n, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+
+int pce_selftest_w2v_posconv(pce_ctx *c, const float *x, int32_t n_win, int32_t T, int32_t d, int32_t groups, const uint16_t *w, const float *bias, float *out)
+{
+    if (!c || !x || !w || !bias || !out || n_win < 1 || n_win > 65535 || T < 1) return PCE_E_INVALID;
+    if (!w2v_posconv_fits(d, groups) || d % 4) return pce_fail(c, PCE_E_LIMIT, "selftest positional convolution: d = %d in %d groups (16, 32, 48 or 64 columns per group)", d, groups);
+    PCE_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)n_win * T * d, nw = (size_t)d * PC_TAPS * (d / groups);
+    DevBuf dx, dw, db, dout;
+    PCE_HIP(c, dx.reserve(sizeof(float) * n)); PCE_HIP(c, dw.reserve(sizeof(op_t) * nw)); PCE_HIP(c, db.reserve(sizeof(float) * d));
+    PCE_HIP(c, dout.reserve(sizeof(float) * n));
+    PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(op_t) * nw, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(db.p, bias, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemsetAsync(dout.p, 0, sizeof(float) * n, c->stream));
+    w2v_launch_posconv(c, dx.as<float>(), dw.as<op_t>(), db.as<float>(), T, T, d, groups, n_win, dout.as<float>());
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, hipMemcpyAsync(out, dout.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+
+} // extern "C"

@@ -1,4 +1,4 @@
-// pce_whisper_dispatch.hip -- the Whisper / BERT entry points of include/pce.h: each forwards to the build of pce_whisper_impl.inc (and the .inc files it includes)
+// pce_whisper_dispatch.hip -- the Whisper / BERT / wav2vec2 entry points of include/pce.h: each forwards to the build of pce_whisper_impl.inc (and the .inc files it includes)
 // (bf16 or fp16 operands) the context has selected.  The two builds keep separate state (weights, buffers): switching the operand
 // type means loading the weights again.
 #include "pce_internal.h"
@@ -38,6 +38,15 @@ PCE_BOTH(int, pce_whisper_detect_language, (pce_ctx *, int32_t, int32_t, int32_t
 PCE_BOTH(int, pce_bert_load, (pce_ctx *, const pce_bert_dims *, const float *, int64_t))
 PCE_BOTH(int, pce_bert_run, (pce_ctx *, const int32_t *, const int32_t *, int32_t))
 PCE_BOTH(int, pce_bert_fetch, (pce_ctx *, int32_t, float *, int32_t *))
+PCE_BOTH(int, pce_w2v_check, (const pce_w2v_dims *, int64_t, char *, size_t))
+PCE_BOTH(int, pce_w2v_load, (pce_ctx *, const pce_w2v_dims *, const float *, int64_t))
+PCE_BOTH(int, pce_w2v_run, (pce_ctx *, const pce_w2v_plan *))
+PCE_BOTH(int, pce_w2v_shape, (pce_ctx *, int32_t, int64_t *, int32_t *))
+PCE_BOTH(int, pce_w2v_fetch, (pce_ctx *, int32_t, float *))
+PCE_BOTH(int, pce_w2v_device, (pce_ctx *, const float **, const int64_t **, const int32_t **, int32_t *))
+PCE_BOTH(int, pce_selftest_w2v_wave, (pce_ctx *, const int16_t *, int64_t, int32_t, int32_t, int32_t, int32_t, int32_t, const float *, const float *, const float *, const float *, uint16_t *))
+PCE_BOTH(int, pce_selftest_w2v_lngelu, (pce_ctx *, const uint16_t *, int32_t, int32_t, const float *, const float *, float, int32_t, uint16_t *))
+PCE_BOTH(int, pce_selftest_w2v_posconv, (pce_ctx *, const float *, int32_t, int32_t, int32_t, int32_t, const uint16_t *, const float *, float *))
 void pce_whisper_free_bf16(pce_ctx *c);
 void pce_whisper_free_f16(pce_ctx *c);
 
@@ -154,5 +163,38 @@ int pce_whisper_detect_language(pce_ctx *c, int32_t sot, int32_t lang_begin, int
 int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, int64_t n_floats) { return PCE_FWD(pce_bert_load, c, dims, weights, n_floats); }
 int pce_bert_run(pce_ctx *c, const int32_t *input_ids, const int32_t *offsets, int32_t n_seq) { return PCE_FWD(pce_bert_run, c, input_ids, offsets, n_seq); }
 int pce_bert_fetch(pce_ctx *c, int32_t seq, float *logits, int32_t *labels) { return PCE_FWD(pce_bert_fetch, c, seq, logits, labels); }
+// (the loader's conditions are the same in both operand builds)
+int pce_w2v_check(const pce_w2v_dims *dims, int64_t n_floats, char *msg, size_t cap) { return pce_w2v_check_f16(dims, n_floats, msg, cap); }
+int pce_w2v_load(pce_ctx *c, const pce_w2v_dims *dims, const float *weights, int64_t n_floats) { return PCE_FWD(pce_w2v_load, c, dims, weights, n_floats); }
+int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan) { return PCE_FWD(pce_w2v_run, c, plan); }
+int pce_w2v_shape(pce_ctx *c, int32_t clip, int64_t *n_frames, int32_t *n_cols) { return PCE_FWD(pce_w2v_shape, c, clip, n_frames, n_cols); }
+int pce_w2v_fetch(pce_ctx *c, int32_t clip, float *log_probs) { return PCE_FWD(pce_w2v_fetch, c, clip, log_probs); }
+int pce_w2v_device(pce_ctx *c, const float **d_emissions, const int64_t **h_row_start, const int32_t **h_n_frames, int32_t *n_cols)
+{
+    return PCE_FWD(pce_w2v_device, c, d_emissions, h_row_start, h_n_frames, n_cols);
+}
+// windows and kept frames of one clip: ctc_emissions.window_plan's arithmetic (true division and truncation in double)
+int pce_w2v_window_plan(int64_t n_samples, int32_t window_samples, int32_t context_samples, int64_t *n_windows, int64_t *n_frames)
+{
+    if (n_samples < 0 || window_samples < 1 || context_samples < 0 || !n_windows || !n_frames) return PCE_E_INVALID;
+    const int64_t window = window_samples, n_win = n_samples > window ? (n_samples + window - 1) / window : 1, extension = n_win * window - n_samples;
+    const int64_t wf = (int64_t)((double)window / 16000.0 * 50.0);
+    *n_windows = n_win;
+    *n_frames = n_win * wf - (extension > 0 ? (int64_t)((double)extension / 16000.0 * 50.0) : 0);
+    return PCE_OK;
+}
+int pce_selftest_w2v_wave(pce_ctx *c, const int16_t *pcm, int64_t n_samples, int32_t window_samples, int32_t context_samples, int32_t feat_norm, int32_t C,
+                          int32_t stride, const float *w, const float *bias, const float *gamma, const float *beta, uint16_t *out)
+{
+    return PCE_FWD(pce_selftest_w2v_wave, c, pcm, n_samples, window_samples, context_samples, feat_norm, C, stride, w, bias, gamma, beta, out);
+}
+int pce_selftest_w2v_lngelu(pce_ctx *c, const uint16_t *x, int32_t rows, int32_t C, const float *w, const float *b, float eps, int32_t gelu, uint16_t *out)
+{
+    return PCE_FWD(pce_selftest_w2v_lngelu, c, x, rows, C, w, b, eps, gelu, out);
+}
+int pce_selftest_w2v_posconv(pce_ctx *c, const float *x, int32_t n_win, int32_t T, int32_t d, int32_t groups, const uint16_t *w, const float *bias, float *out)
+{
+    return PCE_FWD(pce_selftest_w2v_posconv, c, x, n_win, T, d, groups, w, bias, out);
+}
 
 } // extern "C"

@@ -2,7 +2,7 @@
 // text decoder (teacher-forced forced alignment with cross-attention DTW; free-running greedy decoding with a K / V
 // cache and openai-whisper's logit filters), and the break-prediction BERT forward, which shares the same kernels.
 // This file: the kernels (with pce_gemm256.inc, pce_xattn.inc), WhisperState, the launchers, the log-mel and encoder entry points; it ends by
-// including the other entry points: pce_whisper_selftest.inc, pce_whisper_decoder.inc, pce_bert.inc (one translation unit per operand type).
+// including the other entry points: pce_whisper_selftest.inc, pce_whisper_decoder.inc, pce_bert.inc, pce_w2v.inc (one translation unit per operand type).
 //
 // Replaces the device work of whisper_timestamped.transcribe
 // (Code/Aligners/use_whisper_timestamped.py:139,150-163), as openai-whisper==20240930 defines it (third-party,
@@ -68,6 +68,15 @@
 #define pce_bert_load PCE_WFN(pce_bert_load)
 #define pce_bert_run PCE_WFN(pce_bert_run)
 #define pce_bert_fetch PCE_WFN(pce_bert_fetch)
+#define pce_w2v_check PCE_WFN(pce_w2v_check)
+#define pce_w2v_load PCE_WFN(pce_w2v_load)
+#define pce_w2v_run PCE_WFN(pce_w2v_run)
+#define pce_w2v_shape PCE_WFN(pce_w2v_shape)
+#define pce_w2v_fetch PCE_WFN(pce_w2v_fetch)
+#define pce_w2v_device PCE_WFN(pce_w2v_device)
+#define pce_selftest_w2v_wave PCE_WFN(pce_selftest_w2v_wave)
+#define pce_selftest_w2v_lngelu PCE_WFN(pce_selftest_w2v_lngelu)
+#define pce_selftest_w2v_posconv PCE_WFN(pce_selftest_w2v_posconv)
 #define pce_selftest_xattn PCE_WFN(pce_selftest_xattn)
 #define pce_selftest_gemm_tiled PCE_WFN(pce_selftest_gemm_tiled)
 #define pce_selftest_layernorm PCE_WFN(pce_selftest_layernorm)
@@ -2099,6 +2108,21 @@ struct WhisperState {
         int n_seq = -1, T_pad = 0;
         std::vector<int> lens;
     } bert;
+    // wav2vec2 / MMS CTC acoustic model (pce_w2v.inc): weights, the images of one chunk of windows, the packed emissions of the batch
+    struct W2v {
+        pce_w2v_dims dims{};
+        bool loaded = false;
+        DevBuf w16, w32;
+        struct Conv { size_t w = 0, b = 0, g = 0, beta = 0; bool has_b = false, has_ln = false; } conv[8];
+        struct Layer { size_t qkv_w, qkv_b, out_w, out_b, ln1_w, ln1_b, m1_w, m1_b, m2_w, m2_b, ln2_w, ln2_b; };
+        std::vector<Layer> layers;
+        size_t fp_ln_w = 0, fp_ln_b = 0, proj_w = 0, proj_b = 0, pos_w = 0, pos_b = 0, enc_ln_w = 0, enc_ln_b = 0, lm_w = 0, lm_b = 0;
+        int Vp = 0;                         // lm_head's columns, padded to whole GEMM tiles
+        DevBuf img[2], part, ss, wintab, tailtab, atab, fpln, h0, h, ln, qk, vt, attn, hidden, logits, em;
+        std::vector<int64_t> row_start;     // first row of clip q in em
+        std::vector<int32_t> n_frames;
+        int n_cols = 0, n_clips = -1;       // n_clips < 0: no run yet
+    } w2v;
     // offsets (elements) into w_bf16 / w_f32
     struct Layer { size_t ln1_w, ln1_b, qkv_w, qkv_b, out_w, out_b, ln2_w, ln2_b, m1_w, m1_b, m2_w, m2_b; };
     size_t c1_w = 0, c1_b = 0, c2_w = 0, c2_b = 0, lnp_w = 0, lnp_b = 0;
@@ -2779,3 +2803,4 @@ int pce_whisper_encode_fetch(pce_ctx *c, int32_t clip, float *out)
 #include "pce_whisper_selftest.inc"
 #include "pce_whisper_decoder.inc"
 #include "pce_bert.inc"
+#include "pce_w2v.inc"

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -104,6 +105,50 @@ class BertDims(C.Structure):
                 ("n_layer", C.c_int32), ("n_labels", C.c_int32)]
 
 
+class W2vDims(C.Structure):
+    _fields_ = [("n_conv", C.c_int32), ("conv_dim", C.c_int32 * 8), ("conv_kernel", C.c_int32 * 8), ("conv_stride", C.c_int32 * 8),
+                ("feat_norm", C.c_int32), ("conv_bias", C.c_int32), ("n_state", C.c_int32), ("n_head", C.c_int32), ("n_inter", C.c_int32),
+                ("n_layer", C.c_int32), ("stable_ln", C.c_int32), ("pos_taps", C.c_int32), ("pos_groups", C.c_int32), ("n_vocab", C.c_int32),
+                ("ln_eps", C.c_float)]
+
+    @classmethod
+    def of(cls, dims: dict):
+        """``w2v_weights.dims(config)`` -> the struct (at most eight feature-encoder layers fit; the loader takes seven)."""
+        if not 1 <= len(dims["conv_dim"]) <= 8 or not len(dims["conv_dim"]) == len(dims["conv_kernel"]) == len(dims["conv_stride"]) == dims["n_conv"]:
+            raise ValueError("conv_dim / conv_kernel / conv_stride: n_conv entries each, at most eight")
+        pad = lambda v: (C.c_int32 * 8)(*(list(v) + [0] * (8 - len(v))))
+        return cls(dims["n_conv"], pad(dims["conv_dim"]), pad(dims["conv_kernel"]), pad(dims["conv_stride"]), dims["feat_norm"], dims["conv_bias"],
+                   dims["n_state"], dims["n_head"], dims["n_inter"], dims["n_layer"], dims["stable_ln"], dims["pos_taps"], dims["pos_groups"],
+                   dims["n_vocab"], dims["ln_eps"])
+
+
+class W2vPlan(C.Structure):
+    _fields_ = [("window_samples", C.c_int32), ("context_samples", C.c_int32), ("windows_per_chunk", C.c_int32), ("star", C.c_int32)]
+
+
+class DeviceEmissions:
+    """The packed emissions of ``ProsodyEngine.w2v_emissions``: device memory ``[sum n_frames][n_cols]`` float32 of the engine that made them
+    (valid until its next ``w2v_emissions`` / ``w2v_load``, which may free or overwrite the memory), clip ``q`` in rows
+    ``row_start[q] .. row_start[q] + n_frames[q]``.  ``ProsodyEngine.ctc_align`` reads it in place.  ``epoch`` is the engine's count of
+    ``w2v_load`` / ``w2v_emissions`` calls when it was made: an object from before the engine's latest call is refused (``check``), not read."""
+
+    def __init__(self, engine, pointer: int, row_start: np.ndarray, n_frames: np.ndarray, n_cols: int, epoch: int):
+        self.engine, self.pointer, self.row_start, self.n_frames, self.n_cols = engine, int(pointer), row_start, n_frames, int(n_cols)
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.n_frames)
+
+    def check(self):
+        if self.epoch != self.engine._w2v_epoch:
+            raise ValueError("these emissions are stale: the engine has run w2v_emissions / w2v_load since they were made")
+
+    def numpy(self):
+        """-> one float32 array ``[n_frames][n_cols]`` per clip (fetched to the host)."""
+        self.check()
+        return [self.engine.w2v_fetch(q) for q in range(len(self.n_frames))]
+
+
 class CtcParams(C.Structure):
     _fields_ = [("blank", C.c_int32), ("form", C.c_int32), ("reserved", C.c_int32 * 2)]
 
@@ -143,6 +188,7 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace",
               "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges",
               "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
+              "w2v_forward", "k_w2v_wave", "k_w2v_posconv", "k_w2v_tail",
               "k_ctc", "k_ctc_general", "k_ctc_trace", "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
 # every symbol include/pce.h declares
@@ -159,6 +205,8 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_dtw", "pce_dtw_series", "pce_ctc_align", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
            "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_selftest_align_matrix", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
+           "pce_w2v_check", "pce_w2v_load", "pce_w2v_run", "pce_w2v_shape", "pce_w2v_fetch", "pce_w2v_device", "pce_w2v_window_plan",
+           "pce_selftest_w2v_wave", "pce_selftest_w2v_lngelu", "pce_selftest_w2v_posconv",
            "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
 
 
@@ -237,6 +285,16 @@ def load_library() -> C.CDLL:
     lib.pce_bert_load.argtypes = [vp, C.POINTER(BertDims), vp, i64]
     lib.pce_bert_run.argtypes = [vp, vp, vp, i32]
     lib.pce_bert_fetch.argtypes = [vp, i32, vp, vp]
+    lib.pce_w2v_check.argtypes = [C.POINTER(W2vDims), i64, C.c_char_p, C.c_size_t]
+    lib.pce_w2v_load.argtypes = [vp, C.POINTER(W2vDims), vp, i64]
+    lib.pce_w2v_run.argtypes = [vp, C.POINTER(W2vPlan)]
+    lib.pce_w2v_shape.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i32)]
+    lib.pce_w2v_fetch.argtypes = [vp, i32, vp]
+    lib.pce_w2v_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
+    lib.pce_w2v_window_plan.argtypes = [i64, i32, i32, C.POINTER(i64), C.POINTER(i64)]
+    lib.pce_selftest_w2v_wave.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.pce_selftest_w2v_lngelu.argtypes = [vp, vp, i32, i32, vp, vp, C.c_float, i32, vp]
+    lib.pce_selftest_w2v_posconv.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.pce_logmel_run.argtypes = [vp, i32]
     lib.pce_logmel_run_at.argtypes = [vp, i32, vp]
     lib.pce_logmel_fetch.argtypes = [vp, i32, vp]
@@ -264,6 +322,24 @@ def load_library() -> C.CDLL:
     return lib
 
 
+def w2v_check(dims: dict, n_floats: int, lib=None):
+    """-> (status, message) ``pce_w2v_load`` would give for these dims (``w2v_weights.dims``) and a blob of ``n_floats``: ``pce_w2v_check``, no device."""
+    lib = lib or load_library()
+    msg = C.create_string_buffer(320)
+    rc = lib.pce_w2v_check(C.byref(W2vDims.of(dims)), int(n_floats), msg, len(msg))
+    return rc, msg.value.decode(errors="replace")
+
+
+def w2v_window_plan(n_samples: int, window_s=30, context_s=2, lib=None):
+    """-> (windows, frames kept) of one 16 kHz clip as ``pce_w2v_run`` counts them: ``pce_w2v_window_plan``, host arithmetic that needs no device."""
+    lib = lib or load_library()
+    nw, nf = C.c_int64(), C.c_int64()
+    rc = lib.pce_w2v_window_plan(int(n_samples), int(window_s * 16000), int(context_s * 16000), C.byref(nw), C.byref(nf))
+    if rc:
+        raise PceError(f"pce_w2v_window_plan: status {rc}")
+    return nw.value, nf.value
+
+
 def make_slices(clips, begins, ends, x1=None) -> np.ndarray:
     """Pack parallel arrays into the ``pce_slice`` layout."""
     n = len(clips)
@@ -288,6 +364,8 @@ class ProsodyEngine:
         self.rate = 0
         self.clip_lengths = np.zeros(0, dtype=np.int64)
         self._keep = []
+        self._w2v_epoch = 0                  # w2v_load / w2v_emissions calls so far (DeviceEmissions.check)
+        self._w2v_held = None                # (weak reference to the model object of the latest w2v_load, operand mode)
 
     # ---------------------------------------------------------------- plumbing
     def close(self):
@@ -900,7 +978,8 @@ class ProsodyEngine:
     def ctc_align(self, emissions, targets, blank=0, n_frames=None, form="auto", return_path=True):
         """CTC forced alignment of a batch of clips (``pce_ctc_align``: the Viterbi pass of ``torchaudio.functional.forced_align`` over the
         ``2 L + 1`` blank-interleaved states of each transcript, bit-identical to its CPU restatement).  ``emissions``: a list of
-        ``[T_c, V]`` float32 arrays of log-probabilities (packed and uploaded by the call), or ONE float32 contiguous torch tensor
+        ``[T_c, V]`` float32 arrays of log-probabilities (packed and uploaded by the call), a ``DeviceEmissions`` of this engine's
+        ``w2v_emissions`` (read in place), or ONE float32 contiguous torch tensor
         ``[B, T_max, V]`` with ``n_frames`` (valid frames per clip; default ``T_max`` for all): a ROCm tensor is read in place through its
         pointer, a CPU tensor is handed over as host memory (a process that uses ROCm tensors imports torch BEFORE it creates its first engine:
         torch ships its own copy of the HIP runtime, and the copy loaded first serves both).  ``targets``: one sequence of vocabulary indices per clip (none may be ``blank``).
@@ -914,7 +993,16 @@ class ProsodyEngine:
             raise ValueError(f"form: one of {sorted(CTC_FORMS)}")
         tg = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in targets]
         keep = None
-        if isinstance(emissions, (list, tuple)):
+        if isinstance(emissions, DeviceEmissions):
+            if n_frames is not None:
+                raise ValueError("n_frames goes with a tensor of emissions; DeviceEmissions carries its own lengths")
+            if emissions.engine is not self:
+                raise ValueError("these emissions live in another engine's memory")
+            emissions.check()
+            n, V = len(emissions), emissions.n_cols
+            nfr = np.ascontiguousarray(emissions.n_frames, dtype=np.int32); row_start = np.ascontiguousarray(emissions.row_start, dtype=np.int64)
+            ptr, on_device = emissions.pointer, 1
+        elif isinstance(emissions, (list, tuple)):
             if n_frames is not None:
                 raise ValueError("n_frames goes with a tensor of emissions; a list carries its own lengths")
             rows = [np.ascontiguousarray(e, dtype=np.float32) for e in emissions]
@@ -1148,6 +1236,96 @@ class ProsodyEngine:
     def bert_token_classify(self, token_lists):
         self.bert_run(token_lists)
         return [self.bert_fetch(i) for i in range(len(token_lists))]
+
+    # ---------------------------------------------------------------- wav2vec2 / MMS CTC acoustic model
+    def w2v_load(self, model_or_config, weights=None):
+        """Load a ``transformers`` ``Wav2Vec2ForCTC``: the model itself (its config and ``state_dict`` are packed here), or a config / a dims dict
+        of ``w2v_weights.dims`` with ``weights`` = a ``state_dict`` or the flat float32 blob of ``w2v_weights.tensor_order``."""
+        from . import w2v_weights as WW
+        src = model_or_config
+        if weights is None:
+            if not hasattr(src, "state_dict"):
+                raise ValueError("w2v_load: a model, or a config / dims with weights")
+            weights, src = src.state_dict(), src.config
+        model = model_or_config if src is not model_or_config else None
+        dims = src if isinstance(src, dict) else WW.dims(src)
+        w = WW.pack(weights, dims) if hasattr(weights, "keys") else np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        self._w2v_dims = W2vDims.of(dims)
+        self._w2v_epoch += 1                                        # DeviceEmissions made before this call are stale
+        self._w2v_held = None
+        self._check(self._lib.pce_w2v_load(self._ctx, C.byref(self._w2v_dims), w.ctypes.data, w.size))
+        if model is not None:      # which model object the selected operand build now holds (a weak reference: the engine does not keep it alive)
+            self._w2v_held = (weakref.ref(model), self._lib.pce_whisper_get_operands(self._ctx))
+
+    def w2v_holds(self, model) -> bool:
+        """Did this engine's latest ``w2v_load`` load ``model`` (the same object; weights changed in place since are not seen) into the operand
+        build now selected?  What ``ctc_emissions.engine_emissions`` asks before it loads."""
+        held = self._w2v_held
+        return held is not None and held[0]() is model and held[1] == self._lib.pce_whisper_get_operands(self._ctx)
+
+    def w2v_emissions(self, window_s=30, context_s=2, windows_per_chunk=None, star=True) -> DeviceEmissions:
+        """Frame-wise log-probabilities of the resident 16 kHz batch under the loaded model (``pce_w2v_run``), windowed as
+        ``Aligners.ctc_emissions.hf_emissions`` windows them; ``star`` appends the zero ``<star>`` column.  ``windows_per_chunk``: windows per
+        launch group (default: by ``PCE_W2V_IMAGE_BUDGET``); a window's emissions do not depend on it.  -> ``DeviceEmissions``."""
+        window, context = int(window_s * 16000), int(context_s * 16000)
+        if int(window / 16000 * 50) != int(window_s * 50) or int(context / 16000 * 50) != int(context_s * 50):
+            raise ValueError("window_s / context_s: the whole samples they span must keep their frame counts (int(s * 50))")
+        plan = W2vPlan(window, context, int(windows_per_chunk or 0), 1 if star else 0)
+        self._w2v_epoch += 1                                        # the run may move or overwrite what earlier DeviceEmissions point to
+        self._check(self._lib.pce_w2v_run(self._ctx, C.byref(plan)))
+        ptr, rs, nf, nc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        self._check(self._lib.pce_w2v_device(self._ctx, C.byref(ptr), C.byref(rs), C.byref(nf), C.byref(nc)))
+        n = int(self._lib.pce_num_clips(self._ctx))
+        row_start = np.ctypeslib.as_array(C.cast(rs, C.POINTER(C.c_int64)), shape=(n,)).copy() if n else np.zeros(0, np.int64)
+        n_frames = np.ctypeslib.as_array(C.cast(nf, C.POINTER(C.c_int32)), shape=(n,)).copy() if n else np.zeros(0, np.int32)
+        return DeviceEmissions(self, ptr.value or 0, row_start, n_frames, nc.value, self._w2v_epoch)
+
+    def w2v_fetch(self, clip: int) -> np.ndarray:
+        """-> float32 ``[n_frames][n_cols]``: one clip's emissions of the last ``w2v_emissions``."""
+        nf, nc = C.c_int64(), C.c_int32()
+        self._check(self._lib.pce_w2v_shape(self._ctx, int(clip), C.byref(nf), C.byref(nc)))
+        out = np.zeros((nf.value, nc.value), dtype=np.float32)
+        if out.size:
+            self._check(self._lib.pce_w2v_fetch(self._ctx, int(clip), out.ctypes.data))
+        return out
+
+    def w2v_window_plan(self, n_samples: int, window_s=30, context_s=2):
+        """-> (windows, frames kept) of one clip, as ``pce_w2v_run`` counts them (host arithmetic: ``pce_w2v_window_plan``)."""
+        return w2v_window_plan(n_samples, window_s, context_s, self._lib)
+
+    def selftest_w2v_wave(self, pcm, window: int, context: int, feat_norm: int, w, gamma, beta, bias=None, stride: int = 5):
+        """``pce_selftest_w2v_wave``: the waveform layer over the windows of one int16 clip.  w [C][10] float32.  -> uint16 bits [windows][T0][C]."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+        w = np.ascontiguousarray(w, dtype=np.float32); gamma = np.ascontiguousarray(gamma, dtype=np.float32); beta = np.ascontiguousarray(beta, dtype=np.float32)
+        bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        ch = w.shape[0]
+        length = window + 2 * context
+        t0 = (length - 10) // stride + 1 if length >= 10 else 0
+        n_win = max(1, -(-len(pcm) // window))
+        out = np.zeros((n_win, t0, ch), dtype=np.uint16)
+        self._check(self._lib.pce_selftest_w2v_wave(self._ctx, pcm.ctypes.data, len(pcm), int(window), int(context), int(feat_norm), ch, int(stride),
+                                                    w.ctypes.data, None if bias is None else bias.ctypes.data, gamma.ctypes.data, beta.ctypes.data,
+                                                    out.ctypes.data))
+        return out
+
+    def selftest_w2v_lngelu(self, x_bits, w, b, eps: float = 1e-5, gelu: bool = True):
+        """``pce_selftest_w2v_lngelu``: x uint16 bits [rows][C] -> uint16 bits [rows][C]."""
+        x = np.ascontiguousarray(x_bits, dtype=np.uint16)
+        w = np.ascontiguousarray(w, dtype=np.float32); b = np.ascontiguousarray(b, dtype=np.float32)
+        out = np.zeros_like(x)
+        self._check(self._lib.pce_selftest_w2v_lngelu(self._ctx, x.ctypes.data, x.shape[0], x.shape[1], w.ctypes.data, b.ctypes.data, float(eps),
+                                                      1 if gelu else 0, out.ctypes.data))
+        return out
+
+    def selftest_w2v_posconv(self, x, w_bits, bias, groups: int):
+        """``pce_selftest_w2v_posconv``: x float32 [windows][T][d], w uint16 bits [d][128][d / groups] -> float32 [windows][T][d]."""
+        x = np.ascontiguousarray(x, dtype=np.float32); w = np.ascontiguousarray(w_bits, dtype=np.uint16); bias = np.ascontiguousarray(bias, dtype=np.float32)
+        n_win, t, d = x.shape
+        if w.shape != (d, 128, d // groups):
+            raise ValueError("w: [d][128][d / groups]")
+        out = np.zeros_like(x)
+        self._check(self._lib.pce_selftest_w2v_posconv(self._ctx, x.ctypes.data, n_win, t, d, int(groups), w.ctypes.data, bias.ctypes.data, out.ctypes.data))
+        return out
 
     def levenshtein(self, pairs):
         """Levenshtein distances of a batch of string pairs in one launch (``pce_levenshtein``): ``pairs`` = [(s1, s2), ...] of ``str``
