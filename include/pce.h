@@ -67,9 +67,11 @@ extern "C" {
  * front of PCE_K_SEQMATCH as minor 13's do: the numeric values of PCE_K_SEQMATCH / PCE_K_SEQMATCH_ALIGN moved by three (pce_kernel_name follows);
  * 16 = pce_w2v_check / _load / _run / _shape / _fetch / _device, pce_w2v_window_plan and pce_selftest_w2v_wave / _lngelu / _posconv (the wav2vec2 / MMS CTC
  * forward pass of the resident batch: the emissions pce_ctc_align reads in place) and their four kernel ids, which sit behind minor 13's and in
- * front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by four (pce_kernel_name follows). */
+ * front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by four (pce_kernel_name follows);
+ * 17 = pce_selftest_decode_rules (the kernels that turn a decoding step's logits into tokens and carry them into the loop's tables, on host arrays
+ * through the decoding calls' own launches). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 16
+#define PCE_API_MINOR 17
 
 typedef struct pce_ctx pce_ctx;
 
@@ -546,6 +548,32 @@ int pce_whisper_decode_step_ex(pce_ctx *ctx, const int32_t *tokens, const int32_
  * transcribe() passes a hash of the clip's samples and its window start); they hold for the batch now encoded -- the next
  * pce_whisper_encode_run drops them -- and n must be that batch's clip count (n = 0: drop them now).  PCE_E_STATE before an encoder run. */
 int pce_whisper_sample_keys(pce_ctx *ctx, const int32_t *keys /* [n] */, int32_t n);
+
+/* Self-test of the kernels that turn a decoding step's logits into tokens (k_decode_rules: vocabulary mask, blank and timestamp rules, the
+ * timestamp-mass rule, first arg-max or Gumbel sampling, log-probability, probe) and carry them into the device-resident loop's tables
+ * (k_step_advance), on host arrays through the launches pce_whisper_decode_step_ex and pce_whisper_decode_loop make; no model need be loaded.
+ * logits [steps][n][ld] fp32, ld = n_vocab rounded up to 128 (the padding columns travel as given); tokens / token_offsets [n + 1]: the sequences so
+ * far; sample_begin [n], or NULL: sample_begin_all for all; rules, vocab_mask [n_vocab], temperature, seed, probe_token (< 0: none) and
+ * sample_keys [n] (or NULL: the batch position) as in pce_whisper_decode_step_ex / pce_whisper_sample_keys.  t_cap (1..448): the text context.
+ *   form 0: one step (steps == 1) as pce_whisper_decode_step_ex launches it: the sequences as rows of T_pad ids (the longest rounded up to 16), entries
+ *           past a sequence's length = pad_token.  out_tok / out_lp / probe_prob [out_elems >= n]: next token, its log-probability, the probe.
+ *   form 1: the loop as pce_whisper_decode_loop runs it, probe-less: table [n][t_cap] receives the sequences (entries past their lengths keep the
+ *           caller's values); for s = 0 .. steps - 1 (steps <= max_new) the rules on logits[s], then k_step_advance.  out_tok / out_lp [n][max_new];
+ *           table: the final one; loop_state: len [n] | ended [n] | ct [8 n] (new token | . | . | . | key count | . | . | position) |
+ *           n_ended [max_new] | step counter -- len, n_ended and the counter are initialised here (the lengths; zero), ended and ct start
+ *           from the caller's values.
+ * Every output is read and written back whole: what no launch writes keeps the caller's values.  The log-probability is the filtered, unscaled
+ * log-softmax at the choice, computed as -log(sum exp(x - x[choice])): it is -inf when a sampled choice lies more than about 88 below the maximum.
+ * PCE_E_INVALID, before anything is launched, for what the decoding calls refuse (eot / timestamp_begin order, temperature < 0,
+ * probe_token >= n_vocab, n_vocab > 52224, a token outside the vocabulary), a sequence longer than t_cap, sample_begin outside 1 .. its length,
+ * steps != 1 in form 0 or > max_new in form 1, and arrays (logits_elems, mask_elems, out_elems, table_elems, state_elems: their lengths in
+ * elements) shorter than the shape needs.  Since minor 17. */
+int pce_selftest_decode_rules(pce_ctx *ctx, int32_t form, int32_t n, int32_t n_vocab, int32_t steps, const float *logits, int64_t logits_elems,
+                              const int32_t *tokens, const int32_t *token_offsets, int32_t pad_token, int32_t t_cap, const int32_t *sample_begin,
+                              int32_t sample_begin_all, const pce_whisper_decode_rules *rules, const uint8_t *vocab_mask, int64_t mask_elems,
+                              float temperature, uint32_t seed_lo, uint32_t seed_hi, int32_t probe_token, const int32_t *sample_keys, int32_t max_new,
+                              int32_t *out_tok, float *out_lp, float *probe_prob, int64_t out_elems, int32_t *table, int64_t table_elems,
+                              int32_t *loop_state, int64_t state_elems);
 
 /* Operand type of every Whisper / BERT matrix product (round 3).  Default since round 4: PCE_OPERANDS_F16_RESID16 (below; PCE_WHISPER_OPERANDS=fp16
  * or bf16 in the environment at pce_create selects another default).  PCE_OPERANDS_FP16: fp16 operands, the reference's own

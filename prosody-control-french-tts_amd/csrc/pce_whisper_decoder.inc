@@ -629,6 +629,23 @@ static int decode_prompts_to_lastln(pce_ctx *c, WhisperState *w, const int32_t *
     return PCE_OK;
 }
 
+// ---- From a step's logits to its tokens: the two launches decode_step_device, pce_whisper_decode_loop and pce_selftest_decode_rules (their test hook,
+// pce_whisper_selftest.inc) make.  launch_decode_rules: one workgroup per sequence over logits [n][R.ld]; `tokens` holds one row of `pitch` ids per sequence
+// (T_pad of a step's padded prompts, T_cap of the loop's table).  launch_step_advance: ONE workgroup carries the choices into the loop's tables.
+// the loop's device-resident state: table [n][T_cap], len / ended [n], out_tok / out_lp [n][max_new], the step counter, n_ended [max_new]
+struct DecodeLoopState { int *tok_table, *len, *ended, *out_tok; float *out_lp; int *ctr, *n_ended; };
+static void launch_decode_rules(pce_ctx *c, int n, const float *logits, const int *tokens, const int *t_len, int pitch, const unsigned char *vmask, const DecRules &R,
+                                const int *sample_begin_of, int *next, float *next_logprob, float *probe_prob, const int *sample_key)
+{
+    hipLaunchKernelGGL(k_decode_rules, dim3((unsigned)n), dim3(DR_T), 0, c->stream, logits, tokens, t_len, pitch, vmask, R, sample_begin_of, next, next_logprob,
+                       probe_prob, sample_key);
+}
+static void launch_step_advance(pce_ctx *c, const DecodeLoopState &s, int n, int T_cap, int eot, int max_new, const int *next, const float *next_lp, int *ct)
+{
+    hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(256), 0, c->stream, n, T_cap, eot, max_new, s.tok_table, s.len, next, next_lp, ct, s.ended, s.out_tok, s.out_lp,
+                       s.ctr, s.n_ended);
+}
+
 static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
                               const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, bool want_probe)
 {
@@ -657,9 +674,9 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
     launch_gemm<EPI_F32>(c, w->g_lastln.as<op_t>(), d, 0, w->g_emb_bf16.as<op_t>(), n, (int)Vp, d, nullptr, w->g_logits.as<float>(), Vp, 0, 1);
     DecRules R{rules->eot, rules->timestamp_begin, V, (int)Vp, sample_begin, rules->max_initial_timestamp_index, opts->temperature, opts->seed_lo,
                opts->seed_hi, probe_prob ? opts->probe_token : -1};
-    hipLaunchKernelGGL(k_decode_rules, dim3((unsigned)n), dim3(DR_T), 0, c->stream, w->g_logits.as<float>(), w->d_tokens.as<int>(), TL, rows.T_pad,
-                       w->g_mask.as<unsigned char>(), R, T0 + 4 * n, w->g_next.as<int>(), reinterpret_cast<float *>(w->g_next.as<int>() + n),
-                       reinterpret_cast<float *>(w->g_next.as<int>() + 2 * n), w->g_keys_n == n ? w->g_keys.as<int>() : nullptr);
+    launch_decode_rules(c, n, w->g_logits.as<float>(), w->d_tokens.as<int>(), TL, rows.T_pad, w->g_mask.as<unsigned char>(), R, T0 + 4 * n, w->g_next.as<int>(),
+                        reinterpret_cast<float *>(w->g_next.as<int>() + n), reinterpret_cast<float *>(w->g_next.as<int>() + 2 * n),
+                        w->g_keys_n == n ? w->g_keys.as<int>() : nullptr);
     PCE_HIP(c, hipGetLastError());
     return PCE_OK;
 }
@@ -760,10 +777,8 @@ extern "C" int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const 
     int *CT = w->g_c_tab.as<int>();
     const int *next = w->g_next.as<int>();
     const float *next_lp = reinterpret_cast<const float *>(w->g_next.as<int>() + n);
-    auto advance = [&]() {
-        hipLaunchKernelGGL(k_step_advance, dim3(1), dim3(256), 0, c->stream, n, T_cap, (int)rules->eot, (int)max_new, tok_table, len, next, next_lp, CT, ended,
-                           out_tok, out_lp, ctr, n_ended);
-    };
+    const DecodeLoopState state{tok_table, len, ended, out_tok, out_lp, ctr, n_ended};
+    auto advance = [&]() { launch_step_advance(c, state, n, T_cap, (int)rules->eot, (int)max_new, next, next_lp, CT); };
     auto all_ended = [&](int step, bool *yes) -> int {
         int cnt = 0;
         PCE_HIP(c, hipMemcpyAsync(&cnt, n_ended + step, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -780,9 +795,8 @@ extern "C" int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const 
     while (!stop && steps < max_new) {
         decode_incremental_launches(c, w, n, CT, ended);
         launch_gemm<EPI_F32>(c, w->g_lastln.as<op_t>(), d, 0, w->g_emb_bf16.as<op_t>(), n, (int)Vp, d, nullptr, w->g_logits.as<float>(), Vp, 0, 1);
-        hipLaunchKernelGGL(k_decode_rules, dim3((unsigned)n), dim3(DR_T), 0, c->stream, w->g_logits.as<float>(), tok_table, len, T_cap,
-                           w->g_mask.as<unsigned char>(), R, sb, w->g_next.as<int>(), reinterpret_cast<float *>(w->g_next.as<int>() + n),
-                           static_cast<float *>(nullptr), w->g_keys_n == n ? w->g_keys.as<int>() : nullptr);
+        launch_decode_rules(c, n, w->g_logits.as<float>(), tok_table, len, T_cap, w->g_mask.as<unsigned char>(), R, sb, w->g_next.as<int>(),
+                            reinterpret_cast<float *>(w->g_next.as<int>() + n), nullptr, w->g_keys_n == n ? w->g_keys.as<int>() : nullptr);
         advance();
         steps++;
         if (steps % check_every == 0 && steps < max_new) { const int rc = all_ended(steps - 1, &stop); if (rc) return rc; }

@@ -17,6 +17,9 @@ PCE_BOTH(int, pce_selftest_attention_ragged, (pce_ctx *, const uint16_t *, const
 PCE_BOTH(int, pce_selftest_attn1, (pce_ctx *, int32_t, int32_t, int32_t, const uint16_t *, int64_t, uint16_t *, int64_t, uint16_t *, int64_t, const int32_t *, const int32_t *, const int32_t *, int32_t, uint16_t *, int64_t))
 PCE_BOTH(int, pce_selftest_align_matrix, (pce_ctx *, int32_t, int32_t, const uint16_t *, int64_t, const uint16_t *, int64_t, int32_t, const int32_t *, const int32_t *,
                                            const int32_t *, int32_t, int32_t, int32_t, int32_t, float, float *, int64_t, float *, int64_t, double *, int64_t))
+PCE_BOTH(int, pce_selftest_decode_rules, (pce_ctx *, int32_t, int32_t, int32_t, int32_t, const float *, int64_t, const int32_t *, const int32_t *, int32_t, int32_t, const int32_t *,
+                                           int32_t, const pce_whisper_decode_rules *, const uint8_t *, int64_t, float, uint32_t, uint32_t, int32_t, const int32_t *, int32_t,
+                                           int32_t *, float *, float *, int64_t, int32_t *, int64_t, int32_t *, int64_t))
 PCE_BOTH(int, pce_selftest_gemm, (pce_ctx *, const uint16_t *, const uint16_t *, const float *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
 PCE_BOTH(int, pce_selftest_gemm_resid, (pce_ctx *, const uint16_t *, const uint16_t *, const float *, uint16_t *, int32_t, int32_t, int32_t))
 PCE_BOTH(int, pce_selftest_xattn, (pce_ctx *, const float *, const float *, const float *, const uint16_t *, const float *, const uint16_t *, const uint16_t *, const float *, const uint16_t *, const int32_t *, int32_t, int32_t, int32_t, int32_t, int32_t, uint16_t *))
@@ -93,6 +96,16 @@ int pce_selftest_align_matrix(pce_ctx *c, int32_t n, int32_t heads, const uint16
 {
     return PCE_FWD(pce_selftest_align_matrix, c, n, heads, q, q_elems, k, k_elems, k_rows, t_len, f_len, heads_sel, n_sel, split, sot_len, medfilt_width, qk_scale,
                    w_soft, w_soft_elems, w_norm, w_norm_elems, cost, cost_elems);
+}
+int pce_selftest_decode_rules(pce_ctx *c, int32_t form, int32_t n, int32_t n_vocab, int32_t steps, const float *logits, int64_t logits_elems, const int32_t *tokens,
+                              const int32_t *token_offsets, int32_t pad_token, int32_t t_cap, const int32_t *sample_begin, int32_t sample_begin_all,
+                              const pce_whisper_decode_rules *rules, const uint8_t *vocab_mask, int64_t mask_elems, float temperature, uint32_t seed_lo,
+                              uint32_t seed_hi, int32_t probe_token, const int32_t *sample_keys, int32_t max_new, int32_t *out_tok, float *out_lp,
+                              float *probe_prob, int64_t out_elems, int32_t *table, int64_t table_elems, int32_t *loop_state, int64_t state_elems)
+{
+    return PCE_FWD(pce_selftest_decode_rules, c, form, n, n_vocab, steps, logits, logits_elems, tokens, token_offsets, pad_token, t_cap, sample_begin, sample_begin_all,
+                   rules, vocab_mask, mask_elems, temperature, seed_lo, seed_hi, probe_token, sample_keys, max_new, out_tok, out_lp, probe_prob, out_elems, table,
+                   table_elems, loop_state, state_elems);
 }
 int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const float *bias, int32_t M, int32_t N, int32_t K, int32_t epilogue, int32_t rows_per_clip,
                       int32_t vt_sp, uint16_t *out)

@@ -52,6 +52,7 @@
 #define pce_selftest_attention_ragged PCE_WFN(pce_selftest_attention_ragged)
 #define pce_selftest_attn1 PCE_WFN(pce_selftest_attn1)
 #define pce_selftest_align_matrix PCE_WFN(pce_selftest_align_matrix)
+#define pce_selftest_decode_rules PCE_WFN(pce_selftest_decode_rules)
 #define pce_selftest_gemm PCE_WFN(pce_selftest_gemm)
 #define pce_selftest_gemm_resid PCE_WFN(pce_selftest_gemm_resid)
 #define pce_whisper_decoder_load PCE_WFN(pce_whisper_decoder_load)
@@ -2800,7 +2801,7 @@ int pce_whisper_encode_fetch(pce_ctx *c, int32_t clip, float *out)
 
 } // extern "C"
 
-#include "pce_whisper_selftest.inc"
 #include "pce_whisper_decoder.inc"
+#include "pce_whisper_selftest.inc"      // (after the decoder: pce_selftest_decode_rules shares its launch helpers)
 #include "pce_bert.inc"
 #include "pce_w2v.inc"

@@ -229,6 +229,105 @@ int pce_selftest_align_matrix(pce_ctx *c, int32_t n, int32_t heads, const uint16
     return PCE_OK;
 }
 
+// Self-test hook of the kernels that turn a decoding step's logits into tokens (k_decode_rules, k_step_advance) on host arrays, through launch_decode_rules /
+// launch_step_advance, which decode_step_device and pce_whisper_decode_loop make their launches with: no model is loaded.  form 0: ONE launch over the prompts
+// padded to T_pad, as decode_step_device; form 1: `steps` times the rules at the table's pitch t_cap, then k_step_advance, as the loop.  The log-probability is
+// -log(sum exp(x - x[choice])) over what the filters leave: a sampled choice more than about 88 below the maximum overflows the sum and reads -inf.
+// See include/pce.h.
+int pce_selftest_decode_rules(pce_ctx *c, int32_t form, int32_t n, int32_t n_vocab, int32_t steps, const float *logits, int64_t logits_elems, const int32_t *tokens,
+                              const int32_t *token_offsets, int32_t pad_token, int32_t t_cap, const int32_t *sample_begin, int32_t sample_begin_all,
+                              const pce_whisper_decode_rules *rules, const uint8_t *vocab_mask, int64_t mask_elems, float temperature, uint32_t seed_lo,
+                              uint32_t seed_hi, int32_t probe_token, const int32_t *sample_keys, int32_t max_new, int32_t *out_tok, float *out_lp,
+                              float *probe_prob, int64_t out_elems, int32_t *table, int64_t table_elems, int32_t *loop_state, int64_t state_elems)
+{
+    if (!c) return PCE_E_INVALID;
+    if (form < 0 || form > 1 || !logits || !tokens || !token_offsets || !rules || !vocab_mask || !out_tok || !out_lp || n < 1 || n > 65535 || steps < 1)
+        return pce_fail(c, PCE_E_INVALID, "selftest decode rules: form 0 or 1, 1 <= n <= 65535, steps >= 1, and logits, tokens, token_offsets, rules, vocab_mask, out_tok, out_lp given");
+    if (form == 0 && (!probe_prob || steps != 1)) return pce_fail(c, PCE_E_INVALID, "selftest decode rules: form 0 is one step with probe_prob");
+    if (form == 1 && (!table || !loop_state || max_new < 1 || steps > max_new))
+        return pce_fail(c, PCE_E_INVALID, "selftest decode rules: form 1 needs table, loop_state and 1 <= steps <= max_new");
+    const int V = n_vocab;
+    if (V < 1 || V > DR_K * DR_T) return pce_fail(c, PCE_E_INVALID, "selftest decode rules: n_vocab %d (1..%d)", V, DR_K * DR_T);
+    if (rules->eot < 0 || rules->eot >= V || rules->timestamp_begin <= rules->eot || rules->timestamp_begin > V)
+        return pce_fail(c, PCE_E_INVALID, "decoding rules: need 0 <= eot < timestamp_begin <= n_vocab, sample_begin >= 1");
+    if (!(temperature >= 0.f) || probe_token >= V) return pce_fail(c, PCE_E_INVALID, "decoding options: temperature >= 0, probe_token < n_vocab");
+    if (t_cap < 1 || t_cap > 448) return pce_fail(c, PCE_E_INVALID, "selftest decode rules: t_cap %d (1..448)", t_cap);
+    const int64_t ld = div_up(V, 128) * 128;
+    int T_max = 0;
+    std::vector<int> h_len((size_t)n), h_sb((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int T = token_offsets[i + 1] - token_offsets[i], sb = sample_begin ? sample_begin[i] : sample_begin_all;
+        if (sb < 1 || T < sb || T > t_cap) return pce_fail(c, PCE_E_INVALID, "clip %d: %d tokens (need %d..%d)", i, T, sb, t_cap);
+        for (int t = 0; t < T; t++) {
+            const int v = tokens[token_offsets[i] + t];
+            if (v < 0 || v >= V) return pce_fail(c, PCE_E_INVALID, "token %d out of the vocabulary", v);
+        }
+        h_len[(size_t)i] = T; h_sb[(size_t)i] = sb; T_max = std::max(T_max, T);
+    }
+    const int pitch = form == 0 ? token_rows_pad(T_max) : t_cap;
+    const int64_t logits_need = (int64_t)steps * n * ld, out_need = form == 0 ? n : (int64_t)n * max_new, table_need = form == 0 ? 0 : (int64_t)n * t_cap,
+                  state_need = form == 0 ? 0 : (int64_t)10 * n + max_new + 1;
+    if (logits_elems < logits_need || mask_elems < V || out_elems < out_need || table_elems < table_need || state_elems < state_need || logits_elems >= ((int64_t)1 << 30) ||
+        out_elems >= ((int64_t)1 << 28) || table_elems >= ((int64_t)1 << 28) || state_elems >= ((int64_t)1 << 28))
+        return pce_fail(c, PCE_E_INVALID, "selftest decode rules: form %d needs logits %lld, vocab_mask %d, outputs %lld, table %lld, loop_state %lld elements", form,
+                        (long long)logits_need, V, (long long)out_need, (long long)table_need, (long long)state_need);
+    PCE_HIP(c, hipSetDevice(c->device));
+    // the token rows: the prompts at the launch's pitch; what lies past a sequence's length is pad_token (form 0) or what the caller's table holds (form 1)
+    std::vector<int> h_tok;
+    if (form == 0) h_tok.assign((size_t)n * pitch, pad_token); else h_tok.assign(table, table + table_elems);
+    for (int i = 0; i < n; i++) memcpy(&h_tok[(size_t)i * pitch], &tokens[token_offsets[i]], sizeof(int) * (size_t)h_len[(size_t)i]);
+    DevBuf dlog, dtok, dlen, dsb, dmask, dkeys, dout, dlp, dprobe, dstate, dnext;
+    PCE_HIP(c, dlog.reserve(sizeof(float) * (size_t)logits_elems)); PCE_HIP(c, dtok.reserve(sizeof(int) * h_tok.size())); PCE_HIP(c, dlen.reserve(sizeof(int) * (size_t)n));
+    PCE_HIP(c, dsb.reserve(sizeof(int) * (size_t)n)); PCE_HIP(c, dmask.reserve((size_t)V + 64)); PCE_HIP(c, dout.reserve(sizeof(int) * (size_t)out_elems));
+    PCE_HIP(c, dlp.reserve(sizeof(float) * (size_t)out_elems));
+    PCE_HIP(c, hipMemcpyAsync(dlog.p, logits, sizeof(float) * (size_t)logits_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dtok.p, h_tok.data(), sizeof(int) * h_tok.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dsb.p, h_sb.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dmask.p, vocab_mask, (size_t)V, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dout.p, out_tok, sizeof(int) * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(dlp.p, out_lp, sizeof(float) * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
+    if (sample_keys) {
+        PCE_HIP(c, dkeys.reserve(sizeof(int) * (size_t)n));
+        PCE_HIP(c, hipMemcpyAsync(dkeys.p, sample_keys, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    const int *keys = sample_keys ? dkeys.as<int>() : nullptr;
+    DecRules R{rules->eot, rules->timestamp_begin, V, (int)ld, sample_begin_all, rules->max_initial_timestamp_index, temperature, seed_lo, seed_hi,
+               form == 0 && probe_token >= 0 ? probe_token : -1};
+    if (form == 0) {
+        PCE_HIP(c, dprobe.reserve(sizeof(float) * (size_t)out_elems));
+        PCE_HIP(c, hipMemcpyAsync(dprobe.p, probe_prob, sizeof(float) * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(dlen.p, h_len.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        launch_decode_rules(c, n, dlog.as<float>(), dtok.as<int>(), dlen.as<int>(), pitch, dmask.as<unsigned char>(), R, dsb.as<int>(), dout.as<int>(), dlp.as<float>(),
+                            dprobe.as<float>(), keys);
+        PCE_HIP(c, hipGetLastError());
+        PCE_HIP(c, hipMemcpyAsync(probe_prob, dprobe.p, sizeof(float) * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        // loop_state: len [n] | ended [n] | ct [8 n] | n_ended [max_new] | step counter.  The lengths are the prompts', the counts and the counter start at zero (as the
+        // loop's do); ended and ct come in with the caller's values
+        std::vector<int> h_state(loop_state, loop_state + state_elems);
+        memcpy(h_state.data(), h_len.data(), sizeof(int) * (size_t)n);
+        std::fill(h_state.begin() + (size_t)10 * n, h_state.begin() + (size_t)state_need, 0);
+        PCE_HIP(c, dstate.reserve(sizeof(int) * h_state.size())); PCE_HIP(c, dnext.reserve((sizeof(int) + sizeof(float)) * (size_t)n));
+        PCE_HIP(c, hipMemcpyAsync(dstate.p, h_state.data(), sizeof(int) * h_state.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipStreamSynchronize(c->stream));              // (h_state leaves scope below)
+        int *S = dstate.as<int>(), *next = dnext.as<int>();
+        float *next_lp = reinterpret_cast<float *>(next + n);
+        const DecodeLoopState state{dtok.as<int>(), S, S + n, dout.as<int>(), dlp.as<float>(), S + (size_t)10 * n + max_new, S + (size_t)10 * n};
+        for (int s = 0; s < steps; s++) {
+            launch_decode_rules(c, n, dlog.as<float>() + (size_t)s * n * (size_t)ld, state.tok_table, state.len, pitch, dmask.as<unsigned char>(), R, dsb.as<int>(), next,
+                                next_lp, nullptr, keys);
+            launch_step_advance(c, state, n, t_cap, (int)rules->eot, (int)max_new, next, next_lp, S + (size_t)2 * n);
+        }
+        PCE_HIP(c, hipGetLastError());
+        PCE_HIP(c, hipMemcpyAsync(table, dtok.p, sizeof(int) * (size_t)table_elems, hipMemcpyDeviceToHost, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(loop_state, dstate.p, sizeof(int) * (size_t)state_elems, hipMemcpyDeviceToHost, c->stream));
+    }
+    PCE_HIP(c, hipMemcpyAsync(out_tok, dout.p, sizeof(int) * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipMemcpyAsync(out_lp, dlp.p, sizeof(float) * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
+}
+
 // Self-test hook of the encoder-output cross-attention of an incremental decoding step (pce_xattn.inc): k_xq_fused -> k_xattn_absorbed -> k_uv_absorb of ONE
 // layer on host arrays, with the number of workgroups per clip forced (0: what the batch size selects).  See include/pce.h.
 int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,

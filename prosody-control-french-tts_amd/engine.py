@@ -203,7 +203,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
            "pce_dtw", "pce_dtw_series", "pce_ctc_align", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
-           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_selftest_align_matrix", "pce_whisper_encode_fetch",
+           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_selftest_align_matrix", "pce_selftest_decode_rules", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_w2v_check", "pce_w2v_load", "pce_w2v_run", "pce_w2v_shape", "pce_w2v_fetch", "pce_w2v_device", "pce_w2v_window_plan",
            "pce_selftest_w2v_wave", "pce_selftest_w2v_lngelu", "pce_selftest_w2v_posconv",
@@ -306,6 +306,8 @@ def load_library() -> C.CDLL:
     lib.pce_selftest_attention_ragged.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i64, vp]
     lib.pce_selftest_attn1.argtypes = [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i64]
     lib.pce_selftest_align_matrix.argtypes = [vp, i32, i32, vp, i64, vp, i64, i32, vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, i64, vp, i64, vp, i64]
+    lib.pce_selftest_decode_rules.argtypes = [vp, i32, i32, i32, i32, vp, i64, vp, vp, i32, i32, vp, i32, C.POINTER(WhisperDecodeRules), vp, i64, C.c_float, C.c_uint32,
+                                              C.c_uint32, i32, vp, i32, vp, vp, vp, i64, vp, i64, vp, i64]
     lib.pce_selftest_xattn.argtypes = [vp] * 11 + [i32] * 5 + [vp]
     lib.pce_selftest_gemm_tiled.argtypes = [vp, i32, i32, vp, i64, i64, i64, i32, vp, vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp]
     lib.pce_selftest_layernorm.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp]
@@ -808,6 +810,33 @@ class ProsodyEngine:
                                                         tl.ctypes.data, fl.ctypes.data, hs.ctypes.data, int(hs.size), int(split), int(sot_len),
                                                         int(medfilt_width), float(qk_scale), w_soft.ctypes.data, w_soft.size, w_norm.ctypes.data,
                                                         w_norm.size, cost.ctypes.data, cost.size))
+
+    def selftest_decode_rules(self, form: int, n_vocab: int, logits, token_lists, sample_begin, eot: int, timestamp_begin: int, vocab_mask, out_tok, out_lp,
+                              probe_prob=None, max_initial_timestamp_index=None, temperature: float = 0.0, seed: int = 0, probe_token: int = -1,
+                              sample_keys=None, pad_token: int = 0, t_cap: int = 448, max_new: int = 0, table=None, loop_state=None):
+        """``pce_selftest_decode_rules``: k_decode_rules (and, form 1, k_step_advance) on host arrays through the decoding calls' own launches.
+        logits: float32 [steps][n][ld], ld = n_vocab rounded up to 128; ``sample_begin``: int or one per sequence.  form 0: one step over the
+        sequences padded with ``pad_token``; out_tok (int32) / out_lp / probe_prob (float32) [>= n] are read and updated in place.  form 1: ``steps``
+        loop steps at pitch ``t_cap``; out_tok / out_lp [n][max_new], table int32 [n][t_cap] and loop_state int32 [10 n + max_new + 1]
+        (len | ended | ct [8][n] | n_ended | step counter) are read and updated in place."""
+        for x, dt in ((logits, np.float32), (out_tok, np.int32), (out_lp, np.float32), (probe_prob, np.float32), (table, np.int32), (loop_state, np.int32)):
+            assert x is None or (isinstance(x, np.ndarray) and x.dtype == dt and x.flags["C_CONTIGUOUS"]), getattr(x, "dtype", None)
+        toks = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int32) for t in token_lists] + [np.zeros(0, np.int32)]), dtype=np.int32)
+        off = np.zeros(len(token_lists) + 1, dtype=np.int32); np.cumsum([len(t) for t in token_lists], out=off[1:])
+        n = len(token_lists)
+        rules = WhisperDecodeRules(int(eot), int(timestamp_begin), -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index), 0)
+        vm = np.ascontiguousarray(vocab_mask, dtype=np.uint8)
+        sb = None if np.isscalar(sample_begin) else np.ascontiguousarray(sample_begin, dtype=np.int32)
+        keys = None if sample_keys is None else np.ascontiguousarray(sample_keys, dtype=np.int32)
+        assert (sb is None or sb.size == n) and (keys is None or keys.size == n) and out_tok.size == out_lp.size and (probe_prob is None or probe_prob.size == out_tok.size)
+        steps = logits.shape[0] if logits.ndim == 3 else 1
+        ptr = lambda x: None if x is None else x.ctypes.data
+        size = lambda x: 0 if x is None else x.size
+        self._check(self._lib.pce_selftest_decode_rules(self._ctx, int(form), n, int(n_vocab), int(steps), logits.ctypes.data, logits.size, toks.ctypes.data,
+                                                        off.ctypes.data, int(pad_token), int(t_cap), ptr(sb), int(sample_begin) if sb is None else 0, C.byref(rules),
+                                                        vm.ctypes.data, vm.size, float(temperature), int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF,
+                                                        int(probe_token), ptr(keys), int(max_new), out_tok.ctypes.data, out_lp.ctypes.data, ptr(probe_prob),
+                                                        out_tok.size, ptr(table), size(table), ptr(loop_state), size(loop_state)))
 
     def selftest_xattn(self, resid, ln_w, ln_b, wq, bq, wk, wv, bv, E, k_len, heads: int, workgroups_per_clip: int = 0):
         """One layer of the encoder-output cross-attention of a decoding step (``pce_selftest_xattn``): resid [n][d], E [n][k_cap][d], weights [d][d]
