@@ -69,9 +69,10 @@ extern "C" {
  * forward pass of the resident batch: the emissions pce_ctc_align reads in place) and their four kernel ids, which sit behind minor 13's and in
  * front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by four (pce_kernel_name follows);
  * 17 = pce_selftest_decode_rules (the kernels that turn a decoding step's logits into tokens and carry them into the loop's tables, on host arrays
- * through the decoding calls' own launches). */
+ * through the decoding calls' own launches);
+ * 18 = pce_selftest_logmel_image (the 16-bit time-major log-mel image the conv stem reads, copied out as the last run left it). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 17
+#define PCE_API_MINOR 18
 
 typedef struct pce_ctx pce_ctx;
 
@@ -385,6 +386,11 @@ int pce_logmel_run(pce_ctx *ctx, int32_t n_mels);
  * the maximum over the whole recording.  start_frames[clip] * 160 must not exceed the clip length. */
 int pce_logmel_run_at(pce_ctx *ctx, int32_t n_mels, const int64_t *start_frames /* [clips] */);
 int pce_logmel_fetch(pce_ctx *ctx, int32_t clip, float *out /* [n_mels][3000] */);
+/* Self-test, read-only: the time-major image [3002][n_mels] of `clip` that the last pce_logmel_run / pce_logmel_run_at left for the conv stem, as bit
+ * patterns of the context's operand type (bf16 or fp16): rows 1 .. 3000 are frames 0 .. 2999, rows 0 and 3001 the stem's zero padding.  Nothing is
+ * launched and nothing written: the copy shows what the encoder would read.  PCE_E_STATE before a run (of the selected operand build), PCE_E_INVALID
+ * for a clip outside the run's batch.  Since minor 18. */
+int pce_selftest_logmel_image(pce_ctx *ctx, int32_t clip, uint16_t *out /* [3002][n_mels] */);
 int pce_whisper_load(pce_ctx *ctx, const pce_whisper_dims *dims, const float *weights, int64_t n_floats);
 int pce_whisper_encode_run(pce_ctx *ctx);
 /* Self-test of the GEMM kernel the encoder's projections run on (persistent 256 x 256 tiles, csrc/pce_gemm256.inc) on host arrays of bf16 bit

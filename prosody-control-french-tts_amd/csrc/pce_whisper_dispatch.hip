@@ -9,6 +9,7 @@
 PCE_BOTH(int, pce_logmel_run, (pce_ctx *, int32_t))
 PCE_BOTH(int, pce_logmel_run_at, (pce_ctx *, int32_t, const int64_t *))
 PCE_BOTH(int, pce_logmel_fetch, (pce_ctx *, int32_t, float *))
+PCE_BOTH(int, pce_selftest_logmel_image, (pce_ctx *, int32_t, uint16_t *))
 PCE_BOTH(int, pce_whisper_load, (pce_ctx *, const pce_whisper_dims *, const float *, int64_t))
 PCE_BOTH(int, pce_whisper_encode_run, (pce_ctx *))
 PCE_BOTH(int, pce_whisper_encode_fetch, (pce_ctx *, int32_t, float *))
@@ -71,6 +72,7 @@ int pce_whisper_get_operands(pce_ctx *c) { return c ? c->whisper_ops : PCE_E_INV
 int pce_logmel_run(pce_ctx *c, int32_t n_mels) { return PCE_FWD(pce_logmel_run, c, n_mels); }
 int pce_logmel_run_at(pce_ctx *c, int32_t n_mels, const int64_t *start_frames) { return PCE_FWD(pce_logmel_run_at, c, n_mels, start_frames); }
 int pce_logmel_fetch(pce_ctx *c, int32_t clip, float *out) { return PCE_FWD(pce_logmel_fetch, c, clip, out); }
+int pce_selftest_logmel_image(pce_ctx *c, int32_t clip, uint16_t *out) { return PCE_FWD(pce_selftest_logmel_image, c, clip, out); }
 int pce_whisper_load(pce_ctx *c, const pce_whisper_dims *dims, const float *weights, int64_t n_floats) { return PCE_FWD(pce_whisper_load, c, dims, weights, n_floats); }
 int pce_whisper_encode_run(pce_ctx *c) { return PCE_FWD(pce_whisper_encode_run, c); }
 int pce_whisper_encode_fetch(pce_ctx *c, int32_t clip, float *out) { return PCE_FWD(pce_whisper_encode_fetch, c, clip, out); }

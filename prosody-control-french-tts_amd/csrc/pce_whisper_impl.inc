@@ -45,6 +45,7 @@
 #define pce_logmel_run PCE_WFN(pce_logmel_run)
 #define pce_logmel_run_at PCE_WFN(pce_logmel_run_at)
 #define pce_logmel_fetch PCE_WFN(pce_logmel_fetch)
+#define pce_selftest_logmel_image PCE_WFN(pce_selftest_logmel_image)
 #define pce_whisper_load PCE_WFN(pce_whisper_load)
 #define pce_whisper_encode_run PCE_WFN(pce_whisper_encode_run)
 #define pce_whisper_encode_fetch PCE_WFN(pce_whisper_encode_fetch)
@@ -2531,6 +2532,22 @@ int pce_logmel_fetch(pce_ctx *c, int32_t clip, float *out)
     PCE_HIP(c, hipMemcpyAsync(out, w->mel_stage.p, sizeof(float) * per, hipMemcpyDeviceToHost, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
+    return PCE_OK;
+}
+
+// the op_t time-major image of one clip as the last run left it (what the conv stem reads), copied out: nothing is launched, nothing written
+int pce_selftest_logmel_image(pce_ctx *c, int32_t clip, uint16_t *out)
+{
+    if (!c || !out) return PCE_E_INVALID;
+    WhisperState *w = ws_of(c);
+    if (w->n_clips_mel < 0) return pce_fail(c, PCE_E_STATE, "pce_selftest_logmel_image before pce_logmel_run");
+    if (clip < 0 || clip >= w->n_clips_mel) return pce_fail(c, PCE_E_INVALID, "clip out of range");
+    static_assert(sizeof(op_t) == sizeof(uint16_t), "the image travels as 16-bit patterns");
+    const size_t per = (size_t)(W_FRAMES + 2) * (size_t)w->mel_nmels;
+    if (sizeof(op_t) * per * ((size_t)clip + 1) > w->mel_tm.cap) return pce_fail(c, PCE_E_STATE, "the last log-mel run did not finish: run it again");
+    PCE_HIP(c, hipSetDevice(c->device));
+    PCE_HIP(c, hipMemcpyAsync(out, w->mel_tm.as<op_t>() + (size_t)clip * per, sizeof(op_t) * per, hipMemcpyDeviceToHost, c->stream));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
 

@@ -203,7 +203,7 @@ EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_v
            "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
            "pce_resample_run", "pce_download_pcm_s16",
            "pce_dtw", "pce_dtw_series", "pce_ctc_align", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
-           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_selftest_align_matrix", "pce_selftest_decode_rules", "pce_whisper_encode_fetch",
+           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_selftest_logmel_image", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_selftest_align_matrix", "pce_selftest_decode_rules", "pce_whisper_encode_fetch",
            "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
            "pce_w2v_check", "pce_w2v_load", "pce_w2v_run", "pce_w2v_shape", "pce_w2v_fetch", "pce_w2v_device", "pce_w2v_window_plan",
            "pce_selftest_w2v_wave", "pce_selftest_w2v_lngelu", "pce_selftest_w2v_posconv",
@@ -298,6 +298,7 @@ def load_library() -> C.CDLL:
     lib.pce_logmel_run.argtypes = [vp, i32]
     lib.pce_logmel_run_at.argtypes = [vp, i32, vp]
     lib.pce_logmel_fetch.argtypes = [vp, i32, vp]
+    lib.pce_selftest_logmel_image.argtypes = [vp, i32, vp]
     lib.pce_whisper_load.argtypes = [vp, C.POINTER(WhisperDims), vp, i64]
     lib.pce_whisper_encode_run.argtypes = [vp]
     lib.pce_selftest_gemm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
@@ -654,6 +655,13 @@ class ProsodyEngine:
     def logmel_fetch(self, clip: int) -> np.ndarray:
         out = np.zeros((self._n_mels, 3000), dtype=np.float32)
         self._check(self._lib.pce_logmel_fetch(self._ctx, int(clip), out.ctypes.data))
+        return out
+
+    def selftest_logmel_image(self, clip: int) -> np.ndarray:
+        """The 16-bit time-major image ``[3002][n_mels]`` the conv stem reads, as the last ``logmel_run`` / ``logmel_run_at`` left it
+        (bit patterns of the context's operand type; rows 0 and 3001 are the stem's zero padding).  Read-only."""
+        out = np.zeros((3002, getattr(self, "_n_mels", 128)), dtype=np.uint16)
+        self._check(self._lib.pce_selftest_logmel_image(self._ctx, int(clip), out.ctypes.data))
         return out
 
     # ---------------------------------------------------------------- operand type of the Whisper / BERT products
