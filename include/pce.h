@@ -401,7 +401,7 @@ int pce_selftest_gemm(pce_ctx *ctx, const uint16_t *A, const uint16_t *B, const 
 /* The same kernel with its residual epilogue, in place as the encoder's attention projection and fc2 run it on the 16-bit residual stream:
  * resid_inout[M][N] = r16(resid_inout + r16(A B^T + bias)) (r16: rounding to the context's 16-bit operand type; bit patterns in and out). */
 int pce_selftest_gemm_resid(pce_ctx *ctx, const uint16_t *A, const uint16_t *B, const float *bias, uint16_t *resid_inout, int32_t M, int32_t N, int32_t K);
-/* Self-test of the attention kernel (64-wide heads; csrc/pce_whisper_impl.inc k_attention_lean16) on host arrays of bf16 bit patterns: clips x
+/* Self-test of the attention kernel (64-wide heads; csrc/pce_attention.inc k_attention_lean16) on host arrays of bf16 bit patterns: clips x
  * heads independent problems, q [clips][q_len][heads * 64], k and v [clips][k_len][heads * 64], out like q; softmax(q k^T / 8) v with the
  * causal mask when causal != 0.  mode 0: the kernel as the engine runs it (fixed softmax reference, exact fallback), 1: its exact
  * path only.  *fell_back (may be NULL): number of workgroups that had to take the exact path (mode 0). */

@@ -17,7 +17,7 @@ __global__ void k_bert_embed(const int *__restrict__ tokens /* [seqs][T_pad] */,
 // Break-prediction token classifier: BertForTokenClassification forward (post-LN encoder layers on the same GEMM /
 // attention / LayerNorm kernels as the Whisper encoder; Code/baseline_models/pause_bert.py:127-132).
 // ---------------------------------------------------------------------------
-extern "C" {
+namespace PCE_BUILD_NS {
 
 int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, int64_t n_floats)
 {
@@ -42,7 +42,7 @@ int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, i
     const float *type = p; p += (size_t)TY * d;
     b.lne_w = add_vec(p, (size_t)d); p += d; b.lne_b = add_vec(p, (size_t)d); p += d;
     for (int l = 0; l < L; l++) {
-        WhisperState::Bert::Layer &ly = b.layers[(size_t)l];
+        EncoderLayerW &ly = b.layers[(size_t)l];
         const float *qw = p, *qb = qw + dd, *kw = qb + d, *kb = kw + dd, *vw = kb + d, *vb = vw + dd;
         ly.qkv_w = add_mat(qw, (size_t)dd); add_mat(kw, (size_t)dd); add_mat(vw, (size_t)dd);          // fused [3d][d]
         ly.qkv_b = add_vec(qb, (size_t)d); add_vec(kb, (size_t)d); add_vec(vb, (size_t)d);
@@ -124,7 +124,7 @@ int pce_bert_run(pce_ctx *c, const int32_t *input_ids, const int32_t *offsets, i
     };
     ln(b.lne_w, b.lne_b);
     for (int l = 0; l < L; l++) {
-        const WhisperState::Bert::Layer &ly = b.layers[(size_t)l];
+        const EncoderLayerW &ly = b.layers[(size_t)l];
         launch_gemm<EPI_QKV>(c, b.ln.as<op_t>(), d, 0, Wb + ly.qkv_w, (int)M, 3 * d, d, Wf + ly.qkv_b, b.qk.as<op_t>(), 2 * d, 0, 1,
                              reinterpret_cast<const float *>(b.vt.as<op_t>()), T_pad, 2 * d, SPD);
         launch_attention_rows(c, n, H, T_pad, b.qk.as<op_t>(), 2 * d, b.qk.as<op_t>() + d, 2 * d, b.vt.as<op_t>(), SPD, T0, TL, T0, TL, b.attn.as<op_t>(),
@@ -166,4 +166,4 @@ int pce_bert_fetch(pce_ctx *c, int32_t seq, float *logits, int32_t *labels)
     return PCE_OK;
 }
 
-} // extern "C"
+} // namespace PCE_BUILD_NS

@@ -265,7 +265,7 @@ int pce_ctc_align(pce_ctx *c, const float *emissions, int32_t emissions_on_devic
     if ((total_frames && !emissions) || (target_off[n] && (!tok_first || !tok_last))) return pce_fail(c, PCE_E_INVALID, "pce_ctc_align: NULL emissions or token outputs");
 
     // groups of consecutive clips whose traces fit the budget
-    const int64_t budget_words = (int64_t)(c->ctc_trace_budget / 4);
+    const int64_t budget_words = (int64_t)(c->sw.ctc_trace_budget / 4);
     std::vector<size_t> group_end;
     int64_t scratch_floats = 0, max_group_words = 0;
     {
@@ -275,7 +275,7 @@ int pce_ctc_align(pce_ctx *c, const float *emissions, int32_t emissions_on_devic
             const int64_t w = div_up(tab[q].T, 4) * (int64_t)tab[q].NT;
             if (w > budget_words)
                 return pce_fail(c, PCE_E_LIMIT, "pce_ctc_align: clip %zu (%d frames, %d targets) needs %.1f MiB of trace, the budget is %.1f MiB (PCE_CTC_TRACE_MB)", q,
-                                tab[q].T, tab[q].L, w * 4.0 / 1048576.0, c->ctc_trace_budget / 1048576.0);
+                                tab[q].T, tab[q].L, w * 4.0 / 1048576.0, c->sw.ctc_trace_budget / 1048576.0);
             if (words + w > budget_words) { group_end.push_back(q); words = 0; }
             tab[q].trace0 = words;
             words += w;

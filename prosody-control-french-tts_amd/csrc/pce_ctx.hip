@@ -49,7 +49,7 @@ int pce_join_aux(pce_ctx *c)
 int pce_side_begin(pce_ctx *c, int which, hipStream_t *out)
 {
     *out = c->stream;
-    if (c->no_side) return PCE_OK;
+    if (c->sw.no_side) return PCE_OK;
     pce_ctx::Side &sd = c->side[which];
     PCE_HIP(c, hipEventRecord(sd.fork, c->stream));
     PCE_HIP(c, hipStreamWaitEvent(sd.s, sd.fork, 0));
@@ -80,6 +80,25 @@ void pce_profile_collect(pce_ctx *ctx, bool wait)
         ctx->ev_pool.push_back(p.b);
     }
     ctx->pending.resize(kept);
+}
+
+// The switches a context takes from the environment when it is created (pce_ctx::Switches)
+static pce_ctx::Switches switches_from_env()
+{
+    pce_ctx::Switches sw;
+    sw.no_side = getenv("PCE_NO_AUX") != nullptr;
+    sw.stft_two_fft = getenv("PCE_STFT_TWO_FFT") != nullptr;
+    sw.generic_median = getenv("PCE_ALIGN_GENERIC_MEDIAN") != nullptr;
+    sw.gemm_flat = !(getenv("PCE_GEMM_FLAT") && atoi(getenv("PCE_GEMM_FLAT")) == 0);
+    if (const char *re = getenv("PCE_RESID_EPILOGUE")) sw.resid_epilogue = atoi(re) == 0 ? 0 : atoi(re) == 2 ? 2 : 1;
+    sw.stem_skip = !(getenv("PCE_STEM_SKIP") && atoi(getenv("PCE_STEM_SKIP")) == 0);
+    sw.en_cpb = getenv("PCE_EN_CPB") ? atoi(getenv("PCE_EN_CPB")) : 0;
+    sw.gemm_skinny = !(getenv("PCE_GEMM_SKINNY") && atoi(getenv("PCE_GEMM_SKINNY")) == 0);
+    sw.self_rows = !(getenv("PCE_SELF_ROWS") && atoi(getenv("PCE_SELF_ROWS")) == 0);
+    sw.xattn_absorb = !(getenv("PCE_XATTN_ABSORB") && atoi(getenv("PCE_XATTN_ABSORB")) == 0);
+    if (getenv("PCE_DTW_TRACE_MB") && atoll(getenv("PCE_DTW_TRACE_MB")) > 0) sw.dtw_trace_budget = (size_t)atoll(getenv("PCE_DTW_TRACE_MB")) << 20;
+    if (getenv("PCE_CTC_TRACE_MB") && atoll(getenv("PCE_CTC_TRACE_MB")) > 0) sw.ctc_trace_budget = (size_t)atoll(getenv("PCE_CTC_TRACE_MB")) << 20;
+    return sw;
 }
 
 extern "C" {
@@ -115,16 +134,7 @@ pce_ctx *pce_create(int device, void *stream, char *err, size_t errlen)
         if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) { delete c; return fail("hipStreamCreate", e); }
         c->own_stream = true;
     }
-    c->no_side = getenv("PCE_NO_AUX") != nullptr;
-    c->stft_two_fft = getenv("PCE_STFT_TWO_FFT") != nullptr;
-    c->generic_median = getenv("PCE_ALIGN_GENERIC_MEDIAN") != nullptr;
-    c->gemm_flat = !(getenv("PCE_GEMM_FLAT") && atoi(getenv("PCE_GEMM_FLAT")) == 0);
-    if (const char *re = getenv("PCE_RESID_EPILOGUE")) c->resid_epilogue = atoi(re) == 0 ? 0 : atoi(re) == 2 ? 2 : 1;
-    c->stem_skip = !(getenv("PCE_STEM_SKIP") && atoi(getenv("PCE_STEM_SKIP")) == 0);
-    c->en_cpb = getenv("PCE_EN_CPB") ? atoi(getenv("PCE_EN_CPB")) : 0;
-    c->gemm_skinny = !(getenv("PCE_GEMM_SKINNY") && atoi(getenv("PCE_GEMM_SKINNY")) == 0);
-    c->self_rows = !(getenv("PCE_SELF_ROWS") && atoi(getenv("PCE_SELF_ROWS")) == 0);
-    c->xattn_absorb = !(getenv("PCE_XATTN_ABSORB") && atoi(getenv("PCE_XATTN_ABSORB")) == 0);
+    c->sw = switches_from_env();
     {
         const char *ops = getenv("PCE_WHISPER_OPERANDS");
         // default (round 4): fp16 operands AND the fp16 residual stream, the reference's own arithmetic end to end (openai-whisper fp16=True);
@@ -141,8 +151,6 @@ pce_ctx *pce_create(int device, void *stream, char *err, size_t errlen)
         c->resid16 = c->whisper_ops == 2;
     }
     c->pitch_refine_praat = getenv("PCE_PITCH_REFINE") && !strcmp(getenv("PCE_PITCH_REFINE"), "praat");
-    if (getenv("PCE_DTW_TRACE_MB") && atoll(getenv("PCE_DTW_TRACE_MB")) > 0) c->dtw_trace_budget = (size_t)atoll(getenv("PCE_DTW_TRACE_MB")) << 20;
-    if (getenv("PCE_CTC_TRACE_MB") && atoll(getenv("PCE_CTC_TRACE_MB")) > 0) c->ctc_trace_budget = (size_t)atoll(getenv("PCE_CTC_TRACE_MB")) << 20;
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
     for (int si = 0; si < pce_ctx::SIDE_COUNT; si++) {

@@ -181,7 +181,7 @@ int pce_dtw_series(pce_ctx *c, const double *a, const int64_t *a_off, const doub
     for (size_t x = 0; x < nb; x++) if (!std::isfinite(b[x])) return pce_fail(c, PCE_E_INVALID, "pce_dtw_series: b[%zu] is not finite", x);
 
     // plan every pair from its own n, m and window alone (what a pair computes does not depend on its batch)
-    const long long budget_words = (long long)(c->dtw_trace_budget / 4);
+    const long long budget_words = (long long)(c->sw.dtw_trace_budget / 4);
     std::vector<PairPlan> plans;
     for (int32_t q = 0; q < batch; q++) {
         const int n = (int)(a_off[q + 1] - a_off[q]), m = (int)(b_off[q + 1] - b_off[q]);
@@ -210,7 +210,7 @@ int pce_dtw_series(pce_ctx *c, const double *a, const int64_t *a_off, const doub
         }
         if (pl.trace_words > budget_words)
             return pce_fail(c, PCE_E_LIMIT, "pce_dtw_series: pair %d (%d x %d) needs %.1f MiB of trace, the budget is %.1f MiB (PCE_DTW_TRACE_MB)", q, n, m,
-                            pl.trace_words * 4.0 / 1048576.0, c->dtw_trace_budget / 1048576.0);
+                            pl.trace_words * 4.0 / 1048576.0, c->sw.dtw_trace_budget / 1048576.0);
         plans.push_back(std::move(pl));
     }
     if (plans.empty()) return PCE_OK;

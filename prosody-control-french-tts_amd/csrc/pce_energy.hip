@@ -183,7 +183,7 @@ int pce_energy_launch(pce_ctx *c, int32_t n, int32_t loud_thr, int64_t n_work, D
         // chunks per workgroup: as many as leave every CU >= 24 workgroups (7 are resident), at most 8 (the per-lane sums above).
         // Measured (us per launch at 82 MB / 400 MB / 1.6 GB): 1 chunk 21.5 / 73.5 / 310, 2: 23.2 / 68.9 / 296, 4: 23.2 / 72.9 / 288, 8: 30.0 / 79.1 / 291
         const int64_t cus = c->cu_count > 0 ? c->cu_count : 256;
-        int cpb = c->en_cpb > 0 ? c->en_cpb : (int)std::min<int64_t>(8, std::max<int64_t>(1, n_work / (cus * 24)));
+        int cpb = c->sw.en_cpb > 0 ? c->sw.en_cpb : (int)std::min<int64_t>(8, std::max<int64_t>(1, n_work / (cus * 24)));
         if (cpb > 8) cpb = 8;
         const unsigned grid = (unsigned)((n_work + cpb - 1) / cpb);
         auto launch = [&](auto kern) {

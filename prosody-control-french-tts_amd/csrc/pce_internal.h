@@ -67,16 +67,24 @@ struct pce_ctx {
     //              beside the pitch kernels it only competed for VALU issue, 3.33 -> 3.54 ms)
     enum { SIDE_TAIL = 0, SIDE_LUFS = 1, SIDE_STFT = 2, SIDE_COUNT = 3 };
     struct Side { hipStream_t s = nullptr; hipEvent_t fork = nullptr, join = nullptr; bool pending = false; } side[SIDE_COUNT];
-    bool no_side = false;                // PCE_NO_AUX at pce_create: everything on `stream`
-    bool generic_median = false;         // PCE_ALIGN_GENERIC_MEDIAN at pce_create: the insertion-sort median filter for every width
+    // what pce_create reads from the environment, once (switches_from_env, pce_ctx.hip)
+    struct Switches {
+        bool no_side = false;                // PCE_NO_AUX at pce_create: everything on `stream`
+        bool generic_median = false;         // PCE_ALIGN_GENERIC_MEDIAN at pce_create: the insertion-sort median filter for every width
+        bool gemm_skinny = true;             // PCE_GEMM_SKINNY=0 at pce_create: few-row launches stay on the 128 x 128 kernel
+        bool gemm_flat = true;               // PCE_GEMM_FLAT=0 at pce_create: the encoder's projections stay on the 128 x 128 / 128 x 256 tile kernels
+        int resid_epilogue = 1;              // PCE_RESID_EPILOGUE at pce_create: 0 = the 16-bit-stream encoder stores its branch outputs and adds them in k_add_layernorm (A/B, bit-identity
+                                             // test), 2 = only fc2 adds in its epilogue (the per-shape A/B of DESIGN.md section 4); default 1: the attention projection and fc2 do
+        bool stem_skip = true;               // PCE_STEM_SKIP=0 at pce_create: the conv stem multiplies every row of the 30 s window, the zero padding's included (A/B, bit-identity test)
+        bool stft_two_fft = false;           // PCE_STFT_TWO_FFT at pce_create: traffic-minimal STFT-dB (the FFT runs twice)
+        int en_cpb = 0;                      // PCE_EN_CPB: chunks per k_energy workgroup (0 = by batch size)
+        bool xattn_absorb = true;            // incremental decoding steps: cross-attention from the encoder output (pce_xattn.inc); PCE_XATTN_ABSORB=0: from the K / V^T cache
+        bool self_rows = true;               // incremental steps' self-attention on row-major K / V caches (k_self_attn1w); PCE_SELF_ROWS=0: k_cross_attn1w on K rows + V^T
+        size_t dtw_trace_budget = (size_t)4096 << 20;   // PCE_DTW_TRACE_MB at pce_create: bytes of trace one group of pairs may hold
+        size_t ctc_trace_budget = (size_t)4096 << 20;   // PCE_CTC_TRACE_MB at pce_create: bytes of trace one group of clips may hold
+    } sw;
     bool pitch_refine_praat = false;     // PCE_PITCH_REFINE=praat at pce_create: the candidate refinement replays NUMminimize_brent's own iterates (round 1 / 2 behaviour)
     bool gemm_few_rows = false;          // set by the incremental decoding step around its launches: k_gemm_skinny is eligible
-    bool gemm_skinny = true;             // PCE_GEMM_SKINNY=0 at pce_create: few-row launches stay on the 128 x 128 kernel
-    bool gemm_flat = true;               // PCE_GEMM_FLAT=0 at pce_create: the encoder's projections stay on the 128 x 128 / 128 x 256 tile kernels
-    int resid_epilogue = 1;              // PCE_RESID_EPILOGUE at pce_create: 0 = the 16-bit-stream encoder stores its branch outputs and adds them in k_add_layernorm (A/B, bit-identity
-                                         // test), 2 = only fc2 adds in its epilogue (the per-shape A/B of DESIGN.md section 4); default 1: the attention projection and fc2 do
-    bool stem_skip = true;               // PCE_STEM_SKIP=0 at pce_create: the conv stem multiplies every row of the 30 s window, the zero padding's included (A/B, bit-identity test)
-    bool stft_two_fft = false;           // PCE_STFT_TWO_FFT at pce_create: traffic-minimal STFT-dB (the FFT runs twice)
     std::string err;
     int cu_count = 0;
 
@@ -89,7 +97,6 @@ struct pce_ctx {
     int32_t rate = 0;
 
     // energy
-    int en_cpb = 0;                 // PCE_EN_CPB: chunks per k_energy workgroup (0 = by batch size)
     DevBuf en_work, en_out;
     SliceCache en_cache;
     int64_t en_n_work = 0;
@@ -110,8 +117,6 @@ struct pce_ctx {
     double pi_P[32] = {0};          // PiParams image
     int64_t pi_n_work = 0, pi_n_energy_work = 0;
     int pi_np2 = 1;
-    bool xattn_absorb = true;       // incremental decoding steps: cross-attention from the encoder output (pce_xattn.inc); PCE_XATTN_ABSORB=0: from the K / V^T cache
-    bool self_rows = true;          // incremental steps' self-attention on row-major K / V caches (k_self_attn1w); PCE_SELF_ROWS=0: k_cross_attn1w on K rows + V^T
     bool pi_long_slices = false;    // some slice has more frames than the in-LDS median sort holds (k_pitch_median_long takes those)
     SliceCache pi_cache;
     pce_pitch_params pi_params;
@@ -177,12 +182,10 @@ struct pce_ctx {
 
     // DTW of series pairs (pce_dtw_series.hip): the batch's inputs and results, the tables of the group in flight, its boundary rows / columns and trace
     struct DtwSeries { DevBuf a, b, lo, hi, pi, pj, dist, len, status, pairs, tab, tiles, rows, cols, trace; } ds;
-    size_t dtw_trace_budget = (size_t)4096 << 20;   // PCE_DTW_TRACE_MB at pce_create: bytes of trace one group of pairs may hold
 
     // CTC forced alignment (pce_ctc.hip): uploaded emissions, clip table, clip-id lists, targets, final alphas, the trace of the group in flight, the general
     // form's alpha rows, the batch's results
     struct Ctc { DevBuf lp, tab, ids, tgt, fin, trace, scratch, path, fscore, first, last, score, status; } ctc;
-    size_t ctc_trace_budget = (size_t)4096 << 20;   // PCE_CTC_TRACE_MB at pce_create: bytes of trace one group of clips may hold
 
     // whisper / BERT state, opaque (pce_whisper_impl.inc): one slot per operand-type build (0: bf16, 1: fp16); whisper_ops selects the build the
     // entry points of include/pce.h forward to (pce_whisper_set_operands, or PCE_WHISPER_OPERANDS=fp16 at pce_create)

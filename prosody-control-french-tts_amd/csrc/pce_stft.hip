@@ -392,7 +392,7 @@ int pce_stft_db_run(pce_ctx *c, int32_t n_fft, int32_t hop)
     const float2 *g512 = c->st_twiddle.as<float2>();
     const float2 *g1024 = g512 + MC;
     PCE_HIP(c, hipMemsetAsync(c->st_max.p, 0, sizeof(unsigned int) * (size_t)c->n_clips, c->stream));
-    if (c->stft_two_fft) {                                                           // traffic-minimal form: run the FFT twice
+    if (c->sw.stft_two_fft) {                                                           // traffic-minimal form: run the FFT twice
         {
             KernelTimer t(c, PCE_K_STFT_MAX);
             hipLaunchKernelGGL((k_stft_max<F, WAVES>), dim3(grid), dim3(64 * WAVES), 0, c->stream, c->d_pcm, c->st_off.as<StClip>(),
@@ -416,7 +416,7 @@ int pce_stft_db_run(pce_ctx *c, int32_t n_fft, int32_t hop)
         // the clip's maximum, and whoever takes the values applies `max(x - ref_db, -80)`: pce_stft_db_fetch per clip on its way out, pce_stft_db_device once,
         // in place, when a device-side consumer asks for the finished matrix.  Same kernel, same arithmetic, same bits as the eager pass.
     }
-    c->st_final = c->stft_two_fft;
+    c->st_final = c->sw.stft_two_fft;
     PCE_HIP(c, hipGetLastError());
     c->st_ran = true;
     return PCE_OK;

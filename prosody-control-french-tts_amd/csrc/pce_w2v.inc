@@ -387,7 +387,7 @@ static int w2v_check(const pce_w2v_dims &m, int64_t n_floats, char *msg, size_t 
 
 } // namespace
 
-extern "C" {
+namespace PCE_BUILD_NS {
 
 int pce_w2v_check(const pce_w2v_dims *dims, int64_t n_floats, char *msg, size_t cap)
 {
@@ -427,7 +427,7 @@ int pce_w2v_load(pce_ctx *c, const pce_w2v_dims *dims, const float *weights, int
     b.pos_w = add_mat(p, (size_t)d * cg * PC_TAPS); p += (size_t)d * cg * PC_TAPS; b.pos_b = add_vec(p, (size_t)d); p += d;
     b.enc_ln_w = add_vec(p, (size_t)d); p += d; b.enc_ln_b = add_vec(p, (size_t)d); p += d;
     for (int l = 0; l < L; l++) {
-        WhisperState::W2v::Layer &ly = b.layers[(size_t)l];
+        EncoderLayerW &ly = b.layers[(size_t)l];
         const float *qw = p, *qb = qw + dd, *kw = qb + d, *kb = kw + dd, *vw = kb + d, *vb = vw + dd;
         ly.qkv_w = add_mat(qw, dd); add_mat(kw, dd); add_mat(vw, dd);                                   // fused [3d][d]
         {   // (one vector: the three biases contiguous)
@@ -588,7 +588,7 @@ int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan)
         const bool pre = m.stable_ln != 0;
         if (!pre) ln(b.enc_ln_w, b.enc_ln_b, true);
         for (int l = 0; l < L; l++) {
-            const WhisperState::W2v::Layer &ly = b.layers[(size_t)l];
+            const EncoderLayerW &ly = b.layers[(size_t)l];
             if (pre) ln(ly.ln1_w, ly.ln1_b, false);
             fit &= w2v_gemm<EPI_QKV>(c, b.ln.as<op_t>(), d, 0, Wb + ly.qkv_w, M, 3 * d, d, Wf + ly.qkv_b, b.qk.as<op_t>(), 2 * d, 0, 1,
                               reinterpret_cast<const float *>(b.vt.as<op_t>()), T_pad, 2 * d, vt_sp);
@@ -727,4 +727,4 @@ int pce_selftest_w2v_posconv(pce_ctx *c, const float *x, int32_t n_win, int32_t 
     return PCE_OK;
 }
 
-} // extern "C"
+} // namespace PCE_BUILD_NS

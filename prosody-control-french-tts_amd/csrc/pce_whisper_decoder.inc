@@ -91,7 +91,7 @@ static void prefix_cross_out_mlp(pce_ctx *c, WhisperState *w, const PrefixRun &r
     launch_gemm<EPI_RESID_F32>(c, w->d_hidden.as<op_t>(), 4 * r.d, 0, r.Wb + ly.m2_w, (int)r.Mt, r.d, 4 * r.d, r.Wf + ly.m2_b, w->d_resid.as<float>(), r.d, 0, 1);
 }
 
-extern "C" {
+namespace PCE_BUILD_NS {
 
 int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, const float *weights, int64_t n_floats)
 {
@@ -365,21 +365,19 @@ int pce_whisper_align_shape(pce_ctx *c, int32_t clip, int32_t *n_rows, int32_t *
     return PCE_OK;
 }
 
-} // extern "C"
-
 // ---------------------------------------------------------------------------
 // Free-running decoding, one step: the text decoder over the sequences so far (cross K / V of every layer computed once
 // per encoded batch and kept; a prefix pass fills the self-attention K / V cache, a step that extends it by one token
 // runs that position alone), logits of the last position through the tied output projection, openai-whisper's logit
 // filters and greedy choice.  The loop over steps, the prompt and the stopping rule are host logic (Aligners/decoding.py).
 // ---------------------------------------------------------------------------
-extern "C" int pce_whisper_decode_step(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, int32_t sample_begin,
+int pce_whisper_decode_step(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, int32_t sample_begin,
                                        const pce_whisper_decode_rules *rules, const uint8_t *vocab_mask, int32_t *next_tokens,
                                        float *next_logprobs)
 {
     pce_whisper_decode_opts o{};
     o.sample_begin = nullptr; o.sample_begin_all = sample_begin; o.temperature = 0.f; o.probe_token = -1;
-    return pce_whisper_decode_step_ex(c, tokens, token_offsets, rules, vocab_mask, &o, next_tokens, next_logprobs, nullptr);
+    return PCE_BUILD_NS::pce_whisper_decode_step_ex(c, tokens, token_offsets, rules, vocab_mask, &o, next_tokens, next_logprobs, nullptr);
 }
 
 // launches of ONE incremental step (one new position per sequence) from the tables ct[8 n] (see k_step_advance) -- host-uploaded by
@@ -409,7 +407,7 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
         launch_layernorm<op_t>(c, w->g_c_resid.as<float>(), Wf + w_off, Wf + b_off, (int64_t)n, d, w->g_c_ln.as<op_t>());
     };
     // cross-attention from the encoder output (pce_xattn.inc): E once per layer instead of K and V^T
-    const bool absorb = c->xattn_absorb && xa_has_form(d, H) && w->g_qp.p && w->g_wkT.p;
+    const bool absorb = c->sw.xattn_absorb && xa_has_form(d, H) && w->g_qp.p && w->g_wkT.p;
     static const int env_wpc = getenv("PCE_XATTN_WPC") ? atoi(getenv("PCE_XATTN_WPC")) : 0;
     XaArgs xa{};
     xa.E = w->d_enc_bf16.as<op_t>(); xa.e_clip = (int64_t)W_CTX * d; xa.e_ld = d; xa.k_len = XL; xa.skip = ended;
@@ -429,7 +427,7 @@ static void decode_incremental_launches(pce_ctx *c, WhisperState *w, int n, cons
         //  and dropped: four dependent L2 round trips per wave, 17 us per launch against 11.8 + 5.5 for the two launches)
         cln(ly.ln1_w, ly.ln1_b);
         launch_gemm<EPI_BF16>(c, w->g_c_ln.as<op_t>(), d, 0, Wb + ly.qkv_w, n, 3 * d, d, Wf + ly.qkv_b, w->g_c_qkv.as<op_t>(), 3 * d, 0, 1);
-        if (c->self_rows && w->g_sv.p) {
+        if (c->sw.self_rows && w->g_sv.p) {
             // row-major K / V caches: the append is two coalesced row stores (the V^T image is not touched by incremental steps: only prefix runs,
             // which rewrite every position they attend to, read it)
             SelfAttn1Args sa{};
@@ -465,7 +463,7 @@ static int decode_incremental_reserve(pce_ctx *c, WhisperState *w, int n)
     }
     PCE_HIP(c, w->g_c_q.reserve(sizeof(op_t) * (size_t)(n + 128) * d + 4096));
     PCE_HIP(c, w->g_c_hidden.reserve(sizeof(op_t) * (size_t)(n + 128) * 4 * d + 4096));
-    if (c->xattn_absorb) {
+    if (c->sw.xattn_absorb) {
         const size_t before = w->g_qp.cap, R = (size_t)xa_rows(w->tdims.n_head);   // R rows of heads per clip (pce_xattn.inc)
         PCE_HIP(c, w->g_qp.reserve(sizeof(op_t) * 2 * (size_t)n * R * d + 256));
         if (w->g_qp.cap != before) PCE_HIP(c, hipMemsetAsync(w->g_qp.p, 0, w->g_qp.cap, c->stream));               // (rows >= heads feed MFMA rows nobody reads: finite all the same)
@@ -481,7 +479,7 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
                               const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, bool want_probe);
 
 // the ids temperature sampling keys its noise by, one per clip of the encoded batch; they last until the next pce_whisper_encode_run
-extern "C" int pce_whisper_sample_keys(pce_ctx *c, const int32_t *keys, int32_t n)
+int pce_whisper_sample_keys(pce_ctx *c, const int32_t *keys, int32_t n)
 {
     if (!c || n < 0 || (n > 0 && !keys)) return PCE_E_INVALID;
     WhisperState *w = ws_of(c);
@@ -496,7 +494,7 @@ extern "C" int pce_whisper_sample_keys(pce_ctx *c, const int32_t *keys, int32_t 
     return PCE_OK;
 }
 
-extern "C" int pce_whisper_decode_step_ex(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
+int pce_whisper_decode_step_ex(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
                                           const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, int32_t *next_tokens,
                                           float *next_logprobs, float *probe_prob)
 {
@@ -683,9 +681,9 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
 
 // ---------------------------------------------------------------------------
 // Language detection (openai-whisper decoding.py detect_language): the decoder over the one token <|startoftranscript|> per clip, then k_lang_probs
-// (pce_whisper_impl.inc) on the n_lang language rows of the tied embedding -- no output projection over the vocabulary, no k_decode_rules.
+// (pce_decode_rules.inc) on the n_lang language rows of the tied embedding -- no output projection over the vocabulary, no k_decode_rules.
 // ---------------------------------------------------------------------------
-extern "C" int pce_whisper_detect_language(pce_ctx *c, int32_t sot, int32_t lang_begin, int32_t n_lang, int32_t *ids, float *probs)
+int pce_whisper_detect_language(pce_ctx *c, int32_t sot, int32_t lang_begin, int32_t n_lang, int32_t *ids, float *probs)
 {
     if (!c) return PCE_E_INVALID;
     WhisperState *w = ws_of(c);
@@ -731,7 +729,7 @@ extern "C" int pce_whisper_detect_language(pce_ctx *c, int32_t sot, int32_t lang
 // Same kernels, same filters, same counter-based sampling keys (seed, clip, position): token for token what the host-driven loop
 // of Aligners/decoding.py produces (tests/test_gpu_aligner.py).
 // ---------------------------------------------------------------------------
-extern "C" int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
+int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const pce_whisper_decode_rules *rules,
                                        const uint8_t *vocab_mask, const pce_whisper_decode_opts *opts, int32_t max_new, int32_t check_every,
                                        int32_t *out_tokens, float *out_logprobs, int32_t *out_steps, float *probe_prob)
 {
@@ -820,3 +818,5 @@ extern "C" int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const 
     w->g_cache_len = -1;                                         // the host's copy of the cached prefixes is stale: the next host-driven step re-runs its prefixes
     return PCE_OK;
 }
+
+} // namespace PCE_BUILD_NS

@@ -2,5 +2,5 @@
 // openai-whisper's fp16=True default, Code/Aligners/use_whisper_timestamped.py:163).
 #define PCE_OP_T _Float16
 #define PCE_OP_INDEX 1
-#define PCE_WFN(name) name##_f16
+#define PCE_BUILD_NS pce_f16
 #include "pce_whisper_impl.inc"

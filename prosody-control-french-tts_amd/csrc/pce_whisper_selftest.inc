@@ -41,8 +41,6 @@ static int selftest_add_layernorm(pce_ctx *c, int64_t rows, int d, const void *x
 }
 } // namespace
 
-extern "C" {
-
 // V rows of clip c at rows k_row0[c] .. + k_len[c] of [.][heads * 64] -> the V^T image the attention kernels read: [clip][head * 64 + d][sp] (the
 // rest of the key axis keeps its zeros)
 static __global__ void k_selftest_vt(const op_t *__restrict__ v, const int *__restrict__ k_row0, const int *__restrict__ k_len, int hd, int sp,
@@ -55,6 +53,8 @@ static __global__ void k_selftest_vt(const op_t *__restrict__ v, const int *__re
         vt[((int64_t)clip * hd + col) * sp + t] = v[(int64_t)k_row0[clip] * hd + i];
     }
 }
+
+namespace PCE_BUILD_NS {
 
 // Self-test hooks of the attention kernel through launch_attention (see pce.h)
 int pce_selftest_attention_ragged(pce_ctx *c, const uint16_t *q, const uint16_t *k, const uint16_t *v, int32_t clips, int32_t heads, const int32_t *q_len,
@@ -107,7 +107,7 @@ int pce_selftest_attention(pce_ctx *c, const uint16_t *q, const uint16_t *k, con
     if (!c || !out || clips <= 0 || heads <= 0 || q_len <= 0 || k_len <= 0) return PCE_E_INVALID;
     const std::vector<int32_t> ql((size_t)clips, q_len), kl((size_t)clips, k_len);
     std::fill(out, out + (size_t)clips * q_len * heads * 64, (uint16_t)0);
-    return pce_selftest_attention_ragged(c, q, k, v, clips, heads, ql.data(), kl.data(), causal, mode, out, (int64_t)clips * q_len, fell_back);
+    return PCE_BUILD_NS::pce_selftest_attention_ragged(c, q, k, v, clips, heads, ql.data(), kl.data(), causal, mode, out, (int64_t)clips * q_len, fell_back);
 }
 
 // Self-test hook of the single-query attention kernels of an incremental decoding step, through the launches the step makes (see pce.h)
@@ -573,4 +573,4 @@ int pce_selftest_layernorm(pce_ctx *c, int32_t form, int32_t rows, int32_t d, co
     return selftest_add_layernorm<op_t, op_t, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
 }
 
-} // extern "C"
+} // namespace PCE_BUILD_NS

@@ -191,23 +191,137 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "w2v_forward", "k_w2v_wave", "k_w2v_posconv", "k_w2v_tail",
               "k_ctc", "k_ctc_general", "k_ctc_trace", "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
-# every symbol include/pce.h declares
-EXPORTS = ["pce_create", "pce_destroy", "pce_last_error", "pce_sync", "pce_api_version", "pce_api_minor", "pce_device_info",
-           "pce_upload_pcm_s16", "pce_bind_pcm_s16_device", "pce_num_clips",
-           "pce_energy_run", "pce_energy_fetch", "pce_lufs_set_meter_rate", "pce_lufs_run", "pce_lufs_fetch",
-           "pce_frame_energy_run", "pce_frame_energy_shape", "pce_frame_energy_fetch", "pce_pyin_run", "pce_pyin_shape", "pce_pyin_fetch",
-           "pce_crepe_load", "pce_crepe_run", "pce_crepe_shape", "pce_crepe_fetch", "pce_selftest_crepe_layer", "pce_selftest_crepe_decode",
-           "pce_pitch_plan", "pce_pitch_run", "pce_pitch_set_refine", "pce_pitch_fetch",
-           "pce_intensity_plan", "pce_intensity_run", "pce_intensity_fetch",
-           "pce_silence_run", "pce_silence_shape", "pce_silence_fetch",
-           "pce_stft_db_run", "pce_stft_db_shape", "pce_stft_db_fetch", "pce_stft_db_device",
-           "pce_resample_run", "pce_download_pcm_s16",
-           "pce_dtw", "pce_dtw_series", "pce_ctc_align", "pce_nw_align", "pce_levenshtein", "pce_seqmatch", "pce_seqmatch_align", "pce_whisper_decoder_load", "pce_whisper_align_run", "pce_whisper_align_shape", "pce_whisper_align_fetch", "pce_whisper_align_paths_enqueue", "pce_whisper_align_paths_wait", "pce_whisper_sample_keys", "pce_whisper_decode_step", "pce_whisper_decode_step_ex", "pce_whisper_decode_loop", "pce_whisper_detect_language", "pce_whisper_set_operands", "pce_whisper_get_operands", "pce_selftest_xattn", "pce_selftest_gemm_tiled", "pce_selftest_layernorm",
-           "pce_logmel_run", "pce_logmel_run_at", "pce_logmel_fetch", "pce_selftest_logmel_image", "pce_whisper_load", "pce_whisper_encode_run", "pce_selftest_gemm", "pce_selftest_gemm_resid", "pce_selftest_attention", "pce_selftest_attention_ragged", "pce_selftest_attn1", "pce_selftest_align_matrix", "pce_selftest_decode_rules", "pce_whisper_encode_fetch",
-           "pce_stats_enqueue", "pce_stats_wait", "pce_bert_load", "pce_bert_run", "pce_bert_fetch",
-           "pce_w2v_check", "pce_w2v_load", "pce_w2v_run", "pce_w2v_shape", "pce_w2v_fetch", "pce_w2v_device", "pce_w2v_window_plan",
-           "pce_selftest_w2v_wave", "pce_selftest_w2v_lngelu", "pce_selftest_w2v_posconv",
-           "pce_profile_enable", "pce_profile_reset", "pce_profile_get", "pce_profile_get_work", "pce_kernel_name"]
+# every symbol include/pce.h declares (tests/test_abi_and_shard.py), in the header's order and under its section titles: name -> argtypes, or
+# (argtypes, restype) where the function does not return int
+_vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+SIGNATURES = {
+    # context
+    "pce_create": ([C.c_int, _vp, C.c_char_p, C.c_size_t], _vp),
+    "pce_destroy": ([_vp], None),
+    "pce_last_error": ([_vp], C.c_char_p),
+    "pce_sync": [_vp],
+    "pce_api_version": [],
+    "pce_api_minor": [],
+    "pce_device_info": [_vp, C.c_char_p, C.c_size_t, C.POINTER(_i32), C.POINTER(_i64)],
+    # batch residency
+    "pce_upload_pcm_s16": [_vp, _vp, _vp, _i32, _i32],
+    "pce_bind_pcm_s16_device": [_vp, _vp, _vp, _i32, _i32],
+    "pce_num_clips": [_vp],
+    # sample-rate conversion of the resident batch
+    "pce_resample_run": [_vp, _i32, _i32, _vp, _i32, _i64],
+    "pce_download_pcm_s16": [_vp, _vp, _vp, C.POINTER(_i32)],
+    # frame-level short-time energy
+    "pce_frame_energy_run": [_vp, _i32, _i32, _i32],
+    "pce_frame_energy_shape": [_vp, _i32, C.POINTER(_i64)],
+    "pce_frame_energy_fetch": [_vp, _i32, _vp, _vp],
+    # R3 / R7: short-time energy, peak, silence gate
+    "pce_energy_run": [_vp, _vp, _i32, _i32],
+    "pce_energy_fetch": [_vp, _vp],
+    # R4: BS.1770 integrated loudness
+    "pce_lufs_set_meter_rate": [_vp, _i32],
+    "pce_lufs_run": [_vp, _vp, _i32],
+    "pce_lufs_fetch": [_vp, _vp, _vp],
+    # R1 / R2: Praat autocorrelation pitch
+    "pce_pitch_plan": [_vp, C.POINTER(PitchParams), _vp, _i32, _vp, _vp],
+    "pce_pitch_run": [_vp, C.POINTER(PitchParams), _vp, _i32],
+    "pce_pitch_set_refine": [_vp, _i32],
+    "pce_pitch_fetch": [_vp, _vp, _vp, _vp],
+    # Praat intensity
+    "pce_intensity_plan": [_vp, C.POINTER(IntensityParams), _vp, _i32, _vp, _vp],
+    "pce_intensity_run": [_vp, C.POINTER(IntensityParams), _vp, _i32, _vp, _i32],
+    "pce_intensity_fetch": [_vp, _vp, _vp],
+    # silence detection
+    "pce_silence_run": [_vp, C.POINTER(SilenceParams), _vp, _vp, _i32],
+    "pce_silence_shape": [_vp, _vp, _vp, _vp],
+    "pce_silence_fetch": [_vp, _vp],
+    # R10: STFT magnitude in dB
+    "pce_stft_db_run": [_vp, _i32, _i32],
+    "pce_stft_db_shape": [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)],
+    "pce_stft_db_fetch": [_vp, _i32, _vp],
+    "pce_stft_db_device": [_vp, C.POINTER(_vp), C.POINTER(_i64)],
+    # R10: probabilistic YIN
+    "pce_pyin_run": [_vp, _vp, _vp, _i64],
+    "pce_pyin_shape": [_vp, _i32, C.POINTER(_i64)],
+    "pce_pyin_fetch": [_vp, _i32, _vp, _vp, C.POINTER(_i32)],
+    # CREPE pitch tracking
+    "pce_crepe_load": [_vp, C.POINTER(CrepeDims), _vp, _i64],
+    "pce_crepe_run": [_vp, C.POINTER(CrepePlan)],
+    "pce_crepe_shape": [_vp, _i32, C.POINTER(_i64)],
+    "pce_crepe_fetch": [_vp, _i32, _vp, _vp, _vp, _vp],
+    "pce_selftest_crepe_layer": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pce_selftest_crepe_decode": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    # R8: log-mel spectrogram + Whisper audio encoder
+    "pce_logmel_run": [_vp, _i32],
+    "pce_logmel_run_at": [_vp, _i32, _vp],
+    "pce_logmel_fetch": [_vp, _i32, _vp],
+    "pce_selftest_logmel_image": [_vp, _i32, _vp],
+    "pce_whisper_load": [_vp, C.POINTER(WhisperDims), _vp, _i64],
+    "pce_whisper_encode_run": [_vp],
+    "pce_selftest_gemm": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "pce_selftest_gemm_resid": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32],
+    "pce_selftest_attention": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "pce_selftest_attention_ragged": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp],
+    "pce_selftest_attn1": [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64],
+    "pce_selftest_align_matrix": [_vp, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _i64, _vp, _i64, _vp, _i64],
+    "pce_selftest_xattn": [_vp] * 11 + [_i32] * 5 + [_vp],
+    "pce_selftest_gemm_tiled": [_vp, _i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
+    "pce_selftest_layernorm": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.c_float, _i32, _vp, _vp, _vp],
+    "pce_whisper_encode_fetch": [_vp, _i32, _vp],
+    # R8: forced alignment of known text tokens
+    "pce_whisper_decoder_load": [_vp, C.POINTER(WhisperTextDims), _vp, _i64],
+    "pce_whisper_align_run": [_vp, _vp, _vp, _vp, _i32, _vp, _i32, C.c_float],
+    "pce_whisper_align_shape": [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)],
+    "pce_whisper_align_fetch": [_vp, _i32, _vp, _vp, C.POINTER(_i32), _vp],
+    "pce_whisper_align_paths_enqueue": [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)],
+    "pce_whisper_align_paths_wait": [_vp, _i32, _vp, _vp, _vp],
+    # R8: free-running decoding, one step
+    "pce_whisper_decode_step": [_vp, _vp, _vp, _i32, C.POINTER(WhisperDecodeRules), _vp, _vp, _vp],
+    "pce_whisper_decode_step_ex": [_vp, _vp, _vp, C.POINTER(WhisperDecodeRules), _vp, C.POINTER(WhisperDecodeOpts), _vp, _vp, _vp],
+    "pce_whisper_sample_keys": [_vp, _vp, _i32],
+    "pce_selftest_decode_rules": [_vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(WhisperDecodeRules), _vp, _i64, C.c_float, C.c_uint32, C.c_uint32, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64],
+    "pce_whisper_set_operands": [_vp, _i32],
+    "pce_whisper_get_operands": [_vp],
+    "pce_whisper_decode_loop": [_vp, _vp, _vp, C.POINTER(WhisperDecodeRules), _vp, C.POINTER(WhisperDecodeOpts), _i32, _i32, _vp, _vp, _vp, _vp],
+    "pce_whisper_detect_language": [_vp, _i32, _i32, _i32, _vp, _vp],
+    # R8: dynamic time warping
+    "pce_dtw": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
+    # DTW of pairs of series
+    "pce_dtw_series": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
+    # CTC forced alignment
+    "pce_ctc_align": [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # batched Needleman-Wunsch word alignment
+    "pce_nw_align": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    # batched Levenshtein distance
+    "pce_levenshtein": [_vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    # batched difflib.SequenceMatcher and the fuzzy alignment of "Compare Breaks"
+    "pce_seqmatch": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp],
+    "pce_seqmatch_align": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.POINTER(_i32)],
+    # break-prediction token classifier
+    "pce_bert_load": [_vp, C.POINTER(BertDims), _vp, _i64],
+    "pce_bert_run": [_vp, _vp, _vp, _i32],
+    "pce_bert_fetch": [_vp, _i32, _vp, _vp],
+    # wav2vec2 / MMS CTC acoustic model: the emissions of the forced alignment
+    "pce_w2v_load": [_vp, C.POINTER(W2vDims), _vp, _i64],
+    "pce_w2v_check": [C.POINTER(W2vDims), _i64, C.c_char_p, C.c_size_t],
+    "pce_w2v_run": [_vp, C.POINTER(W2vPlan)],
+    "pce_w2v_shape": [_vp, _i32, C.POINTER(_i64), C.POINTER(_i32)],
+    "pce_w2v_fetch": [_vp, _i32, _vp],
+    "pce_w2v_device": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32)],
+    "pce_w2v_window_plan": [_i64, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)],
+    "pce_selftest_w2v_wave": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "pce_selftest_w2v_lngelu": [_vp, _vp, _i32, _i32, _vp, _vp, C.c_float, _i32, _vp],
+    "pce_selftest_w2v_posconv": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    # asynchronous statistics fetch
+    "pce_stats_enqueue": [_vp, _i32],
+    "pce_stats_wait": [_vp, _i32, _vp, _vp, _vp, _vp],
+    # measurement
+    "pce_profile_enable": [_vp, C.c_int],
+    "pce_profile_reset": [_vp],
+    "pce_profile_get": [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(_i64)],
+    "pce_profile_get_work": [_vp, C.c_int, C.POINTER(C.c_double)],
+    "pce_kernel_name": ([C.c_int], C.c_char_p),
+}
+EXPORTS = list(SIGNATURES)
 
 
 def load_library() -> C.CDLL:
@@ -216,112 +330,9 @@ def load_library() -> C.CDLL:
         raise PceError(f"{path} is missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950); "
                        "this engine has no CPU fallback")
     lib = C.CDLL(path)
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    lib.pce_create.argtypes = [C.c_int, vp, C.c_char_p, C.c_size_t]; lib.pce_create.restype = vp
-    lib.pce_destroy.argtypes = [vp]; lib.pce_destroy.restype = None
-    lib.pce_last_error.argtypes = [vp]; lib.pce_last_error.restype = C.c_char_p
-    lib.pce_sync.argtypes = [vp]
-    lib.pce_api_version.argtypes = []
-    lib.pce_api_minor.argtypes = []
-    lib.pce_device_info.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(i32), C.POINTER(i64)]
-    lib.pce_upload_pcm_s16.argtypes = [vp, vp, vp, i32, i32]
-    lib.pce_bind_pcm_s16_device.argtypes = [vp, vp, vp, i32, i32]
-    lib.pce_num_clips.argtypes = [vp]
-    lib.pce_energy_run.argtypes = [vp, vp, i32, i32]
-    lib.pce_energy_fetch.argtypes = [vp, vp]
-    lib.pce_lufs_set_meter_rate.argtypes = [vp, i32]
-    lib.pce_pitch_set_refine.argtypes = [vp, i32]
-    lib.pce_lufs_run.argtypes = [vp, vp, i32]
-    lib.pce_frame_energy_run.argtypes = [vp, i32, i32, i32]
-    lib.pce_pyin_run.argtypes = [vp, vp, vp, i64]
-    lib.pce_pyin_shape.argtypes = [vp, i32, C.POINTER(i64)]
-    lib.pce_pyin_fetch.argtypes = [vp, i32, vp, vp, C.POINTER(i32)]
-    lib.pce_crepe_load.argtypes = [vp, C.POINTER(CrepeDims), vp, i64]
-    lib.pce_crepe_run.argtypes = [vp, C.POINTER(CrepePlan)]
-    lib.pce_crepe_shape.argtypes = [vp, i32, C.POINTER(i64)]
-    lib.pce_crepe_fetch.argtypes = [vp, i32, vp, vp, vp, vp]
-    lib.pce_selftest_crepe_layer.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.pce_selftest_crepe_decode.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.pce_frame_energy_shape.argtypes = [vp, i32, C.POINTER(i64)]
-    lib.pce_frame_energy_fetch.argtypes = [vp, i32, vp, vp]
-    lib.pce_lufs_fetch.argtypes = [vp, vp, vp]
-    lib.pce_pitch_plan.argtypes = [vp, C.POINTER(PitchParams), vp, i32, vp, vp]
-    lib.pce_pitch_run.argtypes = [vp, C.POINTER(PitchParams), vp, i32]
-    lib.pce_pitch_fetch.argtypes = [vp, vp, vp, vp]
-    lib.pce_intensity_plan.argtypes = [vp, C.POINTER(IntensityParams), vp, i32, vp, vp]
-    lib.pce_intensity_run.argtypes = [vp, C.POINTER(IntensityParams), vp, i32, vp, i32]
-    lib.pce_intensity_fetch.argtypes = [vp, vp, vp]
-    lib.pce_silence_run.argtypes = [vp, C.POINTER(SilenceParams), vp, vp, i32]
-    lib.pce_silence_shape.argtypes = [vp, vp, vp, vp]
-    lib.pce_silence_fetch.argtypes = [vp, vp]
-    lib.pce_stats_enqueue.argtypes = [vp, i32]
-    lib.pce_nw_align.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.pce_levenshtein.argtypes = [vp, vp, vp, vp, vp, i32, vp]
-    lib.pce_seqmatch.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, i64, i32, vp]
-    lib.pce_seqmatch_align.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, C.POINTER(i32)]
-    lib.pce_stats_wait.argtypes = [vp, i32, vp, vp, vp, vp]
-    lib.pce_stft_db_run.argtypes = [vp, i32, i32]
-    lib.pce_stft_db_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.pce_stft_db_fetch.argtypes = [vp, i32, vp]
-    lib.pce_stft_db_device.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
-    lib.pce_resample_run.argtypes = [vp, i32, i32, vp, i32, i64]
-    lib.pce_download_pcm_s16.argtypes = [vp, vp, vp, C.POINTER(i32)]
-    lib.pce_dtw.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
-    lib.pce_dtw_series.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-    lib.pce_ctc_align.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.pce_whisper_decoder_load.argtypes = [vp, C.POINTER(WhisperTextDims), vp, i64]
-    lib.pce_whisper_align_run.argtypes = [vp, vp, vp, vp, i32, vp, i32, C.c_float]
-    lib.pce_whisper_align_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.pce_whisper_decode_step.argtypes = [vp, vp, vp, i32, C.POINTER(WhisperDecodeRules), vp, vp, vp]
-    lib.pce_whisper_decode_step_ex.argtypes = [vp, vp, vp, C.POINTER(WhisperDecodeRules), vp, C.POINTER(WhisperDecodeOpts), vp, vp, vp]
-    lib.pce_whisper_set_operands.argtypes = [vp, i32]
-    lib.pce_whisper_get_operands.argtypes = [vp]
-    lib.pce_whisper_decode_loop.argtypes = [vp, vp, vp, C.POINTER(WhisperDecodeRules), vp, C.POINTER(WhisperDecodeOpts), i32, i32, vp, vp, vp, vp]
-    lib.pce_whisper_align_fetch.argtypes = [vp, i32, vp, vp, C.POINTER(i32), vp]
-    lib.pce_whisper_align_paths_enqueue.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.pce_whisper_align_paths_wait.argtypes = [vp, i32, vp, vp, vp]
-    lib.pce_whisper_sample_keys.argtypes = [vp, vp, i32]
-    lib.pce_whisper_detect_language.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.pce_bert_load.argtypes = [vp, C.POINTER(BertDims), vp, i64]
-    lib.pce_bert_run.argtypes = [vp, vp, vp, i32]
-    lib.pce_bert_fetch.argtypes = [vp, i32, vp, vp]
-    lib.pce_w2v_check.argtypes = [C.POINTER(W2vDims), i64, C.c_char_p, C.c_size_t]
-    lib.pce_w2v_load.argtypes = [vp, C.POINTER(W2vDims), vp, i64]
-    lib.pce_w2v_run.argtypes = [vp, C.POINTER(W2vPlan)]
-    lib.pce_w2v_shape.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i32)]
-    lib.pce_w2v_fetch.argtypes = [vp, i32, vp]
-    lib.pce_w2v_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i32)]
-    lib.pce_w2v_window_plan.argtypes = [i64, i32, i32, C.POINTER(i64), C.POINTER(i64)]
-    lib.pce_selftest_w2v_wave.argtypes = [vp, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.pce_selftest_w2v_lngelu.argtypes = [vp, vp, i32, i32, vp, vp, C.c_float, i32, vp]
-    lib.pce_selftest_w2v_posconv.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.pce_logmel_run.argtypes = [vp, i32]
-    lib.pce_logmel_run_at.argtypes = [vp, i32, vp]
-    lib.pce_logmel_fetch.argtypes = [vp, i32, vp]
-    lib.pce_selftest_logmel_image.argtypes = [vp, i32, vp]
-    lib.pce_whisper_load.argtypes = [vp, C.POINTER(WhisperDims), vp, i64]
-    lib.pce_whisper_encode_run.argtypes = [vp]
-    lib.pce_selftest_gemm.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    lib.pce_selftest_gemm_resid.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32]
-    lib.pce_selftest_attention.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
-    lib.pce_selftest_attention_ragged.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, i64, vp]
-    lib.pce_selftest_attn1.argtypes = [vp, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, i32, vp, i64]
-    lib.pce_selftest_align_matrix.argtypes = [vp, i32, i32, vp, i64, vp, i64, i32, vp, vp, vp, i32, i32, i32, i32, C.c_float, vp, i64, vp, i64, vp, i64]
-    lib.pce_selftest_decode_rules.argtypes = [vp, i32, i32, i32, i32, vp, i64, vp, vp, i32, i32, vp, i32, C.POINTER(WhisperDecodeRules), vp, i64, C.c_float, C.c_uint32,
-                                              C.c_uint32, i32, vp, i32, vp, vp, vp, i64, vp, i64, vp, i64]
-    lib.pce_selftest_xattn.argtypes = [vp] * 11 + [i32] * 5 + [vp]
-    lib.pce_selftest_gemm_tiled.argtypes = [vp, i32, i32, vp, i64, i64, i64, i32, vp, vp, i32, i32, i32, vp, i64, i64, i64, vp, i32, i32, i32, i32, vp, i64, vp]
-    lib.pce_selftest_layernorm.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp]
-    lib.pce_whisper_encode_fetch.argtypes = [vp, i32, vp]
-    lib.pce_profile_enable.argtypes = [vp, C.c_int]
-    lib.pce_profile_reset.argtypes = [vp]
-    lib.pce_profile_get.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(i64)]
-    lib.pce_profile_get_work.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
-    lib.pce_kernel_name.argtypes = [C.c_int]; lib.pce_kernel_name.restype = C.c_char_p
-    for name in EXPORTS:
+    for name, sig in SIGNATURES.items():
         fn = getattr(lib, name)
-        if fn.restype is C.c_int and name not in ("pce_create",):
-            fn.restype = C.c_int
+        fn.argtypes, fn.restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
     return lib
 
 

@@ -6,7 +6,7 @@ this file).  Each stage takes the previous stage's array, so a kernel can be che
     norm   (w - mean_t) / std_t, the population std over the tokens t < T
     cost   reflect padding and the median of ``width`` along s (skipped when F <= width // 2), the mean over heads, rows [sot_len, T - 1), negated
 
-Written from the definitions, independently of csrc/pce_whisper_impl.inc: one matrix product per head, NumPy's own (pairwise) sums, np.pad's reflect
+Written from the definitions, independently of csrc/pce_align_kernels.inc: one matrix product per head, NumPy's own (pairwise) sums, np.pad's reflect
 mode, a full sort per window.  ``soft`` also returns sum_e |q_e k_e| * scale per score, the magnitude an fp32 dot product's rounding is relative to,
 and the scores.
 

@@ -1,7 +1,7 @@
 """Float64 NumPy restatement of scaled dot-product attention over 64-wide heads (the checker of the attention kernels; no test in this file).
 
 Per (clip, head): out = softmax(q k^T / 8) v over the first ``n_keys`` keys, with the causal mask (key j visible to query i only if j <= i) on
-request.  Written from the definition, independently of csrc/pce_whisper_impl.inc: the scores of a head are one matrix product, the softmax
+request.  Written from the definition, independently of csrc/pce_attention.inc: the scores of a head are one matrix product, the softmax
 subtracts the row maximum, NumPy's own (pairwise) sums.
 
 Beside the output it returns A = sum_t p_t |v_t| per output element: every rounding of a kernel's weighted sum is relative to that magnitude, not to

@@ -143,7 +143,7 @@ def test_tiled_gemms_at_model_widths(engine, ops, d):
 
 
 def test_bias_and_fp32_epilogues_are_identical_across_kernels_and_row_counts(engine, ops):
-    """pce_whisper_impl.inc claims the bias and fp32-accumulate epilogues give the same bits on the few-row, 128 x 256 and 128 x 128 kernels (the
+    """pce_whisper_impl.inc (gemm_choose) claims the bias and fp32-accumulate epilogues give the same bits on the few-row, 128 x 256 and 128 x 128 kernels (the
     sums run in the same order), and EPI_F32 the same bits on 128 x 256 and the four-stage kernel; and a row's bits never depend on M."""
     M, N, K = 300, 1536, 768
     p = Prob(ops, M, N, K, seed=5)

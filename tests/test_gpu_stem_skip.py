@@ -1,4 +1,4 @@
-"""The conv stem leaves out the row tiles of the 30 s window's zero padding (csrc/pce_whisper_impl.inc: GemmSkip, k_stem_fill).
+"""The conv stem leaves out the row tiles of the 30 s window's zero padding (csrc/pce_whisper_impl.inc: GemmSkip; csrc/pce_gemm_tiled.inc: k_stem_fill).
 
 Everything here is bit for bit: a surviving row keeps its own K loop, a skipped conv2 row is the repeated row's accumulators through conv2's own
 epilogue expression, so the encoder output of a default context must be the bytes of a context created with PCE_STEM_SKIP=0 (two full launches).
