@@ -16,45 +16,13 @@ import torch
 from oracle import bert_oracle as BO
 from oracle import whisper_oracle as WO
 from prosody_control_french_tts_amd import PceError, bert_weights as BW, synth, whisper_weights as WW
+from tests.gemm_restatement import U, _dt, _gelu, _gelu_err, _half_ulp, bits, r16, val
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
 EPI_BF16, EPI_GELU, EPI_GELU_POS, EPI_RESID, EPI_QKV, EPI_F32 = range(6)
 AUTO, SKINNY, WIDE, T128, T128_DEEP = range(5)
 torch.set_num_threads(min(16, torch.get_num_threads()))
-
-
-def _dt(ops):
-    return getattr(torch, ops["torch"])
-
-
-def _half_ulp(ops):
-    return 2.0 ** -8 if ops["torch"] == "bfloat16" else 2.0 ** -11
-
-
-def bits(x, ops):
-    """float array -> uint16 bit patterns of the operand type (round to nearest even)"""
-    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(_dt(ops)).view(torch.int16).numpy().view(np.uint16)
-
-
-def val(u, ops):
-    """uint16 bit patterns -> float64 values"""
-    return torch.from_numpy(np.ascontiguousarray(u).view(np.int16)).view(_dt(ops)).double().numpy()
-
-
-def r16(x, ops):
-    """fp32 values rounded to the operand type and back (what the kernels' (op_t) conversion does)"""
-    return torch.from_numpy(np.asarray(x, dtype=np.float32)).to(_dt(ops)).float().numpy()
-
-
-def _gelu(x):
-    from scipy.special import erf
-    return 0.5 * x * (1.0 + erf(x / np.sqrt(2.0)))
-
-
-def _gelu_err(pre, pre_err):
-    return 1.13 * pre_err + (0.75e-7 + 16 * U) * np.abs(pre)
 
 
 def _check16(got_bits, want, err, ops, what):
