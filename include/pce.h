@@ -70,9 +70,11 @@ extern "C" {
  * front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by four (pce_kernel_name follows);
  * 17 = pce_selftest_decode_rules (the kernels that turn a decoding step's logits into tokens and carry them into the loop's tables, on host arrays
  * through the decoding calls' own launches);
- * 18 = pce_selftest_logmel_image (the 16-bit time-major log-mel image the conv stem reads, copied out as the last run left it). */
+ * 18 = pce_selftest_logmel_image (the 16-bit time-major log-mel image the conv stem reads, copied out as the last run left it);
+ * 19 = pce_selftest_xattn_stages (pce_selftest_xattn with the skip list and the buffers between its three kernels copied out: Q' as hi + lo, the nodes' U
+ * and (m, l)). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 18
+#define PCE_API_MINOR 19
 
 typedef struct pce_ctx pce_ctx;
 
@@ -454,6 +456,25 @@ int pce_selftest_align_matrix(pce_ctx *ctx, int32_t n, int32_t heads, const uint
 int pce_selftest_xattn(pce_ctx *ctx, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,
                        const uint16_t *wv, const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads,
                        int32_t workgroups_per_clip, uint16_t *out);
+/* pce_selftest_xattn stage by stage: the same launch (k_xq_fused -> k_xattn_absorbed -> k_uv_absorb through the product's launch code), with the list of
+ * ended clips and the buffers the launch writes between its kernels copied out.  Operands as pce_selftest_xattn; E holds e_elems >= n k_cap d elements.
+ *   skip [n] (may be NULL): a clip with skip != 0 is left alone by all three kernels.
+ *   out [n][d] (out_elems >= n d), 16-bit patterns.
+ *   qp_hi, qp_lo [n][R][d] (qp_elems >= n R d each), R = heads rounded up to 16: Q'_h = (log2 e / 8) q_h Wk_h as a hi + lo pair of the operand type; rows
+ *           >= heads are never written.
+ *   u_part [n][nodes][R][d] fp32 and ml_part [n][nodes][R][2] fp32 (u_elems / ml_elems: at least that many): per node of the merge tree, over its frames t,
+ *           U = sum_t 2^(s_t - m) E[t], the reference m and l = sum_t 2^(s_t - m), s_t = Q' . E[t].  *nodes_out (may be NULL) receives nodes: 4 where the
+ *           launch wrote the four leaves (leaf i = tiles [i per, (i + 1) per) of the ceil(k_len / 16) 16-frame tiles, per = ceil(tiles / 4); an empty
+ *           leaf is m = -1e30, l = 0, U = 0), 2 where it wrote the pair nodes L0 + L1 and L2 + L3 (d <= 768 with 1 or 2 workgroups per clip).  Rows >= heads
+ *           are never written.  Arrays sized for 4 nodes always suffice; only the first n nodes R d (n nodes R 2) elements are used.
+ * qp_hi / qp_lo and u_part / ml_part may be NULL in pairs (not copied out).  out, qp_hi, qp_lo, u_part and ml_part are read and written back whole (the
+ * used part): the caller's values are uploaded first, and what no launch writes keeps them.  PCE_E_INVALID, before anything is launched, for what
+ * pce_selftest_xattn refuses and for arrays shorter than the shape needs.  pce_selftest_xattn is this call with skip = NULL, a zeroed out and no stage
+ * outputs.  Since minor 19. */
+int pce_selftest_xattn_stages(pce_ctx *ctx, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,
+                              const uint16_t *wv, const float *bv, const uint16_t *E, int64_t e_elems, const int32_t *k_len, const int32_t *skip, int32_t n,
+                              int32_t k_cap, int32_t d, int32_t heads, int32_t workgroups_per_clip, uint16_t *out, int64_t out_elems, uint16_t *qp_hi,
+                              uint16_t *qp_lo, int64_t qp_elems, float *u_part, int64_t u_elems, float *ml_part, int64_t ml_elems, int32_t *nodes_out);
 /* Self-test of the tiled / few-row GEMM kernels the convolutions, the teacher-forced decoder, the decoding steps, BERT and the vocabulary logits run
  * on, through the product's own launch code: C = epilogue(A B^T + bias) for `batch` problems, A [batch] rows of K at pitch lda (a_batch apart; rows may
  * overlap: lda < K), B [N][K] and A as 16-bit patterns of the context's operand type, bias [N] fp32 (may be NULL).  epilogue 0: bias, 16-bit C;

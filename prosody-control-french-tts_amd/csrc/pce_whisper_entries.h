@@ -55,6 +55,13 @@
       (pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk, const uint16_t *wv, \
        const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads, int32_t workgroups_per_clip, uint16_t *out), \
       (c, resid, ln_w, ln_b, wq, bq, wk, wv, bv, E, k_len, n, k_cap, d, heads, workgroups_per_clip, out)) \
+    X(pce_selftest_xattn_stages, \
+      (pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk, const uint16_t *wv, \
+       const float *bv, const uint16_t *E, int64_t e_elems, const int32_t *k_len, const int32_t *skip, int32_t n, int32_t k_cap, int32_t d, int32_t heads, \
+       int32_t workgroups_per_clip, uint16_t *out, int64_t out_elems, uint16_t *qp_hi, uint16_t *qp_lo, int64_t qp_elems, float *u_part, int64_t u_elems, \
+       float *ml_part, int64_t ml_elems, int32_t *nodes_out), \
+      (c, resid, ln_w, ln_b, wq, bq, wk, wv, bv, E, e_elems, k_len, skip, n, k_cap, d, heads, workgroups_per_clip, out, out_elems, qp_hi, qp_lo, qp_elems, \
+       u_part, u_elems, ml_part, ml_elems, nodes_out)) \
     X(pce_selftest_gemm_tiled, \
       (pce_ctx *c, int32_t kernel, int32_t epilogue, const uint16_t *A, int64_t a_len, int64_t lda, int64_t a_batch, int32_t batch, const uint16_t *B, \
        const float *bias, int32_t M, int32_t N, int32_t K, void *C, int64_t c_len, int64_t ldc, int64_t c_batch, const float *pos, int32_t pos_T, \

@@ -330,42 +330,79 @@ int pce_selftest_decode_rules(pce_ctx *c, int32_t form, int32_t n, int32_t n_voc
 
 // Self-test hook of the encoder-output cross-attention of an incremental decoding step (pce_xattn.inc): k_xq_fused -> k_xattn_absorbed -> k_uv_absorb of ONE
 // layer on host arrays, with the number of workgroups per clip forced (0: what the batch size selects).  See include/pce.h.
-int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,
-                       const uint16_t *wv, const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads,
-                       int32_t workgroups_per_clip, uint16_t *out)
+// pce_selftest_xattn_stages adds the skip list and copies out what the launch leaves between its kernels: Q' (hi | lo), the nodes' U and (m, l).  Every DevBuf
+// frees itself on the early returns of PCE_HIP (pce_internal.h).
+int pce_selftest_xattn_stages(pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,
+                              const uint16_t *wv, const float *bv, const uint16_t *E, int64_t e_elems, const int32_t *k_len, const int32_t *skip, int32_t n,
+                              int32_t k_cap, int32_t d, int32_t heads, int32_t workgroups_per_clip, uint16_t *out, int64_t out_elems, uint16_t *qp_hi,
+                              uint16_t *qp_lo, int64_t qp_elems, float *u_part, int64_t u_elems, float *ml_part, int64_t ml_elems, int32_t *nodes_out)
 {
     if (!c || !resid || !ln_w || !ln_b || !wq || !bq || !wk || !wv || !bv || !E || !k_len || !out || n <= 0 || k_cap <= 0) return PCE_E_INVALID;
     if (!xa_has_form(d, heads))
         return pce_fail(c, PCE_E_INVALID, "selftest xattn: d = %d with %d heads is not a width the encoder-output form is built for", d, heads);
     if (!(workgroups_per_clip == 0 || workgroups_per_clip == 1 || workgroups_per_clip == 2 || workgroups_per_clip == 4)) return PCE_E_INVALID;
     for (int i = 0; i < n; i++) if (k_len[i] <= 0 || k_len[i] > k_cap) return pce_fail(c, PCE_E_INVALID, "selftest xattn: clip %d has %d frames of %d", i, k_len[i], k_cap);
+    const size_t dd = (size_t)d * d, ne = (size_t)n * k_cap * d;
+    const size_t R = (size_t)xa_rows(heads);
+    const int nsplit = xa_split(n, workgroups_per_clip);
+    // the nodes xattn_launch_d will write: the pair form (two) where the width has it and a workgroup owns both leaves of a pair, else the four leaves
+    const int nodes = (d <= 768 && nsplit <= XA_LEAVES / 2) ? XA_LEAVES / 2 : XA_LEAVES;
+    const size_t nqp = (size_t)n * R * d, nup = (size_t)n * nodes * R * d, nml = (size_t)n * nodes * R * 2;
+    if ((qp_hi != nullptr) != (qp_lo != nullptr) || (u_part != nullptr) != (ml_part != nullptr)) return PCE_E_INVALID;
+    if (e_elems < (int64_t)ne || out_elems < (int64_t)n * d || (qp_hi && qp_elems < (int64_t)nqp) || (u_part && (u_elems < (int64_t)nup || ml_elems < (int64_t)nml)))
+        return pce_fail(c, PCE_E_INVALID, "selftest xattn: needs E %lld, out %lld, qp_hi / qp_lo %lld, u_part %lld, ml_part %lld elements",
+                        (long long)ne, (long long)n * d, (long long)nqp, (long long)nup, (long long)nml);
     PCE_HIP(c, hipSetDevice(c->device));
     { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
-    const size_t dd = (size_t)d * d, ne = (size_t)n * k_cap * d;
     DevBuf dres, dlw, dlb, dwq, dbq, dwk, dwkT, dwv, dbv, dE, dkl, dqp, dup, dml, dout;
     PCE_HIP(c, dres.reserve(sizeof(float) * (size_t)n * d)); PCE_HIP(c, dlw.reserve(sizeof(float) * d)); PCE_HIP(c, dlb.reserve(sizeof(float) * d));
     PCE_HIP(c, dwq.reserve(2 * dd)); PCE_HIP(c, dbq.reserve(sizeof(float) * d)); PCE_HIP(c, dwk.reserve(2 * dd)); PCE_HIP(c, dwkT.reserve(2 * dd));
-    PCE_HIP(c, dwv.reserve(2 * dd)); PCE_HIP(c, dbv.reserve(sizeof(float) * d)); PCE_HIP(c, dE.reserve(2 * ne + 4096)); PCE_HIP(c, dkl.reserve(sizeof(int) * (size_t)n));
-    const size_t R = (size_t)xa_rows(heads);
-    PCE_HIP(c, dqp.reserve(2 * 2 * (size_t)n * R * d + 256)); PCE_HIP(c, dup.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
+    PCE_HIP(c, dwv.reserve(2 * dd)); PCE_HIP(c, dbv.reserve(sizeof(float) * d)); PCE_HIP(c, dE.reserve(2 * ne + 4096)); PCE_HIP(c, dkl.reserve(sizeof(int) * 2 * (size_t)n));
+    PCE_HIP(c, dqp.reserve(2 * 2 * nqp + 256)); PCE_HIP(c, dup.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
     PCE_HIP(c, dml.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * 2 + 256)); PCE_HIP(c, dout.reserve(2 * (size_t)n * d + 64));
     struct Up { void *dst; const void *src; size_t bytes; } ups[] = {
         {dres.p, resid, sizeof(float) * (size_t)n * d}, {dlw.p, ln_w, sizeof(float) * d}, {dlb.p, ln_b, sizeof(float) * d}, {dwq.p, wq, 2 * dd}, {dbq.p, bq, sizeof(float) * d},
-        {dwk.p, wk, 2 * dd}, {dwv.p, wv, 2 * dd}, {dbv.p, bv, sizeof(float) * d}, {dE.p, E, 2 * ne}, {dkl.p, k_len, sizeof(int) * (size_t)n}};
+        {dwk.p, wk, 2 * dd}, {dwv.p, wv, 2 * dd}, {dbv.p, bv, sizeof(float) * d}, {dE.p, E, 2 * ne}, {dkl.p, k_len, sizeof(int) * (size_t)n},
+        {dout.p, out, 2 * (size_t)n * d}};
     for (const Up &u : ups) PCE_HIP(c, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dqp.p, 0, dqp.cap, c->stream)); PCE_HIP(c, hipMemsetAsync(dout.p, 0, dout.cap, c->stream));
+    op_t *QH = dqp.as<op_t>(), *QL = QH + nqp;
+    if (qp_hi) {
+        PCE_HIP(c, hipMemcpyAsync(QH, qp_hi, 2 * nqp, hipMemcpyHostToDevice, c->stream)); PCE_HIP(c, hipMemcpyAsync(QL, qp_lo, 2 * nqp, hipMemcpyHostToDevice, c->stream));
+    } else PCE_HIP(c, hipMemsetAsync(dqp.p, 0, dqp.cap, c->stream));
+    if (u_part) {
+        PCE_HIP(c, hipMemcpyAsync(dup.p, u_part, sizeof(float) * nup, hipMemcpyHostToDevice, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(dml.p, ml_part, sizeof(float) * nml, hipMemcpyHostToDevice, c->stream));
+    }
+    if (skip) PCE_HIP(c, hipMemcpyAsync(dkl.as<int>() + n, skip, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_transpose_sq, dim3((unsigned)(d / 32), (unsigned)(d / 32)), dim3(256), 0, c->stream, dwk.as<op_t>(), dwkT.as<op_t>(), d);
     XaArgs a{};
-    a.E = dE.as<op_t>(); a.e_clip = (int64_t)k_cap * d; a.e_ld = d; a.k_len = dkl.as<int>(); a.skip = nullptr;
-    a.u_part = dup.as<float>(); a.ml_part = dml.as<float>(); a.heads = heads; a.nsplit = xa_split(n, workgroups_per_clip); a.rows = (int)R;
+    a.E = dE.as<op_t>(); a.e_clip = (int64_t)k_cap * d; a.e_ld = d; a.k_len = dkl.as<int>(); a.skip = skip ? dkl.as<int>() + n : nullptr;
+    a.u_part = dup.as<float>(); a.ml_part = dml.as<float>(); a.heads = heads; a.nsplit = nsplit; a.rows = (int)R;
     XaLayer y{};
     y.resid = dres.as<float>(); y.ln_w = dlw.as<float>(); y.ln_b = dlb.as<float>(); y.wq = dwq.as<op_t>(); y.bq = dbq.as<float>(); y.wkT = dwkT.as<op_t>();
-    y.wv = dwv.as<op_t>(); y.bv = dbv.as<float>(); y.qp_hi = dqp.as<op_t>(); y.qp_lo = y.qp_hi + (size_t)n * R * d; y.out = dout.as<op_t>(); y.out_ld = d;
+    y.wv = dwv.as<op_t>(); y.bv = dbv.as<float>(); y.qp_hi = QH; y.qp_lo = QL; y.out = dout.as<op_t>(); y.out_ld = d;
     xattn_launch(c, d, n, a, y);
     PCE_HIP(c, hipGetLastError());
     PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)n * d, hipMemcpyDeviceToHost, c->stream));
+    if (qp_hi) {
+        PCE_HIP(c, hipMemcpyAsync(qp_hi, QH, 2 * nqp, hipMemcpyDeviceToHost, c->stream)); PCE_HIP(c, hipMemcpyAsync(qp_lo, QL, 2 * nqp, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (u_part) {
+        PCE_HIP(c, hipMemcpyAsync(u_part, dup.p, sizeof(float) * nup, hipMemcpyDeviceToHost, c->stream));
+        PCE_HIP(c, hipMemcpyAsync(ml_part, dml.p, sizeof(float) * nml, hipMemcpyDeviceToHost, c->stream));
+    }
     PCE_HIP(c, hipStreamSynchronize(c->stream));
+    if (nodes_out) *nodes_out = nodes;
     return PCE_OK;
+}
+int pce_selftest_xattn(pce_ctx *c, const float *resid, const float *ln_w, const float *ln_b, const uint16_t *wq, const float *bq, const uint16_t *wk,
+                       const uint16_t *wv, const float *bv, const uint16_t *E, const int32_t *k_len, int32_t n, int32_t k_cap, int32_t d, int32_t heads,
+                       int32_t workgroups_per_clip, uint16_t *out)
+{
+    if (!c || !out || n <= 0 || k_cap <= 0 || d <= 0) return PCE_E_INVALID;
+    std::fill(out, out + (size_t)n * d, (uint16_t)0);
+    return PCE_BUILD_NS::pce_selftest_xattn_stages(c, resid, ln_w, ln_b, wq, bq, wk, wv, bv, E, (int64_t)n * k_cap * d, k_len, nullptr, n, k_cap, d, heads,
+                                                   workgroups_per_clip, out, (int64_t)n * d, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, nullptr);
 }
 
 // Self-test hook of the persistent 256 x 256 GEMM: C = epilogue(A B^T + bias) on host arrays (op_t bit patterns in, op_t bit patterns out).

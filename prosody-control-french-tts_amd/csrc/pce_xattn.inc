@@ -15,6 +15,7 @@
 // Arithmetic: Q', P and U enter their MFMAs as hi + lo pairs of op_t (two products each), so the rounding the reference's own arithmetic has
 // at k = key(xa) / v = value(xa) / softmax(...).to(fp16) is not replaced by a coarser one: against the fp32 restatement this path is as close as
 // the K / V path (tests/test_gpu_whisper.py compares both with it, step by step; the prefix step of a decode still runs on the K / V cache).
+// tests/test_gpu_xattn.py holds each of the three kernels to that claim on its own (pce_selftest_xattn_stages copies out Q', the nodes' U and (m, l)).
 // profiles/r05/xattn_absorb.txt: the development bench (tools/lab/xattn_absorb.hip) and the A/B of the decoding loop.
 
 typedef short xa_s16x4 __attribute__((__vector_size__(4 * sizeof(short))));
@@ -401,7 +402,15 @@ __global__ __launch_bounds__(256) PCE_NO_PK_F32 void k_xq_fused(const float *__r
         if (dead) continue;
         xa_opx4 h4, l4;
 #pragma unroll
-        for (int e = 0; e < 4; e++) { const float v = r[e] * scale; h4[e] = (op_t)v; l4[e] = (op_t)(v - (float)h4[e]); }
+        for (int e = 0; e < 4; e++) {
+            // v is made opaque: left to itself the compiler converts the STORED hi from the fp32 product (v_mul_f32, v_cvt_pk_f16_f32) but takes the hi
+            // it subtracts from the product fused into the conversion (v_fma_mixlo_f16: one rounding of the exact product).  Where the fp32 product
+            // is a tie of the fp16 grid -- one element in 2^13 -- the two differ by a step of hi and hi + lo missed v by that step (fp16 build;
+            // tests/test_gpu_xattn.py reads the query's bits back through Wk = I and found it)
+            float v = r[e] * scale;
+            asm volatile("" : "+v"(v));
+            h4[e] = (op_t)v; l4[e] = (op_t)(v - (float)h4[e]);
+        }
         const int64_t o = ((int64_t)c * rows + h) * D + wv * (D / 4) + 16 * jb + 4 * g;
         *reinterpret_cast<xa_opx4 *>(qp_hi + o) = h4;
         *reinterpret_cast<xa_opx4 *>(qp_lo + o) = l4;

@@ -264,6 +264,7 @@ SIGNATURES = {
     "pce_selftest_attn1": [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64],
     "pce_selftest_align_matrix": [_vp, _i32, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, C.c_float, _vp, _i64, _vp, _i64, _vp, _i64],
     "pce_selftest_xattn": [_vp] * 11 + [_i32] * 5 + [_vp],
+    "pce_selftest_xattn_stages": [_vp] * 10 + [_i64, _vp, _vp] + [_i32] * 5 + [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "pce_selftest_gemm_tiled": [_vp, _i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     "pce_selftest_layernorm": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.c_float, _i32, _vp, _vp, _vp],
     "pce_whisper_encode_fetch": [_vp, _i32, _vp],
@@ -874,6 +875,29 @@ class ProsodyEngine:
         self._check(self._lib.pce_selftest_xattn(self._ctx, res.ctypes.data, lw.ctypes.data, lb.ctypes.data, ptr(tq), vq.ctypes.data, ptr(tk), ptr(tv), vv.ctypes.data,
                                                  ptr(tE), kl.ctypes.data, int(n), int(k_cap), int(d), int(heads), int(workgroups_per_clip), ptr(out)))
         return out.float().numpy(), tq.float().numpy(), tk.float().numpy(), tv.float().numpy(), tE.float().numpy()
+
+    def selftest_xattn_stages(self, resid, ln_w, ln_b, wq, bq, wk, wv, bv, E, k_len, heads: int, out, qp_hi, qp_lo, u_part, ml_part, skip=None,
+                              workgroups_per_clip: int = 0) -> int:
+        """``pce_selftest_xattn_stages``: one layer of the encoder-output cross-attention through the product's launch, with what lies between its three
+        kernels.  wq / wk / wv [d][d], E [n][k_cap][d], out [n][d] and qp_hi / qp_lo [n][R][d] (R = heads rounded up to 16) are uint16 bit patterns of the
+        context's operand type; resid [n][d], ln_w / ln_b / bq / bv [d], u_part [n][4][R][d] and ml_part [n][4][R][2] float32.  out, qp_hi, qp_lo, u_part
+        and ml_part are read and updated in place.  Returns nodes (2: pair nodes, 4: leaves): the first n * nodes * R * d elements of u_part (n * nodes * R * 2
+        of ml_part) are [n][nodes][R][.], the rest keeps the caller's values."""
+        wq, wk, wv, E, out, qp_hi, qp_lo = (self._u16(x) for x in (wq, wk, wv, E, out, qp_hi, qp_lo))
+        for x in (resid, ln_w, ln_b, bq, bv, u_part, ml_part):
+            assert isinstance(x, np.ndarray) and x.dtype == np.float32 and x.flags["C_CONTIGUOUS"], getattr(x, "dtype", None)
+        n, k_cap, d = E.shape
+        kl = np.ascontiguousarray(k_len, dtype=np.int32)
+        sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.int32)
+        assert kl.size == n and (sk is None or sk.size == n) and resid.shape == (n, d) and wq.shape == wk.shape == wv.shape == (d, d)
+        assert ln_w.size == ln_b.size == bq.size == bv.size == d and qp_hi.size == qp_lo.size
+        nodes = C.c_int32(0)
+        self._check(self._lib.pce_selftest_xattn_stages(self._ctx, resid.ctypes.data, ln_w.ctypes.data, ln_b.ctypes.data, wq.ctypes.data, bq.ctypes.data,
+                                                        wk.ctypes.data, wv.ctypes.data, bv.ctypes.data, E.ctypes.data, E.size, kl.ctypes.data,
+                                                        None if sk is None else sk.ctypes.data, int(n), int(k_cap), int(d), int(heads),
+                                                        int(workgroups_per_clip), out.ctypes.data, out.size, qp_hi.ctypes.data, qp_lo.ctypes.data, qp_hi.size,
+                                                        u_part.ctypes.data, u_part.size, ml_part.ctypes.data, ml_part.size, C.addressof(nodes)))
+        return int(nodes.value)
 
     def selftest_gemm_tiled(self, epilogue: int, A, B, bias, M: int, N: int, K: int, C, lda: int, ldc: int, kernel: int = 0, a_batch: int = 0,
                             batch: int = 1, c_batch: int = 0, pos=None, v_col0: int = 0, rows_per_clip: int = 0, vt=None, vt_sp: int = 0) -> int:
