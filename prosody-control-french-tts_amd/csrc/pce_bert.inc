@@ -33,46 +33,27 @@ int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, i
     PCE_HIP(c, hipSetDevice(c->device));
     WhisperState::Bert &b = ws_of(c)->bert;
     b.dims = *dims; b.loaded = false; b.n_seq = -1; b.layers.assign((size_t)L, {});
-    std::vector<float> mats, vecs;
-    auto add_vec = [&](const float *p, size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), p, p + n); return o; };
-    auto add_mat = [&](const float *p, size_t n) { size_t o = mats.size(); mats.insert(mats.end(), p, p + n); return o; };
+    WeightPack pk;
     const float *p = weights;
     const float *word = p; p += (size_t)V * d;
     const float *pos = p; p += (size_t)P * d;
     const float *type = p; p += (size_t)TY * d;
-    b.lne_w = add_vec(p, (size_t)d); p += d; b.lne_b = add_vec(p, (size_t)d); p += d;
-    for (int l = 0; l < L; l++) {
-        EncoderLayerW &ly = b.layers[(size_t)l];
-        const float *qw = p, *qb = qw + dd, *kw = qb + d, *kb = kw + dd, *vw = kb + d, *vb = vw + dd;
-        ly.qkv_w = add_mat(qw, (size_t)dd); add_mat(kw, (size_t)dd); add_mat(vw, (size_t)dd);          // fused [3d][d]
-        ly.qkv_b = add_vec(qb, (size_t)d); add_vec(kb, (size_t)d); add_vec(vb, (size_t)d);
-        p = vb + d;
-        ly.out_w = add_mat(p, (size_t)dd); p += dd; ly.out_b = add_vec(p, (size_t)d); p += d;
-        ly.ln1_w = add_vec(p, (size_t)d); p += d; ly.ln1_b = add_vec(p, (size_t)d); p += d;
-        ly.m1_w = add_mat(p, (size_t)(4 * dd)); p += 4 * dd; ly.m1_b = add_vec(p, (size_t)4 * d); p += 4 * d;
-        ly.m2_w = add_mat(p, (size_t)(4 * dd)); p += 4 * dd; ly.m2_b = add_vec(p, (size_t)d); p += d;
-        ly.ln2_w = add_vec(p, (size_t)d); p += d; ly.ln2_b = add_vec(p, (size_t)d); p += d;
-    }
+    b.lne_w = pk.vec(p, (size_t)d); b.lne_b = pk.vec(p, (size_t)d);
+    for (EncoderLayerW &ly : b.layers) ly = pack_encoder_layer(pk, p, (size_t)d, (size_t)4 * d, false, true);
     {   // classifier [n_labels][d] padded with zero rows to one 128-column GEMM tile
         std::vector<float> cw((size_t)128 * d, 0.f), cb(128, 0.f);
         memcpy(cw.data(), p, sizeof(float) * (size_t)NL * d); p += (size_t)NL * d;
         memcpy(cb.data(), p, sizeof(float) * (size_t)NL); p += NL;
-        b.cls_w = add_mat(cw.data(), cw.size()); b.cls_b = add_vec(cb.data(), cb.size());
+        b.cls_w = pk.mat_at(cw.data(), cw.size()); b.cls_b = pk.vec_at(cb.data(), cb.size());
     }
     DevBuf tmp;
-    PCE_HIP(c, tmp.reserve(sizeof(float) * mats.size()));
-    PCE_HIP(c, b.w_bf16.reserve(sizeof(op_t) * mats.size() + 256));
-    PCE_HIP(c, b.w_f32.reserve(sizeof(float) * vecs.size()));
+    if (const int rc = upload_weights(c, pk, tmp, b.w_bf16, b.w_f32)) return rc;
     PCE_HIP(c, b.word.reserve(sizeof(float) * (size_t)V * d));
     PCE_HIP(c, b.pos.reserve(sizeof(float) * (size_t)P * d));
     PCE_HIP(c, b.type0.reserve(sizeof(float) * (size_t)d));
-    PCE_HIP(c, hipMemcpyAsync(tmp.p, mats.data(), sizeof(float) * mats.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.w_f32.p, vecs.data(), sizeof(float) * vecs.size(), hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(b.word.p, word, sizeof(float) * (size_t)V * d, hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(b.pos.p, pos, sizeof(float) * (size_t)P * d, hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(b.type0.p, type, sizeof(float) * (size_t)d, hipMemcpyHostToDevice, c->stream));      // token_type_ids = 0
-    hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(),
-                       b.w_bf16.as<op_t>(), (int64_t)mats.size());
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     b.loaded = true;
     return PCE_OK;
@@ -84,7 +65,7 @@ int pce_bert_run(pce_ctx *c, const int32_t *input_ids, const int32_t *offsets, i
     WhisperState::Bert &b = ws_of(c)->bert;
     if (!b.loaded) return pce_fail(c, PCE_E_STATE, "pce_bert_run before pce_bert_load");
     PCE_HIP(c, hipSetDevice(c->device));
-    const int d = b.dims.n_state, H = b.dims.n_head, L = b.dims.n_layer, V = b.dims.n_vocab, n = n_seq, SPD = 512;
+    const int d = b.dims.n_state, H = b.dims.n_head, V = b.dims.n_vocab, n = n_seq, SPD = 512;
     b.n_seq = -1;
     for (int i = 0; i < n; i++) {
         const int T = offsets[i + 1] - offsets[i];
@@ -119,22 +100,11 @@ int pce_bert_run(pce_ctx *c, const int32_t *input_ids, const int32_t *offsets, i
     KernelTimer timer(c, PCE_K_BERT);
     hipLaunchKernelGGL(k_bert_embed, dim3((unsigned)div_up(M * d, 256)), dim3(256), 0, c->stream, b.tokens.as<int>(), b.word.as<float>(),
                        b.pos.as<float>(), b.type0.as<float>(), T_pad, b.dims.n_pos, d, M, b.resid.as<float>());
-    auto ln = [&](size_t w_off, size_t b_off) {                  // resid <- LN(resid) (fp32, in place) and its op_t copy
-        launch_layernorm<op_t>(c, b.resid.as<float>(), Wf + w_off, Wf + b_off, M, d, b.ln.as<op_t>(), eps, b.resid.as<float>());
-    };
-    ln(b.lne_w, b.lne_b);
-    for (int l = 0; l < L; l++) {
-        const EncoderLayerW &ly = b.layers[(size_t)l];
-        launch_gemm<EPI_QKV>(c, b.ln.as<op_t>(), d, 0, Wb + ly.qkv_w, (int)M, 3 * d, d, Wf + ly.qkv_b, b.qk.as<op_t>(), 2 * d, 0, 1,
-                             reinterpret_cast<const float *>(b.vt.as<op_t>()), T_pad, 2 * d, SPD);
-        launch_attention_rows(c, n, H, T_pad, b.qk.as<op_t>(), 2 * d, b.qk.as<op_t>() + d, 2 * d, b.vt.as<op_t>(), SPD, T0, TL, T0, TL, b.attn.as<op_t>(),
-                              0);                                // keys beyond the sequence length are masked (right padding)
-        launch_gemm<EPI_RESID_F32>(c, b.attn.as<op_t>(), d, 0, Wb + ly.out_w, (int)M, d, d, Wf + ly.out_b, b.resid.as<float>(), d, 0, 1);
-        ln(ly.ln1_w, ly.ln1_b);
-        launch_gemm<EPI_GELU_BF16>(c, b.ln.as<op_t>(), d, 0, Wb + ly.m1_w, (int)M, 4 * d, d, Wf + ly.m1_b, b.hidden.as<op_t>(), 4 * d, 0, 1);
-        launch_gemm<EPI_RESID_F32>(c, b.hidden.as<op_t>(), 4 * d, 0, Wb + ly.m2_w, (int)M, d, 4 * d, Wf + ly.m2_b, b.resid.as<float>(), d, 0, 1);
-        ln(ly.ln2_w, ly.ln2_b);
-    }
+    // the embedding LayerNorm opens the post-LN stack: resid <- LN(resid) (fp32, in place) and its op_t copy
+    launch_layernorm<op_t>(c, b.resid.as<float>(), Wf + b.lne_w, Wf + b.lne_b, M, d, b.ln.as<op_t>(), eps, b.resid.as<float>());
+    const EncoderRun r{(int)M, d, H, 4 * d, n, T_pad, SPD, T0, TL, eps, 0.0, false, b.resid.as<float>(), b.ln.as<op_t>(), b.qk.as<op_t>(), b.vt.as<op_t>(),
+                       b.attn.as<op_t>(), b.hidden.as<op_t>(), Wb, Wf};
+    encoder_walk<ProductGemm>(c, r, b.layers, false);
     // classifier: logits[M][128] = 0 + hidden . W^T + b (the first n_labels columns are real)
     launch_gemm<EPI_F32>(c, b.ln.as<op_t>(), d, 0, Wb + b.cls_w, (int)M, 128, d, Wf + b.cls_b, b.logits.as<float>(), 128, 0, 1);
     PCE_HIP(c, hipGetLastError());

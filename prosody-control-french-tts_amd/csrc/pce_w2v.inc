@@ -285,6 +285,9 @@ static bool w2v_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, co
     launch_gemm_kernel<EPI>(c, kind, A, lda, a_batch, B, M, N, K, bias, C, ldc, c_batch, batch, pos, pos_T, v_col0, vt_sp);
     return true;
 }
+struct W2vGemm {                       // encoder_walk's GEMM rule for this model
+    template <int EPI, class... A> static bool run(pce_ctx *c, A... a) { return w2v_gemm<EPI>(c, a...); }
+};
 
 static void w2v_launch_posconv(pce_ctx *c, const float *x, const op_t *w, const float *bias, int T, int rows_per_win, int d, int groups, int n_win, float *out)
 {
@@ -408,55 +411,32 @@ int pce_w2v_load(pce_ctx *c, const pce_w2v_dims *dims, const float *weights, int
     PCE_HIP(c, hipSetDevice(c->device));
     WhisperState::W2v &b = ws_of(c)->w2v;
     b.dims = m; b.loaded = false; b.n_clips = -1; b.layers.assign((size_t)L, {});
-    std::vector<float> mats, vecs;
-    auto add_vec = [&](const float *p, size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), p, p + n); vecs.resize((vecs.size() + 3) & ~(size_t)3); return o; };
-    auto add_mat = [&](const float *p, size_t n) { size_t o = mats.size(); mats.insert(mats.end(), p, p + n); return o; };
+    WeightPack pk;
     const bool layer = m.feat_norm == 1;
     const float *p = weights;
     for (int i = 0; i < 7; i++) {
         const size_t cin = i ? (size_t)m.conv_dim[i - 1] : 1, co = (size_t)m.conv_dim[i], nw = co * cin * (size_t)m.conv_kernel[i];
         WhisperState::W2v::Conv &cv = b.conv[i];
-        cv.w = i ? add_mat(p, nw) : add_vec(p, nw); p += nw;                       // the waveform layer's taps stay fp32
+        cv.w = i ? pk.mat(p, nw) : pk.vec(p, nw);                                  // the waveform layer's taps stay fp32
         cv.has_b = m.conv_bias != 0; cv.has_ln = layer || i == 0;
-        if (cv.has_b) { cv.b = add_vec(p, co); p += co; }
-        if (cv.has_ln) { cv.g = add_vec(p, co); p += co; cv.beta = add_vec(p, co); p += co; }
+        if (cv.has_b) cv.b = pk.vec(p, co);
+        if (cv.has_ln) { cv.g = pk.vec(p, co); cv.beta = pk.vec(p, co); }
     }
-    const size_t c6 = (size_t)m.conv_dim[6], dd = (size_t)d * d, cg = (size_t)(d / m.pos_groups);
-    b.fp_ln_w = add_vec(p, c6); p += c6; b.fp_ln_b = add_vec(p, c6); p += c6;
-    b.proj_w = add_mat(p, (size_t)d * c6); p += (size_t)d * c6; b.proj_b = add_vec(p, (size_t)d); p += d;
-    b.pos_w = add_mat(p, (size_t)d * cg * PC_TAPS); p += (size_t)d * cg * PC_TAPS; b.pos_b = add_vec(p, (size_t)d); p += d;
-    b.enc_ln_w = add_vec(p, (size_t)d); p += d; b.enc_ln_b = add_vec(p, (size_t)d); p += d;
-    for (int l = 0; l < L; l++) {
-        EncoderLayerW &ly = b.layers[(size_t)l];
-        const float *qw = p, *qb = qw + dd, *kw = qb + d, *kb = kw + dd, *vw = kb + d, *vb = vw + dd;
-        ly.qkv_w = add_mat(qw, dd); add_mat(kw, dd); add_mat(vw, dd);                                   // fused [3d][d]
-        {   // (one vector: the three biases contiguous)
-            std::vector<float> qkv_b(3 * (size_t)d);
-            memcpy(qkv_b.data(), qb, sizeof(float) * d); memcpy(qkv_b.data() + d, kb, sizeof(float) * d); memcpy(qkv_b.data() + 2 * d, vb, sizeof(float) * d);
-            ly.qkv_b = add_vec(qkv_b.data(), qkv_b.size());
-        }
-        p = vb + d;
-        ly.out_w = add_mat(p, dd); p += dd; ly.out_b = add_vec(p, (size_t)d); p += d;
-        ly.ln1_w = add_vec(p, (size_t)d); p += d; ly.ln1_b = add_vec(p, (size_t)d); p += d;
-        ly.m1_w = add_mat(p, (size_t)I * d); p += (size_t)I * d; ly.m1_b = add_vec(p, (size_t)I); p += I;
-        ly.m2_w = add_mat(p, (size_t)d * I); p += (size_t)d * I; ly.m2_b = add_vec(p, (size_t)d); p += d;
-        ly.ln2_w = add_vec(p, (size_t)d); p += d; ly.ln2_b = add_vec(p, (size_t)d); p += d;
-    }
+    const size_t c6 = (size_t)m.conv_dim[6], cg = (size_t)(d / m.pos_groups);
+    b.fp_ln_w = pk.vec(p, c6); b.fp_ln_b = pk.vec(p, c6);
+    b.proj_w = pk.mat(p, (size_t)d * c6); b.proj_b = pk.vec(p, (size_t)d);
+    b.pos_w = pk.mat(p, (size_t)d * cg * PC_TAPS); b.pos_b = pk.vec(p, (size_t)d);
+    b.enc_ln_w = pk.vec(p, (size_t)d); b.enc_ln_b = pk.vec(p, (size_t)d);
+    for (EncoderLayerW &ly : b.layers) ly = pack_encoder_layer(pk, p, (size_t)d, (size_t)I, false, true);
     {   // lm_head [n_vocab][d] padded with zero rows to whole 128-column GEMM tiles
         b.Vp = (int)div_up(V, 128) * 128;
         std::vector<float> lw((size_t)b.Vp * d, 0.f), lb((size_t)b.Vp, 0.f);
         memcpy(lw.data(), p, sizeof(float) * (size_t)V * d); p += (size_t)V * d;
         memcpy(lb.data(), p, sizeof(float) * (size_t)V); p += V;
-        b.lm_w = add_mat(lw.data(), lw.size()); b.lm_b = add_vec(lb.data(), lb.size());
+        b.lm_w = pk.mat_at(lw.data(), lw.size()); b.lm_b = pk.vec_at(lb.data(), lb.size());
     }
     DevBuf tmp;
-    PCE_HIP(c, tmp.reserve(sizeof(float) * mats.size()));
-    PCE_HIP(c, b.w16.reserve(sizeof(op_t) * mats.size() + 256));
-    PCE_HIP(c, b.w32.reserve(sizeof(float) * vecs.size()));
-    PCE_HIP(c, hipMemcpyAsync(tmp.p, mats.data(), sizeof(float) * mats.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.w32.p, vecs.data(), sizeof(float) * vecs.size(), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(), b.w16.as<op_t>(),
-                       (int64_t)mats.size());
+    if (const int rc = upload_weights(c, pk, tmp, b.w16, b.w32)) return rc;
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     b.loaded = true;
     return PCE_OK;
@@ -485,7 +465,7 @@ int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan)
                         (long long)window, (long long)context, std::min(T - cut + 1, T) - cut, cut, wf);
     PCE_HIP(c, hipSetDevice(c->device));
     b.n_clips = -1;
-    const int n = c->n_clips, d = m.n_state, H = m.n_head, I = m.n_inter, L = m.n_layer, V = m.n_vocab, Vp = b.Vp, C6 = m.conv_dim[6];
+    const int n = c->n_clips, d = m.n_state, H = m.n_head, I = m.n_inter, V = m.n_vocab, Vp = b.Vp, C6 = m.conv_dim[6];
     const int T_pad = w2v_rows_pad(T), vt_sp = (int)div_up(T, 64) * 64, n_cols = V + (plan->star ? 1 : 0);
     // the attention's buffer resources and the transposed-V epilogue form 32-bit byte offsets inside one window
     if (((int64_t)T * 2 * d + 64) * 2 >= ((int64_t)1 << 31) || (int64_t)64 * vt_sp * 2 >= ((int64_t)1 << 31))
@@ -581,26 +561,13 @@ int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan)
         w2v_launch_ln16(c, false, b.img[0].as<op_t>(), Wf + b.fp_ln_w, Wf + b.fp_ln_b, M, C6, eps, b.fpln.as<op_t>());
         fit &= w2v_gemm<EPI_F32>(c, b.fpln.as<op_t>(), C6, 0, Wb + b.proj_w, M, d, C6, Wf + b.proj_b, b.h0.as<float>(), d, 0, 1);
         w2v_launch_posconv(c, b.h0.as<float>(), Wb + b.pos_w, Wf + b.pos_b, T, T_pad, d, m.pos_groups, Wc, b.h.as<float>());
-        float *resid = b.h.as<float>();
-        auto ln = [&](size_t w_off, size_t b_off, bool in_place) {          // ln <- LN(resid) as op_t; the post-LN stream also keeps it in fp32, in place
-            launch_layernorm<op_t>(c, resid, Wf + w_off, Wf + b_off, M, d, b.ln.as<op_t>(), eps, in_place ? resid : nullptr);
-        };
         const bool pre = m.stable_ln != 0;
-        if (!pre) ln(b.enc_ln_w, b.enc_ln_b, true);
-        for (int l = 0; l < L; l++) {
-            const EncoderLayerW &ly = b.layers[(size_t)l];
-            if (pre) ln(ly.ln1_w, ly.ln1_b, false);
-            fit &= w2v_gemm<EPI_QKV>(c, b.ln.as<op_t>(), d, 0, Wb + ly.qkv_w, M, 3 * d, d, Wf + ly.qkv_b, b.qk.as<op_t>(), 2 * d, 0, 1,
-                              reinterpret_cast<const float *>(b.vt.as<op_t>()), T_pad, 2 * d, vt_sp);
-            launch_attention_rows(c, Wc, H, T_pad, b.qk.as<op_t>(), 2 * d, b.qk.as<op_t>() + d, 2 * d, b.vt.as<op_t>(), vt_sp, R0, RL, R0, RL, b.attn.as<op_t>(), 0,
-                                  4.0 * Wc * (double)T * T * d);
-            fit &= w2v_gemm<EPI_RESID_F32>(c, b.attn.as<op_t>(), d, 0, Wb + ly.out_w, M, d, d, Wf + ly.out_b, resid, d, 0, 1);
-            if (pre) ln(ly.ln2_w, ly.ln2_b, false); else ln(ly.ln1_w, ly.ln1_b, true);
-            fit &= w2v_gemm<EPI_GELU_BF16>(c, b.ln.as<op_t>(), d, 0, Wb + ly.m1_w, M, I, d, Wf + ly.m1_b, b.hidden.as<op_t>(), I, 0, 1);
-            fit &= w2v_gemm<EPI_RESID_F32>(c, b.hidden.as<op_t>(), I, 0, Wb + ly.m2_w, M, d, I, Wf + ly.m2_b, resid, d, 0, 1);
-            if (!pre) ln(ly.ln2_w, ly.ln2_b, true);
-        }
-        if (pre) ln(b.enc_ln_w, b.enc_ln_b, false);
+        const EncoderRun r{M, d, H, I, Wc, T_pad, vt_sp, R0, RL, eps, 4.0 * Wc * (double)T * T * d, false, b.h.as<float>(), b.ln.as<op_t>(), b.qk.as<op_t>(),
+                           b.vt.as<op_t>(), b.attn.as<op_t>(), b.hidden.as<op_t>(), Wb, Wf};
+        // the encoder LayerNorm: in front of a post-LN stack (in place on the fp32 stream, and its op_t copy), behind a pre-LN one
+        if (!pre) launch_layernorm<op_t>(c, b.h.as<float>(), Wf + b.enc_ln_w, Wf + b.enc_ln_b, M, d, b.ln.as<op_t>(), eps, b.h.as<float>());
+        fit &= encoder_walk<W2vGemm>(c, r, b.layers, pre);
+        if (pre) launch_layernorm<op_t>(c, b.h.as<float>(), Wf + b.enc_ln_w, Wf + b.enc_ln_b, M, d, b.ln.as<op_t>(), eps);
         fit &= w2v_gemm<EPI_F32>(c, b.ln.as<op_t>(), d, 0, Wb + b.lm_w, M, Vp, d, Wf + b.lm_b, b.logits.as<float>(), Vp, 0, 1);
         {
             KernelTimer kt(c, PCE_K_W2V_TAIL);

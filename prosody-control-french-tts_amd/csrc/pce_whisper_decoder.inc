@@ -108,50 +108,31 @@ int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, cons
     WhisperState *w = ws_of(c);
     { const int rc = lds_optins(c, w); if (rc) return rc; }
     w->tdims = *dims; w->dec_loaded = false; w->dlayers.assign((size_t)L, {});
-    std::vector<float> mats, vecs;
-    auto add_vec = [&](const float *p, size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), p, p + n); return o; };
-    auto add_zero = [&](size_t n) { size_t o = vecs.size(); vecs.insert(vecs.end(), n, 0.f); return o; };
-    auto add_mat = [&](const float *p, size_t n) { size_t o = mats.size(); mats.insert(mats.end(), p, p + n); return o; };
+    WeightPack pk;
     const float *p = weights;
     const float *tok = p; p += (size_t)V * d;
     const float *pos = p; p += (size_t)TC * d;
     const size_t dd = (size_t)d * d;
-    for (int l = 0; l < L; l++) {
-        WhisperState::DLayer &ly = w->dlayers[(size_t)l];
-        ly.ln1_w = add_vec(p, (size_t)d); p += d; ly.ln1_b = add_vec(p, (size_t)d); p += d;
-        {   // self attention: q.w q.b k.w v.w v.b out.w out.b -> fused [3d][d]
-            const float *qw = p, *qb = qw + dd, *kw = qb + d, *vw = kw + dd, *vb = vw + dd;
-            ly.qkv_w = add_mat(qw, dd); add_mat(kw, dd); add_mat(vw, dd);
-            ly.qkv_b = add_vec(qb, (size_t)d); add_zero((size_t)d); add_vec(vb, (size_t)d);
-            p = vb + d;
-            ly.out_w = add_mat(p, dd); p += dd; ly.out_b = add_vec(p, (size_t)d); p += d;
-        }
-        ly.lnx_w = add_vec(p, (size_t)d); p += d; ly.lnx_b = add_vec(p, (size_t)d); p += d;
-        {   // cross attention: q from text, k | v from audio -> [d][d] and fused [2d][d]
-            const float *qw = p, *qb = qw + dd, *kw = qb + d, *vw = kw + dd, *vb = vw + dd;
-            ly.xq_w = add_mat(qw, dd); ly.xq_b = add_vec(qb, (size_t)d);
-            ly.xkv_w = add_mat(kw, dd); add_mat(vw, dd);
-            ly.xkv_b = add_zero((size_t)d); add_vec(vb, (size_t)d);
-            p = vb + d;
-            ly.xout_w = add_mat(p, dd); p += dd; ly.xout_b = add_vec(p, (size_t)d); p += d;
-        }
-        ly.ln2_w = add_vec(p, (size_t)d); p += d; ly.ln2_b = add_vec(p, (size_t)d); p += d;
-        ly.m1_w = add_mat(p, 4 * dd); p += 4 * dd; ly.m1_b = add_vec(p, (size_t)4 * d); p += 4 * d;
-        ly.m2_w = add_mat(p, 4 * dd); p += 4 * dd; ly.m2_b = add_vec(p, (size_t)d); p += d;
+    for (WhisperState::DLayer &ly : w->dlayers) {
+        ly.ln1_w = pk.vec(p, (size_t)d); ly.ln1_b = pk.vec(p, (size_t)d);
+        { const WeightPack::Attn a = pk.self_attention(p, (size_t)d, false); ly.qkv_w = a.qkv_w; ly.qkv_b = a.qkv_b; ly.out_w = a.out_w; ly.out_b = a.out_b; }
+        ly.lnx_w = pk.vec(p, (size_t)d); ly.lnx_b = pk.vec(p, (size_t)d);
+        // cross attention: q from text, k | v from audio -> [d][d] and fused [2d][d] with bias [0 | v.b]
+        ly.xq_w = pk.mat(p, dd); ly.xq_b = pk.vec(p, (size_t)d);
+        ly.xkv_w = pk.mat(p, dd); pk.mat(p, dd);
+        ly.xkv_b = pk.zeros((size_t)d); pk.vec(p, (size_t)d);
+        ly.xout_w = pk.mat(p, dd); ly.xout_b = pk.vec(p, (size_t)d);
+        ly.ln2_w = pk.vec(p, (size_t)d); ly.ln2_b = pk.vec(p, (size_t)d);
+        ly.m1_w = pk.mat(p, 4 * dd); ly.m1_b = pk.vec(p, (size_t)4 * d);
+        ly.m2_w = pk.mat(p, 4 * dd); ly.m2_b = pk.vec(p, (size_t)d);
     }
-    w->dln_w = add_vec(p, (size_t)d); p += d; w->dln_b = add_vec(p, (size_t)d); p += d;
+    w->dln_w = pk.vec(p, (size_t)d); w->dln_b = pk.vec(p, (size_t)d);
     DevBuf tmp;
-    PCE_HIP(c, tmp.reserve(sizeof(float) * mats.size()));
-    PCE_HIP(c, w->dw_bf16.reserve(sizeof(op_t) * mats.size() + 256));
-    PCE_HIP(c, w->dw_f32.reserve(sizeof(float) * vecs.size()));
+    if (const int rc = upload_weights(c, pk, tmp, w->dw_bf16, w->dw_f32)) return rc;
     PCE_HIP(c, w->d_tok_emb.reserve(sizeof(float) * (size_t)V * d));
     PCE_HIP(c, w->d_pos_emb.reserve(sizeof(float) * (size_t)TC * d));
-    PCE_HIP(c, hipMemcpyAsync(tmp.p, mats.data(), sizeof(float) * mats.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->dw_f32.p, vecs.data(), sizeof(float) * vecs.size(), hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(w->d_tok_emb.p, tok, sizeof(float) * (size_t)V * d, hipMemcpyHostToDevice, c->stream));
     PCE_HIP(c, hipMemcpyAsync(w->d_pos_emb.p, pos, sizeof(float) * (size_t)TC * d, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(),
-                       w->dw_bf16.as<op_t>(), (int64_t)mats.size());
     {   // tied output projection for free-running decoding: the token embedding in op_t, rows padded to the 128-column GEMM tile
         const size_t Vp = (size_t)div_up(V, 128) * 128;
         PCE_HIP(c, w->g_emb_bf16.reserve(sizeof(op_t) * Vp * (size_t)d + 256));
