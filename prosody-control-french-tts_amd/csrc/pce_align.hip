@@ -242,16 +242,14 @@ int pce_dtw(pce_ctx *c, const double *x, int32_t n_rows, int32_t n_cols, int32_t
     PCE_HIP(c, hipSetDevice(c->device));
     const size_t cells = (size_t)batch * n_rows * n_cols, pl = (size_t)batch * (size_t)(n_rows + n_cols);
     DevBuf dx, dtr, dpi, dpj, dpl;
-    PCE_HIP(c, dx.reserve(sizeof(double) * cells));
+    PCE_UPLOAD(c, dx, x, cells);
     PCE_HIP(c, dtr.reserve((size_t)batch * (size_t)(n_rows + 1) * (size_t)(n_cols + 1)));
     PCE_HIP(c, dpi.reserve(sizeof(int) * pl)); PCE_HIP(c, dpj.reserve(sizeof(int) * pl)); PCE_HIP(c, dpl.reserve(sizeof(int) * (size_t)batch));
-    PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(double) * cells, hipMemcpyHostToDevice, c->stream));
-    int rc = pce_dtw_launch(c, dx.as<double>(), (int64_t)n_rows * n_cols, n_cols, nullptr, nullptr, n_rows, n_cols, batch,
-                            dtr.as<unsigned char>(), dpi.as<int>(), dpj.as<int>(), dpl.as<int>());
-    if (rc) return rc;
-    PCE_HIP(c, hipMemcpyAsync(path_i, dpi.p, sizeof(int) * pl, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(path_j, dpj.p, sizeof(int) * pl, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(path_len, dpl.p, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
+    PCE_TRY(pce_dtw_launch(c, dx.as<double>(), (int64_t)n_rows * n_cols, n_cols, nullptr, nullptr, n_rows, n_cols, batch,
+                           dtr.as<unsigned char>(), dpi.as<int>(), dpj.as<int>(), dpl.as<int>()));
+    PCE_FETCH(c, path_i, dpi.p, pl);
+    PCE_FETCH(c, path_j, dpj.p, pl);
+    PCE_FETCH(c, path_len, dpl.p, (size_t)batch);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -277,19 +275,11 @@ int pce_nw_align(pce_ctx *c, const int32_t *a_ids, const int64_t *a_off, const i
     if (a_off[0] != 0 || b_off[0] != 0) return pce_fail(c, PCE_E_INVALID, "pce_nw_align: offsets must start at 0");
     if ((na && !a_ids) || (nb && !b_ids)) return PCE_E_INVALID;
     DevBuf da, db, dao, dbo, dtr, dtro, doi, doj, doo, dol, drw, drwo;
-    PCE_HIP(c, drw.reserve(sizeof(int) * ((size_t)rwo[(size_t)batch] + 1))); PCE_HIP(c, drwo.reserve(sizeof(long long) * ((size_t)batch + 1)));
-    PCE_HIP(c, da.reserve(sizeof(int) * (na + 1))); PCE_HIP(c, db.reserve(sizeof(int) * (nb + 1)));
-    PCE_HIP(c, dao.reserve(sizeof(long long) * ((size_t)batch + 1))); PCE_HIP(c, dbo.reserve(sizeof(long long) * ((size_t)batch + 1)));
-    PCE_HIP(c, dtr.reserve((size_t)tro[(size_t)batch] + 1)); PCE_HIP(c, dtro.reserve(sizeof(long long) * ((size_t)batch + 1)));
-    PCE_HIP(c, doi.reserve(sizeof(int) * (no + 1))); PCE_HIP(c, doj.reserve(sizeof(int) * (no + 1)));
-    PCE_HIP(c, doo.reserve(sizeof(long long) * ((size_t)batch + 1))); PCE_HIP(c, dol.reserve(sizeof(int) * (size_t)batch));
-    if (na) PCE_HIP(c, hipMemcpyAsync(da.p, a_ids, sizeof(int) * na, hipMemcpyHostToDevice, c->stream));
-    if (nb) PCE_HIP(c, hipMemcpyAsync(db.p, b_ids, sizeof(int) * nb, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dao.p, a_off, sizeof(long long) * ((size_t)batch + 1), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dbo.p, b_off, sizeof(long long) * ((size_t)batch + 1), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dtro.p, tro.data(), sizeof(long long) * tro.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(doo.p, oo.data(), sizeof(long long) * oo.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(drwo.p, rwo.data(), sizeof(long long) * rwo.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, drw.reserve(sizeof(int) * ((size_t)rwo[(size_t)batch] + 1))); PCE_HIP(c, dtr.reserve((size_t)tro[(size_t)batch] + 1));
+    PCE_HIP(c, doi.reserve(sizeof(int) * (no + 1))); PCE_HIP(c, doj.reserve(sizeof(int) * (no + 1))); PCE_HIP(c, dol.reserve(sizeof(int) * (size_t)batch));
+    PCE_UPLOAD(c, da, a_ids, na, 1); PCE_UPLOAD(c, db, b_ids, nb, 1);
+    PCE_UPLOAD(c, dao, a_off, (size_t)batch + 1); PCE_UPLOAD(c, dbo, b_off, (size_t)batch + 1);
+    PCE_UPLOAD(c, dtro, tro); PCE_UPLOAD(c, doo, oo); PCE_UPLOAD(c, drwo, rwo);
     int threads = 64; while (threads < max_rows && threads < DTW_MAXN) threads <<= 1;
     {
         KernelTimer t(c, PCE_K_NW);
@@ -299,10 +289,10 @@ int pce_nw_align(pce_ctx *c, const int32_t *a_ids, const int64_t *a_off, const i
     }
     PCE_HIP(c, hipGetLastError());
     if (no) {
-        PCE_HIP(c, hipMemcpyAsync(out_i, doi.p, sizeof(int) * no, hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(out_j, doj.p, sizeof(int) * no, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, out_i, doi.p, no);
+        PCE_FETCH(c, out_j, doj.p, no);
     }
-    PCE_HIP(c, hipMemcpyAsync(out_len, dol.p, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out_len, dol.p, (size_t)batch);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -325,22 +315,16 @@ int pce_levenshtein(pce_ctx *c, const uint32_t *a_chars, const int64_t *a_off, c
     const size_t na = (size_t)a_off[batch], nb = (size_t)b_off[batch];
     if ((na && !a_chars) || (nb && !b_chars)) return PCE_E_INVALID;
     DevBuf da, db, dao, dbo, dro, drows, dout;
-    PCE_HIP(c, da.reserve(sizeof(unsigned) * (na + 1))); PCE_HIP(c, db.reserve(sizeof(unsigned) * (nb + 1)));
-    PCE_HIP(c, dao.reserve(sizeof(long long) * ((size_t)batch + 1))); PCE_HIP(c, dbo.reserve(sizeof(long long) * ((size_t)batch + 1)));
-    PCE_HIP(c, dro.reserve(sizeof(long long) * ((size_t)batch + 1))); PCE_HIP(c, drows.reserve(sizeof(int) * ((size_t)ro[(size_t)batch] + 1)));
-    PCE_HIP(c, dout.reserve(sizeof(int) * (size_t)batch));
-    if (na) PCE_HIP(c, hipMemcpyAsync(da.p, a_chars, sizeof(unsigned) * na, hipMemcpyHostToDevice, c->stream));
-    if (nb) PCE_HIP(c, hipMemcpyAsync(db.p, b_chars, sizeof(unsigned) * nb, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dao.p, a_off, sizeof(long long) * ((size_t)batch + 1), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dbo.p, b_off, sizeof(long long) * ((size_t)batch + 1), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dro.p, ro.data(), sizeof(long long) * ro.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, drows.reserve(sizeof(int) * ((size_t)ro[(size_t)batch] + 1))); PCE_HIP(c, dout.reserve(sizeof(int) * (size_t)batch));
+    PCE_UPLOAD(c, da, a_chars, na, 1); PCE_UPLOAD(c, db, b_chars, nb, 1);
+    PCE_UPLOAD(c, dao, a_off, (size_t)batch + 1); PCE_UPLOAD(c, dbo, b_off, (size_t)batch + 1); PCE_UPLOAD(c, dro, ro);
     {
         KernelTimer t(c, PCE_K_LEVENSHTEIN);
         hipLaunchKernelGGL(k_levenshtein, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, c->stream, da.as<unsigned>(), dao.as<long long>(),
                            db.as<unsigned>(), dbo.as<long long>(), batch, drows.as<int>(), dro.as<long long>(), dout.as<int>());
     }
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out_dist, dout.p, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out_dist, dout.p, (size_t)batch);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;

@@ -47,13 +47,10 @@ int pce_bert_load(pce_ctx *c, const pce_bert_dims *dims, const float *weights, i
         b.cls_w = pk.mat_at(cw.data(), cw.size()); b.cls_b = pk.vec_at(cb.data(), cb.size());
     }
     DevBuf tmp;
-    if (const int rc = upload_weights(c, pk, tmp, b.w_bf16, b.w_f32)) return rc;
-    PCE_HIP(c, b.word.reserve(sizeof(float) * (size_t)V * d));
-    PCE_HIP(c, b.pos.reserve(sizeof(float) * (size_t)P * d));
-    PCE_HIP(c, b.type0.reserve(sizeof(float) * (size_t)d));
-    PCE_HIP(c, hipMemcpyAsync(b.word.p, word, sizeof(float) * (size_t)V * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.pos.p, pos, sizeof(float) * (size_t)P * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.type0.p, type, sizeof(float) * (size_t)d, hipMemcpyHostToDevice, c->stream));      // token_type_ids = 0
+    PCE_TRY(upload_weights(c, pk, tmp, b.w_bf16, b.w_f32));
+    PCE_UPLOAD(c, b.word, word, (size_t)V * d);
+    PCE_UPLOAD(c, b.pos, pos, (size_t)P * d);
+    PCE_UPLOAD(c, b.type0, type, (size_t)d);     // token_type_ids = 0
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     b.loaded = true;
     return PCE_OK;
@@ -73,26 +70,22 @@ int pce_bert_run(pce_ctx *c, const int32_t *input_ids, const int32_t *offsets, i
     }
     if (n == 0) { b.lens.clear(); b.n_seq = 0; return PCE_OK; }
     TokenRows rows;                                              // tables: [row0 | length]
-    { const int rc = pad_token_rows(c, input_ids, offsets, n, V, "token id", 2, rows); if (rc) return rc; }
+    PCE_TRY(pad_token_rows(c, input_ids, offsets, n, V, "token id", 2, rows));
     b.lens = rows.t_len;
     const int T_pad = rows.T_pad; const int64_t M = (int64_t)n * T_pad;
     const std::vector<int> &tab = rows.tab, &tok = rows.tok;
-    PCE_HIP(c, b.tab.reserve(sizeof(int) * tab.size()));
-    PCE_HIP(c, b.tokens.reserve(sizeof(int) * tok.size()));
     PCE_HIP(c, b.resid.reserve(sizeof(float) * (size_t)M * d));
     PCE_HIP(c, b.ln.reserve(sizeof(op_t) * (size_t)M * d + 4096));
     PCE_HIP(c, b.qk.reserve(sizeof(op_t) * (size_t)M * 2 * d + 4096));
-    PCE_HIP(c, b.attn.reserve(sizeof(op_t) * (size_t)M * d + 4096));
     PCE_HIP(c, b.hidden.reserve(sizeof(op_t) * (size_t)M * 4 * d + 4096));
     PCE_HIP(c, b.logits.reserve(sizeof(float) * (size_t)M * 128));
     const size_t vt_elems = (size_t)n * (size_t)d * SPD + 64;
-    PCE_HIP(c, b.vt.reserve(sizeof(op_t) * vt_elems));
-    PCE_HIP(c, hipMemcpyAsync(b.tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(b.tokens.p, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, b.tab, tab);
+    PCE_UPLOAD(c, b.tokens, tok);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     // the attention kernel writes the rows of real tokens only and V^T columns beyond T_pad are never written: no stale bits
-    PCE_HIP(c, hipMemsetAsync(b.attn.p, 0, sizeof(op_t) * (size_t)M * d + 4096, c->stream));
-    PCE_HIP(c, hipMemsetAsync(b.vt.p, 0, sizeof(op_t) * vt_elems, c->stream));
+    PCE_ZERO(op_t, c, b.attn, (size_t)M * d + 2048);
+    PCE_ZERO(op_t, c, b.vt, vt_elems);
     const int *T0 = b.tab.as<int>(), *TL = T0 + n;
     const op_t *Wb = b.w_bf16.as<op_t>();
     const float *Wf = b.w_f32.as<float>();
@@ -121,7 +114,7 @@ int pce_bert_fetch(pce_ctx *c, int32_t seq, float *logits, int32_t *labels)
     PCE_HIP(c, hipSetDevice(c->device));
     const int T = b.lens[(size_t)seq], NL = b.dims.n_labels;
     std::vector<float> rows((size_t)T * 128);
-    PCE_HIP(c, hipMemcpyAsync(rows.data(), b.logits.as<float>() + (size_t)seq * b.T_pad * 128, sizeof(float) * rows.size(), hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, rows.data(), b.logits.as<float>() + (size_t)seq * b.T_pad * 128, rows.size());
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     for (int t = 0; t < T; t++) {

@@ -462,9 +462,8 @@ int crepe_launch_block(pce_ctx *c, int block, const h16 *in, int c_in, int N, co
 
 int upload_f16(pce_ctx *c, const float *src, int64_t n, DevBuf &dst, DevBuf &tmp)
 {
-    PCE_HIP(c, tmp.reserve(sizeof(float) * (size_t)n));
+    PCE_UPLOAD(c, tmp, src, (size_t)n);
     PCE_HIP(c, dst.reserve(sizeof(h16) * (size_t)n + 64));
-    PCE_HIP(c, hipMemcpyAsync(tmp.p, src, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_crepe_f32_to_f16, dim3(1024), dim3(256), 0, c->stream, tmp.as<float>(), dst.as<h16>(), n);
     PCE_HIP(c, hipGetLastError());
     PCE_HIP(c, hipStreamSynchronize(c->stream));       // tmp is reused by the next tensor
@@ -476,7 +475,6 @@ int upload_f16(pce_ctx *c, const float *src, int64_t n, DevBuf &dst, DevBuf &tmp
 int crepe_decode_prepare(pce_ctx *c, int32_t n_clips, int64_t total)
 {
     auto &cr = c->cr;
-    PCE_HIP(c, cr.doff.reserve(sizeof(int64_t) * ((size_t)n_clips + 1)));
     PCE_HIP(c, cr.P.reserve(sizeof(float) * (size_t)total * CR_BINS));
     PCE_HIP(c, cr.amax.reserve(sizeof(int) * (size_t)total));
     PCE_HIP(c, cr.bins.reserve(sizeof(int) * (size_t)total));
@@ -495,9 +493,8 @@ int crepe_decode_prepare(pce_ctx *c, int32_t n_clips, int64_t total)
             tab[(size_t)CR_BINS + (size_t)(e + CR_HALF) * CR_BINS + i] = std::log(p + tiny);
         }
     }
-    PCE_HIP(c, cr.tab.reserve(sizeof(double) * tab.size()));
-    PCE_HIP(c, hipMemcpyAsync(cr.tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(cr.doff.p, cr.off.data(), sizeof(int64_t) * ((size_t)n_clips + 1), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, cr.tab, tab);
+    PCE_UPLOAD(c, cr.doff, cr.off.data(), (size_t)n_clips + 1);
     PCE_HIP(c, hipStreamSynchronize(c->stream));                 // `tab` is a source of an asynchronous copy
     return PCE_OK;
 }
@@ -543,7 +540,7 @@ int pce_crepe_load(pce_ctx *c, const pce_crepe_dims *dims, const float *weights,
     auto &cr = c->cr;
     int c_in[6], c_out[6];
     for (int i = 0; i < 6; i++) { c_out[i] = dims->c_out[i]; c_in[i] = i == 0 ? 1 : dims->c_out[i - 1]; }
-    { int rc = crepe_dims_ok(c, c_in, c_out); if (rc) return rc; }
+    PCE_TRY(crepe_dims_ok(c, c_in, c_out));
     const int E = 4 * c_out[5];
     int64_t expect = (int64_t)CR_BINS * E + CR_BINS;
     for (int i = 0; i < 6; i++) expect += (int64_t)c_out[i] * (i == 0 ? CR_TAPS1 : CR_TAPS) * c_in[i] + 3 * (int64_t)c_out[i];
@@ -554,17 +551,14 @@ int pce_crepe_load(pce_ctx *c, const pce_crepe_dims *dims, const float *weights,
     const float *w = weights;
     for (int i = 0; i < 6; i++) {
         const int64_t nw = (int64_t)c_out[i] * (i == 0 ? CR_TAPS1 : CR_TAPS) * c_in[i];
-        { int rc = upload_f16(c, w, nw, cr.w16[i], tmp); if (rc) return rc; }
+        PCE_TRY(upload_f16(c, w, nw, cr.w16[i], tmp));
         w += nw;
-        PCE_HIP(c, cr.bss[i].reserve(sizeof(float) * 3 * (size_t)c_out[i]));
-        PCE_HIP(c, hipMemcpyAsync(cr.bss[i].p, w, sizeof(float) * 3 * (size_t)c_out[i], hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, cr.bss[i], w, 3 * (size_t)c_out[i]);
         w += 3 * (int64_t)c_out[i];
     }
-    PCE_HIP(c, cr.cls_w.reserve(sizeof(float) * (size_t)CR_BINS * E));
-    PCE_HIP(c, cr.cls_b.reserve(sizeof(float) * CR_BINS));
-    PCE_HIP(c, hipMemcpyAsync(cr.cls_w.p, w, sizeof(float) * (size_t)CR_BINS * E, hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, cr.cls_w, w, (size_t)CR_BINS * E);
     w += (int64_t)CR_BINS * E;
-    PCE_HIP(c, hipMemcpyAsync(cr.cls_b.p, w, sizeof(float) * CR_BINS, hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, cr.cls_b, w, (size_t)CR_BINS);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < 6; i++) { cr.c_in[i] = c_in[i]; cr.c_out[i] = c_out[i]; }
     cr.n_emb = E;
@@ -602,10 +596,9 @@ int pce_crepe_run(pce_ctx *c, const pce_crepe_plan *plan)
     const int E = cr.n_emb;
     for (int i = 0; i < 7; i++) {
         const int64_t elems = i == 0 ? CR_IMG1 : i == 6 ? E : crepe_img_elems(cr.c_in, i);
-        PCE_HIP(c, cr.img[i].reserve(sizeof(h16) * (size_t)(elems * F) + 64));
-        PCE_HIP(c, hipMemsetAsync(cr.img[i].p, 0, sizeof(h16) * (size_t)(elems * F) + 64, c->stream));     // the pad rows: once per run
+        PCE_ZERO(h16, c, cr.img[i], (size_t)(elems * F) + 32);                                             // the pad rows: once per run
     }
-    { int rc = crepe_decode_prepare(c, c->n_clips, total); if (rc) return rc; }
+    PCE_TRY(crepe_decode_prepare(c, c->n_clips, total));
     const size_t cls_lds = sizeof(h16) * (size_t)CL_FRAMES * E;
     PCE_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_crepe_classifier), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cls_lds));
     for (int64_t g0 = 0; g0 < total; g0 += F) {
@@ -618,9 +611,8 @@ int pce_crepe_run(pce_ctx *c, const pce_crepe_plan *plan)
         for (int b = 1; b <= 6; b++) {
             const bool last = b == 6;
             const int64_t ofs = last ? E : crepe_img_elems(cr.c_in, b);
-            int rc = crepe_launch_block(c, b, cr.img[b - 1].as<h16>(), cr.c_in[b - 1], cr.c_out[b - 1], cr.w16[b - 1].as<h16>(), cr.bss[b - 1].as<float>(),
-                                        cr.img[b].as<h16>(), ofs, last ? 0 : CR_PADL, n);
-            if (rc) return rc;
+            PCE_TRY(crepe_launch_block(c, b, cr.img[b - 1].as<h16>(), cr.c_in[b - 1], cr.c_out[b - 1], cr.w16[b - 1].as<h16>(), cr.bss[b - 1].as<float>(),
+                                       cr.img[b].as<h16>(), ofs, last ? 0 : CR_PADL, n));
         }
         {
             KernelTimer t(c, PCE_K_CREPE_CLASSIFIER, nullptr, 2.0 * CR_BINS * (double)E * n);
@@ -629,7 +621,7 @@ int pce_crepe_run(pce_ctx *c, const pce_crepe_plan *plan)
         }
         PCE_HIP(c, hipGetLastError());
     }
-    { int rc = crepe_decode(c, c->n_clips, total, plan->lo, plan->hi, plan->decoder); if (rc) return rc; }
+    PCE_TRY(crepe_decode(c, c->n_clips, total, plan->lo, plan->hi, plan->decoder));
     PCE_HIP(c, hipGetLastError());
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     cr.decoder = plan->decoder;
@@ -655,10 +647,10 @@ int pce_crepe_fetch(pce_ctx *c, int32_t clip, int32_t *bins, double *f0, float *
     PCE_HIP(c, hipSetDevice(c->device));
     const int64_t g0 = cr.off[(size_t)clip], nf = cr.off[(size_t)clip + 1] - g0;
     const int *b = cr.decoder == 0 ? cr.bins.as<int>() : cr.amax.as<int>();
-    if (bins) PCE_HIP(c, hipMemcpyAsync(bins, b + g0, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
-    if (f0) PCE_HIP(c, hipMemcpyAsync(f0, cr.f0.as<double>() + g0, sizeof(double) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
-    if (periodicity) PCE_HIP(c, hipMemcpyAsync(periodicity, cr.per.as<float>() + g0, sizeof(float) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
-    if (salience) PCE_HIP(c, hipMemcpyAsync(salience, cr.P.as<float>() + g0 * CR_BINS, sizeof(float) * (size_t)nf * CR_BINS, hipMemcpyDeviceToHost, c->stream));
+    if (bins) PCE_FETCH(c, bins, b + g0, (size_t)nf);
+    if (f0) PCE_FETCH(c, f0, cr.f0.as<double>() + g0, (size_t)nf);
+    if (periodicity) PCE_FETCH(c, periodicity, cr.per.as<float>() + g0, (size_t)nf);
+    if (salience) PCE_FETCH(c, salience, cr.P.as<float>() + g0 * CR_BINS, (size_t)nf * CR_BINS);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -676,21 +668,18 @@ int pce_selftest_crepe_layer(pce_ctx *c, int32_t block, int32_t c_in, int32_t c_
     const int64_t in_row = block == 1 ? CR_IMG1 : (int64_t)(T + CR_PADL + CR_PADR) * c_in;
     const int64_t nw = (int64_t)c_out * (block == 1 ? CR_TAPS1 : CR_TAPS) * c_in, n_out = (int64_t)T_out * c_out;
     DevBuf d_in, d_w, d_bss, d_out;
-    PCE_HIP(c, d_in.reserve(sizeof(h16) * (size_t)(in_row * n_frames) + 64));
-    PCE_HIP(c, d_w.reserve(sizeof(h16) * (size_t)nw + 64));
-    PCE_HIP(c, d_bss.reserve(sizeof(float) * 3 * (size_t)c_out));
+    PCE_ZERO(h16, c, d_in, (size_t)(in_row * n_frames) + 32);
     PCE_HIP(c, d_out.reserve(sizeof(h16) * (size_t)(n_out * n_frames) + 64));
-    PCE_HIP(c, hipMemsetAsync(d_in.p, 0, sizeof(h16) * (size_t)(in_row * n_frames) + 64, c->stream));
     const int64_t x_row = (int64_t)T * c_in, x_off = block == 1 ? CR_PAD1 : (int64_t)CR_PADL * c_in;
     PCE_HIP(c, hipMemcpy2DAsync(d_in.as<h16>() + x_off, sizeof(h16) * (size_t)in_row, x, sizeof(h16) * (size_t)x_row, sizeof(h16) * (size_t)x_row,
                                 (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d_w.p, w, sizeof(h16) * (size_t)nw, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d_bss.p, bias, sizeof(float) * (size_t)c_out, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d_bss.as<float>() + c_out, scale, sizeof(float) * (size_t)c_out, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d_bss.as<float>() + 2 * c_out, shift, sizeof(float) * (size_t)c_out, hipMemcpyHostToDevice, c->stream));
-    { int rc = crepe_launch_block(c, block, d_in.as<h16>(), c_in, c_out, d_w.as<h16>(), d_bss.as<float>(), d_out.as<h16>(), n_out, 0, n_frames); if (rc) return rc; }
+    PCE_UPLOAD(c, d_w, w, (size_t)nw, 32);
+    PCE_UPLOAD(c, d_bss, bias, (size_t)c_out, 2 * (size_t)c_out);      // bias | scale | shift
+    PCE_PUT(c, d_bss.as<float>() + c_out, scale, (size_t)c_out);
+    PCE_PUT(c, d_bss.as<float>() + 2 * c_out, shift, (size_t)c_out);
+    PCE_TRY(crepe_launch_block(c, block, d_in.as<h16>(), c_in, c_out, d_w.as<h16>(), d_bss.as<float>(), d_out.as<h16>(), n_out, 0, n_frames));
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, d_out.p, sizeof(h16) * (size_t)(n_out * n_frames), hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, d_out.p, (size_t)(n_out * n_frames));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -704,13 +693,13 @@ int pce_selftest_crepe_decode(pce_ctx *c, const float *salience, int32_t n_frame
     PCE_HIP(c, hipSetDevice(c->device));
     cr.ran = false;                                               // the results of the last pce_crepe_run are overwritten
     cr.off.assign({0, (int64_t)n_frames});
-    { int rc = crepe_decode_prepare(c, 1, n_frames); if (rc) return rc; }
-    PCE_HIP(c, hipMemcpyAsync(cr.P.p, salience, sizeof(float) * (size_t)n_frames * CR_BINS, hipMemcpyHostToDevice, c->stream));
-    { int rc = crepe_decode(c, 1, n_frames, lo, hi, decoder); if (rc) return rc; }
+    PCE_TRY(crepe_decode_prepare(c, 1, n_frames));
+    PCE_PUT(c, cr.P.p, salience, (size_t)n_frames * CR_BINS);
+    PCE_TRY(crepe_decode(c, 1, n_frames, lo, hi, decoder));
     const int *b = decoder == 0 ? cr.bins.as<int>() : cr.amax.as<int>();
-    if (bins) PCE_HIP(c, hipMemcpyAsync(bins, b, sizeof(int) * (size_t)n_frames, hipMemcpyDeviceToHost, c->stream));
-    if (f0) PCE_HIP(c, hipMemcpyAsync(f0, cr.f0.p, sizeof(double) * (size_t)n_frames, hipMemcpyDeviceToHost, c->stream));
-    if (periodicity) PCE_HIP(c, hipMemcpyAsync(periodicity, cr.per.p, sizeof(float) * (size_t)n_frames, hipMemcpyDeviceToHost, c->stream));
+    if (bins) PCE_FETCH(c, bins, b, (size_t)n_frames);
+    if (f0) PCE_FETCH(c, f0, cr.f0.p, (size_t)n_frames);
+    if (periodicity) PCE_FETCH(c, periodicity, cr.per.p, (size_t)n_frames);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }

@@ -291,9 +291,7 @@ int pce_ctc_align(pce_ctx *c, const float *emissions, int32_t emissions_on_devic
     const float *d_lp = emissions;
     int64_t row_shift = 0;
     if (!emissions_on_device && nf) {
-        const size_t bytes = sizeof(float) * (size_t)(row_hi - row_lo) * (size_t)n_vocab;
-        PCE_HIP(c, d.lp.reserve(bytes));
-        PCE_HIP(c, hipMemcpyAsync(d.lp.p, emissions + row_lo * (int64_t)n_vocab, bytes, hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, d.lp, emissions + row_lo * (int64_t)n_vocab, (size_t)(row_hi - row_lo) * (size_t)n_vocab);
         d_lp = d.lp.as<float>(); row_shift = row_lo;
     }
     for (size_t q = 0; q < n; q++) tab[q].row0 -= row_shift;
@@ -314,16 +312,12 @@ int pce_ctc_align(pce_ctx *c, const float *emissions, int32_t emissions_on_devic
             g0 = ge;
         }
     }
-    PCE_HIP(c, d.tab.reserve(sizeof(CtcClip) * n)); PCE_HIP(c, d.ids.reserve(sizeof(int) * (ids.size() + 1)));
-    PCE_HIP(c, d.tgt.reserve(sizeof(int) * (n_tok + 1))); PCE_HIP(c, d.fin.reserve(sizeof(float) * 2 * n));
+    PCE_HIP(c, d.fin.reserve(sizeof(float) * 2 * n));
     PCE_HIP(c, d.trace.reserve(sizeof(unsigned) * (size_t)(max_group_words + 1))); PCE_HIP(c, d.scratch.reserve(sizeof(float) * (size_t)(scratch_floats + 1)));
     PCE_HIP(c, d.path.reserve(sizeof(int) * (nf + 1))); PCE_HIP(c, d.fscore.reserve(sizeof(float) * (nf + 1)));
     PCE_HIP(c, d.first.reserve(sizeof(int) * (n_tok + 1))); PCE_HIP(c, d.last.reserve(sizeof(int) * (n_tok + 1)));
-    PCE_HIP(c, d.score.reserve(sizeof(float) * n)); PCE_HIP(c, d.status.reserve(sizeof(int) * n));
-    PCE_HIP(c, hipMemcpyAsync(d.tab.p, tab.data(), sizeof(CtcClip) * n, hipMemcpyHostToDevice, c->stream));
-    if (!ids.empty()) PCE_HIP(c, hipMemcpyAsync(d.ids.p, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, c->stream));
-    if (n_tok) PCE_HIP(c, hipMemcpyAsync(d.tgt.p, targets, sizeof(int) * n_tok, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d.status.p, status, sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    PCE_HIP(c, d.score.reserve(sizeof(float) * n));
+    PCE_UPLOAD(c, d.tab, tab); PCE_UPLOAD(c, d.ids, ids, 1); PCE_UPLOAD(c, d.tgt, targets, n_tok, 1); PCE_UPLOAD(c, d.status, status, (size_t)n);
     if (n_tok) { PCE_HIP(c, hipMemsetAsync(d.first.p, 0xFF, sizeof(int) * n_tok, c->stream)); PCE_HIP(c, hipMemsetAsync(d.last.p, 0xFF, sizeof(int) * n_tok, c->stream)); }
     if (nf) { PCE_HIP(c, hipMemsetAsync(d.path.p, 0xFF, sizeof(int) * nf, c->stream)); PCE_HIP(c, hipMemsetAsync(d.fscore.p, 0xFF, sizeof(float) * nf, c->stream)); }
     PCE_HIP(c, hipMemsetAsync(d.score.p, 0xFF, sizeof(float) * n, c->stream));
@@ -352,14 +346,14 @@ int pce_ctc_align(pce_ctx *c, const float *emissions, int32_t emissions_on_devic
         }
         PCE_HIP(c, hipGetLastError());
     }
-    if (nf && path) PCE_HIP(c, hipMemcpyAsync(path, d.path.p, sizeof(int) * nf, hipMemcpyDeviceToHost, c->stream));
-    if (nf && frame_score) PCE_HIP(c, hipMemcpyAsync(frame_score, d.fscore.p, sizeof(float) * nf, hipMemcpyDeviceToHost, c->stream));
+    if (nf && path) PCE_FETCH(c, path, d.path.p, nf);
+    if (nf && frame_score) PCE_FETCH(c, frame_score, d.fscore.p, nf);
     if (n_tok) {
-        PCE_HIP(c, hipMemcpyAsync(tok_first, d.first.p, sizeof(int) * n_tok, hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(tok_last, d.last.p, sizeof(int) * n_tok, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, tok_first, d.first.p, n_tok);
+        PCE_FETCH(c, tok_last, d.last.p, n_tok);
     }
-    PCE_HIP(c, hipMemcpyAsync(score, d.score.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(status, d.status.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, score, d.score.p, n);
+    PCE_FETCH(c, status, d.status.p, n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     // a clip without a path: path -1, frame_score NaN, token frames -1; score NaN unless the sweep ran (PCE_CTC_NO_PATH keeps its final value)

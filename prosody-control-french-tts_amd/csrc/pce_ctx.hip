@@ -13,6 +13,15 @@ int pce_fail(pce_ctx *ctx, int code, const char *fmt, ...)
     if (ctx) ctx->err = buf;
     return code;
 }
+int pce_stage_fail(pce_ctx *c, const char *what, hipError_t e, const char *file, int line)
+{
+    return pce_fail(c, PCE_E_DEVICE, "%s: %s (%s:%d)", what, hipGetErrorString(e), file, line);
+}
+int pce_stage_copy(pce_ctx *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, const char *file, int line)
+{
+    const hipError_t e = bytes ? hipMemcpyAsync(dst, src, bytes, kind, c->stream) : hipSuccess;
+    return e == hipSuccess ? PCE_OK : pce_stage_fail(c, kind == hipMemcpyHostToDevice ? "hipMemcpyAsync to the device" : "hipMemcpyAsync to the host", e, file, line);
+}
 
 KernelTimer::KernelTimer(pce_ctx *ctx, int kid, hipStream_t on, double work_flops) : c(ctx), id(kid), s(on ? on : ctx->stream), flops(work_flops)
 {
@@ -43,7 +52,7 @@ int pce_side_join(pce_ctx *c, int which)
 }
 int pce_join_aux(pce_ctx *c)
 {
-    for (int i = 0; i < pce_ctx::SIDE_COUNT; i++) { int rc = pce_side_join(c, i); if (rc) return rc; }
+    for (int i = 0; i < pce_ctx::SIDE_COUNT; i++) PCE_TRY(pce_side_join(c, i));
     return PCE_OK;
 }
 int pce_side_begin(pce_ctx *c, int which, hipStream_t *out)
@@ -193,7 +202,7 @@ const char *pce_last_error(const pce_ctx *c) { return c ? c->err.c_str() : "null
 int pce_sync(pce_ctx *c)
 {
     if (!c) return PCE_E_INVALID;
-    { int rc = pce_join_aux(c); if (rc) return rc; }
+    PCE_TRY(pce_join_aux(c));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -223,12 +232,12 @@ int pce_stats_enqueue(pce_ctx *c, int32_t slot)
     // this one is still running.  The side streams stay `pending`: whoever reuses their buffers joins them as before.
     // The STFT pass (SIDE_STFT) is not involved: the statistics do not depend on it.
     pce_ctx::Side &sl = c->side[pce_ctx::SIDE_LUFS], &stl = c->side[pce_ctx::SIDE_TAIL];
-    if (c->en_n >= 0) { int rc = pce_energy_stage_enqueue(c, base, st.en_len); if (rc) return rc; }
+    if (c->en_n >= 0) PCE_TRY(pce_energy_stage_enqueue(c, base, st.en_len));
     if (c->lu_n > 0) PCE_HIP(c, hipMemcpyAsync(base + st.off_lu, c->lu_out.p, b_lu, hipMemcpyDeviceToHost, sl.pending ? sl.s : c->stream));
     if (sl.pending) PCE_HIP(c, hipEventRecord(sl.join, sl.s));                  // the join now covers the copy
     if (c->lu_n >= 0) st.lu_status = c->lu_host_status;
     if (c->pi_n >= 0) {
-        int rc = pce_pitch_stage_enqueue(c, base + st.off_pi, stl.pending ? stl.s : c->stream); if (rc) return rc;
+        PCE_TRY(pce_pitch_stage_enqueue(c, base + st.off_pi, stl.pending ? stl.s : c->stream));
         st.pi_frames.resize((size_t)c->pi_n);
         for (int32_t i = 0; i < c->pi_n; i++) st.pi_frames[(size_t)i] = c->pi_frame_off[(size_t)i + 1] - c->pi_frame_off[(size_t)i];
         st.pi_t1 = c->pi_t1; st.pi_status = c->pi_status;
@@ -241,7 +250,7 @@ int pce_stats_enqueue(pce_ctx *c, int32_t slot)
         PCE_HIP(c, hipEventRecord(st.ev, stl.s));
         PCE_HIP(c, hipEventRecord(stl.join, stl.s));                           // later joins cover the copy and the waits
     } else {
-        { int rc = pce_side_join(c, pce_ctx::SIDE_LUFS); if (rc) return rc; }
+        PCE_TRY(pce_side_join(c, pce_ctx::SIDE_LUFS));
         PCE_HIP(c, hipEventRecord(st.ev, c->stream));
     }
     st.armed = true;
@@ -292,8 +301,7 @@ static int set_offsets(pce_ctx *c, const int64_t *offsets, int32_t n_clips, int3
         if (offsets[i + 1] < offsets[i]) return pce_fail(c, PCE_E_INVALID, "offsets must be non-decreasing");
     c->clip_off.assign(offsets, offsets + n_clips + 1);
     c->n_clips = n_clips; c->rate = rate;
-    PCE_HIP(c, c->d_clip_off.reserve(sizeof(int64_t) * (size_t)(n_clips + 1)));
-    PCE_HIP(c, hipMemcpyAsync(c->d_clip_off.p, offsets, sizeof(int64_t) * (size_t)(n_clips + 1), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, c->d_clip_off, offsets, (size_t)(n_clips + 1));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     c->en_n = c->lu_n = c->pi_n = c->in_n = c->si_n = -1; c->st_nfft = 0; c->st_ran = false; c->fr_ran = false; c->py_ran = false; c->cr.ran = false;
     c->en_cache.drop(); c->lu_cache.drop(); c->pi_cache.drop(); c->in_cache.drop();
@@ -304,14 +312,12 @@ int pce_upload_pcm_s16(pce_ctx *c, const int16_t *pcm, const int64_t *offsets, i
 {
     if (!c || !pcm) return PCE_E_INVALID;
     PCE_HIP(c, hipSetDevice(c->device));
-    { int rc = pce_join_aux(c); if (rc) return rc; }           // side-stream kernels may still read the old batch
-    int st = set_offsets(c, offsets, n_clips, rate);
-    if (st) return st;
+    PCE_TRY(pce_join_aux(c));                                  // side-stream kernels may still read the old batch
+    PCE_TRY(set_offsets(c, offsets, n_clips, rate));
     size_t total = (size_t)offsets[n_clips];
     // 64 bytes of zero slack so that 16-byte vector loads may run past the last sample
-    PCE_HIP(c, c->pcm_own.reserve(total * 2 + 64));
-    PCE_HIP(c, hipMemsetAsync((char *)c->pcm_own.p + total * 2, 0, 64, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(c->pcm_own.p, pcm, total * 2, hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, c->pcm_own, pcm, total, 32);
+    PCE_HIP(c, hipMemsetAsync(c->pcm_own.as<int16_t>() + total, 0, 64, c->stream));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     c->d_pcm = c->pcm_own.as<const int16_t>();
     return PCE_OK;
@@ -322,9 +328,8 @@ int pce_bind_pcm_s16_device(pce_ctx *c, const void *d_pcm, const int64_t *offset
     if (!c || !d_pcm) return PCE_E_INVALID;
     if (((uintptr_t)d_pcm) & 15) return pce_fail(c, PCE_E_INVALID, "device PCM pointer must be 16-byte aligned");
     PCE_HIP(c, hipSetDevice(c->device));
-    { int rc = pce_join_aux(c); if (rc) return rc; }
-    int st = set_offsets(c, offsets, n_clips, rate);
-    if (st) return st;
+    PCE_TRY(pce_join_aux(c));
+    PCE_TRY(set_offsets(c, offsets, n_clips, rate));
     c->d_pcm = (const int16_t *)d_pcm;
     return PCE_OK;
 }

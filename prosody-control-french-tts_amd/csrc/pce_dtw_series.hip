@@ -217,20 +217,11 @@ int pce_dtw_series(pce_ctx *c, const double *a, const int64_t *a_off, const doub
 
     PCE_HIP(c, hipSetDevice(c->device));
     pce_ctx::DtwSeries &w = c->ds;
-    PCE_HIP(c, w.a.reserve(sizeof(double) * na)); PCE_HIP(c, w.b.reserve(sizeof(double) * nb));
     PCE_HIP(c, w.pi.reserve(sizeof(int) * no)); PCE_HIP(c, w.pj.reserve(sizeof(int) * no));
-    PCE_HIP(c, w.dist.reserve(sizeof(double) * (size_t)batch)); PCE_HIP(c, w.len.reserve(sizeof(int) * (size_t)batch)); PCE_HIP(c, w.status.reserve(sizeof(int) * (size_t)batch));
-    PCE_HIP(c, hipMemcpyAsync(w.a.p, a, sizeof(double) * na, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w.b.p, b, sizeof(double) * nb, hipMemcpyHostToDevice, c->stream));
-    if (win_lo) {
-        PCE_HIP(c, w.lo.reserve(sizeof(int) * na)); PCE_HIP(c, w.hi.reserve(sizeof(int) * na));
-        PCE_HIP(c, hipMemcpyAsync(w.lo.p, win_lo, sizeof(int) * na, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(w.hi.p, win_hi, sizeof(int) * na, hipMemcpyHostToDevice, c->stream));
-    }
+    PCE_UPLOAD(c, w.a, a, na); PCE_UPLOAD(c, w.b, b, nb);
+    if (win_lo) { PCE_UPLOAD(c, w.lo, win_lo, na); PCE_UPLOAD(c, w.hi, win_hi, na); }
     // the host's initial values (inf / NaN, no path / empty, 0) are the device's too
-    PCE_HIP(c, hipMemcpyAsync(w.dist.p, dist, sizeof(double) * (size_t)batch, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w.status.p, status, sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w.len.p, path_len, sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, w.dist, dist, (size_t)batch); PCE_UPLOAD(c, w.status, status, (size_t)batch); PCE_UPLOAD(c, w.len, path_len, (size_t)batch);
 
     // groups of consecutive pairs whose traces fit the budget together
     for (size_t g0 = 0; g0 < plans.size();) {
@@ -273,13 +264,9 @@ int pce_dtw_series(pce_ctx *c, const double *a, const int64_t *a_off, const doub
                 threads[(size_t)L] = std::max(threads[(size_t)L], (int)div_up(Rs, 64) * 64);
             }
         }
-        PCE_HIP(c, w.pairs.reserve(sizeof(DsPair) * dp.size())); PCE_HIP(c, w.tab.reserve(sizeof(long long) * (tab.size() + 1)));
-        PCE_HIP(c, w.tiles.reserve(sizeof(DsTile) * (sorted.size() + 1)));
         PCE_HIP(c, w.rows.reserve(sizeof(double) * (size_t)row_words)); PCE_HIP(c, w.cols.reserve(sizeof(double) * (size_t)col_words));
         PCE_HIP(c, w.trace.reserve(sizeof(unsigned) * (size_t)(tr + 1)));
-        PCE_HIP(c, hipMemcpyAsync(w.pairs.p, dp.data(), sizeof(DsPair) * dp.size(), hipMemcpyHostToDevice, c->stream));
-        if (!tab.empty()) PCE_HIP(c, hipMemcpyAsync(w.tab.p, tab.data(), sizeof(long long) * tab.size(), hipMemcpyHostToDevice, c->stream));
-        if (!sorted.empty()) PCE_HIP(c, hipMemcpyAsync(w.tiles.p, sorted.data(), sizeof(DsTile) * sorted.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, w.pairs, dp); PCE_UPLOAD(c, w.tab, tab, 1); PCE_UPLOAD(c, w.tiles, sorted, 1);
         {
             KernelTimer t(c, PCE_K_DTW_SERIES, nullptr, cells);
             for (int L = 0; L < n_diag; L++) {
@@ -302,12 +289,12 @@ int pce_dtw_series(pce_ctx *c, const double *a, const int64_t *a_off, const doub
         g0 = g1;
     }
     if (no) {
-        PCE_HIP(c, hipMemcpyAsync(path_i, w.pi.p, sizeof(int) * no, hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(path_j, w.pj.p, sizeof(int) * no, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, path_i, w.pi.p, no);
+        PCE_FETCH(c, path_j, w.pj.p, no);
     }
-    PCE_HIP(c, hipMemcpyAsync(path_len, w.len.p, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dist, w.dist.p, sizeof(double) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(status, w.status.p, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, path_len, w.len.p, (size_t)batch);
+    PCE_FETCH(c, dist, w.dist.p, (size_t)batch);
+    PCE_FETCH(c, status, w.status.p, (size_t)batch);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     // the walk wrote every path at the end of its room: move it to the front

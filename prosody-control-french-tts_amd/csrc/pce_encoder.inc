@@ -77,7 +77,7 @@ int pce_whisper_load(pce_ctx *c, const pce_whisper_dims *dims, const float *weig
     if (n_floats != expect) return pce_fail(c, PCE_E_INVALID, "weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
     PCE_HIP(c, hipSetDevice(c->device));
     WhisperState *w = ws_of(c);
-    { const int rc = lds_optins(c, w); if (rc) return rc; }
+    PCE_TRY(lds_optins(c, w));
     w->dims = *dims; w->loaded = false; w->layers.assign((size_t)L, {});
     WeightPack pk;
     const float *p = weights;
@@ -114,9 +114,8 @@ int pce_whisper_load(pce_ctx *c, const pce_whisper_dims *dims, const float *weig
             }
     }
     DevBuf tmp;
-    if (const int rc = upload_weights(c, pk, tmp, w->w_bf16, w->w_f32)) return rc;
-    PCE_HIP(c, w->pos.reserve(sizeof(float) * pos.size()));
-    PCE_HIP(c, hipMemcpyAsync(w->pos.p, pos.data(), sizeof(float) * pos.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_TRY(upload_weights(c, pk, tmp, w->w_bf16, w->w_f32));
+    PCE_UPLOAD(c, w->pos, pos);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     w->loaded = true;
     return PCE_OK;
@@ -157,8 +156,7 @@ int pce_whisper_encode_run(pce_ctx *c)
                                    // batch size, so a steady stream of equal batches uploads (and waits for) them once
         std::vector<int> tab((size_t)2 * n);
         for (int i = 0; i < n; i++) { tab[(size_t)i] = i * W_CTX; tab[(size_t)n + i] = W_CTX; }
-        PCE_HIP(c, w->enc_tab.reserve(sizeof(int) * tab.size()));
-        PCE_HIP(c, hipMemcpyAsync(w->enc_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, w->enc_tab, tab);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         w->enc_tab_clips = n;
     }
@@ -286,7 +284,7 @@ int pce_whisper_encode_fetch(pce_ctx *c, int32_t clip, float *out)
     if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "pce_whisper_encode_fetch before pce_whisper_encode_run");
     if (clip < 0 || clip >= w->n_clips_enc) return pce_fail(c, PCE_E_INVALID, "clip out of range");
     const size_t per = (size_t)W_CTX * (size_t)w->dims.n_state;
-    PCE_HIP(c, hipMemcpyAsync(out, w->final_out.as<float>() + per * (size_t)clip, sizeof(float) * per, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, w->final_out.as<float>() + per * (size_t)clip, per);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;

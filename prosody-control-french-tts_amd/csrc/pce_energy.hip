@@ -163,9 +163,7 @@ int pce_energy_plan(pce_ctx *c, const pce_slice *slices, int32_t n, DevBuf &work
         }
     }
     PCE_HIP(c, out_buf.reserve(sizeof(EnAcc) * (size_t)(n > 0 ? n : 1)));
-    PCE_HIP(c, work_buf.reserve(sizeof(EnWork) * (work.size() + 1)));
-    if (!work.empty())
-        PCE_HIP(c, hipMemcpyAsync(work_buf.p, work.data(), sizeof(EnWork) * work.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, work_buf, work, 1);
     PCE_HIP(c, hipStreamSynchronize(c->stream));   // `work` is pageable and dies at return
     *n_work = (int64_t)work.size();
     return PCE_OK;
@@ -219,7 +217,7 @@ int pce_energy_run(pce_ctx *c, const pce_slice *slices, int32_t n, int32_t loud_
     if (!c->d_pcm) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
     PCE_HIP(c, hipSetDevice(c->device));
     if (c->lu_reads_en_out) {                                    // a LUFS chain on its side stream reads the peaks of the previous run out of en_out
-        int rc = pce_side_join(c, pce_ctx::SIDE_LUFS); if (rc) return rc;
+        PCE_TRY(pce_side_join(c, pce_ctx::SIDE_LUFS));
         c->lu_reads_en_out = false;
     }
     if (!c->en_cache.same(slices, n)) {
@@ -241,7 +239,7 @@ int pce_energy_fetch(pce_ctx *c, pce_energy *out)
     PCE_HIP(c, hipSetDevice(c->device));
     std::vector<EnAcc> acc((size_t)(c->en_n > 0 ? c->en_n : 1));
     if (c->en_n > 0)
-        PCE_HIP(c, hipMemcpyAsync(acc.data(), c->en_out.p, sizeof(EnAcc) * (size_t)c->en_n, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, acc.data(), c->en_out.p, (size_t)c->en_n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     for (int32_t i = 0; i < c->en_n; i++) {

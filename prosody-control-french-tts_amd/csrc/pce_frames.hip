@@ -139,10 +139,9 @@ int pce_frame_energy_run(pce_ctx *c, int32_t window, int32_t hop, int32_t requan
         if (nf > max_frames) max_frames = nf;
     }
     const int64_t total = c->fr_off[(size_t)c->n_clips];
-    PCE_HIP(c, c->fr_doff.reserve(sizeof(int64_t) * ((size_t)c->n_clips + 1)));
     PCE_HIP(c, c->fr_sum.reserve(sizeof(long long) * (size_t)(total > 0 ? total : 1)));
     PCE_HIP(c, c->fr_cnt.reserve(sizeof(int) * (size_t)(total > 0 ? total : 1)));
-    PCE_HIP(c, hipMemcpyAsync(c->fr_doff.p, c->fr_off.data(), sizeof(int64_t) * ((size_t)c->n_clips + 1), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, c->fr_doff, c->fr_off.data(), (size_t)c->n_clips + 1);
     if (total > 0) {
         const unsigned gy = (unsigned)(c->n_clips < 65535 ? c->n_clips : 65535);
         const int per_wg = (FR_THREADS / 64) * (window <= 1024 ? FR_FPW : 1);     // frames per workgroup and trip
@@ -180,9 +179,9 @@ int pce_frame_energy_fetch(pce_ctx *c, int32_t clip, int64_t *sum_sq, int32_t *c
     PCE_HIP(c, hipSetDevice(c->device));
     const int64_t f0 = c->fr_off[(size_t)clip], nf = c->fr_off[(size_t)clip + 1] - f0;
     if (nf > 0 && sum_sq)
-        PCE_HIP(c, hipMemcpyAsync(sum_sq, c->fr_sum.as<long long>() + f0, sizeof(int64_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, sum_sq, c->fr_sum.as<long long>() + f0, (size_t)nf);
     if (nf > 0 && count)
-        PCE_HIP(c, hipMemcpyAsync(count, c->fr_cnt.as<int>() + f0, sizeof(int32_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, count, c->fr_cnt.as<int>() + f0, (size_t)nf);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;

@@ -14,12 +14,11 @@
 //     everything that moves is a scalar offset (no address arithmetic, no 64-bit pointers in VGPRs);
 //   * 8 waves as 2 (M) x 4 (N); a wave owns 64 rows of EACH A half and 32 columns of EACH B half, so each of its four
 //     64 x 32 quadrants touches one A half and one B half;
-//   * round 3 (F_PINGPONG, the form that runs): a K-step is four phases of [LDS reads of the phase's new fragments + one half-tile
+//   * round 3 (the ping-pong K-step): a K-step is four phases of [LDS reads of the phase's new fragments + one half-tile
 //     staged + wait] barrier [16 MFMAs] barrier, and wave row 1 runs one barrier behind wave row 0, so the two waves of a SIMD are
-//     always in opposite sections (kstep_pp below); the rows meet for the epilogue.  1 006 -> 1 076 TFLOP/s over the encoder's
+//     always in opposite sections (kstep below); the rows meet for the epilogue.  1 006 -> 1 076 TFLOP/s over the encoder's
 //     launches on one box (same-box A/B of the two builds), results bit-identical;
-//   * rounds 2-3a (F_PINGPONG = false, kept for A/B): two barriers per K-step, all eight waves in step, fragments read two MFMA
-//     groups (or a barrier) ahead of their first use into registers whose last use is behind them;
+//   * rounds 2-3a ran two barriers per K-step with all eight waves in step: measured and retired, see profiles/r03;
 //   * 64 fragment VGPRs + 128 accumulator VGPRs, no spills (205-217 VGPRs);
 //   * MFMA operands are swapped (D^T = B A^T) and the B rows of every 32-row group are permuted at staging time, so a
 //     lane ends up with 8 CONSECUTIVE COLUMNS of one row: rows leave as 16-byte buffer stores straight from the
@@ -51,7 +50,6 @@
 
 constexpr int F_T = 256, F_K = 64, F_THREADS = 512;
 constexpr int F_N_MAX = 6144;            // widest output launch_gemm_flat takes: the bias row of a tile column lives in LDS (ring + N floats)
-constexpr bool F_PINGPONG = true;                          // K-step form: four phases, wave rows one barrier apart (kstep_pp) / two barriers, rows in step (kstep)
 constexpr int F_HALF = 128 * F_K;                          // elements of a half-tile (16 KB)
 constexpr int F_RING_BYTES = 8 * F_HALF * 2;
 enum { FEPI_BF16 = 0, FEPI_GELU = 1, FEPI_VT = 2, FEPI_SPLIT = 3, FEPI_RESID = 4 };
@@ -118,7 +116,7 @@ __device__ __forceinline__ void f_read_B(FFrags &F, const op_t *dsm, const int (
         if (HALF) F.RB1[KK][j] = v; else F.RB0[KK][j] = v;
     }
 }
-template <bool VT, int HA, int HB, int KK, bool ZERO>
+template <bool VT, int HA, int HB, int KK>
 __device__ __forceinline__ void f_mma8(f32x4 (&acc)[2][2][4][2], const FFrags &F)
 {
 #pragma unroll
@@ -126,9 +124,8 @@ __device__ __forceinline__ void f_mma8(f32x4 (&acc)[2][2][4][2], const FFrags &F
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             const opx8 b = HB ? F.RB1[KK][j] : F.RB0[KK][j];
-            const f32x4 c = ZERO ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[HA][HB][i][j];
-            acc[HA][HB][i][j] = VT ? mfma16(F.RA[KK][i], b, c)
-                                   : mfma16(b, F.RA[KK][i], c);
+            acc[HA][HB][i][j] = VT ? mfma16(F.RA[KK][i], b, acc[HA][HB][i][j])
+                                   : mfma16(b, F.RA[KK][i], acc[HA][HB][i][j]);
         }
 }
 
@@ -367,7 +364,7 @@ __global__ __launch_bounds__(F_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
     constexpr int EPI_OPS = 16;                              // vector-memory operations of the epilogue that sit in the vmcnt queue, AT LEAST (the V^T form issues one or
                                                              // two more when a clip boundary cuts a lane's 8 positions: the counted waits then wait for those too, which is safe)
 
-    // ---- prologue: all of K-step 0, the first three half-tiles of K-step 1; then the fragments "the second half of step -1" reads
+    // ---- prologue: all of K-step 0, the first three half-tiles of K-step 1
     {
         FCursor c0; c0.kofs = 0; set_tile(c0, 0);
         it1 = 0; kt1 = 0; pc1 = c0; advance(pc1, it1, kt1);
@@ -377,52 +374,20 @@ __global__ __launch_bounds__(F_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
         issue(pc1, 0, 1); issue(pc1, 1, 1); issue(pc1, 2, 1);
         f_wait_vm<6>();
         __builtin_amdgcn_s_barrier();
-        if constexpr (!F_PINGPONG) {
-            f_read_A<0, 0>(F, dsm, ra, 0); f_read_B<0, 0>(F, dsm, rb, 0); f_read_B<0, 1>(F, dsm, rb, 0); f_read_B<1, 1>(F, dsm, rb, 0);
-            f_wait_lgkm<0>();
-        }
     }
     int c_m0, c_n0;
     S.tile(0, c_m0, c_n0);
     int par = 0;
-    // K-step s (ring parity par).  MFMA groups (8 each): first half (0,0)k0 (0,1)k0 (0,0)k1 (0,1)k1, second half (1,1)k0 (1,0)k0 (1,1)k1
-    // (1,0)k1; fragment reads are issued two groups (or a barrier) before their first use.  DMA: the first half issues A-bottom(s+1), the
-    // second half A-top(s+2), B-left(s+2), B-right(s+2); a half-tile lands at the latest by the end of the half after the one that
-    // issued it.  FIRST: the previous tile's stores still sit among the youngest operations at the end of the first half.
-#define F_GROUP(HA, HB, KK) __builtin_amdgcn_s_setprio(1); f_mma8<VT, HA, HB, KK, false>(acc, F); \
+#define F_GROUP(HA, HB, KK) __builtin_amdgcn_s_setprio(1); f_mma8<VT, HA, HB, KK>(acc, F);        \
                              __builtin_amdgcn_s_setprio(0); __builtin_amdgcn_sched_barrier(0);
 #define F_ISSUE(C, KIND, PAR) __builtin_amdgcn_sched_barrier(0); issue(C, KIND, PAR); __builtin_amdgcn_sched_barrier(0);
     constexpr bool VT = EPI == FEPI_VT;                      // MFMA operand order (a split launch computes its transposed tiles as the transposed problem: same order)
-    auto kstep = [&](bool first_stores) {
-        __builtin_amdgcn_s_barrier();
-        F_ISSUE(pc1, 3, par ^ 1)
-        f_read_A<1, 0>(F, dsm, ra, par); f_read_B<1, 0>(F, dsm, rb, par);
-        f_wait_lgkm<6>(); F_GROUP(0, 0, 0)
-        F_GROUP(0, 1, 0)
-        f_read_A<0, 1>(F, dsm, ra, par);
-        f_wait_lgkm<4>(); F_GROUP(0, 0, 1)
-        F_GROUP(0, 1, 1)
-        if (first_stores) f_wait_vm<2 + EPI_OPS>(); else f_wait_vm<2>();    // (the first tile has no stores in the queue: counting them let K-step 1 be read before it landed)
-        f_wait_lgkm<0>();
-        __builtin_amdgcn_s_barrier();
-        F_ISSUE(pc2, 0, par)
-        f_read_A<1, 1>(F, dsm, ra, par);
-        f_wait_lgkm<4>(); F_GROUP(1, 1, 0)
-        F_ISSUE(pc2, 1, par)
-        f_read_B<0, 1>(F, dsm, rb, par ^ 1);
-        f_wait_lgkm<2>(); F_GROUP(1, 0, 0)
-        F_ISSUE(pc2, 2, par)
-        f_read_A<0, 0>(F, dsm, ra, par ^ 1); f_read_B<0, 0>(F, dsm, rb, par ^ 1);
-        f_wait_lgkm<6>(); F_GROUP(1, 1, 1)
-        f_read_B<1, 1>(F, dsm, rb, par ^ 1);
-        f_wait_lgkm<2>(); F_GROUP(1, 0, 1)
-    };
-    // Ping-pong form of a K-step (round 3): FOUR phases, each = [read this phase's new fragments out of LDS, stage one half-tile of a later
+    // K-step s (ring parity par), the ping-pong form of round 3: FOUR phases, each = [read this phase's new fragments out of LDS, stage one half-tile of a later
     // K-step, wait for the reads] barrier [16 MFMAs: one 64 x 32 quadrant over the whole K-step] barrier, and wave row 1 runs ONE BARRIER
     // BEHIND wave row 0 (an extra barrier before its first K-step, one for row 0 after its last): the two waves of a SIMD (w and w + 4) are
     // then always in opposite sections -- one owns the matrix pipe while the other issues its LDS reads and DMA and waits.  (In the
-    // two-barrier form above both partners want the pipe at the same time and sit at the barrier / counted wait at the same time: PMC,
-    // profiles/r03: waves 23 % issuing, 30 % parked, 48 % stalled at issue; pipe 58 % busy.)
+    // two-barrier form of rounds 2-3a both partners wanted the pipe at the same time and sat at the barrier / counted wait at the same time:
+    // PMC, profiles/r03: waves 23 % issuing, 30 % parked, 48 % stalled at issue; pipe 58 % busy.)
     // Quadrant order (0,0) (0,1) (1,1) (1,0): phase 1 reads A-top + B-left (12 ds_read_b128), phase 2 B-right (4), phase 3 A-bottom (8, over
     // A-top's registers), phase 4 nothing (B-left is still in its registers).  Staging: phase 1 A-bottom(s+1), phase 2 A-top(s+2), phase 3
     // B-left(s+2), phase 4 B-right(s+2): a slot is re-staged at least one interval after BOTH rows read it (A-top and B-left are read in
@@ -432,7 +397,7 @@ __global__ __launch_bounds__(F_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
     // after_stores: 1 = the first K-step after an epilogue (its 16+ stores sit in the in-order vmcnt queue behind the three half-tiles
     // K-step s + 1 reads first: the wait lets them and this K-step's 8 DMA instructions stay in flight), 2 = the second (A-bottom(s+1) was
     // staged after the stores: waited for at the end of phase 2, as late as its first read allows: the stores must have completed by then).
-    auto kstep_pp = [&](int after_stores) {
+    auto kstep = [&](int after_stores) {
         f_read_A<0, 0>(F, dsm, ra, par); f_read_A<1, 0>(F, dsm, ra, par); f_read_B<0, 0>(F, dsm, rb, par); f_read_B<1, 0>(F, dsm, rb, par);
         F_ISSUE(pc1, 3, par ^ 1)
         f_wait_lgkm<0>();
@@ -458,23 +423,21 @@ __global__ __launch_bounds__(F_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
         F_GROUP(1, 0, 0) F_GROUP(1, 0, 1)
         __builtin_amdgcn_s_barrier();
     };
-    if (F_PINGPONG && wr == 1) __builtin_amdgcn_s_barrier();
+    if (wr == 1) __builtin_amdgcn_s_barrier();
     for (int it = 0; it < S.my_tiles; it++) {
         const bool cur_vt = SPLIT ? (c_n0 >= P.vt_n0) : (EPI == FEPI_VT);            // workgroup-uniform
         for (int kt = 0; kt < nk; kt++) {
-            const bool first = kt == 0, last = kt == nk - 1;
-            if constexpr (F_PINGPONG) kstep_pp(it > 0 && nk >= 2 ? (kt == 0 ? 1 : kt == 1 ? 2 : 0) : 0);   // (a one-step K loop waits for its stores: plain counts)
-            else kstep(first && it > 0);
+            const bool last = kt == nk - 1;
+            kstep(it > 0 && nk >= 2 ? (kt == 0 ? 1 : kt == 1 ? 2 : 0) : 0);   // (a one-step K loop waits for its stores: plain counts)
             pc1 = pc2; it1 = it2; kt1 = kt2; advance(pc2, it2, kt2);
             if (last) {
                 // the two wave rows write their halves of the tile AT THE SAME TIME: row 0 lets row 1 finish its last phase first (one extra
                 // barrier), and row 1 falls one barrier behind again after the stores; left one barrier apart, each row's epilogue stood in an
                 // interval of its own while the other row waited at the next barrier -- two epilogue times per tile instead of one
-                if (F_PINGPONG && wr == 0) __builtin_amdgcn_s_barrier();
+                if (wr == 0) __builtin_amdgcn_s_barrier();
                 if constexpr (SPLIT) { if (cur_vt) store_vtT(c_m0, c_n0); else store_rm(c_m0, c_n0); }
                 else if constexpr (EPI == FEPI_VT) store_vt(c_m0, c_n0, c_n0);
                 else store_rm(c_m0, c_n0);
-                if constexpr (!F_PINGPONG) f_wait_vm<6 + EPI_OPS>();
                 // (starting the next tile from the zero CONSTANT instead -- v_mfma ..., 0 -- lets the register allocator place the fresh destination
                 // on top of a dying A fragment; this multi-pass MFMA reads its sources while it already writes results: wrong values in a few lanes)
 #pragma unroll
@@ -485,14 +448,14 @@ __global__ __launch_bounds__(F_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2)
                         for (int i = 0; i < 4; i++)
 #pragma unroll
                             for (int j = 0; j < 2; j++) acc[a][b][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (F_PINGPONG && wr == 1) __builtin_amdgcn_s_barrier();
-            } else if constexpr (!F_PINGPONG) f_wait_vm<6>();
+                if (wr == 1) __builtin_amdgcn_s_barrier();
+            }
             f_wait_lgkm<0>();
             par ^= 1;
         }
         if (it + 1 < S.my_tiles) S.tile(it + 1, c_m0, c_n0);
     }
-    if (F_PINGPONG && wr == 0) __builtin_amdgcn_s_barrier();
+    if (wr == 0) __builtin_amdgcn_s_barrier();
     f_wait_vm<0>();                                           // the surplus refills land before the workgroup (and its LDS allocation) ends
 #undef F_GROUP
 #undef F_ISSUE

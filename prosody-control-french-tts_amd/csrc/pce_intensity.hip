@@ -185,8 +185,7 @@ int pce_intensity_plan(pce_ctx *c, const pce_intensity_params *p, const pce_slic
     if (!c || !p || (!slices && n > 0) || n < 0 || !frame_offsets) return PCE_E_INVALID;
     if (c->rate <= 0) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
     std::vector<int64_t> fo; std::vector<int32_t> st; std::vector<double> t1;
-    int rc = intensity_plan_slices(c, p, slices, n, fo, st, t1);
-    if (rc) return rc;
+    PCE_TRY(intensity_plan_slices(c, p, slices, n, fo, st, t1));
     memcpy(frame_offsets, fo.data(), sizeof(int64_t) * (size_t)(n + 1));
     if (status && n > 0) memcpy(status, st.data(), sizeof(int32_t) * (size_t)n);
     return PCE_OK;
@@ -202,8 +201,7 @@ int pce_intensity_run(pce_ctx *c, const pce_intensity_params *p, const double *t
                       (n_taps <= 0 || memcmp(c->in_taps_host.data(), taps, sizeof(double) * (size_t)n_taps) == 0);
     if (!same) {
         c->in_n = -1; c->in_params_valid = false; c->in_cache.drop();
-        int rc = intensity_plan_slices(c, p, slices, n, c->in_frame_off, c->in_status, c->in_t1);
-        if (rc) return rc;
+        PCE_TRY(intensity_plan_slices(c, p, slices, n, c->in_frame_off, c->in_status, c->in_t1));
         const double dx = 1.0 / (double)c->rate;
         const double window = 6.4 / p->pitch_floor, half = 0.5 * window;
         const double dt = p->time_step <= 0.0 ? 0.8 / p->pitch_floor : p->time_step;
@@ -233,14 +231,9 @@ int pce_intensity_run(pce_ctx *c, const pce_intensity_params *p, const double *t
             for (int32_t f = 0; f < m.n_frames; f += fpb) work.push_back({i, f});
         }
         const int64_t total = c->in_frame_off[(size_t)n];
-        PCE_HIP(c, c->in_meta.reserve(sizeof(InSlice) * meta.size()));
-        PCE_HIP(c, c->in_work.reserve(sizeof(InWork) * (work.size() + 1)));
-        PCE_HIP(c, c->in_taps.reserve(sizeof(double) * (size_t)n_taps));
         PCE_HIP(c, c->in_out.reserve(sizeof(double) * (size_t)(total > 0 ? total : 1)));
         PCE_HIP(c, c->in_summary.reserve(sizeof(InSummaryDev) * meta.size()));
-        PCE_HIP(c, hipMemcpyAsync(c->in_meta.p, meta.data(), sizeof(InSlice) * meta.size(), hipMemcpyHostToDevice, c->stream));
-        if (!work.empty()) PCE_HIP(c, hipMemcpyAsync(c->in_work.p, work.data(), sizeof(InWork) * work.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(c->in_taps.p, taps, sizeof(double) * (size_t)n_taps, hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, c->in_meta, meta); PCE_UPLOAD(c, c->in_work, work, 1); PCE_UPLOAD(c, c->in_taps, taps, (size_t)n_taps);
         PCE_HIP(c, hipStreamSynchronize(c->stream));             // the sources are pageable and die at return
         c->in_n_work = (int64_t)work.size();
         c->in_total_frames = total;
@@ -275,8 +268,8 @@ int pce_intensity_fetch(pce_ctx *c, double *values, pce_intensity_summary *summa
     const int32_t n = c->in_n;
     const int64_t total = c->in_total_frames;
     std::vector<InSummaryDev> sd((size_t)(n > 0 ? n : 1));
-    if (values && total > 0) PCE_HIP(c, hipMemcpyAsync(values, c->in_out.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-    if (summary && n > 0) PCE_HIP(c, hipMemcpyAsync(sd.data(), c->in_summary.p, sizeof(InSummaryDev) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (values && total > 0) PCE_FETCH(c, values, c->in_out.p, (size_t)total);
+    if (summary && n > 0) PCE_FETCH(c, sd.data(), c->in_summary.p, (size_t)n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     if (summary)

@@ -220,6 +220,44 @@ int pce_fail(pce_ctx *ctx, int code, const char *fmt, ...);
         if (e__ != hipSuccess)                                                                  \
             return pce_fail((ctx), PCE_E_DEVICE, "%s: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); \
     } while (0)
+#define PCE_TRY(expr) do { const int rc__ = (expr); if (rc__) return rc__; } while (0)
+
+// Host <-> device staging on c->stream.  Counts are in ELEMENTS of T, the only multiplications by sizeof(T) are the ones below, and a failure reads like
+// PCE_HIP's, with the caller's file and line.  A helper takes a buffer's .p only after its own reserve; none synchronises.
+int pce_stage_fail(pce_ctx *c, const char *what, hipError_t e, const char *file, int line);
+int pce_stage_copy(pce_ctx *c, void *dst, const void *src, size_t bytes, hipMemcpyKind kind, const char *file, int line);
+// reserve count + slack elements in b, copy count of them from the host (src == nullptr with count == 0: reserve only)
+template <class T> static inline int pce_upload_at(pce_ctx *c, const char *file, int line, DevBuf &b, const T *src, size_t count, size_t slack = 0)
+{
+    const hipError_t e = b.reserve(sizeof(T) * (count + slack));
+    if (e != hipSuccess) return pce_stage_fail(c, "reserve", e, file, line);
+    return count ? pce_stage_copy(c, b.p, src, sizeof(T) * count, hipMemcpyHostToDevice, file, line) : PCE_OK;
+}
+template <class T> static inline int pce_upload_at(pce_ctx *c, const char *file, int line, DevBuf &b, const std::vector<T> &src, size_t slack = 0)
+{
+    return pce_upload_at(c, file, line, b, src.data(), src.size(), slack);
+}
+// count elements from the host into a range of a buffer that is already reserved
+template <class T> static inline int pce_put_at(pce_ctx *c, const char *file, int line, void *dst, const T *src, size_t count)
+{
+    return pce_stage_copy(c, dst, src, sizeof(T) * count, hipMemcpyHostToDevice, file, line);
+}
+// reserve count + slack elements of T in b, zero the first count
+template <class T> static inline int pce_zero_at(pce_ctx *c, const char *file, int line, DevBuf &b, size_t count, size_t slack = 0)
+{
+    hipError_t e = b.reserve(sizeof(T) * (count + slack));
+    if (e == hipSuccess && count) e = hipMemsetAsync(b.p, 0, sizeof(T) * count, c->stream);
+    return e == hipSuccess ? PCE_OK : pce_stage_fail(c, "reserve + memset", e, file, line);
+}
+// count elements back to the host
+template <class T> static inline int pce_fetch_at(pce_ctx *c, const char *file, int line, T *dst, const void *src, size_t count)
+{
+    return pce_stage_copy(c, dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, file, line);
+}
+#define PCE_UPLOAD(c, ...) PCE_TRY(pce_upload_at((c), __FILE__, __LINE__, __VA_ARGS__))
+#define PCE_PUT(c, ...) PCE_TRY(pce_put_at((c), __FILE__, __LINE__, __VA_ARGS__))
+#define PCE_ZERO(T, c, ...) PCE_TRY(pce_zero_at<T>((c), __FILE__, __LINE__, __VA_ARGS__))
+#define PCE_FETCH(c, ...) PCE_TRY(pce_fetch_at((c), __FILE__, __LINE__, __VA_ARGS__))
 
 // Kernel-launch bracket for the profiler: records events around the launch when enabled.
 struct KernelTimer {

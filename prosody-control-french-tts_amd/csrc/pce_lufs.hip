@@ -332,21 +332,12 @@ static int lufs_plan(pce_ctx *c, const pce_slice *slices, int32_t n)
     static_assert(sizeof(LuCoef) == sizeof(double) * 13, "LuCoef layout");
     memcpy(c->lu_coef, &k, sizeof k);
 
-    PCE_HIP(c, c->lu_meta.reserve(sizeof(LuSlice) * hs.size()));
-    PCE_HIP(c, c->lu_chunks.reserve(sizeof(LuChunk) * (chunks.size() + 1)));
-    PCE_HIP(c, c->lu_blocks.reserve(sizeof(LuBlock) * (blocks.size() + 1)));
-    PCE_HIP(c, c->lu_pow.reserve(sizeof(double) * pw.size()));
     PCE_HIP(c, c->lu_state_end.reserve(sizeof(double) * 4 * (chunks.size() + 1)));
     PCE_HIP(c, c->lu_state_init.reserve(sizeof(double) * 4 * (chunks.size() + 1)));
     PCE_HIP(c, c->lu_energy.reserve(sizeof(double) * (chunks.size() + 1)));
     PCE_HIP(c, c->lu_zbuf.reserve(sizeof(double) * (blocks.size() + 1)));   // per-block z scratch
     PCE_HIP(c, c->lu_out.reserve(sizeof(double) * hs.size()));
-    PCE_HIP(c, hipMemcpyAsync(c->lu_meta.p, hs.data(), sizeof(LuSlice) * hs.size(), hipMemcpyHostToDevice, c->stream));
-    if (!chunks.empty())
-        PCE_HIP(c, hipMemcpyAsync(c->lu_chunks.p, chunks.data(), sizeof(LuChunk) * chunks.size(), hipMemcpyHostToDevice, c->stream));
-    if (!blocks.empty())
-        PCE_HIP(c, hipMemcpyAsync(c->lu_blocks.p, blocks.data(), sizeof(LuBlock) * blocks.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(c->lu_pow.p, pw.data(), sizeof(double) * pw.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, c->lu_meta, hs); PCE_UPLOAD(c, c->lu_chunks, chunks, 1); PCE_UPLOAD(c, c->lu_blocks, blocks, 1); PCE_UPLOAD(c, c->lu_pow, pw);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     // peaks of the same slices
     return pce_energy_plan(c, slices, n, c->lu_en_work, c->lu_en_acc, &c->lu_n_energy_work);
@@ -367,7 +358,7 @@ int pce_lufs_run(pce_ctx *c, const pce_slice *slices, int32_t n)
     if (!c->d_pcm) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
     PCE_HIP(c, hipSetDevice(c->device));
     if (!c->lu_cache.same(slices, n)) {
-        { int rc = pce_side_join(c, pce_ctx::SIDE_LUFS); if (rc) return rc; }      // the previous chain still uses the plan's buffers
+        PCE_TRY(pce_side_join(c, pce_ctx::SIDE_LUFS));      // the previous chain still uses the plan's buffers
         c->lu_n = -1;
         int st = lufs_plan(c, slices, n);
         if (st) return st;
@@ -376,7 +367,7 @@ int pce_lufs_run(pce_ctx *c, const pce_slice *slices, int32_t n)
     // The whole chain goes to the second side stream (forked behind whatever the main stream holds: the upload, the
     // previous batch's result copies), so the pitch kernels launched next run beside it; consumers join first.
     hipStream_t ls = c->stream;
-    { int rc = pce_side_begin(c, pce_ctx::SIDE_LUFS, &ls); if (rc) return rc; }
+    PCE_TRY(pce_side_begin(c, pce_ctx::SIDE_LUFS, &ls));
     // the peaks that normalise the slices (get_lufs divides by max |x|): when pce_energy_run has just covered the SAME slices its
     // accumulators hold them (the fork above orders this chain behind it): no second pass over the PCM.  pce_energy_run joins this side
     // stream before it overwrites them (lu_reads_en_out).
@@ -417,7 +408,7 @@ int pce_lufs_run(pce_ctx *c, const pce_slice *slices, int32_t n)
                            c->lu_zbuf.as<double>(), c->lu_out.as<double>());
     }
     PCE_HIP(c, hipGetLastError());
-    { int rc = pce_side_end(c, pce_ctx::SIDE_LUFS, ls); if (rc) return rc; }
+    PCE_TRY(pce_side_end(c, pce_ctx::SIDE_LUFS, ls));
     c->lu_n = n;
     return PCE_OK;
 }
@@ -427,9 +418,9 @@ int pce_lufs_fetch(pce_ctx *c, double *lufs, int32_t *status)
     if (!c || !lufs) return PCE_E_INVALID;
     if (c->lu_n < 0) return pce_fail(c, PCE_E_STATE, "pce_lufs_fetch before pce_lufs_run");
     PCE_HIP(c, hipSetDevice(c->device));
-    { int rc = pce_side_join(c, pce_ctx::SIDE_LUFS); if (rc) return rc; }
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_LUFS));
     if (c->lu_n > 0)
-        PCE_HIP(c, hipMemcpyAsync(lufs, c->lu_out.p, sizeof(double) * (size_t)c->lu_n, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, lufs, c->lu_out.p, (size_t)c->lu_n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     if (status) for (int32_t i = 0; i < c->lu_n; i++) status[i] = c->lu_host_status[(size_t)i];

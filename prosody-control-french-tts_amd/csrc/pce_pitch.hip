@@ -1436,8 +1436,7 @@ int pce_pitch_plan(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slice
     if (!c || !p || (!slices && n > 0) || n < 0 || !frame_offsets) return PCE_E_INVALID;
     if (c->rate <= 0) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
     std::vector<int64_t> fo; std::vector<int32_t> st; std::vector<double> t1; PitchPlan common;
-    int rc = pitch_plan_slices(c, p, slices, n, fo, st, t1, &common);
-    if (rc) return rc;
+    PCE_TRY(pitch_plan_slices(c, p, slices, n, fo, st, t1, &common));
     memcpy(frame_offsets, fo.data(), sizeof(int64_t) * (size_t)(n + 1));
     if (status) memcpy(status, st.data(), sizeof(int32_t) * (size_t)n);
     return PCE_OK;
@@ -1456,12 +1455,11 @@ int pce_pitch_run(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
     if (!c || !p || (!slices && n > 0) || n < 0) return PCE_E_INVALID;
     if (!c->d_pcm) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
     PCE_HIP(c, hipSetDevice(c->device));
-    { int rc = pce_side_join(c, pce_ctx::SIDE_TAIL); if (rc) return rc; }   // the previous run's tail still owns the pitch buffers
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_TAIL));   // the previous run's tail still owns the pitch buffers
     if (!(c->pi_cache.same(slices, n) && c->pi_params_valid && same_params(c->pi_params, *p))) {
         c->pi_n = -1; c->pi_params_valid = false;
         PitchPlan pl;
-        int rc = pitch_plan_slices(c, p, slices, n, c->pi_frame_off, c->pi_status, c->pi_t1, &pl);
-        if (rc) return rc;
+        PCE_TRY(pitch_plan_slices(c, p, slices, n, c->pi_frame_off, c->pi_status, c->pi_t1, &pl));
         const int64_t total = c->pi_frame_off[(size_t)n];
         c->pi_total_frames = total;
         PiParams P; memset(&P, 0, sizeof P);
@@ -1493,14 +1491,11 @@ int pce_pitch_run(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
             std::vector<double> tw((size_t)(Mc + Mc + 1) * 2);
             for (int m = 0; m < Mc; m++) { tw[2 * (size_t)m] = std::cos(2.0 * PI_D * m / Mc); tw[2 * (size_t)m + 1] = -std::sin(2.0 * PI_D * m / Mc); }
             for (int k = 0; k <= Mc; k++) { tw[2 * (size_t)(Mc + k)] = std::cos(2.0 * PI_D * k / nfft); tw[2 * (size_t)(Mc + k) + 1] = -std::sin(2.0 * PI_D * k / nfft); }
-            PCE_HIP(c, c->pi_tw.reserve(sizeof(double) * tw.size()));
-            PCE_HIP(c, hipMemcpyAsync(c->pi_tw.p, tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice, c->stream));
+            PCE_UPLOAD(c, c->pi_tw, tw);
             std::vector<double> window, windowR;
             make_window_tables(pl, window, windowR);
-            PCE_HIP(c, c->pi_window.reserve(sizeof(double) * window.size()));
-            PCE_HIP(c, c->pi_windowR.reserve(sizeof(double) * windowR.size()));
-            PCE_HIP(c, hipMemcpyAsync(c->pi_window.p, window.data(), sizeof(double) * window.size(), hipMemcpyHostToDevice, c->stream));
-            PCE_HIP(c, hipMemcpyAsync(c->pi_windowR.p, windowR.data(), sizeof(double) * windowR.size(), hipMemcpyHostToDevice, c->stream));
+            PCE_UPLOAD(c, c->pi_window, window);
+            PCE_UPLOAD(c, c->pi_windowR, windowR);
             P.pcm_span = (((int)std::ceil((double)(P.fpb - 1) * P.dt / P.dx) + P.nw + 4) + 7) & ~7;   // samples under one work item's frames
             std::vector<double> blob;
             if (P.mode != 0) {
@@ -1520,8 +1515,7 @@ int pce_pitch_run(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
                 for (int k = 0; k <= P.bix; k++) blob.push_back(windowR[(size_t)k]);
                 if (blob.size() & 1) blob.push_back(0.0);
                 P.blob_f64 = (int)blob.size();
-                PCE_HIP(c, c->pi_blob.reserve(sizeof(double) * blob.size()));
-                PCE_HIP(c, hipMemcpyAsync(c->pi_blob.p, blob.data(), sizeof(double) * blob.size(), hipMemcpyHostToDevice, c->stream));
+                PCE_UPLOAD(c, c->pi_blob, blob);
             }
             PCE_HIP(c, hipStreamSynchronize(c->stream));
         }
@@ -1546,8 +1540,6 @@ int pce_pitch_run(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
         c->pi_np2 = np2;                                       // the in-LDS sort's size; longer slices (a recording of more than 82 s at floor 150) go to k_pitch_median_long
         c->pi_long_slices = max_frames > PI_MEDIAN_LDS;
         c->pi_n_work = (int64_t)work.size();
-        PCE_HIP(c, c->pi_meta.reserve(sizeof(PiSlice) * hs.size()));
-        PCE_HIP(c, c->pi_work.reserve(sizeof(PiWork) * (work.size() + 1)));
         PCE_HIP(c, c->pi_cand.reserve(sizeof(double) * 32 * (size_t)(total + 1)));
         PCE_HIP(c, c->pi_gpeak.reserve((sizeof(int) + sizeof(double)) * (size_t)(total + 1)));   // ncand + intensity
         PCE_HIP(c, c->pi_psi.reserve((size_t)PI_MAXC * (size_t)(total + 1) + 16));
@@ -1555,21 +1547,18 @@ int pce_pitch_run(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
         PCE_HIP(c, c->pi_strength.reserve(sizeof(double) * (size_t)(total + 1)));
         PCE_HIP(c, c->pi_summary.reserve(sizeof(PiSummaryDev) * hs.size()));
         PCE_HIP(c, c->pi_runs.reserve(sizeof(unsigned int) * RUN_LISTS * RF_CSTRIDE + sizeof(PathRun) * (size_t)RUN_LISTS * (size_t)(total / RUN_LISTS + 64)));
-        PCE_HIP(c, c->pi_fslice.reserve(sizeof(int) * (size_t)(total + 1)));
         PCE_HIP(c, c->pi_dl.reserve(sizeof(double) * 2 * PI_MAXC * (size_t)(total + 1)));
         PCE_HIP(c, c->pi_rr.reserve(sizeof(double) * (size_t)P.rr_half * (size_t)(total + 1)));
         PCE_HIP(c, c->pi_items.reserve(sizeof(RefineItem) * (size_t)(PI_MAXC - 1) * (size_t)(2 * PI_FPB) * (size_t)(div_up((int64_t)work.size() + 8, RF_LISTS) * RF_LISTS + RF_LISTS)
                                        + sizeof(unsigned int) * RF_LISTS * RF_CSTRIDE));
-        PCE_HIP(c, hipMemcpyAsync(c->pi_meta.p, hs.data(), sizeof(PiSlice) * hs.size(), hipMemcpyHostToDevice, c->stream));
-        if (!work.empty())
-            PCE_HIP(c, hipMemcpyAsync(c->pi_work.p, work.data(), sizeof(PiWork) * work.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, c->pi_meta, hs);
+        PCE_UPLOAD(c, c->pi_work, work, 1);
         std::vector<int> fslice((size_t)total + 1, 0);
         for (int32_t i = 0; i < n; i++)
             for (int64_t f = c->pi_frame_off[(size_t)i]; f < c->pi_frame_off[(size_t)i + 1]; f++) fslice[(size_t)f] = i;
-        PCE_HIP(c, hipMemcpyAsync(c->pi_fslice.p, fslice.data(), sizeof(int) * fslice.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, c->pi_fslice, fslice);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
-        rc = pce_energy_plan(c, slices, n, c->pi_peakwork, c->pi_acc, &c->pi_n_energy_work);
-        if (rc) return rc;
+        PCE_TRY(pce_energy_plan(c, slices, n, c->pi_peakwork, c->pi_acc, &c->pi_n_energy_work));
         c->pi_cache.store(slices, n);
         c->pi_params = *p; c->pi_params_valid = true;
     }
@@ -1581,8 +1570,7 @@ int pce_pitch_run(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
         // for this very slice list they are read from its accumulators (stream ordered) instead of streaming the batch again
         const bool reuse = c->en_n == n && c->en_cache.same(slices, n);
         if (!reuse) {
-            int rc = pce_energy_launch(c, n, 500, c->pi_n_energy_work, c->pi_peakwork, c->pi_acc);
-            if (rc) return rc;
+            PCE_TRY(pce_energy_launch(c, n, 500, c->pi_n_energy_work, c->pi_peakwork, c->pi_acc));
         }
         size_t stride; const long long *a_sum; const int *a_hi, *a_lo;
         pce_energy_range_ptrs(reuse ? c->en_out : c->pi_acc, &stride, &a_sum, &a_hi, &a_lo);
@@ -1597,14 +1585,20 @@ int pce_pitch_run(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
             if (P.mode != 0) wpb = PI_WPB;
             const size_t lds = P.mode != 0 ? sizeof(double) * ((size_t)reg_wave_f64(P.mode) * PI_WPB + (P.tabs ? (size_t)P.blob_f64 : 0)) + sizeof(int16_t) * (size_t)P.pcm_span
                                            : sizeof(double) * 4 * (size_t)P.zlen * (size_t)wpb + sizeof(int16_t) * (size_t)P.pcm_span;
-            const void *kfn = P.mode == 1 ? (P.tabs ? reinterpret_cast<const void *>(k_pitch_frames<4, 1, true>) : reinterpret_cast<const void *>(k_pitch_frames<4, 1, false>))
-                              : P.mode == 2 ? (P.tabs ? reinterpret_cast<const void *>(k_pitch_frames<4, 2, true>) : reinterpret_cast<const void *>(k_pitch_frames<4, 2, false>))
-                              : P.mode == 3 ? reinterpret_cast<const void *>(k_pitch_frames<4, 3, false>)
-                              : wpb == 4 ? reinterpret_cast<const void *>(k_pitch_frames<4, 0, false>)
-                              : wpb == 2 ? reinterpret_cast<const void *>(k_pitch_frames<2, 0, false>)
-                                         : reinterpret_cast<const void *>(k_pitch_frames<1, 0, false>);
+            // (P.mode, wpb) -> the instantiation that runs, handed to f: the LDS opt-in and the launch name it through here (mode 2 alone has P.tabs)
+            auto with_kernel = [&](auto &&f) -> int {
+                if (P.mode == 1) return f(k_pitch_frames<4, 1, false>);
+                if (P.mode == 2) return f(k_pitch_frames<4, 2, true>);
+                if (P.mode == 3) return f(k_pitch_frames<4, 3, false>);
+                if (wpb == 4) return f(k_pitch_frames<4, 0, false>);
+                if (wpb == 2) return f(k_pitch_frames<2, 0, false>);
+                return f(k_pitch_frames<1, 0, false>);
+            };
             if (lds > 64 * 1024)
-                PCE_HIP(c, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                PCE_TRY(with_kernel([&](auto kern) -> int {
+                    PCE_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    return PCE_OK;
+                }));
             const size_t cnt_bytes = sizeof(unsigned int) * RF_LISTS * RF_CSTRIDE;
             RefineItem *items = reinterpret_cast<RefineItem *>(c->pi_items.as<char>() + cnt_bytes);
             unsigned int *item_count = c->pi_items.as<unsigned int>();
@@ -1615,20 +1609,15 @@ int pce_pitch_run(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
                 // (2.5 nfft log2 nfft each), the power spectrum (3 nfft / 2), the window-autocorrelation division (maxlag)
                 const double f_flops = 3.0 * P.nw + 5.0 * P.nfft * std::log2((double)P.nfft) + 1.5 * P.nfft + (double)P.maxlag;
                 KernelTimer t(c, PCE_K_PITCH_FRAMES, nullptr, f_flops * (double)total);
-                auto launch = [&](auto kern) {
+                with_kernel([&](auto kern) -> int {
                     hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64 * wpb), lds, c->stream, c->d_pcm,
                                        c->pi_meta.as<PiSlice>(), c->pi_work.as<PiWork>(), (int)c->pi_n_work, P,
                                        c->pi_window.as<double>(), c->pi_windowR.as<double>(), c->pi_tw.as<double2>(),
                                        c->pi_tw.as<double2>() + (P.nfft >> 1), a_sum, a_hi, a_lo, stride,
                                        c->pi_cand.as<double>(), ncand, intensity, c->pi_rr.as<double>(), items, item_count, list_cap,
                                        c->pi_blob.as<double>());
-                };
-                if (P.mode == 1) launch(k_pitch_frames<4, 1, false>);
-                else if (P.mode == 2) launch(k_pitch_frames<4, 2, true>);
-                else if (P.mode == 3) launch(k_pitch_frames<4, 3, false>);
-                else if (wpb == 4) launch(k_pitch_frames<4, 0, false>);
-                else if (wpb == 2) launch(k_pitch_frames<2, 0, false>);
-                else launch(k_pitch_frames<1, 0, false>);
+                    return PCE_OK;
+                });
             }
             {
                 KernelTimer t(c, PCE_K_PITCH_REFINE);
@@ -1692,13 +1681,13 @@ int pce_pitch_fetch(pce_ctx *c, double *f0, double *strength, pce_pitch_summary 
     if (!c) return PCE_E_INVALID;
     if (c->pi_n < 0) return pce_fail(c, PCE_E_STATE, "pce_pitch_fetch before pce_pitch_run");
     PCE_HIP(c, hipSetDevice(c->device));
-    { int rc = pce_side_join(c, pce_ctx::SIDE_TAIL); if (rc) return rc; }
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_TAIL));
     const int32_t n = c->pi_n;
     const int64_t total = c->pi_total_frames;
     std::vector<PiSummaryDev> sd((size_t)(n > 0 ? n : 1));
-    if (f0 && total > 0) PCE_HIP(c, hipMemcpyAsync(f0, c->pi_f0.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-    if (strength && total > 0) PCE_HIP(c, hipMemcpyAsync(strength, c->pi_strength.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-    if (summary && n > 0) PCE_HIP(c, hipMemcpyAsync(sd.data(), c->pi_summary.p, sizeof(PiSummaryDev) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (f0 && total > 0) PCE_FETCH(c, f0, c->pi_f0.p, (size_t)total);
+    if (strength && total > 0) PCE_FETCH(c, strength, c->pi_strength.p, (size_t)total);
+    if (summary && n > 0) PCE_FETCH(c, sd.data(), c->pi_summary.p, (size_t)n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     if (summary)

@@ -407,15 +407,13 @@ int pce_pyin_run(pce_ctx *c, const pce_pyin_plan *plan, const double *tables, in
     }
     const int64_t total = c->py_off[(size_t)c->n_clips];
     if (c->n_clips == 0) { c->py_ran = true; return PCE_OK; }
-    PCE_HIP(c, c->py_doff.reserve(sizeof(int64_t) * ((size_t)c->n_clips + 1)));
-    PCE_HIP(c, c->py_tab.reserve(sizeof(double) * (size_t)n_tables));
     PCE_HIP(c, c->py_hdr.reserve(sizeof(PyObs) * (size_t)total));
     PCE_HIP(c, c->py_bin.reserve(sizeof(short) * (size_t)total * PY_MAXTR));
     PCE_HIP(c, c->py_lp.reserve(sizeof(double) * (size_t)total * PY_MAXTR));
     PCE_HIP(c, c->py_ptr.reserve(sizeof(unsigned short) * (size_t)total * (size_t)(2 * P.n_bins)));
     PCE_HIP(c, c->py_states.reserve(sizeof(int) * (size_t)total));
-    PCE_HIP(c, hipMemcpyAsync(c->py_doff.p, c->py_off.data(), sizeof(int64_t) * ((size_t)c->n_clips + 1), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(c->py_tab.p, tables, sizeof(double) * (size_t)n_tables, hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, c->py_doff, c->py_off.data(), (size_t)c->n_clips + 1);
+    PCE_UPLOAD(c, c->py_tab, tables, (size_t)n_tables);
     {
         const size_t lds = sizeof(double) * (size_t)PY_WPB * (PY_FRAME + 64 + PY_MAXTAU + 2 + 2 * PY_MAXTR);
         const void *kfn = P.n_groups == 5 ? reinterpret_cast<const void *>(k_pyin_frames<5>)
@@ -465,8 +463,8 @@ int pce_pyin_fetch(pce_ctx *c, int32_t clip, int32_t *states, double *voiced_pro
     PCE_HIP(c, hipSetDevice(c->device));
     const int64_t f0 = c->py_off[(size_t)clip], nf = c->py_off[(size_t)clip + 1] - f0;
     std::vector<PyObs> h((size_t)nf);
-    if (states) PCE_HIP(c, hipMemcpyAsync(states, c->py_states.as<int>() + f0, sizeof(int) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(h.data(), c->py_hdr.as<PyObs>() + f0, sizeof(PyObs) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+    if (states) PCE_FETCH(c, states, c->py_states.as<int>() + f0, (size_t)nf);
+    PCE_FETCH(c, h.data(), c->py_hdr.as<PyObs>() + f0, (size_t)nf);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     int st = 0;

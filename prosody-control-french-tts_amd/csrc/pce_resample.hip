@@ -42,7 +42,7 @@ int pce_resample_run(pce_ctx *c, int32_t up, int32_t down, const double *taps, i
 {
     if (!c || !taps || up <= 0 || down <= 0 || n_taps <= 0 || n_pre_remove < 0) return PCE_E_INVALID;
     if (!c->d_pcm) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
-    { int rc = pce_join_aux(c); if (rc) return rc; }           // side-stream kernels may still read the batch this call replaces
+    PCE_TRY(pce_join_aux(c));           // side-stream kernels may still read the batch this call replaces
     if (((int64_t)c->rate * up) % down) return pce_fail(c, PCE_E_INVALID, "rate %d * %d / %d is not an integer", c->rate, up, down);
     PCE_HIP(c, hipSetDevice(c->device));
     const int32_t n = c->n_clips;
@@ -54,11 +54,9 @@ int pce_resample_run(pce_ctx *c, int32_t up, int32_t down, const double *taps, i
     }
     const size_t total = (size_t)new_off[(size_t)n];
     DevBuf d_taps, d_newoff, d_out;
-    PCE_HIP(c, d_taps.reserve(sizeof(double) * (size_t)n_taps));
-    PCE_HIP(c, d_newoff.reserve(sizeof(int64_t) * (size_t)(n + 1)));
     PCE_HIP(c, d_out.reserve(total * 2 + 64));
-    PCE_HIP(c, hipMemcpyAsync(d_taps.p, taps, sizeof(double) * (size_t)n_taps, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d_newoff.p, new_off.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, d_taps, taps, (size_t)n_taps);
+    PCE_UPLOAD(c, d_newoff, new_off.data(), (size_t)(n + 1));
     PCE_HIP(c, hipMemsetAsync((char *)d_out.p + total * 2, 0, 64, c->stream));
     {
         KernelTimer t(c, PCE_K_RESAMPLE);
@@ -90,7 +88,7 @@ int pce_download_pcm_s16(pce_ctx *c, int16_t *pcm, int64_t *offsets, int32_t *sa
     if (offsets) memcpy(offsets, c->clip_off.data(), sizeof(int64_t) * (size_t)(c->n_clips + 1));
     if (sample_rate) *sample_rate = c->rate;
     if (pcm) {
-        PCE_HIP(c, hipMemcpyAsync(pcm, c->d_pcm, (size_t)c->clip_off[(size_t)c->n_clips] * 2, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, pcm, c->d_pcm, (size_t)c->clip_off[(size_t)c->n_clips]);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
     }
     return PCE_OK;

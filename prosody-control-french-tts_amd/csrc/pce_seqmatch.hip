@@ -230,9 +230,8 @@ int sm_run(pce_ctx *c, const char *who, const uint32_t *a_chars, const int64_t *
            int32_t n_b, const int32_t *pair_a, const int32_t *pair_b, int64_t n_pairs, int32_t autojunk, SmDevice &d)
 {
     int64_t max_la = 0, max_lb = 0;
-    int rc = sm_check_table(c, who, "a", a_chars, a_off, n_a, &max_la);
-    if (rc) return rc;
-    if ((rc = sm_check_table(c, who, "b", b_chars, b_off, n_b, &max_lb))) return rc;
+    PCE_TRY(sm_check_table(c, who, "a", a_chars, a_off, n_a, &max_la));
+    PCE_TRY(sm_check_table(c, who, "b", b_chars, b_off, n_b, &max_lb));
     if (pair_a) {
         for (int64_t p = 0; p < n_pairs; p++)
             if (pair_a[p] < 0 || pair_a[p] >= n_a || pair_b[p] < 0 || pair_b[p] >= n_b)
@@ -251,21 +250,11 @@ int sm_run(pce_ctx *c, const char *who, const uint32_t *a_chars, const int64_t *
     sm_popular_flags(b_chars, b_off, n_b, autojunk != 0, pop);
     const size_t na = (size_t)a_off[n_a], nb = (size_t)b_off[n_b];
     const size_t waves = (size_t)groups * SM_WAVES;
-    PCE_HIP(c, d.a.reserve(sizeof(unsigned) * (na + 1))); PCE_HIP(c, d.b.reserve(sizeof(unsigned) * (nb + 1)));
-    PCE_HIP(c, d.ao.reserve(sizeof(long long) * ((size_t)n_a + 1))); PCE_HIP(c, d.bo.reserve(sizeof(long long) * ((size_t)n_b + 1)));
-    PCE_HIP(c, d.pop.reserve(pop.size()));
     PCE_HIP(c, d.rows.reserve(sizeof(int) * (waves * (size_t)row_stride + 1))); PCE_HIP(c, d.spill.reserve(sizeof(int4) * waves * (size_t)spill_stride));
     PCE_HIP(c, d.cells.reserve(sizeof(unsigned long long) * waves)); PCE_HIP(c, d.out.reserve(sizeof(int) * (size_t)n_pairs));
-    if (na) PCE_HIP(c, hipMemcpyAsync(d.a.p, a_chars, sizeof(unsigned) * na, hipMemcpyHostToDevice, c->stream));
-    if (nb) PCE_HIP(c, hipMemcpyAsync(d.b.p, b_chars, sizeof(unsigned) * nb, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d.ao.p, a_off, sizeof(long long) * ((size_t)n_a + 1), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d.bo.p, b_off, sizeof(long long) * ((size_t)n_b + 1), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(d.pop.p, pop.data(), pop.size(), hipMemcpyHostToDevice, c->stream));
-    if (pair_a) {
-        PCE_HIP(c, d.pa.reserve(sizeof(int) * (size_t)n_pairs)); PCE_HIP(c, d.pb.reserve(sizeof(int) * (size_t)n_pairs));
-        PCE_HIP(c, hipMemcpyAsync(d.pa.p, pair_a, sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(d.pb.p, pair_b, sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-    }
+    PCE_UPLOAD(c, d.a, a_chars, na, 1); PCE_UPLOAD(c, d.b, b_chars, nb, 1);
+    PCE_UPLOAD(c, d.ao, a_off, (size_t)n_a + 1); PCE_UPLOAD(c, d.bo, b_off, (size_t)n_b + 1); PCE_UPLOAD(c, d.pop, pop);
+    if (pair_a) { PCE_UPLOAD(c, d.pa, pair_a, (size_t)n_pairs); PCE_UPLOAD(c, d.pb, pair_b, (size_t)n_pairs); }
     {
         KernelTimer t(c, PCE_K_SEQMATCH);
         hipLaunchKernelGGL(k_seqmatch, dim3((unsigned)groups), dim3(64 * SM_WAVES), 0, c->stream, d.a.as<unsigned>(), d.ao.as<long long>(),
@@ -276,7 +265,7 @@ int sm_run(pce_ctx *c, const char *who, const uint32_t *a_chars, const int64_t *
     PCE_HIP(c, hipGetLastError());
     if (c->prof) {                                         // the work count of the launch: cells its waves swept, recursion included
         std::vector<unsigned long long> cells(waves);
-        PCE_HIP(c, hipMemcpyAsync(cells.data(), d.cells.p, sizeof(unsigned long long) * waves, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, cells.data(), d.cells.p, waves);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         double sum = 0.0;
         for (unsigned long long v : cells) sum += (double)v;
@@ -300,15 +289,14 @@ extern "C" {
 int pce_seqmatch(pce_ctx *c, const uint32_t *a_chars, const int64_t *a_off, int32_t n_a, const uint32_t *b_chars, const int64_t *b_off, int32_t n_b,
                  const int32_t *pair_a, const int32_t *pair_b, int64_t n_pairs, int32_t autojunk, int32_t *out_matches)
 {
-    int rc = sm_check_args(c, "pce_seqmatch", a_off, n_a, b_off, n_b, n_pairs);
-    if (rc) return rc;
+    PCE_TRY(sm_check_args(c, "pce_seqmatch", a_off, n_a, b_off, n_b, n_pairs));
     if ((pair_a == nullptr) != (pair_b == nullptr)) return pce_fail(c, PCE_E_INVALID, "pce_seqmatch: pair_a and pair_b go together");
     if (!pair_a && n_pairs != (int64_t)n_a * (int64_t)n_b) return pce_fail(c, PCE_E_INVALID, "pce_seqmatch: all pairs of %d x %d strings are not %lld", n_a, n_b, (long long)n_pairs);
     if (n_pairs && !out_matches) return PCE_E_INVALID;
     PCE_HIP(c, hipSetDevice(c->device));
     SmDevice d;
-    if ((rc = sm_run(c, "pce_seqmatch", a_chars, a_off, n_a, b_chars, b_off, n_b, pair_a, pair_b, n_pairs, autojunk, d))) return rc;
-    if (n_pairs) PCE_HIP(c, hipMemcpyAsync(out_matches, d.out.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
+    PCE_TRY(sm_run(c, "pce_seqmatch", a_chars, a_off, n_a, b_chars, b_off, n_b, pair_a, pair_b, n_pairs, autojunk, d));
+    if (n_pairs) PCE_FETCH(c, out_matches, d.out.p, (size_t)n_pairs);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -318,12 +306,11 @@ int pce_seqmatch_align(pce_ctx *c, const uint32_t *a_chars, const int64_t *a_off
                        int32_t autojunk, double *sim, int32_t *match_a, int32_t *match_b, int32_t *n_matches)
 {
     const int64_t cells = (int64_t)(n_a > 0 ? n_a : 0) * (int64_t)(n_b > 0 ? n_b : 0);
-    int rc = sm_check_args(c, "pce_seqmatch_align", a_off, n_a, b_off, n_b, cells);
-    if (rc) return rc;
+    PCE_TRY(sm_check_args(c, "pce_seqmatch_align", a_off, n_a, b_off, n_b, cells));
     if (!n_matches || (cells && (!match_a || !match_b))) return PCE_E_INVALID;
     PCE_HIP(c, hipSetDevice(c->device));
     SmDevice d;
-    if ((rc = sm_run(c, "pce_seqmatch_align", a_chars, a_off, n_a, b_chars, b_off, n_b, nullptr, nullptr, cells, autojunk, d))) return rc;
+    PCE_TRY(sm_run(c, "pce_seqmatch_align", a_chars, a_off, n_a, b_chars, b_off, n_b, nullptr, nullptr, cells, autojunk, d));
     *n_matches = 0;
     if (!cells) { PCE_HIP(c, hipStreamSynchronize(c->stream)); pce_profile_collect(c); return PCE_OK; }
     const size_t tr_ld = ((size_t)n_b + 15) / 16, k_max = (size_t)std::min(n_a, n_b);
@@ -340,10 +327,10 @@ int pce_seqmatch_align(pce_ctx *c, const uint32_t *a_chars, const int64_t *a_off
                            dma.as<int>(), dmb.as<int>(), dn.as<int>());
     }
     PCE_HIP(c, hipGetLastError());
-    if (sim) PCE_HIP(c, hipMemcpyAsync(sim, dsim.p, sizeof(double) * (size_t)cells, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(match_a, dma.p, sizeof(int) * k_max, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(match_b, dmb.p, sizeof(int) * k_max, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(n_matches, dn.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (sim) PCE_FETCH(c, sim, dsim.p, (size_t)cells);
+    PCE_FETCH(c, match_a, dma.p, k_max);
+    PCE_FETCH(c, match_b, dmb.p, k_max);
+    PCE_FETCH(c, n_matches, dn.p, 1);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;

@@ -293,16 +293,14 @@ int pce_silence_run(pce_ctx *c, const pce_silence_params *p, const pce_slice *sl
     end.p_off = p_off; end.chunk_off = chunk_off; end.tile_off = tile_off; end.range_off = range_off;
     if (chunk_off > 0x7FFFFFFF || tile_off > 0x7FFFFFFF) return pce_fail(c, PCE_E_LIMIT, "silence: more chunks than one launch holds");
     PCE_HIP(c, hipSetDevice(c->device));
-    PCE_HIP(c, c->si_meta.reserve(sizeof(SiSlice) * meta.size()));
     PCE_HIP(c, c->si_pl.reserve(sizeof(unsigned long long) * (size_t)(p_off + 1)));
     PCE_HIP(c, c->si_csum.reserve(sizeof(unsigned long long) * (size_t)(chunk_off + 1)));
     PCE_HIP(c, c->si_coff.reserve(sizeof(unsigned long long) * (size_t)(chunk_off + 1)));
     PCE_HIP(c, c->si_tsum.reserve(sizeof(SiTile) * (size_t)(tile_off + 1)));
     PCE_HIP(c, c->si_tin.reserve(sizeof(SiCarry) * (size_t)(tile_off + 1)));
     PCE_HIP(c, c->si_out.reserve(sizeof(int32_t) * 2 * (size_t)(range_off + 1)));
-    PCE_HIP(c, c->si_count.reserve(sizeof(int32_t) * (size_t)(n + 1)));
-    PCE_HIP(c, hipMemcpyAsync(c->si_meta.p, meta.data(), sizeof(SiSlice) * meta.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(c->si_count.p, 0, sizeof(int32_t) * (size_t)(n + 1), c->stream));
+    PCE_UPLOAD(c, c->si_meta, meta);
+    PCE_ZERO(int32_t, c, c->si_count, (size_t)(n + 1));
     const SiSlice *d_meta = c->si_meta.as<SiSlice>();
     if (chunk_off > 0) {
         const int lds_words = (int)chunk_words(1 << cb_log2);
@@ -347,7 +345,7 @@ static int si_counts(pce_ctx *c)
     c->si_counts.assign((size_t)c->si_n + 1, 0);
     PCE_HIP(c, hipSetDevice(c->device));
     if (c->si_n > 0)
-        PCE_HIP(c, hipMemcpyAsync(c->si_counts.data(), c->si_count.p, sizeof(int32_t) * (size_t)c->si_n, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, c->si_counts.data(), c->si_count.p, (size_t)c->si_n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     for (int32_t i = 0; i < c->si_n; i++) {
@@ -363,7 +361,7 @@ int pce_silence_shape(pce_ctx *c, int64_t *range_offsets, int32_t *len_ms, int32
 {
     if (!c || !range_offsets) return PCE_E_INVALID;
     if (c->si_n < 0) return pce_fail(c, PCE_E_STATE, "pce_silence_shape before pce_silence_run");
-    int rc = si_counts(c); if (rc) return rc;
+    PCE_TRY(si_counts(c));
     range_offsets[0] = 0;
     for (int32_t i = 0; i < c->si_n; i++) {
         range_offsets[i + 1] = range_offsets[i] + c->si_counts[(size_t)i];
@@ -377,14 +375,14 @@ int pce_silence_fetch(pce_ctx *c, int32_t *ranges)
 {
     if (!c) return PCE_E_INVALID;
     if (c->si_n < 0) return pce_fail(c, PCE_E_STATE, "pce_silence_fetch before pce_silence_run");
-    int rc = si_counts(c); if (rc) return rc;
+    PCE_TRY(si_counts(c));
     const int64_t cap_total = c->si_cap_off[(size_t)c->si_n];
     int64_t total = 0;
     for (int32_t i = 0; i < c->si_n; i++) total += c->si_counts[(size_t)i];
     if (total == 0) return PCE_OK;
     if (!ranges) return PCE_E_INVALID;
     std::vector<int32_t> all((size_t)cap_total * 2);
-    PCE_HIP(c, hipMemcpyAsync(all.data(), c->si_out.p, sizeof(int32_t) * 2 * (size_t)cap_total, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, all.data(), c->si_out.p, 2 * (size_t)cap_total);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     int64_t w = 0;
     for (int32_t i = 0; i < c->si_n; i++) {

@@ -345,7 +345,7 @@ int pce_stft_db_run(pce_ctx *c, int32_t n_fft, int32_t hop)
     if (n_fft != NFFT) return pce_fail(c, PCE_E_LIMIT, "n_fft %d unsupported (the engine implements the reference's n_fft=1024)", n_fft);
     if (hop <= 0 || hop > NFFT) return pce_fail(c, PCE_E_INVALID, "bad hop %d", hop);
     PCE_HIP(c, hipSetDevice(c->device));
-    { int rc = pce_side_join(c, pce_ctx::SIDE_STFT); if (rc) return rc; }       // (a lazy normalisation of the previous run, if one is still in flight)
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_STFT));       // (a lazy normalisation of the previous run, if one is still in flight)
     constexpr int F = 16, WAVES = 4;
     if (c->st_nfft != n_fft || c->st_hop != hop) {
         const int32_t n = c->n_clips;
@@ -374,16 +374,9 @@ int pce_stft_db_run(pce_ctx *c, int32_t n_fft, int32_t hop)
             tw[2 * (size_t)(MC + i)] = (float)std::cos(2.0 * PI * i / NFFT);
             tw[2 * (size_t)(MC + i) + 1] = (float)(-std::sin(2.0 * PI * i / NFFT));
         }
-        PCE_HIP(c, c->st_off.reserve(sizeof(StClip) * (size_t)n));
-        PCE_HIP(c, c->st_work.reserve(sizeof(StTile) * (tiles.size() + 1)));
-        PCE_HIP(c, c->st_window.reserve(sizeof(float) * window.size()));
-        PCE_HIP(c, c->st_twiddle.reserve(sizeof(float) * tw.size()));
         PCE_HIP(c, c->st_max.reserve(sizeof(unsigned int) * (size_t)n));
         PCE_HIP(c, c->st_out.reserve(sizeof(float) * (size_t)c->st_off_host[(size_t)n] + 64));
-        PCE_HIP(c, hipMemcpyAsync(c->st_off.p, clips.data(), sizeof(StClip) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(c->st_work.p, tiles.data(), sizeof(StTile) * tiles.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(c->st_window.p, window.data(), sizeof(float) * window.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(c->st_twiddle.p, tw.data(), sizeof(float) * tw.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, c->st_off, clips.data(), (size_t)n); PCE_UPLOAD(c, c->st_work, tiles, 1); PCE_UPLOAD(c, c->st_window, window); PCE_UPLOAD(c, c->st_twiddle, tw);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         c->st_nfft = n_fft; c->st_hop = hop;
     }
@@ -438,7 +431,7 @@ int pce_stft_db_fetch(pce_ctx *c, int32_t clip, float *out)
     if (!c->st_nfft || !c->st_ran) return pce_fail(c, PCE_E_STATE, "pce_stft_db_fetch before pce_stft_db_run");
     if (clip < 0 || clip >= c->n_clips) return pce_fail(c, PCE_E_INVALID, "clip out of range");
     PCE_HIP(c, hipSetDevice(c->device));
-    { int rc = pce_side_join(c, pce_ctx::SIDE_STFT); if (rc) return rc; }
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_STFT));
     const int64_t off = c->st_off_host[(size_t)clip], cnt = c->st_off_host[(size_t)clip + 1] - off;
     const float *src = c->st_out.as<float>() + off;
     if (!c->st_final) {
@@ -450,7 +443,7 @@ int pce_stft_db_fetch(pce_ctx *c, int32_t clip, float *out)
         PCE_HIP(c, hipGetLastError());
         src = c->st_stage.as<float>();
     }
-    PCE_HIP(c, hipMemcpyAsync(out, src, sizeof(float) * (size_t)cnt, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, src, (size_t)cnt);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -460,7 +453,7 @@ int pce_stft_db_device(pce_ctx *c, const void **d_ptr, int64_t *bytes)
 {
     if (!c) return PCE_E_INVALID;
     if (!c->st_nfft || !c->st_ran) return pce_fail(c, PCE_E_STATE, "pce_stft_db_device before pce_stft_db_run");
-    { int rc = pce_side_join(c, pce_ctx::SIDE_STFT); if (rc) return rc; }
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_STFT));
     if (!c->st_final && c->n_clips > 0) {
         // a device-side consumer wants the finished matrix: normalise once, in place, on the context's stream (work queued behind this call sees the final values)
         PCE_HIP(c, hipSetDevice(c->device));

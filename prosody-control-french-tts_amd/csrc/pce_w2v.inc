@@ -436,7 +436,7 @@ int pce_w2v_load(pce_ctx *c, const pce_w2v_dims *dims, const float *weights, int
         b.lm_w = pk.mat_at(lw.data(), lw.size()); b.lm_b = pk.vec_at(lb.data(), lb.size());
     }
     DevBuf tmp;
-    if (const int rc = upload_weights(c, pk, tmp, b.w16, b.w32)) return rc;
+    PCE_TRY(upload_weights(c, pk, tmp, b.w16, b.w32));
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     b.loaded = true;
     return PCE_OK;
@@ -498,34 +498,28 @@ int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan)
     wpc = std::min<int64_t>(std::min<int64_t>(wpc, W), 4096);
     while (wpc > 1 && wpc * T_pad * (int64_t)std::max(std::max(3 * d, I), Vp) >= ((int64_t)1 << 31)) wpc--;      // (the launchers count rows in int)
     const int64_t M_max = wpc * T_pad;
-    PCE_HIP(c, b.wintab.reserve(sizeof(int64_t) * win_tab.size()));
-    PCE_HIP(c, b.tailtab.reserve(sizeof(int64_t) * tail_tab.size()));
-    PCE_HIP(c, b.atab.reserve(sizeof(int) * 2 * (size_t)wpc));
-    PCE_HIP(c, b.img[0].reserve(sizeof(op_t) * (size_t)(wpc * img_e[0]) + 4096));
     PCE_HIP(c, b.img[1].reserve(sizeof(op_t) * (size_t)(wpc * img_e[1]) + 4096));
     PCE_HIP(c, b.fpln.reserve(sizeof(op_t) * (size_t)M_max * C6 + 4096));
     PCE_HIP(c, b.h0.reserve(sizeof(float) * (size_t)M_max * d));
     PCE_HIP(c, b.h.reserve(sizeof(float) * (size_t)M_max * d));
     PCE_HIP(c, b.ln.reserve(sizeof(op_t) * (size_t)M_max * d + 4096));
     PCE_HIP(c, b.qk.reserve(sizeof(op_t) * (size_t)M_max * 2 * d + 4096));
-    PCE_HIP(c, b.attn.reserve(sizeof(op_t) * (size_t)M_max * d + 4096));
     PCE_HIP(c, b.hidden.reserve(sizeof(op_t) * (size_t)M_max * I + 4096));
     PCE_HIP(c, b.logits.reserve(sizeof(float) * (size_t)M_max * Vp));
     const size_t vt_elems = (size_t)wpc * (size_t)d * vt_sp + 64;
-    PCE_HIP(c, b.vt.reserve(sizeof(op_t) * vt_elems));
     PCE_HIP(c, b.em.reserve(sizeof(float) * (size_t)rows_total * n_cols + 256));
     {
         std::vector<int> at(2 * (size_t)wpc);
         for (int64_t i = 0; i < wpc; i++) { at[(size_t)i] = (int)(i * T_pad); at[(size_t)(wpc + i)] = T; }
-        PCE_HIP(c, hipMemcpyAsync(b.wintab.p, win_tab.data(), sizeof(int64_t) * win_tab.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(b.tailtab.p, tail_tab.data(), sizeof(int64_t) * tail_tab.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(b.atab.p, at.data(), sizeof(int) * at.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, b.wintab, win_tab);
+        PCE_UPLOAD(c, b.tailtab, tail_tab);
+        PCE_UPLOAD(c, b.atab, at);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
     }
     // pad rows and the key columns no launch writes: cleared, so that no stale bits (a NaN) meet a zero probability
-    PCE_HIP(c, hipMemsetAsync(b.img[0].p, 0, sizeof(op_t) * (size_t)(wpc * img_e[0]) + 4096, c->stream));
-    PCE_HIP(c, hipMemsetAsync(b.attn.p, 0, sizeof(op_t) * (size_t)M_max * d + 4096, c->stream));
-    PCE_HIP(c, hipMemsetAsync(b.vt.p, 0, sizeof(op_t) * vt_elems, c->stream));
+    PCE_ZERO(op_t, c, b.img[0], (size_t)(wpc * img_e[0]) + 2048);
+    PCE_ZERO(op_t, c, b.attn, (size_t)M_max * d + 2048);
+    PCE_ZERO(op_t, c, b.vt, vt_elems);
     const int *R0 = b.atab.as<int>(), *RL = R0 + wpc;
     const op_t *Wb = b.w16.as<op_t>();
     const float *Wf = b.w32.as<float>();
@@ -537,9 +531,8 @@ int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan)
         const int M = Wc * T_pad;
         {   // the feature encoder
             const WhisperState::W2v::Conv &c0 = b.conv[0];
-            const int rc = w2v_launch_wave(c, m.feat_norm, b.wintab.as<int64_t>() + 3 * w0, Wc, Wf + c0.w, c0.has_b ? Wf + c0.b : nullptr, Wf + c0.g, Wf + c0.beta,
-                                           m.conv_dim[0], m.conv_stride[0], Tl[0], b.part, b.ss, b.img[0].as<op_t>());
-            if (rc) return rc;
+            PCE_TRY(w2v_launch_wave(c, m.feat_norm, b.wintab.as<int64_t>() + 3 * w0, Wc, Wf + c0.w, c0.has_b ? Wf + c0.b : nullptr, Wf + c0.g, Wf + c0.beta,
+                                    m.conv_dim[0], m.conv_stride[0], Tl[0], b.part, b.ss, b.img[0].as<op_t>()));
             for (int i = 1; i < 7; i++) {
                 const WhisperState::W2v::Conv &cv = b.conv[i];
                 const int ci = m.conv_dim[i - 1], co = m.conv_dim[i];
@@ -598,8 +591,7 @@ int pce_w2v_fetch(pce_ctx *c, int32_t clip, float *log_probs)
     if (b.n_clips < 0) return pce_fail(c, PCE_E_STATE, "pce_w2v_fetch before pce_w2v_run");
     if (clip < 0 || clip >= b.n_clips) return pce_fail(c, PCE_E_INVALID, "clip out of range");
     PCE_HIP(c, hipSetDevice(c->device));
-    PCE_HIP(c, hipMemcpyAsync(log_probs, b.em.as<float>() + b.row_start[(size_t)clip] * b.n_cols, sizeof(float) * (size_t)b.n_frames[(size_t)clip] * b.n_cols,
-                              hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, log_probs, b.em.as<float>() + b.row_start[(size_t)clip] * b.n_cols, (size_t)b.n_frames[(size_t)clip] * b.n_cols);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -634,16 +626,10 @@ int pce_selftest_w2v_wave(pce_ctx *c, const int16_t *pcm, int64_t n_samples, int
     for (int64_t j = 0; j < n_win; j++) { tab.push_back(0); tab.push_back(j * window_samples - context_samples); tab.push_back(n_samples); }
     DevBuf dp, dt, dw, db, dg, dbe, part, ss, dout;
     const size_t n_out = (size_t)n_win * (size_t)T0 * C;
-    PCE_HIP(c, dp.reserve(sizeof(int16_t) * (size_t)n_samples)); PCE_HIP(c, dt.reserve(sizeof(int64_t) * tab.size()));
-    PCE_HIP(c, dw.reserve(sizeof(float) * (size_t)C * WV_K0)); PCE_HIP(c, db.reserve(sizeof(float) * C)); PCE_HIP(c, dg.reserve(sizeof(float) * C));
-    PCE_HIP(c, dbe.reserve(sizeof(float) * C)); PCE_HIP(c, dout.reserve(sizeof(op_t) * n_out));
-    PCE_HIP(c, hipMemcpyAsync(dp.p, pcm, sizeof(int16_t) * (size_t)n_samples, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dt.p, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * (size_t)C * WV_K0, hipMemcpyHostToDevice, c->stream));
-    if (bias) PCE_HIP(c, hipMemcpyAsync(db.p, bias, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dg.p, gamma, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dbe.p, beta, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dout.p, 0, sizeof(op_t) * n_out, c->stream));
+    PCE_UPLOAD(c, dp, pcm, (size_t)n_samples); PCE_UPLOAD(c, dt, tab); PCE_UPLOAD(c, dw, w, (size_t)C * WV_K0);
+    if (bias) PCE_UPLOAD(c, db, bias, (size_t)C);
+    PCE_UPLOAD(c, dg, gamma, (size_t)C); PCE_UPLOAD(c, dbe, beta, (size_t)C);
+    PCE_ZERO(op_t, c, dout, n_out);
     const int16_t *keep_pcm = c->d_pcm;                                          // (w2v_launch_wave reads the context's resident batch)
     c->d_pcm = dp.as<int16_t>();
     const int rc = w2v_launch_wave(c, feat_norm, dt.as<int64_t>(), (int)n_win, dw.as<float>(), bias ? db.as<float>() : nullptr, dg.as<float>(), dbe.as<float>(), C,
@@ -651,7 +637,7 @@ int pce_selftest_w2v_wave(pce_ctx *c, const int16_t *pcm, int64_t n_samples, int
     c->d_pcm = keep_pcm;
     if (rc) return rc;
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, sizeof(op_t) * n_out, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, dout.p, n_out);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -663,13 +649,10 @@ int pce_selftest_w2v_lngelu(pce_ctx *c, const uint16_t *x, int32_t rows, int32_t
     PCE_HIP(c, hipSetDevice(c->device));
     const size_t n = (size_t)rows * C;
     DevBuf dx, dw, db;
-    PCE_HIP(c, dx.reserve(sizeof(op_t) * n)); PCE_HIP(c, dw.reserve(sizeof(float) * C)); PCE_HIP(c, db.reserve(sizeof(float) * C));
-    PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(op_t) * n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * C, hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, dx, x, n); PCE_UPLOAD(c, dw, w, (size_t)C); PCE_UPLOAD(c, db, b, (size_t)C);
     w2v_launch_ln16(c, gelu != 0, dx.as<op_t>(), dw.as<float>(), db.as<float>(), rows, C, eps, dx.as<op_t>());      // in place, as the run launches it
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dx.p, sizeof(op_t) * n, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, dx.p, n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -681,15 +664,11 @@ int pce_selftest_w2v_posconv(pce_ctx *c, const float *x, int32_t n_win, int32_t 
     PCE_HIP(c, hipSetDevice(c->device));
     const size_t n = (size_t)n_win * T * d, nw = (size_t)d * PC_TAPS * (d / groups);
     DevBuf dx, dw, db, dout;
-    PCE_HIP(c, dx.reserve(sizeof(float) * n)); PCE_HIP(c, dw.reserve(sizeof(op_t) * nw)); PCE_HIP(c, db.reserve(sizeof(float) * d));
-    PCE_HIP(c, dout.reserve(sizeof(float) * n));
-    PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(op_t) * nw, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(db.p, bias, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dout.p, 0, sizeof(float) * n, c->stream));
+    PCE_UPLOAD(c, dx, x, n); PCE_UPLOAD(c, dw, w, nw); PCE_UPLOAD(c, db, bias, (size_t)d);
+    PCE_ZERO(float, c, dout, n);
     w2v_launch_posconv(c, dx.as<float>(), dw.as<op_t>(), db.as<float>(), T, T, d, groups, n_win, dout.as<float>());
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, dout.p, n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }

@@ -49,11 +49,10 @@ static int prefix_reserve_and_embed(pce_ctx *c, WhisperState *w, const PrefixRun
 {
     const size_t rows16 = sizeof(op_t) * (size_t)r.Mt * r.d;         // bytes of one op_t image of the rows
     PCE_HIP(c, w->d_resid.reserve(sizeof(float) * (size_t)r.Mt * r.d)); PCE_HIP(c, w->d_ln.reserve(rows16 + 4096));
-    PCE_HIP(c, w->d_qk.reserve(2 * rows16 + 4096)); PCE_HIP(c, w->d_attn.reserve(rows16 + 4096));
-    PCE_HIP(c, w->d_q.reserve(rows16 + 4096)); PCE_HIP(c, w->d_hidden.reserve(4 * rows16 + 4096));
+    PCE_HIP(c, w->d_qk.reserve(2 * rows16 + 4096)); PCE_HIP(c, w->d_q.reserve(rows16 + 4096)); PCE_HIP(c, w->d_hidden.reserve(4 * rows16 + 4096));
     // k_attention writes the rows of real tokens only: the pad rows (T..T_pad of every clip) must not hold stale bits, a NaN
     // there would reach the next layer's V^T and poison valid queries through 0 * NaN (seen as an intermittent NaN cost matrix)
-    PCE_HIP(c, hipMemsetAsync(w->d_attn.p, 0, rows16 + 4096, c->stream));
+    PCE_ZERO(op_t, c, w->d_attn, (size_t)r.Mt * r.d + 2048);
     hipLaunchKernelGGL(k_embed_tokens, dim3((unsigned)div_up(r.Mt * r.d, 256)), dim3(256), 0, c->stream, w->d_tokens.as<int>(),
                        w->d_tok_emb.as<float>(), w->d_pos_emb.as<float>(), r.T_pad, w->tdims.n_text_ctx, r.d, r.Mt, w->d_resid.as<float>());
     return PCE_OK;
@@ -106,7 +105,7 @@ int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, cons
     if (n_floats != expect) return pce_fail(c, PCE_E_INVALID, "decoder weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)expect);
     PCE_HIP(c, hipSetDevice(c->device));
     WhisperState *w = ws_of(c);
-    { const int rc = lds_optins(c, w); if (rc) return rc; }
+    PCE_TRY(lds_optins(c, w));
     w->tdims = *dims; w->dec_loaded = false; w->dlayers.assign((size_t)L, {});
     WeightPack pk;
     const float *p = weights;
@@ -128,15 +127,12 @@ int pce_whisper_decoder_load(pce_ctx *c, const pce_whisper_text_dims *dims, cons
     }
     w->dln_w = pk.vec(p, (size_t)d); w->dln_b = pk.vec(p, (size_t)d);
     DevBuf tmp;
-    if (const int rc = upload_weights(c, pk, tmp, w->dw_bf16, w->dw_f32)) return rc;
-    PCE_HIP(c, w->d_tok_emb.reserve(sizeof(float) * (size_t)V * d));
-    PCE_HIP(c, w->d_pos_emb.reserve(sizeof(float) * (size_t)TC * d));
-    PCE_HIP(c, hipMemcpyAsync(w->d_tok_emb.p, tok, sizeof(float) * (size_t)V * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->d_pos_emb.p, pos, sizeof(float) * (size_t)TC * d, hipMemcpyHostToDevice, c->stream));
+    PCE_TRY(upload_weights(c, pk, tmp, w->dw_bf16, w->dw_f32));
+    PCE_UPLOAD(c, w->d_tok_emb, tok, (size_t)V * d);
+    PCE_UPLOAD(c, w->d_pos_emb, pos, (size_t)TC * d);
     {   // tied output projection for free-running decoding: the token embedding in op_t, rows padded to the 128-column GEMM tile
         const size_t Vp = (size_t)div_up(V, 128) * 128;
-        PCE_HIP(c, w->g_emb_bf16.reserve(sizeof(op_t) * Vp * (size_t)d + 256));
-        PCE_HIP(c, hipMemsetAsync(w->g_emb_bf16.p, 0, sizeof(op_t) * Vp * (size_t)d, c->stream));
+        PCE_ZERO(op_t, c, w->g_emb_bf16, Vp * (size_t)d, 128);
         hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)V * d, 256)), dim3(256), 0, c->stream, w->d_tok_emb.as<float>(),
                            w->g_emb_bf16.as<op_t>(), (int64_t)V * d);
     }
@@ -168,7 +164,7 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
     std::vector<int> f_len((size_t)n);
     for (int i = 0; i < n; i++) {
         const int F = std::min(num_frames[i] / 2, W_CTX);
-        const int rc = align_clip_dims(c, i, token_offsets[i + 1] - token_offsets[i], F, sot_len, w->tdims.n_text_ctx, dims); if (rc) return rc;
+        PCE_TRY(align_clip_dims(c, i, token_offsets[i + 1] - token_offsets[i], F, sot_len, w->tdims.n_text_ctx, dims));
         f_len[(size_t)i] = F;
     }
     const int F_max = dims.F_max, N_max = dims.N_max, F_pad = dims.F_pad();
@@ -185,7 +181,7 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
     if (n_sel == 0) return pce_fail(c, PCE_E_INVALID, "no alignment head selected");
     // ---- tables: [q_row0 | q_len | a_row0 | a_len | f_len | n_rows(dtw)] and padded tokens
     TokenRows rows;
-    { const int rc = pad_token_rows(c, tokens, token_offsets, n, V, "token", 6, rows); if (rc) return rc; }
+    PCE_TRY(pad_token_rows(c, tokens, token_offsets, n, V, "token", 6, rows));
     const int T_pad = rows.T_pad;
     std::vector<int> &tab = rows.tab, &tok = rows.tok;
     for (int i = 0; i < n; i++) { tab[(size_t)4 * n + i] = f_len[(size_t)i]; tab[(size_t)5 * n + i] = rows.t_len[(size_t)i] - sot_len - 1; }
@@ -201,9 +197,9 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
     // included) only when they differ from what the device already holds: a caller that aligns the same token lists again -- the
     // bench's step, a retried batch -- keeps enqueuing
     if (w->al_tab_host.empty() || tab != w->al_tab_host || tok != w->al_tok_host || heads != w->al_heads_host) {
-        PCE_HIP(c, hipMemcpyAsync(w->d_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(w->d_tokens.p, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(w->d_heads.p, heads.data(), sizeof(int) * heads.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_PUT(c, w->d_tab.p, tab.data(), tab.size());
+        PCE_PUT(c, w->d_tokens.p, tok.data(), tok.size());
+        PCE_PUT(c, w->d_heads.p, heads.data(), heads.size());
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         w->al_tab_host = tab; w->al_tok_host = tok; w->al_heads_host = heads;
     }
@@ -233,7 +229,7 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
     if (w->enc_bf16_clips != n)                                   // (the persistent-GEMM encoder path has already written it)
         hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up(Ma * d, 256)), dim3(256), 0, c->stream, w->final_out.as<float>(),
                                w->d_enc_bf16.as<op_t>(), Ma * d);
-    { const int rc = prefix_reserve_and_embed(c, w, run); if (rc) return rc; }
+    PCE_TRY(prefix_reserve_and_embed(c, w, run));
     for (int l = 0; l < L; l++) {
         const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
         prefix_self_qkv(c, w, run, ly, w->d_vt.as<op_t>());
@@ -253,9 +249,8 @@ int pce_whisper_align_run(pce_ctx *c, const int32_t *tokens, const int32_t *toke
     }
     // alignment matrix: normalise over tokens, median filter over time, mean over heads, DTW
     launch_align_cost(c, am, (int)sot_len, (int)medfilt_width, N_max, w->d_cost.as<double>());
-    int rc = pce_dtw_launch(c, w->d_cost.as<double>(), (int64_t)N_max * F_pad, F_pad, NR, FL, N_max, F_max, n, w->d_trace.as<unsigned char>(),
-                            w->d_pi.as<int>(), w->d_pj.as<int>(), w->d_pl.as<int>());
-    if (rc) return rc;
+    PCE_TRY(pce_dtw_launch(c, w->d_cost.as<double>(), (int64_t)N_max * F_pad, F_pad, NR, FL, N_max, F_max, n, w->d_trace.as<unsigned char>(),
+                           w->d_pi.as<int>(), w->d_pj.as<int>(), w->d_pl.as<int>()));
     PCE_HIP(c, hipGetLastError());
     w->al_n = n; w->al_Nmax = N_max; w->al_Fpad = F_pad; w->al_Mmax = F_max;
     return PCE_OK;
@@ -270,11 +265,11 @@ int pce_whisper_align_fetch(pce_ctx *c, int32_t clip, int32_t *text_idx, int32_t
     PCE_HIP(c, hipSetDevice(c->device));
     const size_t stride = (size_t)(w->al_Nmax + w->al_Mmax);
     int n = 0;
-    PCE_HIP(c, hipMemcpyAsync(&n, w->d_pl.as<int>() + clip, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, &n, w->d_pl.as<int>() + clip, 1);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     *path_len = n;
-    if (text_idx) PCE_HIP(c, hipMemcpyAsync(text_idx, w->d_pi.as<int>() + stride * (size_t)clip, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (time_idx) PCE_HIP(c, hipMemcpyAsync(time_idx, w->d_pj.as<int>() + stride * (size_t)clip, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (text_idx) PCE_FETCH(c, text_idx, w->d_pi.as<int>() + stride * (size_t)clip, (size_t)n);
+    if (time_idx) PCE_FETCH(c, time_idx, w->d_pj.as<int>() + stride * (size_t)clip, (size_t)n);
     if (cost) {
         const int N = w->al_rows[(size_t)clip], F = w->al_cols[(size_t)clip];
         PCE_HIP(c, hipMemcpy2DAsync(cost, sizeof(double) * (size_t)F, w->d_cost.as<double>() + (size_t)clip * w->al_Nmax * (size_t)w->al_Fpad,
@@ -304,9 +299,9 @@ int pce_whisper_align_paths_enqueue(pce_ctx *c, int32_t slot, int32_t *n_clips, 
     if (!ps.ev) PCE_HIP(c, hipEventCreateWithFlags(&ps.ev, hipEventDisableTiming));
     int *h = static_cast<int *>(ps.host);
     // behind the DTW on the context's stream: lengths, then the two index arrays as they lie ([clip][stride], a few MB at most)
-    PCE_HIP(c, hipMemcpyAsync(h, w->d_pl.p, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(h + n, w->d_pi.p, sizeof(int) * n * stride, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(h + n + n * stride, w->d_pj.p, sizeof(int) * n * stride, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, h, w->d_pl.p, n);
+    PCE_FETCH(c, h + n, w->d_pi.p, n * stride);
+    PCE_FETCH(c, h + n + n * stride, w->d_pj.p, n * stride);
     PCE_HIP(c, hipEventRecord(ps.ev, c->stream));
     ps.armed = true; ps.n = (int)n; ps.stride = (int)stride;
     if (n_clips) *n_clips = (int32_t)n;
@@ -468,9 +463,8 @@ int pce_whisper_sample_keys(pce_ctx *c, const int32_t *keys, int32_t n)
     if (w->n_clips_enc < 0) return pce_fail(c, PCE_E_STATE, "pce_whisper_sample_keys before pce_whisper_encode_run");
     if (n != w->n_clips_enc) return pce_fail(c, PCE_E_INVALID, "pce_whisper_sample_keys: %d keys for %d encoded clips", n, w->n_clips_enc);
     PCE_HIP(c, hipSetDevice(c->device));
-    PCE_HIP(c, w->g_keys.reserve(sizeof(int) * (size_t)n));
     // (pageable source: the copy has left `keys` when the call returns; it is ordered before the next decode on the same stream)
-    PCE_HIP(c, hipMemcpyAsync(w->g_keys.p, keys, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, w->g_keys, keys, (size_t)n);
     w->g_keys_n = n;
     return PCE_OK;
 }
@@ -480,15 +474,14 @@ int pce_whisper_decode_step_ex(pce_ctx *c, const int32_t *tokens, const int32_t 
                                           float *next_logprobs, float *probe_prob)
 {
     if (!c || !tokens || !token_offsets || !rules || !vocab_mask || !next_tokens || !opts) return PCE_E_INVALID;
-    const int rc = decode_step_device(c, tokens, token_offsets, rules, vocab_mask, opts, probe_prob != nullptr);
-    if (rc) return rc;
+    PCE_TRY(decode_step_device(c, tokens, token_offsets, rules, vocab_mask, opts, probe_prob != nullptr));
     WhisperState *w = ws_of(c);
     const int n = w->n_clips_enc;
     if (n == 0) return PCE_OK;
-    PCE_HIP(c, hipMemcpyAsync(next_tokens, w->g_next.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (next_logprobs) PCE_HIP(c, hipMemcpyAsync(next_logprobs, w->g_next.as<int>() + n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, next_tokens, w->g_next.p, (size_t)n);
+    if (next_logprobs) PCE_FETCH(c, next_logprobs, w->g_next.as<int>() + n, (size_t)n);
     if (probe_prob && opts->probe_token >= 0)
-        PCE_HIP(c, hipMemcpyAsync(probe_prob, w->g_next.as<int>() + 2 * n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, probe_prob, w->g_next.as<int>() + 2 * n, (size_t)n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -506,18 +499,15 @@ static int decode_stage_prompts(pce_ctx *c, WhisperState *w, const int32_t *toke
         const int sb = sample_begin_of ? sample_begin_of[i] : sample_begin_all;
         if (sb < 1 || T < sb || T > w->tdims.n_text_ctx) return pce_fail(c, PCE_E_INVALID, "clip %d: %d tokens (need %d..%d)", i, T, sb, w->tdims.n_text_ctx);
     }
-    { const int rc = pad_token_rows(c, tokens, token_offsets, n, V, "token", 5, rows); if (rc) return rc; }
+    PCE_TRY(pad_token_rows(c, tokens, token_offsets, n, V, "token", 5, rows));
     std::vector<int> &tok = rows.tok, &tab = rows.tab;
     for (int i = 0; i < n; i++) tab[(size_t)4 * n + i] = sample_begin_of ? sample_begin_of[i] : sample_begin_all;
-    PCE_HIP(c, w->d_tab.reserve(sizeof(int) * tab.size()));
-    PCE_HIP(c, w->d_tokens.reserve(sizeof(int) * tok.size()));
     PCE_HIP(c, w->g_last.reserve(sizeof(float) * (size_t)n * d));
     PCE_HIP(c, w->g_lastln.reserve(sizeof(op_t) * (size_t)(n + 128) * d + 4096));
-    if (vocab_mask) PCE_HIP(c, w->g_mask.reserve((size_t)V + 64));
     w->al_tab_host.clear();                                     // (d_tab / d_tokens are shared with pce_whisper_align_run: it uploads again)
-    PCE_HIP(c, hipMemcpyAsync(w->d_tab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->d_tokens.p, tok.data(), sizeof(int) * tok.size(), hipMemcpyHostToDevice, c->stream));
-    if (vocab_mask) PCE_HIP(c, hipMemcpyAsync(w->g_mask.p, vocab_mask, (size_t)V, hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, w->d_tab, tab);
+    PCE_UPLOAD(c, w->d_tokens, tok);
+    if (vocab_mask) PCE_UPLOAD(c, w->g_mask, vocab_mask, (size_t)V, 64);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -536,9 +526,8 @@ static int decode_prompts_to_lastln(pce_ctx *c, WhisperState *w, const int32_t *
     const size_t xk_l = (size_t)Ma * d, xvt_l = (size_t)n * (size_t)d * AT_SP;
     if (w->g_xkv_clips != n) {
         PCE_HIP(c, w->g_xk.reserve(sizeof(op_t) * xk_l * (size_t)L + 4096));
-        PCE_HIP(c, w->g_xvt.reserve(sizeof(op_t) * xvt_l * (size_t)L + 4096));
         PCE_HIP(c, w->d_enc_bf16.reserve(sizeof(op_t) * (size_t)Ma * d + 4096));
-        PCE_HIP(c, hipMemsetAsync(w->g_xvt.p, 0, sizeof(op_t) * xvt_l * (size_t)L, c->stream));      // V^T columns 1500..AT_SP are read as zeros
+        PCE_ZERO(op_t, c, w->g_xvt, xvt_l * (size_t)L, 2048);                                         // V^T columns 1500..AT_SP are read as zeros
         if (w->enc_bf16_clips != n)
             hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up(Ma * d, 256)), dim3(256), 0, c->stream, w->final_out.as<float>(),
                                w->d_enc_bf16.as<op_t>(), Ma * d);
@@ -553,12 +542,9 @@ static int decode_prompts_to_lastln(pce_ctx *c, WhisperState *w, const int32_t *
     const int T_cap = w->tdims.n_text_ctx;
     const size_t sk_l = (size_t)n * T_cap * d, svt_l = (size_t)n * (size_t)d * SPD;
     if (w->g_cache_n != n || !w->g_sk.p) {
-        PCE_HIP(c, w->g_sk.reserve(sizeof(op_t) * sk_l * (size_t)L + 4096));
-        PCE_HIP(c, w->g_svt.reserve(sizeof(op_t) * svt_l * (size_t)L + 4096));
-        PCE_HIP(c, w->g_sv.reserve(sizeof(op_t) * sk_l * (size_t)L + 4096));
-        PCE_HIP(c, hipMemsetAsync(w->g_sv.p, 0, sizeof(op_t) * sk_l * (size_t)L, c->stream));
-        PCE_HIP(c, hipMemsetAsync(w->g_sk.p, 0, sizeof(op_t) * sk_l * (size_t)L, c->stream));
-        PCE_HIP(c, hipMemsetAsync(w->g_svt.p, 0, sizeof(op_t) * svt_l * (size_t)L, c->stream));
+        PCE_ZERO(op_t, c, w->g_sk, sk_l * (size_t)L, 2048);
+        PCE_ZERO(op_t, c, w->g_svt, svt_l * (size_t)L, 2048);
+        PCE_ZERO(op_t, c, w->g_sv, sk_l * (size_t)L, 2048);
         w->g_cache_n = n; w->g_cache_len = -1; w->g_cache_tok.assign((size_t)n * T_cap, 0); w->g_cache_lens.assign((size_t)n, -1);
     }
     // incremental: every sequence extends what the cache holds for it by exactly one token (lengths may differ between sequences)
@@ -576,12 +562,12 @@ static int decode_prompts_to_lastln(pce_ctx *c, WhisperState *w, const int32_t *
             ct[(size_t)i] = tokens[token_offsets[i] + pos_i]; ct[(size_t)n + i] = i; ct[(size_t)2 * n + i] = 1; ct[(size_t)3 * n + i] = i * T_cap;
             ct[(size_t)4 * n + i] = pos_i + 1; ct[(size_t)5 * n + i] = i * W_CTX; ct[(size_t)6 * n + i] = W_CTX; ct[(size_t)7 * n + i] = pos_i;
         }
-        { const int rc = decode_incremental_reserve(c, w, n); if (rc) return rc; }
-        PCE_HIP(c, hipMemcpyAsync(w->g_c_tab.p, ct.data(), sizeof(int) * ct.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_TRY(decode_incremental_reserve(c, w, n));
+        PCE_PUT(c, w->g_c_tab.p, ct.data(), ct.size());
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         decode_incremental_launches(c, w, n, w->g_c_tab.as<int>(), nullptr);
     } else {
-    { const int rc = prefix_reserve_and_embed(c, w, run); if (rc) return rc; }
+    PCE_TRY(prefix_reserve_and_embed(c, w, run));
     for (int l = 0; l < L; l++) {
         const WhisperState::DLayer &ly = w->dlayers[(size_t)l];
         op_t *svt = w->g_svt.as<op_t>() + svt_l * (size_t)l;       // the prefix run fills the cache: V^T straight from the epilogue, K rows copied
@@ -645,9 +631,9 @@ static int decode_step_device(pce_ctx *c, const int32_t *tokens, const int32_t *
     PCE_HIP(c, w->g_logits.reserve(sizeof(float) * (size_t)n * (size_t)Vp));
     PCE_HIP(c, w->g_next.reserve((sizeof(int) + 2 * sizeof(float)) * (size_t)n));
     TokenRows rows;
-    { const int rc = decode_stage_prompts(c, w, tokens, token_offsets, opts->sample_begin, sample_begin, vocab_mask, rows); if (rc) return rc; }
+    PCE_TRY(decode_stage_prompts(c, w, tokens, token_offsets, opts->sample_begin, sample_begin, vocab_mask, rows));
     KernelTimer timer(c, PCE_K_WHISPER_DECODE);
-    { const int rc = decode_prompts_to_lastln(c, w, tokens, token_offsets, rows, !(opts->flags & 1)); if (rc) return rc; }
+    PCE_TRY(decode_prompts_to_lastln(c, w, tokens, token_offsets, rows, !(opts->flags & 1)));
     // ---- logits = hidden . E^T (fp32, zero-initialised accumulator), the filters and the choice
     const int *T0 = w->d_tab.as<int>(), *TL = T0 + n;
     launch_gemm<EPI_F32>(c, w->g_lastln.as<op_t>(), d, 0, w->g_emb_bf16.as<op_t>(), n, (int)Vp, d, nullptr, w->g_logits.as<float>(), Vp, 0, 1);
@@ -681,13 +667,13 @@ int pce_whisper_detect_language(pce_ctx *c, int32_t sot, int32_t lang_begin, int
     for (int i = 0; i <= n; i++) offsets[(size_t)i] = i;
     PCE_HIP(c, w->g_lang.reserve((sizeof(float) * (size_t)n_lang + sizeof(int)) * (size_t)n));
     TokenRows rows;
-    { const int rc = decode_stage_prompts(c, w, tokens.data(), offsets.data(), nullptr, 1, nullptr, rows); if (rc) return rc; }
+    PCE_TRY(decode_stage_prompts(c, w, tokens.data(), offsets.data(), nullptr, 1, nullptr, rows));
     float *d_probs = w->g_lang.as<float>();
     int *d_ids = reinterpret_cast<int *>(d_probs + (size_t)n * n_lang);
     {
         KernelTimer timer(c, PCE_K_WHISPER_DECODE);
         // (never the incremental form: a one-token prompt extends nothing)
-        { const int rc = decode_prompts_to_lastln(c, w, tokens.data(), offsets.data(), rows, false); if (rc) return rc; }
+        PCE_TRY(decode_prompts_to_lastln(c, w, tokens.data(), offsets.data(), rows, false));
         hipLaunchKernelGGL(k_lang_probs, dim3((unsigned)n), dim3(LANG_T), 0, c->stream, w->g_lastln.as<op_t>(), w->g_emb_bf16.as<op_t>(), d, (int)lang_begin,
                            (int)n_lang, d_probs, d_ids);
         PCE_HIP(c, hipGetLastError());
@@ -696,8 +682,8 @@ int pce_whisper_detect_language(pce_ctx *c, int32_t sot, int32_t lang_begin, int
     // dropped, so that the next decoding call runs its prompts through the prefix pass exactly as it does after a fresh pce_whisper_encode_run
     // (the cross K / V of the batch stay: they are what that call would compute first)
     w->g_cache_len = -1;
-    if (ids) PCE_HIP(c, hipMemcpyAsync(ids, d_ids, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    if (probs) PCE_HIP(c, hipMemcpyAsync(probs, d_probs, sizeof(float) * (size_t)n * n_lang, hipMemcpyDeviceToHost, c->stream));
+    if (ids) PCE_FETCH(c, ids, d_ids, (size_t)n);
+    if (probs) PCE_FETCH(c, probs, d_probs, (size_t)n * n_lang);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -728,11 +714,8 @@ int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *to
     PCE_HIP(c, hipSetDevice(c->device));
     KernelTimer loop_timer(c, PCE_K_DECODE_LOOP);
     // ---- step 0: the prompts (prefix run, or one more position when the cache already holds them); next token stays in g_next
-    {
-        const int rc = decode_step_device(c, tokens, token_offsets, rules, vocab_mask, opts, probe_prob != nullptr && opts->probe_token >= 0);
-        if (rc) return rc;
-    }
-    { const int rc = decode_incremental_reserve(c, w, n); if (rc) return rc; }
+    PCE_TRY(decode_step_device(c, tokens, token_offsets, rules, vocab_mask, opts, probe_prob != nullptr && opts->probe_token >= 0));
+    PCE_TRY(decode_incremental_reserve(c, w, n));
     const int64_t Vp = div_up(V, 128) * 128;
     // ---- device-resident loop state
     const size_t n_state_ints = (size_t)n * T_cap + 3 * (size_t)n + (size_t)n * max_new + 8 + (size_t)max_new;
@@ -748,10 +731,10 @@ int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *to
         ct[(size_t)n + i] = i; ct[(size_t)2 * n + i] = 1; ct[(size_t)3 * n + i] = i * T_cap; ct[(size_t)5 * n + i] = i * W_CTX; ct[(size_t)6 * n + i] = W_CTX;
     }
     PCE_HIP(c, hipMemsetAsync(ended, 0, sizeof(int) * (n_state_ints - (size_t)n * T_cap - (size_t)n) + sizeof(float) * (size_t)n * max_new, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(tok_table, h_tab.data(), sizeof(int) * h_tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(len, h_len.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(sb, h_sb.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w->g_c_tab.p, ct.data(), sizeof(int) * ct.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_PUT(c, tok_table, h_tab.data(), h_tab.size());
+    PCE_PUT(c, len, h_len.data(), (size_t)n);
+    PCE_PUT(c, sb, h_sb.data(), (size_t)n);
+    PCE_PUT(c, w->g_c_tab.p, ct.data(), ct.size());
     PCE_HIP(c, hipStreamSynchronize(c->stream));                 // (the host vectors are done with; the ONE upload of the window)
     int *CT = w->g_c_tab.as<int>();
     const int *next = w->g_next.as<int>();
@@ -760,7 +743,7 @@ int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *to
     auto advance = [&]() { launch_step_advance(c, state, n, T_cap, (int)rules->eot, (int)max_new, next, next_lp, CT); };
     auto all_ended = [&](int step, bool *yes) -> int {
         int cnt = 0;
-        PCE_HIP(c, hipMemcpyAsync(&cnt, n_ended + step, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, &cnt, n_ended + step, 1);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         *yes = cnt >= n;
         return PCE_OK;
@@ -770,7 +753,7 @@ int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *to
     bool stop = false;
     DecRules R{rules->eot, rules->timestamp_begin, V, (int)Vp, opts->sample_begin_all, rules->max_initial_timestamp_index, opts->temperature, opts->seed_lo,
                opts->seed_hi, -1};
-    if (max_new > 1) { const int rc = all_ended(0, &stop); if (rc) return rc; }
+    if (max_new > 1) PCE_TRY(all_ended(0, &stop));
     while (!stop && steps < max_new) {
         decode_incremental_launches(c, w, n, CT, ended);
         launch_gemm<EPI_F32>(c, w->g_lastln.as<op_t>(), d, 0, w->g_emb_bf16.as<op_t>(), n, (int)Vp, d, nullptr, w->g_logits.as<float>(), Vp, 0, 1);
@@ -778,16 +761,16 @@ int pce_whisper_decode_loop(pce_ctx *c, const int32_t *tokens, const int32_t *to
                             reinterpret_cast<float *>(w->g_next.as<int>() + n), nullptr, w->g_keys_n == n ? w->g_keys.as<int>() : nullptr);
         advance();
         steps++;
-        if (steps % check_every == 0 && steps < max_new) { const int rc = all_ended(steps - 1, &stop); if (rc) return rc; }
+        if (steps % check_every == 0 && steps < max_new) PCE_TRY(all_ended(steps - 1, &stop));
     }
     PCE_HIP(c, hipGetLastError());
     // ---- the ONE download of the window
     std::vector<int> h_out((size_t)n * max_new);
     std::vector<float> h_lp((size_t)n * max_new);
-    PCE_HIP(c, hipMemcpyAsync(h_out.data(), out_tok, sizeof(int) * h_out.size(), hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(h_lp.data(), out_lp, sizeof(float) * h_lp.size(), hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, h_out.data(), out_tok, h_out.size());
+    PCE_FETCH(c, h_lp.data(), out_lp, h_lp.size());
     if (probe_prob && opts->probe_token >= 0)
-        PCE_HIP(c, hipMemcpyAsync(probe_prob, w->g_next.as<int>() + 2 * n, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, probe_prob, w->g_next.as<int>() + 2 * n, (size_t)n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n; i++)
         for (int sidx = 0; sidx < max_new; sidx++) {

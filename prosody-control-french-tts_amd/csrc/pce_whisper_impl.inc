@@ -123,11 +123,9 @@ __global__ void k_f32_to_bf16(const float *__restrict__ in, op_t *__restrict__ o
 // synchronises it before `tmp` goes out of scope.
 static int upload_weights(pce_ctx *c, const WeightPack &pk, DevBuf &tmp, DevBuf &w16, DevBuf &w32)
 {
-    PCE_HIP(c, tmp.reserve(sizeof(float) * pk.mats.size()));
+    PCE_UPLOAD(c, tmp, pk.mats);
+    PCE_UPLOAD(c, w32, pk.vecs);
     PCE_HIP(c, w16.reserve(sizeof(op_t) * pk.mats.size() + 256));
-    PCE_HIP(c, w32.reserve(sizeof(float) * pk.vecs.size()));
-    PCE_HIP(c, hipMemcpyAsync(tmp.p, pk.mats.data(), sizeof(float) * pk.mats.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(w32.p, pk.vecs.data(), sizeof(float) * pk.vecs.size(), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_f32_to_bf16, dim3((unsigned)div_up((int64_t)pk.mats.size(), 256)), dim3(256), 0, c->stream, tmp.as<float>(), w16.as<op_t>(),
                        (int64_t)pk.mats.size());
     return PCE_OK;
@@ -265,19 +263,21 @@ int mel_setup(pce_ctx *c, WhisperState *w, int n_mels)
     const size_t bytes = sizeof(float) * (32 + 800 + 50 + W_NFFT + packed.size()) + sizeof(int) * 3 * (size_t)n_mels + 64;
     PCE_HIP(c, w->tables.reserve(bytes));
     char *d = w->tables.as<char>(); size_t o = 0;
-    auto put = [&](const void *src, size_t n) -> const void * {
-        (void)hipMemcpyAsync(d + o, src, n, hipMemcpyHostToDevice, c->stream);
-        const void *p = d + o; o += (n + 15) & ~(size_t)15; return p;
+    int rc = PCE_OK;
+    auto put = [&](const auto &v) -> const void * {                // every table starts at a multiple of 16 bytes; the first failed copy is kept
+        if (!rc) rc = pce_put_at(c, __FILE__, __LINE__, d + o, v.data(), v.size());
+        const void *p = d + o; o += (sizeof(v[0]) * v.size() + 15) & ~(size_t)15; return p;
     };
-    w->mt.w16 = (const float2 *)put(w16.data(), sizeof(float) * 32);
-    w->mt.w400 = (const float2 *)put(w400.data(), sizeof(float) * 800);
-    w->mt.w25 = (const float2 *)put(w25.data(), sizeof(float) * 50);
-    w->mt.window = (const float *)put(win.data(), sizeof(float) * W_NFFT);
-    w->mt.mel_lo = (const int *)put(lo.data(), sizeof(int) * (size_t)n_mels);
-    w->mt.mel_n = (const int *)put(cnt.data(), sizeof(int) * (size_t)n_mels);
-    w->mt.mel_off = (const int *)put(off.data(), sizeof(int) * (size_t)n_mels);
-    w->mt.mel_w = (const float *)put(packed.data(), sizeof(float) * packed.size());
+    w->mt.w16 = (const float2 *)put(w16);
+    w->mt.w400 = (const float2 *)put(w400);
+    w->mt.w25 = (const float2 *)put(w25);
+    w->mt.window = (const float *)put(win);
+    w->mt.mel_lo = (const int *)put(lo);
+    w->mt.mel_n = (const int *)put(cnt);
+    w->mt.mel_off = (const int *)put(off);
+    w->mt.mel_w = (const float *)put(packed);
     w->mt.mel_total = (int)packed.size();
+    PCE_TRY(rc);
     if (packed.size() > (size_t)LM_MELW) return pce_fail(c, PCE_E_LIMIT, "%zu packed mel weights (the kernel holds %d)", packed.size(), LM_MELW);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     w->mel_nmels = n_mels;
@@ -560,12 +560,10 @@ static int logmel_run_impl(pce_ctx *c, int32_t n_mels, const int64_t *start_fram
     if (n_mels <= 0 || n_mels > 128) return pce_fail(c, PCE_E_INVALID, "n_mels %d out of range", n_mels);
     PCE_HIP(c, hipSetDevice(c->device));
     WhisperState *w = ws_of(c);
-    int rc = mel_setup(c, w, n_mels);
-    if (rc) return rc;
+    PCE_TRY(mel_setup(c, w, n_mels));
     const int32_t n = c->n_clips;
     const size_t tm_elems = (size_t)n * (W_FRAMES + 2) * (size_t)n_mels + 512;
     PCE_HIP(c, w->logspec.reserve(sizeof(float) * (size_t)n * (size_t)n_mels * W_FRAMES));
-    PCE_HIP(c, w->clipmax.reserve(sizeof(unsigned int) * (size_t)n));
     PCE_HIP(c, w->mel_tm.reserve(sizeof(op_t) * tm_elems));
     PCE_HIP(c, w->stem_skip.reserve(sizeof(int2) * 2 * (size_t)(n > 0 ? n : 1)));
     w->stem_tiles_c1 = w->stem_tiles_c2 = 0;
@@ -574,7 +572,7 @@ static int logmel_run_impl(pce_ctx *c, int32_t n_mels, const int64_t *start_fram
         const int s = stem_first_skipped_tile(start_frames ? full : std::min<int64_t>(full, W_SAMPLES), start_frames ? start_frames[i] : 0);
         if (s < ST_C2_LAST) { w->stem_tiles_c2 += ST_C2_LAST - s; w->stem_tiles_c1 += ST_C1_KEEP - 2 * s; }
     }
-    PCE_HIP(c, hipMemsetAsync(w->clipmax.p, 0, sizeof(unsigned int) * (size_t)n, c->stream));
+    PCE_ZERO(unsigned int, c, w->clipmax, (size_t)n);
     if (w->mel_tm.cap != w->mel_tm_zero_cap || w->mel_tm_zero_nm != n_mels) {
         PCE_HIP(c, hipMemsetAsync(w->mel_tm.p, 0, w->mel_tm.cap, c->stream));
         w->mel_tm_zero_cap = w->mel_tm.cap; w->mel_tm_zero_nm = n_mels;
@@ -589,8 +587,7 @@ static int logmel_run_impl(pce_ctx *c, int32_t n_mels, const int64_t *start_fram
             if (start_frames[i] < 0 || start_frames[i] * W_HOP > len) return pce_fail(c, PCE_E_INVALID, "clip %d: window start %lld frames is past the audio", i, (long long)start_frames[i]);
             longest = std::max(longest, len);
         }
-        PCE_HIP(c, w->mel_start.reserve(sizeof(int64_t) * (size_t)(n > 0 ? n : 1)));
-        PCE_HIP(c, hipMemcpyAsync(w->mel_start.p, start_frames, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, w->mel_start, start_frames, (size_t)n, n > 0 ? 0 : 1);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         d_start = w->mel_start.as<int64_t>();
         if (n > 0) {       // the clamp of log_mel_spectrogram uses the maximum over the whole recording
@@ -631,7 +628,7 @@ int pce_logmel_fetch(pce_ctx *c, int32_t clip, float *out)
                        w->clipmax.as<unsigned int>(), (int)w->mel_nmels, c->d_clip_off.as<int64_t>(), w->mel_windowed ? w->mel_start.as<int64_t>() : (const int64_t *)nullptr,
                        (int)clip, (op_t *)nullptr, w->mel_stage.as<float>(), (int2 *)nullptr, (int2 *)nullptr);
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, w->mel_stage.p, sizeof(float) * per, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, w->mel_stage.p, per);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -648,7 +645,7 @@ int pce_selftest_logmel_image(pce_ctx *c, int32_t clip, uint16_t *out)
     const size_t per = (size_t)(W_FRAMES + 2) * (size_t)w->mel_nmels;
     if (sizeof(op_t) * per * ((size_t)clip + 1) > w->mel_tm.cap) return pce_fail(c, PCE_E_STATE, "the last log-mel run did not finish: run it again");
     PCE_HIP(c, hipSetDevice(c->device));
-    PCE_HIP(c, hipMemcpyAsync(out, w->mel_tm.as<op_t>() + (size_t)clip * per, sizeof(op_t) * per, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, w->mel_tm.as<op_t>() + (size_t)clip * per, per);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }

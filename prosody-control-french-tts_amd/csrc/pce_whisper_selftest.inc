@@ -16,26 +16,18 @@ static int selftest_add_layernorm(pce_ctx *c, int64_t rows, int d, const void *x
     constexpr bool IN_PLACE = std::is_same<RIN, ROUT>::value;
     const size_t n = (size_t)rows * d;
     DevBuf din, dres, ddl, ddl2, dw, db, dout, dcopy;
-    PCE_HIP(c, din.reserve(sizeof(RIN) * n)); PCE_HIP(c, ddl.reserve(2 * n)); PCE_HIP(c, dw.reserve(sizeof(float) * d)); PCE_HIP(c, db.reserve(sizeof(float) * d));
-    PCE_HIP(c, dout.reserve(sizeof(OUT) * n));
-    if (!IN_PLACE) PCE_HIP(c, dres.reserve(sizeof(ROUT) * n));
-    if (delta2) PCE_HIP(c, ddl2.reserve(2 * n));
-    if (out_copy) PCE_HIP(c, dcopy.reserve(2 * n));
-    PCE_HIP(c, hipMemcpyAsync(din.p, x, sizeof(RIN) * n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(ddl.p, delta, 2 * n, hipMemcpyHostToDevice, c->stream));
-    if (delta2) PCE_HIP(c, hipMemcpyAsync(ddl2.p, delta2, 2 * n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dout.p, 0, sizeof(OUT) * n, c->stream));
-    if (!IN_PLACE) PCE_HIP(c, hipMemsetAsync(dres.p, 0, sizeof(ROUT) * n, c->stream));
-    if (out_copy) PCE_HIP(c, hipMemsetAsync(dcopy.p, 0, 2 * n, c->stream));
+    PCE_UPLOAD(c, din, static_cast<const RIN *>(x), n); PCE_UPLOAD(c, ddl, delta, n); PCE_UPLOAD(c, dw, w, (size_t)d); PCE_UPLOAD(c, db, b, (size_t)d);
+    if (delta2) PCE_UPLOAD(c, ddl2, delta2, n);
+    PCE_ZERO(OUT, c, dout, n);
+    if (!IN_PLACE) PCE_ZERO(ROUT, c, dres, n);
+    if (out_copy) PCE_ZERO(uint16_t, c, dcopy, n);
     ROUT *rout = IN_PLACE ? din.as<ROUT>() : dres.as<ROUT>();
     launch_add_layernorm<OUT, RIN, ROUT>(c, din.as<RIN>(), rout, ddl.as<op_t>(), delta2 ? ddl2.as<op_t>() : nullptr, write_resid, dw.as<float>(), db.as<float>(),
                                          rows, d, dout.as<OUT>(), eps, out_copy ? dcopy.as<op_t>() : nullptr);
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, sizeof(OUT) * n, hipMemcpyDeviceToHost, c->stream));
-    if (resid_out) PCE_HIP(c, hipMemcpyAsync(resid_out, rout, sizeof(ROUT) * n, hipMemcpyDeviceToHost, c->stream));
-    if (out_copy) PCE_HIP(c, hipMemcpyAsync(out_copy, dcopy.p, 2 * n, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, static_cast<OUT *>(out), dout.p, n);
+    if (resid_out) PCE_FETCH(c, static_cast<ROUT *>(resid_out), rout, n);
+    if (out_copy) PCE_FETCH(c, out_copy, dcopy.p, n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -76,15 +68,9 @@ int pce_selftest_attention_ragged(pce_ctx *c, const uint16_t *q, const uint16_t 
     PCE_HIP(c, hipSetDevice(c->device));
     const size_t nq = (size_t)q_rows * hd, nk = (size_t)k_rows * hd, nvt = (size_t)clips * hd * sp, no = (size_t)out_rows * hd;
     DevBuf dq, dk, dv, dvt, dout, dtab, dcnt;
-    PCE_HIP(c, dq.reserve(nq * 2 + 64)); PCE_HIP(c, dk.reserve(nk * 2 + 64)); PCE_HIP(c, dv.reserve(nk * 2 + 64)); PCE_HIP(c, dvt.reserve(nvt * 2 + 128));
-    PCE_HIP(c, dout.reserve(no * 2 + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * 4 * (size_t)clips)); PCE_HIP(c, dcnt.reserve(sizeof(int)));
-    PCE_HIP(c, hipMemcpyAsync(dq.p, q, nq * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dk.p, k, nk * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dv.p, v, nk * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dout.p, out, no * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dvt.p, 0, nvt * 2 + 128, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dcnt.p, 0, sizeof(int), c->stream));
+    PCE_UPLOAD(c, dq, q, nq, 32); PCE_UPLOAD(c, dk, k, nk, 32); PCE_UPLOAD(c, dv, v, nk, 32); PCE_UPLOAD(c, dout, out, no, 32); PCE_UPLOAD(c, dtab, tab);
+    PCE_ZERO(uint16_t, c, dvt, nvt + 64);
+    PCE_ZERO(int, c, dcnt, 1);
     AttnArgs a{};
     a.q = dq.as<op_t>(); a.q_ld = hd; a.k = dk.as<op_t>(); a.k_ld = hd; a.vt = dvt.as<op_t>(); a.vt_clip = (int64_t)hd * sp; a.vt_sp = sp;
     a.q_row0 = dtab.as<int>(); a.q_len = a.q_row0 + clips; a.k_row0 = a.q_row0 + 2 * clips; a.k_len = a.q_row0 + 3 * clips;
@@ -95,8 +81,8 @@ int pce_selftest_attention_ragged(pce_ctx *c, const uint16_t *q, const uint16_t 
     launch_attention(c, dim3((unsigned)div_up(q_max, AT_QB), (unsigned)heads, (unsigned)clips), a, 0.0, mode);
     PCE_HIP(c, hipGetLastError());
     int cnt = 0;
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, no * 2, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(&cnt, dcnt.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out, dout.p, no);
+    PCE_FETCH(c, &cnt, dcnt.p, 1);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     if (fell_back) *fell_back = cnt;
     return PCE_OK;
@@ -140,15 +126,10 @@ int pce_selftest_attn1(pce_ctx *c, int32_t form, int32_t n, int32_t heads, const
         return pce_fail(c, PCE_E_INVALID, "selftest attn1: form %d needs q %lld, k %lld, v %lld, out %lld elements", form, (long long)q_need, (long long)k_need,
                         (long long)v_need, (long long)o_need);
     PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    PCE_TRY(lds_optins(c, ws_of(c)));
     DevBuf dq, dk, dv, dout, dtab;
-    PCE_HIP(c, dq.reserve(2 * (size_t)q_elems + 64)); PCE_HIP(c, dk.reserve(2 * (size_t)k_elems + 64)); PCE_HIP(c, dv.reserve(2 * (size_t)v_elems + 64));
-    PCE_HIP(c, dout.reserve(2 * (size_t)out_elems + 64)); PCE_HIP(c, dtab.reserve(sizeof(int) * tab.size()));
-    PCE_HIP(c, hipMemcpyAsync(dq.p, q, 2 * (size_t)q_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dk.p, k, 2 * (size_t)k_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dv.p, v, 2 * (size_t)v_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dout.p, out, 2 * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, dq, q, (size_t)q_elems, 32); PCE_UPLOAD(c, dk, k, (size_t)k_elems, 32); PCE_UPLOAD(c, dv, v, (size_t)v_elems, 32);
+    PCE_UPLOAD(c, dout, out, (size_t)out_elems, 32); PCE_UPLOAD(c, dtab, tab);
     const int *T = dtab.as<int>(), *SKIP = skip ? T + 3 * n : nullptr;
     if (form == 2) {
         SelfAttn1Args sa{};
@@ -163,11 +144,8 @@ int pce_selftest_attn1(pce_ctx *c, int32_t form, int32_t n, int32_t heads, const
         launch_cross_attn1(c, n, heads, a);
     }
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
-    if (form != 0) {
-        PCE_HIP(c, hipMemcpyAsync(k, dk.p, 2 * (size_t)k_elems, hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(v, dv.p, 2 * (size_t)v_elems, hipMemcpyDeviceToHost, c->stream));
-    }
+    PCE_FETCH(c, out, dout.p, (size_t)out_elems);
+    if (form != 0) { PCE_FETCH(c, k, dk.p, (size_t)k_elems); PCE_FETCH(c, v, dv.p, (size_t)v_elems); }
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -192,7 +170,7 @@ int pce_selftest_align_matrix(pce_ctx *c, int32_t n, int32_t heads, const uint16
     int T_max = 0;
     for (int i = 0; i < n; i++) {
         if (f_len[i] > k_rows) return pce_fail(c, PCE_E_INVALID, "selftest align: clip %d has %d frames, %d key rows", i, f_len[i], k_rows);
-        const int rc = align_clip_dims(c, i, t_len[i], f_len[i], sot_len, 448, dims); if (rc) return rc;      // (448: the longest n_text_ctx a decoder loads with)
+        PCE_TRY(align_clip_dims(c, i, t_len[i], f_len[i], sot_len, 448, dims));                               // (448: the longest n_text_ctx a decoder loads with)
         T_max = std::max(T_max, t_len[i]);
     }
     const int d = heads * 64, T_pad = token_rows_pad(T_max), F_pad = dims.F_pad(), N_max = dims.N_max;
@@ -206,25 +184,21 @@ int pce_selftest_align_matrix(pce_ctx *c, int32_t n, int32_t heads, const uint16
     for (int s = 0; s < n_sel; s++) tab[(size_t)2 * n + s] = heads_sel[s];
     DevBuf dq, dk, dw, dc, dtab;
     const size_t k_clip = (size_t)W_CTX * d;                      // the key pitch k_align_scores assumes: 1500 rows per clip
-    PCE_HIP(c, dq.reserve(2 * (size_t)q_need + 64)); PCE_HIP(c, dk.reserve(2 * k_clip * (size_t)n + 64)); PCE_HIP(c, dw.reserve(sizeof(float) * (size_t)w_need));
-    PCE_HIP(c, dc.reserve(sizeof(double) * (size_t)c_need)); PCE_HIP(c, dtab.reserve(sizeof(int) * tab.size()));
-    PCE_HIP(c, hipMemcpyAsync(dq.p, q, 2 * (size_t)q_need, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dk.p, 0, 2 * k_clip * (size_t)n, c->stream));
+    PCE_UPLOAD(c, dq, q, (size_t)q_need, 32);
+    PCE_ZERO(uint16_t, c, dk, k_clip * (size_t)n, 32);
     PCE_HIP(c, hipMemcpy2DAsync(dk.p, 2 * k_clip, k, 2 * (size_t)k_rows * d, 2 * (size_t)k_rows * d, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dw.p, w_soft, sizeof(float) * (size_t)w_need, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dc.p, cost, sizeof(double) * (size_t)c_need, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dtab.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    PCE_UPLOAD(c, dw, w_soft, (size_t)w_need); PCE_UPLOAD(c, dc, cost, (size_t)c_need); PCE_UPLOAD(c, dtab, tab);
     const int *TL = dtab.as<int>(), *FL = TL + n, *HS = TL + 2 * n;
     const AlignMatrix am{dw.as<float>(), TL, FL, n, n_sel, T_pad, F_pad};
     const int first = split == 0 ? n_sel : split;                // heads of the first launch (the rest: a second layer's)
     launch_align_scores(c, am, dq.as<op_t>(), dk.as<op_t>(), d, HS, 0, first, qk_scale);
     if (first < n_sel) launch_align_scores(c, am, dq.as<op_t>(), dk.as<op_t>(), d, HS, first, n_sel - first, qk_scale);
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(w_soft, dw.p, sizeof(float) * (size_t)w_need, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, w_soft, dw.p, (size_t)w_need);
     launch_align_cost(c, am, sot_len, medfilt_width, N_max, dc.as<double>());
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(w_norm, dw.p, sizeof(float) * (size_t)w_need, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(cost, dc.p, sizeof(double) * (size_t)c_need, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, w_norm, dw.p, (size_t)w_need);
+    PCE_FETCH(c, cost, dc.p, (size_t)c_need);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -277,38 +251,25 @@ int pce_selftest_decode_rules(pce_ctx *c, int32_t form, int32_t n, int32_t n_voc
     if (form == 0) h_tok.assign((size_t)n * pitch, pad_token); else h_tok.assign(table, table + table_elems);
     for (int i = 0; i < n; i++) memcpy(&h_tok[(size_t)i * pitch], &tokens[token_offsets[i]], sizeof(int) * (size_t)h_len[(size_t)i]);
     DevBuf dlog, dtok, dlen, dsb, dmask, dkeys, dout, dlp, dprobe, dstate, dnext;
-    PCE_HIP(c, dlog.reserve(sizeof(float) * (size_t)logits_elems)); PCE_HIP(c, dtok.reserve(sizeof(int) * h_tok.size())); PCE_HIP(c, dlen.reserve(sizeof(int) * (size_t)n));
-    PCE_HIP(c, dsb.reserve(sizeof(int) * (size_t)n)); PCE_HIP(c, dmask.reserve((size_t)V + 64)); PCE_HIP(c, dout.reserve(sizeof(int) * (size_t)out_elems));
-    PCE_HIP(c, dlp.reserve(sizeof(float) * (size_t)out_elems));
-    PCE_HIP(c, hipMemcpyAsync(dlog.p, logits, sizeof(float) * (size_t)logits_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dtok.p, h_tok.data(), sizeof(int) * h_tok.size(), hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dsb.p, h_sb.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dmask.p, vocab_mask, (size_t)V, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dout.p, out_tok, sizeof(int) * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dlp.p, out_lp, sizeof(float) * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
-    if (sample_keys) {
-        PCE_HIP(c, dkeys.reserve(sizeof(int) * (size_t)n));
-        PCE_HIP(c, hipMemcpyAsync(dkeys.p, sample_keys, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    }
+    PCE_UPLOAD(c, dlog, logits, (size_t)logits_elems); PCE_UPLOAD(c, dtok, h_tok); PCE_UPLOAD(c, dsb, h_sb); PCE_UPLOAD(c, dmask, vocab_mask, (size_t)V, 64);
+    PCE_UPLOAD(c, dout, out_tok, (size_t)out_elems); PCE_UPLOAD(c, dlp, out_lp, (size_t)out_elems);
+    if (sample_keys) PCE_UPLOAD(c, dkeys, sample_keys, (size_t)n);
     const int *keys = sample_keys ? dkeys.as<int>() : nullptr;
     DecRules R{rules->eot, rules->timestamp_begin, V, (int)ld, sample_begin_all, rules->max_initial_timestamp_index, temperature, seed_lo, seed_hi,
                form == 0 && probe_token >= 0 ? probe_token : -1};
     if (form == 0) {
-        PCE_HIP(c, dprobe.reserve(sizeof(float) * (size_t)out_elems));
-        PCE_HIP(c, hipMemcpyAsync(dprobe.p, probe_prob, sizeof(float) * (size_t)out_elems, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(dlen.p, h_len.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, dprobe, probe_prob, (size_t)out_elems); PCE_UPLOAD(c, dlen, h_len);
         launch_decode_rules(c, n, dlog.as<float>(), dtok.as<int>(), dlen.as<int>(), pitch, dmask.as<unsigned char>(), R, dsb.as<int>(), dout.as<int>(), dlp.as<float>(),
                             dprobe.as<float>(), keys);
         PCE_HIP(c, hipGetLastError());
-        PCE_HIP(c, hipMemcpyAsync(probe_prob, dprobe.p, sizeof(float) * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, probe_prob, dprobe.p, (size_t)out_elems);
     } else {
         // loop_state: len [n] | ended [n] | ct [8 n] | n_ended [max_new] | step counter.  The lengths are the prompts', the counts and the counter start at zero (as the
         // loop's do); ended and ct come in with the caller's values
         std::vector<int> h_state(loop_state, loop_state + state_elems);
         memcpy(h_state.data(), h_len.data(), sizeof(int) * (size_t)n);
         std::fill(h_state.begin() + (size_t)10 * n, h_state.begin() + (size_t)state_need, 0);
-        PCE_HIP(c, dstate.reserve(sizeof(int) * h_state.size())); PCE_HIP(c, dnext.reserve((sizeof(int) + sizeof(float)) * (size_t)n));
-        PCE_HIP(c, hipMemcpyAsync(dstate.p, h_state.data(), sizeof(int) * h_state.size(), hipMemcpyHostToDevice, c->stream));
+        PCE_UPLOAD(c, dstate, h_state); PCE_HIP(c, dnext.reserve((sizeof(int) + sizeof(float)) * (size_t)n));
         PCE_HIP(c, hipStreamSynchronize(c->stream));              // (h_state leaves scope below)
         int *S = dstate.as<int>(), *next = dnext.as<int>();
         float *next_lp = reinterpret_cast<float *>(next + n);
@@ -319,11 +280,11 @@ int pce_selftest_decode_rules(pce_ctx *c, int32_t form, int32_t n, int32_t n_voc
             launch_step_advance(c, state, n, t_cap, (int)rules->eot, (int)max_new, next, next_lp, S + (size_t)2 * n);
         }
         PCE_HIP(c, hipGetLastError());
-        PCE_HIP(c, hipMemcpyAsync(table, dtok.p, sizeof(int) * (size_t)table_elems, hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(loop_state, dstate.p, sizeof(int) * (size_t)state_elems, hipMemcpyDeviceToHost, c->stream));
+        PCE_FETCH(c, table, dtok.p, (size_t)table_elems);
+        PCE_FETCH(c, loop_state, dstate.p, (size_t)state_elems);
     }
-    PCE_HIP(c, hipMemcpyAsync(out_tok, dout.p, sizeof(int) * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(out_lp, dlp.p, sizeof(float) * (size_t)out_elems, hipMemcpyDeviceToHost, c->stream));
+    PCE_FETCH(c, out_tok, dout.p, (size_t)out_elems);
+    PCE_FETCH(c, out_lp, dlp.p, (size_t)out_elems);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
@@ -353,27 +314,19 @@ int pce_selftest_xattn_stages(pce_ctx *c, const float *resid, const float *ln_w,
         return pce_fail(c, PCE_E_INVALID, "selftest xattn: needs E %lld, out %lld, qp_hi / qp_lo %lld, u_part %lld, ml_part %lld elements",
                         (long long)ne, (long long)n * d, (long long)nqp, (long long)nup, (long long)nml);
     PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    PCE_TRY(lds_optins(c, ws_of(c)));
     DevBuf dres, dlw, dlb, dwq, dbq, dwk, dwkT, dwv, dbv, dE, dkl, dqp, dup, dml, dout;
-    PCE_HIP(c, dres.reserve(sizeof(float) * (size_t)n * d)); PCE_HIP(c, dlw.reserve(sizeof(float) * d)); PCE_HIP(c, dlb.reserve(sizeof(float) * d));
-    PCE_HIP(c, dwq.reserve(2 * dd)); PCE_HIP(c, dbq.reserve(sizeof(float) * d)); PCE_HIP(c, dwk.reserve(2 * dd)); PCE_HIP(c, dwkT.reserve(2 * dd));
-    PCE_HIP(c, dwv.reserve(2 * dd)); PCE_HIP(c, dbv.reserve(sizeof(float) * d)); PCE_HIP(c, dE.reserve(2 * ne + 4096)); PCE_HIP(c, dkl.reserve(sizeof(int) * 2 * (size_t)n));
-    PCE_HIP(c, dqp.reserve(2 * 2 * nqp + 256)); PCE_HIP(c, dup.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
-    PCE_HIP(c, dml.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * 2 + 256)); PCE_HIP(c, dout.reserve(2 * (size_t)n * d + 64));
-    struct Up { void *dst; const void *src; size_t bytes; } ups[] = {
-        {dres.p, resid, sizeof(float) * (size_t)n * d}, {dlw.p, ln_w, sizeof(float) * d}, {dlb.p, ln_b, sizeof(float) * d}, {dwq.p, wq, 2 * dd}, {dbq.p, bq, sizeof(float) * d},
-        {dwk.p, wk, 2 * dd}, {dwv.p, wv, 2 * dd}, {dbv.p, bv, sizeof(float) * d}, {dE.p, E, 2 * ne}, {dkl.p, k_len, sizeof(int) * (size_t)n},
-        {dout.p, out, 2 * (size_t)n * d}};
-    for (const Up &u : ups) PCE_HIP(c, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    const size_t nd = (size_t)n * d, w = (size_t)d;
+    PCE_UPLOAD(c, dres, resid, nd); PCE_UPLOAD(c, dlw, ln_w, w); PCE_UPLOAD(c, dlb, ln_b, w); PCE_UPLOAD(c, dwq, wq, dd); PCE_UPLOAD(c, dbq, bq, w);
+    PCE_UPLOAD(c, dwk, wk, dd); PCE_UPLOAD(c, dwv, wv, dd); PCE_UPLOAD(c, dbv, bv, w); PCE_UPLOAD(c, dE, E, ne, 2048); PCE_UPLOAD(c, dout, out, nd, 32);
+    PCE_UPLOAD(c, dkl, k_len, (size_t)n, (size_t)n);             // k_len | skip
+    PCE_HIP(c, dwkT.reserve(2 * dd)); PCE_HIP(c, dqp.reserve(2 * 2 * nqp + 256)); PCE_HIP(c, dup.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * d + 256));
+    PCE_HIP(c, dml.reserve(sizeof(float) * (size_t)n * XA_MAX_SPLIT * R * 2 + 256));
     op_t *QH = dqp.as<op_t>(), *QL = QH + nqp;
-    if (qp_hi) {
-        PCE_HIP(c, hipMemcpyAsync(QH, qp_hi, 2 * nqp, hipMemcpyHostToDevice, c->stream)); PCE_HIP(c, hipMemcpyAsync(QL, qp_lo, 2 * nqp, hipMemcpyHostToDevice, c->stream));
-    } else PCE_HIP(c, hipMemsetAsync(dqp.p, 0, dqp.cap, c->stream));
-    if (u_part) {
-        PCE_HIP(c, hipMemcpyAsync(dup.p, u_part, sizeof(float) * nup, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(dml.p, ml_part, sizeof(float) * nml, hipMemcpyHostToDevice, c->stream));
-    }
-    if (skip) PCE_HIP(c, hipMemcpyAsync(dkl.as<int>() + n, skip, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (qp_hi) { PCE_PUT(c, QH, qp_hi, nqp); PCE_PUT(c, QL, qp_lo, nqp); }
+    else PCE_HIP(c, hipMemsetAsync(dqp.p, 0, dqp.cap, c->stream));
+    if (u_part) { PCE_PUT(c, dup.p, u_part, nup); PCE_PUT(c, dml.p, ml_part, nml); }
+    if (skip) PCE_PUT(c, dkl.as<int>() + n, skip, (size_t)n);
     hipLaunchKernelGGL(k_transpose_sq, dim3((unsigned)(d / 32), (unsigned)(d / 32)), dim3(256), 0, c->stream, dwk.as<op_t>(), dwkT.as<op_t>(), d);
     XaArgs a{};
     a.E = dE.as<op_t>(); a.e_clip = (int64_t)k_cap * d; a.e_ld = d; a.k_len = dkl.as<int>(); a.skip = skip ? dkl.as<int>() + n : nullptr;
@@ -383,14 +336,9 @@ int pce_selftest_xattn_stages(pce_ctx *c, const float *resid, const float *ln_w,
     y.wv = dwv.as<op_t>(); y.bv = dbv.as<float>(); y.qp_hi = QH; y.qp_lo = QL; y.out = dout.as<op_t>(); y.out_ld = d;
     xattn_launch(c, d, n, a, y);
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(out, dout.p, 2 * (size_t)n * d, hipMemcpyDeviceToHost, c->stream));
-    if (qp_hi) {
-        PCE_HIP(c, hipMemcpyAsync(qp_hi, QH, 2 * nqp, hipMemcpyDeviceToHost, c->stream)); PCE_HIP(c, hipMemcpyAsync(qp_lo, QL, 2 * nqp, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (u_part) {
-        PCE_HIP(c, hipMemcpyAsync(u_part, dup.p, sizeof(float) * nup, hipMemcpyDeviceToHost, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(ml_part, dml.p, sizeof(float) * nml, hipMemcpyDeviceToHost, c->stream));
-    }
+    PCE_FETCH(c, out, dout.p, nd);
+    if (qp_hi) { PCE_FETCH(c, qp_hi, QH, nqp); PCE_FETCH(c, qp_lo, QL, nqp); }
+    if (u_part) { PCE_FETCH(c, u_part, dup.p, nup); PCE_FETCH(c, ml_part, dml.p, nml); }
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     if (nodes_out) *nodes_out = nodes;
     return PCE_OK;
@@ -412,21 +360,18 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
 {
     if (!c || !A || !B || !out || M <= 0 || N <= 0 || K <= 0) return PCE_E_INVALID;
     PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    PCE_TRY(lds_optins(c, ws_of(c)));
     if (epilogue >= 16 && epilogue <= 19) {
         // the tiled / few-row kernels behind launch_gemm (which of them runs follows from the shape and PCE_GEMM_SKINNY; pce_selftest_gemm_tiled
         // chooses one and takes every epilogue): 16 = bias,
         // 17 = bias + GELU (16-bit outputs), 19 = accumulate into a zeroed fp32 matrix (out receives M * N floats)
         const bool f32 = epilogue == 19;
         DevBuf tA, tB, tC, tb;
-        PCE_HIP(c, tA.reserve((size_t)M * K * 2 + 4096)); PCE_HIP(c, tB.reserve((size_t)(N + 128) * K * 2 + 4096)); PCE_HIP(c, tC.reserve((size_t)M * N * 4 + 4096));
-        PCE_HIP(c, tb.reserve((size_t)(N + 128) * 4));
-        PCE_HIP(c, hipMemsetAsync(tB.p, 0, (size_t)(N + 128) * K * 2, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(tA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(tB.p, B, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemsetAsync(tb.p, 0, (size_t)(N + 128) * 4, c->stream));
-        if (bias) PCE_HIP(c, hipMemcpyAsync(tb.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemsetAsync(tC.p, 0, (size_t)M * N * 4, c->stream));
+        PCE_UPLOAD(c, tA, A, (size_t)M * K, 2048);
+        PCE_ZERO(uint16_t, c, tB, (size_t)(N + 128) * K, 2048); PCE_PUT(c, tB.p, B, (size_t)N * K);
+        PCE_ZERO(float, c, tb, (size_t)(N + 128));
+        if (bias) PCE_PUT(c, tb.p, bias, (size_t)N);
+        PCE_ZERO(float, c, tC, (size_t)M * N, 1024);
         if (N % 128) return pce_fail(c, PCE_E_INVALID, "selftest gemm (tiled): N must be a multiple of 128");
         c->gemm_few_rows = true;                                   // (the few-row kernel is eligible here, as in an incremental decoding step)
         struct Off { pce_ctx *c; ~Off() { c->gemm_few_rows = false; } } off{c};
@@ -435,7 +380,8 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
         else if (epilogue == 19) launch_gemm<EPI_RESID_F32>(c, tA.as<op_t>(), K, 0, tB.as<op_t>(), M, N, K, tb.as<float>(), tC.p, N, 0, 1);
         else return pce_fail(c, PCE_E_INVALID, "selftest gemm: epilogue 18 does not exist");
         PCE_HIP(c, hipGetLastError());
-        PCE_HIP(c, hipMemcpyAsync(out, tC.p, (size_t)M * N * (f32 ? 4 : 2), hipMemcpyDeviceToHost, c->stream));
+        if (f32) PCE_FETCH(c, reinterpret_cast<float *>(out), tC.p, (size_t)M * N);
+        else PCE_FETCH(c, out, tC.p, (size_t)M * N);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         pce_profile_collect(c);
         return PCE_OK;
@@ -443,11 +389,9 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
     const size_t n_out = epilogue == 2 ? (size_t)(M / rows_per_clip) * N * vt_sp
                          : epilogue >= 256 ? (size_t)M * epilogue + (size_t)(M / rows_per_clip) * (N - epilogue) * vt_sp : (size_t)M * N;
     DevBuf dA, dB, dC, dbias;
-    PCE_HIP(c, dA.reserve((size_t)M * K * 2)); PCE_HIP(c, dB.reserve((size_t)N * K * 2)); PCE_HIP(c, dC.reserve(n_out * 2)); PCE_HIP(c, dbias.reserve((size_t)N * 4));
-    PCE_HIP(c, hipMemcpyAsync(dA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dB.p, B, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
-    if (bias) PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemsetAsync(dC.p, 0, n_out * 2, c->stream));
+    PCE_UPLOAD(c, dA, A, (size_t)M * K); PCE_UPLOAD(c, dB, B, (size_t)N * K);
+    if (bias) PCE_UPLOAD(c, dbias, bias, (size_t)N);
+    PCE_ZERO(uint16_t, c, dC, n_out);
     bool ok = false;
     const float *bp = bias ? dbias.as<float>() : nullptr;
     if (epilogue == 0) ok = launch_gemm_flat<FEPI_BF16>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, N);
@@ -456,14 +400,8 @@ int pce_selftest_gemm(pce_ctx *c, const uint16_t *A, const uint16_t *B, const fl
     else if (epilogue >= 256 && epilogue % 256 == 0 && epilogue < N)      // split launch: columns [0, epilogue) row-major [M][epilogue], then the V^T image of the rest
         ok = launch_gemm_flat<FEPI_SPLIT>(c, dA.as<op_t>(), dB.as<op_t>(), bp, dC.as<op_t>(), M, N, K, epilogue, rows_per_clip, vt_sp, PCE_K_GEMM_FLAT,
                                           dC.as<op_t>() + (size_t)M * epilogue, epilogue);
-    int rc = PCE_OK;
-    if (!ok) rc = pce_fail(c, PCE_E_LIMIT, "shape not handled by the 256 x 256 kernel (N %% 256, K %% 64)");
-    else {
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dC.p, n_out * 2, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = pce_fail(c, PCE_E_DEVICE, "selftest gemm: %s", hipGetErrorString(e));
-    }
+    int rc = ok ? PCE_OK : pce_fail(c, PCE_E_LIMIT, "shape not handled by the 256 x 256 kernel (N %% 256, K %% 64)");
+    if (ok) rc = [&]() -> int { PCE_HIP(c, hipGetLastError()); PCE_FETCH(c, out, dC.p, n_out); PCE_HIP(c, hipStreamSynchronize(c->stream)); return PCE_OK; }();
     (void)hipStreamSynchronize(c->stream);
     pce_profile_collect(c);
     return rc;
@@ -475,23 +413,14 @@ int pce_selftest_gemm_resid(pce_ctx *c, const uint16_t *A, const uint16_t *B, co
 {
     if (!c || !A || !B || !resid_inout || M <= 0 || N <= 0 || K <= 0) return PCE_E_INVALID;
     PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
+    PCE_TRY(lds_optins(c, ws_of(c)));
     DevBuf dA, dB, dC, dbias;
-    PCE_HIP(c, dA.reserve((size_t)M * K * 2)); PCE_HIP(c, dB.reserve((size_t)N * K * 2)); PCE_HIP(c, dC.reserve((size_t)M * N * 2)); PCE_HIP(c, dbias.reserve((size_t)N * 4));
-    PCE_HIP(c, hipMemcpyAsync(dA.p, A, (size_t)M * K * 2, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dB.p, B, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
-    if (bias) PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dC.p, resid_inout, (size_t)M * N * 2, hipMemcpyHostToDevice, c->stream));
-    int rc = PCE_OK;
-    if (!launch_gemm_flat<FEPI_RESID>(c, dA.as<op_t>(), dB.as<op_t>(), bias ? dbias.as<float>() : nullptr, dC.as<op_t>(), M, N, K, N, 1, 0, PCE_K_GEMM_FLAT, nullptr, 0,
-                                      dC.as<op_t>()))
-        rc = pce_fail(c, PCE_E_LIMIT, "shape not handled by the 256 x 256 kernel (N %% 256, K %% 64)");
-    else {
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(resid_inout, dC.p, (size_t)M * N * 2, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = pce_fail(c, PCE_E_DEVICE, "selftest gemm (residual epilogue): %s", hipGetErrorString(e));
-    }
+    PCE_UPLOAD(c, dA, A, (size_t)M * K); PCE_UPLOAD(c, dB, B, (size_t)N * K); PCE_UPLOAD(c, dC, resid_inout, (size_t)M * N);
+    if (bias) PCE_UPLOAD(c, dbias, bias, (size_t)N);
+    const bool ok = launch_gemm_flat<FEPI_RESID>(c, dA.as<op_t>(), dB.as<op_t>(), bias ? dbias.as<float>() : nullptr, dC.as<op_t>(), M, N, K, N, 1, 0, PCE_K_GEMM_FLAT,
+                                                 nullptr, 0, dC.as<op_t>());
+    int rc = ok ? PCE_OK : pce_fail(c, PCE_E_LIMIT, "shape not handled by the 256 x 256 kernel (N %% 256, K %% 64)");
+    if (ok) rc = [&]() -> int { PCE_HIP(c, hipGetLastError()); PCE_FETCH(c, resid_inout, dC.p, (size_t)M * N); PCE_HIP(c, hipStreamSynchronize(c->stream)); return PCE_OK; }();
     (void)hipStreamSynchronize(c->stream);
     pce_profile_collect(c);
     return rc;
@@ -534,19 +463,15 @@ int pce_selftest_gemm_tiled(pce_ctx *c, int32_t kernel, int32_t epilogue, const 
                         kernel, epilogue, M, N, K, (long long)lda, batch, v_col0);
     if (kernel_used) *kernel_used = kind;
     PCE_HIP(c, hipSetDevice(c->device));
-    { const int rc = lds_optins(c, ws_of(c)); if (rc) return rc; }
-    const size_t esz = f32 ? 4 : 2;
+    PCE_TRY(lds_optins(c, ws_of(c)));
     DevBuf dA, dB, dbias, dC, dpos, dvt;
-    PCE_HIP(c, dA.reserve(2 * (size_t)a_len)); PCE_HIP(c, dB.reserve(2 * (size_t)N * K)); PCE_HIP(c, dC.reserve(esz * (size_t)c_len + 16));
-    PCE_HIP(c, hipMemcpyAsync(dA.p, A, 2 * (size_t)a_len, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dB.p, B, 2 * (size_t)N * K, hipMemcpyHostToDevice, c->stream));
-    PCE_HIP(c, hipMemcpyAsync(dC.p, C, esz * (size_t)c_len, hipMemcpyHostToDevice, c->stream));       // (read by RESID_F32; kept where nothing is written)
-    if (bias) { PCE_HIP(c, dbias.reserve(sizeof(float) * N)); PCE_HIP(c, hipMemcpyAsync(dbias.p, bias, sizeof(float) * N, hipMemcpyHostToDevice, c->stream)); }
-    if (epilogue == EPI_GELU_POS_F32) {
-        PCE_HIP(c, dpos.reserve(sizeof(float) * (size_t)pos_T * N));
-        PCE_HIP(c, hipMemcpyAsync(dpos.p, pos, sizeof(float) * (size_t)pos_T * N, hipMemcpyHostToDevice, c->stream));
-    }
-    if (qkv) { PCE_HIP(c, dvt.reserve(2 * (size_t)vt_len)); PCE_HIP(c, hipMemcpyAsync(dvt.p, vt, 2 * (size_t)vt_len, hipMemcpyHostToDevice, c->stream)); }
+    PCE_UPLOAD(c, dA, A, (size_t)a_len); PCE_UPLOAD(c, dB, B, (size_t)N * K);
+    // C goes in as well: read by RESID_F32, kept where nothing is written (16 bytes of slack)
+    if (f32) PCE_UPLOAD(c, dC, static_cast<const float *>(C), (size_t)c_len, 4);
+    else PCE_UPLOAD(c, dC, static_cast<const uint16_t *>(C), (size_t)c_len, 8);
+    if (bias) PCE_UPLOAD(c, dbias, bias, (size_t)N);
+    if (epilogue == EPI_GELU_POS_F32) PCE_UPLOAD(c, dpos, pos, (size_t)pos_T * N);
+    if (qkv) PCE_UPLOAD(c, dvt, vt, (size_t)vt_len);
     const op_t *a = dA.as<op_t>(), *b = dB.as<op_t>();
     const float *bp = bias ? dbias.as<float>() : nullptr;
     switch (epilogue) {
@@ -561,8 +486,9 @@ int pce_selftest_gemm_tiled(pce_ctx *c, int32_t kernel, int32_t epilogue, const 
     default: launch_gemm_kernel<EPI_F32>(c, kind, a, lda, a_batch, b, M, N, K, bp, dC.p, ldc, c_batch, batch, nullptr, 1, 0, 0); break;
     }
     PCE_HIP(c, hipGetLastError());
-    PCE_HIP(c, hipMemcpyAsync(C, dC.p, esz * (size_t)c_len, hipMemcpyDeviceToHost, c->stream));
-    if (qkv) PCE_HIP(c, hipMemcpyAsync(vt, dvt.p, 2 * (size_t)vt_len, hipMemcpyDeviceToHost, c->stream));
+    if (f32) PCE_FETCH(c, static_cast<float *>(C), dC.p, (size_t)c_len);
+    else PCE_FETCH(c, static_cast<uint16_t *>(C), dC.p, (size_t)c_len);
+    if (qkv) PCE_FETCH(c, vt, dvt.p, (size_t)vt_len);
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     return PCE_OK;
@@ -581,18 +507,14 @@ int pce_selftest_layernorm(pce_ctx *c, int32_t form, int32_t rows, int32_t d, co
         const bool in_place = flags & 2;
         if (in_place && !resid_out) return PCE_E_INVALID;
         DevBuf dx, dw, db, dout;
-        PCE_HIP(c, dx.reserve(sizeof(float) * n)); PCE_HIP(c, dw.reserve(sizeof(float) * d)); PCE_HIP(c, db.reserve(sizeof(float) * d));
-        PCE_HIP(c, dout.reserve((form ? 2 : 4) * n));
-        PCE_HIP(c, hipMemcpyAsync(dx.p, x, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(dw.p, w, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemcpyAsync(db.p, b, sizeof(float) * d, hipMemcpyHostToDevice, c->stream));
-        PCE_HIP(c, hipMemsetAsync(dout.p, 0, (form ? 2 : 4) * n, c->stream));
+        PCE_UPLOAD(c, dx, static_cast<const float *>(x), n); PCE_UPLOAD(c, dw, w, (size_t)d); PCE_UPLOAD(c, db, b, (size_t)d);
+        if (form) PCE_ZERO(uint16_t, c, dout, n); else PCE_ZERO(float, c, dout, n);
         float *o2 = in_place ? dx.as<float>() : nullptr;
         if (form) launch_layernorm<op_t>(c, dx.as<float>(), dw.as<float>(), db.as<float>(), rows, d, dout.as<op_t>(), eps, o2, flags & 1);
         else launch_layernorm<float>(c, dx.as<float>(), dw.as<float>(), db.as<float>(), rows, d, dout.as<float>(), eps, o2, flags & 1);
         PCE_HIP(c, hipGetLastError());
-        PCE_HIP(c, hipMemcpyAsync(out, dout.p, (form ? 2 : 4) * n, hipMemcpyDeviceToHost, c->stream));
-        if (in_place) PCE_HIP(c, hipMemcpyAsync(resid_out, dx.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+        if (form) PCE_FETCH(c, static_cast<uint16_t *>(out), dout.p, n); else PCE_FETCH(c, static_cast<float *>(out), dout.p, n);
+        if (in_place) PCE_FETCH(c, static_cast<float *>(resid_out), dx.p, n);
         PCE_HIP(c, hipStreamSynchronize(c->stream));
         return PCE_OK;
     }
