@@ -72,9 +72,11 @@ extern "C" {
  * through the decoding calls' own launches);
  * 18 = pce_selftest_logmel_image (the 16-bit time-major log-mel image the conv stem reads, copied out as the last run left it);
  * 19 = pce_selftest_xattn_stages (pce_selftest_xattn with the skip list and the buffers between its three kernels copied out: Q' as hi + lo, the nodes' U
- * and (m, l)). */
+ * and (m, l));
+ * 20 = pce_wx_align (whisperX's forced alignment of a batch of segments: wildcard trellis and beam back-track) and its three kernel ids, which
+ * sit behind minor 16's and in front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by three (pce_kernel_name follows). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 19
+#define PCE_API_MINOR 20
 
 typedef struct pce_ctx pce_ctx;
 
@@ -680,7 +682,7 @@ enum pce_dtw_status { PCE_DTW_OK = 0, PCE_DTW_EMPTY = 1, PCE_DTW_NO_PATH = 2 };
 int pce_dtw_series(pce_ctx *ctx, const double *a, const int64_t *a_off, const double *b, const int64_t *b_off, const int32_t *win_lo,
                    const int32_t *win_hi, int32_t batch, int32_t *path_i, int32_t *path_j, int32_t *path_len, double *dist, int32_t *status);
 
-/* ---- CTC forced alignment (the numeric core of Code/Aligners/CTCFA.py and of whisperX.py's wav2vec2 pass) ----
+/* ---- CTC forced alignment (the numeric core of Code/Aligners/CTCFA.py; whisperX.py runs its own programme: pce_wx_align below) ----
  * A CTC acoustic model gives frame-wise log-probabilities; the Viterbi pass over the 2 L + 1 blank-interleaved states of the transcript gives
  * the frame-to-label path.  The recurrence is the CPU implementation of torchaudio.functional.forced_align (third party and absent: restated
  * from its published source, parity unpinned).  State i carries `blank` (i even) or targets[i / 2] (i odd);  t = 0: alpha[0] = lp[0][blank],
@@ -712,6 +714,52 @@ int pce_ctc_align(pce_ctx *ctx, const float *emissions, int32_t emissions_on_dev
                   int32_t n_clips, const pce_ctc_params *p,
                   int32_t *path /* [sum n_frames] or NULL */, float *frame_score /* [sum n_frames] or NULL */,
                   int32_t *tok_first, int32_t *tok_last /* [target_off[n]] */, float *score /* [n] */, int32_t *status /* [n] */);
+
+/* ---- whisperX forced alignment (the numeric core of Code/Aligners/whisperX.py: whisperx.align's trellis, wildcard and beam back-track) ----
+ * whisperX does not run the CTC recurrence above: it runs a trellis over the J characters of a transcript segment with no interleaved blanks,
+ * gives characters the model's dictionary lacks a wildcard emission, and walks back with a beam search that reads the trellis values
+ * themselves.  whisperx is third party and absent: restated from the published source of whisperx 3.3.x (alignment.py).  The trellis lines
+ * are pinned bit for bit to torch's CPU operators (zeros / cumsum / maximum / where); the back-track's parity with the package is unpinned.
+ * Per clip (one transcript segment): e[T][V] fp32 log-probabilities, tok[J] with -1 = wildcard, else 0 <= tok[j] < V; blank; beam width W.
+ * Wildcard emission: wild(t, k) = e[t][k] for k >= 0; for k = -1 the max over v != blank of e[t][v] (-inf when V = 1).
+ * Trellis, fp32 tr[T][J]:  tr[0][0] = 0;  for t >= 1, tr[t][0] = fp32(sum_{u = 1..t} (double) e[u][blank]), accumulated in fp64 in frame order,
+ * each prefix rounded to fp32 (what torch.cumsum does for float32 on the CPU; a sequential fp32 sum differs);  tr[0][j] = -inf for j >= 1;
+ * the wedge: tr[t][0] = +inf for t >= max(0, T - J + 1) when J >= 2, and for every t when J = 1 (Python's trellis[-J + 1:, 0] = inf, where
+ * -0: is the whole column);  for t = 0 .. T - 2 and j >= 1:
+ *     tr[t + 1][j] = max(fp32(tr[t][j] + e[t][blank]), fp32(tr[t][j - 1] + wild(t, tok[j])))
+ * fp32 adds and a max only (no multiply: no FMA can form).  The wedge carries +inf along the diagonal and never reaches tr[T - 1][J - 1].
+ * Beam back-track: a beam is (j, t, score) plus its path; all beams move in lock step, each step takes t to t - 1.  It starts with one beam
+ * (J - 1, T - 1, tr[T - 1][J - 1]) whose path holds the point (token index J - 1, frame T - 1, lp = e[T - 1][blank]).  While beams exist and
+ * the first beam has j > 0, for every beam in order: a beam with t <= 0 is dropped;  STAY: if tr[t - 1][j] is not +-inf, the candidate
+ * (j, t - 1, tr[t - 1][j]) with the point (j, t - 1, lp = e[t - 1][blank]);  CHANGE: if j > 0 and tr[t - 1][j - 1] is not +-inf, the candidate
+ * (j - 1, t - 1, tr[t - 1][j - 1]) with the point (j - 1, t - 1, lp = wild(t - 1, tok[j])): the emission belongs to the token being left (the
+ * source's choice).  The candidates are ordered by score, descending, by a STABLE sort (equal scores keep their emission order, as Python's
+ * sorted(..., reverse=True) does; stay from (t, j) and change from (t, j + 1) land on one cell with one score, so ties are structural), and
+ * the first W are kept.  No beams left: PCE_WX_NO_PATH.  Otherwise the first beam wins; its remaining frames t - 1 .. 0 get the points
+ * (j, ., lp = e[.][blank]).  Per frame: path_tok[t] (a token INDEX, 0 .. J - 1) and path_lp[t] (an fp32 copy of the emission named above; no
+ * exp on the device).  It follows that J = 1 gives token 0 on every frame (score +inf: the wedge), that T = 1 with J >= 2 and J > T are
+ * PCE_WX_NO_PATH, and that J = T changes at every step.  NaN emissions: the result is unspecified, but the call returns and every written
+ * index is in range.
+ * emissions, row_start, n_frames, n_vocab, emissions_on_device: exactly as pce_ctc_align takes them (ragged rows or a padded tensor; device
+ * memory is read in place).  Every other pointer is host memory.  tokens[token_off[q] .. token_off[q + 1]) are clip q's tokens; a token may
+ * equal blank.  PCE_E_INVALID, before anything is launched: a token outside {-1} u [0, n_vocab), beam_width outside 1 .. PCE_WX_MAX_BEAM, NULL
+ * or decreasing offsets.  A clip of more than PCE_WX_MAX_TOKENS tokens is PCE_E_LIMIT: the sweep keeps a clip's row in the registers of one
+ * workgroup and has no general form (whisperX aligns segments of at most 30 s, so J <= T <= 1 500 at wav2vec2's stride of 20 ms).
+ * path_tok / path_lp (either may be NULL): clip q's frames start at element sum of n_frames[0 .. q).  trellis (or NULL): the stage hook, the
+ * tables between the two kernels, clip-major, clip q's T_q x J_q row-major floats behind those of the clips before it.  score[q] =
+ * tr[T - 1][J - 1].  status[q]: PCE_WX_EMPTY (J = 0 or T = 0; nothing is launched for the clip, score NaN), PCE_WX_NO_PATH (score keeps the
+ * final cell); such a clip has path_tok -1 and path_lp NaN.  Clips are processed in groups whose tables (T x J fp32, J rounded up to 4) fit
+ * PCE_CTC_TRACE_MB MiB together (environment, read at pce_create; default 4096); a single clip over that budget is PCE_E_LIMIT.  A clip's
+ * outputs depend on its own emissions and tokens only: not on the batch, or on its place in it.  Since minor 20. */
+#define PCE_WX_MAX_TOKENS 4096
+#define PCE_WX_MAX_BEAM 8
+typedef struct { int32_t blank; int32_t beam_width; int32_t reserved[2]; } pce_wx_params;
+enum pce_wx_status { PCE_WX_OK = 0, PCE_WX_EMPTY = 1, PCE_WX_NO_PATH = 2 };
+int pce_wx_align(pce_ctx *ctx, const float *emissions, int32_t emissions_on_device, const int64_t *row_start /* [n] */,
+                 const int32_t *n_frames /* [n] */, int32_t n_vocab, const int32_t *tokens, const int64_t *token_off /* [n+1] */,
+                 int32_t n_clips, const pce_wx_params *p,
+                 int32_t *path_tok /* [sum n_frames] or NULL */, float *path_lp /* [sum n_frames] or NULL */,
+                 float *trellis /* [sum T_q * J_q] or NULL */, float *score /* [n] */, int32_t *status /* [n] */);
 
 /* ---- batched Needleman-Wunsch word alignment ------------------------------
  * Replaces needleman_wunsch (Code/Pipeline/NeedlemanWunschAlignement.py:27-81) for a batch of sequence pairs.
@@ -885,6 +933,9 @@ enum pce_kernel_id {
     PCE_K_CREPE_FRAMES, PCE_K_CREPE_CONV1, PCE_K_CREPE_CONV2, PCE_K_CREPE_CONV, PCE_K_CREPE_CLASSIFIER, PCE_K_CREPE_DECODE, PCE_K_CREPE_VITERBI,
     /* minor 16: pce_w2v_run as a whole; the waveform layer (statistics, finish and recompute passes together), the positional convolution, the log-softmax tail */
     PCE_K_W2V, PCE_K_W2V_WAVE, PCE_K_W2V_POSCONV, PCE_K_W2V_TAIL,
+    /* minor 20: pce_wx_align's row maxima for the wildcard (launched only when a clip holds one), the sweep (both launch shapes) and the beam back-track;
+     * work count = emission values read, trellis CELLS, frames */
+    PCE_K_WX_ROWMAX, PCE_K_WX_TRELLIS, PCE_K_WX_BACKTRACK,
     /* minor 15: the register form (both launch shapes), the general form and the walk back of pce_ctc_align; work count = trellis CELLS (frames for the walk) */
     PCE_K_CTC, PCE_K_CTC_GENERAL, PCE_K_CTC_TRACE,
     /* minor 10: their work count is swept CELLS (k_seqmatch: every range of every pair, recursion included; k_seqmatch_align: n_a * n_b) */

@@ -1,6 +1,7 @@
 """Frame-wise log-probabilities of a ``transformers`` ``...ForCTC`` model for 16 kHz clips: ``hf_emissions`` runs the caller's model under torch
 (plumbing, no kernel of this project; the default), ``engine_emissions`` runs a ``Wav2Vec2ForCTC``'s forward pass on the engine's own kernels
-(``pce_w2v_run``) with the same windowing and leaves the emissions in device memory.
+(``pce_w2v_run``) with the same windowing and leaves the emissions in device memory.  ``segment_emissions`` is whisperX's way:
+one transcript segment at a time, no windows (torch plumbing too; ``Aligners/whisperX.py``).
 
 The windowing is that of ``ctc-forced-aligner``'s ``generate_emissions`` (third party and absent: restated from the published source,
 parity unpinned): a clip is padded to a whole number of windows of ``window_s`` seconds, every window is run with ``context_s`` seconds
@@ -85,3 +86,50 @@ def engine_emissions(engine, model, pcm_list, window_s=30, context_s=2):
         engine.w2v_load(model)
     engine.upload(clips, SAMPLE_RATE)
     return engine.w2v_emissions(window_s, context_s, star=True)
+
+
+MIN_SEGMENT_SAMPLES = 400       # wav2vec2's feature encoder gives no frame for less
+
+
+def segment_emissions(model, pcm16k, segments, device, batch_size=1):
+    """The emissions ``whisperx.align`` computes, one transcript segment at a time (third party and absent: restated from the published source
+    of whisperx 3.3.x, parity unpinned): segment ``{"start": t1, "end": t2}`` owns the samples ``int(t1 * 16000) : int(t2 * 16000)`` of the
+    16 kHz mono signal ``pcm16k`` (int16, scaled by 1 / 32768, or float); fewer than 400 samples are padded with zeros to 400; the caller's
+    ``transformers`` ``...ForCTC`` model runs on each segment ALONE (no padding to a common length: a segment's frames do not depend on its
+    neighbours; ``batch_size`` only groups segments of equal length) and ``log_softmax`` is applied in float32.  Torch plumbing, as
+    ``hf_emissions`` is.  -> (float32 tensor ``[B, T_max, V]`` on ``device``, rows past a segment's frames zero; ``n_frames`` int32 numpy
+    [B]): what ``ProsodyEngine.wx_align`` takes by pointer."""
+    import torch
+    import torch.nn.functional as F
+
+    dev = torch.device(device)
+    model = model.to(dev).eval()
+    dtype = next(model.parameters()).dtype
+    x = np.asarray(pcm16k).reshape(-1)
+    x = x.astype(np.float32) / 32768.0 if x.dtype.kind in "iu" else x.astype(np.float32)
+    wave = torch.from_numpy(x)
+    pieces = []
+    for seg in segments:
+        piece = wave[int(seg["start"] * SAMPLE_RATE):int(seg["end"] * SAMPLE_RATE)]
+        if piece.shape[0] < MIN_SEGMENT_SAMPLES:
+            piece = F.pad(piece, (0, MIN_SEGMENT_SAMPLES - piece.shape[0]))
+        pieces.append(piece)
+    out = [None] * len(pieces)
+    by_length = {}
+    for k, piece in enumerate(pieces):
+        by_length.setdefault(int(piece.shape[0]), []).append(k)
+    with torch.inference_mode():
+        for ks in by_length.values():
+            for i in range(0, len(ks), max(1, int(batch_size))):
+                group = ks[i:i + max(1, int(batch_size))]
+                logits = model(torch.stack([pieces[k] for k in group]).to(dev, dtype)).logits.float()
+                em = torch.log_softmax(logits, dim=-1)
+                for r, k in enumerate(group):
+                    out[k] = em[r]
+    n_frames = np.array([int(e.shape[0]) for e in out], dtype=np.int32)
+    if not len(out):
+        return torch.zeros((0, 0, 0), dtype=torch.float32, device=dev), n_frames
+    packed = torch.zeros((len(out), int(n_frames.max()), int(out[0].shape[1])), dtype=torch.float32, device=dev)
+    for k, e in enumerate(out):
+        packed[k, :n_frames[k]] = e
+    return packed.contiguous(), n_frames

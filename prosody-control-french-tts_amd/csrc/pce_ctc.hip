@@ -1,7 +1,7 @@
 // pce_ctc.hip -- CTC forced alignment: the Viterbi pass over the 2 L + 1 blank-interleaved states of a transcript, for a batch of clips.
 //
-// Two of the reference's aligners (Code/Aligners/CTCFA.py through the ctc-forced-aligner command, Code/Aligners/whisperX.py through its
-// wav2vec2 pass) rest on this dynamic programme.  The recurrence is the CPU implementation of torchaudio.functional.forced_align; that
+// One of the reference's aligners (Code/Aligners/CTCFA.py through the ctc-forced-aligner command) rests on this dynamic programme;
+// Code/Aligners/whisperX.py does not: it runs its own trellis and back-track (pce_wx.hip).  The recurrence is the CPU implementation of torchaudio.functional.forced_align; that
 // package is third party and absent: restated from its published source, parity unpinned.  State i carries `blank` (i even) or
 // targets[i / 2] (i odd).  alpha_0[0] = lp[0][blank], alpha_0[1] = lp[0][targets[0]], the rest -inf.  For t >= 1:
 //     x0 = alpha[i],  x1 = alpha[i - 1],  x2 = alpha[i - 2] where i is odd, i != 1 and targets[i / 2] != targets[i / 2 - 1], else -inf

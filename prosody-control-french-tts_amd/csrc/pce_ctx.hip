@@ -372,6 +372,7 @@ const char *pce_kernel_name(int id)
         "k_ms_energy", "k_silence_scan", "k_silence_ranges",
         "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
         "w2v_forward", "k_w2v_wave", "k_w2v_posconv", "k_w2v_tail",
+        "k_wx_rowmax", "k_wx_trellis", "k_wx_backtrack",
         "k_ctc", "k_ctc_general", "k_ctc_trace", "k_seqmatch", "k_seqmatch_align"};
     return (id >= 0 && id < PCE_K_COUNT) ? names[id] : "?";
 }

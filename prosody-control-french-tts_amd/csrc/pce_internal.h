@@ -187,6 +187,10 @@ struct pce_ctx {
     // form's alpha rows, the batch's results
     struct Ctc { DevBuf lp, tab, ids, tgt, fin, trace, scratch, path, fscore, first, last, score, status; } ctc;
 
+    // whisperX alignment (pce_wx.hip): uploaded emissions, clip table, clip-id lists, tokens, the wildcard's row maxima, the trellis tables of the group in
+    // flight, the back-track's record (8 words per frame), the batch's results
+    struct Wx { DevBuf lp, tab, ids, tok, wmax, table, rec, path, plp, score, status; } wx;
+
     // whisper / BERT state, opaque (pce_whisper_impl.inc): one slot per operand-type build (0: bf16, 1: fp16); whisper_ops selects the build the
     // entry points of include/pce.h forward to (pce_whisper_set_operands, or PCE_WHISPER_OPERANDS=fp16 at pce_create)
     void *whisper_slot[2] = {nullptr, nullptr};

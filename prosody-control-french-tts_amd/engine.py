@@ -153,6 +153,10 @@ class CtcParams(C.Structure):
     _fields_ = [("blank", C.c_int32), ("form", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class WxParams(C.Structure):
+    _fields_ = [("blank", C.c_int32), ("beam_width", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class CrepeDims(C.Structure):
     _fields_ = [("c_out", C.c_int32 * 6), ("reserved", C.c_int32 * 2)]
 
@@ -178,6 +182,8 @@ DTW_OK, DTW_EMPTY, DTW_NO_PATH = 0, 1, 2                      # enum pce_dtw_sta
 CTC_OK, CTC_EMPTY, CTC_TOO_SHORT, CTC_NO_PATH = 0, 1, 2, 3     # enum pce_ctc_status
 CTC_REG_STATES = 4096                                         # PCE_CTC_REG_STATES of include/pce.h: the states (2 L + 1) the register form of k_ctc holds
 CTC_FORMS = {"auto": 0, "register": 1, "general": 2}
+WX_OK, WX_EMPTY, WX_NO_PATH = 0, 1, 2                         # enum pce_wx_status
+WX_MAX_TOKENS, WX_MAX_BEAM = 4096, 8                          # PCE_WX_MAX_TOKENS / PCE_WX_MAX_BEAM of include/pce.h: the tokens k_wx_trellis sweeps, the beams k_wx_backtrack keeps
 DTW_SERIES_ROWS, DTW_SERIES_COLS = 1024, 2048                 # PCE_DTW_SERIES_ROWS / _COLS of include/pce.h: the tile of k_dtw_series
 
 KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs_gate",
@@ -189,6 +195,7 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges",
               "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
               "w2v_forward", "k_w2v_wave", "k_w2v_posconv", "k_w2v_tail",
+              "k_wx_rowmax", "k_wx_trellis", "k_wx_backtrack",
               "k_ctc", "k_ctc_general", "k_ctc_trace", "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
 
 # every symbol include/pce.h declares (tests/test_abi_and_shard.py), in the header's order and under its section titles: name -> argtypes, or
@@ -290,6 +297,8 @@ SIGNATURES = {
     "pce_dtw_series": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     # CTC forced alignment
     "pce_ctc_align": [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    # whisperX forced alignment
+    "pce_wx_align": [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     # batched Needleman-Wunsch word alignment
     "pce_nw_align": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
     # batched Levenshtein distance
@@ -1047,23 +1056,9 @@ class ProsodyEngine:
                                              pi.ctypes.data, pj.ctypes.data, pl.ctypes.data, dist.ctypes.data, st.ctypes.data))
         return [(np.stack([pi[oo[k]:oo[k] + pl[k]], pj[oo[k]:oo[k] + pl[k]]], axis=1), float(dist[k]), int(st[k])) for k in range(nb)]
 
-    def ctc_align(self, emissions, targets, blank=0, n_frames=None, form="auto", return_path=True):
-        """CTC forced alignment of a batch of clips (``pce_ctc_align``: the Viterbi pass of ``torchaudio.functional.forced_align`` over the
-        ``2 L + 1`` blank-interleaved states of each transcript, bit-identical to its CPU restatement).  ``emissions``: a list of
-        ``[T_c, V]`` float32 arrays of log-probabilities (packed and uploaded by the call), a ``DeviceEmissions`` of this engine's
-        ``w2v_emissions`` (read in place), or ONE float32 contiguous torch tensor
-        ``[B, T_max, V]`` with ``n_frames`` (valid frames per clip; default ``T_max`` for all): a ROCm tensor is read in place through its
-        pointer, a CPU tensor is handed over as host memory (a process that uses ROCm tensors imports torch BEFORE it creates its first engine:
-        torch ships its own copy of the HIP runtime, and the copy loaded first serves both).  ``targets``: one sequence of vocabulary indices per clip (none may be ``blank``).
-        ``form``: ``"auto"`` | ``"register"`` | ``"general"`` (the register form holds ``CTC_REG_STATES`` states; asking it for more raises).
-        -> one dict per clip: ``path`` int32 [T] (the label of every frame) and ``frame_score`` float32 [T] (``emissions[t, path[t]]``) unless
-        ``return_path`` is false, ``tok_first`` / ``tok_last`` int32 [L] (first and last frame, inclusive, of every target), ``score``
-        (numpy float32: the final alpha) and ``status`` (``CTC_OK``; ``CTC_EMPTY``: no targets or no frames; ``CTC_TOO_SHORT``: fewer frames
-        than targets + adjacent repeats; ``CTC_NO_PATH``: the best score is -inf or NaN).  A clip without a path has ``path`` -1,
-        ``frame_score`` NaN and token frames -1."""
-        if form not in CTC_FORMS:
-            raise ValueError(f"form: one of {sorted(CTC_FORMS)}")
-        tg = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in targets]
+    def _emission_args(self, emissions, n_frames):
+        """The three ways ``ctc_align`` and ``wx_align`` take emissions (a list of ``[T, V]`` arrays, a ``DeviceEmissions``, one torch tensor
+        ``[B, T_max, V]`` with ``n_frames``) -> ``(n, V, n_frames int32, row_start int64, pointer, on_device, keepalive)``."""
         keep = None
         if isinstance(emissions, DeviceEmissions):
             if n_frames is not None:
@@ -1105,6 +1100,26 @@ class ProsodyEngine:
             if on_device:
                 import torch
                 torch.cuda.current_stream(e.device).synchronize()      # the tensor's producer has finished before this engine's stream reads it
+        return n, V, nfr, row_start, ptr, on_device, keep
+
+    def ctc_align(self, emissions, targets, blank=0, n_frames=None, form="auto", return_path=True):
+        """CTC forced alignment of a batch of clips (``pce_ctc_align``: the Viterbi pass of ``torchaudio.functional.forced_align`` over the
+        ``2 L + 1`` blank-interleaved states of each transcript, bit-identical to its CPU restatement).  ``emissions``: a list of
+        ``[T_c, V]`` float32 arrays of log-probabilities (packed and uploaded by the call), a ``DeviceEmissions`` of this engine's
+        ``w2v_emissions`` (read in place), or ONE float32 contiguous torch tensor
+        ``[B, T_max, V]`` with ``n_frames`` (valid frames per clip; default ``T_max`` for all): a ROCm tensor is read in place through its
+        pointer, a CPU tensor is handed over as host memory (a process that uses ROCm tensors imports torch BEFORE it creates its first engine:
+        torch ships its own copy of the HIP runtime, and the copy loaded first serves both).  ``targets``: one sequence of vocabulary indices per clip (none may be ``blank``).
+        ``form``: ``"auto"`` | ``"register"`` | ``"general"`` (the register form holds ``CTC_REG_STATES`` states; asking it for more raises).
+        -> one dict per clip: ``path`` int32 [T] (the label of every frame) and ``frame_score`` float32 [T] (``emissions[t, path[t]]``) unless
+        ``return_path`` is false, ``tok_first`` / ``tok_last`` int32 [L] (first and last frame, inclusive, of every target), ``score``
+        (numpy float32: the final alpha) and ``status`` (``CTC_OK``; ``CTC_EMPTY``: no targets or no frames; ``CTC_TOO_SHORT``: fewer frames
+        than targets + adjacent repeats; ``CTC_NO_PATH``: the best score is -inf or NaN).  A clip without a path has ``path`` -1,
+        ``frame_score`` NaN and token frames -1."""
+        if form not in CTC_FORMS:
+            raise ValueError(f"form: one of {sorted(CTC_FORMS)}")
+        tg = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in targets]
+        n, V, nfr, row_start, ptr, on_device, keep = self._emission_args(emissions, n_frames)
         if len(tg) != n:
             raise ValueError("targets: one sequence per clip")
         if not n:
@@ -1128,6 +1143,47 @@ class ProsodyEngine:
                  "score": score[k], "status": int(status[k])}
             if return_path:
                 d["path"] = path[foff[k]:foff[k + 1]].copy(); d["frame_score"] = fsc[foff[k]:foff[k + 1]].copy()
+            out.append(d)
+        return out
+
+    def wx_align(self, emissions, tokens, blank=0, beam_width=2, n_frames=None, return_path=True, return_trellis=False):
+        """whisperX's forced alignment of a batch of transcript segments (``pce_wx_align``: its trellis over the ``J`` characters of a segment with
+        no interleaved blanks, the wildcard emission, the ``inf`` wedge and the beam-search back-track; the specification stands above
+        ``pce_wx_align`` in ``include/pce.h``).  ``emissions``: as ``ctc_align`` takes them (a list of ``[T_c, V]`` float32 arrays, a
+        ``DeviceEmissions`` read in place, or one contiguous float32 torch tensor ``[B, T_max, V]`` with ``n_frames``).  ``tokens``: one
+        sequence of vocabulary indices per clip, ``-1`` for a wildcard (a character the dictionary lacks); at most ``WX_MAX_TOKENS``.
+        ``beam_width``: 1 .. ``WX_MAX_BEAM`` (whisperx's default is 2; the width changes paths).
+        -> one dict per clip: ``path_tok`` int32 [T] (the token INDEX of every frame) and ``path_lp`` float32 [T] (the log-probability the
+        step consumed) unless ``return_path`` is false, ``score`` (numpy float32: the final trellis cell), ``status`` (``WX_OK``;
+        ``WX_EMPTY``: no tokens or no frames; ``WX_NO_PATH``: the beams died out, e.g. more tokens than frames) and, if ``return_trellis``,
+        ``trellis`` float32 [T, J].  A clip without a path has ``path_tok`` -1 and ``path_lp`` NaN."""
+        tk = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in tokens]
+        n, V, nfr, row_start, ptr, on_device, keep = self._emission_args(emissions, n_frames)
+        if len(tk) != n:
+            raise ValueError("tokens: one sequence per clip")
+        if not n:
+            return []
+        toff = np.zeros(n + 1, dtype=np.int64); np.cumsum([len(t) for t in tk], out=toff[1:])
+        tok = np.concatenate(tk + [np.zeros(1, dtype=np.int32)])
+        foff = np.zeros(n + 1, dtype=np.int64); np.cumsum(nfr, out=foff[1:])
+        coff = np.zeros(n + 1, dtype=np.int64); np.cumsum(nfr.astype(np.int64) * np.diff(toff), out=coff[1:])
+        path = np.zeros(int(foff[-1]) + 1, dtype=np.int32) if return_path else None
+        plp = np.zeros(int(foff[-1]) + 1, dtype=np.float32) if return_path else None
+        tre = np.zeros(int(coff[-1]) + 1, dtype=np.float32) if return_trellis else None
+        score = np.zeros(n, dtype=np.float32); status = np.zeros(n, dtype=np.int32)
+        prm = WxParams(int(blank), int(beam_width))
+        self._check(self._lib.pce_wx_align(self._ctx, C.c_void_p(ptr), on_device, row_start.ctypes.data, nfr.ctypes.data, V, tok.ctypes.data,
+                                           toff.ctypes.data, n, C.byref(prm), path.ctypes.data if return_path else None,
+                                           plp.ctypes.data if return_path else None, tre.ctypes.data if return_trellis else None,
+                                           score.ctypes.data, status.ctypes.data))
+        del keep
+        out = []
+        for k in range(n):
+            d = {"score": score[k], "status": int(status[k])}
+            if return_path:
+                d["path_tok"] = path[foff[k]:foff[k + 1]].copy(); d["path_lp"] = plp[foff[k]:foff[k + 1]].copy()
+            if return_trellis:
+                d["trellis"] = tre[coff[k]:coff[k + 1]].reshape(int(nfr[k]), int(toff[k + 1] - toff[k])).copy()
             out.append(d)
         return out
 
