@@ -12,6 +12,7 @@
 // previous diagonals live in LDS (double buffered), the 1-byte trace goes to global memory and is walked
 // back by one lane.  N <= 1024 rows (Whisper: <= 448 tokens), any number of columns.
 #include "pce_internal.h"
+#include "pce_wave.h"
 #include <vector>
 
 namespace {
@@ -192,8 +193,8 @@ __global__ __launch_bounds__(256) void k_levenshtein(const unsigned *__restrict_
             }
             const unsigned b_in = (unsigned)__builtin_amdgcn_readlane((int)chB, k);            // B[t]
             const int top_in = __builtin_amdgcn_readlane(chT, k);                               // score[r0][t + 1]
-            const int upn_s = __builtin_amdgcn_update_dpp(0, cur, 0x138, 0xF, 0xF, true);                   // wave_shr:1 = the lane above's value
-            const unsigned bch_s = (unsigned)__builtin_amdgcn_update_dpp(0, (int)bch, 0x138, 0xF, 0xF, true);
+            const int upn_s = dpp<0x138>(cur);                                                  // wave_shr:1 = the lane above's value
+            const unsigned bch_s = (unsigned)dpp<0x138>((int)bch);
             const int upn = lane == 0 ? top_in : upn_s;
             bch = lane == 0 ? b_in : bch_s;
             const int c = t - lane + 1;                    // this lane's column at this step

@@ -1,5 +1,6 @@
 // pce_ctx.hip -- context, batch residency, profiling brackets of libpce.so.
 #include "pce_internal.h"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <cstdarg>
@@ -21,6 +22,37 @@ int pce_stage_copy(pce_ctx *c, void *dst, const void *src, size_t bytes, hipMemc
 {
     const hipError_t e = bytes ? hipMemcpyAsync(dst, src, bytes, kind, c->stream) : hipSuccess;
     return e == hipSuccess ? PCE_OK : pce_stage_fail(c, kind == hipMemcpyHostToDevice ? "hipMemcpyAsync to the device" : "hipMemcpyAsync to the host", e, file, line);
+}
+
+// ---- what pce_ctc_align and pce_wx_align do alike before their launches (declared in pce_internal.h)
+int pce_sweep_check(pce_ctx *c, const char *fn, const int64_t *row_start, const int32_t *n_frames, const int64_t *seq_off, const void *p, const float *score,
+                    const int32_t *status, int32_t n_clips, int32_t n_vocab, int32_t blank)
+{
+    if (!row_start || !n_frames || !seq_off || !p || !score || !status || n_clips <= 0 || n_vocab <= 0)
+        return pce_fail(c, PCE_E_INVALID, "%s: NULL argument, no clips or no vocabulary", fn);
+    if (blank < 0 || blank >= n_vocab) return pce_fail(c, PCE_E_INVALID, "%s: blank %d outside the vocabulary of %d", fn, blank, n_vocab);
+    return PCE_OK;
+}
+int pce_sweep_scan_clip(pce_ctx *c, const char *fn, const char *seq, size_t q, const int64_t *row_start, const int32_t *n_frames, const int64_t *seq_off, SweepScan &s,
+                        SweepClip &cl)
+{
+    if (q == 0 && seq_off[0] != 0) return pce_fail(c, PCE_E_INVALID, "%s: %s offsets must start at 0", fn, seq);
+    const int64_t N = seq_off[q + 1] - seq_off[q], T = n_frames[q];
+    if (N < 0 || T < 0 || row_start[q] < 0) return pce_fail(c, PCE_E_INVALID, "%s: clip %zu has a negative length or row (%s offsets must not decrease)", fn, q, seq);
+    cl = SweepClip{row_start[q], seq_off[q], 0, s.total_frames, 0, (int)T, (int)N, 0, 0};
+    s.total_frames += T;
+    if (T) { s.row_lo = std::min<int64_t>(s.row_lo, row_start[q]); s.row_hi = std::max<int64_t>(s.row_hi, row_start[q] + T); }
+    return PCE_OK;
+}
+int pce_sweep_stage_emissions(pce_ctx *c, DevBuf &buf, const float *emissions, int32_t on_device, int32_t n_vocab, const SweepScan &s, std::vector<SweepClip> &tab,
+                              const float **d_lp)
+{
+    *d_lp = emissions;
+    if (on_device || !s.total_frames) return PCE_OK;
+    PCE_UPLOAD(c, buf, emissions + s.row_lo * (int64_t)n_vocab, (size_t)(s.row_hi - s.row_lo) * (size_t)n_vocab);
+    *d_lp = buf.as<float>();
+    for (SweepClip &cl : tab) cl.row0 -= s.row_lo;
+    return PCE_OK;
 }
 
 KernelTimer::KernelTimer(pce_ctx *ctx, int kid, hipStream_t on, double work_flops) : c(ctx), id(kid), s(on ? on : ctx->stream), flops(work_flops)

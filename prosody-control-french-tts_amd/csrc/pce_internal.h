@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "pce.h"
+#include "pce_sweep_plan.h"
 
 // A kernel marked PCE_NO_PK_F32 is compiled without packed fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32).  Why (round 6,
 // profiles/r06/multiprocess_glitch.txt, tools/lab/pk_victim.hip): on the MI355X boxes of this pool a packed fp32 instruction whose low result lane
@@ -262,6 +263,18 @@ template <class T> static inline int pce_fetch_at(pce_ctx *c, const char *file, 
 #define PCE_PUT(c, ...) PCE_TRY(pce_put_at((c), __FILE__, __LINE__, __VA_ARGS__))
 #define PCE_ZERO(T, c, ...) PCE_TRY(pce_zero_at<T>((c), __FILE__, __LINE__, __VA_ARGS__))
 #define PCE_FETCH(c, ...) PCE_TRY(pce_fetch_at((c), __FILE__, __LINE__, __VA_ARGS__))
+
+// What pce_ctc_align and pce_wx_align do alike before their launches (pce_ctx.hip).  `fn` is the entry point's name and `seq` what it calls its label
+// sequences ("target" / "token"), for the messages.
+struct SweepScan { int64_t row_lo = INT64_MAX, row_hi = 0, total_frames = 0; };     // emission rows [row_lo, row_hi) are read; frames of all clips
+int pce_sweep_check(pce_ctx *c, const char *fn, const int64_t *row_start, const int32_t *n_frames, const int64_t *seq_off, const void *p, const float *score,
+                    const int32_t *status, int32_t n_clips, int32_t n_vocab, int32_t blank);
+// clip q into cl: rows, offsets, frames and length (stride, st0, scr0, wild: the caller's), and into the batch's totals
+int pce_sweep_scan_clip(pce_ctx *c, const char *fn, const char *seq, size_t q, const int64_t *row_start, const int32_t *n_frames, const int64_t *seq_off, SweepScan &s,
+                        SweepClip &cl);
+// host emissions: rows [row_lo, row_hi) go to buf and the table's rows shift; -> the device pointer the kernels read
+int pce_sweep_stage_emissions(pce_ctx *c, DevBuf &buf, const float *emissions, int32_t on_device, int32_t n_vocab, const SweepScan &s, std::vector<SweepClip> &tab,
+                              const float **d_lp);
 
 // Kernel-launch bracket for the profiler: records events around the launch when enabled.
 struct KernelTimer {

@@ -16,14 +16,10 @@
 //
 // k_wx_rowmax          wmax[frame] = max over v != blank of e[frame][v], for the frames of the clips that hold a wildcard.  16 lanes per frame,
 //     one DPP row tree; a max is order-free, so the value is exact.  It keeps the V-wide reduction off the serial chain of the sweep.
-// k_wx_trellis<false / true>   the register sweep of k_ctc (pce_ctc.hip): a thread owns WX_RUN consecutive tokens in registers, the left
-//     neighbour's top value arrives by ONE DPP wave shift per frame.  <false>: a clip of up to 256 tokens on one wave, no LDS and no barrier,
-//     four clips per workgroup.  <true>: one workgroup per clip; the top value of a wave crosses to lane 0 of the next through an LDS slot,
-//     double buffered by frame parity: ONE barrier per frame.  Frame t + 1's emissions (the tok gather, e[t + 1][blank], wmax[t + 1]) are
-//     loaded while frame t is computed.  Column 0 (the fp64 prefix of the blank column and the wedge) is produced by the thread that owns
-//     token 0, from the same prefetched e[t + 1][blank].  Each frame's row leaves as one 16-byte store per thread: the device table has rows
-//     of JP = J rounded up to 4 floats.  Up to PCE_WX_MAX_TOKENS tokens; there is no general form (whisperX aligns segments of at most 30 s:
-//     J <= T <= 1 500 at wav2vec2's stride).
+// k_wx_trellis<false / true>   the register sweep of pce_sweep.h over tokens; a frame's emissions are the tok gather, e[t + 1][blank] and
+//     wmax[t + 1].  Column 0 (the fp64 prefix of the blank column and the wedge) is produced by the thread that owns token 0, from the same
+//     prefetched e[t + 1][blank].  Each frame's row leaves as one 16-byte store per thread: the device table has rows of JP = J rounded up
+//     to 4 floats.  Up to PCE_WX_MAX_TOKENS tokens; there is no general form (whisperX aligns segments of at most 30 s: J <= T <= 1 500).
 // k_wx_backtrack       one wave per clip.  A beam is its token index (its score is the trellis cell it stands on, all beams share t); beam slot
 //     s lives in lane s, candidate i = 2 * slot + (0 stay | 1 change) in lane i < 16.  Every candidate counts the candidates that precede it in
 //     the stable descending order (16 lane reads): that count is its place, and it sends its state to the lane of its place (one ds_permute);
@@ -37,41 +33,32 @@
 //     slots by lane reads (no dependent load per frame), then all lanes write path_tok and path_lp (copies of the emission the move consumed:
 //     no exp on the device).
 //
-// k_wx_trellis is marked PCE_NO_PK_F32 as k_ctc is (its adds could pair).  The other two hold no fp32 arithmetic a packed instruction could
-// form (a max, compares), and the attribute would keep the runtime's un-attributed helpers (__ballot, make_int4) from being inlined into them.
+// k_wx_trellis is marked PCE_NO_PK_F32 as k_ctc is (its adds could pair; pce_sweep.h keeps it free of calls).  The other two hold no fp32 arithmetic
+// a packed instruction could form (a max, compares), and the attribute would keep the runtime's helpers (__ballot, make_int4) out of line in them.
 //
 // Clips run in groups of consecutive clips whose tables fit PCE_CTC_TRACE_MB MiB together (read at pce_create); a clip's outputs depend on
 // its own emissions and tokens only.
 #include "pce_internal.h"
-#include "pce_wave.h"
-#include <algorithm>
+#include "pce_sweep.h"
 #include <cmath>
-#include <vector>
 
 namespace {
 
-constexpr int WX_RUN = 4;                                   // tokens per thread: one 16-byte store per frame
-constexpr int WX_MAX_THREADS = 1024;
-static_assert(PCE_WX_MAX_TOKENS == WX_RUN * WX_MAX_THREADS, "include/pce.h states the sweep's limit");
+constexpr int WX_RUN = SWEEP_RUN;                           // tokens per thread: one 16-byte store per frame
+static_assert(PCE_WX_MAX_TOKENS == WX_RUN * SWEEP_MAX_THREADS, "include/pce.h states the sweep's limit");
 constexpr int WX_SLOTS = PCE_WX_MAX_BEAM;                   // beam slots, and words of back-track record per frame
 static_assert(WX_SLOTS == 8, "a record packs the parent slot in 3 bits; 2 * WX_SLOTS candidates fit one DPP row");
 constexpr int WX_CHUNK = 7;                                 // back-track steps per prefetched chunk: offsets 0 .. WX_CHUNK x WX_SLOTS origins = one wave
 
-struct WxClip {
-    long long row0;      // first emission row
-    long long tok0;      // first token
-    long long tr0;       // first float of its table inside the group's buffer (a multiple of 4)
-    long long out0;      // first entry of path_tok / path_lp / wmax, and (x WX_SLOTS) of the back-track record
-    int T, J, JP, wild;  // JP: floats per table row (J rounded up to WX_RUN); wild: the clip holds a wildcard (wmax is valid for its frames)
-};
+// SweepClip here: n = J tokens; stride = JP, the floats per table row (J rounded up to WX_RUN: st0 is a multiple of 4); out0 also counts wmax
 
 // torch.maximum on the CPU: NaN if either is NaN, else std::max(a, b)
 __device__ __forceinline__ float wx_max(float a, float b) { return (a < b || b != b) ? b : a; }
 
-__global__ __launch_bounds__(256) void k_wx_rowmax(const float *__restrict__ lp, int V, int blank, const WxClip *__restrict__ clips, const int *__restrict__ ids,
+__global__ __launch_bounds__(256) void k_wx_rowmax(const float *__restrict__ lp, int V, int blank, const SweepClip *__restrict__ clips, const int *__restrict__ ids,
                                                    float *__restrict__ wmax)
 {
-    const WxClip cl = clips[ids[blockIdx.y]];
+    const SweepClip cl = clips[ids[blockIdx.y]];
     const int f = (int)blockIdx.x * 16 + (int)(threadIdx.x >> 4), l = threadIdx.x & 15;
     if (f >= cl.T) return;                                   // (a whole DPP row leaves: f is one value per 16 lanes)
     const float *row = lp + (cl.row0 + f) * (long long)V;
@@ -82,18 +69,17 @@ __global__ __launch_bounds__(256) void k_wx_rowmax(const float *__restrict__ lp,
 }
 
 template <bool MULTI>
-__global__ __launch_bounds__(MULTI ? WX_MAX_THREADS : 256) PCE_NO_PK_F32 void k_wx_trellis(const float *__restrict__ lp, int V, int blank, const int *__restrict__ tokens,
-                                                                                           const float *__restrict__ wmax, const WxClip *__restrict__ clips,
+__global__ __launch_bounds__(MULTI ? SWEEP_MAX_THREADS : 256) PCE_NO_PK_F32 void k_wx_trellis(const float *__restrict__ lp, int V, int blank, const int *__restrict__ tokens,
+                                                                                           const float *__restrict__ wmax, const SweepClip *__restrict__ clips,
                                                                                            const int *__restrict__ ids, int n_ids, float *__restrict__ table)
 {
-    __shared__ float xch[2][WX_MAX_THREADS / WAVE_SIZE];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int slot = MULTI ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;
-    if (slot >= n_ids) return;                               // (<false> only: a whole wave leaves, and that form has no barrier)
-    const WxClip cl = clips[ids[slot]];
-    const int T = cl.T, J = cl.J, JP = cl.JP;
-    const int tid = MULTI ? (int)threadIdx.x : lane;
-    const int *tk = tokens + cl.tok0;
+    __shared__ SweepXch xch;
+    const SweepWho who = sweep_who<MULTI>();
+    const int lane = who.lane, wave = who.wave, tid = who.tid;
+    if (who.slot >= n_ids) return;                           // (<false> only: a whole wave leaves, and that form has no barrier)
+    const SweepClip cl = clips[ids[who.slot]];
+    const int T = cl.T, J = cl.n, JP = cl.stride;
+    const int *tk = tokens + cl.seq0;
     const float NINF = -INFINITY, PINF = INFINITY;
     const int wedge = J >= 2 ? max(0, T - J + 1) : 0;        // column 0 is +inf from this frame on
     const bool stores = tid * WX_RUN < JP, col0 = tid == 0;
@@ -110,7 +96,7 @@ __global__ __launch_bounds__(MULTI ? WX_MAX_THREADS : 256) PCE_NO_PK_F32 void k_
     }
     const float *row = lp + cl.row0 * (long long)V;
     const float *wm = wmax + cl.out0;
-    float *out = table + cl.tr0 + (long long)tid * WX_RUN;
+    float *out = table + cl.st0 + (long long)tid * WX_RUN;
     float a[WX_RUN], w[WX_RUN], wn[WX_RUN];
 #pragma unroll
     for (int k = 0; k < WX_RUN; k++) a[k] = NINF;
@@ -121,11 +107,8 @@ __global__ __launch_bounds__(MULTI ? WX_MAX_THREADS : 256) PCE_NO_PK_F32 void k_
 #pragma unroll
         for (int k = 0; k < WX_RUN; k++) { const float g = row[lab[k]]; w[k] = star[k] ? m : g; wn[k] = 0.0f; }
     }
-    if (stores) *reinterpret_cast<float4 *>(out) = make_float4(a[0], a[1], a[2], a[3]);
-    if (MULTI) {
-        if (lane == 63) xch[0][wave] = a[WX_RUN - 1];
-        __syncthreads();
-    }
+    if (stores) sweep_store4(out, a);
+    sweep_publish<MULTI>(a[WX_RUN - 1], xch, 0, lane, wave);
     double c = 0.0;                                          // the blank column's prefix, frames 1 .. t
     for (int t = 0; t + 1 < T; t++) {
         row += V;
@@ -135,8 +118,7 @@ __global__ __launch_bounds__(MULTI ? WX_MAX_THREADS : 256) PCE_NO_PK_F32 void k_
 #pragma unroll
             for (int k = 0; k < WX_RUN; k++) { const float g = row[lab[k]]; wn[k] = star[k] ? m : g; }
         }
-        float p1 = dpp<0x138>(a[WX_RUN - 1]);                // wave_shr:1 -- tr[t][j0 - 1]: the last token of the thread before
-        if (lane == 0) p1 = (MULTI && wave > 0) ? xch[t & 1][wave - 1] : NINF;
+        const float p1 = sweep_left<MULTI>(a[WX_RUN - 1], xch, t & 1, lane, wave);             // tr[t][j0 - 1]: the last token of the thread before
         float na[WX_RUN];
 #pragma unroll
         for (int k = 0; k < WX_RUN; k++) {
@@ -148,11 +130,8 @@ __global__ __launch_bounds__(MULTI ? WX_MAX_THREADS : 256) PCE_NO_PK_F32 void k_
 #pragma unroll
         for (int k = 0; k < WX_RUN; k++) { a[k] = na[k]; w[k] = wn[k]; }
         eb = ebn;
-        if (MULTI) {
-            if (lane == 63) xch[(t + 1) & 1][wave] = a[WX_RUN - 1];
-            __syncthreads();
-        }
-        if (stores) *reinterpret_cast<float4 *>(out + (long long)(t + 1) * JP) = make_float4(a[0], a[1], a[2], a[3]);
+        sweep_publish<MULTI>(a[WX_RUN - 1], xch, (t + 1) & 1, lane, wave);
+        if (stores) sweep_store4(out + (long long)(t + 1) * JP, a);
     }
 }
 
@@ -165,16 +144,16 @@ __device__ __forceinline__ unsigned wx_key(float v)
 }
 
 __global__ __launch_bounds__(WAVE_SIZE) void k_wx_backtrack(const float *__restrict__ lp, int V, int blank, int W, const int *__restrict__ tokens,
-                                                            const float *__restrict__ wmax, const WxClip *__restrict__ clips, const int *__restrict__ ids,
+                                                            const float *__restrict__ wmax, const SweepClip *__restrict__ clips, const int *__restrict__ ids,
                                                             const float *__restrict__ table, int *__restrict__ rec, int *__restrict__ path_tok,
                                                             float *__restrict__ path_lp, float *__restrict__ score, int *__restrict__ status)
 {
     const int q = ids[blockIdx.x];
-    const WxClip cl = clips[q];
-    const int T = cl.T, J = cl.J, JP = cl.JP, lane = threadIdx.x;
-    const float *tr = table + cl.tr0;
+    const SweepClip cl = clips[q];
+    const int T = cl.T, J = cl.n, JP = cl.stride, lane = threadIdx.x;
+    const float *tr = table + cl.st0;
     const float *e = lp + cl.row0 * (long long)V;
-    const int *tk = tokens + cl.tok0;
+    const int *tk = tokens + cl.seq0;
     int *rc = rec + cl.out0 * WX_SLOTS;
     if (lane == 0) score[q] = tr[(long long)(T - 1) * JP + (J - 1)];
 
@@ -278,95 +257,54 @@ int pce_wx_align(pce_ctx *c, const float *emissions, int32_t emissions_on_device
                  float *score, int32_t *status)
 {
     if (!c) return PCE_E_INVALID;
-    if (!row_start || !n_frames || !token_off || !p || !score || !status || n_clips <= 0 || n_vocab <= 0)
-        return pce_fail(c, PCE_E_INVALID, "pce_wx_align: NULL argument, no clips or no vocabulary");
-    if (p->blank < 0 || p->blank >= n_vocab) return pce_fail(c, PCE_E_INVALID, "pce_wx_align: blank %d outside the vocabulary of %d", p->blank, n_vocab);
+    const char *fn = "pce_wx_align";
+    PCE_TRY(pce_sweep_check(c, fn, row_start, n_frames, token_off, p, score, status, n_clips, n_vocab, p ? p->blank : 0));
     if (p->beam_width < 1 || p->beam_width > PCE_WX_MAX_BEAM)
         return pce_fail(c, PCE_E_INVALID, "pce_wx_align: beam width %d outside 1 .. %d", p->beam_width, PCE_WX_MAX_BEAM);
-    if (token_off[0] != 0) return pce_fail(c, PCE_E_INVALID, "pce_wx_align: token offsets must start at 0");
     const size_t n = (size_t)n_clips;
-    int64_t row_lo = INT64_MAX, row_hi = 0, total_frames = 0;
-    std::vector<WxClip> tab(n);
-    std::vector<int> kind(n, -1);                            // -1: not run; 0: one wave; 1..4: 128 / 256 / 512 / 1024 threads
+    SweepScan scan;
+    std::vector<SweepClip> tab(n);
+    std::vector<int> kind(n, -1);                            // -1: not run; 0 .. 4: sweep_kind
+    std::vector<int64_t> floats(n, -1);                      // table floats of a clip that runs
     std::vector<int64_t> cells_off(n + 1, 0);                // floats of the caller's trellis before clip q
     for (size_t q = 0; q < n; q++) {
-        const int64_t J = token_off[q + 1] - token_off[q], T = n_frames[q];
-        if (J < 0 || T < 0 || row_start[q] < 0) return pce_fail(c, PCE_E_INVALID, "pce_wx_align: clip %zu has a negative length or row (token offsets must not decrease)", q);
+        SweepClip &cl = tab[q];
+        PCE_TRY(pce_sweep_scan_clip(c, fn, "token", q, row_start, n_frames, token_off, scan, cl));
+        const int64_t J = token_off[q + 1] - token_off[q], T = cl.T;
         if (J > PCE_WX_MAX_TOKENS) return pce_fail(c, PCE_E_LIMIT, "pce_wx_align: clip %zu has %lld tokens, the sweep holds %d", q, (long long)J, PCE_WX_MAX_TOKENS);
         if (J && !tokens) return pce_fail(c, PCE_E_INVALID, "pce_wx_align: tokens is NULL");
-        int wild = 0;
         for (int64_t l = 0; l < J; l++) {
             const int32_t id = tokens[token_off[q] + l];
             if (id < -1 || id >= n_vocab)
                 return pce_fail(c, PCE_E_INVALID, "pce_wx_align: token %lld of clip %zu is %d (vocabulary %d, -1 = wildcard)", (long long)l, q, id, n_vocab);
-            if (id < 0) wild = 1;
+            if (id < 0) cl.wild = 1;
         }
-        WxClip &cl = tab[q];
-        cl.row0 = row_start[q]; cl.tok0 = token_off[q]; cl.tr0 = 0; cl.out0 = total_frames;
-        cl.T = (int)T; cl.J = (int)J; cl.JP = (int)(div_up(J, WX_RUN) * WX_RUN); cl.wild = wild;
-        total_frames += T;
+        cl.stride = (int)(div_up(J, WX_RUN) * WX_RUN);
         cells_off[q + 1] = cells_off[q] + T * J;
         status[q] = (J == 0 || T == 0) ? PCE_WX_EMPTY : PCE_WX_OK;
-        if (T) { row_lo = std::min<int64_t>(row_lo, row_start[q]); row_hi = std::max<int64_t>(row_hi, row_start[q] + T); }
         if (status[q] != PCE_WX_OK) continue;
-        const int64_t threads = div_up(J, WX_RUN);
-        int k = 0, nt = WAVE_SIZE;
-        while (nt < threads) { nt <<= 1; k++; }
-        kind[q] = k;
+        kind[q] = sweep_kind(div_up(J, WX_RUN));
+        floats[q] = T * cl.stride;
     }
-    if (total_frames && !emissions) return pce_fail(c, PCE_E_INVALID, "pce_wx_align: NULL emissions");
-
-    // groups of consecutive clips whose tables fit the budget
-    const int64_t budget_floats = (int64_t)(c->sw.ctc_trace_budget / 4);
-    std::vector<size_t> group_end;
-    int64_t max_group_floats = 0;
-    {
-        int64_t floats = 0;
-        for (size_t q = 0; q < n; q++) {
-            if (kind[q] < 0) continue;
-            const int64_t w = (int64_t)tab[q].T * tab[q].JP;
-            if (w > budget_floats)
-                return pce_fail(c, PCE_E_LIMIT, "pce_wx_align: clip %zu (%d frames, %d tokens) needs %.1f MiB of trellis, the budget is %.1f MiB (PCE_CTC_TRACE_MB)", q,
-                                tab[q].T, tab[q].J, w * 4.0 / 1048576.0, c->sw.ctc_trace_budget / 1048576.0);
-            if (floats + w > budget_floats) { group_end.push_back(q); floats = 0; }
-            tab[q].tr0 = floats;
-            floats += w;
-            max_group_floats = std::max(max_group_floats, floats);
-        }
-        group_end.push_back(n);
-    }
+    if (scan.total_frames && !emissions) return pce_fail(c, PCE_E_INVALID, "pce_wx_align: NULL emissions");
+    const SweepGroups groups = sweep_groups(floats, (int64_t)(c->sw.ctc_trace_budget / 4));      // consecutive clips whose tables fit the budget
+    if (const size_t q = (size_t)groups.too_large; groups.too_large >= 0)
+        return pce_fail(c, PCE_E_LIMIT, "pce_wx_align: clip %zu (%d frames, %d tokens) needs %.1f MiB of trellis, the budget is %.1f MiB (PCE_CTC_TRACE_MB)", q, tab[q].T,
+                        tab[q].n, floats[q] * 4.0 / 1048576.0, c->sw.ctc_trace_budget / 1048576.0);
+    for (size_t q = 0; q < n; q++) tab[q].st0 = groups.offset[q];
 
     PCE_HIP(c, hipSetDevice(c->device));
     auto &d = c->wx;
-    const size_t n_tok = (size_t)token_off[n], nf = (size_t)total_frames;
-    const float *d_lp = emissions;
-    int64_t row_shift = 0;
-    if (!emissions_on_device && nf) {
-        PCE_UPLOAD(c, d.lp, emissions + row_lo * (int64_t)n_vocab, (size_t)(row_hi - row_lo) * (size_t)n_vocab);
-        d_lp = d.lp.as<float>(); row_shift = row_lo;
-    }
-    for (size_t q = 0; q < n; q++) tab[q].row0 -= row_shift;
+    const size_t n_tok = (size_t)token_off[n], nf = (size_t)scan.total_frames;
+    const float *d_lp;
+    PCE_TRY(pce_sweep_stage_emissions(c, d.lp, emissions, emissions_on_device, n_vocab, scan, tab, &d_lp));
     // id lists: the clips with a wildcard first, then per group, per kind
     std::vector<int> ids; ids.reserve(2 * n);
     int max_wild_T = 0;
     for (size_t q = 0; q < n; q++) if (kind[q] >= 0 && tab[q].wild) { ids.push_back((int)q); max_wild_T = std::max(max_wild_T, tab[q].T); }
     const size_t n_wild = ids.size();
-    struct Launch { int kind; size_t first, count, g0, ge; };
-    std::vector<Launch> launches;                            // kind 5: the back-track of a group
-    {
-        size_t g0 = 0;
-        for (size_t ge : group_end) {
-            const size_t first_of_group = ids.size();
-            for (int k = 0; k <= 4; k++) {
-                const size_t first = ids.size();
-                for (size_t q = g0; q < ge; q++) if (kind[q] == k) ids.push_back((int)q);
-                if (ids.size() > first) launches.push_back({k, first, ids.size() - first, g0, ge});
-            }
-            if (ids.size() > first_of_group) launches.push_back({5, first_of_group, ids.size() - first_of_group, g0, ge});
-            g0 = ge;
-        }
-    }
-    PCE_HIP(c, d.table.reserve(sizeof(float) * (size_t)(max_group_floats + 4)));
+    const std::vector<SweepLaunch> launches = sweep_launches(kind, groups.group_end, 5, 5, ids);      // kind 5: the back-track of a group
+    PCE_HIP(c, d.table.reserve(sizeof(float) * (size_t)(groups.largest + 4)));
     PCE_HIP(c, d.wmax.reserve(sizeof(float) * (nf + 1)));
     PCE_HIP(c, d.rec.reserve(sizeof(int) * (nf + 1) * WX_SLOTS));
     PCE_HIP(c, d.path.reserve(sizeof(int) * (nf + 1))); PCE_HIP(c, d.plp.reserve(sizeof(float) * (nf + 1)));
@@ -380,26 +318,26 @@ int pce_wx_align(pce_ctx *c, const float *emissions, int32_t emissions_on_device
         for (size_t x = 0; x < n_wild; x++) cells += (double)tab[(size_t)ids[x]].T * n_vocab;
         KernelTimer t(c, PCE_K_WX_ROWMAX, nullptr, cells);
         hipLaunchKernelGGL(k_wx_rowmax, dim3((unsigned)div_up(max_wild_T, 16), (unsigned)n_wild), dim3(256), 0, c->stream, d_lp, (int)n_vocab, (int)p->blank,
-                           d.tab.as<WxClip>(), d.ids.as<int>(), d.wmax.as<float>());
+                           d.tab.as<SweepClip>(), d.ids.as<int>(), d.wmax.as<float>());
         PCE_HIP(c, hipGetLastError());
     }
-    for (const Launch &l : launches) {
+    for (const SweepLaunch &l : launches) {
         const int *lids = d.ids.as<int>() + l.first;
         double cells = 0.0;
-        for (size_t x = 0; x < l.count; x++) { const WxClip &cl = tab[(size_t)ids[l.first + x]]; cells += l.kind == 5 ? (double)cl.T : (double)cl.T * cl.J; }
+        for (size_t x = 0; x < l.count; x++) { const SweepClip &cl = tab[(size_t)ids[l.first + x]]; cells += l.kind == 5 ? (double)cl.T : (double)cl.T * cl.n; }
         if (l.kind == 0) {
             KernelTimer t(c, PCE_K_WX_TRELLIS, nullptr, cells);
             hipLaunchKernelGGL(k_wx_trellis<false>, dim3((unsigned)div_up((int64_t)l.count, 4)), dim3(256), 0, c->stream, d_lp, (int)n_vocab, (int)p->blank, d.tok.as<int>(),
-                               d.wmax.as<float>(), d.tab.as<WxClip>(), lids, (int)l.count, d.table.as<float>());
+                               d.wmax.as<float>(), d.tab.as<SweepClip>(), lids, (int)l.count, d.table.as<float>());
         } else if (l.kind <= 4) {
             KernelTimer t(c, PCE_K_WX_TRELLIS, nullptr, cells);
             hipLaunchKernelGGL(k_wx_trellis<true>, dim3((unsigned)l.count), dim3((unsigned)(WAVE_SIZE << l.kind)), 0, c->stream, d_lp, (int)n_vocab, (int)p->blank,
-                               d.tok.as<int>(), d.wmax.as<float>(), d.tab.as<WxClip>(), lids, (int)l.count, d.table.as<float>());
+                               d.tok.as<int>(), d.wmax.as<float>(), d.tab.as<SweepClip>(), lids, (int)l.count, d.table.as<float>());
         } else {
             {
                 KernelTimer t(c, PCE_K_WX_BACKTRACK, nullptr, cells);
                 hipLaunchKernelGGL(k_wx_backtrack, dim3((unsigned)l.count), dim3(WAVE_SIZE), 0, c->stream, d_lp, (int)n_vocab, (int)p->blank, (int)p->beam_width,
-                                   d.tok.as<int>(), d.wmax.as<float>(), d.tab.as<WxClip>(), lids, d.table.as<float>(), d.rec.as<int>(),
+                                   d.tok.as<int>(), d.wmax.as<float>(), d.tab.as<SweepClip>(), lids, d.table.as<float>(), d.rec.as<int>(),
                                    path_tok ? d.path.as<int>() : nullptr, path_lp ? d.plp.as<float>() : nullptr, d.score.as<float>(), d.status.as<int>());
             }
             PCE_HIP(c, hipGetLastError());
@@ -407,9 +345,9 @@ int pce_wx_align(pce_ctx *c, const float *emissions, int32_t emissions_on_device
             if (trellis) {
                 for (size_t q = l.g0; q < l.ge; q++) {
                     if (kind[q] < 0) continue;
-                    const WxClip &cl = tab[q];
-                    PCE_HIP(c, hipMemcpy2DAsync(trellis + cells_off[q], sizeof(float) * (size_t)cl.J, d.table.as<float>() + cl.tr0, sizeof(float) * (size_t)cl.JP,
-                                                sizeof(float) * (size_t)cl.J, (size_t)cl.T, hipMemcpyDeviceToHost, c->stream));
+                    const SweepClip &cl = tab[q];
+                    PCE_HIP(c, hipMemcpy2DAsync(trellis + cells_off[q], sizeof(float) * (size_t)cl.n, d.table.as<float>() + cl.st0, sizeof(float) * (size_t)cl.stride,
+                                                sizeof(float) * (size_t)cl.n, (size_t)cl.T, hipMemcpyDeviceToHost, c->stream));
                 }
             }
         }
@@ -424,7 +362,7 @@ int pce_wx_align(pce_ctx *c, const float *emissions, int32_t emissions_on_device
     // a clip without a path: path_tok -1, path_lp NaN; score NaN unless the sweep ran (PCE_WX_NO_PATH keeps the final trellis cell)
     for (size_t q = 0; q < n; q++) {
         if (status[q] == PCE_WX_OK) continue;
-        const WxClip &cl = tab[q];
+        const SweepClip &cl = tab[q];
         for (int t = 0; t < cl.T; t++) { if (path_tok) path_tok[cl.out0 + t] = -1; if (path_lp) path_lp[cl.out0 + t] = NAN; }
         if (status[q] != PCE_WX_NO_PATH) score[q] = NAN;
     }

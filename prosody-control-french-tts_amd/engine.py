@@ -1102,6 +1102,18 @@ class ProsodyEngine:
                 torch.cuda.current_stream(e.device).synchronize()      # the tensor's producer has finished before this engine's stream reads it
         return n, V, nfr, row_start, ptr, on_device, keep
 
+    def _sequence_args(self, what, seqs, emissions, n_frames):
+        """``_emission_args`` plus the label sequences of ``ctc_align`` / ``wx_align`` (``what`` names them in the error) ->
+        ``(n, V, nfr, row_start, ptr, on_device, keep, labels int32 packed (+ 1 slack), toff int64 [n + 1], foff int64 [n + 1])``: a clip's labels
+        are ``[toff[k], toff[k + 1])`` and its frames ``[foff[k], foff[k + 1])`` of the packed per-label and per-frame results."""
+        sq = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in seqs]
+        n, V, nfr, row_start, ptr, on_device, keep = self._emission_args(emissions, n_frames)
+        if len(sq) != n:
+            raise ValueError(f"{what}: one sequence per clip")
+        toff = np.zeros(n + 1, dtype=np.int64); np.cumsum([len(t) for t in sq], out=toff[1:])
+        foff = np.zeros(n + 1, dtype=np.int64); np.cumsum(nfr, out=foff[1:])
+        return n, V, nfr, row_start, ptr, on_device, keep, np.concatenate(sq + [np.zeros(1, dtype=np.int32)]), toff, foff
+
     def ctc_align(self, emissions, targets, blank=0, n_frames=None, form="auto", return_path=True):
         """CTC forced alignment of a batch of clips (``pce_ctc_align``: the Viterbi pass of ``torchaudio.functional.forced_align`` over the
         ``2 L + 1`` blank-interleaved states of each transcript, bit-identical to its CPU restatement).  ``emissions``: a list of
@@ -1118,15 +1130,9 @@ class ProsodyEngine:
         ``frame_score`` NaN and token frames -1."""
         if form not in CTC_FORMS:
             raise ValueError(f"form: one of {sorted(CTC_FORMS)}")
-        tg = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in targets]
-        n, V, nfr, row_start, ptr, on_device, keep = self._emission_args(emissions, n_frames)
-        if len(tg) != n:
-            raise ValueError("targets: one sequence per clip")
+        n, V, nfr, row_start, ptr, on_device, keep, tgt, toff, foff = self._sequence_args("targets", targets, emissions, n_frames)
         if not n:
             return []
-        toff = np.zeros(n + 1, dtype=np.int64); np.cumsum([len(t) for t in tg], out=toff[1:])
-        tgt = np.concatenate(tg + [np.zeros(1, dtype=np.int32)])
-        foff = np.zeros(n + 1, dtype=np.int64); np.cumsum(nfr, out=foff[1:])
         path = np.zeros(int(foff[-1]) + 1, dtype=np.int32) if return_path else None
         fsc = np.zeros(int(foff[-1]) + 1, dtype=np.float32) if return_path else None
         first = np.zeros(int(toff[-1]) + 1, dtype=np.int32); last = np.zeros_like(first)
@@ -1157,15 +1163,9 @@ class ProsodyEngine:
         step consumed) unless ``return_path`` is false, ``score`` (numpy float32: the final trellis cell), ``status`` (``WX_OK``;
         ``WX_EMPTY``: no tokens or no frames; ``WX_NO_PATH``: the beams died out, e.g. more tokens than frames) and, if ``return_trellis``,
         ``trellis`` float32 [T, J].  A clip without a path has ``path_tok`` -1 and ``path_lp`` NaN."""
-        tk = [np.ascontiguousarray(t, dtype=np.int32).reshape(-1) for t in tokens]
-        n, V, nfr, row_start, ptr, on_device, keep = self._emission_args(emissions, n_frames)
-        if len(tk) != n:
-            raise ValueError("tokens: one sequence per clip")
+        n, V, nfr, row_start, ptr, on_device, keep, tok, toff, foff = self._sequence_args("tokens", tokens, emissions, n_frames)
         if not n:
             return []
-        toff = np.zeros(n + 1, dtype=np.int64); np.cumsum([len(t) for t in tk], out=toff[1:])
-        tok = np.concatenate(tk + [np.zeros(1, dtype=np.int32)])
-        foff = np.zeros(n + 1, dtype=np.int64); np.cumsum(nfr, out=foff[1:])
         coff = np.zeros(n + 1, dtype=np.int64); np.cumsum(nfr.astype(np.int64) * np.diff(toff), out=coff[1:])
         path = np.zeros(int(foff[-1]) + 1, dtype=np.int32) if return_path else None
         plp = np.zeros(int(foff[-1]) + 1, dtype=np.float32) if return_path else None
