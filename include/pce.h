@@ -74,9 +74,12 @@ extern "C" {
  * 19 = pce_selftest_xattn_stages (pce_selftest_xattn with the skip list and the buffers between its three kernels copied out: Q' as hi + lo, the nodes' U
  * and (m, l));
  * 20 = pce_wx_align (whisperX's forced alignment of a batch of segments: wildcard trellis and beam back-track) and its three kernel ids, which
- * sit behind minor 16's and in front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by three (pce_kernel_name follows). */
+ * sit behind minor 16's and in front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by three (pce_kernel_name follows);
+ * 21 = pce_w2v_run_segments, pce_w2v_segments_plan, pce_w2v_segment_frames and pce_selftest_w2v_wave_segments / _posconv_segments (the wav2vec2 forward pass over
+ * segments of unequal length, each alone and unpadded: whisperX's emissions, which pce_wx_align reads in place).  No kernel id: its launches
+ * count under minor 16's four. */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 20
+#define PCE_API_MINOR 21
 
 typedef struct pce_ctx pce_ctx;
 
@@ -883,6 +886,27 @@ int pce_w2v_fetch(pce_ctx *ctx, int32_t clip, float *log_probs);
 int pce_w2v_device(pce_ctx *ctx, const float **d_emissions, const int64_t **h_row_start, const int32_t **h_n_frames, int32_t *n_cols);
 /* host arithmetic only (ctx-free): windows and kept frames of a clip of n_samples, as ctc_emissions.window_plan counts them */
 int pce_w2v_window_plan(int64_t n_samples, int32_t window_samples, int32_t context_samples, int64_t *n_windows, int64_t *n_frames);
+/* whisperX's emissions (whisperx 3.3.x alignment.py as Aligners/ctc_emissions.segment_emissions restates it; parity unpinned): segment j owns
+ * samples [begin, end) of resident clip `clip`, int16 / 32768; one of fewer than min_samples samples (begin == end included) is followed by
+ * zeros up to min_samples; the model runs on the segment ALONE (no context, no cut, no attention mask, no padding to a neighbour's length);
+ * log-softmax in fp32 over the n_vocab columns, one column of zeros behind them with `star`.  pce_w2v_shape / _fetch / _device then read the
+ * result indexed by SEGMENT, in the caller's order (row_start follows that order whatever order the chunks ran in).  Arithmetic and kernels
+ * are pce_w2v_run's.  Segments run in chunks of similar length (csrc/pce_w2v_seg_plan.h): longest first, a chunk takes segments down to half
+ * its longest one's padded frames, at most segments_per_chunk (0: as many as keep the chunk's images within PCE_W2V_IMAGE_BUDGET); its
+ * launches cover all its segments, each in a slot of the longest one's rows.  No kernel reduces across segments and none is chosen by the row
+ * count: a segment's emissions are bit-identical whatever it is batched with, in whatever order, and whatever ran before.
+ * PCE_E_INVALID: a batch that is not at 16 kHz, a clip index out of range, 0 <= begin <= end <= clip length violated, a segment the model
+ * gives no frame for (min_samples below its receptive field).  PCE_E_LIMIT: the 32-bit limits of pce_w2v_run, for the longest segment (2^26
+ * samples; the attention's offsets).  PCE_E_STATE: as pce_w2v_run.  Since minor 21. */
+typedef struct pce_w2v_segment { int32_t clip; int32_t reserved; int64_t begin, end; } pce_w2v_segment;   /* samples [begin, end) of a resident clip */
+typedef struct pce_w2v_seg_plan { int32_t min_samples /* 400 */, segments_per_chunk /* 0 = by budget */, star; } pce_w2v_seg_plan;
+int pce_w2v_run_segments(pce_ctx *ctx, const pce_w2v_segment *segments, int32_t n_segments, const pce_w2v_seg_plan *plan);
+/* what the latest pce_w2v_run_segments cost: its chunks, the rows its launches covered (slots x slot rows, summed over the chunks) and the
+ * frames among them that belong to a segment (PCE_E_STATE when the latest run was none) */
+int pce_w2v_segments_plan(pce_ctx *ctx, int64_t *n_chunks, int64_t *rows_computed, int64_t *rows_valid);
+/* host arithmetic only (ctx-free): frames the model of `dims` gives for a segment of n_samples run on max(n_samples, min_samples); 0 when that
+ * is shorter than the feature encoder's receptive field */
+int pce_w2v_segment_frames(const pce_w2v_dims *dims, int64_t n_samples, int32_t min_samples, int64_t *n_frames);
 /* Stage self-tests: the three new stages through the run's own launches, 16-bit values as raw bits of the context's operand type.
  * _wave: the waveform layer over the windows of ONE clip: w [C][10], bias [C] or NULL, gamma / beta [C]; out [n_windows][T0][C],
  * T0 = (window + 2 context - 10) / stride + 1 (nothing is written when the window is shorter than the 10 taps).
@@ -894,6 +918,15 @@ int pce_selftest_w2v_wave(pce_ctx *ctx, const int16_t *pcm, int64_t n_samples, i
 int pce_selftest_w2v_lngelu(pce_ctx *ctx, const uint16_t *x, int32_t rows, int32_t C, const float *w, const float *b, float eps, int32_t gelu, uint16_t *out);
 int pce_selftest_w2v_posconv(pce_ctx *ctx, const float *x, int32_t n_win, int32_t T, int32_t d, int32_t groups, const uint16_t *w, const float *bias,
                              float *out);
+/* ... and the two stages that take per-item frame counts, through pce_w2v_run_segments' launches.  _wave_segments: item i is samples
+ * [seg[2 i], seg[2 i + 1]) of ONE clip, run on max(its samples, min_samples); out [n_seg][slot][C], slot = the longest item's frames, rows behind
+ * an item's own frames zero.  _posconv_segments: window i holds len[i] <= T frames in a slot of T rows of x / out [n_win][T][d]; rows behind
+ * its frames come back as x.  Since minor 21. */
+int pce_selftest_w2v_wave_segments(pce_ctx *ctx, const int16_t *pcm, int64_t n_samples, const int64_t *seg, int32_t n_seg, int32_t min_samples,
+                                   int32_t feat_norm, int32_t C, int32_t stride, const float *w, const float *bias, const float *gamma, const float *beta,
+                                   uint16_t *out);
+int pce_selftest_w2v_posconv_segments(pce_ctx *ctx, const float *x, int32_t n_win, const int32_t *len, int32_t T, int32_t d, int32_t groups,
+                                      const uint16_t *w, const float *bias, float *out);
 
 /* ---- asynchronous statistics fetch ---------------------------------------
  * The per-slice numbers of the last pce_energy_run / pce_lufs_run / pce_pitch_run are what the reference's

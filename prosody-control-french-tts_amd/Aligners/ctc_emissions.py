@@ -1,7 +1,8 @@
 """Frame-wise log-probabilities of a ``transformers`` ``...ForCTC`` model for 16 kHz clips: ``hf_emissions`` runs the caller's model under torch
 (plumbing, no kernel of this project; the default), ``engine_emissions`` runs a ``Wav2Vec2ForCTC``'s forward pass on the engine's own kernels
 (``pce_w2v_run``) with the same windowing and leaves the emissions in device memory.  ``segment_emissions`` is whisperX's way:
-one transcript segment at a time, no windows (torch plumbing too; ``Aligners/whisperX.py``).
+one transcript segment at a time, no windows (torch plumbing too; ``Aligners/whisperX.py``); ``engine_segment_emissions`` runs the same
+segments on the engine's kernels (``pce_w2v_run_segments``), all files' segments in one call.
 
 The windowing is that of ``ctc-forced-aligner``'s ``generate_emissions`` (third party and absent: restated from the published source,
 parity unpinned): a clip is padded to a whole number of windows of ``window_s`` seconds, every window is run with ``context_s`` seconds
@@ -133,3 +134,33 @@ def segment_emissions(model, pcm16k, segments, device, batch_size=1):
     for k, e in enumerate(out):
         packed[k, :n_frames[k]] = e
     return packed.contiguous(), n_frames
+
+
+def segment_samples(segment, n_samples: int):
+    """-> ``(begin, end)``: the samples ``segment_emissions``' slice ``wave[int(start * 16000):int(end * 16000)]`` takes out of a signal of
+    ``n_samples``: an end (or a start) beyond the signal is clamped to it and an end in front of the start gives an empty piece, as Python's
+    slice does.  A negative time would count from the signal's END in that slice; nothing aligns such a segment on purpose: ValueError."""
+    begin, end = int(segment["start"] * SAMPLE_RATE), int(segment["end"] * SAMPLE_RATE)
+    if begin < 0 or end < 0:
+        raise ValueError(f"segment {segment.get('text', '')!r}: negative time ({segment['start']}, {segment['end']})")
+    begin = min(begin, n_samples)
+    return begin, max(begin, min(end, n_samples))
+
+
+def engine_segment_emissions(engine, model, jobs):
+    """``segment_emissions``' segments and numbers on the engine's kernels: ``jobs`` = ``[(pcm16k int16, [{"start", "end"}, ...])]``, one entry
+    per file.  Uploads the files as the resident batch, loads ``model`` (a ``transformers`` ``Wav2Vec2ForCTC``) unless the engine holds it, and
+    runs every segment of every file in ONE ``ProsodyEngine.w2v_segment_emissions`` call (no star column).  -> ``DeviceEmissions``, one entry per
+    segment in the order of ``jobs``, which ``ProsodyEngine.wx_align`` reads in place."""
+    clips, triples = [], []
+    for pcm, segments in jobs:
+        x = np.asarray(pcm).reshape(-1)
+        if x.dtype.kind not in "iu":
+            raise ValueError("engine_segment_emissions: int16 samples (the resident batch is PCM)")
+        for seg in segments:
+            triples.append((len(clips), *segment_samples(seg, len(x))))
+        clips.append(x.astype(np.int16))
+    if not engine.w2v_holds(model):
+        engine.w2v_load(model)
+    engine.upload(clips, SAMPLE_RATE)
+    return engine.w2v_segment_emissions(triples, MIN_SEGMENT_SAMPLES, star=False)

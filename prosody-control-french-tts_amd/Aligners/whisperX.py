@@ -33,8 +33,10 @@ def blank_id(dictionary: dict) -> int:
     return blank
 
 
-def _align_files(jobs, model, metadata, engine, beam_width, emissions):
+def _align_files(jobs, model, metadata, engine, beam_width, emissions, acoustic="torch"):
     """``jobs``: [(segments, pcm16k)] -> one ``{"segments", "word_segments"}`` per job; every alignable segment of every job in one ``wx_align``."""
+    if acoustic not in ("torch", "engine"):
+        raise ValueError(f"acoustic: 'torch' or 'engine', not {acoustic!r}")
     dictionary, language = metadata["dictionary"], metadata["language"]
     if metadata.get("type", "huggingface") != "huggingface":
         raise NotImplementedError("align: a transformers ...ForCTC model (metadata type 'huggingface'); torchaudio pipelines are absent")
@@ -61,6 +63,10 @@ def _align_files(jobs, model, metadata, engine, beam_width, emissions):
         blank = blank_id(dictionary)
         if emissions is not None:
             em = emissions if isinstance(emissions, DeviceEmissions) else [np.ascontiguousarray(e, dtype=np.float32) for job in emissions for e in job]
+            aligned = engine.wx_align(em, tokens, blank=blank, beam_width=beam_width)
+        elif acoustic == "engine":
+            from . import ctc_emissions
+            em = ctc_emissions.engine_segment_emissions(engine, model, [(pcm, [seg for j, seg in todo if j == jdx]) for jdx, (_, pcm) in enumerate(jobs)])
             aligned = engine.wx_align(em, tokens, blank=blank, beam_width=beam_width)
         else:
             import torch
@@ -91,14 +97,16 @@ def _align_files(jobs, model, metadata, engine, beam_width, emissions):
     return results
 
 
-def align(segments, model, metadata, audio, engine, beam_width=2, emissions=None):
+def align(segments, model, metadata, audio, engine, beam_width=2, emissions=None, acoustic="torch"):
     """``whisperx.align(segments, model, metadata, audio, device)``: ``segments`` = ``[{"start", "end", "text"}]``; ``audio``: the 16 kHz mono
     signal (int16 or float array) or the path of a WAV file; ``engine``: a ``ProsodyEngine``; ``emissions``: precomputed ``[T, V]`` float32
     log-probabilities (a list of arrays, or a ``DeviceEmissions`` of this engine), one per ALIGNABLE segment (one with a character left and a start inside the audio) in order, in place of ``model``.
+    ``acoustic``: where ``model`` runs when no emissions are given: ``"torch"`` (``ctc_emissions.segment_emissions``, one forward per segment) or
+    ``"engine"`` (``ctc_emissions.engine_segment_emissions``: a ``Wav2Vec2ForCTC`` on the engine's kernels, int16 audio, all segments in one call).
     A segment with no characters, one that starts at or beyond the audio's end, and one without a path come back unaligned (original times,
     no words), with a warning.  -> ``{"segments": [{"start", "end", "text", "words"}], "word_segments": [{"word", "start", "end", "score"}]}``."""
     pcm = load_audio(audio) if isinstance(audio, (str, os.PathLike)) else np.asarray(audio).reshape(-1)
-    return _align_files([(segments, pcm)], model, metadata, engine, beam_width, _one_job(emissions))[0]
+    return _align_files([(segments, pcm)], model, metadata, engine, beam_width, _one_job(emissions), acoustic)[0]
 
 
 def _one_job(emissions):
@@ -147,12 +155,14 @@ def _transcribe(whisper, engine, clips):
     return [r["segments"] for r in transcribe_batch(engine, model, tokenizer, clips, options)]
 
 
-def process_files(audio_dir, transcription_dir, output_dir, *, engine, align_model, metadata, whisper=None, segments=None, emissions=None, beam_width=2):
+def process_files(audio_dir, transcription_dir, output_dir, *, engine, align_model, metadata, whisper=None, segments=None, emissions=None, beam_width=2,
+                  acoustic="torch"):
     """The reference's ``main`` for a whole directory at once: one ``.TextGrid`` per ``.wav`` of ``sorted(os.listdir(audio_dir))`` whose
     transcription file exists (the reference checks for it and never reads it: the words come from the transcription model).
     ``segments``: {file name: ``[{"start", "end", "text"}]``}, or ``whisper = (model, tokenizer[, TranscribeOptions])`` of the project's Whisper
     path (``transcribe.transcribe_batch``, greedy) to transcribe the files; ``emissions``: {file name: ``[T, V]`` arrays, one per alignable
-    segment} in place of ``align_model``.  The grid's duration is the last aligned segment's ``end``, or 0.0.  -> {file name: word_segments}."""
+    segment} in place of ``align_model``; ``acoustic``: as ``align`` takes it (``"engine"``: every segment of every file in one forward call).
+    The grid's duration is the last aligned segment's ``end``, or 0.0.  -> {file name: word_segments}."""
     if segments is None and whisper is None:
         raise ValueError("process_files: one of whisper / segments is required")
     if align_model is None and emissions is None:
@@ -169,7 +179,7 @@ def process_files(audio_dir, transcription_dir, output_dir, *, engine, align_mod
     clips = [load_audio(os.path.join(audio_dir, name)) for name in names]
     per_file = [segments[name] for name in names] if segments is not None else _transcribe(whisper, engine, clips)
     results = _align_files(list(zip(per_file, clips)), align_model, metadata, engine, beam_width,
-                           None if emissions is None else [emissions[name] for name in names])
+                           None if emissions is None else [emissions[name] for name in names], acoustic)
     out = {}
     for name, result in zip(names, results):
         output_path = os.path.join(output_dir, name.replace(".wav", ".TextGrid"))
@@ -179,7 +189,8 @@ def process_files(audio_dir, transcription_dir, output_dir, *, engine, align_mod
     return out
 
 
-def process_file(audio_path, transcription_path, *, engine, align_model, metadata, whisper=None, segments=None, emissions=None, beam_width=2):
+def process_file(audio_path, transcription_path, *, engine, align_model, metadata, whisper=None, segments=None, emissions=None, beam_width=2,
+                 acoustic="torch"):
     """One recording -> ``(word_segments, duration)``, as the reference's ``process_file`` returns them."""
     if not os.path.exists(audio_path):
         raise FileNotFoundError(f"no audio file: {audio_path}")
@@ -189,7 +200,7 @@ def process_file(audio_path, transcription_path, *, engine, align_model, metadat
         raise ValueError("process_file: one of whisper / segments is required")
     pcm = load_audio(audio_path)
     segs = segments if segments is not None else _transcribe(whisper, engine, [pcm])[0]
-    result = _align_files([(segs, pcm)], align_model, metadata, engine, beam_width, _one_job(emissions))[0]
+    result = _align_files([(segs, pcm)], align_model, metadata, engine, beam_width, _one_job(emissions), acoustic)[0]
     return result["word_segments"], _duration(result)
 
 

@@ -4,6 +4,7 @@
 // pce_whisper_entries.h; the few entry points that do not follow its rule are written out below.
 #include "pce_internal.h"
 #include "pce_whisper_entries.h"
+#include "pce_w2v_seg_plan.h"
 
 namespace pce_bf16 {
 PCE_WHISPER_ENTRIES(PCE_DECLARE)
@@ -44,6 +45,18 @@ int pce_w2v_window_plan(int64_t n_samples, int32_t window_samples, int32_t conte
     const int64_t wf = (int64_t)((double)window / 16000.0 * 50.0);
     *n_windows = n_win;
     *n_frames = n_win * wf - (extension > 0 ? (int64_t)((double)extension / 16000.0 * 50.0) : 0);
+    return PCE_OK;
+}
+
+// frames the model gives for a segment of n_samples run on max(n_samples, min_samples): the feature encoder's arithmetic (pce_w2v_seg_plan.h)
+int pce_w2v_segment_frames(const pce_w2v_dims *dims, int64_t n_samples, int32_t min_samples, int64_t *n_frames)
+{
+    if (!dims || !n_frames || n_samples < 0 || min_samples < 0 || dims->n_conv < 1 || dims->n_conv > 8) return PCE_E_INVALID;
+    for (int i = 0; i < dims->n_conv; i++)
+        if (dims->conv_kernel[i] < 1 || dims->conv_stride[i] < 1) return PCE_E_INVALID;
+    int64_t t[8];
+    w2v_seg_layer_frames(dims->conv_kernel, dims->conv_stride, dims->n_conv, n_samples > min_samples ? n_samples : (int64_t)min_samples, t);
+    *n_frames = t[dims->n_conv - 1];
     return PCE_OK;
 }
 

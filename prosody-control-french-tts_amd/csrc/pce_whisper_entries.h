@@ -4,7 +4,7 @@
 //   * pce_whisper_dispatch.hip declares it inside both namespaces and generates the exported extern "C" function of every line, which forwards
 //     to the build the context has selected.
 // A line that disagrees with include/pce.h does not compile (conflicting extern "C" declaration), one that disagrees with a definition does not link.
-// Not here (hand-written in pce_whisper_dispatch.hip): pce_whisper_set_operands / _get_operands, pce_w2v_window_plan, pce_w2v_check (no context:
+// Not here (hand-written in pce_whisper_dispatch.hip): pce_whisper_set_operands / _get_operands, pce_w2v_window_plan, pce_w2v_segment_frames, pce_w2v_check (no context:
 // always the fp16 build's) and pce_whisper_free.
 #pragma once
 
@@ -104,6 +104,8 @@
     X(pce_bert_fetch, (pce_ctx *c, int32_t seq, float *logits, int32_t *labels), (c, seq, logits, labels)) \
     X(pce_w2v_load, (pce_ctx *c, const pce_w2v_dims *dims, const float *weights, int64_t n_floats), (c, dims, weights, n_floats)) \
     X(pce_w2v_run, (pce_ctx *c, const pce_w2v_plan *plan), (c, plan)) \
+    X(pce_w2v_run_segments, (pce_ctx *c, const pce_w2v_segment *segments, int32_t n_segments, const pce_w2v_seg_plan *plan), (c, segments, n_segments, plan)) \
+    X(pce_w2v_segments_plan, (pce_ctx *c, int64_t *n_chunks, int64_t *rows_computed, int64_t *rows_valid), (c, n_chunks, rows_computed, rows_valid)) \
     X(pce_w2v_shape, (pce_ctx *c, int32_t clip, int64_t *n_frames, int32_t *n_cols), (c, clip, n_frames, n_cols)) \
     X(pce_w2v_fetch, (pce_ctx *c, int32_t clip, float *log_probs), (c, clip, log_probs)) \
     X(pce_w2v_device, (pce_ctx *c, const float **d_emissions, const int64_t **h_row_start, const int32_t **h_n_frames, int32_t *n_cols), \
@@ -117,4 +119,11 @@
       (c, x, rows, C, w, b, eps, gelu, out)) \
     X(pce_selftest_w2v_posconv, \
       (pce_ctx *c, const float *x, int32_t n_win, int32_t T, int32_t d, int32_t groups, const uint16_t *w, const float *bias, float *out), \
-      (c, x, n_win, T, d, groups, w, bias, out))
+      (c, x, n_win, T, d, groups, w, bias, out)) \
+    X(pce_selftest_w2v_wave_segments, \
+      (pce_ctx *c, const int16_t *pcm, int64_t n_samples, const int64_t *seg, int32_t n_seg, int32_t min_samples, int32_t feat_norm, int32_t C, int32_t stride, \
+       const float *w, const float *bias, const float *gamma, const float *beta, uint16_t *out), \
+      (c, pcm, n_samples, seg, n_seg, min_samples, feat_norm, C, stride, w, bias, gamma, beta, out)) \
+    X(pce_selftest_w2v_posconv_segments, \
+      (pce_ctx *c, const float *x, int32_t n_win, const int32_t *len, int32_t T, int32_t d, int32_t groups, const uint16_t *w, const float *bias, float *out), \
+      (c, x, n_win, len, T, d, groups, w, bias, out))

@@ -221,10 +221,11 @@ struct WhisperState {
         std::vector<EncoderLayerW> layers;
         size_t fp_ln_w = 0, fp_ln_b = 0, proj_w = 0, proj_b = 0, pos_w = 0, pos_b = 0, enc_ln_w = 0, enc_ln_b = 0, lm_w = 0, lm_b = 0;
         int Vp = 0;                         // lm_head's columns, padded to whole GEMM tiles
-        DevBuf img[2], part, ss, wintab, tailtab, atab, fpln, h0, h, ln, qk, vt, attn, hidden, logits, em;
+        DevBuf img[2], part, ss, wintab, tailtab, atab, t0tab, fpln, h0, h, ln, qk, vt, attn, hidden, logits, em;
         std::vector<int64_t> row_start;     // first row of clip q in em
         std::vector<int32_t> n_frames;
         int n_cols = 0, n_clips = -1;       // n_clips < 0: no run yet
+        int64_t seg_plan[3] = {-1, 0, 0};   // the latest pce_w2v_run_segments: chunks, rows computed, rows valid (chunks < 0: the latest run was none)
     } w2v;
     // offsets (elements) into w_bf16 / w_f32
     size_t c1_w = 0, c1_b = 0, c2_w = 0, c2_b = 0, lnp_w = 0, lnp_b = 0;

@@ -126,11 +126,20 @@ class W2vPlan(C.Structure):
     _fields_ = [("window_samples", C.c_int32), ("context_samples", C.c_int32), ("windows_per_chunk", C.c_int32), ("star", C.c_int32)]
 
 
+class W2vSegment(C.Structure):
+    _fields_ = [("clip", C.c_int32), ("reserved", C.c_int32), ("begin", C.c_int64), ("end", C.c_int64)]
+
+
+class W2vSegPlan(C.Structure):
+    _fields_ = [("min_samples", C.c_int32), ("segments_per_chunk", C.c_int32), ("star", C.c_int32)]
+
+
 class DeviceEmissions:
-    """The packed emissions of ``ProsodyEngine.w2v_emissions``: device memory ``[sum n_frames][n_cols]`` float32 of the engine that made them
-    (valid until its next ``w2v_emissions`` / ``w2v_load``, which may free or overwrite the memory), clip ``q`` in rows
-    ``row_start[q] .. row_start[q] + n_frames[q]``.  ``ProsodyEngine.ctc_align`` reads it in place.  ``epoch`` is the engine's count of
-    ``w2v_load`` / ``w2v_emissions`` calls when it was made: an object from before the engine's latest call is refused (``check``), not read."""
+    """The packed emissions of ``ProsodyEngine.w2v_emissions`` / ``w2v_segment_emissions``: device memory ``[sum n_frames][n_cols]`` float32 of
+    the engine that made them (valid until its next ``w2v_emissions`` / ``w2v_segment_emissions`` / ``w2v_load``, which may free or overwrite
+    the memory), clip (or segment) ``q`` in rows ``row_start[q] .. row_start[q] + n_frames[q]``.  ``ProsodyEngine.ctc_align`` and ``wx_align``
+    read it in place.  ``epoch`` is the engine's count of those calls when it was made: an object from before the engine's latest call is
+    refused (``check``), not read."""
 
     def __init__(self, engine, pointer: int, row_start: np.ndarray, n_frames: np.ndarray, n_cols: int, epoch: int):
         self.engine, self.pointer, self.row_start, self.n_frames, self.n_cols = engine, int(pointer), row_start, n_frames, int(n_cols)
@@ -141,7 +150,7 @@ class DeviceEmissions:
 
     def check(self):
         if self.epoch != self.engine._w2v_epoch:
-            raise ValueError("these emissions are stale: the engine has run w2v_emissions / w2v_load since they were made")
+            raise ValueError("these emissions are stale: the engine has run w2v_emissions / w2v_segment_emissions / w2v_load since they were made")
 
     def numpy(self):
         """-> one float32 array ``[n_frames][n_cols]`` per clip (fetched to the host)."""
@@ -318,9 +327,14 @@ SIGNATURES = {
     "pce_w2v_fetch": [_vp, _i32, _vp],
     "pce_w2v_device": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32)],
     "pce_w2v_window_plan": [_i64, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64)],
+    "pce_w2v_run_segments": [_vp, C.POINTER(W2vSegment), _i32, C.POINTER(W2vSegPlan)],
+    "pce_w2v_segment_frames": [C.POINTER(W2vDims), _i64, _i32, C.POINTER(_i64)],
+    "pce_w2v_segments_plan": [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "pce_selftest_w2v_wave": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "pce_selftest_w2v_lngelu": [_vp, _vp, _i32, _i32, _vp, _vp, C.c_float, _i32, _vp],
     "pce_selftest_w2v_posconv": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
+    "pce_selftest_w2v_wave_segments": [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "pce_selftest_w2v_posconv_segments": [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     # asynchronous statistics fetch
     "pce_stats_enqueue": [_vp, _i32],
     "pce_stats_wait": [_vp, _i32, _vp, _vp, _vp, _vp],
@@ -362,6 +376,17 @@ def w2v_window_plan(n_samples: int, window_s=30, context_s=2, lib=None):
     if rc:
         raise PceError(f"pce_w2v_window_plan: status {rc}")
     return nw.value, nf.value
+
+
+def w2v_segment_frames(dims: dict, n_samples: int, min_samples: int = 400, lib=None) -> int:
+    """-> frames the model of ``dims`` (``w2v_weights.dims``) gives for a segment of ``n_samples`` run on ``max(n_samples, min_samples)``, as
+    ``pce_w2v_run_segments`` counts them: ``pce_w2v_segment_frames``, host arithmetic that needs no device."""
+    lib = lib or load_library()
+    nf = C.c_int64()
+    rc = lib.pce_w2v_segment_frames(C.byref(W2vDims.of(dims)), int(n_samples), int(min_samples), C.byref(nf))
+    if rc:
+        raise PceError(f"pce_w2v_segment_frames: status {rc}")
+    return nf.value
 
 
 def make_slices(clips, begins, ends, x1=None) -> np.ndarray:
@@ -1401,15 +1426,36 @@ class ProsodyEngine:
         plan = W2vPlan(window, context, int(windows_per_chunk or 0), 1 if star else 0)
         self._w2v_epoch += 1                                        # the run may move or overwrite what earlier DeviceEmissions point to
         self._check(self._lib.pce_w2v_run(self._ctx, C.byref(plan)))
+        return self._w2v_device_emissions(int(self._lib.pce_num_clips(self._ctx)))
+
+    def _w2v_device_emissions(self, n: int) -> DeviceEmissions:
         ptr, rs, nf, nc = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
         self._check(self._lib.pce_w2v_device(self._ctx, C.byref(ptr), C.byref(rs), C.byref(nf), C.byref(nc)))
-        n = int(self._lib.pce_num_clips(self._ctx))
         row_start = np.ctypeslib.as_array(C.cast(rs, C.POINTER(C.c_int64)), shape=(n,)).copy() if n else np.zeros(0, np.int64)
         n_frames = np.ctypeslib.as_array(C.cast(nf, C.POINTER(C.c_int32)), shape=(n,)).copy() if n else np.zeros(0, np.int32)
         return DeviceEmissions(self, ptr.value or 0, row_start, n_frames, nc.value, self._w2v_epoch)
 
+    def w2v_segment_emissions(self, segments, min_samples=400, segments_per_chunk=None, star=False) -> DeviceEmissions:
+        """whisperX's emissions under the loaded model (``pce_w2v_run_segments``): ``segments`` = ``[(clip, begin, end)]``, samples
+        ``[begin, end)`` of a clip of the resident 16 kHz batch; each segment runs ALONE (one of fewer than ``min_samples`` samples is followed
+        by zeros up to that many), as ``Aligners.ctc_emissions.segment_emissions`` runs them.  ``segments_per_chunk``: segments per launch
+        group (default: by ``PCE_W2V_IMAGE_BUDGET``); a segment's emissions do not depend on it, on the order or on its neighbours.
+        -> ``DeviceEmissions`` indexed by segment, in the order given; ``wx_align`` / ``ctc_align`` read it in place."""
+        segs = [(int(q), int(b), int(e)) for q, b, e in segments]
+        arr = (W2vSegment * max(1, len(segs)))(*[W2vSegment(q, 0, b, e) for q, b, e in segs])
+        plan = W2vSegPlan(int(min_samples), int(segments_per_chunk or 0), 1 if star else 0)
+        self._w2v_epoch += 1                                        # the run may move or overwrite what earlier DeviceEmissions point to
+        self._check(self._lib.pce_w2v_run_segments(self._ctx, arr, len(segs), C.byref(plan)))
+        return self._w2v_device_emissions(len(segs))
+
+    def w2v_segments_plan(self):
+        """-> (chunks, rows computed, rows valid) of the latest ``w2v_segment_emissions`` (``pce_w2v_segments_plan``)."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.pce_w2v_segments_plan(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def w2v_fetch(self, clip: int) -> np.ndarray:
-        """-> float32 ``[n_frames][n_cols]``: one clip's emissions of the last ``w2v_emissions``."""
+        """-> float32 ``[n_frames][n_cols]``: one clip's emissions (or segment's) emissions of the last ``w2v_emissions`` / ``w2v_segment_emissions``."""
         nf, nc = C.c_int64(), C.c_int32()
         self._check(self._lib.pce_w2v_shape(self._ctx, int(clip), C.byref(nf), C.byref(nc)))
         out = np.zeros((nf.value, nc.value), dtype=np.float32)
@@ -1453,6 +1499,32 @@ class ProsodyEngine:
             raise ValueError("w: [d][128][d / groups]")
         out = np.zeros_like(x)
         self._check(self._lib.pce_selftest_w2v_posconv(self._ctx, x.ctypes.data, n_win, t, d, int(groups), w.ctypes.data, bias.ctypes.data, out.ctypes.data))
+        return out
+
+    def selftest_w2v_wave_segments(self, pcm, segments, feat_norm: int, w, gamma, beta, bias=None, stride: int = 5, min_samples: int = 400):
+        """``pce_selftest_w2v_wave_segments``: the waveform layer over ``segments`` = ``[(begin, end)]`` of one int16 clip, each with its own
+        frame count.  -> (uint16 bits [segments][slot][C], frames per segment); rows behind a segment's frames are zero."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16).reshape(-1)
+        w = np.ascontiguousarray(w, dtype=np.float32); gamma = np.ascontiguousarray(gamma, dtype=np.float32); beta = np.ascontiguousarray(beta, dtype=np.float32)
+        bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+        seg = np.ascontiguousarray(segments, dtype=np.int64).reshape(-1, 2)
+        frames = [(max(int(e - b), int(min_samples)) - 10) // stride + 1 for b, e in seg]
+        out = np.zeros((len(seg), max(frames), w.shape[0]), dtype=np.uint16)
+        self._check(self._lib.pce_selftest_w2v_wave_segments(self._ctx, pcm.ctypes.data, len(pcm), seg.ctypes.data, len(seg), int(min_samples), int(feat_norm),
+                                                             w.shape[0], int(stride), w.ctypes.data, None if bias is None else bias.ctypes.data,
+                                                             gamma.ctypes.data, beta.ctypes.data, out.ctypes.data))
+        return out, frames
+
+    def selftest_w2v_posconv_segments(self, x, lens, w_bits, bias, groups: int):
+        """``pce_selftest_w2v_posconv_segments``: x float32 [windows][T][d], window i holding ``lens[i] <= T`` frames -> float32 [windows][T][d]."""
+        x = np.ascontiguousarray(x, dtype=np.float32); w = np.ascontiguousarray(w_bits, dtype=np.uint16); bias = np.ascontiguousarray(bias, dtype=np.float32)
+        lens = np.ascontiguousarray(lens, dtype=np.int32).reshape(-1)
+        n_win, t, d = x.shape
+        if w.shape != (d, 128, d // groups) or lens.shape != (n_win,):
+            raise ValueError("w: [d][128][d / groups]; lens: one per window")
+        out = np.zeros_like(x)
+        self._check(self._lib.pce_selftest_w2v_posconv_segments(self._ctx, x.ctypes.data, n_win, lens.ctypes.data, t, d, int(groups), w.ctypes.data,
+                                                                bias.ctypes.data, out.ctypes.data))
         return out
 
     def levenshtein(self, pairs):
