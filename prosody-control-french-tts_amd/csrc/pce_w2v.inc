@@ -13,9 +13,9 @@
 // Which kernel computes a product follows from N and K alone (w2v_gemm), and no kernel reduces across windows: a window's emissions do not
 // depend on the chunk size or on what the window is batched with.
 //
-// pce_w2v_run_segments runs the same model on segments of unequal length, each alone (whisperX's emissions): the same per-chunk forward
-// (w2v_forward_chunk) over slots of the chunk's longest segment's rows, every segment's own frame counts in the kernels' tables (the _seg
-// kernels below and the tables the attention and the tail read anyway); pce_w2v_seg_plan.h forms the chunks.
+// pce_w2v_run_segments runs the same model on segments of unequal length, each alone (whisperX's emissions); pce_w2v_seg_plan.h forms its
+// chunks.  Both entries fill one description of a run (W2vRun) and share what follows (w2v_run_chunks, w2v_forward_chunk): every kernel that
+// looks at an item's frame count reads it from a table, and equal windows are items whose counts are equal.
 #include <cstdarg>
 #include "pce_w2v_seg_plan.h"
 
@@ -46,163 +46,122 @@ __device__ __forceinline__ float w2v_conv10(const float *x, const float (&wk)[WV
     return y + b;
 }
 
-// The bodies of the waveform layer's kernels and of the positional convolution are written once, as macros over the names of the uniform
-// kernels' parameters: the uniform kernels (pce_w2v_run) expand them with one frame count for every item, the _seg kernels
-// (pce_w2v_run_segments) with each item's own count from a table.  Same operations in the same order; a macro and not an inlined function
-// because the uniform kernels then compile to the instructions they had before the _seg kernels existed (tools/code_identity.py).
+// The waveform layer's kernels and the positional convolution take every item's own frame count from a device table: a run over equal
+// windows (pce_w2v_run) is a run over items whose counts are all the same.  A slot is the rows between two items' images: the chunk's longest
+// item's frames.
 
-// Group form, pass 1: sum and sum of squares of every channel over the frames [WV_PART p, WV_PART (p + 1)) of window blockIdx.y, in fp64.
-// Names: pcm, win, w, bias, C, stride, T0 (the window's frames), n_part (partials per row of part), part.
-#define W2V_WAVE_STATS_BODY                                                                                          \
-    __shared__ float xs[(WV_PART - 1) * WV_STRIDE_MAX + 16];                                                         \
-    const int wdx = (int)blockIdx.y, p = (int)blockIdx.x;                                                            \
-    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];                                  \
-    const int f0 = p * WV_PART, nf = min(WV_PART, T0 - f0), ns = (nf - 1) * stride + WV_K0;                          \
-    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i); \
-    __syncthreads();                                                                                                 \
-    for (int ch = (int)threadIdx.x; ch < C; ch += 256) {                                                             \
-        float wk[WV_K0];                                                                                             \
-_Pragma("unroll")                                                                                                    \
-        for (int k = 0; k < WV_K0; k++) wk[k] = w[ch * WV_K0 + k];                                                   \
-        const float b = bias ? bias[ch] : 0.f;                                                                       \
-        double s = 0.0, q = 0.0;                                                                                     \
-        for (int f = 0; f < nf; f++) {                                                                               \
-            const double y = (double)w2v_conv10(xs + f * stride, wk, b);                                             \
-            s += y; q += y * y;                                                                                      \
-        }                                                                                                            \
-        double *o = part + (((int64_t)wdx * n_part + p) * 2) * C;                                                    \
-        o[ch] = s; o[C + ch] = q;                                                                                    \
-    }
+// Group form, pass 1: sum and sum of squares of every channel over the frames [WV_PART p, WV_PART (p + 1)) of item blockIdx.y, in fp64.  The
+// partition of the time axis is fixed, so an item has ceil(t0 / WV_PART) partials among the n_part slots of its row of `part`; a block behind
+// its item's last frame leaves (the whole block: blockIdx decides)
 __global__ __launch_bounds__(256) void k_w2v_wave_stats(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win /* [W][3] */,
                                                         const float *__restrict__ w /* [C][10] */, const float *__restrict__ bias /* or null */, int C,
-                                                        int stride, int T0, int n_part, double *__restrict__ part /* [W][n_part][2][C] */)
-{
-    W2V_WAVE_STATS_BODY
-}
-// ... with every item's own frame count t0[item]: the same fixed partition, so an item has ceil(t0 / WV_PART) partials among the n_part slots of
-// its row of `part`; a block behind an item's last frame leaves (the whole block: blockIdx decides)
-__global__ __launch_bounds__(256) void k_w2v_wave_stats_seg(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win /* [W][3] */,
-                                                            const float *__restrict__ w /* [C][10] */, const float *__restrict__ bias /* or null */, int C,
-                                                            int stride, const int *__restrict__ t0 /* [W] */, int n_part,
-                                                            double *__restrict__ part /* [W][n_part][2][C] */)
+                                                        int stride, const int *__restrict__ t0 /* [W] */, int n_part,
+                                                        double *__restrict__ part /* [W][n_part][2][C] */)
 {
     const int T0 = t0[blockIdx.y];
     if ((int)blockIdx.x * WV_PART >= T0) return;
-    W2V_WAVE_STATS_BODY
-}
-// ... the partials of a (window, channel) added in the order of the partition: scale = gamma rstd, shift = beta - mean scale (biased variance).
-// Names: i (window C + channel), part, n_part, n_sum (the partials of the row that hold frames), C, T0, gamma, beta, eps, ss.
-#define W2V_WAVE_FINISH_BODY                                                     \
-    const int wdx = i / C, ch = i - wdx * C;                                     \
-    double s = 0.0, q = 0.0;                                                     \
-    for (int p = 0; p < n_sum; p++) {                                            \
-        const double *o = part + (((int64_t)wdx * n_part + p) * 2) * C;          \
-        s += o[ch]; q += o[C + ch];                                              \
-    }                                                                            \
-    const double mean = s / (double)T0;                                          \
-    double var = q / (double)T0 - mean * mean;                                   \
-    if (var < 0.0) var = 0.0;                                                    \
-    const double scale = (double)gamma[ch] / sqrt(var + (double)eps);            \
-    ss[i] = make_float2((float)scale, (float)((double)beta[ch] - mean * scale));
-__global__ void k_w2v_wave_finish(const double *__restrict__ part, int n_part, int C, int T0, int W, const float *__restrict__ gamma,
-                                  const float *__restrict__ beta, float eps, float2 *__restrict__ ss /* [W][C] */)
-{
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= W * C) return;
-    const int n_sum = n_part;
-    W2V_WAVE_FINISH_BODY
-}
-__global__ void k_w2v_wave_finish_seg(const double *__restrict__ part, int n_part, int C, const int *__restrict__ t0 /* [W] */, int W,
-                                      const float *__restrict__ gamma, const float *__restrict__ beta, float eps, float2 *__restrict__ ss /* [W][C] */)
-{
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= W * C) return;
-    const int T0 = t0[i / C], n_sum = (T0 + WV_PART - 1) / WV_PART;
-    W2V_WAVE_FINISH_BODY
-}
-// Group form, pass 2: the convolution again (its pre-norm image is never stored), normalised, GELU, op_t rows [window][slot][C].
-// Names: as pass 1, ss, out, slot (rows between two windows' images: T0 in the uniform run, the chunk's longest item's frames in the segment run).
-#define W2V_WAVE_GROUP_BODY                                                                                          \
-    __shared__ float xs[(WV_TILE - 1) * WV_STRIDE_MAX + 16];                                                         \
-    const int wdx = (int)blockIdx.y;                                                                                 \
-    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];                                  \
-    const int f0 = (int)blockIdx.x * WV_TILE, nf = min(WV_TILE, T0 - f0), ns = (nf - 1) * stride + WV_K0;            \
-    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i); \
-    __syncthreads();                                                                                                 \
-    for (int ch = 2 * (int)threadIdx.x; ch < C; ch += 512) {                                                         \
-        float wa[WV_K0], wb[WV_K0];                                                                                  \
-_Pragma("unroll")                                                                                                    \
-        for (int k = 0; k < WV_K0; k++) { wa[k] = w[ch * WV_K0 + k]; wb[k] = w[(ch + 1) * WV_K0 + k]; }              \
-        const float ba = bias ? bias[ch] : 0.f, bb = bias ? bias[ch + 1] : 0.f;                                      \
-        const float2 sa = ss[(int64_t)wdx * C + ch], sb = ss[(int64_t)wdx * C + ch + 1];                             \
-        op_t *o = out + ((int64_t)wdx * slot + f0) * C + ch;                                                         \
-        for (int f = 0; f < nf; f++) {                                                                               \
-            const float ya = w2v_conv10(xs + f * stride, wa, ba), yb = w2v_conv10(xs + f * stride, wb, bb);          \
-            opx2 v;                                                                                                  \
-            v[0] = (op_t)gelu_exact(fmaf(ya, sa.x, sa.y)); v[1] = (op_t)gelu_exact(fmaf(yb, sb.x, sb.y));            \
-            *reinterpret_cast<opx2 *>(o + (int64_t)f * C) = v;                                                       \
-        }                                                                                                            \
+    __shared__ float xs[(WV_PART - 1) * WV_STRIDE_MAX + 16];
+    const int wdx = (int)blockIdx.y, p = (int)blockIdx.x;
+    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];
+    const int f0 = p * WV_PART, nf = min(WV_PART, T0 - f0), ns = (nf - 1) * stride + WV_K0;
+    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i);
+    __syncthreads();
+    for (int ch = (int)threadIdx.x; ch < C; ch += 256) {
+        float wk[WV_K0];
+#pragma unroll
+        for (int k = 0; k < WV_K0; k++) wk[k] = w[ch * WV_K0 + k];
+        const float b = bias ? bias[ch] : 0.f;
+        double s = 0.0, q = 0.0;
+        for (int f = 0; f < nf; f++) {
+            const double y = (double)w2v_conv10(xs + f * stride, wk, b);
+            s += y; q += y * y;
+        }
+        double *o = part + (((int64_t)wdx * n_part + p) * 2) * C;
+        o[ch] = s; o[C + ch] = q;
     }
+}
+// ... the partials of an (item, channel) added in the order of the partition: scale = gamma rstd, shift = beta - mean scale (biased variance)
+__global__ void k_w2v_wave_finish(const double *__restrict__ part, int n_part, int C, const int *__restrict__ t0 /* [W] */, int W,
+                                  const float *__restrict__ gamma, const float *__restrict__ beta, float eps, float2 *__restrict__ ss /* [W][C] */)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= W * C) return;
+    const int T0 = t0[i / C], n_sum = (T0 + WV_PART - 1) / WV_PART;      // the partials of the row that hold frames
+    const int wdx = i / C, ch = i - wdx * C;
+    double s = 0.0, q = 0.0;
+    for (int p = 0; p < n_sum; p++) {
+        const double *o = part + (((int64_t)wdx * n_part + p) * 2) * C;
+        s += o[ch]; q += o[C + ch];
+    }
+    const double mean = s / (double)T0;
+    double var = q / (double)T0 - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const double scale = (double)gamma[ch] / sqrt(var + (double)eps);
+    ss[i] = make_float2((float)scale, (float)((double)beta[ch] - mean * scale));
+}
+// Group form, pass 2: the convolution again (its pre-norm image is never stored), normalised, GELU, op_t rows [item][slot][C]
 __global__ __launch_bounds__(256) void k_w2v_wave_group(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win, const float *__restrict__ w,
                                                         const float *__restrict__ bias, const float2 *__restrict__ ss, int C /* % 2 == 0 */, int stride,
-                                                        int T0, op_t *__restrict__ out)
-{
-    const int slot = T0;
-    W2V_WAVE_GROUP_BODY
-}
-__global__ __launch_bounds__(256) void k_w2v_wave_group_seg(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win, const float *__restrict__ w,
-                                                            const float *__restrict__ bias, const float2 *__restrict__ ss, int C /* % 2 == 0 */, int stride,
-                                                            const int *__restrict__ t0 /* [W] */, int slot, op_t *__restrict__ out)
+                                                        const int *__restrict__ t0 /* [W] */, int slot, op_t *__restrict__ out)
 {
     const int T0 = t0[blockIdx.y];
     if ((int)blockIdx.x * WV_TILE >= T0) return;
-    W2V_WAVE_GROUP_BODY
+    __shared__ float xs[(WV_TILE - 1) * WV_STRIDE_MAX + 16];
+    const int wdx = (int)blockIdx.y;
+    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];
+    const int f0 = (int)blockIdx.x * WV_TILE, nf = min(WV_TILE, T0 - f0), ns = (nf - 1) * stride + WV_K0;
+    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i);
+    __syncthreads();
+    for (int ch = 2 * (int)threadIdx.x; ch < C; ch += 512) {
+        float wa[WV_K0], wb[WV_K0];
+#pragma unroll
+        for (int k = 0; k < WV_K0; k++) { wa[k] = w[ch * WV_K0 + k]; wb[k] = w[(ch + 1) * WV_K0 + k]; }
+        const float ba = bias ? bias[ch] : 0.f, bb = bias ? bias[ch + 1] : 0.f;
+        const float2 sa = ss[(int64_t)wdx * C + ch], sb = ss[(int64_t)wdx * C + ch + 1];
+        op_t *o = out + ((int64_t)wdx * slot + f0) * C + ch;
+        for (int f = 0; f < nf; f++) {
+            const float ya = w2v_conv10(xs + f * stride, wa, ba), yb = w2v_conv10(xs + f * stride, wb, bb);
+            opx2 v;
+            v[0] = (op_t)gelu_exact(fmaf(ya, sa.x, sa.y)); v[1] = (op_t)gelu_exact(fmaf(yb, sb.x, sb.y));
+            *reinterpret_cast<opx2 *>(o + (int64_t)f * C) = v;
+        }
+    }
 }
 // Layer form: convolution + bias into an LDS tile [frame][channel], then one wave per frame: LayerNorm over the channels (fp32, two-pass), GELU.
-// Names: as the group form, gamma, beta, eps.
-#define W2V_WAVE_LAYER_BODY                                                                                                  \
-    __shared__ float xs[(WV_LN_F - 1) * WV_STRIDE_MAX + 16];                                                                 \
-    __shared__ float tile[WV_LN_F * WV_C_MAX];                                                                               \
-    const int wdx = (int)blockIdx.y, lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;                               \
-    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];                                          \
-    const int f0 = (int)blockIdx.x * WV_LN_F, nf = min(WV_LN_F, T0 - f0), ns = (nf - 1) * stride + WV_K0;                    \
-    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i);         \
-    __syncthreads();                                                                                                         \
-    for (int ch = (int)threadIdx.x; ch < C; ch += 256) {                                                                     \
-        float wk[WV_K0];                                                                                                     \
-_Pragma("unroll")                                                                                                            \
-        for (int k = 0; k < WV_K0; k++) wk[k] = w[ch * WV_K0 + k];                                                           \
-        const float b = bias ? bias[ch] : 0.f;                                                                               \
-        for (int f = 0; f < nf; f++) tile[f * C + ch] = w2v_conv10(xs + f * stride, wk, b);                                  \
-    }                                                                                                                        \
-    __syncthreads();                                                                                                         \
-    for (int f = wv; f < nf; f += 4) {                              /* (wave-uniform: the DPP reductions see whole waves) */ \
-        const float *row = tile + f * C;                                                                                     \
-        float s = 0.f;                                                                                                       \
-        for (int ch = lane; ch < C; ch += 64) s += row[ch];                                                                  \
-        const float mean = wave_dpp_sum_f32(s) / (float)C;                                                                   \
-        float q = 0.f;                                                                                                       \
-        for (int ch = lane; ch < C; ch += 64) { const float a = row[ch] - mean; q += a * a; }                                \
-        const float inv = rsqrtf(wave_dpp_sum_f32(q) / (float)C + eps);                                                      \
-        op_t *o = out + ((int64_t)wdx * slot + f0 + f) * C;                                                                  \
-        for (int ch = lane; ch < C; ch += 64) o[ch] = (op_t)gelu_exact((row[ch] - mean) * inv * gamma[ch] + beta[ch]);       \
-    }
+// A block behind its item's last frame leaves before the first barrier (the whole block: blockIdx decides)
 __global__ __launch_bounds__(256) void k_w2v_wave_layer(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win, const float *__restrict__ w,
                                                         const float *__restrict__ bias, const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                        int C /* <= WV_C_MAX */, int stride, int T0, float eps, op_t *__restrict__ out)
-{
-    const int slot = T0;
-    W2V_WAVE_LAYER_BODY
-}
-// ... a block behind its item's last frame leaves before the first barrier (the whole block: blockIdx decides)
-__global__ __launch_bounds__(256) void k_w2v_wave_layer_seg(const int16_t *__restrict__ pcm, const int64_t *__restrict__ win, const float *__restrict__ w,
-                                                            const float *__restrict__ bias, const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                            int C /* <= WV_C_MAX */, int stride, const int *__restrict__ t0 /* [W] */, int slot, float eps,
-                                                            op_t *__restrict__ out)
+                                                        int C /* <= WV_C_MAX */, int stride, const int *__restrict__ t0 /* [W] */, int slot, float eps,
+                                                        op_t *__restrict__ out)
 {
     const int T0 = t0[blockIdx.y];
     if ((int)blockIdx.x * WV_LN_F >= T0) return;
-    W2V_WAVE_LAYER_BODY
+    __shared__ float xs[(WV_LN_F - 1) * WV_STRIDE_MAX + 16];
+    __shared__ float tile[WV_LN_F * WV_C_MAX];
+    const int wdx = (int)blockIdx.y, lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
+    const int64_t base = win[3 * wdx], s0 = win[3 * wdx + 1], n = win[3 * wdx + 2];
+    const int f0 = (int)blockIdx.x * WV_LN_F, nf = min(WV_LN_F, T0 - f0), ns = (nf - 1) * stride + WV_K0;
+    for (int i = (int)threadIdx.x; i < ns; i += 256) xs[i] = w2v_sample(pcm, base, s0, n, (int64_t)f0 * stride + i);
+    __syncthreads();
+    for (int ch = (int)threadIdx.x; ch < C; ch += 256) {
+        float wk[WV_K0];
+#pragma unroll
+        for (int k = 0; k < WV_K0; k++) wk[k] = w[ch * WV_K0 + k];
+        const float b = bias ? bias[ch] : 0.f;
+        for (int f = 0; f < nf; f++) tile[f * C + ch] = w2v_conv10(xs + f * stride, wk, b);
+    }
+    __syncthreads();
+    for (int f = wv; f < nf; f += 4) {                              // (wave-uniform: the DPP reductions see whole waves)
+        const float *row = tile + f * C;
+        float s = 0.f;
+        for (int ch = lane; ch < C; ch += 64) s += row[ch];
+        const float mean = wave_dpp_sum_f32(s) / (float)C;
+        float q = 0.f;
+        for (int ch = lane; ch < C; ch += 64) { const float a = row[ch] - mean; q += a * a; }
+        const float inv = rsqrtf(wave_dpp_sum_f32(q) / (float)C + eps);
+        op_t *o = out + ((int64_t)wdx * slot + f0 + f) * C;
+        for (int ch = lane; ch < C; ch += 64) o[ch] = (op_t)gelu_exact((row[ch] - mean) * inv * gamma[ch] + beta[ch]);
+    }
 }
 
 // LayerNorm over the channels of 16-bit rows (one wave per row, the row in registers: C % 8 == 0, C <= LN_D_MAX), then GELU where asked: the
@@ -257,69 +216,60 @@ __global__ __launch_bounds__(256) void k_w2v_ln16(const op_t *x, const float *__
 // The weights [column][tap][channel] stream from L2 straight into the B fragments (16 bytes per lane: 8 channels of one tap, CG % 8 == 0).
 // Four waves x 64 frames; v_mfma_f32_16x16x32: lane (m = lane & 15, g = lane >> 4) gives A[m][8 g ..], B[8 g ..][m] and holds D[4 g + i][m].
 // LDS rows are CG + 8 elements apart: the 16 rows of a fragment read start 16 bytes x an odd multiple apart and meet no bank twice.
-// (the body: names x, w, bias, T (the window's frames), rows_per_win, d, out and the template's CG)
-#define W2V_POSCONV_BODY                                                                                                                                  \
-    constexpr int LD = CG + 8, NB = CG / 16, TPR = CG / 4, KT = PC_TAPS * CG / 32;                                                                        \
-    __shared__ __attribute__((aligned(16))) op_t xs[PC_ROWS * LD];                                                                                        \
-    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, m = lane & 15, g4 = lane >> 4;                                                      \
-    const int t0 = (int)blockIdx.x * PC_MT, grp = (int)blockIdx.y;                                                                                        \
-    const int64_t row0 = (int64_t)blockIdx.z * rows_per_win;                                                                                              \
-    for (int i = tid; i < PC_ROWS * TPR; i += 256) {                                                                                                      \
-        const int r = i / TPR, c4 = (i - r * TPR) * 4, t = t0 - PC_TAPS / 2 + r;                                                                          \
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);                                                                                                       \
-        if (t >= 0 && t < T) v = *reinterpret_cast<const float4 *>(x + (row0 + t) * d + grp * CG + c4);                                                   \
-        opx4_w o; o[0] = (op_t)v.x; o[1] = (op_t)v.y; o[2] = (op_t)v.z; o[3] = (op_t)v.w;                                                                 \
-        *reinterpret_cast<opx4_w *>(xs + r * LD + c4) = o;                                                                                                \
-    }                                                                                                                                                     \
-    __syncthreads();                                                                                                                                      \
-    f32x4 acc[4][NB];                                                                                                                                     \
-_Pragma("unroll")                                                                                                                                         \
-    for (int a = 0; a < 4; a++)                                                                                                                           \
-_Pragma("unroll")                                                                                                                                         \
-        for (int nb = 0; nb < NB; nb++) acc[a][nb] = f32x4{0.f, 0.f, 0.f, 0.f};                                                                           \
-    if (t0 + wv * 64 < T) {                                       /* (wave-uniform) a wave whose 64 frames lie behind the window's last has no product */ \
-        const op_t *wb = w + (int64_t)(grp * CG + m) * (PC_TAPS * CG) + 8 * g4;                                                                           \
-        const op_t *xa = xs + (wv * 64 + m) * LD;                                                                                                         \
-_Pragma("unroll 4")                                                                                                                                       \
-        for (int s = 0; s < KT; s++) {                                                                                                                    \
-            const int kk = s * 32 + 8 * g4, k = kk / CG, ci = kk - k * CG;                                                                                \
-            opx8 a[4], b[NB];                                                                                                                             \
-_Pragma("unroll")                                                                                                                                         \
-            for (int nb = 0; nb < NB; nb++) b[nb] = *reinterpret_cast<const opx8 *>(wb + (int64_t)nb * 16 * (PC_TAPS * CG) + s * 32);                     \
-_Pragma("unroll")                                                                                                                                         \
-            for (int mb = 0; mb < 4; mb++) a[mb] = *reinterpret_cast<const opx8 *>(xa + (mb * 16 + k) * LD + ci);                                         \
-_Pragma("unroll")                                                                                                                                         \
-            for (int mb = 0; mb < 4; mb++)                                                                                                                \
-_Pragma("unroll")                                                                                                                                         \
-                for (int nb = 0; nb < NB; nb++) acc[mb][nb] = mfma16(a[mb], b[nb], acc[mb][nb]);                                                          \
-        }                                                                                                                                                 \
-    }                                                                                                                                                     \
-_Pragma("unroll")                                                                                                                                         \
-    for (int mb = 0; mb < 4; mb++)                                                                                                                        \
-_Pragma("unroll")                                                                                                                                         \
-        for (int nb = 0; nb < NB; nb++)                                                                                                                   \
-_Pragma("unroll")                                                                                                                                         \
-            for (int i = 0; i < 4; i++) {                                                                                                                 \
-                const int t = t0 + wv * 64 + mb * 16 + 4 * g4 + i, col = grp * CG + nb * 16 + m;                                                          \
-                if (t >= rows_per_win) continue;                                                                                                          \
-                const int64_t idx = (row0 + t) * d + col;                                                                                                 \
-                const float h = x[idx];                                                                                                                   \
-                out[idx] = t < T ? h + gelu_exact(acc[mb][nb][i] + bias[col]) : h;       /* (a pad row: any finite value) */                              \
-            }
+// Window z holds len[z] <= rows_per_win frames: the halo's zeros, the wave-uniform skip and the epilogue's t < T follow it.
 template <int CG>
 __global__ __launch_bounds__(256) void k_w2v_posconv(const float *__restrict__ x /* [window][rows_per_win][d] */, const op_t *__restrict__ w,
-                                                     const float *__restrict__ bias, int T, int rows_per_win, int d, float *__restrict__ out)
-{
-    W2V_POSCONV_BODY
-}
-// ... with every window's own frame count len[window] <= rows_per_win: the halo's zeros, the wave-uniform skip and the epilogue's t < T follow it
-template <int CG>
-__global__ __launch_bounds__(256) void k_w2v_posconv_seg(const float *__restrict__ x /* [window][rows_per_win][d] */, const op_t *__restrict__ w,
-                                                         const float *__restrict__ bias, const int *__restrict__ len /* [windows] */, int rows_per_win, int d,
-                                                         float *__restrict__ out)
+                                                     const float *__restrict__ bias, const int *__restrict__ len /* [windows] */, int rows_per_win, int d,
+                                                     float *__restrict__ out)
 {
     const int T = len[blockIdx.z];
-    W2V_POSCONV_BODY
+    constexpr int LD = CG + 8, NB = CG / 16, TPR = CG / 4, KT = PC_TAPS * CG / 32;
+    __shared__ __attribute__((aligned(16))) op_t xs[PC_ROWS * LD];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6, m = lane & 15, g4 = lane >> 4;
+    const int t0 = (int)blockIdx.x * PC_MT, grp = (int)blockIdx.y;
+    const int64_t row0 = (int64_t)blockIdx.z * rows_per_win;
+    for (int i = tid; i < PC_ROWS * TPR; i += 256) {
+        const int r = i / TPR, c4 = (i - r * TPR) * 4, t = t0 - PC_TAPS / 2 + r;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t >= 0 && t < T) v = *reinterpret_cast<const float4 *>(x + (row0 + t) * d + grp * CG + c4);
+        opx4_w o; o[0] = (op_t)v.x; o[1] = (op_t)v.y; o[2] = (op_t)v.z; o[3] = (op_t)v.w;
+        *reinterpret_cast<opx4_w *>(xs + r * LD + c4) = o;
+    }
+    __syncthreads();
+    f32x4 acc[4][NB];
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++) acc[a][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (t0 + wv * 64 < T) {                                       // (wave-uniform) a wave whose 64 frames lie behind the window's last has no product
+        const op_t *wb = w + (int64_t)(grp * CG + m) * (PC_TAPS * CG) + 8 * g4;
+        const op_t *xa = xs + (wv * 64 + m) * LD;
+#pragma unroll 4
+        for (int s = 0; s < KT; s++) {
+            const int kk = s * 32 + 8 * g4, k = kk / CG, ci = kk - k * CG;
+            opx8 a[4], b[NB];
+#pragma unroll
+            for (int nb = 0; nb < NB; nb++) b[nb] = *reinterpret_cast<const opx8 *>(wb + (int64_t)nb * 16 * (PC_TAPS * CG) + s * 32);
+#pragma unroll
+            for (int mb = 0; mb < 4; mb++) a[mb] = *reinterpret_cast<const opx8 *>(xa + (mb * 16 + k) * LD + ci);
+#pragma unroll
+            for (int mb = 0; mb < 4; mb++)
+#pragma unroll
+                for (int nb = 0; nb < NB; nb++) acc[mb][nb] = mfma16(a[mb], b[nb], acc[mb][nb]);
+        }
+    }
+#pragma unroll
+    for (int mb = 0; mb < 4; mb++)
+#pragma unroll
+        for (int nb = 0; nb < NB; nb++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int t = t0 + wv * 64 + mb * 16 + 4 * g4 + i, col = grp * CG + nb * 16 + m;
+                if (t >= rows_per_win) continue;
+                const int64_t idx = (row0 + t) * d + col;
+                const float h = x[idx];
+                out[idx] = t < T ? h + gelu_exact(acc[mb][nb][i] + bias[col]) : h;       // (a pad row: any finite value)
+            }
 }
 
 // The tail: frames [cut, cut + n_keep) of every window, log-softmax in fp32 over the V real columns of the padded logits, a zero <star> column
@@ -363,27 +313,18 @@ struct W2vGemm {                       // encoder_walk's GEMM rule for this mode
     template <int EPI, class... A> static bool run(pce_ctx *c, A... a) { return w2v_gemm<EPI>(c, a...); }
 };
 
-// len == nullptr: every window holds T frames; else window i holds len[i] <= T (device table) and `frames` of them in all (the timer's work count)
-static void w2v_launch_posconv(pce_ctx *c, const float *x, const op_t *w, const float *bias, int T, int rows_per_win, int d, int groups, int n_win, float *out,
-                               const int *len = nullptr, double frames = 0.0)
+// n_win windows of len[i] <= rows_per_win frames (device table) in slots of rows_per_win rows, `frames` of them in all (the timer's work count)
+static void w2v_launch_posconv(pce_ctx *c, const float *x, const op_t *w, const float *bias, const int *len, double frames, int rows_per_win, int d, int groups,
+                               int n_win, float *out)
 {
     const int cg = d / groups;
     const dim3 grid((unsigned)div_up(rows_per_win, PC_MT), (unsigned)groups, (unsigned)n_win), block(256);
-    KernelTimer kt(c, PCE_K_W2V_POSCONV, nullptr, 2.0 * (len ? frames : (double)n_win * T) * d * PC_TAPS * cg);
-    if (len) {
-        switch (cg) {
-        case 16: hipLaunchKernelGGL(k_w2v_posconv_seg<16>, grid, block, 0, c->stream, x, w, bias, len, rows_per_win, d, out); break;
-        case 32: hipLaunchKernelGGL(k_w2v_posconv_seg<32>, grid, block, 0, c->stream, x, w, bias, len, rows_per_win, d, out); break;
-        case 48: hipLaunchKernelGGL(k_w2v_posconv_seg<48>, grid, block, 0, c->stream, x, w, bias, len, rows_per_win, d, out); break;
-        default: hipLaunchKernelGGL(k_w2v_posconv_seg<64>, grid, block, 0, c->stream, x, w, bias, len, rows_per_win, d, out); break;
-        }
-        return;
-    }
+    KernelTimer kt(c, PCE_K_W2V_POSCONV, nullptr, 2.0 * frames * d * PC_TAPS * cg);
     switch (cg) {
-    case 16: hipLaunchKernelGGL(k_w2v_posconv<16>, grid, block, 0, c->stream, x, w, bias, T, rows_per_win, d, out); break;
-    case 32: hipLaunchKernelGGL(k_w2v_posconv<32>, grid, block, 0, c->stream, x, w, bias, T, rows_per_win, d, out); break;
-    case 48: hipLaunchKernelGGL(k_w2v_posconv<48>, grid, block, 0, c->stream, x, w, bias, T, rows_per_win, d, out); break;
-    default: hipLaunchKernelGGL(k_w2v_posconv<64>, grid, block, 0, c->stream, x, w, bias, T, rows_per_win, d, out); break;
+    case 16: hipLaunchKernelGGL(k_w2v_posconv<16>, grid, block, 0, c->stream, x, w, bias, len, rows_per_win, d, out); break;
+    case 32: hipLaunchKernelGGL(k_w2v_posconv<32>, grid, block, 0, c->stream, x, w, bias, len, rows_per_win, d, out); break;
+    case 48: hipLaunchKernelGGL(k_w2v_posconv<48>, grid, block, 0, c->stream, x, w, bias, len, rows_per_win, d, out); break;
+    default: hipLaunchKernelGGL(k_w2v_posconv<64>, grid, block, 0, c->stream, x, w, bias, len, rows_per_win, d, out); break;
     }
 }
 static bool w2v_posconv_fits(int d, int groups)
@@ -393,30 +334,23 @@ static bool w2v_posconv_fits(int d, int groups)
     return cg == 16 || cg == 32 || cg == 48 || cg == 64;
 }
 
-// the waveform layer of n_win windows: group form (feat_norm 0: statistics, finish, recompute) or layer form (1).  d_t0 == nullptr: T0 frames per
-// window; else window i holds d_t0[i] <= T0 frames (device table) in a slot of T0 rows, `frames` of them in all (the timer's work count)
-static int w2v_launch_wave(pce_ctx *c, int feat_norm, const int64_t *d_win, int n_win, const float *w, const float *bias, const float *gamma,
-                           const float *beta, int C, int stride, int T0, DevBuf &part, DevBuf &ss, op_t *out, const int *d_t0 = nullptr, double frames = 0.0)
+// the waveform layer of n_win windows of pcm: group form (feat_norm 0: statistics, finish, recompute) or layer form (1).  Window i holds
+// d_t0[i] <= slot frames (device table) in a slot of `slot` rows, `frames` of them in all (the timer's work count)
+static int w2v_launch_wave(pce_ctx *c, int feat_norm, const int16_t *pcm, const int64_t *d_win, const int *d_t0, double frames, int n_win, const float *w,
+                           const float *bias, const float *gamma, const float *beta, int C, int stride, int slot, DevBuf &part, DevBuf &ss, op_t *out)
 {
-    KernelTimer kt(c, PCE_K_W2V_WAVE, nullptr, 2.0 * (d_t0 ? frames : (double)n_win * T0) * C * WV_K0 * (feat_norm == 0 ? 2 : 1));
+    KernelTimer kt(c, PCE_K_W2V_WAVE, nullptr, 2.0 * frames * C * WV_K0 * (feat_norm == 0 ? 2 : 1));
     if (feat_norm == 0) {
-        const int n_part = (int)div_up(T0, WV_PART);
+        const int n_part = (int)div_up(slot, WV_PART);
         PCE_HIP(c, part.reserve(sizeof(double) * (size_t)n_win * n_part * 2 * C));
         PCE_HIP(c, ss.reserve(sizeof(float2) * (size_t)n_win * C));
-        const dim3 g_stats((unsigned)n_part, (unsigned)n_win), g_fin((unsigned)div_up((int64_t)n_win * C, 256)), g_group((unsigned)div_up(T0, WV_TILE), (unsigned)n_win);
-        if (d_t0) {
-            hipLaunchKernelGGL(k_w2v_wave_stats_seg, g_stats, dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias, C, stride, d_t0, n_part, part.as<double>());
-            hipLaunchKernelGGL(k_w2v_wave_finish_seg, g_fin, dim3(256), 0, c->stream, part.as<double>(), n_part, C, d_t0, n_win, gamma, beta, 1e-5f, ss.as<float2>());
-            hipLaunchKernelGGL(k_w2v_wave_group_seg, g_group, dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias, ss.as<float2>(), C, stride, d_t0, T0, out);
-        } else {
-            hipLaunchKernelGGL(k_w2v_wave_stats, g_stats, dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias, C, stride, T0, n_part, part.as<double>());
-            hipLaunchKernelGGL(k_w2v_wave_finish, g_fin, dim3(256), 0, c->stream, part.as<double>(), n_part, C, T0, n_win, gamma, beta, 1e-5f, ss.as<float2>());
-            hipLaunchKernelGGL(k_w2v_wave_group, g_group, dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias, ss.as<float2>(), C, stride, T0, out);
-        }
+        const dim3 g_stats((unsigned)n_part, (unsigned)n_win), g_fin((unsigned)div_up((int64_t)n_win * C, 256)), g_group((unsigned)div_up(slot, WV_TILE), (unsigned)n_win);
+        hipLaunchKernelGGL(k_w2v_wave_stats, g_stats, dim3(256), 0, c->stream, pcm, d_win, w, bias, C, stride, d_t0, n_part, part.as<double>());
+        hipLaunchKernelGGL(k_w2v_wave_finish, g_fin, dim3(256), 0, c->stream, part.as<double>(), n_part, C, d_t0, n_win, gamma, beta, 1e-5f, ss.as<float2>());
+        hipLaunchKernelGGL(k_w2v_wave_group, g_group, dim3(256), 0, c->stream, pcm, d_win, w, bias, ss.as<float2>(), C, stride, d_t0, slot, out);
     } else {
-        const dim3 grid((unsigned)div_up(T0, WV_LN_F), (unsigned)n_win);
-        if (d_t0) hipLaunchKernelGGL(k_w2v_wave_layer_seg, grid, dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias, gamma, beta, C, stride, d_t0, T0, 1e-5f, out);
-        else hipLaunchKernelGGL(k_w2v_wave_layer, grid, dim3(256), 0, c->stream, c->d_pcm, d_win, w, bias, gamma, beta, C, stride, T0, 1e-5f, out);
+        const dim3 grid((unsigned)div_up(slot, WV_LN_F), (unsigned)n_win);
+        hipLaunchKernelGGL(k_w2v_wave_layer, grid, dim3(256), 0, c->stream, pcm, d_win, w, bias, gamma, beta, C, stride, d_t0, slot, 1e-5f, out);
     }
     return PCE_OK;
 }
@@ -479,30 +413,48 @@ static int w2v_check(const pce_w2v_dims &m, int64_t n_floats, char *msg, size_t 
     return PCE_OK;
 }
 
-
-// One chunk of n_win windows through the whole model, from the resident PCM to its rows of b.em.  A window's slot is Tl[i] rows at
-// convolution i (T_pad behind the last) and T_pad rows from there on.  t0 == nullptr: every window holds Tl[0] waveform frames and T frames
-// (pce_w2v_run); else window i holds t0[i] waveform frames and len[i] frames (pce_w2v_run_segments).  All tables are device pointers.
+// A run as the host describes it: items (the windows of pce_w2v_run, the segments of pce_w2v_run_segments) in chunks that go through one set
+// of launches each, and the tables those launches read.  An item's slot in its chunk is Tl[i] rows behind convolution i (T_pad behind the
+// last, whose frames are Tl[6]) and T_pad rows from there on; the item itself holds t0[] waveform frames and len[] frames.
 struct W2vChunk {
-    int n_win; const int *Tl; int T, T_pad, vt_sp;
-    const int64_t *win;                 // [n_win][3]: first sample of the clip, the window's first sample relative to it, samples it may read
-    const int *t0; double wave_frames;  // waveform frames per window, or null; their sum (the timer's work count)
-    const int *row0, *len; double frames, attn_flops;      // the attention's tables (len: also the positional convolution's, with t0)
-    const int64_t *tail; int tail_frames, cut, star, n_cols;
+    int64_t first; int n_win;           // items [first, first + n_win) of win and tail
+    int64_t tab;                        // the chunk's first entry of t0, row0 and len
+    int Tl[7], T_pad, vt_sp;            // the slot; columns of a row of V^T
+    int tail_frames;                    // frames an item keeps, at most (the tail's grid)
+    double wave_frames, frames, attn_flops;      // the timers' work counts: waveform frames, frames and attention flops of the chunk's items
 };
-static int w2v_forward_chunk(pce_ctx *c, WhisperState::W2v &b, const W2vChunk &k, bool &fit)
+struct W2vRun {
+    std::vector<W2vChunk> chunks;
+    std::vector<int64_t> win;           // [item][3]: first sample of the clip, the item's first sample relative to it, samples it may read
+    std::vector<int64_t> tail;          // [item][2]: first row of b.em, frames kept
+    std::vector<int> t0, row0, len;     // waveform frames; first row of the slot in its chunk; frames (attention, positional convolution)
+    int64_t rows_total = 0;             // rows of b.em
+    int cut = 0, star = 0, n_cols = 0;  // frames dropped in front of every item; the <star> column; columns of b.em
+};
+static W2vChunk w2v_chunk(int64_t first, int n_win, int64_t tab, const int *Tl)
+{
+    W2vChunk k{};
+    k.first = first; k.n_win = n_win; k.tab = tab;
+    std::copy(Tl, Tl + 7, k.Tl);
+    k.T_pad = w2v_rows_pad(Tl[6]); k.vt_sp = (int)div_up(Tl[6], 64) * 64;
+    return k;
+}
+
+// One chunk through the whole model, from the resident PCM to its rows of b.em (the run's tables are on the device: w2v_run_chunks)
+static int w2v_forward_chunk(pce_ctx *c, WhisperState::W2v &b, const W2vRun &run, const W2vChunk &k, bool &fit)
 {
     const pce_w2v_dims &m = b.dims;
     const int d = m.n_state, H = m.n_head, I = m.n_inter, V = m.n_vocab, Vp = b.Vp, C6 = m.conv_dim[6];
     const int Wc = k.n_win, T_pad = k.T_pad, M = Wc * T_pad;
     const int *Tl = k.Tl;
+    const int *t0 = b.t0tab.as<int>() + k.tab, *row0 = b.atab.as<int>() + k.tab, *len = row0 + run.row0.size();
     const op_t *Wb = b.w16.as<op_t>();
     const float *Wf = b.w32.as<float>();
     const float eps = m.ln_eps;
     {   // the feature encoder
         const WhisperState::W2v::Conv &c0 = b.conv[0];
-        PCE_TRY(w2v_launch_wave(c, m.feat_norm, k.win, Wc, Wf + c0.w, c0.has_b ? Wf + c0.b : nullptr, Wf + c0.g, Wf + c0.beta, m.conv_dim[0], m.conv_stride[0], Tl[0],
-                                b.part, b.ss, b.img[0].as<op_t>(), k.t0, k.wave_frames));
+        PCE_TRY(w2v_launch_wave(c, m.feat_norm, c->d_pcm, b.wintab.as<int64_t>() + 3 * k.first, t0, k.wave_frames, Wc, Wf + c0.w, c0.has_b ? Wf + c0.b : nullptr,
+                                Wf + c0.g, Wf + c0.beta, m.conv_dim[0], m.conv_stride[0], Tl[0], b.part, b.ss, b.img[0].as<op_t>()));
         for (int i = 1; i < 7; i++) {
             const WhisperState::W2v::Conv &cv = b.conv[i];
             const int ci = m.conv_dim[i - 1], co = m.conv_dim[i];
@@ -523,9 +475,9 @@ static int w2v_forward_chunk(pce_ctx *c, WhisperState::W2v &b, const W2vChunk &k
     // feature projection, positional convolution
     w2v_launch_ln16(c, false, b.img[0].as<op_t>(), Wf + b.fp_ln_w, Wf + b.fp_ln_b, M, C6, eps, b.fpln.as<op_t>());
     fit &= w2v_gemm<EPI_F32>(c, b.fpln.as<op_t>(), C6, 0, Wb + b.proj_w, M, d, C6, Wf + b.proj_b, b.h0.as<float>(), d, 0, 1);
-    w2v_launch_posconv(c, b.h0.as<float>(), Wb + b.pos_w, Wf + b.pos_b, k.T, T_pad, d, m.pos_groups, Wc, b.h.as<float>(), k.t0 ? k.len : nullptr, k.frames);
+    w2v_launch_posconv(c, b.h0.as<float>(), Wb + b.pos_w, Wf + b.pos_b, len, k.frames, T_pad, d, m.pos_groups, Wc, b.h.as<float>());
     const bool pre = m.stable_ln != 0;
-    const EncoderRun r{M, d, H, I, Wc, T_pad, k.vt_sp, k.row0, k.len, eps, k.attn_flops, false, b.h.as<float>(), b.ln.as<op_t>(), b.qk.as<op_t>(),
+    const EncoderRun r{M, d, H, I, Wc, T_pad, k.vt_sp, row0, len, eps, k.attn_flops, false, b.h.as<float>(), b.ln.as<op_t>(), b.qk.as<op_t>(),
                        b.vt.as<op_t>(), b.attn.as<op_t>(), b.hidden.as<op_t>(), Wb, Wf};
     // the encoder LayerNorm: in front of a post-LN stack (in place on the fp32 stream, and its op_t copy), behind a pre-LN one
     if (!pre) launch_layernorm<op_t>(c, b.h.as<float>(), Wf + b.enc_ln_w, Wf + b.enc_ln_b, M, d, b.ln.as<op_t>(), eps, b.h.as<float>());
@@ -534,8 +486,8 @@ static int w2v_forward_chunk(pce_ctx *c, WhisperState::W2v &b, const W2vChunk &k
     fit &= w2v_gemm<EPI_F32>(c, b.ln.as<op_t>(), d, 0, Wb + b.lm_w, M, Vp, d, Wf + b.lm_b, b.logits.as<float>(), Vp, 0, 1);
     {
         KernelTimer kt(c, PCE_K_W2V_TAIL);
-        hipLaunchKernelGGL(k_w2v_tail, dim3((unsigned)div_up(k.tail_frames, 4), (unsigned)Wc), dim3(256), 0, c->stream, b.logits.as<float>(), Vp, V, k.star, k.tail,
-                           T_pad, k.cut, b.em.as<float>(), k.n_cols);
+        hipLaunchKernelGGL(k_w2v_tail, dim3((unsigned)div_up(k.tail_frames, 4), (unsigned)Wc), dim3(256), 0, c->stream, b.logits.as<float>(), Vp, V, run.star,
+                           b.tailtab.as<int64_t>() + 2 * k.first, T_pad, run.cut, b.em.as<float>(), run.n_cols);
     }
     PCE_HIP(c, hipGetLastError());
     if (!fit) return pce_fail(c, PCE_E_LIMIT, "a product of this model has a shape the tiled GEMM kernels do not compute (N %% 128, K %% 64)");
@@ -549,6 +501,82 @@ static int64_t w2v_slot_bytes(const pce_w2v_dims &m, int Vp, const int *Tl, int6
     for (int i = 0; i < 7; i++) img_e[i & 1] = std::max<int64_t>(img_e[i & 1], (int64_t)(i == 6 ? T_pad : Tl[i]) * m.conv_dim[i]);
     return 2 * (img_e[0] + img_e[1]) + (int64_t)T_pad * (2LL * C6 + 8LL * d + 2LL * d + 4LL * d + 2LL * d + 2LL * I + 4LL * Vp) + 2LL * d * vt_sp +
            (m.feat_norm == 0 ? 16LL * div_up(Tl[0], WV_PART) * m.conv_dim[0] : 0);
+}
+
+// The run: buffers for the largest chunk, the tables, the clears, the chunks.  A chunk's launches cover n_win slots of its own rows, every item's
+// own frame counts in the tables of the waveform layer, the positional convolution, the attention and the tail.
+//
+// Rows behind an item's own frames, and why nothing that is not finite sits in them although the slot stride changes from chunk to chunk.
+// A real row reads pad rows of its own slot in one place only: the attention multiplies the V^T columns of masked keys by probabilities that
+// are exactly zero, so those columns must be finite; everything else a real row reads is a real row of its slot (a convolution row t < Tl[i]
+// reads rows < Tl[i - 1], the positional convolution takes frames >= len as zeros, GEMM and LayerNorm rows are independent).  The pad rows are
+// finite by induction over the launches.  Every buffer but three is written in all rows of all slots of a chunk before the
+// chunk reads it (img[1], fpln, h0, h, ln, qk, hidden, logits: GEMM, LayerNorm and positional-convolution launches cover M = slots x rows), so
+// what an earlier chunk or call left there under another stride is never read.  The three that a chunk writes in part are img[0] (the waveform
+// layer writes t < t0 of a slot of Tl[0] rows; the last convolution Tl[6] of T_pad rows), attn (the attention writes queries < len) and vt (the
+// V epilogue writes keys < T_pad of vt_sp columns).  Their other elements hold what an earlier chunk stored there under its own stride, and
+// that is always a value one of these kernels stored for some row -- a GELU or LayerNorm output, an attention output, a V projection, computed
+// from finite inputs -- or the zero of the clear below: the three are cleared over the largest extent any chunk of this call uses before the
+// first launch, so no element is read that this call or the clear did not write (a buffer that grew holds fresh memory).  Stale rows are
+// therefore finite under any stride, and a finite pad row gives finite pad rows downstream (no kernel divides by a row's own values but the
+// LayerNorms, whose eps > 0 keeps a constant row finite).
+static int w2v_run_chunks(pce_ctx *c, WhisperState::W2v &b, const W2vRun &run)
+{
+    const pce_w2v_dims &m = b.dims;
+    const int d = m.n_state, I = m.n_inter, Vp = b.Vp, C6 = m.conv_dim[6];
+    int64_t img0 = 0, img1 = 0, M_max = 0, vt_max = 0;
+    for (const W2vChunk &k : run.chunks) {
+        int64_t e[2];
+        w2v_slot_bytes(m, Vp, k.Tl, e);
+        img0 = std::max(img0, k.n_win * e[0]); img1 = std::max(img1, k.n_win * e[1]);
+        M_max = std::max(M_max, (int64_t)k.n_win * k.T_pad); vt_max = std::max(vt_max, (int64_t)k.n_win * d * k.vt_sp);
+    }
+    PCE_HIP(c, b.img[1].reserve(sizeof(op_t) * (size_t)img1 + 4096));
+    PCE_HIP(c, b.fpln.reserve(sizeof(op_t) * (size_t)M_max * C6 + 4096));
+    PCE_HIP(c, b.h0.reserve(sizeof(float) * (size_t)M_max * d));
+    PCE_HIP(c, b.h.reserve(sizeof(float) * (size_t)M_max * d));
+    PCE_HIP(c, b.ln.reserve(sizeof(op_t) * (size_t)M_max * d + 4096));
+    PCE_HIP(c, b.qk.reserve(sizeof(op_t) * (size_t)M_max * 2 * d + 4096));
+    PCE_HIP(c, b.hidden.reserve(sizeof(op_t) * (size_t)M_max * I + 4096));
+    PCE_HIP(c, b.logits.reserve(sizeof(float) * (size_t)M_max * Vp));
+    PCE_HIP(c, b.em.reserve(sizeof(float) * (size_t)run.rows_total * run.n_cols + 256));
+    std::vector<int> at(run.row0);                              // the attention's two tables in one buffer: every row0, then every len
+    at.insert(at.end(), run.len.begin(), run.len.end());
+    PCE_UPLOAD(c, b.wintab, run.win);
+    PCE_UPLOAD(c, b.tailtab, run.tail);
+    PCE_UPLOAD(c, b.t0tab, run.t0);
+    PCE_UPLOAD(c, b.atab, at);
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    // what the argument above needs cleared: the three buffers a chunk writes in part, over the largest extent any chunk uses
+    PCE_ZERO(op_t, c, b.img[0], (size_t)img0 + 2048);
+    PCE_ZERO(op_t, c, b.attn, (size_t)M_max * d + 2048);
+    PCE_ZERO(op_t, c, b.vt, (size_t)vt_max + 64);
+    KernelTimer timer(c, PCE_K_W2V);
+    bool fit = true;                                             // every product's shape fits its kernel (w2v_gemm)
+    for (const W2vChunk &k : run.chunks) PCE_TRY(w2v_forward_chunk(c, b, run, k, fit));
+    return PCE_OK;
+}
+
+// the waveform layer's selftests: items tab[i] of t0[i] frames of pcm through the run's launches into out [item][slot][C], slot = the longest
+// item's frames; rows behind an item's frames are left as the zeros out is cleared to
+static int w2v_selftest_wave(pce_ctx *c, const int16_t *pcm, int64_t n_samples, const std::vector<int64_t> &tab, const std::vector<int> &t0, int feat_norm, int C,
+                             int stride, const float *w, const float *bias, const float *gamma, const float *beta, uint16_t *out)
+{
+    const int n_win = (int)t0.size(), slot = *std::max_element(t0.begin(), t0.end());
+    double frames = 0.0;
+    for (const int t : t0) frames += (double)t;
+    DevBuf dp, dt, d0, dw, db, dg, dbe, part, ss, dout;
+    const size_t n_out = (size_t)n_win * (size_t)slot * C;
+    PCE_UPLOAD(c, dp, pcm, (size_t)n_samples); PCE_UPLOAD(c, dt, tab); PCE_UPLOAD(c, d0, t0); PCE_UPLOAD(c, dw, w, (size_t)C * WV_K0);
+    if (bias) PCE_UPLOAD(c, db, bias, (size_t)C);
+    PCE_UPLOAD(c, dg, gamma, (size_t)C); PCE_UPLOAD(c, dbe, beta, (size_t)C);
+    PCE_ZERO(op_t, c, dout, n_out);
+    PCE_TRY(w2v_launch_wave(c, feat_norm, dp.as<int16_t>(), dt.as<int64_t>(), d0.as<int>(), frames, n_win, dw.as<float>(), bias ? db.as<float>() : nullptr,
+                            dg.as<float>(), dbe.as<float>(), C, stride, slot, part, ss, dout.as<op_t>()));
+    PCE_HIP(c, hipGetLastError());
+    PCE_FETCH(c, out, dout.p, n_out);
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    return PCE_OK;
 }
 
 } // namespace
@@ -628,28 +656,29 @@ int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan)
                         (long long)window, (long long)context, std::min(T - cut + 1, T) - cut, cut, wf);
     PCE_HIP(c, hipSetDevice(c->device));
     b.n_clips = -1; b.seg_plan[0] = -1;
-    const int n = c->n_clips, d = m.n_state, I = m.n_inter, V = m.n_vocab, Vp = b.Vp, C6 = m.conv_dim[6];
+    const int n = c->n_clips, d = m.n_state, I = m.n_inter, V = m.n_vocab, Vp = b.Vp;
     const int T_pad = w2v_rows_pad(T), vt_sp = (int)div_up(T, 64) * 64, n_cols = V + (plan->star ? 1 : 0);
     // the attention's buffer resources and the transposed-V epilogue form 32-bit byte offsets inside one window
     if (((int64_t)T * 2 * d + 64) * 2 >= ((int64_t)1 << 31) || (int64_t)64 * vt_sp * 2 >= ((int64_t)1 << 31))
         return pce_fail(c, PCE_E_LIMIT, "%d frames per window: the attention kernel's 32-bit offsets do not reach that far", T);
     // the plan: every clip's windows, the rows its kept frames take
-    std::vector<int64_t> win_tab, tail_tab;
+    W2vRun run;
+    run.cut = cut; run.star = plan->star ? 1 : 0; run.n_cols = n_cols;
     b.row_start.assign((size_t)n, 0); b.n_frames.assign((size_t)n, 0);
-    int64_t rows_total = 0;
+    int64_t &rows_total = run.rows_total;
     for (int q = 0; q < n; q++) {
         const int64_t len = c->clip_off[(size_t)q + 1] - c->clip_off[(size_t)q];
         int64_t n_win, keep;
         pce_w2v_window_plan(len, (int32_t)window, (int32_t)context, &n_win, &keep);
         b.row_start[(size_t)q] = rows_total; b.n_frames[(size_t)q] = (int32_t)keep;
         for (int64_t j = 0; j < n_win; j++) {
-            win_tab.push_back(c->clip_off[(size_t)q]); win_tab.push_back(j * window - context); win_tab.push_back(len);
-            tail_tab.push_back(rows_total + j * wf); tail_tab.push_back(std::min<int64_t>(wf, keep - j * wf));
+            run.win.push_back(c->clip_off[(size_t)q]); run.win.push_back(j * window - context); run.win.push_back(len);
+            run.tail.push_back(rows_total + j * wf); run.tail.push_back(std::min<int64_t>(wf, keep - j * wf));
         }
         rows_total += keep;
         if (rows_total > INT32_MAX) return pce_fail(c, PCE_E_LIMIT, "more than 2^31 emission frames in one batch");
     }
-    const int64_t W = (int64_t)(win_tab.size() / 3);
+    const int64_t W = (int64_t)(run.win.size() / 3);
     b.n_cols = n_cols;
     if (W == 0) { b.n_clips = 0; return PCE_OK; }
     // chunk size: the images of one window
@@ -658,60 +687,21 @@ int pce_w2v_run(pce_ctx *c, const pce_w2v_plan *plan)
     int64_t wpc = plan->windows_per_chunk > 0 ? plan->windows_per_chunk : std::max<int64_t>(1, PCE_W2V_IMAGE_BUDGET / per_window);
     wpc = std::min<int64_t>(std::min<int64_t>(wpc, W), 4096);
     while (wpc > 1 && wpc * T_pad * (int64_t)std::max(std::max(3 * d, I), Vp) >= ((int64_t)1 << 31)) wpc--;      // (the launchers count rows in int)
-    const int64_t M_max = wpc * T_pad;
-    PCE_HIP(c, b.img[1].reserve(sizeof(op_t) * (size_t)(wpc * img_e[1]) + 4096));
-    PCE_HIP(c, b.fpln.reserve(sizeof(op_t) * (size_t)M_max * C6 + 4096));
-    PCE_HIP(c, b.h0.reserve(sizeof(float) * (size_t)M_max * d));
-    PCE_HIP(c, b.h.reserve(sizeof(float) * (size_t)M_max * d));
-    PCE_HIP(c, b.ln.reserve(sizeof(op_t) * (size_t)M_max * d + 4096));
-    PCE_HIP(c, b.qk.reserve(sizeof(op_t) * (size_t)M_max * 2 * d + 4096));
-    PCE_HIP(c, b.hidden.reserve(sizeof(op_t) * (size_t)M_max * I + 4096));
-    PCE_HIP(c, b.logits.reserve(sizeof(float) * (size_t)M_max * Vp));
-    const size_t vt_elems = (size_t)wpc * (size_t)d * vt_sp + 64;
-    PCE_HIP(c, b.em.reserve(sizeof(float) * (size_t)rows_total * n_cols + 256));
-    {
-        std::vector<int> at(2 * (size_t)wpc);
-        for (int64_t i = 0; i < wpc; i++) { at[(size_t)i] = (int)(i * T_pad); at[(size_t)(wpc + i)] = T; }
-        PCE_UPLOAD(c, b.wintab, win_tab);
-        PCE_UPLOAD(c, b.tailtab, tail_tab);
-        PCE_UPLOAD(c, b.atab, at);
-        PCE_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    // pad rows and the key columns no launch writes: cleared, so that no stale bits (a NaN) meet a zero probability
-    PCE_ZERO(op_t, c, b.img[0], (size_t)(wpc * img_e[0]) + 2048);
-    PCE_ZERO(op_t, c, b.attn, (size_t)M_max * d + 2048);
-    PCE_ZERO(op_t, c, b.vt, vt_elems);
-    const int *R0 = b.atab.as<int>(), *RL = R0 + wpc;
-    KernelTimer timer(c, PCE_K_W2V);
-    bool fit = true;                                             // every product's shape fits its kernel (w2v_gemm)
+    // equal chunks of equal windows share one range of t0, row0 and len: the largest chunk's, of which a shorter last chunk reads the front
+    for (int64_t i = 0; i < wpc; i++) { run.t0.push_back(Tl[0]); run.row0.push_back((int)(i * T_pad)); run.len.push_back(T); }
     for (int64_t w0 = 0; w0 < W; w0 += wpc) {
-        const int Wc = (int)std::min<int64_t>(wpc, W - w0);
-        const W2vChunk k{Wc, Tl, T, T_pad, vt_sp, b.wintab.as<int64_t>() + 3 * w0, nullptr, 0.0, R0, RL, (double)Wc * T, 4.0 * Wc * (double)T * T * d,
-                         b.tailtab.as<int64_t>() + 2 * w0, wf, cut, plan->star ? 1 : 0, n_cols};
-        PCE_TRY(w2v_forward_chunk(c, b, k, fit));
+        W2vChunk k = w2v_chunk(w0, (int)std::min<int64_t>(wpc, W - w0), 0, Tl);
+        k.tail_frames = wf;
+        k.wave_frames = (double)k.n_win * Tl[0]; k.frames = (double)k.n_win * T; k.attn_flops = 4.0 * k.n_win * (double)T * T * d;
+        run.chunks.push_back(k);
     }
+    PCE_TRY(w2v_run_chunks(c, b, run));
     b.n_clips = n;
     return PCE_OK;
 }
 
 // whisperX's emissions: the model on every segment alone (Aligners/ctc_emissions.segment_emissions), in chunks of segments of similar length
-// (pce_w2v_seg_plan.h).  A chunk is pce_w2v_run's chunk with per-chunk quantities: slots of the rows of its longest segment at every layer,
-// every segment's own frame counts in the tables of the waveform layer, the positional convolution, the attention and the tail (cut = 0).
-//
-// Rows behind a segment's own frames, and why nothing that is not finite sits in them although the slot stride changes from chunk to chunk.
-// A real row reads pad rows of its own slot in one place only: the attention multiplies the V^T columns of masked keys by probabilities that
-// are exactly zero, so those columns must be finite; everything else a real row reads is a real row of its slot (a convolution row t < Tl[i]
-// reads rows < Tl[i - 1], the positional convolution takes frames >= len as zeros, GEMM and LayerNorm rows are independent).  The pad rows are
-// finite by induction over the launches, as in pce_w2v_run.  Every buffer but three is written in all rows of all slots of a chunk before the
-// chunk reads it (img[1], fpln, h0, h, ln, qk, hidden, logits: GEMM, LayerNorm and positional-convolution launches cover M = slots x rows), so
-// what an earlier chunk or call left there under another stride is never read.  The three that a chunk writes in part are img[0] (the waveform
-// layer writes t < t0 of a slot of Tl[0] rows; the last convolution Tl[6] of T_pad rows), attn (the attention writes queries < len) and vt (the
-// V epilogue writes keys < T_pad of vt_sp columns).  Their other elements hold what an earlier chunk stored there under its own stride, and
-// that is always a value one of these kernels stored for some row -- a GELU or LayerNorm output, an attention output, a V projection, computed
-// from finite inputs -- or the zero of the clear below: the three are cleared over the largest extent any chunk of this call uses before the
-// first launch, so no element is read that this call or the clear did not write (a buffer that grew holds fresh memory).  Stale rows are
-// therefore finite under any stride, and a finite pad row gives finite pad rows downstream (no kernel divides by a row's own values but the
-// LayerNorms, whose eps > 0 keeps a constant row finite).
+// (pce_w2v_seg_plan.h): slots of the rows of a chunk's longest segment at every layer, every segment's own frame counts in the tables, cut = 0.
 int pce_w2v_run_segments(pce_ctx *c, const pce_w2v_segment *segs, int32_t n_seg, const pce_w2v_seg_plan *plan)
 {
     if (!c || !plan || n_seg < 0 || (n_seg && !segs)) return PCE_E_INVALID;
@@ -721,7 +711,7 @@ int pce_w2v_run_segments(pce_ctx *c, const pce_w2v_segment *segs, int32_t n_seg,
     if (c->rate != 16000) return pce_fail(c, PCE_E_INVALID, "wav2vec2 runs at 16000 Hz: the resident batch is at %d Hz (resample it first)", c->rate);
     if (plan->min_samples < 0 || plan->segments_per_chunk < 0) return pce_fail(c, PCE_E_INVALID, "bad segment plan (min_samples >= 0, segments_per_chunk >= 0)");
     const pce_w2v_dims &m = b.dims;
-    const int d = m.n_state, I = m.n_inter, V = m.n_vocab, Vp = b.Vp, C6 = m.conv_dim[6], n_cols = V + (plan->star ? 1 : 0);
+    const int d = m.n_state, I = m.n_inter, V = m.n_vocab, Vp = b.Vp, n_cols = V + (plan->star ? 1 : 0);
     const auto layer_frames = [&](int64_t samples, int *Tl) {
         int64_t t[7];
         w2v_seg_layer_frames(m.conv_kernel, m.conv_stride, 7, samples, t);
@@ -767,65 +757,26 @@ int pce_w2v_run_segments(pce_ctx *c, const pce_w2v_segment *segs, int32_t n_seg,
     const W2vSegPlan sp = w2v_seg_plan(
         samples, plan->segments_per_chunk, PCE_W2V_IMAGE_BUDGET, row_limit, [&](int64_t s) { int Tl[7]; layer_frames(s, Tl); return (int64_t)Tl[6]; },
         [&](int64_t s) { int Tl[7]; int64_t e[2]; layer_frames(s, Tl); return w2v_slot_bytes(m, Vp, Tl, e); });
-    // the tables, in the plan's order; per chunk the attention's {first row of slot i} then {frames of slot i}
-    std::vector<int64_t> win_tab, tail_tab;
-    std::vector<int> t0_tab, at;
-    int64_t img0 = 0, img1 = 0, M_max = 0, vt_max = 0;
+    // the run, in the plan's order: a chunk's slot is its first (longest) segment's rows at every layer
+    W2vRun run;
+    run.rows_total = rows_total; run.star = plan->star ? 1 : 0; run.n_cols = n_cols;
     for (const W2vSegChunk &ch : sp.chunks) {
         int Tl[7];
-        int64_t e[2];
         layer_frames(ch.samples, Tl);
-        w2v_slot_bytes(m, Vp, Tl, e);
-        const int64_t Wc = (int64_t)ch.count;
-        img0 = std::max(img0, Wc * e[0]); img1 = std::max(img1, Wc * e[1]);
-        M_max = std::max(M_max, Wc * ch.T_pad); vt_max = std::max(vt_max, Wc * d * (div_up(ch.T, 64) * 64));
-        for (size_t i = 0; i < ch.count; i++) at.push_back((int)((int64_t)i * ch.T_pad));
+        W2vChunk k = w2v_chunk((int64_t)ch.first, (int)ch.count, (int64_t)ch.first, Tl);
+        k.tail_frames = Tl[6];
         for (size_t i = 0; i < ch.count; i++) {
-            const int j = sp.order[ch.first + i];
+            const int j = sp.order[ch.first + i], nf = b.n_frames[(size_t)j];
             const pce_w2v_segment &sg = segs[j];
-            at.push_back(b.n_frames[(size_t)j]);
             // the waveform layer reads samples [0, end - begin) behind the segment's first and supplies the zeros up to min_samples itself
-            win_tab.push_back(c->clip_off[(size_t)sg.clip] + sg.begin); win_tab.push_back(0); win_tab.push_back(sg.end - sg.begin);
-            t0_tab.push_back(t0_of[(size_t)j]);
-            tail_tab.push_back(b.row_start[(size_t)j]); tail_tab.push_back(b.n_frames[(size_t)j]);
+            run.win.push_back(c->clip_off[(size_t)sg.clip] + sg.begin); run.win.push_back(0); run.win.push_back(sg.end - sg.begin);
+            run.tail.push_back(b.row_start[(size_t)j]); run.tail.push_back(nf);
+            run.t0.push_back(t0_of[(size_t)j]); run.row0.push_back((int)((int64_t)i * k.T_pad)); run.len.push_back(nf);
+            k.frames += nf; k.wave_frames += t0_of[(size_t)j]; k.attn_flops += 4.0 * (double)nf * nf * d;
         }
+        run.chunks.push_back(k);
     }
-    PCE_HIP(c, b.img[1].reserve(sizeof(op_t) * (size_t)img1 + 4096));
-    PCE_HIP(c, b.fpln.reserve(sizeof(op_t) * (size_t)M_max * C6 + 4096));
-    PCE_HIP(c, b.h0.reserve(sizeof(float) * (size_t)M_max * d));
-    PCE_HIP(c, b.h.reserve(sizeof(float) * (size_t)M_max * d));
-    PCE_HIP(c, b.ln.reserve(sizeof(op_t) * (size_t)M_max * d + 4096));
-    PCE_HIP(c, b.qk.reserve(sizeof(op_t) * (size_t)M_max * 2 * d + 4096));
-    PCE_HIP(c, b.hidden.reserve(sizeof(op_t) * (size_t)M_max * I + 4096));
-    PCE_HIP(c, b.logits.reserve(sizeof(float) * (size_t)M_max * Vp));
-    PCE_HIP(c, b.em.reserve(sizeof(float) * (size_t)rows_total * n_cols + 256));
-    PCE_UPLOAD(c, b.wintab, win_tab);
-    PCE_UPLOAD(c, b.tailtab, tail_tab);
-    PCE_UPLOAD(c, b.t0tab, t0_tab);
-    PCE_UPLOAD(c, b.atab, at);
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    // what the argument above needs cleared: the three buffers a chunk writes in part, over the largest extent any chunk uses
-    PCE_ZERO(op_t, c, b.img[0], (size_t)img0 + 2048);
-    PCE_ZERO(op_t, c, b.attn, (size_t)M_max * d + 2048);
-    PCE_ZERO(op_t, c, b.vt, (size_t)vt_max + 64);
-    KernelTimer timer(c, PCE_K_W2V);
-    bool fit = true;
-    size_t at0 = 0;
-    for (const W2vSegChunk &ch : sp.chunks) {
-        int Tl[7];
-        layer_frames(ch.samples, Tl);
-        const int Wc = (int)ch.count, T = (int)ch.T;
-        double frames = 0.0, wave_frames = 0.0, attn = 0.0;
-        for (size_t i = 0; i < ch.count; i++) {
-            const int j = sp.order[ch.first + i];
-            frames += b.n_frames[(size_t)j]; wave_frames += t0_of[(size_t)j]; attn += 4.0 * (double)b.n_frames[(size_t)j] * b.n_frames[(size_t)j] * d;
-        }
-        const int *R0 = b.atab.as<int>() + at0, *RL = R0 + Wc;
-        const W2vChunk k{Wc, Tl, T, (int)ch.T_pad, (int)div_up(T, 64) * 64, b.wintab.as<int64_t>() + 3 * ch.first, b.t0tab.as<int>() + ch.first, wave_frames, R0, RL,
-                         frames, attn, b.tailtab.as<int64_t>() + 2 * ch.first, T, 0, plan->star ? 1 : 0, n_cols};
-        PCE_TRY(w2v_forward_chunk(c, b, k, fit));
-        at0 += 2 * ch.count;
-    }
+    PCE_TRY(w2v_run_chunks(c, b, run));
     b.n_clips = n_seg;
     b.seg_plan[0] = (int64_t)sp.chunks.size(); b.seg_plan[1] = sp.rows_computed; b.seg_plan[2] = sp.rows_valid;
     return PCE_OK;
@@ -890,22 +841,7 @@ int pce_selftest_w2v_wave(pce_ctx *c, const int16_t *pcm, int64_t n_samples, int
     if (T0 > INT32_MAX / 2 || n_win > 65535) return pce_fail(c, PCE_E_LIMIT, "selftest waveform layer: too many frames or windows");
     std::vector<int64_t> tab;
     for (int64_t j = 0; j < n_win; j++) { tab.push_back(0); tab.push_back(j * window_samples - context_samples); tab.push_back(n_samples); }
-    DevBuf dp, dt, dw, db, dg, dbe, part, ss, dout;
-    const size_t n_out = (size_t)n_win * (size_t)T0 * C;
-    PCE_UPLOAD(c, dp, pcm, (size_t)n_samples); PCE_UPLOAD(c, dt, tab); PCE_UPLOAD(c, dw, w, (size_t)C * WV_K0);
-    if (bias) PCE_UPLOAD(c, db, bias, (size_t)C);
-    PCE_UPLOAD(c, dg, gamma, (size_t)C); PCE_UPLOAD(c, dbe, beta, (size_t)C);
-    PCE_ZERO(op_t, c, dout, n_out);
-    const int16_t *keep_pcm = c->d_pcm;                                          // (w2v_launch_wave reads the context's resident batch)
-    c->d_pcm = dp.as<int16_t>();
-    const int rc = w2v_launch_wave(c, feat_norm, dt.as<int64_t>(), (int)n_win, dw.as<float>(), bias ? db.as<float>() : nullptr, dg.as<float>(), dbe.as<float>(), C,
-                                   stride, (int)T0, part, ss, dout.as<op_t>());
-    c->d_pcm = keep_pcm;
-    if (rc) return rc;
-    PCE_HIP(c, hipGetLastError());
-    PCE_FETCH(c, out, dout.p, n_out);
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    return PCE_OK;
+    return w2v_selftest_wave(c, pcm, n_samples, tab, std::vector<int>((size_t)n_win, (int)T0), feat_norm, C, stride, w, bias, gamma, beta, out);
 }
 
 int pce_selftest_w2v_lngelu(pce_ctx *c, const uint16_t *x, int32_t rows, int32_t C, const float *w, const float *b, float eps, int32_t gelu, uint16_t *out)
@@ -927,21 +863,13 @@ int pce_selftest_w2v_posconv(pce_ctx *c, const float *x, int32_t n_win, int32_t 
 {
     if (!c || !x || !w || !bias || !out || n_win < 1 || n_win > 65535 || T < 1) return PCE_E_INVALID;
     if (!w2v_posconv_fits(d, groups) || d % 4) return pce_fail(c, PCE_E_LIMIT, "selftest positional convolution: d = %d in %d groups (16, 32, 48 or 64 columns per group)", d, groups);
-    PCE_HIP(c, hipSetDevice(c->device));
-    const size_t n = (size_t)n_win * T * d, nw = (size_t)d * PC_TAPS * (d / groups);
-    DevBuf dx, dw, db, dout;
-    PCE_UPLOAD(c, dx, x, n); PCE_UPLOAD(c, dw, w, nw); PCE_UPLOAD(c, db, bias, (size_t)d);
-    PCE_ZERO(float, c, dout, n);
-    w2v_launch_posconv(c, dx.as<float>(), dw.as<op_t>(), db.as<float>(), T, T, d, groups, n_win, dout.as<float>());
-    PCE_HIP(c, hipGetLastError());
-    PCE_FETCH(c, out, dout.p, n);
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    return PCE_OK;
+    const std::vector<int32_t> len((size_t)n_win, T);               // T frames in every window
+    return PCE_BUILD_NS::pce_selftest_w2v_posconv_segments(c, x, n_win, len.data(), T, d, groups, w, bias, out);
 }
 
-// ... and the two stages that take per-item frame counts, through pce_w2v_run_segments' launches.  _wave_segments: item i is samples
-// [seg[2 i], seg[2 i + 1]) of ONE clip, run on max(its samples, min_samples); out [n_seg][slot][C], slot = the longest item's frames; rows
-// behind an item's frames are left as the zeros out was cleared to.  _posconv_segments: n_win windows of len[i] <= T frames in slots of T rows.
+// ... and the two stages with unequal frame counts, as pce_w2v_run_segments launches them.  _wave_segments: item i is samples
+// [seg[2 i], seg[2 i + 1]) of ONE clip, run on max(its samples, min_samples); out as w2v_selftest_wave lays it out.  _posconv_segments: n_win
+// windows of len[i] <= T frames in slots of T rows.
 int pce_selftest_w2v_wave_segments(pce_ctx *c, const int16_t *pcm, int64_t n_samples, const int64_t *seg, int32_t n_seg, int32_t min_samples, int32_t feat_norm,
                                    int32_t C, int32_t stride, const float *w, const float *bias, const float *gamma, const float *beta, uint16_t *out)
 {
@@ -952,8 +880,6 @@ int pce_selftest_w2v_wave_segments(pce_ctx *c, const int16_t *pcm, int64_t n_sam
     PCE_HIP(c, hipSetDevice(c->device));
     std::vector<int64_t> tab;
     std::vector<int> t0;
-    int64_t slot = 0;
-    double frames = 0.0;
     for (int i = 0; i < n_seg; i++) {
         const int64_t b0 = seg[2 * i], e0 = seg[2 * i + 1];
         if (b0 < 0 || b0 > e0 || e0 > n_samples) return pce_fail(c, PCE_E_INVALID, "selftest waveform layer: segment %d outside the clip", i);
@@ -961,24 +887,8 @@ int pce_selftest_w2v_wave_segments(pce_ctx *c, const int16_t *pcm, int64_t n_sam
         if (T0 < 1 || T0 > INT32_MAX / 2) return pce_fail(c, PCE_E_LIMIT, "selftest waveform layer: segment %d gives %lld frames", i, (long long)T0);
         tab.push_back(b0); tab.push_back(0); tab.push_back(e0 - b0);
         t0.push_back((int)T0);
-        slot = std::max(slot, T0); frames += (double)T0;
     }
-    DevBuf dp, dt, d0, dw, db, dg, dbe, part, ss, dout;
-    const size_t n_out = (size_t)n_seg * (size_t)slot * C;
-    PCE_UPLOAD(c, dp, pcm, (size_t)n_samples); PCE_UPLOAD(c, dt, tab); PCE_UPLOAD(c, d0, t0); PCE_UPLOAD(c, dw, w, (size_t)C * WV_K0);
-    if (bias) PCE_UPLOAD(c, db, bias, (size_t)C);
-    PCE_UPLOAD(c, dg, gamma, (size_t)C); PCE_UPLOAD(c, dbe, beta, (size_t)C);
-    PCE_ZERO(op_t, c, dout, n_out);
-    const int16_t *keep_pcm = c->d_pcm;                                          // (w2v_launch_wave reads the context's resident batch)
-    c->d_pcm = dp.as<int16_t>();
-    const int rc = w2v_launch_wave(c, feat_norm, dt.as<int64_t>(), n_seg, dw.as<float>(), bias ? db.as<float>() : nullptr, dg.as<float>(), dbe.as<float>(), C, stride,
-                                   (int)slot, part, ss, dout.as<op_t>(), d0.as<int>(), frames);
-    c->d_pcm = keep_pcm;
-    if (rc) return rc;
-    PCE_HIP(c, hipGetLastError());
-    PCE_FETCH(c, out, dout.p, n_out);
-    PCE_HIP(c, hipStreamSynchronize(c->stream));
-    return PCE_OK;
+    return w2v_selftest_wave(c, pcm, n_samples, tab, t0, feat_norm, C, stride, w, bias, gamma, beta, out);
 }
 
 int pce_selftest_w2v_posconv_segments(pce_ctx *c, const float *x, int32_t n_win, const int32_t *len, int32_t T, int32_t d, int32_t groups, const uint16_t *w,
@@ -996,7 +906,7 @@ int pce_selftest_w2v_posconv_segments(pce_ctx *c, const float *x, int32_t n_win,
     DevBuf dx, dl, dw, db, dout;
     PCE_UPLOAD(c, dx, x, n); PCE_UPLOAD(c, dl, len, (size_t)n_win); PCE_UPLOAD(c, dw, w, nw); PCE_UPLOAD(c, db, bias, (size_t)d);
     PCE_ZERO(float, c, dout, n);
-    w2v_launch_posconv(c, dx.as<float>(), dw.as<op_t>(), db.as<float>(), T, T, d, groups, n_win, dout.as<float>(), dl.as<int>(), frames);
+    w2v_launch_posconv(c, dx.as<float>(), dw.as<op_t>(), db.as<float>(), dl.as<int>(), frames, T, d, groups, n_win, dout.as<float>());
     PCE_HIP(c, hipGetLastError());
     PCE_FETCH(c, out, dout.p, n);
     PCE_HIP(c, hipStreamSynchronize(c->stream));

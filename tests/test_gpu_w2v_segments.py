@@ -94,7 +94,7 @@ def test_ragged_positional_convolution_equals_each_window_alone(engine, cg, oper
         alone = engine.selftest_w2v_posconv(x[i:i + 1, :n], w, bias, groups)
         assert alone.shape == (1, n, d) and np.abs(alone[0] - x[i, :n]).max() > 0.05
         assert _same_bits(got[i, :n], alone[0]), (i, n)
-        assert _same_bits(got[i, n:], x[i, n:])                      # a row behind the frames: the input, as the uniform kernel's pad rows
+        assert _same_bits(got[i, n:], x[i, n:])                      # a row behind the frames: the input, as every pad row
     uniform = engine.selftest_w2v_posconv(x, w, bias, groups)
     assert _same_bits(got[-1], uniform[-1]) and not _same_bits(got[0, :1], uniform[0, :1])      # (a halo over the rows behind would give this)
 

@@ -3,7 +3,8 @@
 base (GroupNorm feature encoder, post-LN, 12 x 768) and large (LayerNorm feature encoder, pre-LN, 24 x 1024).  64 clips of 30 s at the default
 (30 s, 2 s) windows.  Before anything is timed the device's emissions of the first clips are compared with hf_emissions in fp32 on the same
 device (relative L2; more than 2 % ends the run).  HIP events via the engine's profiler; the torch path by wall clock around a synchronised call.
-Writes profiles/r19/w2v_rate.txt.  usage: w2v_rate.py [clips [runs [shapes]]]   (default 64 2 base,large)"""
+Writes profiles/r19/w2v_rate.txt, or the file named last (a comparison run keeps the record).
+usage: w2v_rate.py [clips [runs [shapes [out]]]]   (default 64 2 base,large profiles/r19/w2v_rate.txt)"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -36,6 +37,7 @@ def rel_l2(a, b):
 args = sys.argv[1:]
 n_clips, runs = int(args[0]) if args else 64, int(args[1]) if len(args) > 1 else 2
 shapes = args[2].split(",") if len(args) > 2 else ["base", "large"]
+out_path = os.path.abspath(args[3]) if len(args) > 3 else os.path.join(ROOT, "profiles", "r19", "w2v_rate.txt")
 out = []
 
 
@@ -90,6 +92,6 @@ for shape in shapes:
     del model
     torch.cuda.empty_cache()
 eng.close()
-os.makedirs(os.path.join(ROOT, "profiles", "r19"), exist_ok=True)
-with open(os.path.join(ROOT, "profiles", "r19", "w2v_rate.txt"), "w", encoding="utf-8") as fh:
+os.makedirs(os.path.dirname(out_path), exist_ok=True)
+with open(out_path, "w", encoding="utf-8") as fh:
     fh.write("\n".join(out) + "\n")

@@ -6,8 +6,8 @@ longer than its segment).  Before anything is timed the device's emissions of th
 the same device (relative L2; more than 2 % ends the run).  Then the two paths alternate, twice each, so the spread is seen: the engine's call
 between HIP events, five calls after a warm-up (a call returns when its emissions are complete); the torch path between HIP events too.
 Per batch: both times, rows computed over rows valid, chunks and timed launch groups, the per-kernel shares (pce_profile_get).
-Writes profiles/r21/w2v_segments_rate.txt.
-usage: w2v_segments_rate.py [segments [shapes]]   (default 256 base,large)"""
+Writes profiles/r21/w2v_segments_rate.txt, or the file named last (a comparison run keeps the record).
+usage: w2v_segments_rate.py [segments [shapes [out]]]   (default 256 base,large profiles/r21/w2v_segments_rate.txt)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -76,6 +76,7 @@ def timed(fn, calls):
 args = sys.argv[1:]
 n_seg = int(args[0]) if args else 256
 shapes = args[1].split(",") if len(args) > 1 else ["base", "large"]
+out_path = os.path.abspath(args[2]) if len(args) > 2 else os.path.join(ROOT, "profiles", "r21", "w2v_segments_rate.txt")
 out = []
 
 
@@ -131,6 +132,6 @@ for shape in shapes:
     del model, half
     torch.cuda.empty_cache()
 eng.close()
-os.makedirs(os.path.join(ROOT, "profiles", "r21"), exist_ok=True)
-with open(os.path.join(ROOT, "profiles", "r21", "w2v_segments_rate.txt"), "w", encoding="utf-8") as fh:
+os.makedirs(os.path.dirname(out_path), exist_ok=True)
+with open(out_path, "w", encoding="utf-8") as fh:
     fh.write("\n".join(out) + "\n")
