@@ -77,9 +77,12 @@ extern "C" {
  * sit behind minor 16's and in front of minor 15's: the numeric values of PCE_K_CTC .. PCE_K_SEQMATCH_ALIGN moved by three (pce_kernel_name follows);
  * 21 = pce_w2v_run_segments, pce_w2v_segments_plan, pce_w2v_segment_frames and pce_selftest_w2v_wave_segments / _posconv_segments (the wav2vec2 forward pass over
  * segments of unequal length, each alone and unpadded: whisperX's emissions, which pce_wx_align reads in place).  No kernel id: its launches
- * count under minor 16's four. */
+ * count under minor 16's four;
+ * 22 = pce_pyin_fetch_observations (the observation lists the last pce_pyin_run left for a clip) and pce_selftest_pyin_viterbi (k_pyin_viterbi on given
+ * observation lists through the run's own launch); out-of-band predecessors of the pYIN decoding tie on the rounded sum V + log(tiny), as the dense
+ * argmax does (before: on V, which could name another predecessor where two values lay within a few ulp). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 21
+#define PCE_API_MINOR 22
 
 typedef struct pce_ctx pce_ctx;
 
@@ -319,6 +322,19 @@ int pce_pyin_run(pce_ctx *ctx, const pce_pyin_plan *plan, const double *tables, 
 int pce_pyin_shape(pce_ctx *ctx, int32_t clip, int64_t *n_frames);
 /* states [n_frames] / voiced_prob [n_frames] / status (bit 0: a frame had more troughs than the engine keeps) may be NULL */
 int pce_pyin_fetch(pce_ctx *ctx, int32_t clip, int32_t *states, double *voiced_prob, int32_t *status);
+/* Test hooks of the two pYIN kernels.  An observation list is a row of PCE_PYIN_MAX_TROUGHS entries per frame, of which the first n[frame] count.
+ * pce_pyin_fetch_observations: what k_pyin_frames left for `clip` in the last pce_pyin_run, per frame: n, status (1: more troughs than the engine keeps),
+ * voiced_prob, log_unvoiced = log((1 - voiced_prob) / n_pitch_bins + tiny), and the voiced observations in trough (lag) order: bins [n_frames][512] and
+ * log_probs [n_frames][512] = log(p + tiny); entries at and beyond n[frame] keep the caller's values.  Every output may be NULL.
+ * pce_selftest_pyin_viterbi: k_pyin_viterbi on the caller's lists, through the launch of pce_pyin_run (same grid, block and LDS) and under its plan checks,
+ * in buffers of its own (a resident run is left as it is; no batch need be uploaded).  n_clips >= 1 clips, clip i holding frames frame_off[i] ..
+ * frame_off[i + 1] (frame_off[0] == 0, a clip may be empty); n, log_unvoiced, states_out [frames]; bins, log_probs [frames][512].  PCE_E_INVALID for
+ * n outside 0 .. 512, a bin outside 0 .. n_pitch_bins - 1 or twice in one frame.  states_out: the decoded state of every frame.  Since minor 22. */
+#define PCE_PYIN_MAX_TROUGHS 512
+int pce_pyin_fetch_observations(pce_ctx *ctx, int32_t clip, int32_t *n, int32_t *status, double *voiced_prob, double *log_unvoiced, int32_t *bins,
+                                double *log_probs);
+int pce_selftest_pyin_viterbi(pce_ctx *ctx, const pce_pyin_plan *plan, const double *tables, int64_t n_tables, int32_t n_clips, const int64_t *frame_off,
+                              const int32_t *n, const double *log_unvoiced, const int32_t *bins, const double *log_probs, int32_t *states_out);
 
 /* ---- CREPE pitch tracking ----------------------------------------------------
  * Replaces torchcrepe.predict(audio, sr, hop, fmin, fmax, model, batch_size=..., return_periodicity=True) of Code/Pipeline/evaluate_voice.ipynb

@@ -28,12 +28,13 @@ def frames_of(y, frame_length, hop_length):
     return yp[idx]
 
 
-def cmnd(y_frames, frame_length, win_length, min_period, max_period, exact=False):
+def cmnd(y_frames, frame_length, win_length, min_period, max_period, exact=False, info=None):
     """Cumulative mean normalised difference function, rows min_period..max_period.
     exact=False: librosa's arithmetic (FFT cross-correlation and cumulative-sum energies in the input precision).
     exact=True: the same terms (cross-correlation, window energies, the 1e-6 clamps) evaluated in float64, exact for
     int16-valued samples -- what the GPU kernel computes; the two differ by the float32 rounding noise of the FFT
-    and cumulative-sum route."""
+    and cumulative-sum route.  ``info`` (a dict, exact mode): receives ``acf_clamped`` [n_frames], whether the 1e-6 clamp zeroed
+    a nonzero cross-correlation at a lag whose window energy, like the first window's, it left alone."""
     if exact:
         # the same terms without rounding noise: cross-correlation and window energies in float64 (exact for
         # int16-valued samples), librosa's |v| < 1e-6 -> 0 clamps, then the same combination and normalisation
@@ -44,6 +45,8 @@ def cmnd(y_frames, frame_length, win_length, min_period, max_period, exact=False
             seg = yf[1 + tau:win_length + 1 + tau, :]
             acf[tau] = np.sum(base * seg, axis=0)
             energy[tau] = np.sum(seg * seg, axis=0)
+        if info is not None:
+            info["acf_clamped"] = np.any((acf != 0) & (np.abs(acf) < 1e-6) & (np.abs(energy) >= 1e-6) & (np.abs(energy[:1, :]) >= 1e-6), axis=0)
         acf[np.abs(acf) < 1e-6] = 0
         energy[np.abs(energy) < 1e-6] = 0
         yin = energy[:1, :] + energy - 2 * acf
@@ -118,12 +121,18 @@ def transition_local_triangle(n_states, width):
 
 def viterbi(prob, transition, p_init):
     """librosa.sequence.viterbi: prob (n_states, n_steps) -> states (n_steps)."""
-    n_states, n_steps = prob.shape
-    log_trans = np.log(transition + TINY64)
-    log_prob = np.log(prob.T + TINY64)
+    return viterbi_log(np.log(prob.T + TINY64), np.log(transition + TINY64), np.log(p_init + TINY64))
+
+
+def viterbi_log(log_obs, log_trans, log_p_init):
+    """``viterbi`` on logarithms as given: log_obs (n_steps, n_states), log_trans [k][j] (from k to j), log_p_init (n_states) -> states.
+    The additions are librosa's, in its order: log_obs[t][j] + (value[t - 1][k] + log_trans[k][j]), the predecessor by np.argmax (the
+    first maximum of the rounded sums), the last state by np.argmax."""
+    log_prob = np.asarray(log_obs, dtype=np.float64)
+    n_steps, n_states = log_prob.shape
     value = np.zeros((n_steps, n_states)); ptr = np.zeros((n_steps, n_states), dtype=np.int64)
-    value[0] = log_prob[0] + np.log(p_init + TINY64)
-    lt = log_trans.T.copy()
+    value[0] = log_prob[0] + log_p_init
+    lt = np.asarray(log_trans, dtype=np.float64).T.copy()
     for t in range(1, n_steps):
         trans_out = value[t - 1][None, :] + lt                         # [j][k]
         ptr[t] = np.argmax(trans_out, axis=1)
@@ -135,20 +144,8 @@ def viterbi(prob, transition, p_init):
     return states
 
 
-def pyin(y, sr, fmin=60.0, fmax=2000.0, frame_length=2048, hop_length=256, n_thresholds=100, boltzmann_parameter=2.0,
-         resolution=0.1, max_transition_rate=35.92, switch_prob=0.01, no_trough_prob=0.01, want_intermediate=False, exact=False):
-    """-> (f0 with nan for unvoiced, voiced_flag, voiced_prob)."""
-    y = np.asarray(y, dtype=np.float32)
-    win_length = frame_length // 2
-    y_frames = frames_of(y, frame_length, hop_length)
-    min_period = int(np.floor(sr / fmax))
-    max_period = min(int(np.ceil(sr / fmin)), frame_length - win_length - 1)
-    yin = cmnd(y_frames, frame_length, win_length, min_period, max_period, exact=exact)
-    shifts = parabolic_shifts(yin)
-    thresholds = np.linspace(0, 1, n_thresholds + 1)
-    beta_probs = np.diff(beta_cdf_2_18(thresholds))
-    n_bins_per_semitone = int(np.ceil(1.0 / resolution))
-    n_pitch_bins = int(np.floor(12 * n_bins_per_semitone * np.log2(fmax / fmin))) + 1
+def trough_probs(yin, thresholds, beta_probs, boltzmann_parameter, no_trough_prob):
+    """The per-frame loop of librosa's ``__pyin_helper``: the probability of every trough of every column of ``yin``."""
     n_frames = yin.shape[1]
     yin_probs = np.zeros_like(yin)
     for i in range(n_frames):
@@ -169,6 +166,72 @@ def pyin(y, sr, fmin=60.0, fmax=2000.0, frame_length=2048, hop_length=256, n_thr
         n_below_min = np.count_nonzero(~below[gmin, :])
         probs[gmin] += no_trough_prob * np.sum(beta_probs[:n_below_min])
         yin_probs[idx, i] = probs
+    return yin_probs
+
+
+def observations(y, sr, fmin=60.0, fmax=2000.0, frame_length=2048, hop_length=256, n_thresholds=100, boltzmann_parameter=2.0, resolution=0.1,
+                 no_trough_prob=0.01, exact=True, frames=None):
+    """What ``pyin`` scatters into its observation matrix, as lists: -> (obs, voiced_prob, info).  ``frames``: the frame indices to evaluate
+    (default: all), so that a long clip need not be evaluated whole.  ``obs[i]`` = (bins int64, probs float64) of frame ``frames[i]``: the
+    candidates that reach a voiced row, in trough (lag) order -- a candidate whose bin a later candidate of the frame also has is
+    overwritten by it and left out, and so is one clipped to ``bin == n_pitch_bins`` (numpy writes it into the first unvoiced row,
+    which ``pyin`` then overwrites).  ``voiced_prob`` [len(frames)]: the clipped sum of the kept probabilities in bin order, which is the
+    order in which numpy reduces the dense matrix over its rows.  ``info``: per frame ``raw`` (the unrounded bin index of every
+    candidate, kept or not), ``dropped`` (candidates with bin == n_pitch_bins), ``overwritten``, ``vp_sum`` (the sum before the clip),
+    and from ``cmnd`` ``acf_clamped``; ``n_pitch_bins``, ``min_period``, ``max_period``."""
+    y = np.asarray(y, dtype=np.float32)
+    win_length = frame_length // 2
+    y_frames = frames_of(y, frame_length, hop_length)
+    if frames is not None:
+        y_frames = y_frames[:, np.asarray(frames, dtype=np.int64)]
+    min_period = int(np.floor(sr / fmax))
+    max_period = min(int(np.ceil(sr / fmin)), frame_length - win_length - 1)
+    info = {}
+    yin = cmnd(y_frames, frame_length, win_length, min_period, max_period, exact=exact, info=info if exact else None)
+    shifts = parabolic_shifts(yin)
+    thresholds = np.linspace(0, 1, n_thresholds + 1)
+    beta_probs = np.diff(beta_cdf_2_18(thresholds))
+    n_bins_per_semitone = int(np.ceil(1.0 / resolution))
+    n_pitch_bins = int(np.floor(12 * n_bins_per_semitone * np.log2(fmax / fmin))) + 1
+    yin_probs = trough_probs(yin, thresholds, beta_probs, boltzmann_parameter, no_trough_prob)
+    obs, vps, raws, dropped, overwritten, vp_sums = [], [], [], [], [], []
+    for i in range(yin.shape[1]):
+        (idx,) = np.nonzero(yin_probs[:, i])
+        period = (min_period + idx) + shifts[idx, i]
+        raw = 12 * n_bins_per_semitone * np.log2((sr / period) / fmin)
+        b = np.clip(np.round(raw), 0, n_pitch_bins).astype(np.int64)
+        p = yin_probs[idx, i]
+        last = np.ones(len(b), dtype=bool)
+        for q in range(len(b)):
+            last[q] = not np.any(b[q + 1:] == b[q])
+        keep = last & (b < n_pitch_bins)
+        vp = 0.0
+        for q in np.argsort(b[keep], kind="stable"):
+            vp = vp + float(p[keep][q])
+        obs.append((b[keep], p[keep])); raws.append(raw); vp_sums.append(vp)
+        dropped.append(int(np.count_nonzero(b == n_pitch_bins))); overwritten.append(int(np.count_nonzero(~last & (b < n_pitch_bins))))
+        vps.append(min(max(vp, 0.0), 1.0))
+    info.update(raw=raws, dropped=np.array(dropped), overwritten=np.array(overwritten), vp_sum=np.array(vp_sums), n_pitch_bins=n_pitch_bins,
+                min_period=min_period, max_period=max_period)
+    return obs, np.array(vps), info
+
+
+def pyin(y, sr, fmin=60.0, fmax=2000.0, frame_length=2048, hop_length=256, n_thresholds=100, boltzmann_parameter=2.0,
+         resolution=0.1, max_transition_rate=35.92, switch_prob=0.01, no_trough_prob=0.01, want_intermediate=False, exact=False):
+    """-> (f0 with nan for unvoiced, voiced_flag, voiced_prob)."""
+    y = np.asarray(y, dtype=np.float32)
+    win_length = frame_length // 2
+    y_frames = frames_of(y, frame_length, hop_length)
+    min_period = int(np.floor(sr / fmax))
+    max_period = min(int(np.ceil(sr / fmin)), frame_length - win_length - 1)
+    yin = cmnd(y_frames, frame_length, win_length, min_period, max_period, exact=exact)
+    shifts = parabolic_shifts(yin)
+    thresholds = np.linspace(0, 1, n_thresholds + 1)
+    beta_probs = np.diff(beta_cdf_2_18(thresholds))
+    n_bins_per_semitone = int(np.ceil(1.0 / resolution))
+    n_pitch_bins = int(np.floor(12 * n_bins_per_semitone * np.log2(fmax / fmin))) + 1
+    n_frames = yin.shape[1]
+    yin_probs = trough_probs(yin, thresholds, beta_probs, boltzmann_parameter, no_trough_prob)
     yin_period, frame_index = np.nonzero(yin_probs)
     period = min_period + yin_period
     period = period + shifts[yin_period, frame_index]

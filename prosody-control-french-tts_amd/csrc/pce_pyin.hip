@@ -13,8 +13,9 @@
 //                Lane = lag (tau = lane + 64 g), one fp64 FMA per term.  Then, still per wavefront: troughs, the 100-threshold Boltzmann/beta trough probabilities (lane =
 //                trough, ballot/popcount ranks), parabolic refinement, pitch-bin observation list, voiced probability.
 // k_pyin_viterbi one workgroup per clip: the 2 x n_bins state HMM, exactly librosa's dense argmax (first maximum):
-//                in-band predecessors from the transition table, out-of-band ones (log(0 + tiny)) through prefix/suffix
-//                maxima of the previous column; back-pointers in HBM, back-tracking by one lane.
+//                in-band predecessors from the transition table, out-of-band ones through prefix/suffix maxima of the
+//                previous column's rounded sums V + log(0 + tiny), which is what the dense argmax compares (checked state for
+//                state, ties included, by tests/test_gpu_pyin_stages.py); back-pointers in HBM, back-tracking by one lane.
 // Host-computed tables (numpy, so that every constant has the bits the restatement uses): thresholds, beta
 // probabilities and their prefix sums, Boltzmann factors, log transition rows.
 #include "pce_internal.h"
@@ -249,8 +250,8 @@ __global__ __launch_bounds__(VT_THREADS) void k_pyin_viterbi(const int64_t *__re
     const int nb = P.n_bins, half = P.half;
     double *V = lds;                       // [2][nb] previous column
     double *lo = V + 2 * nb;               // [nb] log observation of the voiced states of the current frame
-    double *pmv = lo + nb;                 // prefix maxima value [2][nb]
-    double *smv = pmv + 2 * nb;            // suffix maxima value [2][nb]
+    double *pmv = lo + nb;                 // prefix maxima of V + log(tiny) [2][nb]
+    double *smv = pmv + 2 * nb;            // suffix maxima of V + log(tiny) [2][nb]
     int *pmi = reinterpret_cast<int *>(smv + 2 * nb);   // [2][nb]
     int *smi = pmi + 2 * nb;               // [2][nb]
     __shared__ MaxIdx wtot[2][VT_THREADS / 64];
@@ -274,10 +275,12 @@ __global__ __launch_bounds__(VT_THREADS) void k_pyin_viterbi(const int64_t *__re
         if (t == 0) {
             if (j < nb) { nv0 = lo[j] + P.log_pinit; nv1 = H.log_unvoiced + P.log_pinit; }
         } else {
-            // ---- prefix / suffix maxima (first index on ties) of both halves of the previous column
+            // ---- prefix / suffix maxima (first index on ties) of both halves of the previous column, taken over the ROUNDED sums
+            //      fl(V[k] + log(tiny)) the dense evaluation compares: |V| is a few units and the sum about -716, so values of V a few ulp apart
+            //      give the same sum and the first of them is the arg-max (a maximum over V itself would name the later, larger one)
 #pragma unroll
             for (int v = 0; v < 2; v++) {
-                MaxIdx a; a.v = j < nb ? V[v * nb + j] : -1e308; a.i = j < nb ? j : 0x7fffffff;
+                MaxIdx a; a.v = j < nb ? V[v * nb + j] + P.c0 : -1e308; a.i = j < nb ? j : 0x7fffffff;
                 MaxIdx p = a;
                 for (int o = 1; o < 64; o <<= 1) {
                     MaxIdx q; q.v = shfl_up_f64(p.v, o); q.i = __shfl_up(p.i, o, 64);
@@ -299,7 +302,7 @@ __global__ __launch_bounds__(VT_THREADS) void k_pyin_viterbi(const int64_t *__re
 #pragma unroll
             for (int v = 0; v < 2; v++) {                          // suffix: scan the reversed order
                 const int jr = nb - 1 - j;                          // this thread's element in reversed order
-                MaxIdx a; a.v = j < nb ? V[v * nb + jr] : -1e308; a.i = j < nb ? jr : 0x7fffffff;
+                MaxIdx a; a.v = j < nb ? V[v * nb + jr] + P.c0 : -1e308; a.i = j < nb ? jr : 0x7fffffff;
                 MaxIdx p = a;
                 for (int o = 1; o < 64; o <<= 1) {
                     MaxIdx q; q.v = shfl_up_f64(p.v, o); q.i = __shfl_up(p.i, o, 64);
@@ -326,8 +329,8 @@ __global__ __launch_bounds__(VT_THREADS) void k_pyin_viterbi(const int64_t *__re
 #pragma unroll
                 for (int v = 0; v < 2; v++) {                      // predecessor half v
                     const double *Vv = V + v * nb;
-                    if (klo > 0) {                                  // out of band below: log(0 + tiny)
-                        const double c = pmv[v * nb + klo - 1] + P.c0; const int ci = v * nb + pmi[v * nb + klo - 1];
+                    if (klo > 0) {                                  // out of band below: log(0 + tiny), already in the scanned sums
+                        const double c = pmv[v * nb + klo - 1]; const int ci = v * nb + pmi[v * nb + klo - 1];
                         if (c > b0) { b0 = c; i0 = ci; }
                         if (c > b1) { b1 = c; i1 = ci; }
                     }
@@ -349,7 +352,7 @@ __global__ __launch_bounds__(VT_THREADS) void k_pyin_viterbi(const int64_t *__re
                         if (ok && c1v > b1) { b1 = c1v; i1 = v * nb + k; }
                     }
                     if (khi < nb - 1) {
-                        const double c = smv[v * nb + khi + 1] + P.c0; const int ci = v * nb + smi[v * nb + khi + 1];
+                        const double c = smv[v * nb + khi + 1]; const int ci = v * nb + smi[v * nb + khi + 1];
                         if (c > b0) { b0 = c; i0 = ci; }
                         if (c > b1) { b1 = c; i1 = ci; }
                     }
@@ -373,15 +376,10 @@ __global__ __launch_bounds__(VT_THREADS) void k_pyin_viterbi(const int64_t *__re
     }
 }
 
-} // namespace
-
-extern "C" {
-
-int pce_pyin_run(pce_ctx *c, const pce_pyin_plan *plan, const double *tables, int64_t n_tables)
+// What pce_pyin_run and pce_selftest_pyin_viterbi check alike: the plan against the kernels' limits, the table blob's length against the plan.
+int pyin_plan_check(pce_ctx *c, const pce_pyin_plan *plan, int64_t n_tables, PyPlan &P)
 {
-    if (!c || !plan || !tables) return PCE_E_INVALID;
-    if (!c->d_pcm) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
-    PyPlan P{};
+    P = PyPlan{};
     P.hop = plan->hop_length; P.min_period = plan->min_period; P.max_period = plan->max_period;
     P.n_tau = P.max_period - P.min_period + 1; P.n_bins = plan->n_pitch_bins; P.half = plan->trans_width / 2; P.n_thr = plan->n_thresholds;
     P.sr = plan->sr; P.fmin = plan->fmin; P.bins_per_octave = plan->bins_per_octave; P.no_trough_prob = plan->no_trough_prob;
@@ -395,6 +393,32 @@ int pce_pyin_run(pce_ctx *c, const pce_pyin_plan *plan, const double *tables, in
     P.o_bexp = P.o_bfac + PY_MAXTR + 1; P.o_lt_same = (P.o_bexp + PY_MAXTR + 1 + 1) & ~1; P.o_lt_sw = P.o_lt_same + W * P.n_bins;   // (16-byte aligned pairs)
     const int64_t expect = (int64_t)P.o_lt_sw + (int64_t)W * P.n_bins;
     if (n_tables != expect) return pce_fail(c, PCE_E_INVALID, "pYIN table blob has %lld doubles, expected %lld", (long long)n_tables, (long long)expect);
+    return PCE_OK;
+}
+
+// The one launch of k_pyin_viterbi: one workgroup per clip, the previous column and its scans in dynamic LDS.
+int pyin_launch_viterbi(pce_ctx *c, const PyPlan &P, int32_t n_clips, const int64_t *d_frame_off, const double *d_tab, const PyObs *d_hdr,
+                        const short *d_bin, const double *d_lp, unsigned short *d_ptr, int *d_states)
+{
+    const size_t lds = sizeof(double) * (size_t)(2 * P.n_bins + P.n_bins + 4 * P.n_bins) + sizeof(int) * (size_t)(4 * P.n_bins) + 64;
+    PCE_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_pyin_viterbi), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    KernelTimer t(c, PCE_K_PYIN_VITERBI);
+    hipLaunchKernelGGL(k_pyin_viterbi, dim3((unsigned)n_clips), dim3(VT_THREADS), lds, c->stream, d_frame_off, P, d_tab, d_hdr, d_bin, d_lp, d_ptr, d_states);
+    return PCE_OK;
+}
+
+static_assert(PY_MAXTR == PCE_PYIN_MAX_TROUGHS, "include/pce.h states the row width of the observation lists");
+
+} // namespace
+
+extern "C" {
+
+int pce_pyin_run(pce_ctx *c, const pce_pyin_plan *plan, const double *tables, int64_t n_tables)
+{
+    if (!c || !plan || !tables) return PCE_E_INVALID;
+    if (!c->d_pcm) return pce_fail(c, PCE_E_STATE, "no batch uploaded");
+    PyPlan P;
+    PCE_TRY(pyin_plan_check(c, plan, n_tables, P));
     PCE_HIP(c, hipSetDevice(c->device));
     c->py_ran = false;
     c->py_off.assign((size_t)c->n_clips + 1, 0);
@@ -432,14 +456,8 @@ int pce_pyin_run(pce_ctx *c, const pce_pyin_plan *plan, const double *tables, in
         else if (P.n_groups == 12) launch(k_pyin_frames<12>);
         else launch(k_pyin_frames<0>);
     }
-    {
-        const size_t lds = sizeof(double) * (size_t)(2 * P.n_bins + P.n_bins + 4 * P.n_bins) + sizeof(int) * (size_t)(4 * P.n_bins) + 64;
-        PCE_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_pyin_viterbi), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        KernelTimer t(c, PCE_K_PYIN_VITERBI);
-        hipLaunchKernelGGL(k_pyin_viterbi, dim3((unsigned)c->n_clips), dim3(VT_THREADS), lds, c->stream, c->py_doff.as<int64_t>(), P,
-                           c->py_tab.as<double>(), c->py_hdr.as<PyObs>(), c->py_bin.as<short>(), c->py_lp.as<double>(),
-                           c->py_ptr.as<unsigned short>(), c->py_states.as<int>());
-    }
+    PCE_TRY(pyin_launch_viterbi(c, P, c->n_clips, c->py_doff.as<int64_t>(), c->py_tab.as<double>(), c->py_hdr.as<PyObs>(), c->py_bin.as<short>(),
+                                c->py_lp.as<double>(), c->py_ptr.as<unsigned short>(), c->py_states.as<int>()));
     PCE_HIP(c, hipGetLastError());
     PCE_HIP(c, hipStreamSynchronize(c->stream));                 // `tables` and py_off were sources of asynchronous copies
     c->py_ran = true;
@@ -470,6 +488,80 @@ int pce_pyin_fetch(pce_ctx *c, int32_t clip, int32_t *states, double *voiced_pro
     int st = 0;
     for (int64_t i = 0; i < nf; i++) { if (voiced_prob) voiced_prob[i] = h[(size_t)i].voiced_prob; st |= h[(size_t)i].status; }
     if (status) *status = st;
+    return PCE_OK;
+}
+
+int pce_pyin_fetch_observations(pce_ctx *c, int32_t clip, int32_t *n, int32_t *status, double *voiced_prob, double *log_unvoiced, int32_t *bins,
+                                double *log_probs)
+{
+    if (!c) return PCE_E_INVALID;
+    if (!c->py_ran) return pce_fail(c, PCE_E_STATE, "pce_pyin_fetch_observations before pce_pyin_run");
+    if (clip < 0 || clip >= c->n_clips) return pce_fail(c, PCE_E_INVALID, "clip out of range");
+    PCE_HIP(c, hipSetDevice(c->device));
+    const int64_t f0 = c->py_off[(size_t)clip], nf = c->py_off[(size_t)clip + 1] - f0;
+    std::vector<PyObs> h((size_t)nf);
+    std::vector<short> b(bins ? (size_t)nf * PY_MAXTR : 0);
+    std::vector<double> lp(log_probs ? (size_t)nf * PY_MAXTR : 0);
+    PCE_FETCH(c, h.data(), c->py_hdr.as<PyObs>() + f0, (size_t)nf);
+    if (bins) PCE_FETCH(c, b.data(), c->py_bin.as<short>() + (size_t)f0 * PY_MAXTR, b.size());
+    if (log_probs) PCE_FETCH(c, lp.data(), c->py_lp.as<double>() + (size_t)f0 * PY_MAXTR, lp.size());
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i < nf; i++) {
+        const PyObs &H = h[(size_t)i];
+        if (H.n < 0 || H.n > PY_MAXTR) return pce_fail(c, PCE_E_STATE, "pYIN frame %lld holds %d observations", (long long)i, H.n);
+        if (n) n[i] = H.n;
+        if (status) status[i] = H.status;
+        if (voiced_prob) voiced_prob[i] = H.voiced_prob;
+        if (log_unvoiced) log_unvoiced[i] = H.log_unvoiced;
+        for (int q = 0; q < H.n; q++) {
+            if (bins) bins[(size_t)i * PY_MAXTR + q] = b[(size_t)i * PY_MAXTR + q];
+            if (log_probs) log_probs[(size_t)i * PY_MAXTR + q] = lp[(size_t)i * PY_MAXTR + q];
+        }
+    }
+    return PCE_OK;
+}
+
+int pce_selftest_pyin_viterbi(pce_ctx *c, const pce_pyin_plan *plan, const double *tables, int64_t n_tables, int32_t n_clips, const int64_t *frame_off,
+                              const int32_t *n, const double *log_unvoiced, const int32_t *bins, const double *log_probs, int32_t *states_out)
+{
+    if (!c || !plan || !tables || !frame_off || !n || !log_unvoiced || !bins || !log_probs || !states_out) return PCE_E_INVALID;
+    PyPlan P;
+    PCE_TRY(pyin_plan_check(c, plan, n_tables, P));
+    if (n_clips < 1 || n_clips > 65535 || frame_off[0] != 0) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pyin_viterbi: 1 .. 65535 clips, frame_off[0] == 0");
+    for (int32_t i = 0; i < n_clips; i++)
+        if (frame_off[i + 1] < frame_off[i]) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pyin_viterbi: frame_off decreases at clip %d", i);
+    const int64_t total = frame_off[n_clips];
+    if (total < 1 || total > (int64_t)1 << 24) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pyin_viterbi: 1 .. 2^24 frames");
+    // a frame's observations: at most PY_MAXTR, every bin a voiced state, no bin twice (the kernel scatters them without an order)
+    std::vector<PyObs> h((size_t)total);
+    std::vector<short> b((size_t)total * PY_MAXTR, 0);
+    std::vector<unsigned char> seen((size_t)P.n_bins);
+    for (int64_t f = 0; f < total; f++) {
+        if (n[f] < 0 || n[f] > PY_MAXTR) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pyin_viterbi: frame %lld has %d observations", (long long)f, n[f]);
+        std::fill(seen.begin(), seen.end(), 0);
+        for (int q = 0; q < n[f]; q++) {
+            const int32_t v = bins[(size_t)f * PY_MAXTR + q];
+            if (v < 0 || v >= P.n_bins || seen[(size_t)v])
+                return pce_fail(c, PCE_E_INVALID, "pce_selftest_pyin_viterbi: frame %lld, observation %d: bin %d outside 0 .. %d or repeated", (long long)f, q, v, P.n_bins - 1);
+            seen[(size_t)v] = 1;
+            b[(size_t)f * PY_MAXTR + q] = (short)v;
+        }
+        h[(size_t)f] = PyObs{n[f], 0, 0.0, log_unvoiced[f]};
+    }
+    PCE_HIP(c, hipSetDevice(c->device));
+    DevBuf d_off, d_tab, d_hdr, d_bin, d_lp, d_ptr, d_states;                 // its own: what a pce_pyin_run left stays
+    PCE_UPLOAD(c, d_off, frame_off, (size_t)n_clips + 1);
+    PCE_UPLOAD(c, d_tab, tables, (size_t)n_tables);
+    PCE_UPLOAD(c, d_hdr, h);
+    PCE_UPLOAD(c, d_bin, b);
+    PCE_UPLOAD(c, d_lp, log_probs, (size_t)total * PY_MAXTR);
+    PCE_HIP(c, d_ptr.reserve(sizeof(unsigned short) * (size_t)total * (size_t)(2 * P.n_bins)));
+    PCE_ZERO(int, c, d_states, (size_t)total);
+    PCE_TRY(pyin_launch_viterbi(c, P, n_clips, d_off.as<int64_t>(), d_tab.as<double>(), d_hdr.as<PyObs>(), d_bin.as<short>(), d_lp.as<double>(),
+                                d_ptr.as<unsigned short>(), d_states.as<int>()));
+    PCE_HIP(c, hipGetLastError());
+    PCE_FETCH(c, states_out, d_states.p, (size_t)total);
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
 

@@ -22,6 +22,9 @@ class PceError(RuntimeError):
     pass
 
 
+PYIN_MAX_TROUGHS = 512       # PCE_PYIN_MAX_TROUGHS of include/pce.h: the row width of pYIN's observation lists
+
+
 def native_library_path() -> str:
     """The library this process binds: ``libpce.so`` beside this file, or the file ``PCE_LIBRARY`` names (laboratory builds are
     selected this way -- ``tools/ab_*.sh`` -- instead of being copied over the product's library)."""
@@ -259,6 +262,8 @@ SIGNATURES = {
     "pce_pyin_run": [_vp, _vp, _vp, _i64],
     "pce_pyin_shape": [_vp, _i32, C.POINTER(_i64)],
     "pce_pyin_fetch": [_vp, _i32, _vp, _vp, C.POINTER(_i32)],
+    "pce_pyin_fetch_observations": [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pce_selftest_pyin_viterbi": [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
     # CREPE pitch tracking
     "pce_crepe_load": [_vp, C.POINTER(CrepeDims), _vp, _i64],
     "pce_crepe_run": [_vp, C.POINTER(CrepePlan)],
@@ -1307,6 +1312,31 @@ class ProsodyEngine:
         st = np.zeros(nf.value, dtype=np.int32); vp = np.zeros(nf.value, dtype=np.float64); status = C.c_int32()
         self._check(self._lib.pce_pyin_fetch(self._ctx, int(clip), st.ctypes.data, vp.ctypes.data, C.byref(status)))
         return st, vp, status.value
+
+    def pyin_fetch_observations(self, clip: int):
+        """``pce_pyin_fetch_observations`` (test hook): what ``k_pyin_frames`` left for ``clip`` -> dict of ``n``, ``status`` int32 [n_frames],
+        ``voiced_prob``, ``log_unvoiced`` float64 [n_frames], ``bins`` int32 and ``log_probs`` float64 [n_frames, 512] (entries beyond ``n``: -1 / NaN)."""
+        nf = C.c_int64()
+        self._check(self._lib.pce_pyin_shape(self._ctx, int(clip), C.byref(nf)))
+        o = {"n": np.zeros(nf.value, np.int32), "status": np.zeros(nf.value, np.int32), "voiced_prob": np.zeros(nf.value), "log_unvoiced": np.zeros(nf.value),
+             "bins": np.full((nf.value, PYIN_MAX_TROUGHS), -1, np.int32), "log_probs": np.full((nf.value, PYIN_MAX_TROUGHS), np.nan)}
+        self._check(self._lib.pce_pyin_fetch_observations(self._ctx, int(clip), *(o[k].ctypes.data for k in ("n", "status", "voiced_prob", "log_unvoiced", "bins", "log_probs"))))
+        return o
+
+    def selftest_pyin_viterbi(self, plan, tables, frame_off, n, log_unvoiced, bins, log_probs):
+        """``pce_selftest_pyin_viterbi`` (test hook): ``k_pyin_viterbi`` on given observation lists (rows of 512 entries, the first ``n`` count) of
+        clips ``frame_off[i] .. frame_off[i + 1]`` -> states int32 [frames]."""
+        t = np.ascontiguousarray(tables, dtype=np.float64)
+        off = np.ascontiguousarray(frame_off, dtype=np.int64); n = np.ascontiguousarray(n, dtype=np.int32)
+        lu = np.ascontiguousarray(log_unvoiced, dtype=np.float64)
+        b = np.ascontiguousarray(bins, dtype=np.int32); lp = np.ascontiguousarray(log_probs, dtype=np.float64)
+        total = int(off[-1]) if off.size else 0
+        if off.ndim != 1 or off.size < 2 or n.shape != (total,) or lu.shape != (total,) or b.shape != (total, PYIN_MAX_TROUGHS) or lp.shape != b.shape:
+            raise ValueError("frame_off [clips + 1]; n, log_unvoiced [frames]; bins, log_probs [frames, 512]")
+        states = np.zeros(total, dtype=np.int32)
+        self._check(self._lib.pce_selftest_pyin_viterbi(self._ctx, C.byref(plan), t.ctypes.data, t.size, off.size - 1, off.ctypes.data, n.ctypes.data,
+                                                        lu.ctypes.data, b.ctypes.data, lp.ctypes.data, states.ctypes.data))
+        return states
 
     # ---------------------------------------------------------------- CREPE pitch tracking (evaluate_voice's F0 RMSE)
     def crepe_load(self, capacity_or_dims, weights):
