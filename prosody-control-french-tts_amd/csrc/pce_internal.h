@@ -8,6 +8,7 @@
 #include <vector>
 #include "pce.h"
 #include "pce_sweep_plan.h"
+#include "pce_pitch_plan.h"
 
 // A kernel marked PCE_NO_PK_F32 is compiled without packed fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32).  Why (round 6,
 // profiles/r06/multiprocess_glitch.txt, tools/lab/pk_victim.hip): on the MI355X boxes of this pool a packed fp32 instruction whose low result lane
@@ -115,7 +116,9 @@ struct pce_ctx {
 
     // pitch
     DevBuf pi_meta, pi_window, pi_windowR, pi_work, pi_cand, pi_gpeak, pi_psi, pi_f0, pi_strength, pi_summary, pi_peakwork, pi_acc, pi_rr, pi_items, pi_tw, pi_dl, pi_runs, pi_fslice, pi_blob;
-    double pi_P[32] = {0};          // PiParams image
+    PiParams pi_P = {};                 // what the kernels take by value (pce_pitch_plan.h)
+    PitchFramesLaunch pi_launch = {};   // the k_pitch_frames launch planned with it
+    PitchSizes pi_sizes = {};           // ... and the list capacities and buffer sizes
     int64_t pi_n_work = 0, pi_n_energy_work = 0;
     int pi_np2 = 1;
     bool pi_long_slices = false;    // some slice has more frames than the in-LDS median sort holds (k_pitch_median_long takes those)
@@ -296,13 +299,11 @@ size_t pce_pitch_stage_bytes(const pce_ctx *c);
 int pce_pitch_stage_enqueue(pce_ctx *c, void *pinned, hipStream_t on = nullptr);
 void pce_pitch_stage_unpack(const void *pinned, int32_t n, pce_pitch_summary *out);
 
-// Host-side copy of the sizes Praat derives before its frame loop (see pce_pitch.hip).
-struct PitchPlan {
-    double dt, t1, ceiling, dt_window;
-    int64_t n_frames, nsamp_period, halfnsamp_period, nsamp_window, halfnsamp_window;
-    int64_t maximum_lag, brent_ixmax, max_candidates;
-};
-int pitch_plan_make(int64_t nx, double dx, double x1, const pce_pitch_params *p, PitchPlan *pl);
+// the integer pass over slices (pce_energy.hip) as the pitch and LUFS paths run it into buffers of their own: plan the work list, launch, and where
+// a slice's sum / extrema lie in out_buf
+int pce_energy_plan(pce_ctx *c, const pce_slice *slices, int32_t n, DevBuf &work_buf, DevBuf &out_buf, int64_t *n_work);
+int pce_energy_launch(pce_ctx *c, int32_t n, int32_t loud_thr, int64_t n_work, DevBuf &work_buf, DevBuf &out_buf, hipStream_t on = nullptr);
+void pce_energy_range_ptrs(const DevBuf &out_buf, size_t *stride_bytes, const long long **sum, const int **m_hi, const int **m_lo);
 
 void pce_whisper_free(pce_ctx *c);
 static inline int64_t div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -23,8 +23,6 @@
 #include <algorithm>
 #include <cmath>
 
-int pce_energy_plan(pce_ctx *c, const pce_slice *slices, int32_t n, DevBuf &work_buf, DevBuf &out_buf, int64_t *n_work);
-int pce_energy_launch(pce_ctx *c, int32_t n, int32_t loud_thr, int64_t n_work, DevBuf &work_buf, DevBuf &out_buf, hipStream_t on = nullptr);
 const int *pce_energy_peak_ptr(const DevBuf &out_buf, size_t *stride_bytes);
 
 namespace {

@@ -189,6 +189,25 @@ def test_pitch_other_rates_match_oracle(engine, rate, floor):
         assert np.max(np.abs(sg[v] - want["strength"][v])) <= 1e-6
 
 
+@pytest.mark.parametrize("rate,floor", [(8000, 150.0), (44100, 75.0), (48000, 50.0)])
+def test_pitch_stockham_forms_match_oracle(engine, rate, floor):
+    """The Stockham form of k_pitch_frames (MODE 0) at 4, 2 and 1 wavefronts per workgroup: N = 256 at 8 kHz / 150 Hz, N = 4096 at
+    44.1 kHz / 75 Hz (72 KB of LDS per wavefront), N = 8192 at 48 kHz / 50 Hz (144 KB); tests/host/pitch_plan_main.cpp holds the plan to
+    these three.  Same assertions and tolerances as the other rates."""
+    from prosody_control_french_tts_amd import synth
+    clips = [synth.synth_clip(i, 1.0, rate) for i in range(2)]
+    engine.upload(clips, rate)
+    res = engine.pitch(engine.whole_clip_slices(), E.PitchParams.praat(floor, 600.0), want_f0=True, want_strength=True)
+    off = res["frame_offsets"]
+    for i, c in enumerate(clips):
+        want = O.pitch_ac(c.astype(np.float64) / 32768.0, 1.0 / rate, 0.5 / rate, O.praat_params(floor, 600.0))
+        f0 = res["f0"][off[i]:off[i + 1]]; sg = res["strength"][off[i]:off[i + 1]]
+        v = want["f0"] > 0
+        assert len(f0) == len(want["f0"]) and np.array_equal(f0 > 0, v) and v.sum() > 10
+        assert np.max(np.abs(f0[v] - want["f0"][v]) / want["f0"][v]) <= 1e-6
+        assert np.max(np.abs(sg[v] - want["strength"][v])) <= 1e-6
+
+
 @pytest.mark.parametrize("rate", [48000, 16000])
 def test_lufs_ebu_tech_3341_cases_on_the_gpu(engine, rate):
     """The five EBU Tech 3341 integrated-loudness cases (tests/test_oracle_kat.py: schedule, published targets and their

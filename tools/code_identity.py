@@ -4,12 +4,19 @@ For a change that is meant to leave the device code alone (a host-side refactor)
 flags and compare: the set of kernel names per code object, each kernel's AMDGPU metadata (register counts, LDS and scratch sizes, spills, kernarg
 size, workgroup size) and the ``llvm-objdump -d`` text of every function with addresses and encodings stripped.  Equality only: nothing is searched for.
 
-usage: python tools/code_identity.py A B        one line per difference, else "N kernels, 0 differences"; exit code 1 when anything differs
+usage: python tools/code_identity.py [--pair-demangled] A B
+    one line per difference, else "N kernels, 0 differences"; exit code 1 when anything differs
+
+Kernels and functions are paired by their mangled names.  --pair-demangled pairs them by the demangled name (llvm-cxxfilt of the same LLVM
+directory; an installation without one: c++filt, which implements the same Itanium rules) with every
+"(anonymous namespace)::" removed instead: for a change that moves a kernel, or a type in its signature, into or out of an anonymous namespace,
+which renames the symbol and nothing else.  Two symbols of one code object with the same such name are an error (exit code 2), not a guess.
 """
 from __future__ import annotations
 
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -36,7 +43,7 @@ def _metadata(notes: str) -> dict:
 
 
 def _functions(disasm: str) -> dict:
-    """{symbol: [instruction text]} with addresses, encodings and the disassembler's comments stripped."""
+    """{symbol: [instruction text]} with addresses, encodings, the disassembler's comments and trailing fill stripped."""
     parts = re.split(r"\n[0-9a-f]+ <([^>]+)>:\n", disasm)
     out = {}
     for i in range(1, len(parts), 2):
@@ -45,6 +52,9 @@ def _functions(disasm: str) -> dict:
             line = line.split("//", 1)[0].strip()
             if line and not line.startswith("Disassembly of section"):
                 body.append(re.sub(r"\s+", " ", line))
+        # what follows the last symbol of the section is the section's fill, not the function's code (how much of it there is depends on the link)
+        while body and body[-1] in ("s_nop 0", "s_code_end"):
+            body.pop()
         out[parts[i]] = body
     return out
 
@@ -62,9 +72,48 @@ def describe(path: str):
     return out
 
 
-def compare(path_a: str, path_b: str):
+def _die(message: str):
+    print(message, file=sys.stderr)
+    sys.exit(2)
+
+
+def _demangled_keys(names, where: str) -> dict:
+    """{mangled: demangled with "(anonymous namespace)::" removed}; exit code 2 when two of ``names`` share a key."""
+    names = sorted(names)
+    if not names:
+        return {}
+    filt = os.path.join(LLVM_BIN, "llvm-cxxfilt")
+    if not os.path.exists(filt):
+        filt = shutil.which("c++filt")
+    if not filt:
+        _die(f"--pair-demangled: neither {os.path.join(LLVM_BIN, 'llvm-cxxfilt')} nor c++filt is installed")
+    out = subprocess.run([filt], input="\n".join(names) + "\n", capture_output=True, text=True, check=True).stdout.splitlines()
+    if len(out) != len(names):
+        _die(f"{where}: llvm-cxxfilt answered {len(out)} lines for {len(names)} names")
+    keys, seen = {}, {}
+    for name, dem in zip(names, out):
+        key = dem.replace("(anonymous namespace)::", "")
+        if key in seen:
+            _die(f"{where}: {seen[key]} and {name} both pair as {key}")
+        seen[key] = name
+        keys[name] = key
+    return keys
+
+
+def _rekey(objects, path: str):
+    """describe()'s result with every kernel and function under its pairing key."""
+    out = []
+    for k, (meta, funcs) in enumerate(objects):
+        keys = _demangled_keys(set(meta) | set(funcs), f"{path}, object {k}")
+        out.append(({keys[n]: v for n, v in meta.items()}, {keys[n]: v for n, v in funcs.items()}))
+    return out
+
+
+def compare(path_a: str, path_b: str, pair_demangled: bool = False):
     """-> (kernels compared, [difference lines])."""
     a, b = describe(path_a), describe(path_b)
+    if pair_demangled:
+        a, b = _rekey(a, path_a), _rekey(b, path_b)
     diffs, n = [], 0
     if len(a) != len(b):
         diffs.append(f"code objects: {len(a)} against {len(b)}")
@@ -89,10 +138,12 @@ def compare(path_a: str, path_b: str):
 
 
 def main(argv):
-    if len(argv) != 3:
+    pair_demangled = "--pair-demangled" in argv[1:]
+    paths = [a for a in argv[1:] if a != "--pair-demangled"]
+    if len(paths) != 2:
         print(__doc__)
         return 2
-    n, diffs = compare(argv[1], argv[2])
+    n, diffs = compare(paths[0], paths[1], pair_demangled)
     for d in diffs:
         print(d)
     print(f"{n} kernels, {len(diffs)} differences")
