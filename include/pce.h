@@ -80,9 +80,13 @@ extern "C" {
  * count under minor 16's four;
  * 22 = pce_pyin_fetch_observations (the observation lists the last pce_pyin_run left for a clip) and pce_selftest_pyin_viterbi (k_pyin_viterbi on given
  * observation lists through the run's own launch); out-of-band predecessors of the pYIN decoding tie on the rounded sum V + log(tiny), as the dense
- * argmax does (before: on V, which could name another predecessor where two values lay within a few ulp). */
+ * argmax does (before: on V, which could name another predecessor where two values lay within a few ulp);
+ * 23 = pce_pitch_fetch_candidates (the refined candidates, their counts and the intensities the last pce_pitch_run left for every frame) and
+ * pce_selftest_pitch_path (k_pitch_delta, k_pitch_path and the two median kernels on given candidates through the run's own launches); the seeded
+ * refinement replays Praat's iterates for candidates above 10.5 x the pitch floor too (before: up to 5e-6 relative from Praat's frequency on candidates
+ * of short lag at 44.1 / 48 kHz, above a 600 Hz ceiling except between 525 and 600 Hz at a 50 Hz floor), and a slice without a peak (all zeros, a constant) stores intensity 0, not NaN, per frame. */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 22
+#define PCE_API_MINOR 23
 
 typedef struct pce_ctx pce_ctx;
 
@@ -223,13 +227,30 @@ int pce_pitch_plan(pce_ctx *ctx, const pce_pitch_params *p, const pce_slice *sli
 int pce_pitch_run(pce_ctx *ctx, const pce_pitch_params *p, const pce_slice *slices, int32_t n_slices);
 /* How k_pitch_refine searches a candidate's maximum (Praat: NUMimproveMaximum -> NUMminimize_brent on the sinc-interpolated
  * autocorrelation).  PCE_REFINE_SEEDED (default): successive parabolic interpolation seeded with the three samples around the peak,
- * Praat's own iterates only where the two could differ (within 0.03 lag of a sample, or when a safeguard trips): candidates agree with
- * Praat's to ~1e-6 relative.  PCE_REFINE_PRAAT: NUMminimize_brent's iterates replayed for every candidate (iterate for iterate; about
+ * Praat's own iterates only where the two could differ (within 0.03 lag of a sample, when a safeguard trips, or at a lag so short that the
+ * tolerance of Praat's minimiser, 3e-8 of the position lag + half window, exceeds 1e-6 of the lag: frequencies above 10.5 x the floor, since
+ * minor 23): every candidate's frequency agrees with Praat's to 1e-6 relative, its strength to 1e-6.  PCE_REFINE_PRAAT: NUMminimize_brent's iterates replayed for every candidate (iterate for iterate; about
  * 2.5 x the refinement time).  The environment variable PCE_PITCH_REFINE=praat at pce_create selects the second as the context's default. */
 enum { PCE_REFINE_SEEDED = 0, PCE_REFINE_PRAAT = 1 };
 int pce_pitch_set_refine(pce_ctx *ctx, int32_t mode);
 /* f0 / strength: ragged [frame_offsets[n_slices]], either may be NULL. */
 int pce_pitch_fetch(pce_ctx *ctx, double *f0, double *strength, pce_pitch_summary *summary /* n_slices */);
+/* Test hooks (tests/test_gpu_pitch_stages.py).  Since minor 23.
+ * pce_pitch_fetch_candidates: what k_pitch_frames and k_pitch_refine left for every frame of the last pce_pitch_run (read only; joins the run's
+ * tail first), in the order of pce_pitch_fetch: ncand [frames] (1 = the voiceless candidate alone), intensity [frames], and the refined candidates
+ * cand_f / cand_s [frames][16] (frequency, strength).  Slot 0 reads 0 / 0; slots at or beyond ncand are not written on the device and keep what the
+ * caller put there.  Any pointer may be NULL.
+ * pce_selftest_pitch_path: Pitch_pathFinder and the voiced summaries on the caller's candidates, through the launches of pce_pitch_run (the same
+ * function: same grids, list capacities and LDS).  Slice i holds frames frame_off[i] .. frame_off[i + 1]; ncand, intensity [frames] and cand_f,
+ * cand_s [frames][16] as the fetch above returns them (slot 0 is the voiceless candidate whatever it holds; slots >= ncand are never read); `p`
+ * supplies the five costs and thresholds and the ceiling, which is taken as given (no clamp to a Nyquist frequency), dt the frame step of the
+ * time-step correction.  Out: f0, strength [frames]; psi [frames][16], the back-pointers of the frames with more than one candidate (0 elsewhere);
+ * summary [n_slices] (t1 = 0).  Each may be NULL.  PCE_E_INVALID for ncand outside 1 .. 16, PCE_E_LIMIT for max_candidates > 16.  Works in the
+ * context's pitch buffers: a pce_pitch_fetch after it is PCE_E_STATE until the next pce_pitch_run, which plans afresh. */
+int pce_pitch_fetch_candidates(pce_ctx *ctx, int32_t *ncand, double *intensity, double *cand_f, double *cand_s);
+int pce_selftest_pitch_path(pce_ctx *ctx, const pce_pitch_params *p, double dt, int32_t n_slices, const int64_t *frame_off, const int32_t *ncand,
+                            const double *intensity, const double *cand_f, const double *cand_s, double *f0, double *strength, uint8_t *psi,
+                            pce_pitch_summary *summary /* n_slices */);
 
 /* ---- Praat intensity ------------------------------------------------------
  * Replaces parselmouth Sound.to_intensity() as Code/visualisation/Compare_speech_noenhanced.py calls it (extract_mean_volume :19-26, the

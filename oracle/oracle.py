@@ -76,7 +76,7 @@ def _lib():
         lib.por_pitch_plan_make.argtypes = [C.c_long, C.c_double, C.c_double, C.POINTER(PitchParams), C.POINTER(PitchPlan)]
         lib.por_pitch_plan_make.restype = C.c_int
         lib.por_pitch_ac.argtypes = [dp, C.c_long, C.c_double, C.c_double, C.POINTER(PitchParams), dp, dp, dp, dp, dp,
-                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), dp]
         lib.por_pitch_ac.restype = C.c_int
         lib.por_window_autocorr.argtypes = [C.c_long, C.c_double, C.c_double, C.POINTER(PitchParams), dp, C.c_long]
         lib.por_window_autocorr.restype = None
@@ -207,7 +207,9 @@ def pitch_plan(nx: int, dx: float, x1: float, params: PitchParams) -> PitchPlan:
 def pitch_ac(z: np.ndarray, dx: float, x1: float, params: PitchParams, want_candidates=False):
     """Praat Sound_to_Pitch_ac + Pitch_pathFinder on float64 samples ``z``.
 
-    Returns dict(f0, strength, intensity, plan[, cand_f, cand_s, ncand, evals]).
+    Returns dict(f0, strength, intensity, plan, evals, n_cands[, cand_f, cand_s, ncand, n_maxima, replace_margin]): with ``want_candidates`` the
+    candidates before path finding [n_frames, max_candidates], and per frame the local maxima that passed the test before the slot limit and the
+    smallest |new - weakest| of its replacement decisions (+inf where there was none).
     Raises PraatError where Praat throws (sound shorter than 3 periods of the floor)."""
     z = np.ascontiguousarray(z, dtype=np.float64)
     pl = pitch_plan(len(z), dx, x1, params)
@@ -215,13 +217,15 @@ def pitch_ac(z: np.ndarray, dx: float, x1: float, params: PitchParams, want_cand
     f0 = np.zeros(nF); st_ = np.zeros(nF); it = np.zeros(nF)
     cf = np.zeros(nF * mc); cs = np.zeros(nF * mc); nc = np.zeros(nF, dtype=np.int32)
     stats = np.zeros(2, dtype=np.int64)
+    nm = np.zeros(nF, dtype=np.int32); rm = np.full(nF, np.inf)
     st = _lib().por_pitch_ac(_dp(z), len(z), dx, x1, C.byref(params), _dp(f0), _dp(st_), _dp(it), _dp(cf), _dp(cs),
-                             nc.ctypes.data_as(C.POINTER(C.c_int32)), stats.ctypes.data_as(C.POINTER(C.c_int64)))
+                             nc.ctypes.data_as(C.POINTER(C.c_int32)), stats.ctypes.data_as(C.POINTER(C.c_int64)),
+                             nm.ctypes.data_as(C.POINTER(C.c_int32)) if want_candidates else None, _dp(rm) if want_candidates else None)
     if st != 0:
         raise PraatError(f"pitch analysis failed (status {st})")
     out = dict(f0=f0, strength=st_, intensity=it, plan=pl, evals=int(stats[0]), n_cands=int(stats[1]))
     if want_candidates:
-        out.update(cand_f=cf.reshape(nF, mc), cand_s=cs.reshape(nF, mc), ncand=nc)
+        out.update(cand_f=cf.reshape(nF, mc), cand_s=cs.reshape(nF, mc), ncand=nc, n_maxima=nm, replace_margin=rm)
     return out
 
 

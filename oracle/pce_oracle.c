@@ -302,10 +302,14 @@ void por_window_autocorr(long nx, double dx, double x1, const por_pitch_params *
  *   cand_f / cand_s     [n_frames * max_candidates] candidates BEFORE path finding (may be NULL)
  *   ncand[n_frames]     (may be NULL)
  *   stats[0] = total Brent evaluations, stats[1] = total candidates (may be NULL)
+ *   n_maxima[n_frames]       local maxima that passed the test, before the slot limit (may be NULL)
+ *   replace_margin[n_frames] smallest |new - weakest| over the frame's replacement decisions (the comparison made once the slots
+ *                            are full), +inf where there was none (may be NULL)
  */
 int por_pitch_ac(const double *z, long nx, double dx, double x1, const por_pitch_params *p,
                  double *f0, double *strength, double *intensity,
-                 double *cand_f_out, double *cand_s_out, int32_t *ncand_out, int64_t *stats)
+                 double *cand_f_out, double *cand_s_out, int32_t *ncand_out, int64_t *stats,
+                 int32_t *n_maxima, double *replace_margin)
 {
     por_pitch_plan pl; fft_table ft;
     int st = por_pitch_plan_make(nx, dx, x1, p, &pl);
@@ -319,6 +323,8 @@ int por_pitch_ac(const double *z, long nx, double dx, double x1, const por_pitch
     double *cs = (double *)calloc((size_t)(nF * maxc), sizeof(double));
     int32_t *nc = (int32_t *)malloc(sizeof(int32_t) * (size_t)nF);
     for (long i = 0; i < nF; i++) { nc[i] = 1; intensity[i] = 0.0; }
+    if (n_maxima) for (long i = 0; i < nF; i++) n_maxima[i] = 0;
+    if (replace_margin) for (long i = 0; i < nF; i++) replace_margin[i] = INFINITY;
 
     /* global absolute peak around the global mean */
     double sum = 0.0, globalPeak = 0.0;
@@ -382,6 +388,7 @@ int por_pitch_ac(const double *z, long nx, double dx, double x1, const por_pitch
                     double strengthOfMaximum = interpolate_sinc(&r[offset], bix - offset,
                                                                 1.0 / dx / frequencyOfMaximum - (double)offset, 30);
                     if (strengthOfMaximum > 1.0) strengthOfMaximum = 1.0 / strengthOfMaximum;
+                    if (n_maxima) n_maxima[iframe - 1]++;
                     if (n < maxc) {
                         place = ++n;
                     } else {
@@ -391,6 +398,10 @@ int por_pitch_ac(const double *z, long nx, double dx, double x1, const por_pitch
                             if (localStrength < weakest) { weakest = localStrength; place = iweak; }
                         }
                         if (strengthOfMaximum - octaveCost * (log(minimumPitch / frequencyOfMaximum) * NUMlog2e) <= weakest) place = 0;
+                        if (replace_margin) {
+                            double margin = fabs(strengthOfMaximum - octaveCost * (log(minimumPitch / frequencyOfMaximum) * NUMlog2e) - weakest);
+                            if (margin < replace_margin[iframe - 1]) replace_margin[iframe - 1] = margin;
+                        }
                     }
                     if (place) { fcf[place] = frequencyOfMaximum; fcs[place] = strengthOfMaximum; imax[place] = i; }
                 }

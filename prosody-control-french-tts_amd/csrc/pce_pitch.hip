@@ -131,12 +131,61 @@ int pitch_prepare(pce_ctx *c, const pce_pitch_params *p, const pce_slice *slices
     return PCE_OK;
 }
 
+// the launches behind the refinement: local terms, path finder and voiced summaries of `n` slices, from the candidates, counts and intensities
+// in the pitch buffers and the plan in the context (pi_P, pi_sizes, pi_total_frames, pi_np2, pi_long_slices, pi_meta, pi_fslice).
+// pitch_launch and pce_selftest_pitch_path both end here: there is no other launch of these four kernels.
+int pitch_launch_tail(pce_ctx *c, int32_t n)
+{
+    const PiParams &P = c->pi_P;
+    const PitchSizes &z = c->pi_sizes;
+    hipStream_t tail = c->stream;
+    const int64_t total = c->pi_total_frames;
+    if (total > 0) {
+        double *intensity = c->pi_gpeak.as<double>();
+        int *ncand = reinterpret_cast<int *>(intensity + (total + 1));
+        unsigned int *run_count = c->pi_runs.as<unsigned int>();
+        PathRun *runs = reinterpret_cast<PathRun *>(c->pi_runs.as<char>() + z.run_count_bytes);
+        // everything after the refinement (local terms, path finder, median) goes to the side stream: it is HBM- and
+        // latency-bound, and whatever the caller launches next on the main stream runs beside it; every consumer
+        // joins first (pce_side_join)
+        { int rc2 = pce_side_begin(c, pce_ctx::SIDE_TAIL, &tail); if (rc2) return rc2; }
+        PCE_HIP(c, hipMemsetAsync(run_count, 0, z.run_count_bytes, tail));
+        const long long ne = total * PI_MAXC;
+        {
+            KernelTimer t(c, PCE_K_PITCH_DELTA, tail);
+            hipLaunchKernelGGL(k_pitch_delta, dim3((unsigned)div_up(ne, 256)), dim3(256), 0, tail, P, c->pi_meta.as<PiSlice>(),
+                               c->pi_fslice.as<int>(), c->pi_cand.as<double>(), ncand, intensity, (long long)total,
+                               c->pi_dl.as<double2>(), c->pi_f0.as<double>(), c->pi_strength.as<double>(), runs, run_count, z.run_cap);
+        }
+        {
+            KernelTimer t(c, PCE_K_PITCH_PATH, tail);
+            const unsigned blocks = (unsigned)(c->cu_count > 0 ? c->cu_count : 256) * 16u;     // multiple of RUN_LISTS
+            hipLaunchKernelGGL(k_pitch_path, dim3(blocks), dim3(64), 0, tail, P,
+                               c->pi_cand.as<double>(), ncand, c->pi_dl.as<double2>(), runs, run_count, z.run_cap,
+                               c->pi_psi.as<unsigned char>(), c->pi_f0.as<double>(), c->pi_strength.as<double>());
+        }
+    }
+    if (n > 0) {
+        const size_t lds = sizeof(double) * (size_t)c->pi_np2;
+        if (lds > 64 * 1024)
+            PCE_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_pitch_median), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        KernelTimer t(c, PCE_K_PITCH_MEDIAN, tail);
+        hipLaunchKernelGGL(k_pitch_median, dim3((unsigned)n), dim3(256), lds, tail, c->pi_meta.as<PiSlice>(),
+                           c->pi_f0.as<double>(), c->pi_np2, c->pi_summary.as<PiSummaryDev>());
+        if (c->pi_long_slices)
+            hipLaunchKernelGGL(k_pitch_median_long, dim3((unsigned)n), dim3(256), 0, tail, c->pi_meta.as<PiSlice>(), c->pi_f0.as<double>(), c->pi_np2,
+                               c->pi_summary.as<PiSummaryDev>());
+    }
+    { int rc2 = pce_side_end(c, pce_ctx::SIDE_TAIL, tail); if (rc2) return rc2; }
+    PCE_HIP(c, hipGetLastError());
+    return PCE_OK;
+}
+
 // the launches of one run, from what pitch_prepare left in the context
 int pitch_launch(pce_ctx *c, const pce_slice *slices, int32_t n)
 {
     const PiParams &P = c->pi_P;
     const PitchSizes &z = c->pi_sizes;
-    hipStream_t tail = c->stream;
     const int64_t total = c->pi_total_frames;
     if (total > 0) {
         // the slice sums and extrema (Praat's mean subtraction and global peak): when pce_energy_run has just produced them
@@ -183,44 +232,8 @@ int pitch_launch(pce_ctx *c, const pce_slice *slices, int32_t n)
                                    z.list_cap, c->pi_cand.as<double>());
             }
         }
-        {
-            unsigned int *run_count = c->pi_runs.as<unsigned int>();
-            PathRun *runs = reinterpret_cast<PathRun *>(c->pi_runs.as<char>() + z.run_count_bytes);
-            // everything after the refinement (local terms, path finder, median) goes to the side stream: it is HBM- and
-            // latency-bound, and whatever the caller launches next on the main stream runs beside it; every consumer
-            // joins first (pce_side_join)
-            { int rc2 = pce_side_begin(c, pce_ctx::SIDE_TAIL, &tail); if (rc2) return rc2; }
-            PCE_HIP(c, hipMemsetAsync(run_count, 0, z.run_count_bytes, tail));
-            const long long ne = total * PI_MAXC;
-            {
-                KernelTimer t(c, PCE_K_PITCH_DELTA, tail);
-                hipLaunchKernelGGL(k_pitch_delta, dim3((unsigned)div_up(ne, 256)), dim3(256), 0, tail, P, c->pi_meta.as<PiSlice>(),
-                                   c->pi_fslice.as<int>(), c->pi_cand.as<double>(), ncand, intensity, (long long)total,
-                                   c->pi_dl.as<double2>(), c->pi_f0.as<double>(), c->pi_strength.as<double>(), runs, run_count, z.run_cap);
-            }
-            {
-                KernelTimer t(c, PCE_K_PITCH_PATH, tail);
-                const unsigned blocks = (unsigned)(c->cu_count > 0 ? c->cu_count : 256) * 16u;     // multiple of RUN_LISTS
-                hipLaunchKernelGGL(k_pitch_path, dim3(blocks), dim3(64), 0, tail, P,
-                                   c->pi_cand.as<double>(), ncand, c->pi_dl.as<double2>(), runs, run_count, z.run_cap,
-                                   c->pi_psi.as<unsigned char>(), c->pi_f0.as<double>(), c->pi_strength.as<double>());
-            }
-        }
     }
-    if (n > 0) {
-        const size_t lds = sizeof(double) * (size_t)c->pi_np2;
-        if (lds > 64 * 1024)
-            PCE_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void *>(k_pitch_median), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        KernelTimer t(c, PCE_K_PITCH_MEDIAN, tail);
-        hipLaunchKernelGGL(k_pitch_median, dim3((unsigned)n), dim3(256), lds, tail, c->pi_meta.as<PiSlice>(),
-                           c->pi_f0.as<double>(), c->pi_np2, c->pi_summary.as<PiSummaryDev>());
-        if (c->pi_long_slices)
-            hipLaunchKernelGGL(k_pitch_median_long, dim3((unsigned)n), dim3(256), 0, tail, c->pi_meta.as<PiSlice>(), c->pi_f0.as<double>(), c->pi_np2,
-                               c->pi_summary.as<PiSummaryDev>());
-    }
-    { int rc2 = pce_side_end(c, pce_ctx::SIDE_TAIL, tail); if (rc2) return rc2; }
-    PCE_HIP(c, hipGetLastError());
-    return PCE_OK;
+    return pitch_launch_tail(c, n);
 }
 
 } // namespace
@@ -281,6 +294,110 @@ int pce_pitch_fetch(pce_ctx *c, double *f0, double *strength, pce_pitch_summary 
             o.n_frames = c->pi_frame_off[(size_t)i + 1] - c->pi_frame_off[(size_t)i];
             o.n_voiced = sd[(size_t)i].n_voiced; o.median_f0 = sd[(size_t)i].median; o.mean_log_f0 = sd[(size_t)i].mean_log;
             o.t1 = c->pi_t1[(size_t)i]; o.status = c->pi_status[(size_t)i]; o.reserved = 0;
+        }
+    return PCE_OK;
+}
+
+int pce_pitch_fetch_candidates(pce_ctx *c, int32_t *ncand, double *intensity, double *cand_f, double *cand_s)
+{
+    if (!c) return PCE_E_INVALID;
+    if (c->pi_n < 0) return pce_fail(c, PCE_E_STATE, "pce_pitch_fetch_candidates before pce_pitch_run");
+    PCE_HIP(c, hipSetDevice(c->device));
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_TAIL));
+    const int64_t total = c->pi_total_frames;
+    if (total <= 0) return PCE_OK;
+    std::vector<int32_t> n((size_t)total);
+    std::vector<double> img((cand_f || cand_s) ? (size_t)total * 32 : 0);
+    const double *d_int = c->pi_gpeak.as<double>();
+    PCE_FETCH(c, n.data(), d_int + (total + 1), (size_t)total);
+    if (intensity) PCE_FETCH(c, intensity, d_int, (size_t)total);
+    if (!img.empty()) PCE_FETCH(c, img.data(), c->pi_cand.p, img.size());
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    for (int64_t f = 0; f < total; f++) {
+        if (ncand) ncand[f] = n[(size_t)f];
+        // slot 0 is the voiceless candidate by definition; slots >= ncand were never written: the caller's prefill stays
+        const int live = n[(size_t)f] < PI_MAXC ? n[(size_t)f] : PI_MAXC;
+        for (int j = 0; j < live; j++) {
+            if (cand_f) cand_f[f * PI_MAXC + j] = j ? img[(size_t)f * 32 + (size_t)j] : 0.0;
+            if (cand_s) cand_s[f * PI_MAXC + j] = j ? img[(size_t)f * 32 + 16 + (size_t)j] : 0.0;
+        }
+    }
+    return PCE_OK;
+}
+
+int pce_selftest_pitch_path(pce_ctx *c, const pce_pitch_params *p, double dt, int32_t n_slices, const int64_t *frame_off, const int32_t *ncand,
+                            const double *intensity, const double *cand_f, const double *cand_s, double *f0, double *strength, uint8_t *psi,
+                            pce_pitch_summary *summary)
+{
+    if (!c || !p || !frame_off || !ncand || !intensity || !cand_f || !cand_s) return PCE_E_INVALID;
+    if (n_slices < 1 || n_slices > (1 << 20) || frame_off[0] != 0) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pitch_path: 1 .. 2^20 slices, frame_off[0] == 0");
+    for (int32_t i = 0; i < n_slices; i++)
+        if (frame_off[i + 1] < frame_off[i]) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pitch_path: frame_off decreases at slice %d", i);
+    const int64_t total = frame_off[n_slices];
+    if (total < 1 || total > (int64_t)1 << 24) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pitch_path: 1 .. 2^24 frames");
+    if (!(dt > 0.0)) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pitch_path: dt must be positive");
+    if (p->max_candidates > PI_MAXC) return pce_fail(c, PCE_E_LIMIT, "more than %d pitch candidates per frame requested", PI_MAXC);
+    for (int64_t f = 0; f < total; f++)
+        if (ncand[f] < 1 || ncand[f] > PI_MAXC) return pce_fail(c, PCE_E_INVALID, "pce_selftest_pitch_path: frame %lld has %d candidates", (long long)f, ncand[f]);
+    PCE_HIP(c, hipSetDevice(c->device));
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_TAIL));
+    c->pi_cache.drop(); c->pi_n = -1; c->pi_params_valid = false;   // the pitch buffers and the plan in the context are this call's from here on
+
+    PiParams P; memset(&P, 0, sizeof P);
+    P.dt = dt; P.min_pitch = p->pitch_floor; P.ceiling = p->pitch_ceiling;    // the ceiling as given: no clamp to the Nyquist frequency without a rate
+    P.voicing_thr = p->voicing_threshold; P.octave_cost = p->octave_cost; P.silence_thr = p->silence_threshold;
+    P.oj_cost = p->octave_jump_cost; P.vuv_cost = p->voiced_unvoiced_cost;
+    P.maxc = p->max_candidates < 2 ? 2 : p->max_candidates; P.fpb = PI_FPB;
+    // the slice table, frame -> slice table and median plan of a real run over slices of these frame counts (no samples behind them)
+    std::vector<pce_slice> sl((size_t)n_slices);
+    memset(sl.data(), 0, sizeof(pce_slice) * sl.size());
+    const std::vector<int64_t> clip_off{0, 0}, fo(frame_off, frame_off + n_slices + 1);
+    const std::vector<int32_t> status((size_t)n_slices, PCE_SLICE_OK);
+    const std::vector<double> t1((size_t)n_slices, 0.0);
+    PitchWork w;
+    pitch_work_make(sl.data(), n_slices, clip_off, fo, status, t1, P.fpb, w);
+    if (w.too_many >= 0) return pce_fail(c, PCE_E_LIMIT, "slice %d has too many frames", w.too_many);
+    c->pi_P = P; c->pi_total_frames = total; c->pi_np2 = w.np2; c->pi_long_slices = w.long_slices;
+    c->pi_n_work = (int64_t)w.work.size();
+    const PitchSizes z = c->pi_sizes = pitch_sizes(P, total, c->pi_n_work, w.slices.size());
+    PCE_HIP(c, c->pi_cand.reserve(z.cand));
+    PCE_HIP(c, c->pi_gpeak.reserve(z.gpeak));
+    PCE_HIP(c, c->pi_psi.reserve(z.psi));
+    PCE_HIP(c, c->pi_f0.reserve(z.f0));
+    PCE_HIP(c, c->pi_strength.reserve(z.strength));
+    PCE_HIP(c, c->pi_summary.reserve(z.summary));
+    PCE_HIP(c, c->pi_runs.reserve(z.runs));
+    PCE_HIP(c, c->pi_dl.reserve(z.dl));
+    PCE_UPLOAD(c, c->pi_meta, w.slices);
+    PCE_UPLOAD(c, c->pi_fslice, w.frame_slice);
+    // the device layout of the candidates: [frames][32], strengths at + 16
+    std::vector<double> img((size_t)total * 32, 0.0);
+    for (int64_t f = 0; f < total; f++)
+        for (int j = 0; j < PI_MAXC; j++) {
+            img[(size_t)f * 32 + (size_t)j] = cand_f[f * PI_MAXC + j];
+            img[(size_t)f * 32 + 16 + (size_t)j] = cand_s[f * PI_MAXC + j];
+        }
+    double *d_int = c->pi_gpeak.as<double>();
+    PCE_PUT(c, c->pi_cand.p, img.data(), img.size());
+    PCE_PUT(c, static_cast<void *>(d_int), intensity, (size_t)total);
+    PCE_PUT(c, static_cast<void *>(d_int + (total + 1)), ncand, (size_t)total);
+    PCE_HIP(c, hipMemsetAsync(c->pi_psi.p, 0, z.psi, c->stream));   // cut frames have no back-pointers: they read 0
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    PCE_TRY(pitch_launch_tail(c, n_slices));
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_TAIL));
+    std::vector<PiSummaryDev> sd((size_t)n_slices);
+    if (f0) PCE_FETCH(c, f0, c->pi_f0.p, (size_t)total);
+    if (strength) PCE_FETCH(c, strength, c->pi_strength.p, (size_t)total);
+    if (psi) PCE_FETCH(c, psi, c->pi_psi.p, (size_t)total * PI_MAXC);
+    if (summary) PCE_FETCH(c, sd.data(), c->pi_summary.p, (size_t)n_slices);
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    pce_profile_collect(c);
+    if (summary)
+        for (int32_t i = 0; i < n_slices; i++) {
+            pce_pitch_summary &o = summary[i];
+            o.n_frames = frame_off[i + 1] - frame_off[i];
+            o.n_voiced = sd[(size_t)i].n_voiced; o.median_f0 = sd[(size_t)i].median; o.mean_log_f0 = sd[(size_t)i].mean_log;
+            o.t1 = 0.0; o.status = PCE_SLICE_OK; o.reserved = 0;
         }
     return PCE_OK;
 }

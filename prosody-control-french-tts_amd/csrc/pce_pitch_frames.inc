@@ -199,7 +199,8 @@ __global__ __launch_bounds__(64 * WPB) void k_pitch_frames(
     }
     }
     const double localPeak = wave_xor_max<LW>(lpk);
-    const double inten = localPeak > globalPeak ? 1.0 : localPeak / globalPeak;
+    // (a slice without a peak -- all zeros, or one constant -- has intensity 0 in every frame, as Praat leaves it: not 0 / 0)
+    const double inten = globalPeak == 0.0 ? 0.0 : localPeak > globalPeak ? 1.0 : localPeak / globalPeak;
     const bool active = live && localPeak != 0.0;
 
     double *rr = nullptr;                                // rr[bix + k] = r[k], k in [-bix, bix]

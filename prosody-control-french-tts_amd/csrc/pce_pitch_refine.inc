@@ -218,14 +218,19 @@ __global__ __launch_bounds__(256, G == 8 ? 3 : 2) void k_pitch_refine(PiParams P
     //     autocorrelation samples themselves: no evaluation): the first trial point already is the parabolic estimate, and the fit through
     //     the best three points converges superlinearly: 3-4 evaluations (stop: a step below 3e-8 |x| after a step below 1e-3).
     //     Praat's NUMminimize_brent (a golden-section opening of [ixmid - 1, ixmid + 1], then a bracket that has to close to 1.5e-8 |x|
-    //     from both sides) takes 9-18 for the same maximum, whose position it reports within that tolerance: 1e-6 lags absolute, 1.5e-8
-    //     relative in F0, against a parity gate of 1e-6;
+    //     from both sides) takes 9-18 for the same maximum, whose position it reports within that tolerance.  |x| is the position in the
+    //     array r[-bix..bix], lag + bix + 1, not the lag: the reference's answer is determined to 2 x 1.5e-8 (lag + bix + 1) lags, which is
+    //     3e-8 (1 + (bix + 1) / lag) relative in F0, against a parity gate of 1e-6 (REFINE_PARITY_REL);
     //   * Praat's own iterates, exactly as before, for the candidates where the two could differ by more than rounding: the
     //     interpolant is smooth on either side of the sample ixmid but has a kink AT it (the sinc window changes with floor(x)), so a
     //     maximum within a few thousandths of a lag of the sample can split into one local maximum per side (measured on synthetic
     //     autocorrelations: discrepancies of 2e-5 .. 7e-5 relative, all within 0.007 lags of the sample) and which one the reference
     //     reports depends on its path.  Every candidate whose parabolic search ends within 0.03 lags of the sample (3 %), or fails a
-    //     safeguard (step outside the bracket, no convergence in 10 steps), is searched again the reference's way.
+    //     safeguard (step outside the bracket, no convergence in 10 steps), is searched again the reference's way.  So is, at once, every
+    //     candidate of a lag so short that the two tolerances together ((2 x 1.5e-8 + 3e-8) |x|) exceed the gate: lag < 0.06 (lag + bix + 1),
+    //     which with bix = 1.5 periods of the floor is a frequency above 10.5 x the floor (lags below 11 at 16 kHz / 150 Hz, below 92 at
+    //     48 kHz / 50 Hz; tests/test_gpu_pitch_stages.py measured up to 5.1e-6 relative on such candidates before).  At the floors in use
+    //     they lie above the ceiling, or just under it at 50 Hz: voiceless to the path finder, which never reads their frequency.
     // Elsewhere the maximum in the bracket is unique, both searches end within their tolerance of it, and the strengths agree to second
     // order (the maximum is flat).  PCE_PITCH_REFINE=praat runs every candidate the reference's way.
     unsigned int it = group;
@@ -237,6 +242,7 @@ __global__ __launch_bounds__(256, G == 8 ? 3 : 2) void k_pitch_refine(PiParams P
     double yv[NR];
     double a = 0.0, b = 0.0, v = 0.0, w = 0.0, x = 0.0, fv = 0.0, fw = 0.0, fx = 0.0, t = 0.0, prev_step = 1.0;
     const double sqrt_epsilon = 1.4901161193847656e-08, spi_stop = P.refine_tol_rel;
+    constexpr double REFINE_PARITY_REL = 1e-6;         // what the seeded mode promises of a candidate's frequency against the reference's (include/pce.h)
     // Brent's choice of the next trial point from the state (a, b, x, w, v); true: converged
     auto brent_next = [&]() -> bool {
         const double range = b - a;
@@ -305,7 +311,7 @@ __global__ __launch_bounds__(256, G == 8 ? 3 : 2) void k_pitch_refine(PiParams P
                 yv[m] = (ix >= 1 && ix <= ynx) ? y[abs(ix - P.bix - 1)] : 0.0;
             }
             have = true;
-            if (P.refine_seeded) {
+            if (P.refine_seeded && (2.0 * sqrt_epsilon + spi_stop) * (double)ixmid <= REFINE_PARITY_REL * (double)item.imax) {
                 // the interpolant passes through the samples: f(ixmid) = -r0, f(ixmid -+ 1) = -rm / -rp
                 a = (double)(ixmid - 1); b = (double)(ixmid + 1);
                 x = (double)ixmid; fx = -r0;

@@ -22,6 +22,7 @@ class PceError(RuntimeError):
     pass
 
 
+PITCH_MAX_CANDIDATES = 16    # PI_MAXC of csrc/pce_pitch_plan.h: the row width of the pitch candidate arrays of the two test hooks
 PYIN_MAX_TROUGHS = 512       # PCE_PYIN_MAX_TROUGHS of include/pce.h: the row width of pYIN's observation lists
 
 
@@ -245,6 +246,8 @@ SIGNATURES = {
     "pce_pitch_run": [_vp, C.POINTER(PitchParams), _vp, _i32],
     "pce_pitch_set_refine": [_vp, _i32],
     "pce_pitch_fetch": [_vp, _vp, _vp, _vp],
+    "pce_pitch_fetch_candidates": [_vp, _vp, _vp, _vp, _vp],
+    "pce_selftest_pitch_path": [_vp, C.POINTER(PitchParams), C.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     # Praat intensity
     "pce_intensity_plan": [_vp, C.POINTER(IntensityParams), _vp, _i32, _vp, _vp],
     "pce_intensity_run": [_vp, C.POINTER(IntensityParams), _vp, _i32, _vp, _i32],
@@ -544,6 +547,35 @@ class ProsodyEngine:
     def pitch(self, slices, params: PitchParams, want_f0=True, want_strength=False):
         self.pitch_run(slices, params)
         return self.pitch_fetch(want_f0, want_strength)
+
+    def pitch_fetch_candidates(self, fill=np.nan):
+        """``pce_pitch_fetch_candidates`` (test hook): what ``k_pitch_frames`` and ``k_pitch_refine`` left for every frame of the last ``pitch_run`` ->
+        dict of ``frame_offsets``, ``ncand`` int32 [frames], ``intensity`` float64 [frames], ``cand_f`` / ``cand_s`` float64 [frames, 16] (slot 0: 0 / 0;
+        slots at or beyond ``ncand``: ``fill``, the device never wrote them)."""
+        off, _ = self.pitch_plan(self._pi_slices, self._pi_params)
+        total = int(off[-1])
+        o = {"frame_offsets": off, "ncand": np.zeros(total, np.int32), "intensity": np.zeros(total), "cand_f": np.full((total, PITCH_MAX_CANDIDATES), fill, np.float64),
+             "cand_s": np.full((total, PITCH_MAX_CANDIDATES), fill, np.float64)}
+        self._check(self._lib.pce_pitch_fetch_candidates(self._ctx, *(o[k].ctypes.data for k in ("ncand", "intensity", "cand_f", "cand_s"))))
+        return o
+
+    def selftest_pitch_path(self, params: PitchParams, dt, frame_off, ncand, intensity, cand_f, cand_s):
+        """``pce_selftest_pitch_path`` (test hook): ``k_pitch_delta``, ``k_pitch_path`` and the median kernels on given candidates (rows of 16, the
+        first ``ncand`` count, slot 0 the voiceless one) of slices ``frame_off[i] .. frame_off[i + 1]``, through the launches of ``pitch_run`` ->
+        dict of ``f0``, ``strength`` float64 [frames], ``psi`` uint8 [frames, 16], ``summary`` [slices].  The ceiling of ``params`` is taken as given.
+        Uses the pitch buffers: ``pitch_fetch`` is refused afterwards until the next ``pitch_run``."""
+        off = np.ascontiguousarray(frame_off, dtype=np.int64); n = np.ascontiguousarray(ncand, dtype=np.int32)
+        it = np.ascontiguousarray(intensity, dtype=np.float64)
+        cf = np.ascontiguousarray(cand_f, dtype=np.float64); cs = np.ascontiguousarray(cand_s, dtype=np.float64)
+        total = int(off[-1]) if off.size else 0
+        if off.ndim != 1 or off.size < 2 or n.shape != (total,) or it.shape != (total,) or cf.shape != (total, PITCH_MAX_CANDIDATES) or cs.shape != cf.shape:
+            raise ValueError("frame_off [slices + 1]; ncand, intensity [frames]; cand_f, cand_s [frames, 16]")
+        o = {"f0": np.zeros(total), "strength": np.zeros(total), "psi": np.zeros((total, PITCH_MAX_CANDIDATES), np.uint8),
+             "summary": np.zeros(off.size - 1, dtype=SUMMARY_DTYPE)}
+        self._check(self._lib.pce_selftest_pitch_path(self._ctx, C.byref(params), float(dt), off.size - 1, off.ctypes.data, n.ctypes.data, it.ctypes.data,
+                                                      cf.ctypes.data, cs.ctypes.data, o["f0"].ctypes.data, o["strength"].ctypes.data, o["psi"].ctypes.data,
+                                                      o["summary"].ctypes.data))
+        return o
 
     def intensity_plan(self, slices, params: IntensityParams):
         """Host-only sizing of a Praat intensity analysis -> (frame_offsets int64 [n + 1], status int32 [n])."""

@@ -45,6 +45,7 @@ static void instantiations()
         {44100, 150.0, 2048, 3, 4, 0, 4, PF_W4_M3, 0},
         {22050, 75.0, 2048, 3, 4, 0, 4, PF_W4_M3, 0},
         {8000, 150.0, 256, 0, 4, 0, 4, PF_W4_M0, 0},
+        {8000, 75.0, 512, 2, 8, 1, 4, PF_W4_M2_TABS, 0},
         {44100, 75.0, 4096, 0, 4, 0, 2, PF_W2_M0, 73792},
         {48000, 50.0, 8192, 0, 4, 0, 1, PF_W1_M0, 147520},
     };
