@@ -84,9 +84,12 @@ extern "C" {
  * 23 = pce_pitch_fetch_candidates (the refined candidates, their counts and the intensities the last pce_pitch_run left for every frame) and
  * pce_selftest_pitch_path (k_pitch_delta, k_pitch_path and the two median kernels on given candidates through the run's own launches); the seeded
  * refinement replays Praat's iterates for candidates above 10.5 x the pitch floor too (before: up to 5e-6 relative from Praat's frequency on candidates
- * of short lag at 44.1 / 48 kHz, above a 600 Hz ceiling except between 525 and 600 Hz at a 50 Hz floor), and a slice without a peak (all zeros, a constant) stores intensity 0, not NaN, per frame. */
+ * of short lag at 44.1 / 48 kHz, above a 600 Hz ceiling except between 525 and 600 Hz at a 50 Hz floor), and a slice without a peak (all zeros, a constant) stores intensity 0, not NaN, per frame;
+ * 24 = pce_ivl_match (the text matching of the aligner evaluation, Code/whisper_testing/splitting.py: batches of claim problems over class tables
+ * of (gold tier, predicted tier) pairs) and its two kernel ids, which sit behind minor 13's and in front of minor 16's: the numeric values of
+ * PCE_K_W2V .. PCE_K_SEQMATCH_ALIGN moved by two (pce_kernel_name follows). */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 23
+#define PCE_API_MINOR 24
 
 typedef struct pce_ctx pce_ctx;
 
@@ -864,6 +867,41 @@ int pce_seqmatch_align(pce_ctx *ctx, const uint32_t *a_chars, const int64_t *a_o
                        const uint32_t *b_chars, const int64_t *b_off, int32_t n_b, int32_t autojunk,
                        double *sim, int32_t *match_a, int32_t *match_b, int32_t *n_matches);
 
+/* ---- the text matching of the aligner evaluation (Code/whisper_testing/splitting.py:94-128) -------------
+ * align_intervals pairs the word intervals of a hand-made gold tier with those of an aligner's tier by their normalised texts (normalize_text,
+ * :90-92: host work).  Gold intervals are taken in list order; each takes, among the predicted intervals no earlier gold interval of the same
+ * call has claimed, the one of the highest score above 0.4.  The score of a pair, in this order of tests:
+ *   equal      1.0 (class 3) when the two texts are equal, code point by code point (two empty texts are equal);
+ *   substring  0.8 (class 2) when either text occurs inside the other; the EMPTY string occurs inside every string, so a gold interval of
+ *              punctuation alone, whose text normalises to nothing, claims the first unclaimed prediction;
+ *   word       0.5 (class 1) when a whitespace-separated word of the gold text equals a word of the predicted text.  Words are integer ids
+ *              which the caller interns per call: equal id = equal word;
+ *   else 0 (class 0): never a match.
+ * The best is replaced on a strict > only: among predicted intervals of one score the FIRST in list order wins.  A claim holds for the later
+ * gold intervals of the same problem and for nothing else.
+ * The score depends on the two texts alone, so one class table per TABLE PAIR (gold tier, predicted tier) serves every problem on that pair.
+ * Table pair t owns gold intervals [pair_gold[t], pair_gold[t+1]) and predicted intervals [pair_pred[t], pair_pred[t+1]) of the concatenated
+ * tiers (both range arrays [n_pairs + 1], from 0, not decreasing, ending at n_gold / n_pred).  Interval s of a tier has code points
+ * chars[off[s] .. off[s+1]) and word ids words[woff[s] .. woff[s+1]), off[0] = woff[0] = 0.
+ * Problem q walks the gold intervals gold_idx[prob_off[q] .. prob_off[q+1]) of pair prob_pair[q], indices local to the pair, in that order,
+ * over the predicted intervals that are members: bit (j & 63) of word member[member_off[q] + (j >> 6)] for local index j, ceil(P / 64) words;
+ * member_off == NULL or member_off[q] < 0: all of them.  A subset of a tier keeps the tier's order (the reference filters its lists), so the
+ * first member in list order is the lowest member index.  out_match[prob_off[q] + i] = the local index of the predicted interval that gold
+ * entry i claimed, or -1; out_class[..] = its class 3 / 2 / 1, or 0.  Integer work only: exactly the reference's pairs.  A problem's outputs
+ * depend on its own lists and its table pair only: not on the batch, on its place in it, or on what ran before.
+ * Table pairs run in groups of consecutive pairs whose class tables -- 24 bytes x gold intervals x ceil(P / 64) per pair that a problem walks --
+ * fit PCE_IVL_TABLE_MB MiB together (environment, read at pce_create; default 2048, which holds a pair of 65 536 x 65 536 intervals: 1.5 GiB,
+ * built by a fixed grid of waves that strides over the pair's tasks, so no launch grows with the tables); a single
+ * pair over that budget is PCE_E_LIMIT, and so are a pair of more than PCE_IVL_MAX_PRED predicted intervals and a text of 2^30 code points.
+ * PCE_E_INVALID: NULL or decreasing offsets or ranges, a pair or gold index outside its table.  n_problems == 0: PCE_OK, nothing written.
+ * Since minor 24. */
+#define PCE_IVL_MAX_PRED (1 << 18)
+int pce_ivl_match(pce_ctx *ctx, const uint32_t *g_chars, const int64_t *g_off, const int32_t *g_words, const int64_t *g_woff, int32_t n_gold,
+                  const uint32_t *p_chars, const int64_t *p_off, const int32_t *p_words, const int64_t *p_woff, int32_t n_pred,
+                  const int32_t *pair_gold, const int32_t *pair_pred, int32_t n_pairs,
+                  const int32_t *prob_pair, const int64_t *prob_off, const int32_t *gold_idx, const int64_t *member_off, const uint64_t *member,
+                  int32_t n_problems, int32_t *out_match, int8_t *out_class);
+
 /* ---- break-prediction token classifier --------------------
  * Forward pass of transformers.BertForTokenClassification, the model Code/baseline_models/pause_bert.py:127-132 trains
  * (bert-base-multilingual-uncased, num_labels = 2, MAX_LENGTH = 128; the reference has training code only: this is the
@@ -1001,6 +1039,8 @@ enum pce_kernel_id {
     /* minor 13: CREPE (PCE_K_CREPE_CONV2: block 2 alone, the launch that carries most of the work; PCE_K_CREPE_CONV: blocks 3-6; PCE_K_CREPE_DECODE:
      * the log-softmax / arg-max pass and the gather) */
     PCE_K_CREPE_FRAMES, PCE_K_CREPE_CONV1, PCE_K_CREPE_CONV2, PCE_K_CREPE_CONV, PCE_K_CREPE_CLASSIFIER, PCE_K_CREPE_DECODE, PCE_K_CREPE_VITERBI,
+    /* minor 24: pce_ivl_match's class tables and claims; work count = text PAIRS tested, gold STEPS */
+    PCE_K_IVL_CLASSES, PCE_K_IVL_CLAIM,
     /* minor 16: pce_w2v_run as a whole; the waveform layer (statistics, finish and recompute passes together), the positional convolution, the log-softmax tail */
     PCE_K_W2V, PCE_K_W2V_WAVE, PCE_K_W2V_POSCONV, PCE_K_W2V_TAIL,
     /* minor 20: pce_wx_align's row maxima for the wildcard (launched only when a clip holds one), the sweep (both launch shapes) and the beam back-track;

@@ -139,6 +139,7 @@ static pce_ctx::Switches switches_from_env()
     sw.xattn_absorb = !(getenv("PCE_XATTN_ABSORB") && atoi(getenv("PCE_XATTN_ABSORB")) == 0);
     if (getenv("PCE_DTW_TRACE_MB") && atoll(getenv("PCE_DTW_TRACE_MB")) > 0) sw.dtw_trace_budget = (size_t)atoll(getenv("PCE_DTW_TRACE_MB")) << 20;
     if (getenv("PCE_CTC_TRACE_MB") && atoll(getenv("PCE_CTC_TRACE_MB")) > 0) sw.ctc_trace_budget = (size_t)atoll(getenv("PCE_CTC_TRACE_MB")) << 20;
+    if (getenv("PCE_IVL_TABLE_MB") && atoll(getenv("PCE_IVL_TABLE_MB")) > 0) sw.ivl_table_budget = (size_t)atoll(getenv("PCE_IVL_TABLE_MB")) << 20;
     return sw;
 }
 
@@ -403,6 +404,7 @@ const char *pce_kernel_name(int id)
         "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace", "k_intensity", "k_intensity_summary",
         "k_ms_energy", "k_silence_scan", "k_silence_ranges",
         "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
+        "k_ivl_classes", "k_ivl_claim",
         "w2v_forward", "k_w2v_wave", "k_w2v_posconv", "k_w2v_tail",
         "k_wx_rowmax", "k_wx_trellis", "k_wx_backtrack",
         "k_ctc", "k_ctc_general", "k_ctc_trace", "k_seqmatch", "k_seqmatch_align"};

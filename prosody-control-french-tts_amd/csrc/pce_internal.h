@@ -84,6 +84,7 @@ struct pce_ctx {
         bool self_rows = true;               // incremental steps' self-attention on row-major K / V caches (k_self_attn1w); PCE_SELF_ROWS=0: k_cross_attn1w on K rows + V^T
         size_t dtw_trace_budget = (size_t)4096 << 20;   // PCE_DTW_TRACE_MB at pce_create: bytes of trace one group of pairs may hold
         size_t ctc_trace_budget = (size_t)4096 << 20;   // PCE_CTC_TRACE_MB at pce_create: bytes of trace one group of clips may hold
+        size_t ivl_table_budget = (size_t)2048 << 20;   // PCE_IVL_TABLE_MB at pce_create: bytes of class tables one group of table pairs may hold
     } sw;
     bool pitch_refine_praat = false;     // PCE_PITCH_REFINE=praat at pce_create: the candidate refinement replays NUMminimize_brent's own iterates (round 1 / 2 behaviour)
     bool gemm_few_rows = false;          // set by the incremental decoding step around its launches: k_gemm_skinny is eligible

@@ -207,6 +207,7 @@ KERNEL_IDS = ["k_energy", "k_lufs_pass1", "k_lufs_scan", "k_lufs_pass2", "k_lufs
               "whisper_decode_loop", "k_cross_attn1", "k_gemm_skinny", "k_levenshtein", "k_dtw_series", "k_dtw_series_trace",
               "k_intensity", "k_intensity_summary", "k_ms_energy", "k_silence_scan", "k_silence_ranges",
               "k_crepe_frames", "k_crepe_conv1", "k_crepe_conv:block2", "k_crepe_conv", "k_crepe_classifier", "k_crepe_decode", "k_crepe_viterbi",
+              "k_ivl_classes", "k_ivl_claim",
               "w2v_forward", "k_w2v_wave", "k_w2v_posconv", "k_w2v_tail",
               "k_wx_rowmax", "k_wx_trellis", "k_wx_backtrack",
               "k_ctc", "k_ctc_general", "k_ctc_trace", "k_seqmatch", "k_seqmatch_align"]     # = pce_kernel_name(id) for every id (tests/test_abi_and_shard.py)
@@ -323,6 +324,8 @@ SIGNATURES = {
     # batched difflib.SequenceMatcher and the fuzzy alignment of "Compare Breaks"
     "pce_seqmatch": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _i32, _vp],
     "pce_seqmatch_align": [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, C.POINTER(_i32)],
+    # the text matching of the aligner evaluation
+    "pce_ivl_match": [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     # break-prediction token classifier
     "pce_bert_load": [_vp, C.POINTER(BertDims), _vp, _i64],
     "pce_bert_run": [_vp, _vp, _vp, _i32],
@@ -1673,6 +1676,56 @@ class ProsodyEngine:
                                                  bo.ctypes.data, m, 1 if autojunk else 0, sim.ctypes.data if sim.size else None, ma.ctypes.data,
                                                  mb.ctypes.data, C.byref(k)))
         return np.stack([ma[:k.value], mb[:k.value]], axis=1), sim
+
+    def interval_match(self, tables, problems):
+        """The text matching of the aligner evaluation (``align_intervals``, Code/whisper_testing/splitting.py:94-128) for a batch of
+        problems in one call (``pce_ivl_match``).  ``tables`` = [(gold_texts, pred_texts), ...] of already normalised ``str`` lists;
+        ``problems`` = [(table, gold_indices, pred_indices or None), ...]: the gold intervals to walk, in that order, and the predicted
+        intervals that may be claimed (None: all; a subset keeps the tier's order, so the indices are a set) -> per problem
+        ``(match int32 [len(gold_indices)], cls int8 [...])``: the index of the claimed predicted interval or -1, and its class 3 (equal) /
+        2 (substring) / 1 (shared word) / 0."""
+        interned = {}
+
+        def pack_words(texts):
+            ids = [[interned.setdefault(w, len(interned)) for w in s.split()] for s in texts]
+            off = np.zeros(len(ids) + 1, dtype=np.int64); np.cumsum([len(x) for x in ids], out=off[1:])
+            return np.array([i for x in ids for i in x], dtype=np.int32), off
+        gold = [s for g, _ in tables for s in g]; pred = [s for _, p in tables for s in p]
+        gc, go = self._pack_strings(gold); pc, po = self._pack_strings(pred)
+        gw, gwo = pack_words(gold); pw, pwo = pack_words(pred)
+        pair_gold = np.zeros(len(tables) + 1, dtype=np.int32); np.cumsum([len(g) for g, _ in tables], out=pair_gold[1:])
+        pair_pred = np.zeros(len(tables) + 1, dtype=np.int32); np.cumsum([len(p) for _, p in tables], out=pair_pred[1:])
+        lists = [np.asarray(g, dtype=np.int64).reshape(-1) for _, g, _ in problems]
+        if any(x.size and (x.min() < -2 ** 31 or x.max() >= 2 ** 31) for x in lists):
+            raise ValueError("gold indices do not fit int32")
+        prob_pair = np.array([t for t, _, _ in problems], dtype=np.int32)
+        prob_off = np.zeros(len(problems) + 1, dtype=np.int64); np.cumsum([len(x) for x in lists], out=prob_off[1:])
+        gold_idx = np.ascontiguousarray(np.concatenate(lists + [np.zeros(0, np.int64)]), dtype=np.int32)
+        member_off = np.full(len(problems), -1, dtype=np.int64)
+        bitmaps, n_words = [], 0
+        for q, (t, _, members) in enumerate(problems):
+            if members is None:
+                continue
+            if not 0 <= t < len(tables):
+                raise ValueError(f"problem {q} names table {t} of {len(tables)}")
+            n_pred = len(tables[t][1])
+            members = np.asarray(members, dtype=np.int64).reshape(-1)
+            if members.size and (members.min() < 0 or members.max() >= n_pred):
+                raise ValueError(f"problem {q} names a predicted interval outside its tier of {n_pred}")
+            bits = np.zeros(((n_pred + 63) // 64) * 64, dtype=np.uint8); bits[members] = 1
+            bitmaps.append(np.packbits(bits, bitorder="little").view("<u8"))
+            member_off[q] = n_words; n_words += len(bitmaps[-1])
+        member = np.ascontiguousarray(np.concatenate(bitmaps + [np.zeros(0, "<u8")]))
+        n_slots = int(prob_off[-1])
+        out_match = np.full(max(n_slots, 1), -1, dtype=np.int32); out_class = np.zeros(max(n_slots, 1), dtype=np.int8)
+
+        def ptr(a):
+            return a.ctypes.data if a.size else None
+        self._check(self._lib.pce_ivl_match(self._ctx, ptr(gc), go.ctypes.data, ptr(gw), gwo.ctypes.data, len(gold), ptr(pc), po.ctypes.data, ptr(pw),
+                                            pwo.ctypes.data, len(pred), pair_gold.ctypes.data, pair_pred.ctypes.data, len(tables), ptr(prob_pair),
+                                            prob_off.ctypes.data, ptr(gold_idx), member_off.ctypes.data if bitmaps else None, ptr(member),
+                                            len(problems), out_match.ctypes.data, out_class.ctypes.data))
+        return [(out_match[prob_off[q]:prob_off[q + 1]].copy(), out_class[prob_off[q]:prob_off[q + 1]].copy()) for q in range(len(problems))]
 
     def nw_align(self, pairs, match=1, mismatch=-1, gap=-1):
         """Batched Needleman-Wunsch over integer token ids: ``pairs`` = [(ids_a, ids_b), ...] ->
