@@ -87,9 +87,11 @@ extern "C" {
  * of short lag at 44.1 / 48 kHz, above a 600 Hz ceiling except between 525 and 600 Hz at a 50 Hz floor), and a slice without a peak (all zeros, a constant) stores intensity 0, not NaN, per frame;
  * 24 = pce_ivl_match (the text matching of the aligner evaluation, Code/whisper_testing/splitting.py: batches of claim problems over class tables
  * of (gold tier, predicted tier) pairs) and its two kernel ids, which sit behind minor 13's and in front of minor 16's: the numeric values of
- * PCE_K_W2V .. PCE_K_SEQMATCH_ALIGN moved by two (pce_kernel_name follows). */
+ * PCE_K_W2V .. PCE_K_SEQMATCH_ALIGN moved by two (pce_kernel_name follows);
+ * 25 = pce_lufs_fetch_stages and pce_lufs_stage_sizes (the chunk and block tables, the coefficients, the power table, the per-chunk states and
+ * energies, the per-block mean squares and the peaks the last pce_lufs_run left).  No kernel changed. */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 24
+#define PCE_API_MINOR 25
 
 typedef struct pce_ctx pce_ctx;
 
@@ -194,6 +196,34 @@ int pce_energy_fetch(pce_ctx *ctx, pce_energy *out /* n_slices */);
 int pce_lufs_set_meter_rate(pce_ctx *ctx, int32_t rate);
 int pce_lufs_run(pce_ctx *ctx, const pce_slice *slices, int32_t n_slices);
 int pce_lufs_fetch(pce_ctx *ctx, double *lufs /* n_slices */, int32_t *status /* n_slices */);
+
+/* Test hooks (tests/test_gpu_lufs_stages.py).  Since minor 25.
+ * pce_lufs_fetch_stages: what the host plan and the four kernels of the last pce_lufs_run left (read only; joins the run's side stream; nothing
+ * is computed or changed).  The loudness chain cuts every slice into chunks of at most 256 samples whose borders hold every gating-block
+ * bound of pyloudnorm; k_lufs_pass1 leaves the end state of every chunk run from a zero state, k_lufs_scan the true begin states, k_lufs_pass2
+ * the sum of squares of the K-weighted samples, k_lufs_gate the mean square z of every gating block.
+ *   coef [13]: b[3], a[3] of the high shelf, c[3], d[3] of the high pass (a[0] = d[0] = 1) and 1 / (0.4 * meter rate), as the kernels took them;
+ *   apow [257][16]: the powers 0 .. 256 of the cascade's zero-input transition matrix (row major 4 x 4; state order: shelf z0, z1, high-pass w0, w1);
+ *   chunks [n_chunks]: rel = first sample relative to the slice's begin; state_end: pass 1; state_init: the scan; energy: pass 2;
+ *   slices [n_slices]: chunk and block ranges (blocks' c0, c1 count chunks from the slice's first_chunk), the status, and peak = the integer the
+ *     run divided the samples by (max |x| of the slice's real samples; 1 where that is 0);
+ *   blocks [n_blocks]: the block sums chunks [c0, c1) of its slice; z = coef[12] * (their energies added in chunk order).
+ * Any pointer may be NULL.  pce_lufs_stage_sizes gives the three counts.  PCE_E_STATE: before a pce_lufs_run, or when the run took its peaks from a
+ * pce_energy_run of the same slices and a pce_energy_run of other slices has replaced them since. */
+typedef struct pce_lufs_chunk {
+    int64_t rel;
+    int32_t len, slice;
+    double state_end[4], state_init[4], energy;
+} pce_lufs_chunk;
+typedef struct pce_lufs_slice_plan {
+    int32_t first_chunk, n_chunks, first_block, n_blocks, status, peak;
+} pce_lufs_slice_plan;
+typedef struct pce_lufs_block {
+    int32_t c0, c1;
+    double z;
+} pce_lufs_block;
+int pce_lufs_stage_sizes(pce_ctx *ctx, int32_t *n_slices, int64_t *n_chunks, int64_t *n_blocks);
+int pce_lufs_fetch_stages(pce_ctx *ctx, double *coef, double *apow, pce_lufs_chunk *chunks, pce_lufs_slice_plan *slices, pce_lufs_block *blocks);
 
 /* ---- R1 / R2: Praat autocorrelation pitch ------------------------------
  * Replaces parselmouth Sound.to_pitch(pitch_floor, pitch_ceiling) followed by

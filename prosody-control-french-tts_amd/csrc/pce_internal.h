@@ -113,6 +113,7 @@ struct pce_ctx {
     int32_t lu_n = -1;
     int32_t lu_meter_rate = 0;       // pce_lufs_set_meter_rate: 0 = the batch's own rate
     bool lu_reads_en_out = false;    // the running LUFS chain takes its peaks from pce_energy_run's accumulators (same slices)
+    bool lu_peaks_in_en_out = false; // the latest pce_lufs_run took them from there (pce_lufs_fetch_stages; lu_reads_en_out is cleared by the next energy run)
     std::vector<int32_t> lu_host_status;
 
     // pitch

@@ -374,7 +374,7 @@ int pce_lufs_run(pce_ctx *c, const pce_slice *slices, int32_t n)
         int st = pce_energy_launch(c, n, 500, c->lu_n_energy_work, c->lu_en_work, c->lu_en_acc, ls);
         if (st) return st;
     }
-    c->lu_reads_en_out = reuse;
+    c->lu_reads_en_out = reuse; c->lu_peaks_in_en_out = reuse;
     LuCoef k; memcpy(&k, c->lu_coef, sizeof k);
     size_t pstride = 0;
     const int *peaks = pce_energy_peak_ptr(reuse ? c->en_out : c->lu_en_acc, &pstride);
@@ -422,6 +422,65 @@ int pce_lufs_fetch(pce_ctx *c, double *lufs, int32_t *status)
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     pce_profile_collect(c);
     if (status) for (int32_t i = 0; i < c->lu_n; i++) status[i] = c->lu_host_status[(size_t)i];
+    return PCE_OK;
+}
+
+int pce_lufs_stage_sizes(pce_ctx *c, int32_t *n_slices, int64_t *n_chunks, int64_t *n_blocks)
+{
+    if (!c) return PCE_E_INVALID;
+    if (c->lu_n < 0) return pce_fail(c, PCE_E_STATE, "pce_lufs_stage_sizes before pce_lufs_run");
+    if (n_slices) *n_slices = c->lu_n;
+    if (n_chunks) *n_chunks = c->lu_n_chunks;
+    if (n_blocks) *n_blocks = c->lu_n_blocks;
+    return PCE_OK;
+}
+
+int pce_lufs_fetch_stages(pce_ctx *c, double *coef, double *apow, pce_lufs_chunk *chunks, pce_lufs_slice_plan *slices, pce_lufs_block *blocks)
+{
+    if (!c) return PCE_E_INVALID;
+    if (c->lu_n < 0) return pce_fail(c, PCE_E_STATE, "pce_lufs_fetch_stages before pce_lufs_run");
+    if (slices && c->lu_peaks_in_en_out && !(c->en_n == c->lu_n && c->en_cache.same(c->lu_cache.v.data(), c->lu_n)))
+        return pce_fail(c, PCE_E_STATE, "pce_lufs_fetch_stages: the run's peaks were pce_energy_run's, which has covered other slices since");
+    PCE_HIP(c, hipSetDevice(c->device));
+    PCE_TRY(pce_side_join(c, pce_ctx::SIDE_LUFS));
+    const size_t n = (size_t)c->lu_n, nch = (size_t)c->lu_n_chunks, nbl = (size_t)c->lu_n_blocks;
+    if (coef) memcpy(coef, c->lu_coef, sizeof c->lu_coef);
+    std::vector<LuChunk> hc(chunks ? nch : 0);
+    std::vector<double> se(chunks ? 4 * nch : 0), si(chunks ? 4 * nch : 0), en(chunks ? nch : 0), z(blocks ? nbl : 0);
+    std::vector<LuSlice> hs(slices ? n : 0);
+    std::vector<LuBlock> hb(blocks ? nbl : 0);
+    std::vector<char> pk;
+    if (apow) PCE_FETCH(c, apow, c->lu_pow.p, (size_t)(LU_LMAX + 1) * 16);
+    if (chunks && nch) {
+        PCE_FETCH(c, hc.data(), c->lu_chunks.p, nch);
+        PCE_FETCH(c, se.data(), c->lu_state_end.p, 4 * nch);
+        PCE_FETCH(c, si.data(), c->lu_state_init.p, 4 * nch);
+        PCE_FETCH(c, en.data(), c->lu_energy.p, nch);
+    }
+    size_t pstride = 0;
+    if (slices && n) {
+        PCE_FETCH(c, hs.data(), c->lu_meta.p, n);
+        const int *peaks = pce_energy_peak_ptr(c->lu_peaks_in_en_out ? c->en_out : c->lu_en_acc, &pstride);
+        pk.resize((n - 1) * pstride + sizeof(int));
+        PCE_FETCH(c, pk.data(), peaks, pk.size());
+    }
+    if (blocks && nbl) {
+        PCE_FETCH(c, hb.data(), c->lu_blocks.p, nbl);
+        PCE_FETCH(c, z.data(), c->lu_zbuf.p, nbl);
+    }
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < hc.size(); i++) {
+        pce_lufs_chunk &o = chunks[i];
+        o.rel = hc[i].rel; o.len = hc[i].len; o.slice = hc[i].slice; o.energy = en[i];
+        for (int t = 0; t < 4; t++) { o.state_end[t] = se[4 * i + (size_t)t]; o.state_init[t] = si[4 * i + (size_t)t]; }
+    }
+    for (size_t i = 0; i < hs.size(); i++) {
+        pce_lufs_slice_plan &o = slices[i];
+        int p; memcpy(&p, pk.data() + i * pstride, sizeof p);
+        o.first_chunk = hs[i].first_chunk; o.n_chunks = hs[i].n_chunks; o.first_block = hs[i].first_block; o.n_blocks = hs[i].n_blocks;
+        o.status = hs[i].status; o.peak = p == 0 ? 1 : p;
+    }
+    for (size_t i = 0; i < hb.size(); i++) { blocks[i].c0 = hb[i].c0; blocks[i].c1 = hb[i].c1; blocks[i].z = z[i]; }
     return PCE_OK;
 }
 

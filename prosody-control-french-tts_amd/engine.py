@@ -190,6 +190,13 @@ INTENSITY_SUMMARY_DTYPE = np.dtype([("n_frames", "<i8"), ("n_positive", "<i8"), 
                                     ("status", "<i4"), ("reserved", "<i4")])
 assert INTENSITY_SUMMARY_DTYPE.itemsize == C.sizeof(IntensitySummary) == 40 and C.sizeof(IntensityParams) == 24
 
+# the records of pce_lufs_fetch_stages
+LUFS_CHUNK_DTYPE = np.dtype([("rel", "<i8"), ("len", "<i4"), ("slice", "<i4"), ("state_end", "<f8", (4,)), ("state_init", "<f8", (4,)), ("energy", "<f8")])
+LUFS_SLICE_DTYPE = np.dtype([("first_chunk", "<i4"), ("n_chunks", "<i4"), ("first_block", "<i4"), ("n_blocks", "<i4"), ("status", "<i4"), ("peak", "<i4")])
+LUFS_BLOCK_DTYPE = np.dtype([("c0", "<i4"), ("c1", "<i4"), ("z", "<f8")])
+assert (LUFS_CHUNK_DTYPE.itemsize, LUFS_SLICE_DTYPE.itemsize, LUFS_BLOCK_DTYPE.itemsize) == (88, 24, 16)
+LUFS_MAX_CHUNK = 256                                          # LU_LMAX of csrc/pce_lufs.hip: the longest chunk, the last power of the table
+
 SLICE_OK, SLICE_TOO_SHORT, SLICE_EMPTY = 0, 1, 2
 DTW_OK, DTW_EMPTY, DTW_NO_PATH = 0, 1, 2                      # enum pce_dtw_status
 CTC_OK, CTC_EMPTY, CTC_TOO_SHORT, CTC_NO_PATH = 0, 1, 2, 3     # enum pce_ctc_status
@@ -242,6 +249,8 @@ SIGNATURES = {
     "pce_lufs_set_meter_rate": [_vp, _i32],
     "pce_lufs_run": [_vp, _vp, _i32],
     "pce_lufs_fetch": [_vp, _vp, _vp],
+    "pce_lufs_stage_sizes": [_vp, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)],
+    "pce_lufs_fetch_stages": [_vp, _vp, _vp, _vp, _vp, _vp],
     # R1 / R2: Praat autocorrelation pitch
     "pce_pitch_plan": [_vp, C.POINTER(PitchParams), _vp, _i32, _vp, _vp],
     "pce_pitch_run": [_vp, C.POINTER(PitchParams), _vp, _i32],
@@ -526,6 +535,17 @@ class ProsodyEngine:
         self.lufs_run(slices)
         return self.lufs_fetch()
 
+    def lufs_fetch_stages(self):
+        """``pce_lufs_fetch_stages`` (test hook): what the plan and the four kernels of the last ``lufs_run`` left -> dict of ``coef`` float64 [13]
+        (b, a, c, d, 1 / (0.4 rate)), ``apow`` float64 [257, 4, 4], and three record arrays: ``chunks`` (``LUFS_CHUNK_DTYPE``), ``slices``
+        (``LUFS_SLICE_DTYPE``; ``peak`` is the integer the run divided by) and ``blocks`` (``LUFS_BLOCK_DTYPE``).  Read only."""
+        n = _i32(); nch = _i64(); nbl = _i64()
+        self._check(self._lib.pce_lufs_stage_sizes(self._ctx, C.byref(n), C.byref(nch), C.byref(nbl)))
+        o = {"coef": np.zeros(13), "apow": np.zeros((LUFS_MAX_CHUNK + 1, 4, 4)), "chunks": np.zeros(nch.value, LUFS_CHUNK_DTYPE),
+             "slices": np.zeros(n.value, LUFS_SLICE_DTYPE), "blocks": np.zeros(nbl.value, LUFS_BLOCK_DTYPE)}
+        self._check(self._lib.pce_lufs_fetch_stages(self._ctx, *(o[k].ctypes.data for k in ("coef", "apow", "chunks", "slices", "blocks"))))
+        return o
+
     def pitch_plan(self, slices, params: PitchParams):
         s = self._slices(slices)
         off = np.zeros(len(s) + 1, dtype=np.int64); st = np.zeros(len(s), dtype=np.int32)
@@ -707,12 +727,15 @@ class ProsodyEngine:
         return p.value, n.value
 
     # ---------------------------------------------------------------- sample-rate conversion
-    def resample(self, target_rate: int):
-        """Resample the resident batch to ``target_rate`` (polyphase, scipy.signal.resample_poly's filter design)."""
+    def resample(self, target_rate: int, filter=None):
+        """Resample the resident batch to ``target_rate`` (polyphase, scipy.signal.resample_poly's filter design).  ``filter``: a caller-made
+        ``(up, down, taps, n_pre_remove)`` for ``pce_resample_run`` in place of that design (``target_rate`` must be rate * up / down)."""
         from .hostrules import resample_filter
-        if target_rate == self.rate:
+        if filter is None and target_rate == self.rate:
             return self
-        up, down, taps, n_pre_remove = resample_filter(self.rate, target_rate)
+        up, down, taps, n_pre_remove = filter if filter is not None else resample_filter(self.rate, target_rate)
+        if self.rate * up != target_rate * down:
+            raise ValueError(f"{self.rate} Hz * {up} / {down} is not {target_rate} Hz")
         taps = np.ascontiguousarray(taps, dtype=np.float64)
         self._check(self._lib.pce_resample_run(self._ctx, up, down, taps.ctypes.data, len(taps), n_pre_remove))
         off = np.zeros(len(self.clip_lengths) + 1, dtype=np.int64); rate = C.c_int32()
