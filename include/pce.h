@@ -89,9 +89,11 @@ extern "C" {
  * of (gold tier, predicted tier) pairs) and its two kernel ids, which sit behind minor 13's and in front of minor 16's: the numeric values of
  * PCE_K_W2V .. PCE_K_SEQMATCH_ALIGN moved by two (pce_kernel_name follows);
  * 25 = pce_lufs_fetch_stages and pce_lufs_stage_sizes (the chunk and block tables, the coefficients, the power table, the per-chunk states and
- * energies, the per-block mean squares and the peaks the last pce_lufs_run left).  No kernel changed. */
+ * energies, the per-block mean squares and the peaks the last pce_lufs_run left).  No kernel changed;
+ * 26 = pce_selftest_encoder_walk (the encoder layer walk Whisper's tiled encoder, BERT and wav2vec2 share, on host arrays through the loaders' weight
+ * packer, with the buffer behind every launch copied out).  No kernel changed. */
 #define PCE_API_VERSION 1
-#define PCE_API_MINOR 25
+#define PCE_API_MINOR 26
 
 typedef struct pce_ctx pce_ctx;
 
@@ -573,6 +575,31 @@ int pce_selftest_gemm_tiled(pce_ctx *ctx, int32_t kernel, int32_t epilogue, cons
  * a 16-bit copy of the output.  Since minor 5. */
 int pce_selftest_layernorm(pce_ctx *ctx, int32_t form, int32_t rows, int32_t d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w,
                            const float *b, float eps, int32_t flags, void *out, void *resid_out, uint16_t *out_copy);
+/* Self-test of the encoder layer walk that Whisper's audio encoder on the tiled kernels, BERT and wav2vec2 share: n_layers (1 or 2) layers over
+ * M = n_items x rows_per_item rows of width d, item i holding len[i] rows from row i x rows_per_item, through the code the product runs (the loaders' weight
+ * packer and upload, the callers' run description, the walk itself).  pre_ln 1: x += proj(MHA(LN1 x)); x += W2 gelu(W1 LN2 x); 0: x = LN1(x + proj(MHA x));
+ * x = LN2(x + W2 gelu(W1 x)), each LayerNorm written to the stream and to its 16-bit image.  gemm_rule 0: the product's kernel choice, 1: wav2vec2's.
+ * weights: the layers one after the other, fp32, PyTorch layouts -- pre_ln 1 with gemm_rule 0 (the Whisper encoder) in openai-whisper's order
+ *   ln1.w,b  q.w,b  k.w [k.b]  v.w,b  out.w,b  ln2.w,b  fc1.w,b  fc2.w,b,
+ * every other form in transformers' (q.w,b  k.w [k.b]  v.w,b  out.w,b  ln1.w,b  fc1.w,b  fc2.w,b  ln2.w,b); k.b only with key_bias.  stream [M][d] fp32: the
+ * stream on entry; ln_in [M][d]: the 16-bit image the caller's opening LayerNorm leaves (pre_ln 0; else ignored, may be NULL).  Behind every launch the
+ * buffer it wrote is copied, per layer l, to
+ *   ln16 [l][3][M][d]   the LayerNorm image behind LN1 in front of the attention (slot 0, pre_ln 1), behind the LayerNorm in front of fc1 (1) and behind the layer's
+ *                       last (2, pre_ln 0);
+ *   qk [l][M][2 d], vt [l][n_items][d][vt_sp]  Q | K and the whole V^T image (zeroed once before the first layer, as every caller zeroes it);
+ *   attn [l][M][d], hidden [l][M][inner]       the attention's output, gelu(fc1);
+ *   x32 [l][4][M][d]    the fp32 stream behind the output projection (0), behind the LayerNorm in front of fc1 (1, pre_ln 0), behind fc2 (2) and behind the
+ *                       layer's last LayerNorm (3, pre_ln 0).
+ * All six are uploaded first and fetched back whole: what no launch writes keeps the caller's values, and the run's own buffers start with what the
+ * caller's arrays hold for layer 0 (so attention rows at and behind len[i] keep them in every layer).  16-bit arrays are bit patterns of the context's
+ * operand type.  *fit_out (may be NULL): whether every product was launched.  PCE_E_LIMIT for what the loaders refuse (d % 128, heads x 64 != d,
+ * d > 2048, inner % 128), PCE_E_INVALID for len[i] outside 1 .. rows_per_item, rows_per_item > vt_sp (or % 4, or vt_sp % 64), a weight blob of another
+ * size and arrays shorter than the shape needs -- all before anything is launched.  Since minor 26. */
+int pce_selftest_encoder_walk(pce_ctx *ctx, int32_t pre_ln, int32_t gemm_rule, int32_t key_bias, int32_t d, int32_t heads, int32_t inner, int32_t n_layers,
+                              int32_t n_items, int32_t rows_per_item, int32_t vt_sp, const int32_t *len, float eps, const float *weights, int64_t n_floats,
+                              const float *stream, int64_t stream_elems, const uint16_t *ln_in, uint16_t *ln16, int64_t ln16_elems, uint16_t *qk, int64_t qk_elems,
+                              uint16_t *vt, int64_t vt_elems, uint16_t *attn, int64_t attn_elems, uint16_t *hidden, int64_t hidden_elems, float *x32,
+                              int64_t x32_elems, int32_t *fit_out);
 int pce_whisper_encode_fetch(pce_ctx *ctx, int32_t clip, float *out /* [1500][n_state] */);
 
 /* ---- R8: forced alignment of known text tokens (teacher-forced decoder + cross-attention DTW) ----

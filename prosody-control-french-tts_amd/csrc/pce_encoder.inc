@@ -32,8 +32,13 @@ struct ProductGemm {
 // The layers of one encoder on the tiled kernels, in place on r.resid.  Pre-LN: x += proj(MHA(LN1(x))); x += W2 gelu(W1 LN2(x)).  Post-LN: r.ln holds
 // LN(x) on entry, x = LN1(x + proj(MHA(x))); x = LN2(x + W2 gelu(W1 x)), each LayerNorm written back into the stream and into r.ln.  The LayerNorm in
 // front of a post-LN stack and the one behind a pre-LN stack are the caller's.  Returns whether every product was launched.
-template <class Gemm>
-static bool encoder_walk(pce_ctx *c, const EncoderRun &r, const std::vector<EncoderLayerW> &layers, bool pre_ln)
+// probe(layer, stage) is called behind every launch, in launch order (EncoderStage names the launch; its buffers: ES_LN_A r.ln; ES_QKV r.qk and r.vt;
+// ES_ATTN r.attn; ES_X1 / ES_X2 r.resid; ES_LN_B / ES_LN_C r.ln, and r.resid where the form is post-LN; ES_HIDDEN r.hidden).  The product's probe is empty and
+// compiles away; pce_selftest_encoder_walk's queues a copy of what the launch wrote.
+enum EncoderStage { ES_LN_A, ES_QKV, ES_ATTN, ES_X1, ES_LN_B, ES_HIDDEN, ES_X2, ES_LN_C };
+struct NoProbe { void operator()(int, EncoderStage) const {} };
+template <class Gemm, class Probe = NoProbe>
+static bool encoder_walk(pce_ctx *c, const EncoderRun &r, const std::vector<EncoderLayerW> &layers, bool pre_ln, Probe probe = Probe{})
 {
     const int M = r.M, d = r.d, I = r.I;
     auto ln = [&](size_t w_off, size_t b_off) {
@@ -42,18 +47,26 @@ static bool encoder_walk(pce_ctx *c, const EncoderRun &r, const std::vector<Enco
         launch_layernorm<op_t>(c, r.resid, r.Wf + w_off, r.Wf + b_off, M, d, r.ln, r.eps, pre_ln ? nullptr : r.resid);
     };
     bool fit = true;
+    int l = 0;
     for (const EncoderLayerW &ly : layers) {
-        if (pre_ln) ln(ly.ln1_w, ly.ln1_b);
+        if (pre_ln) { ln(ly.ln1_w, ly.ln1_b); probe(l, ES_LN_A); }
         // Q | K go to the row-major [M][2d] buffer, V is written transposed per head: one launch sweeps the LayerNorm output once
         fit &= Gemm::template run<EPI_QKV>(c, r.ln, d, 0, r.Wb + ly.qkv_w, M, 3 * d, d, r.Wf + ly.qkv_b, r.qk, 2 * d, 0, 1,
                                            reinterpret_cast<const float *>(r.vt), r.rows_per_item, 2 * d, r.vt_sp);
+        probe(l, ES_QKV);
         launch_attention_rows(c, r.n_items, r.H, r.rows_per_item, r.qk, 2 * d, r.qk + d, 2 * d, r.vt, r.vt_sp, r.row0, r.len, r.row0, r.len, r.attn, 0,
                               r.attn_flops);                     // keys beyond an item's length are masked (right padding)
+        probe(l, ES_ATTN);
         fit &= Gemm::template run<EPI_RESID_F32>(c, r.attn, d, 0, r.Wb + ly.out_w, M, d, d, r.Wf + ly.out_b, r.resid, d, 0, 1);
+        probe(l, ES_X1);
         if (pre_ln) ln(ly.ln2_w, ly.ln2_b); else ln(ly.ln1_w, ly.ln1_b);
+        probe(l, ES_LN_B);
         fit &= Gemm::template run<EPI_GELU_BF16>(c, r.ln, d, 0, r.Wb + ly.m1_w, M, I, d, r.Wf + ly.m1_b, r.hidden, I, 0, 1);
+        probe(l, ES_HIDDEN);
         fit &= Gemm::template run<EPI_RESID_F32>(c, r.hidden, I, 0, r.Wb + ly.m2_w, M, d, I, r.Wf + ly.m2_b, r.resid, d, 0, 1);
-        if (!pre_ln) ln(ly.ln2_w, ly.ln2_b);
+        probe(l, ES_X2);
+        if (!pre_ln) { ln(ly.ln2_w, ly.ln2_b); probe(l, ES_LN_C); }
+        l++;
     }
     return fit;
 }

@@ -312,6 +312,11 @@ static bool w2v_gemm(pce_ctx *c, const op_t *A, int64_t lda, int64_t a_batch, co
 struct W2vGemm {                       // encoder_walk's GEMM rule for this model
     template <int EPI, class... A> static bool run(pce_ctx *c, A... a) { return w2v_gemm<EPI>(c, a...); }
 };
+// (pce_selftest_encoder_walk's walk under this rule, declared in pce_whisper_selftest.inc)
+static bool selftest_walk_w2v(pce_ctx *c, const EncoderRun &r, const std::vector<EncoderLayerW> &layers, bool pre_ln, const WalkCapture &probe)
+{
+    return encoder_walk<W2vGemm>(c, r, layers, pre_ln, probe);
+}
 
 // n_win windows of len[i] <= rows_per_win frames (device table) in slots of rows_per_win rows, `frames` of them in all (the timer's work count)
 static void w2v_launch_posconv(pce_ctx *c, const float *x, const op_t *w, const float *bias, const int *len, double frames, int rows_per_win, int d, int groups,

@@ -72,6 +72,13 @@
       (pce_ctx *c, int32_t form, int32_t rows, int32_t d, const void *x, const uint16_t *delta, const uint16_t *delta2, const float *w, const float *b, \
        float eps, int32_t flags, void *out, void *resid_out, uint16_t *out_copy), \
       (c, form, rows, d, x, delta, delta2, w, b, eps, flags, out, resid_out, out_copy)) \
+    X(pce_selftest_encoder_walk, \
+      (pce_ctx *c, int32_t pre_ln, int32_t gemm_rule, int32_t key_bias, int32_t d, int32_t heads, int32_t inner, int32_t n_layers, int32_t n_items, \
+       int32_t rows_per_item, int32_t vt_sp, const int32_t *len, float eps, const float *weights, int64_t n_floats, const float *stream, int64_t stream_elems, \
+       const uint16_t *ln_in, uint16_t *ln16, int64_t ln16_elems, uint16_t *qk, int64_t qk_elems, uint16_t *vt, int64_t vt_elems, uint16_t *attn, \
+       int64_t attn_elems, uint16_t *hidden, int64_t hidden_elems, float *x32, int64_t x32_elems, int32_t *fit_out), \
+      (c, pre_ln, gemm_rule, key_bias, d, heads, inner, n_layers, n_items, rows_per_item, vt_sp, len, eps, weights, n_floats, stream, stream_elems, ln_in, ln16, \
+       ln16_elems, qk, qk_elems, vt, vt_elems, attn, attn_elems, hidden, hidden_elems, x32, x32_elems, fit_out)) \
     X(pce_whisper_decoder_load, (pce_ctx *c, const pce_whisper_text_dims *dims, const float *weights, int64_t n_floats), (c, dims, weights, n_floats)) \
     X(pce_whisper_align_run, \
       (pce_ctx *c, const int32_t *tokens, const int32_t *token_offsets, const int32_t *num_frames, int32_t sot_len, const uint8_t *head_mask, \

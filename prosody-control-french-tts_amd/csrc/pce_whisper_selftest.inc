@@ -31,6 +31,37 @@ static int selftest_add_layernorm(pce_ctx *c, int64_t rows, int d, const void *x
     PCE_HIP(c, hipStreamSynchronize(c->stream));
     return PCE_OK;
 }
+
+// pce_selftest_encoder_walk's probe: behind a launch of encoder_walk, a device-to-device copy, on the walk's stream, of the buffer(s) that launch wrote into
+// layer l's part of the capture buffers (their layout: include/pce.h).  The first copy that fails is kept.
+struct WalkCapture {
+    pce_ctx *c; const EncoderRun *r; bool pre_ln;
+    op_t *ln16, *qk, *vt, *attn, *hidden; float *x32;
+    size_t Md, MI, nvt;                                          // elements of a [M][d] buffer, of r.hidden, of r.vt
+    hipError_t *failed;
+    void keep(void *dst, const void *src, size_t bytes) const
+    {
+        if (*failed == hipSuccess) *failed = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream);
+    }
+    void operator()(int l, EncoderStage s) const
+    {
+        const size_t y = (size_t)l, b16 = sizeof(op_t), b32 = sizeof(float);
+        op_t *ln_at = ln16 + y * 3 * Md;
+        float *x_at = x32 + y * 4 * Md;
+        switch (s) {
+        case ES_LN_A: keep(ln_at, r->ln, b16 * Md); break;
+        case ES_QKV: keep(qk + y * 2 * Md, r->qk, b16 * 2 * Md); keep(vt + y * nvt, r->vt, b16 * nvt); break;
+        case ES_ATTN: keep(attn + y * Md, r->attn, b16 * Md); break;
+        case ES_X1: keep(x_at, r->resid, b32 * Md); break;
+        case ES_LN_B: keep(ln_at + Md, r->ln, b16 * Md); if (!pre_ln) keep(x_at + Md, r->resid, b32 * Md); break;
+        case ES_HIDDEN: keep(hidden + y * MI, r->hidden, b16 * MI); break;
+        case ES_X2: keep(x_at + 2 * Md, r->resid, b32 * Md); break;
+        case ES_LN_C: keep(ln_at + 2 * Md, r->ln, b16 * Md); keep(x_at + 3 * Md, r->resid, b32 * Md); break;
+        }
+    }
+};
+// encoder_walk<W2vGemm> under that probe: defined at the end of pce_w2v.inc, where wav2vec2's GEMM rule is
+static bool selftest_walk_w2v(pce_ctx *c, const EncoderRun &r, const std::vector<EncoderLayerW> &layers, bool pre_ln, const WalkCapture &probe);
 } // namespace
 
 // V rows of clip c at rows k_row0[c] .. + k_len[c] of [.][heads * 64] -> the V^T image the attention kernels read: [clip][head * 64 + d][sp] (the
@@ -530,6 +561,81 @@ int pce_selftest_layernorm(pce_ctx *c, int32_t form, int32_t rows, int32_t d, co
     if (st == 0) return selftest_add_layernorm<op_t, float, float>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
     if (st == 1) return selftest_add_layernorm<op_t, float, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
     return selftest_add_layernorm<op_t, op_t, op_t>(c, rows, d, x, delta, delta2, w, b, eps, wr, out, resid_out, out_copy);
+}
+
+// Self-test hook of the shared encoder layer walk (encoder_walk, pce_encoder.inc) on host arrays: the weights go through pack_encoder_layer and
+// upload_weights as a loader's do, the EncoderRun is filled as pce_whisper_encode_run (pre_ln, rule 0), pce_bert_run (post-LN, rule 0) and w2v_forward_chunk
+// (rule 1) fill theirs, and the walk's probe copies out, behind every launch, the buffer that launch wrote.  See include/pce.h.
+int pce_selftest_encoder_walk(pce_ctx *c, int32_t pre_ln, int32_t gemm_rule, int32_t key_bias, int32_t d, int32_t heads, int32_t inner, int32_t n_layers,
+                              int32_t n_items, int32_t rows_per_item, int32_t vt_sp, const int32_t *len, float eps, const float *weights, int64_t n_floats,
+                              const float *stream, int64_t stream_elems, const uint16_t *ln_in, uint16_t *ln16, int64_t ln16_elems, uint16_t *qk, int64_t qk_elems,
+                              uint16_t *vt, int64_t vt_elems, uint16_t *attn, int64_t attn_elems, uint16_t *hidden, int64_t hidden_elems, float *x32,
+                              int64_t x32_elems, int32_t *fit_out)
+{
+    if (!c || !len || !weights || !stream || !ln16 || !qk || !vt || !attn || !hidden || !x32 || pre_ln < 0 || pre_ln > 1 || gemm_rule < 0 || gemm_rule > 1 ||
+        key_bias < 0 || key_bias > 1 || n_layers < 1 || n_layers > 2 || n_items < 1 || n_items > 65535)
+        return PCE_E_INVALID;
+    if (!pre_ln && !ln_in) return pce_fail(c, PCE_E_INVALID, "selftest encoder walk: a post-LN stack needs ln_in, the 16-bit image its opening LayerNorm leaves");
+    // what the three loaders refuse
+    if (d <= 0 || d % 128 || heads * 64 != d) return pce_fail(c, PCE_E_LIMIT, "selftest encoder walk: d %d with %d heads (need d %% 128 == 0, head size 64)", d, heads);
+    if (d > LN_D_MAX) return pce_fail(c, PCE_E_LIMIT, "selftest encoder walk: d %d: the LayerNorm kernels hold at most %d", d, LN_D_MAX);
+    if (inner <= 0 || inner % 128) return pce_fail(c, PCE_E_LIMIT, "selftest encoder walk: inner %d is no multiple of 128 (the GEMM's column tile)", inner);
+    // an item's slot: the QKV epilogue stores four rows at a time, the attention reads V^T in 64-key tiles
+    if (rows_per_item < 4 || rows_per_item % 4 || vt_sp % 64 || rows_per_item > vt_sp || vt_sp > (1 << 20))
+        return pce_fail(c, PCE_E_INVALID, "selftest encoder walk: %d rows per item in %d V^T columns (need rows %% 4 == 0, columns %% 64 == 0, rows <= columns)",
+                        rows_per_item, vt_sp);
+    for (int i = 0; i < n_items; i++)
+        if (len[i] < 1 || len[i] > rows_per_item) return pce_fail(c, PCE_E_INVALID, "selftest encoder walk: item %d has %d rows of %d", i, len[i], rows_per_item);
+    const int64_t M = (int64_t)n_items * rows_per_item, L = n_layers, I = inner;
+    const int64_t Md = M * d, MI = M * I, nvt = (int64_t)n_items * d * vt_sp;
+    if (M * std::max<int64_t>(2 * d, I) >= ((int64_t)1 << 30) || nvt >= ((int64_t)1 << 30))
+        return pce_fail(c, PCE_E_LIMIT, "selftest encoder walk: %lld rows are more than the self-test holds", (long long)M);
+    const int64_t per_layer = 4LL * d * d + (key_bias ? 4LL : 3LL) * d + 2LL * d + (I * d + I) + (d * I + d) + 2LL * d;
+    if (n_floats != L * per_layer)
+        return pce_fail(c, PCE_E_INVALID, "selftest encoder walk: weight blob has %lld floats, expected %lld", (long long)n_floats, (long long)(L * per_layer));
+    if (stream_elems < Md || ln16_elems < L * 3 * Md || qk_elems < L * 2 * Md || vt_elems < L * nvt || attn_elems < L * Md || hidden_elems < L * MI || x32_elems < L * 4 * Md)
+        return pce_fail(c, PCE_E_INVALID, "selftest encoder walk: needs stream %lld, ln16 %lld, qk %lld, vt %lld, attn %lld, hidden %lld, x32 %lld elements", (long long)Md,
+                        (long long)(L * 3 * Md), (long long)(L * 2 * Md), (long long)(L * nvt), (long long)(L * Md), (long long)(L * MI), (long long)(L * 4 * Md));
+    PCE_HIP(c, hipSetDevice(c->device));
+    PCE_TRY(lds_optins(c, ws_of(c)));
+    // the loader's half: openai-whisper's tensor order for the Whisper encoder (the pre-LN stack on the product's rule), transformers' for BERT and wav2vec2
+    const bool pre = pre_ln != 0, whisper = pre && gemm_rule == 0;
+    WeightPack pk;
+    std::vector<EncoderLayerW> layers((size_t)L);
+    const float *p = weights;
+    for (EncoderLayerW &ly : layers) ly = pack_encoder_layer(pk, p, (size_t)d, (size_t)I, whisper, key_bias != 0);
+    DevBuf tmp, w16, w32;
+    PCE_TRY(upload_weights(c, pk, tmp, w16, w32));
+    // the run's buffers, each holding what the caller's array of its first layer holds (a post-LN stack's r.ln: the caller's opening LayerNorm), and V^T zeroed once
+    std::vector<int> tab((size_t)2 * n_items);
+    for (int i = 0; i < n_items; i++) { tab[(size_t)i] = i * rows_per_item; tab[(size_t)n_items + i] = len[i]; }
+    DevBuf dtab, dres, dln, dqk, dvt, dattn, dhid, cln, cqk, cvt, cattn, chid, cx;
+    PCE_UPLOAD(c, dtab, tab);
+    PCE_UPLOAD(c, dres, stream, (size_t)Md);
+    PCE_UPLOAD(c, dln, pre ? ln16 : ln_in, (size_t)Md, 2048);
+    PCE_UPLOAD(c, dqk, qk, (size_t)(2 * Md), 2048);
+    PCE_UPLOAD(c, dattn, attn, (size_t)Md, 2048);
+    PCE_UPLOAD(c, dhid, hidden, (size_t)MI, 2048);
+    PCE_ZERO(op_t, c, dvt, (size_t)nvt + 64);
+    // the captures: the caller's arrays, which keep their values where no launch writes
+    PCE_UPLOAD(c, cln, ln16, (size_t)(L * 3 * Md)); PCE_UPLOAD(c, cqk, qk, (size_t)(L * 2 * Md)); PCE_UPLOAD(c, cvt, vt, (size_t)(L * nvt));
+    PCE_UPLOAD(c, cattn, attn, (size_t)(L * Md)); PCE_UPLOAD(c, chid, hidden, (size_t)(L * MI)); PCE_UPLOAD(c, cx, x32, (size_t)(L * 4 * Md));
+    const int *row0 = dtab.as<int>(), *lens = row0 + n_items;
+    const double attn_flops = whisper ? 4.0 * rows_per_item * (double)rows_per_item * d * n_items : 0.0;
+    const EncoderRun r{(int)M, d, heads, (int)I, n_items, rows_per_item, vt_sp, row0, lens, eps, attn_flops, whisper, dres.as<float>(), dln.as<op_t>(), dqk.as<op_t>(),
+                       dvt.as<op_t>(), dattn.as<op_t>(), dhid.as<op_t>(), w16.as<op_t>(), w32.as<float>()};
+    hipError_t copied = hipSuccess;
+    const WalkCapture probe{c, &r, pre, cln.as<op_t>(), cqk.as<op_t>(), cvt.as<op_t>(), cattn.as<op_t>(), chid.as<op_t>(), cx.as<float>(), (size_t)Md, (size_t)MI,
+                            (size_t)nvt, &copied};
+    const bool fit = gemm_rule ? selftest_walk_w2v(c, r, layers, pre, probe) : encoder_walk<ProductGemm>(c, r, layers, pre, probe);
+    PCE_HIP(c, hipGetLastError());
+    PCE_HIP(c, copied);
+    PCE_FETCH(c, ln16, cln.p, (size_t)(L * 3 * Md)); PCE_FETCH(c, qk, cqk.p, (size_t)(L * 2 * Md)); PCE_FETCH(c, vt, cvt.p, (size_t)(L * nvt));
+    PCE_FETCH(c, attn, cattn.p, (size_t)(L * Md)); PCE_FETCH(c, hidden, chid.p, (size_t)(L * MI)); PCE_FETCH(c, x32, cx.p, (size_t)(L * 4 * Md));
+    PCE_HIP(c, hipStreamSynchronize(c->stream));
+    pce_profile_collect(c);
+    if (fit_out) *fit_out = fit ? 1 : 0;
+    return PCE_OK;
 }
 
 } // namespace PCE_BUILD_NS

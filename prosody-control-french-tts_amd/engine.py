@@ -301,6 +301,7 @@ SIGNATURES = {
     "pce_selftest_xattn_stages": [_vp] * 10 + [_i64, _vp, _vp] + [_i32] * 5 + [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "pce_selftest_gemm_tiled": [_vp, _i32, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
     "pce_selftest_layernorm": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, C.c_float, _i32, _vp, _vp, _vp],
+    "pce_selftest_encoder_walk": [_vp] + [_i32] * 10 + [_vp, C.c_float, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "pce_whisper_encode_fetch": [_vp, _i32, _vp],
     # R8: forced alignment of known text tokens
     "pce_whisper_decoder_load": [_vp, C.POINTER(WhisperTextDims), _vp, _i64],
@@ -1042,6 +1043,30 @@ class ProsodyEngine:
         self._check(self._lib.pce_selftest_layernorm(self._ctx, int(form), rows, d, x.ctypes.data, ptr(delta), ptr(delta2), w.ctypes.data, b.ctypes.data,
                                                      float(eps), int(flags), out.ctypes.data, ptr(resid), ptr(cp)))
         return out, resid, cp
+
+    def selftest_encoder_walk(self, pre_ln: bool, gemm_rule: int, key_bias: bool, heads: int, inner: int, n_layers: int, rows_per_item: int, vt_sp: int,
+                              lens, eps: float, weights, stream, stages: dict, ln_in=None, d: int = None) -> bool:
+        """``pce_selftest_encoder_walk``: the shared encoder layer walk on host arrays.  stream [M][d] float32 (M = len(lens) x rows_per_item), weights
+        the layers' fp32 blob in the form's tensor order, ln_in [M][d] uint16 (post-LN).  ``stages``: the capture arrays of include/pce.h by name -- ln16
+        [L][3][M][d], qk [L][M][2 d], vt [L][items][d][vt_sp], attn [L][M][d], hidden [L][M][inner] (uint16) and x32 [L][4][M][d] (float32) -- read and
+        updated in place: what no launch writes keeps its values.  Returns whether every product was launched."""
+        def arr(x, dt):
+            assert isinstance(x, np.ndarray) and x.dtype == dt and x.flags["C_CONTIGUOUS"], (None if x is None else x.dtype, dt)
+            return x
+        stream, w = arr(stream, np.float32), arr(weights, np.float32)
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        d = stream.shape[-1] if d is None else d
+        if ln_in is not None:
+            assert arr(ln_in, np.uint16).size >= stream.size
+        s = {k: arr(stages[k], np.float32 if k == "x32" else np.uint16) for k in ("ln16", "qk", "vt", "attn", "hidden", "x32")}
+        fit = C.c_int32(-1)
+        self._check(self._lib.pce_selftest_encoder_walk(self._ctx, int(bool(pre_ln)), int(gemm_rule), int(bool(key_bias)), int(d), int(heads), int(inner), int(n_layers),
+                                                        int(lens.size), int(rows_per_item), int(vt_sp), lens.ctypes.data, float(eps), w.ctypes.data, w.size,
+                                                        stream.ctypes.data, stream.size, None if ln_in is None else ln_in.ctypes.data, s["ln16"].ctypes.data,
+                                                        s["ln16"].size, s["qk"].ctypes.data, s["qk"].size, s["vt"].ctypes.data, s["vt"].size, s["attn"].ctypes.data,
+                                                        s["attn"].size, s["hidden"].ctypes.data, s["hidden"].size, s["x32"].ctypes.data, s["x32"].size,
+                                                        C.addressof(fit)))
+        return bool(fit.value)
 
     def whisper_encode_fetch(self, clip: int) -> np.ndarray:
         out = np.zeros((1500, self._wdims.n_state), dtype=np.float32)

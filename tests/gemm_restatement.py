@@ -60,6 +60,66 @@ def _gelu_err(pre, pre_err):
     return 1.13 * pre_err + (0.75e-7 + 16 * U) * np.abs(pre)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the per-element bounds of the tiled kernels' checks (tests/test_gpu_kernels.py, tests/encoder_walk_restatement.py): derived in the docstring of
+# tests/test_gpu_kernels.py
+# ---------------------------------------------------------------------------------------------------------------
+def bound16(want, err, ops):
+    """what a 16-bit output may differ by from a float64 value known to within err: one rounding of the output on top"""
+    return err + _half_ulp(ops) * (np.abs(want) + err) + 2.0 ** -24
+
+
+def bound32(want, err):
+    return err + 2 * U * np.abs(want)
+
+
+def _check16(got_bits, want, err, ops, what):
+    """16-bit output against a float64 value known to within err: one rounding of the output on top"""
+    got = val(got_bits, ops)
+    bound = bound16(want, err, ops)
+    bad = np.abs(got - want) > bound
+    assert not bad.any(), (what, int(bad.sum()), float(np.max(np.abs(got - want) - bound)))
+
+
+def _check32(got, want, err, what):
+    bound = bound32(want, err)
+    bad = np.abs(got.astype(np.float64) - want) > bound
+    assert not bad.any(), (what, int(bad.sum()), float(np.max(np.abs(got - want) - bound)))
+
+
+def gemm_acc(A, B):
+    """float64 A B^T of rounded operands (A [m][K], B [N][K]) -> (product, sum |a b|, what fp32 accumulation over K may add: K 2^-24 sum |a b|)"""
+    acc, mag = A @ B.T, np.abs(A) @ np.abs(B).T
+    return acc, mag, A.shape[1] * U * mag
+
+
+def gemm_pre(acc, acc_err, bias):
+    """the epilogue's input acc + bias and its error (one fp32 addition on top of the accumulation)"""
+    pre = acc + np.asarray(bias, dtype=np.float64)
+    return pre, acc_err + U * np.abs(pre)
+
+
+def resid_err(old, acc, err):
+    """the fp32 accumulate epilogue old + pre: two more fp32 additions"""
+    return err + U * (np.abs(old) + np.abs(acc))
+
+
+def _ln_ref(v, w, b, eps):
+    """float64 LayerNorm of the values the kernel normalised, and the error its fp32 arithmetic allows (per element)"""
+    v = v.astype(np.float64)
+    d = v.shape[1]
+    terms = 4 * -(-d // 256) + 6                                  # sequential adds in a lane + the wave tree
+    m = v.mean(axis=1, keepdims=True)
+    xc = v - m
+    q = (xc ** 2).sum(axis=1, keepdims=True)
+    inv = 1.0 / np.sqrt(q / d + eps)
+    y = xc * inv * w + b
+    dm = terms * U * np.abs(v).sum(axis=1, keepdims=True) / d + U * np.abs(m)
+    rel_inv = 0.5 * ((terms + 3) * U + d * dm ** 2 / (q + d * eps)) + 3 * U
+    err = np.abs(w) * inv * (np.abs(xc) * (rel_inv + 3 * U) + dm) + 2 * U * (np.abs(y) + np.abs(b))
+    return y, err
+
+
 def gelu64(x):
     """_gelu in float64 on all threads (torch's erf; the big cases of the persistent kernel)"""
     t = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))

@@ -38,6 +38,7 @@ def test_build_and_exports_match_header():
     assert {"pce_pyin_fetch_observations", "pce_selftest_pyin_viterbi"} <= declared and lib.pce_api_minor() >= 22      # minor 22
     assert {"pce_pitch_fetch_candidates", "pce_selftest_pitch_path"} <= declared and lib.pce_api_minor() >= 23           # minor 23
     assert {"pce_lufs_fetch_stages", "pce_lufs_stage_sizes"} <= declared and lib.pce_api_minor() >= 25                  # minor 25
+    assert "pce_selftest_encoder_walk" in declared and lib.pce_api_minor() >= 26        # minor 26
     assert ctypes.sizeof(ctypes.c_double) * 11 == E.LUFS_CHUNK_DTYPE.itemsize and E.LUFS_SLICE_DTYPE.itemsize == 24 and E.LUFS_BLOCK_DTYPE.itemsize == 16
     lib.pce_kernel_name.restype = ctypes.c_char_p
     assert [lib.pce_kernel_name(i).decode() for i in range(len(E.KERNEL_IDS))] == E.KERNEL_IDS

@@ -46,6 +46,40 @@ def test_base_architecture_matches_torch_restatement(engine):
         _check(g, w)
 
 
+_LONG = {}
+
+
+def _long_problem():
+    """A 2-layer model of mBERT's width and sequences up to the 512 positions pce_bert_run accepts (break_bert.predict_breaks passes
+    max_length = n_pos): at 512 tokens T_pad equals the V^T image's 512 key columns, which leaves no slack column.  Computed once for the operand modes."""
+    if not _LONG:
+        dims = dict(BW.DIMS["mbert-base-uncased"], n_layer=2, n_vocab=2000)
+        W = BW.synthetic_weights(dims, seed=17)
+        rng = np.random.default_rng(9)
+        toks = [rng.integers(0, dims["n_vocab"], size=n).tolist() for n in (129, 300, 511, 512, 37)]
+        _LONG.update(dims=dims, W=W, toks=toks, blob=BW.pack(W, dims), want=BO.forward(toks, W, dims))
+    return _LONG
+
+
+def test_sequences_past_128_tokens_match_torch_restatement(engine, ops):
+    p = _long_problem()
+    assert p["dims"]["n_pos"] == 512
+    engine.bert_load(p["dims"], p["blob"])
+    res = engine.bert_token_classify(p["toks"][:4])
+    for g, w in zip(res, p["want"]):
+        _check(g, w)
+
+
+def test_a_short_sequence_alone_gives_the_bytes_it_has_beside_512_tokens(engine, ops):
+    """37 tokens alone (T_pad = 48, one query block) and inside a batch whose longest sequence has 512 (T_pad = 512, four query blocks)"""
+    p = _long_problem()
+    engine.bert_load(p["dims"], p["blob"])
+    batch = engine.bert_token_classify(p["toks"])
+    alone = engine.bert_token_classify([p["toks"][4]])[0]
+    _check(alone, p["want"][4])
+    assert alone[0].tobytes() == batch[4][0].tobytes() and np.array_equal(alone[1], batch[4][1])
+
+
 def test_bert_argument_errors():
     with ProsodyEngine(0) as eng:
         with pytest.raises(PceError):

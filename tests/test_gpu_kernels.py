@@ -16,27 +16,14 @@ import torch
 from oracle import bert_oracle as BO
 from oracle import whisper_oracle as WO
 from prosody_control_french_tts_amd import PceError, bert_weights as BW, synth, whisper_weights as WW
-from tests.gemm_restatement import U, _dt, _gelu, _gelu_err, _half_ulp, bits, r16, val
+from tests.gemm_restatement import (U, _check16, _check32, _dt, _gelu, _gelu_err, _half_ulp, _ln_ref, bits, gemm_acc, gemm_pre, r16, resid_err,  # noqa: F401
+                                    val)
 
 pytestmark = pytest.mark.gpu
 
 EPI_BF16, EPI_GELU, EPI_GELU_POS, EPI_RESID, EPI_QKV, EPI_F32 = range(6)
 AUTO, SKINNY, WIDE, T128, T128_DEEP = range(5)
 torch.set_num_threads(min(16, torch.get_num_threads()))
-
-
-def _check16(got_bits, want, err, ops, what):
-    """16-bit output against a float64 value known to within err: one rounding of the output on top"""
-    got = val(got_bits, ops)
-    bound = err + _half_ulp(ops) * (np.abs(want) + err) + 2.0 ** -24
-    bad = np.abs(got - want) > bound
-    assert not bad.any(), (what, int(bad.sum()), float(np.max(np.abs(got - want) - bound)))
-
-
-def _check32(got, want, err, what):
-    bound = err + 2 * U * np.abs(want)
-    bad = np.abs(got.astype(np.float64) - want) > bound
-    assert not bad.any(), (what, int(bad.sum()), float(np.max(np.abs(got - want) - bound)))
 
 
 class Prob:
@@ -54,9 +41,7 @@ class Prob:
                                                                 rng.integers(0, M, 48)].clip(0, M - 1))
         self.rows = rows
         A, B = val(self.a, ops)[rows], val(self.b, ops)
-        self.acc = A @ B.T
-        self.mag = np.abs(A) @ np.abs(B).T                       # sum |a b|
-        self.acc_err = K * U * self.mag
+        self.acc, self.mag, self.acc_err = gemm_acc(A, B)          # (mag: sum |a b|)
 
     def run(self, eng, epi, kernel, C=None, **kw):
         f32 = epi in (EPI_GELU_POS, EPI_RESID, EPI_F32)
@@ -67,8 +52,7 @@ class Prob:
         return C.reshape(self.M, -1), used
 
     def check(self, epi, C, what, old=None):
-        pre = self.acc + self.bias.astype(np.float64)
-        err = self.acc_err + U * np.abs(pre)
+        pre, err = gemm_pre(self.acc, self.acc_err, self.bias)
         got = C[self.rows]
         if epi == EPI_BF16 or epi == EPI_QKV:
             _check16(got, pre, err, self.ops, what)
@@ -76,7 +60,7 @@ class Prob:
             _check16(got, _gelu(pre), _gelu_err(pre, err), self.ops, what)
         elif epi == EPI_RESID:
             o = old[self.rows].astype(np.float64)
-            _check32(got, o + pre, err + U * (np.abs(o) + np.abs(self.acc)), what)
+            _check32(got, o + pre, resid_err(o, self.acc, err), what)
         else:
             _check32(got, pre, err, what)
 
@@ -264,22 +248,6 @@ def _ln_rows(d, n_random, rng, spread=1.0):
     x = rng.standard_normal((n_random, d)) * spread
     edge = np.stack([np.full(d, 0.75), 1000.0 + rng.standard_normal(d), 3.0 + 1e-3 * rng.standard_normal(d)])
     return np.concatenate([x, edge]).astype(np.float32)
-
-
-def _ln_ref(v, w, b, eps):
-    """float64 LayerNorm of the values the kernel normalised, and the error its fp32 arithmetic allows (per element)"""
-    v = v.astype(np.float64)
-    d = v.shape[1]
-    terms = 4 * -(-d // 256) + 6                                  # sequential adds in a lane + the wave tree
-    m = v.mean(axis=1, keepdims=True)
-    xc = v - m
-    q = (xc ** 2).sum(axis=1, keepdims=True)
-    inv = 1.0 / np.sqrt(q / d + eps)
-    y = xc * inv * w + b
-    dm = terms * U * np.abs(v).sum(axis=1, keepdims=True) / d + U * np.abs(m)
-    rel_inv = 0.5 * ((terms + 3) * U + d * dm ** 2 / (q + d * eps)) + 3 * U
-    err = np.abs(w) * inv * (np.abs(xc) * (rel_inv + 3 * U) + dm) + 2 * U * (np.abs(y) + np.abs(b))
-    return y, err
 
 
 @pytest.mark.parametrize("d", LN_WIDTHS)
